@@ -70,7 +70,35 @@ def parse_args():
     ap.add_argument("--share-gpu", action="store_true",
                     help="ranks share the visible GPUs (rank r -> device r mod count) and talk over gloo: lets "
                          "the N > 1 path run on a box with fewer GPUs than ranks (not a scaling measurement)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the compressed stream) to DIR/*.npy")
     return ap.parse_args()
+
+
+DUMP_EDGE = 1 << 20      # bytes of the stream's head and of its tail dumped whole
+DUMP_SAMPLE = 4 << 20    # further bytes of the stream at seeded positions
+DUMP_SEED = 20240917
+
+
+def dump_outputs(path, stream):
+    """The stream of the last timed step as .npy files that two builds can compare element for element (a compressed
+    stream is no float, its bytes are stored as float32; 56 MB at most): its length, its first and last DUMP_EDGE bytes
+    (the tail holds the combined CRC of all blocks), and when it is longer than those two, DUMP_SAMPLE bytes at sorted
+    positions drawn by a fixed seed from the rest, with the positions."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    z = np.frombuffer(stream, dtype=np.uint8)
+    arrays = {"stream_length": np.array([z.size], dtype=np.float64),
+              "stream_head": z[:DUMP_EDGE].astype(np.float32),
+              "stream_tail": z[max(DUMP_EDGE, z.size - DUMP_EDGE):].astype(np.float32)}
+    middle = z.size - 2 * DUMP_EDGE
+    if middle > 0:
+        rng = np.random.default_rng(DUMP_SEED)
+        pos = DUMP_EDGE + (np.sort(rng.choice(middle, DUMP_SAMPLE, replace=False)) if middle > DUMP_SAMPLE else np.arange(middle))
+        arrays["stream_sample_positions"] = pos.astype(np.float64)
+        arrays["stream_sample"] = z[pos].astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def self_launch(args):
@@ -423,6 +451,8 @@ def main():
         pmc = load_json("profiles", "pmc_traffic.json")
         out_len = state["out_len"]
         out = bytes(d_out[:out_len].cpu().numpy())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out)
         sha = hashlib.sha256(out).hexdigest()
         # size-independent checks outside the timed region: the stream decodes, and its head is the corpus
         try:

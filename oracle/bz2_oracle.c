@@ -2,7 +2,7 @@
  * TEST INFRASTRUCTURE -- CPU oracle for the BZip2 block-encode hot path.
  *
  * This file is a plain-C restatement of the reference's algorithm
- * (chalharu/rust-compression 0.1.5, /root/reference).  It exists so that the
+ * (chalharu/rust-compression 0.1.5).  It exists so that the
  * HIP product path can be checked bit-for-bit on a CPU.  Only tests/,
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg may load it; the
  * product library (rust-compression_amd/csrc) never links or calls it.

@@ -2,7 +2,7 @@
  * TEST INFRASTRUCTURE -- CPU oracle for the Deflate encode path.
  *
  * Plain-C restatement of the reference's algorithm (chalharu/rust-compression 0.1.5,
- * /root/reference/src): LzssEncoder + SlideDict (lzss/encoder.rs, lzss/slidedict.rs), Inflater /
+ * src/): LzssEncoder + SlideDict (lzss/encoder.rs, lzss/slidedict.rs), Inflater /
  * InflaterInner (deflate/encoder.rs, deflate/mod.rs), the LSB-first bit writer
  * (bitio/writer.rs, bitio/direction/right.rs), and the zlib / gzip containers
  * (zlib/encoder.rs, gzip/encoder.rs, adler32.rs, crc32.rs).  The Huffman length builder is

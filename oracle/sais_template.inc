@@ -1,9 +1,9 @@
 /* TEST INFRASTRUCTURE -- CPU oracle, not product code.
  *
  * Cyclic SA-IS ("BWT without sentinel"), restated from the reference:
- *   /root/reference/src/suffix_array/sais.rs:70-264   (fill, induce_sa, sa_is)
- *   /root/reference/src/suffix_array/ls_type.rs:10-92 (LSTypeArray::with_shift)
- *   /root/reference/src/suffix_array/bucket.rs:18-85  (BucketBuilder / Bucket)
+ *   src/suffix_array/sais.rs:70-264   (fill, induce_sa, sa_is)
+ *   src/suffix_array/ls_type.rs:10-92 (LSTypeArray::with_shift)
+ *   src/suffix_array/bucket.rs:18-85  (BucketBuilder / Bucket)
  *
  * This file is a poor man's generic: it is included twice by bz2_oracle.c, once
  * with SA_T = uint8_t (the block bytes) and once with SA_T = size_t (the names

@@ -2,8 +2,8 @@
 """Writes tests/golden/deflate_vectors.json: the known-answer vectors the reference's own tests hold
 for the LZSS / Deflate / zlib / gzip encode path, as data (inputs + expected outputs).
 
-Run in the build container (reads /root/reference/src to pull the long numeric tables out of the
-tests so they are not transcribed by hand); the JSON it writes is what travels.
+Usage: make_deflate_vectors.py <src directory of chalharu/rust-compression 0.1.5> (it pulls the long numeric
+tables out of the tests so they are not transcribed by hand); the JSON it writes is what travels.
   lzss/encoder.rs:246-598      token vectors (the tests' comparison, window 0x10000, max 256)
   deflate/encoder.rs:660-1027  byte vectors / (value, bits) lists packed LSB first
   deflate/encoder.rs:1029-1210 (length, distance) -> (code, extra, extra bits) vectors
@@ -12,8 +12,9 @@ tests so they are not transcribed by hand); the JSON it writes is what travels.
 import json
 import os
 import re
+import sys
 
-REF = "/root/reference/src"
+REF = sys.argv[1] if len(sys.argv) > 1 else "src"
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 

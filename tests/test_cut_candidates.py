@@ -1,5 +1,5 @@
 """The block cuts without a serial chain (csrc/k_rle1.hip "kernels H"), restated in numpy and checked against the serial
-rule of the reference (/root/reference/src/bzip2/encoder.rs:671-697: a block is closed by the first chunk that brings it
+rule of the reference (the reference's src/bzip2/encoder.rs:671-697: a block is closed by the first chunk that brings it
 to 100000 * level - 19 bytes or more; a chunk is at most 255 equal bytes and leaves at most 5 bytes in the block).
 
 What the kernels rely on:

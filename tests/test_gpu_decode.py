@@ -484,7 +484,7 @@ def test_selector_codes_with_too_many_ones(pkg, oracle):
     the code string are found 8192 bits per trip, a code with n_groups one bits is noted with the smallest selector number.
     Streams whose selector region has such a code -- the first selector, one in the middle, the last one, a run of ones
     that reaches far behind the region -- and clean ones whose region crosses several trips: the oracle's bytes and verdict
-    (/root/reference/src/bzip2/decoder.rs:294-316)."""
+    (the reference's src/bzip2/decoder.rs:294-316)."""
     d = sample(1)[:98000] * 9 + bytes(range(256)) * 40
     for level in (1, 9):
         z = bytearray(bz2.compress(d, level))

@@ -2,7 +2,7 @@
 df_encode_buffer, df_enc_* park ONE engine per device; bz_release_cached_resources frees it).  An engine made by one
 kind of call serves the next call of ANOTHER kind -- decode, Deflate, streaming contexts, in any order --, results
 are the oracle's every time, and the calling thread's current device is left as it was.
-(/root/reference/src/bzip2/decoder.rs:583-612 and src/deflate/encoder.rs are what the calls stand for; the cache is the
+(the reference's src/bzip2/decoder.rs:583-612 and src/deflate/encoder.rs are what the calls stand for; the cache is the
 library's own.)"""
 import pytest
 
@@ -93,7 +93,7 @@ def test_streaming_decoder_reads_behind_the_end_wait_for_the_worker(pkg, oracle)
     """Round 5: bz_dec_end returns at once and bz_dec_read waits behind it.  A stream large enough for the worker thread
     (chunks of 4 MiB and more are decoded beside the caller): written in one piece, ended, then read in small pieces until
     the verdict -- every byte, then 0; a corrupted copy: the bytes in front of the error, then the error
-    (/root/reference/src/bzip2/decoder.rs:583-612: the iterator yields exactly that sequence)."""
+    (the reference's src/bzip2/decoder.rs:583-612: the iterator yields exactly that sequence)."""
     import bz2
     import ctypes as C
     data = _text(30_000_000, 11)
@@ -153,7 +153,7 @@ def test_streaming_decoder_two_lanes(pkg, oracle, monkeypatch):
     out a byte.  Several chunks per stream here (BZ_DEC_CHUNK = 4 MiB): a clean stream, two streams in one file with the
     seam inside a chunk, a block corrupted in the second chunk (the third is in flight on the other lane by then), a
     stream cut off in mid-block, a context destroyed with chunks still in flight: the bytes and the verdict of the oracle's
-    decoder every time (/root/reference/src/bzip2/decoder.rs:583-612: bytes in front of an error, then the error)."""
+    decoder every time (the reference's src/bzip2/decoder.rs:583-612: bytes in front of an error, then the error)."""
     import ctypes as C
     monkeypatch.setenv("BZ_DEC_CHUNK", str(4 << 20))
     monkeypatch.setenv("BZ_DEC_FIRST_CHUNK", str(4 << 20))

@@ -612,7 +612,7 @@ def test_period_round_on_drifting_copies(pkg, oracle, eng):
     over half of its length (a tar of similar files; bench.py's corpus "binary").  The period round lists up to eight
     distances per block (k_period_find), keys every survivor by a pair it belongs to at one of them and checks every pair
     of neighbours of the sorted list against the first difference behind it (k_period_mark) -- the comparison that
-    /root/reference/src/suffix_array/sais.rs:266-272 defines, so the ORDER is the oracle's: rotation order of whole
+    the reference's src/suffix_array/sais.rs:266-272 defines, so the ORDER is the oracle's: rotation order of whole
     blocks, the rounds it took, and whole streams."""
     rng = random.Random(505)
     alpha = b"etaoinshrdlu ,.\n"
@@ -667,7 +667,7 @@ def test_link_rounds_on_copies_of_copies(pkg, oracle, eng):
     k_link_permute), in the period round and in link rounds behind it.  The shape it was built for: a stretch that occurs
     four times in a block -- it repeats inside itself and the whole occurs twice --, every copy with a byte changed every few
     KiB (bench.py's corpus "binary"): groups of four whose members stand in mixed order, a changed byte in a middle copy
-    between two that agree beyond it.  The comparison is what /root/reference/src/suffix_array/sais.rs:266-272 defines, so
+    between two that agree beyond it.  The comparison is what the reference's src/suffix_array/sais.rs:266-272 defines, so
     the ORDER is the oracle's: rotation order of whole blocks, the rounds it took, whole streams, and the same streams with
     the link rounds off."""
     rng = random.Random(606)

@@ -1,5 +1,5 @@
 """The encoder's self-check (bz_enc_set_verify / bz_gpu_engine_set_verify / BZ_VERIFY=1) and the structural checks in
-front of it.  The reference's sequential encoder (/root/reference/src/bzip2/encoder.rs:224-291) cannot write a stream
+front of it.  The reference's sequential encoder (the reference's src/bzip2/encoder.rs:224-291) cannot write a stream
 that does not decode to its input; the GPU pipeline has look-back words, ticket counters and stream-ordered clears, and
 round 3 saw one wrong stream in six from a clear issued on the wrong stream.  Here faults are INJECTED (switches the
 library reads from the environment, so every case runs in a process of its own):

@@ -2,7 +2,7 @@
 # PMC pass over bench.py (run on the GPU box): tools/bz_pmc.sh <mib> "<counters>" <tag>
 set -u
 MIB=${1:-256}; CTRS=${2:-"SQ_INSTS_VALU SQ_INSTS_SALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES"}; TAG=${3:-bzpmc}
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -1,5 +1,5 @@
 import sys, importlib, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 pkg = importlib.import_module("rust-compression_amd")
 from oracle import oracle
 d = open(sys.argv[1], "rb").read()

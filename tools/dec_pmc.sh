@@ -2,7 +2,7 @@
 # PMC pass over one decode (run on the GPU box): tools/dec_pmc.sh <tag> <walk wgs> "<counters>"
 set -u
 TAG=$1; WGS=$2; CTRS=${3:-"TCC_HIT_sum TCC_MISS_sum"}
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/decpmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -2,7 +2,7 @@
 # PMC passes over the Deflate bench (run on the GPU box): tools/df_prof.sh <mib> "<counters>" <tag>
 set -u
 MIB=${1:-64}; CTRS=${2:-"SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_INSTS_VALU"}; TAG=${3:-dfpmc}
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

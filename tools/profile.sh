@@ -3,7 +3,7 @@
 # Usage: [BENCH=bench_decode.py] tools/profile.sh <tag> [bench args...]
 set -u
 TAG=${1:-r01}; shift || true
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 BENCH=${BENCH:-bench.py}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT

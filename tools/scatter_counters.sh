@@ -5,7 +5,7 @@
 # preloaded library initialises the GPU before the program starts), --kernel-trace only.  Output: gpurun_out/<tag>/summary.md
 set -u
 MIB=${1:-256}; TAG=${2:-r04_scatter}
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
