@@ -14,11 +14,14 @@ transport callbacks), which assembles the serial stream.
 touches a GPU); under `python -m torch.distributed.run ... bench.py --gpus N` the ranks already exist
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment).  Rank 0 prints ONE JSON line.
 
-Besides the headline (value, roofline, cpu_baseline, per-step median / min) the line carries, outside the timed
-region: end_to_end (host buffer -> host buffer through the C ABI; at N > 1 ONE process drives all N GPUs through
-bz_encode_buffer_multi -- the drop-in surface's own multi-GPU path, BASELINE.json's "end-to-end" figure),
-extra.decode (configs[3]; at N > 1 all ranks together) and, at N = 1, extra.deflate (configs[4]), the stress
-corpus T2 and the all-cores CPU baseline; at N > 1 a second short leg over the library's own RCCL transport.
+A plain run does only what the headline needs: it sets up (at N > 1 with the preflight of the transport), warms up,
+times the steps, writes --dump-outputs and prints the line: value, ms_per_step, per-step median / min and the roofline
+of the kernel profile the timed steps took.  --full adds, outside the timed region: the checks of the stream (it
+decodes, it equals the oracle's golden), cpu_baseline, end_to_end (host buffer -> host buffer through the C ABI; at
+N > 1 ONE process drives all N GPUs through bz_encode_buffer_multi -- the drop-in surface's own multi-GPU path,
+BASELINE.json's "end-to-end" figure), extra.decode (configs[3]; at N > 1 all ranks together) and, at N = 1,
+extra.deflate (configs[4]), the stress corpus T2 and the all-cores CPU baseline; at N > 1 a second short leg over
+the library's own RCCL transport.
 
 No rank waits for ever: a watchdog thread ends the process with a non-zero status when the run makes no
 progress for --hang-timeout seconds (a peer died inside a collective), process groups are created with that
@@ -51,9 +54,12 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--mib-per-gpu", type=int, default=1024, help="corpus MiB per GPU (default: the 1 GiB config)")
     ap.add_argument("--level", type=int, default=9)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the checks of the stream, the CPU baselines and the legs behind the "
+                         "headline (decode, Deflate, end to end, T2, corpus matrix, ...); a plain run does none of them")
     ap.add_argument("--cpu-sample-mib", type=int, default=64)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (profiling runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: the checks and the CPU baseline only, no legs")
     ap.add_argument("--corpus", default="text", choices=["text", "t2"])
     ap.add_argument("--force-sharded", action="store_true", help="run bz_gpu_encode_sharded even with one rank")
     ap.add_argument("--transport", default="torch", choices=["torch", "rccl"],
@@ -63,7 +69,7 @@ def parse_args():
     ap.add_argument("--hang-timeout", type=float, default=900.0,
                     help="seconds without progress after which a rank gives up with exit status 5")
     ap.add_argument("--extras-timeout", type=float, default=600.0,
-                    help="N > 1: seconds the legs behind the headline may take before rank 0 prints the headline without them")
+                    help="N > 1, --full: seconds the legs behind the headline may take before rank 0 prints the headline without them")
     ap.add_argument("--preflight-timeout", type=float, default=240.0,
                     help="N > 1: seconds the checks in front of the timed steps may take (transport self-test over the real "
                          "communicator, peer copies between the devices) before rank 0 prints a line that says where they stood")
@@ -447,26 +453,11 @@ def main():
 
     result = None
     if rank == 0:
-        golden = load_json("tests", "golden", "corpus_hashes.json")
         pmc = load_json("profiles", "pmc_traffic.json")
         out_len = state["out_len"]
-        out = bytes(d_out[:out_len].cpu().numpy())
+        out = bytes(d_out[:out_len].cpu().numpy()) if (args.full or args.dump_outputs) else None
         if args.dump_outputs:
             dump_outputs(args.dump_outputs, out)
-        sha = hashlib.sha256(out).hexdigest()
-        # size-independent checks outside the timed region: the stream decodes, and its head is the corpus
-        try:
-            head = bz2.BZ2Decompressor().decompress(out[:min(len(out), 48 << 20)], 32 << 20)
-            ok_head = len(head) > 0 and head == bytes(d_in[:len(head)].cpu().numpy())
-        except (OSError, ValueError, EOFError):
-            ok_head = False
-        checks = {"head_decodes_to_input": bool(ok_head)}
-        gkey = None
-        if args.level == 9 and n % (1 << 20) == 0:
-            size = "%dgib" % (n >> 30) if n % (1 << 30) == 0 else "%dmib" % (n >> 20)
-            gkey = "bzip2_l9_%s_%s" % (args.corpus, size)
-        if gkey in golden:  # the oracle's stream for this exact corpus (tests/golden/make_corpus_hashes.py)
-            checks["stream_sha_equals_oracle_golden"] = bool(golden[gkey]["sha256"] == sha and golden[gkey]["bytes"] == out_len)
         value = n * args.steps / dt / 1e6
         roofline = roofline_of(kprof, ENC_KERNELS, pmc)
         # whole-pipeline algorithmic traffic (24 N_in + N_out) over the kernel time, per GPU
@@ -508,8 +499,6 @@ def main():
             "kernels": {k: {"launches": v["launches"], "ms": round(v["seconds"] * 1e3, 3),
                             "GBps": round(v["bytes"] / v["seconds"] / 1e9, 1) if v["seconds"] else 0}
                         for k, v in kprof.items() if v["launches"]},
-            "stream_sha256": sha,
-            "checks": checks,
         }
         if pre is not None:
             result["preflight"] = pre
@@ -523,6 +512,24 @@ def main():
                                              "waited (BZ_CUT_TABLES=0: left halo, tile offsets and the chain kernel); the links are the one "
                                              "serial thing across the ranks.  Ranks that SHARE a GPU wait for each other's kernels "
                                              "here: extra.shard_link_replay of the one-GPU line has the link on an idle GPU"}
+    if rank == 0 and args.full:
+        golden = load_json("tests", "golden", "corpus_hashes.json")
+        sha = hashlib.sha256(out).hexdigest()
+        # size-independent checks outside the timed region: the stream decodes, and its head is the corpus
+        try:
+            head = bz2.BZ2Decompressor().decompress(out[:min(len(out), 48 << 20)], 32 << 20)
+            ok_head = len(head) > 0 and head == bytes(d_in[:len(head)].cpu().numpy())
+        except (OSError, ValueError, EOFError):
+            ok_head = False
+        checks = {"head_decodes_to_input": bool(ok_head)}
+        gkey = None
+        if args.level == 9 and n % (1 << 20) == 0:
+            size = "%dgib" % (n >> 30) if n % (1 << 30) == 0 else "%dmib" % (n >> 20)
+            gkey = "bzip2_l9_%s_%s" % (args.corpus, size)
+        if gkey in golden:  # the oracle's stream for this exact corpus (tests/golden/make_corpus_hashes.py)
+            checks["stream_sha_equals_oracle_golden"] = bool(golden[gkey]["sha256"] == sha and golden[gkey]["bytes"] == out_len)
+        result["stream_sha256"] = sha
+        result["checks"] = checks
         if not args.no_cpu_baseline:
             # cpu_baseline leg: the oracle (a C restatement of the reference algorithm, 1 thread like the
             # reference) on a bounded sample of the same corpus; its output doubles as a parity check.
@@ -548,7 +555,7 @@ def main():
         if not args.no_extras and world == 1 and args.corpus == "text":
             args._beat = dog.beat
             extras(result, args, pkg, eng, torch, dev, d_in, n, d_out, out_len, golden, corpus)
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         # The legs behind the headline.  They have only ever run in one-GPU emulation here, so they get a deadline of
         # their own: when it passes, rank 0 prints the headline with what is there and every rank leaves with status 0
         # (the main watchdog would end the run with status 5 and no line at all).
@@ -619,7 +626,7 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(result))
-        if not all(result["checks"].values()):
+        if not all(result.get("checks", {}).values()):
             sys.exit(3)
 
 

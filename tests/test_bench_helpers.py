@@ -1,5 +1,5 @@
-"""CPU-side checks of bench.py's plumbing that needs no GPU: the per-step statistics and the watchdog that ends
-a rank which makes no progress (a peer died inside a collective) with status 5."""
+"""CPU-side checks of bench.py's plumbing that needs no GPU: the per-step statistics, --full off by default, and the
+watchdog that ends a rank which makes no progress (a peer died inside a collective) with status 5."""
 import importlib.util
 import os
 import subprocess
@@ -22,6 +22,14 @@ def test_step_stats():
     assert s == {"median": 2.0, "min": 1.0, "max": 3.0, "n": 3}
     s = b.step_stats([0.004, 0.001, 0.002, 0.003])
     assert s["median"] == 2.5 and s["n"] == 4
+
+
+def test_full_is_off_by_default(monkeypatch):
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert b.parse_args().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--full"])
+    assert b.parse_args().full is True
 
 
 def test_watchdog_ends_a_stalled_process_with_status_5():

@@ -183,11 +183,11 @@ def _bench_ranks(world, extra_args, env_extra, timeout):
 
 
 def test_bench_two_ranks_line_is_self_sufficient():
-    """bench.py --gpus 2 (two real rank processes sharing the box's one GPU, gloo): the N > 1 line carries
+    """bench.py --gpus 2 --full (two real rank processes sharing the box's one GPU, gloo): the N > 1 line carries
     cpu_baseline, roofline.pipeline_8d, per-step median / min, the rank count, the sharded decode round trip and
     the single-process end-to-end figure over the run's devices -- everything a SCALE line needs."""
     import json
-    outs = _bench_ranks(2, ["--steps", "2", "--warmup", "1", "--mib-per-gpu", "32", "--cpu-sample-mib", "8",
+    outs = _bench_ranks(2, ["--full", "--steps", "2", "--warmup", "1", "--mib-per-gpu", "32", "--cpu-sample-mib", "8",
                             "--hang-timeout", "240"], {}, 900)
     assert [o[0] for o in outs] == [0, 0], outs[0][2][-2000:] + outs[1][2][-2000:]
     lines0 = [x for x in outs[0][1].splitlines() if x.startswith("{")]
