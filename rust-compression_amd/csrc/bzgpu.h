@@ -576,6 +576,9 @@ struct MailSeg {
     size_t n;
 };
 int mail_fetch(hipStream_t st, const MailSeg *segs, int nseg);
+// the stream's mailbox (pinned host memory) is freed: call it for a stream that has been waited for, before it is destroyed,
+// so that a later stream with the same handle does not inherit it; nothing to do for a stream that never fetched
+void mail_release(hipStream_t st);
 // a few bytes from the host in front of the next launch (up to 1 KB as a kernel argument, more by hipMemcpyAsync); 0 = queued
 int mail_poke(hipStream_t st, void *d_dst, const void *h_src, size_t n);
 void launch_huffman(hipStream_t st, const HuffArgs &a);

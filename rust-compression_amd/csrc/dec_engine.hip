@@ -54,11 +54,6 @@ struct DecWorkspace {
 void dec_workspace_free(DecWorkspace *w)
 {
     if (!w) return;
-    DevBuf *all[] = {&w->win_base, &w->win_bytes, &w->cands, &w->count, &w->info, &w->sym, &w->sel, &w->slot, &w->nbmax, &w->perm,
-                     &w->chunk_emit, &w->tt_len, &w->err, &w->L, &w->T, &w->X, &w->samp_next, &w->samp_len,
-                     &w->samp_off, &w->cycle_len, &w->sub_trans, &w->sub_off, &w->sub_state, &w->work_ctr, &w->walk_meta, &w->seg_buf, &w->seg_cont, &w->long_list, &w->out_len, &w->thist, &w->tbase,
-                     &w->crc, &w->out_base, &w->staging, &w->staging2, &w->cand_all};
-    for (DevBuf *b : all) b->release();
     if (w->ev_a) (void)hipEventDestroy(w->ev_a);
     if (w->ev_b) (void)hipEventDestroy(w->ev_b);
     delete w;

@@ -7,6 +7,7 @@
 // Action::Flush in the middle of a stream (a stream is then a sequence of byte-aligned SEGMENTS, df_enc_end).
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "engine_state.h"
@@ -37,10 +38,6 @@ struct DfWorkspace {
 void df_workspace_free(DfWorkspace *w)
 {
     if (!w) return;
-    DevBuf *all[] = {&w->keys_in, &w->keys_out, &w->vals_in, &w->vals_out, &w->sort_tmp, &w->prevd, &w->est, &w->segoff, &w->concat, &w->bitmap, &w->canon, &w->tabs, &w->ents,
-                     &w->bstart, &w->nb, &w->blocks, &w->lens, &w->hdr, &w->lm, &w->total, &w->stream, &w->asum, &w->bsum,
-                     &w->crc, &w->part_res};
-    for (DevBuf *b : all) b->release();
     if (w->ev_ready) {
         for (hipEvent_t e : w->ev) (void)hipEventDestroy(e);
         for (hipEvent_t e : w->evq) (void)hipEventDestroy(e);
@@ -756,8 +753,6 @@ extern "C" void df_enc_destroy(df_enc *e)
         int caller_device = -1;
         (void)hipGetDevice(&caller_device);
         (void)hipSetDevice(e->device);
-        e->d_data.release();
-        e->d_out.release();
         // kept, with its workspace, for the next context or one-shot call on the device -- unless the context met an
         // infrastructure error (a sticky HIP error, a half-grown workspace): bz_decode_buffer, df_encode_buffer and
         // bz_dec_destroy do the same
@@ -819,8 +814,7 @@ static int df_enc_end_impl(df_enc *e, int action)
             HIPCHK(hipMemcpyAsync(bigger.p, e->d_data.p, e->total, hipMemcpyDeviceToDevice, e->g->st));
             HIPCHK(hipStreamSynchronize(e->g->st));
         }
-        e->d_data.release();
-        e->d_data = bigger;
+        e->d_data = std::move(bigger); // (frees the old block)
     }
     if (add) HIPCHK(hipMemcpy(e->d_data.as<u8>() + e->total, e->in.data(), add, hipMemcpyHostToDevice));
     HIPCHK(hipMemsetAsync(e->d_data.as<u8>() + e->total + add, 0, 64, e->g->st)); // (ordered in front of the engine's kernels)

@@ -13,7 +13,6 @@
 #include <cstring>
 #include <vector>
 
-
 // a few bytes for the host and the stream's earlier work done (mail_fetch, k_emit.hip)
 #define MAILCHK(st, ...)                                                             \
     do {                                                                             \
@@ -50,9 +49,6 @@ static void spans_collect(bz_gpu_engine *g)
     g->t_stage[5] = g->t_stage[0] + g->t_stage[1] + g->t_stage[2] + g->t_stage[3] + g->t_stage[4];
 }
 
-// The batch workspace holds `ws_blocks` blocks in flight: as many as the call at hand needs (up to
-// max_blocks, the batch size), grown when a later call needs more -- a context that only ever sees small
-// inputs does not take 31.5 MB x max_blocks of HBM.
 // BZ_ONESWEEP=0: the three-kernel radix passes from the start (tests/test_gpu_parity.py::test_radix_pass_flavours_agree)
 static bool fused_wanted()
 {
@@ -60,6 +56,76 @@ static bool fused_wanted()
     return on;
 }
 
+// The batch workspace, buffer by buffer in the order of allocation: `per_block` bytes for every block in flight plus
+// `fixed` bytes.  This table is the one place on the host that states what a block takes of each buffer; the argument
+// blocks below (make_*_args) hand out base pointers, and the kernels stride by the same constants.
+struct WsBuf {
+    DevBuf bz_gpu_engine::*buf;
+    size_t per_block, fixed;
+    bool fused_only; // exists only with the fused radix passes (fused_wanted())
+};
+static constexpr WsBuf kWorkspace[] = {
+    {&bz_gpu_engine::lblocks, sizeof(BlockDesc), 0, false},
+    {&bz_gpu_engine::lcrc, 4, 0, false},
+    {&bz_gpu_engine::SA, (size_t)kSlot * 4, 0, false},
+    {&bz_gpu_engine::R, (size_t)kSlot * 4, 0, false},
+    {&bz_gpu_engine::KA, (size_t)kSlot * 4, 0, false},
+    {&bz_gpu_engine::VA, (size_t)kSlot * 4, 0, false},
+    {&bz_gpu_engine::KB, (size_t)kSlot * 4, 0, false},
+    {&bz_gpu_engine::VB, (size_t)kSlot * 4, 0, false},
+    {&bz_gpu_engine::tile_hist, (size_t)kTilesPerBlock * kMaxBins * 4, 0, false},
+    {&bz_gpu_engine::count, 4, 0, false},
+    {&bz_gpu_engine::bin_base, (size_t)kMaxBins * 4, 0, false},
+    {&bz_gpu_engine::sym_code, 256, 0, false},
+    {&bz_gpu_engine::count2, 4, 0, false},
+    {&bz_gpu_engine::tile_nf, (size_t)kTilesPerBlock * 4, 0, false},
+    {&bz_gpu_engine::keyinfo, 4, 0, false},
+    {&bz_gpu_engine::flags, kSlot, 0, false},
+    {&bz_gpu_engine::newbits, kSlot / 8, 256, false},
+    {&bz_gpu_engine::tlo, (size_t)kTilesPerBlock * 4, 0, false},
+    {&bz_gpu_engine::tln, (size_t)kTilesPerBlock * 4, 0, false},
+    {&bz_gpu_engine::nonfinal, 4, 0, false},
+    {&bz_gpu_engine::active, 0, 64 * 8 + 64 * 4, false},
+    {&bz_gpu_engine::per_k, 4, 0, false},
+    {&bz_gpu_engine::per_shift, 4, 0, false},
+    {&bz_gpu_engine::lin_p, (size_t)4 * kPerK, 0, false},
+    {&bz_gpu_engine::lin_sig, (size_t)4 * kPerK, 0, false},
+    {&bz_gpu_engine::bin_cursor, (size_t)1024 * 4, 0, false},
+    {&bz_gpu_engine::pb_gate, 4, 1024, false}, // (+ loc_stats behind the gates: 256 words)
+    {&bz_gpu_engine::L, kSlot, 64, false},
+    {&bz_gpu_engine::orig_ptr, 4, 0, false},
+    {&bz_gpu_engine::inuse_bits, 32, 0, false},
+    {&bz_gpu_engine::summ, (size_t)kMaxMtfChunks * 256, 0, false},
+    {&bz_gpu_engine::summ_len, (size_t)kMaxMtfChunks * 2, 0, false},
+    {&bz_gpu_engine::init_state, (size_t)kMaxMtfChunks * 256, 0, false},
+    {&bz_gpu_engine::rank8, kSlot, 64, false},
+    {&bz_gpu_engine::ztile_last, (size_t)kTilesPerBlock * 4, 0, false},
+    {&bz_gpu_engine::ztile_cnt, (size_t)kTilesPerBlock * 4, 0, false},
+    {&bz_gpu_engine::zstate, (size_t)kTilesPerBlock * 16, 0, false},
+    {&bz_gpu_engine::ztick, 0, 64, false},
+    {&bz_gpu_engine::mtf, (size_t)kMtfStride * 2, 0, false},
+    {&bz_gpu_engine::mtf_freq, (size_t)kMaxAlpha * 4, 0, false},
+    {&bz_gpu_engine::bout, sizeof(BlockOut), 0, false},
+    {&bz_gpu_engine::selector, kSelStride, 0, false},
+    {&bz_gpu_engine::code_len, (size_t)6 * kMaxAlpha * 4, 0, false},
+    {&bz_gpu_engine::group_bitoff, (size_t)kGboStride * 4, 0, false},
+    {&bz_gpu_engine::lm_scratch, (size_t)6 * kLmWords * 4, 0, false},
+    {&bz_gpu_engine::hglen, (size_t)6 * (kMaxAlpha + 6), 0, false},
+    {&bz_gpu_engine::hpack, (size_t)kMaxAlpha * 8, 0, false},
+    {&bz_gpu_engine::hrfreq, (size_t)6 * kMaxAlpha * 4, 0, false},
+    {&bz_gpu_engine::hlm, 4, 0, false},
+    {&bz_gpu_engine::hpass, (size_t)32 * 4, 0, false},
+    {&bz_gpu_engine::stream, (size_t)kStreamWords * 4, 0, false},
+    {&bz_gpu_engine::error_flag, 0, 4, false},
+    {&bz_gpu_engine::packlist, sizeof(PackBlock), 0, false},
+    {&bz_gpu_engine::gh_tiles, (size_t)kTilesPerBlock * 3 * kMaxBins * 4, 0, true},
+    {&bz_gpu_engine::gbase, (size_t)3 * kMaxBins * 4, 0, true},
+    {&bz_gpu_engine::tile_state, (size_t)kTilesPerBlock * kMaxBins * 4, 0, true},
+    {&bz_gpu_engine::tickets, 0, (size_t)kSortEpochs * 8 * 4 + 64, true},
+};
+// Per block in flight, before DevBuf's slack of one eighth: 34 179 820 bytes (30 550 764 without the fused radix passes).
+// The batch workspace holds `ws_blocks` blocks in flight: as many as the call at hand needs (up to max_blocks, the batch
+// size), grown when a later call needs more -- a context that only ever sees small inputs does not take 34.2 MB x max_blocks.
 static int ensure_workspace(bz_gpu_engine *g, size_t need_blocks)
 {
     if (need_blocks > g->max_blocks) need_blocks = g->max_blocks;
@@ -68,80 +134,19 @@ static int ensure_workspace(bz_gpu_engine *g, size_t need_blocks)
     // (grow in steps: a stream of growing chunks does not reallocate for every one)
     size_t nb = need_blocks + need_blocks / 4;
     if (nb > g->max_blocks) nb = g->max_blocks;
-    int rc = BZ_OK;
     g->ws_blocks = 0; // (a growth that fails half way leaves some buffers NULL: the next call must ensure them all again)
-#define ENS(buf, bytes)                         \
-    do {                                        \
-        rc = g->buf.ensure((size_t)(bytes));    \
-        if (rc != BZ_OK) return rc;             \
-    } while (0)
-    ENS(lblocks, nb * sizeof(BlockDesc));
-    ENS(lcrc, nb * 4);
-    ENS(SA, nb * (size_t)kSlot * 4);
-    ENS(R, nb * (size_t)kSlot * 4);
-    ENS(KA, nb * (size_t)kSlot * 4);
-    ENS(VA, nb * (size_t)kSlot * 4);
-    ENS(KB, nb * (size_t)kSlot * 4);
-    ENS(VB, nb * (size_t)kSlot * 4);
-    ENS(tile_hist, nb * (size_t)kTilesPerBlock * kMaxBins * 4);
-    ENS(count, nb * 4);
-    ENS(bin_base, nb * (size_t)kMaxBins * 4);
-    ENS(sym_code, nb * (size_t)256);
-    ENS(count2, nb * 4);
-    ENS(tile_nf, nb * (size_t)kTilesPerBlock * 4);
-    ENS(keyinfo, nb * (size_t)4);
-    ENS(flags, nb * (size_t)kSlot);
-    ENS(newbits, nb * (size_t)kSlot / 8 + 256);
-    ENS(tlo, nb * (size_t)kTilesPerBlock * 4);
-    ENS(tln, nb * (size_t)kTilesPerBlock * 4);
-    ENS(nonfinal, nb * 4);
-    ENS(active, 64 * 8 + 64 * 4);
-    ENS(per_k, nb * 4);
-    ENS(per_shift, nb * 4);
-    ENS(lin_p, nb * (size_t)4 * kPerK);
-    ENS(lin_sig, nb * (size_t)4 * kPerK);
-    ENS(bin_cursor, nb * (size_t)1024 * 4);
-    ENS(pb_gate, nb * (size_t)4 + 1024); // (+ loc_stats behind the gates: 256 words)
+    const bool fused = fused_wanted();
+    for (const WsBuf &w : kWorkspace) {
+        if (w.fused_only && !fused) continue;
+        if (const int rc = (g->*w.buf).ensure(nb * w.per_block + w.fixed)) return rc;
+    }
     // (cleared ON THE ENGINE'S STREAM: a memset on the null stream is not ordered against work on a non-blocking stream,
     // and it need not be over when the call returns)
     if (hipMemsetAsync(g->pb_gate.p, 0, g->pb_gate.cap, g->st) != hipSuccess) return BZ_E_UNEXPECTED;
-    ENS(L, nb * (size_t)kSlot + 64);
-    ENS(orig_ptr, nb * 4);
-    ENS(inuse_bits, nb * 32);
-    ENS(summ, nb * (size_t)kMaxMtfChunks * 256);
-    ENS(summ_len, nb * (size_t)kMaxMtfChunks * 2);
-    ENS(init_state, nb * (size_t)kMaxMtfChunks * 256);
-    ENS(rank8, nb * (size_t)kSlot + 64);
-    ENS(ztile_last, nb * (size_t)kTilesPerBlock * 4);
-    ENS(ztile_cnt, nb * (size_t)kTilesPerBlock * 4);
-    ENS(zstate, nb * (size_t)kTilesPerBlock * 16);
-    ENS(ztick, 64);
-    ENS(mtf, nb * (size_t)kMtfStride * 2);
-    ENS(mtf_freq, nb * (size_t)kMaxAlpha * 4);
-    ENS(bout, nb * sizeof(BlockOut));
-    ENS(selector, nb * (size_t)kSelStride);
-    ENS(code_len, nb * (size_t)6 * kMaxAlpha * 4);
-    ENS(group_bitoff, nb * (size_t)kGboStride * 4);
-    ENS(lm_scratch, nb * (size_t)6 * kLmWords * 4);
-    ENS(hglen, nb * (size_t)6 * (kMaxAlpha + 6));
-    ENS(hpack, nb * (size_t)kMaxAlpha * 8);
-    ENS(hrfreq, nb * (size_t)6 * kMaxAlpha * 4);
-    ENS(hlm, nb * 4);
-    ENS(hpass, nb * (size_t)32 * 4);
-    ENS(stream, nb * (size_t)kStreamWords * 4);
-    ENS(error_flag, 4);
-    ENS(packlist, nb * sizeof(PackBlock));
-    if (fused_wanted()) { // buffers of the fused radix passes
-        ENS(gh_tiles, nb * (size_t)kTilesPerBlock * 3 * kMaxBins * 4);
-        ENS(gbase, nb * (size_t)3 * kMaxBins * 4);
-        ENS(tile_state, nb * (size_t)kTilesPerBlock * kMaxBins * 4);
-        ENS(tickets, (size_t)kSortEpochs * 8 * 4 + 64);
-        if (hipMemsetAsync(g->tile_state.p, 0, g->tile_state.cap, g->st) != hipSuccess ||
-            hipMemsetAsync(g->tickets.p, 0, g->tickets.cap, g->st) != hipSuccess)
-            return BZ_E_UNEXPECTED;
-        g->sort_epoch = 0;
-    }
-#undef ENS
+    if (fused && (hipMemsetAsync(g->tile_state.p, 0, g->tile_state.cap, g->st) != hipSuccess ||
+                  hipMemsetAsync(g->tickets.p, 0, g->tickets.cap, g->st) != hipSuccess))
+        return BZ_E_UNEXPECTED;
+    if (fused) g->sort_epoch = 0;
     g->ws_blocks = nb;
     return BZ_OK;
 }
@@ -217,23 +222,15 @@ extern "C" void bz_gpu_engine_destroy(bz_gpu_engine *g)
     (void)hipSetDevice(g->device);
     (void)hipStreamSynchronize(g->st);
     (void)hipStreamSynchronize(g->st2);
-    DevBuf *all[] = {&g->dec_in, &g->oneshot_out, &g->cut_step_t0, &g->cut_step_nt, &g->cut_step_w0, &g->cut_tab, &g->cut_comp,
-                     &g->crc_tab, &g->xp16, &g->xp2, &g->tile_last, &g->carry_in, &g->tile_crc, &g->tile_count,
-                     &g->tile_off, &g->sub_off, &g->sub_rs, &g->scal, &g->scan_part, &g->rle, &g->blocks_all, &g->crc_all, &g->lblocks, &g->lcrc, &g->SA,
-                     &g->R, &g->KA, &g->VA, &g->KB, &g->VB, &g->tile_hist, &g->count, &g->flags, &g->tlo, &g->tln,
-                     &g->nonfinal, &g->active, &g->per_k, &g->per_shift, &g->lin_p, &g->lin_sig, &g->bin_cursor, &g->pb_gate, &g->newbits, &g->bin_base, &g->sym_code, &g->keyinfo, &g->count2, &g->tile_nf, &g->L, &g->orig_ptr, &g->inuse_bits,
-                     &g->summ, &g->summ_len, &g->init_state, &g->rank8, &g->ztile_last, &g->ztile_cnt, &g->mtf,
-                     &g->mtf_freq, &g->bout, &g->selector, &g->code_len, &g->group_bitoff, &g->lm_scratch, &g->hglen, &g->hpack, &g->hrfreq, &g->hlm, &g->hpass,
-                     &g->stream, &g->error_flag, &g->packlist, &g->packed, &g->gathered, &g->asmlist, &g->gh_tiles, &g->gbase, &g->tile_state,
-                     &g->tickets, &g->vstream, &g->vout, &g->vseg, &g->vmis};
-    for (DevBuf *b : all) b->release();
     dec_workspace_free(g->dec);
     df_workspace_free(g->df);
     if (g->h_active) (void)hipHostFree(g->h_active);
+    mail_release(g->st);
+    mail_release(g->st2);
     if (g->st) (void)hipStreamDestroy(g->st);
     if (g->ev_aux) (void)hipEventDestroy(g->ev_aux);
     if (g->st2) (void)hipStreamDestroy(g->st2);
-    delete g;
+    delete g; // (the device buffers go with it: dev_buf.h)
 }
 
 static RleBuffers rle_buffers(bz_gpu_engine *g)
@@ -660,48 +657,48 @@ extern "C" int bz_gpu_partition(bz_gpu_engine *g, int level, const void *d_in, s
     return rc;
 }
 
-// Argument blocks for the sub-batch of `nb` blocks that starts at local block `o`.
-static BwtArgs make_bwt_args(bz_gpu_engine *g, u32 nb, u32 o = 0)
+// Argument blocks for a batch of `nb` blocks: the base of every buffer (the kernels stride by block; what a block takes
+// of each buffer is stated once, in kWorkspace).
+static BwtArgs make_bwt_args(bz_gpu_engine *g, u32 nb)
 {
     BwtArgs x;
-    const size_t s = (size_t)o * kSlot, t = (size_t)o * kTilesPerBlock;
     x.rle = g->rle.as<u8>();
-    x.blocks = g->lblocks.as<BlockDesc>() + o;
+    x.blocks = g->lblocks.as<BlockDesc>();
     x.nb = nb;
     x.tiles = kTilesPerBlock;
-    x.SA = g->SA.as<u32>() + s;
-    x.R = g->R.as<u32>() + s;
-    x.KA = g->KA.as<u32>() + s;
-    x.VA = g->VA.as<u32>() + s;
-    x.KB = g->KB.as<u32>() + s;
-    x.VB = g->VB.as<u32>() + s;
-    x.tile_hist = g->tile_hist.as<u32>() + t * kMaxBins;
-    x.count = g->count.as<u32>() + o;
-    x.count2 = g->count2.as<u32>() + o;
-    x.tile_nf = g->tile_nf.as<u32>() + t;
-    x.bin_base = g->bin_base.as<u32>() + (size_t)o * kMaxBins;
-    x.flags = g->flags.as<u8>() + s;
-    x.newbits = g->newbits.as<u64>() + s / 64;
-    x.tile_last_old = g->tlo.as<int>() + t;
-    x.tile_last_new = g->tln.as<int>() + t;
-    x.nonfinal = g->nonfinal.as<u32>() + o;
+    x.SA = g->SA.as<u32>();
+    x.R = g->R.as<u32>();
+    x.KA = g->KA.as<u32>();
+    x.VA = g->VA.as<u32>();
+    x.KB = g->KB.as<u32>();
+    x.VB = g->VB.as<u32>();
+    x.tile_hist = g->tile_hist.as<u32>();
+    x.count = g->count.as<u32>();
+    x.count2 = g->count2.as<u32>();
+    x.tile_nf = g->tile_nf.as<u32>();
+    x.bin_base = g->bin_base.as<u32>();
+    x.flags = g->flags.as<u8>();
+    x.newbits = g->newbits.as<u64>();
+    x.tile_last_old = g->tlo.as<int>();
+    x.tile_last_new = g->tln.as<int>();
+    x.nonfinal = g->nonfinal.as<u32>();
     x.active = g->active.as<unsigned long long>();
     x.maxnf = reinterpret_cast<u32 *>(g->active.as<unsigned long long>() + 64);
-    x.per_k = g->per_k.as<u32>() + o;
-    x.per_shift = g->per_shift.as<u32>() + o;
-    x.lin_p = g->lin_p.as<u32>() + (size_t)o * kPerK;
-    x.lin_sig = g->lin_sig.as<u32>() + (size_t)o * kPerK;
-    x.bin_cursor = g->bin_cursor.as<u32>() + (size_t)o * 1024;
-    x.pb_gate = g->pb_gate.as<u32>() + o;
+    x.per_k = g->per_k.as<u32>();
+    x.per_shift = g->per_shift.as<u32>();
+    x.lin_p = g->lin_p.as<u32>();
+    x.lin_sig = g->lin_sig.as<u32>();
+    x.bin_cursor = g->bin_cursor.as<u32>();
+    x.pb_gate = g->pb_gate.as<u32>();
     x.loc_stats = g->pb_gate.as<u32>() + g->ws_blocks; // (behind the gates)
-    x.L = g->L.as<u8>() + s;
-    x.orig_ptr = g->orig_ptr.as<u32>() + o;
-    x.ptext = g->rank8.as<u8>() + s; // (free until launch_mtf writes the ranks of this sub-batch)
-    x.sym_code = g->sym_code.as<u8>() + (size_t)o * 256;
-    x.keyinfo = g->keyinfo.as<u8>() + (size_t)o * 4;
-    x.gh_tiles = g->gh_tiles.as<u32>() + t * 3 * kMaxBins;
-    x.gbase = g->gbase.as<u32>() + (size_t)o * 3 * kMaxBins;
-    x.tile_state = g->tile_state.as<u32>() + t * kMaxBins;
+    x.L = g->L.as<u8>();
+    x.orig_ptr = g->orig_ptr.as<u32>();
+    x.ptext = g->rank8.as<u8>(); // (free until launch_mtf writes the batch's ranks)
+    x.sym_code = g->sym_code.as<u8>();
+    x.keyinfo = g->keyinfo.as<u8>();
+    x.gh_tiles = g->gh_tiles.as<u32>();
+    x.gbase = g->gbase.as<u32>();
+    x.tile_state = g->tile_state.as<u32>();
     x.tickets = g->tickets.as<u32>();
     x.sort_err = g->tickets.p ? g->tickets.as<u32>() + (size_t)kSortEpochs * 8 : nullptr; // (no fused passes: not allocated)
     x.epoch = &g->sort_epoch;
@@ -713,57 +710,56 @@ static BwtArgs make_bwt_args(bz_gpu_engine *g, u32 nb, u32 o = 0)
     x.per_links = want_links;
     x.per_keyshift = 0;
     x.per_wide = 0;
-    x.per_aux = reinterpret_cast<u8 *>(g->mtf.as<u16>() + (size_t)o * kMtfStride);
+    x.per_aux = g->mtf.as<u8>();
     return x;
 }
 
-static MtfArgs make_mtf_args(bz_gpu_engine *g, u32 nb, u32 o, u32 total_nb)
+static MtfArgs make_mtf_args(bz_gpu_engine *g, u32 nb)
 {
     MtfArgs ma;
-    const size_t s = (size_t)o * kSlot, t = (size_t)o * kTilesPerBlock, c = (size_t)o * kMaxMtfChunks;
-    ma.blocks = g->lblocks.as<BlockDesc>() + o;
+    ma.blocks = g->lblocks.as<BlockDesc>();
     ma.nb = nb;
     ma.tiles = kTilesPerBlock; // (encode_batch: what the batch's largest block needs)
-    ma.L = g->L.as<u8>() + s;
-    ma.inuse_bits = g->inuse_bits.as<u32>() + (size_t)o * 8;
-    ma.summ = g->summ.as<u8>() + c * 256;
-    ma.summ_len = g->summ_len.as<u16>() + c;
-    ma.init_state = g->init_state.as<u8>() + c * 256;
-    ma.rank8 = g->rank8.as<u8>() + s;
-    ma.ztile_last = g->ztile_last.as<int>() + t;
-    ma.ztile_cnt = g->ztile_cnt.as<u32>() + t;
-    ma.zstate = g->zstate.as<u32>() + t * 4;
+    ma.L = g->L.as<u8>();
+    ma.inuse_bits = g->inuse_bits.as<u32>();
+    ma.summ = g->summ.as<u8>();
+    ma.summ_len = g->summ_len.as<u16>();
+    ma.init_state = g->init_state.as<u8>();
+    ma.rank8 = g->rank8.as<u8>();
+    ma.ztile_last = g->ztile_last.as<int>();
+    ma.ztile_cnt = g->ztile_cnt.as<u32>();
+    ma.zstate = g->zstate.as<u32>();
     ma.ztick = g->ztick.as<u32>();
     static const bool want_fused_zle = !(getenv("BZ_FUSED_ZLE") && atoi(getenv("BZ_FUSED_ZLE")) == 0);
-    ma.fused_zle = (want_fused_zle && !g->zle_fused_broken && o == 0 && nb == total_nb) ? 1u : 0u; // (one sub-batch: one set of tickets)
-    ma.mtf = g->mtf.as<u16>() + (size_t)o * kMtfStride;
-    ma.mtf_freq = g->mtf_freq.as<u32>() + (size_t)o * kMaxAlpha;
-    ma.out = g->bout.as<BlockOut>() + o;
+    ma.fused_zle = (want_fused_zle && !g->zle_fused_broken) ? 1u : 0u;
+    ma.mtf = g->mtf.as<u16>();
+    ma.mtf_freq = g->mtf_freq.as<u32>();
+    ma.out = g->bout.as<BlockOut>();
     return ma;
 }
 
-static HuffArgs make_huff_args(bz_gpu_engine *g, u32 nb, u32 o)
+static HuffArgs make_huff_args(bz_gpu_engine *g, u32 nb)
 {
     HuffArgs ha;
-    ha.blocks = g->lblocks.as<BlockDesc>() + o;
+    ha.blocks = g->lblocks.as<BlockDesc>();
     ha.nb = nb;
-    ha.mtf = g->mtf.as<u16>() + (size_t)o * kMtfStride;
+    ha.mtf = g->mtf.as<u16>();
     ha.mtf_stride = kMtfStride;
-    ha.mtf_freq = g->mtf_freq.as<u32>() + (size_t)o * kMaxAlpha;
-    ha.inuse_bits = g->inuse_bits.as<u32>() + (size_t)o * 8;
-    ha.crc = g->lcrc.as<u32>() + o;
-    ha.orig_ptr = g->orig_ptr.as<u32>() + o;
-    ha.selector = g->selector.as<u8>() + (size_t)o * kSelStride;
-    ha.code_len = g->code_len.as<u32>() + (size_t)o * 6 * kMaxAlpha;
-    ha.group_bitoff = g->group_bitoff.as<u32>() + (size_t)o * kGboStride;
-    ha.lm_scratch = g->lm_scratch.as<u32>() + (size_t)o * 6 * kLmWords;
-    ha.glen = g->hglen.as<u8>() + (size_t)o * 6 * (kMaxAlpha + 6);
-    ha.pack = g->hpack.as<unsigned long long>() + (size_t)o * kMaxAlpha;
-    ha.rfreq = g->hrfreq.as<u32>() + (size_t)o * 6 * kMaxAlpha;
-    ha.hlm = g->hlm.as<u32>() + o;
-    ha.pass_stats = g->debug_figures ? g->hpass.as<u32>() + (size_t)o * 32 : nullptr; // (armed by bz_gpu_profile_enable(g, 2))
-    ha.stream = g->stream.as<u32>() + (size_t)o * kStreamWords;
-    ha.out = g->bout.as<BlockOut>() + o;
+    ha.mtf_freq = g->mtf_freq.as<u32>();
+    ha.inuse_bits = g->inuse_bits.as<u32>();
+    ha.crc = g->lcrc.as<u32>();
+    ha.orig_ptr = g->orig_ptr.as<u32>();
+    ha.selector = g->selector.as<u8>();
+    ha.code_len = g->code_len.as<u32>();
+    ha.group_bitoff = g->group_bitoff.as<u32>();
+    ha.lm_scratch = g->lm_scratch.as<u32>();
+    ha.glen = g->hglen.as<u8>();
+    ha.pack = g->hpack.as<unsigned long long>();
+    ha.rfreq = g->hrfreq.as<u32>();
+    ha.hlm = g->hlm.as<u32>();
+    ha.pass_stats = g->debug_figures ? g->hpass.as<u32>() : nullptr; // (armed by bz_gpu_profile_enable(g, 2))
+    ha.stream = g->stream.as<u32>();
+    ha.out = g->bout.as<BlockOut>();
     ha.error_flag = g->error_flag.as<u32>();
     return ha;
 }
@@ -781,10 +777,9 @@ __global__ void k_test_swap(u8 *L, u32 n)
 }
 
 // symbols in use -> key geometry -> rotation sort.  Returns rounds (<0: error).
-static int sort_batch(bz_gpu_engine *g, const BwtArgs &ba, u32 *inuse_bits, u32 max_n, u64 total_n, u64 *sorted,
-                      KernelProf *prof, u64 *round_active)
+static int sort_batch(bz_gpu_engine *g, const BwtArgs &ba, u32 max_n, u64 total_n, u64 *sorted, KernelProf *prof, u64 *round_active)
 {
-    launch_block_symbols(g->st, ba, inuse_bits, const_cast<u8 *>(ba.sym_code), const_cast<u8 *>(ba.keyinfo));
+    launch_block_symbols(g->st, ba, g->inuse_bits.as<u32>(), const_cast<u8 *>(ba.sym_code), const_cast<u8 *>(ba.keyinfo));
     std::vector<u8> ki((size_t)ba.nb * 4);
     {
         const MailSeg sg = {ki.data(), ba.keyinfo, ki.size()};
@@ -799,109 +794,83 @@ static int sort_batch(bz_gpu_engine *g, const BwtArgs &ba, u32 *inuse_bits, u32 
     return run_bwt(g->st, ba, max_n, total_n, g->h_active, sorted, prof, round_active, wide, min_chars);
 }
 
-// encode one batch of local blocks (descriptors already in g->lblocks / g->lcrc)
-// Encode one batch of local blocks (descriptors already in g->lblocks / g->lcrc; `descs` is the host
-// copy).  The batch is cut into sub-batches: the rotation sort of sub-batch q+1 runs on the main
-// stream while MTF / Huffman / emission of sub-batch q run on the second stream -- those stages are
-// dominated by single-lane serial sections (heap Huffman, list composition) and leave most issue
-// slots and bandwidth free.
+// Encode one batch of local blocks (descriptors already in g->lblocks / g->lcrc; `descs` is the host copy).  The whole
+// batch is sorted on the main stream; MTF / Huffman / emission follow on the second stream behind an event, and the main
+// stream waits for them.  (Sub-batches -- the sort of one beside the tail stages of the one before -- were measured in
+// rounds 1-2 and dropped: a batch fills the chip better whole.)  Whatever happens, both streams are idle and both events
+// are gone when this returns.
 static int encode_batch(bz_gpu_engine *g, u32 nb, const std::vector<BlockDesc> &descs)
 {
-    const u32 parts = 1u; // (sub-batches -- the sort of q + 1 beside the tail stages of q -- were measured in rounds 1-2: a batch fills the chip better whole)
-    std::vector<hipEvent_t> evs;
-    int rc = BZ_OK;
-    bool used_fused_zle = false;
-    u32 zle_tiles = kTilesPerBlock; // tiles per block the one-launch ZLE stage covered (one sub-batch: see make_mtf_args)
-    for (u32 q = 0; q < parts && rc == BZ_OK; ++q) {
-        const u32 o = (u32)(((u64)nb * q) / parts), o1 = (u32)(((u64)nb * (q + 1)) / parts);
-        const u32 nbq = o1 - o;
-        if (nbq == 0) continue;
-        u32 max_n = 0;
-        u64 total_n = 0;
-        for (u32 i = o; i < o1; ++i) {
-            max_n = std::max(max_n, descs[i].n);
-            total_n += descs[i].n;
-        }
-        const BwtArgs ba = make_bwt_args(g, nbq, o);
-        int sp = span_begin(g, 1);
-        u64 sorted = 0;
-        const int rounds = sort_batch(g, ba, g->inuse_bits.as<u32>() + (size_t)o * 8, max_n, total_n, &sorted, &g->prof,
-                                      g->round_active);
-        if (rounds < 0) {
-            rc = BZ_E_UNEXPECTED;
-            break;
-        }
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr; // st -> st2 behind the sort, st2 -> st behind the tail stages
+    const bool have_events = hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) == hipSuccess &&
+                             hipEventCreateWithFlags(&ev_join, hipEventDisableTiming) == hipSuccess;
+    u32 max_n = 0;
+    u64 total_n = 0;
+    for (u32 i = 0; i < nb; ++i) {
+        max_n = std::max(max_n, descs[i].n);
+        total_n += descs[i].n;
+    }
+    MtfArgs ma = make_mtf_args(g, nb);
+    ma.tiles = std::min<u32>(kTilesPerBlock, std::max<u32>(1u, (max_n + kSortTile - 1u) / kSortTile));
+    int sp = have_events ? span_begin(g, 1) : -1;
+    u64 sorted = 0;
+    const int rounds = have_events ? sort_batch(g, make_bwt_args(g, nb), max_n, total_n, &sorted, &g->prof, g->round_active) : -1;
+    int rc = rounds < 0 ? BZ_E_UNEXPECTED : BZ_OK;
+    if (rc == BZ_OK) {
         // (tests) BZ_TEST_CORRUPT=1: a wrong origPtr for the batch's first block while the engine is on its fused passes --
         // a stream that is well formed and decodes to other bytes; nothing but a check of the result can notice
         static const bool corrupt_test = getenv("BZ_TEST_CORRUPT") && atoi(getenv("BZ_TEST_CORRUPT")) != 0;
-        if (corrupt_test && g->fused_state[0] == 0 && descs[o].n > 1)
-            hipLaunchKernelGGL(k_test_bump, dim3(1), dim3(1), 0, g->st, g->orig_ptr.as<u32>() + o, descs[o].n);
+        if (corrupt_test && g->fused_state[0] == 0 && descs[0].n > 1)
+            hipLaunchKernelGGL(k_test_bump, dim3(1), dim3(1), 0, g->st, g->orig_ptr.as<u32>(), descs[0].n);
         // (tests) BZ_TEST_LATE_CLEAR=1: the OUTCOME of round 3's fault -- a sorted order that is not the block's -- as two
         // unequal neighbours of the last column swapped.  (The fault itself, stale look-back words under the first
         // pass's epoch tag, was tried as an injection and is not replayed: tiles scattered to wrong offsets break the
         // digit-count invariants the later passes index with, and the run ends in a GPU memory fault rather than in a
         // wrong stream -- on the test box in two attempts of two.)
         static const bool late_clear_test = getenv("BZ_TEST_LATE_CLEAR") && atoi(getenv("BZ_TEST_LATE_CLEAR")) != 0;
-        if (late_clear_test && g->fused_state[0] == 0 && descs[o].n > 1)
-            hipLaunchKernelGGL(k_test_swap, dim3(1), dim3(1), 0, g->st, g->L.as<u8>() + (size_t)o * kSlot, descs[o].n);
+        if (late_clear_test && g->fused_state[0] == 0 && descs[0].n > 1)
+            hipLaunchKernelGGL(k_test_swap, dim3(1), dim3(1), 0, g->st, g->L.as<u8>(), descs[0].n);
         span_end(g, sp);
         g->bwt_stats[0] = std::max<u64>(g->bwt_stats[0], (u64)rounds);
         g->bwt_stats[1] += sorted;
         g->bwt_stats[2] += 1;
-        hipEvent_t ev;
-        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-            rc = BZ_E_UNEXPECTED;
-            break;
-        }
-        evs.push_back(ev);
-        (void)hipEventRecord(ev, g->st);
-        (void)hipStreamWaitEvent(g->st2, ev, 0);
-
-        MtfArgs ma = make_mtf_args(g, nbq, o, nb);
-        ma.tiles = std::min<u32>(kTilesPerBlock, std::max<u32>(1u, (max_n + kSortTile - 1u) / kSortTile));
-        zle_tiles = ma.tiles;
-        used_fused_zle = used_fused_zle || ma.fused_zle;
+        (void)hipEventRecord(ev_fork, g->st);
+        (void)hipStreamWaitEvent(g->st2, ev_fork, 0);
         sp = span_begin(g, 2, g->st2);
         launch_mtf(g->st2, ma);
         span_end(g, sp);
-        const HuffArgs ha = make_huff_args(g, nbq, o);
         sp = span_begin(g, 3, g->st2);
-        launch_huffman(g->st2, ha);
+        launch_huffman(g->st2, make_huff_args(g, nb));
         span_end(g, sp);
+        (void)hipEventRecord(ev_join, g->st2); // the main stream continues only after the tail stages are done
+        (void)hipStreamWaitEvent(g->st, ev_join, 0);
     }
-    // the main stream continues only after the tail stages are done
-    hipEvent_t done;
-    if (hipEventCreateWithFlags(&done, hipEventDisableTiming) == hipSuccess) {
-        (void)hipEventRecord(done, g->st2);
-        (void)hipStreamWaitEvent(g->st, done, 0);
-        evs.push_back(done);
-    } else {
-        (void)hipStreamSynchronize(g->st2);
-    }
-    u32 tk[9] = {};
-    if (rc == BZ_OK && used_fused_zle) { // (the tickets of the ZLE stage come with the wait for the batch)
+    if (rc == BZ_OK && ma.fused_zle) {
+        // Did the one-launch ZLE stage hand out every tile on every XCD, and did no look-back give up?  (Its tickets come
+        // with the wait for the batch.)  If not (it never has), the MTF / ZLE and Huffman stages run again with the three
+        // ZLE kernels, and the engine stays on them.
+        u32 tk[9] = {};
         const MailSeg sg = {tk, g->ztick.p, sizeof(tk)};
-        if (mail_fetch(g->st, &sg, 1) != 0) return BZ_E_UNEXPECTED;
-    } else {
-        (void)hipStreamSynchronize(g->st);
-    }
-    for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
-    if (rc == BZ_OK && used_fused_zle) {
-        // did the one-launch ZLE stage hand out every tile on every XCD, and did no look-back give up?  If not (it never
-        // has), the MTF / ZLE and Huffman stages run again with the three ZLE kernels, and the engine stays on them.
-        static const bool fail_test = getenv("BZ_FUSED_ZLE_FAILTEST") != nullptr; // (tests: exercise the redo)
-        bool bad = tk[8] != 0 || fail_test;
-        for (u32 x = 0; x < 8; ++x) // (exactly its share of the launch's workgroups: fewer = tiles left out, more = tiles run twice)
-            if (tk[x] != zle_tiles * (xcd_grid_y(nb) / 8u)) bad = true;
-        if (bad) {
-            fprintf(stderr, "bz2_mi355x: the one-launch ZLE stage misbehaved (tile tickets / look-back); stage redone with three kernels\n");
-            g->zle_fused_broken = true;
-            const MtfArgs ma = make_mtf_args(g, nb, 0, nb);
-            launch_mtf(g->st, ma);
-            launch_huffman(g->st, make_huff_args(g, nb, 0));
-            if (hipStreamSynchronize(g->st) != hipSuccess) return BZ_E_UNEXPECTED;
+        if (mail_fetch(g->st, &sg, 1) != 0) {
+            rc = BZ_E_UNEXPECTED; // (no tickets to look at)
+        } else {
+            static const bool fail_test = getenv("BZ_FUSED_ZLE_FAILTEST") != nullptr; // (tests: exercise the redo)
+            bool bad = tk[8] != 0 || fail_test;
+            for (u32 x = 0; x < 8; ++x) // (exactly its share of the launch's workgroups: fewer = tiles left out, more = tiles run twice)
+                if (tk[x] != ma.tiles * (xcd_grid_y(nb) / 8u)) bad = true;
+            if (bad) {
+                fprintf(stderr, "bz2_mi355x: the one-launch ZLE stage misbehaved (tile tickets / look-back); stage redone with three kernels\n");
+                g->zle_fused_broken = true;
+                launch_mtf(g->st, make_mtf_args(g, nb));
+                launch_huffman(g->st, make_huff_args(g, nb));
+            }
         }
     }
+    // the one way out: nothing of this batch is queued or running on either stream behind this point
+    const bool idle = hipStreamSynchronize(g->st2) == hipSuccess;
+    if ((hipStreamSynchronize(g->st) != hipSuccess || !idle) && rc == BZ_OK) rc = BZ_E_UNEXPECTED;
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (ev_join) (void)hipEventDestroy(ev_join);
     return rc;
 }
 
@@ -1671,9 +1640,8 @@ extern "C" int bz_gpu_debug_bwt(bz_gpu_engine *g, const uint8_t *h_block, size_t
     d.n = (u32)n;
     d.pad = 0;
     HIPCHK(hipMemcpyAsync(g->lblocks.p, &d, sizeof(d), hipMemcpyHostToDevice, g->st));
-    const BwtArgs ba = make_bwt_args(g, 1);
     u64 sorted = 0;
-    const int rounds = sort_batch(g, ba, g->inuse_bits.as<u32>(), (u32)n, (u64)n, &sorted, nullptr, nullptr);
+    const int rounds = sort_batch(g, make_bwt_args(g, 1), (u32)n, (u64)n, &sorted, nullptr, nullptr);
     if (rounds < 0) return BZ_E_UNEXPECTED;
     g->bwt_stats[0] = (u64)rounds;
     g->bwt_stats[1] = sorted;
@@ -1706,10 +1674,6 @@ extern "C" int bz_gpu_debug_code_lengths(bz_gpu_engine *g, const uint32_t *h_fre
     HIPCHK(hipStreamSynchronize(g->st));
     HIPCHK(hipGetLastError());
     if (took_length_limited_path) *took_length_limited_path = flag;
-    f.release();
-    o.release();
-    s.release();
-    fl.release();
     return BZ_OK;
 }
 

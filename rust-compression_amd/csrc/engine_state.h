@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/bz2_mi355x.h"
 #include "bzgpu.h"
+#include "dev_buf.h"
 
 #include <cstdio>
 #include <vector>
@@ -33,36 +34,10 @@ void df_workspace_free(DfWorkspace *w);
         }                                                                                             \
     } while (0)
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes)
-    {
-        if (bytes <= cap) return BZ_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes + bytes / 8 + 256;
-        if (hipMalloc(&p, want) != hipSuccess) {
-            if (hipMalloc(&p, bytes) != hipSuccess) return BZ_E_NOMEM;
-            want = bytes;
-        }
-        cap = want;
-        return BZ_OK;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
 struct bz_gpu_engine {
     int device = 0;
     hipStream_t st = nullptr;   // rotation sort (and everything serial)
-    hipStream_t st2 = nullptr;  // MTF / Huffman / emission of the previous sub-batch
+    hipStream_t st2 = nullptr;  // MTF / Huffman of a batch behind its sort (encode_batch); the RLE1 image beside the cut chain
     size_t max_blocks = 0;
 
     // constant tables

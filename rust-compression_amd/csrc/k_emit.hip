@@ -178,13 +178,15 @@ struct Mailbox {
     u32 *hseq = nullptr, *dseq = nullptr;
     u32 seq = 0;
 };
+// one mailbox per stream, made by the stream's first mail_fetch and freed by mail_release when the stream's owner
+// destroys it (a stream is driven by one host thread at a time)
+static std::mutex g_boxes_mu;
+static std::unordered_map<hipStream_t, Mailbox *> g_boxes;
 static Mailbox *mailbox_of(hipStream_t st)
 {
-    static std::mutex mu;
-    static std::unordered_map<hipStream_t, Mailbox *> boxes; // (a stream is driven by one host thread at a time)
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = boxes.find(st);
-    if (it != boxes.end()) return it->second;
+    std::lock_guard<std::mutex> lk(g_boxes_mu);
+    auto it = g_boxes.find(st);
+    if (it != g_boxes.end()) return it->second;
     Mailbox *m = new Mailbox;
     void *p = nullptr;
     if (hipHostMalloc(&p, kMailCap + 64, hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable) != hipSuccess) {
@@ -202,8 +204,17 @@ static Mailbox *mailbox_of(hipStream_t st)
     m->hseq = reinterpret_cast<u32 *>(m->h + kMailCap);
     m->dseq = reinterpret_cast<u32 *>(m->d + kMailCap);
     *m->hseq = 0;
-    boxes[st] = m;
+    g_boxes[st] = m;
     return m;
+}
+void mail_release(hipStream_t st)
+{
+    std::lock_guard<std::mutex> lk(g_boxes_mu);
+    auto it = g_boxes.find(st);
+    if (it == g_boxes.end()) return;
+    (void)hipHostFree(it->second->h);
+    delete it->second;
+    g_boxes.erase(it);
 }
 int mail_fetch(hipStream_t st, const MailSeg *segs, int nseg)
 {

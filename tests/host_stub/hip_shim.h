@@ -10,6 +10,7 @@
 // (peer copies, per-device lanes) run.  Test infrastructure only: nothing under rust-compression_amd/ includes it
 // unless BZ_HOST_PIPELINE_TEST is defined by the test's own build line.
 #pragma once
+#include <atomic>
 #include <condition_variable>
 #include <cstdint>
 #include <cstdlib>
@@ -31,6 +32,30 @@ inline int &current_device()
 {
     static thread_local int d = 0;
     return d;
+}
+// (tests/test_devbuf_host.py) blocks handed out by hipMalloc / hipHostMalloc and not freed yet, and a switch that makes
+// the next N hipMalloc calls fail
+inline std::atomic<long> &live_allocs()
+{
+    static std::atomic<long> n{0};
+    return n;
+}
+inline std::atomic<int> &fail_next_mallocs()
+{
+    static std::atomic<int> n{0};
+    return n;
+}
+inline hipError_t alloc(void **p, size_t n)
+{
+    *p = malloc(n ? n : 1);
+    if (!*p) return hipErrorOutOfMemory;
+    ++live_allocs();
+    return hipSuccess;
+}
+inline void release(void *p)
+{
+    if (p) --live_allocs();
+    free(p);
 }
 struct Event {
     std::mutex mu;
@@ -100,10 +125,18 @@ inline hipError_t hipGetLastError() { return hipSuccess; }
 inline const char *hipGetErrorString(hipError_t) { return "hip shim error"; }
 inline hipError_t hipDeviceCanAccessPeer(int *can, int a, int b) { *can = a != b; return hipSuccess; }
 inline hipError_t hipDeviceEnablePeerAccess(int, unsigned) { return hipSuccess; }
-inline hipError_t hipMalloc(void **p, size_t n) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-inline hipError_t hipFree(void *p) { free(p); return hipSuccess; }
-inline hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-inline hipError_t hipHostFree(void *p) { free(p); return hipSuccess; }
+inline hipError_t hipMalloc(void **p, size_t n)
+{
+    if (hipshim::fail_next_mallocs() > 0) {
+        --hipshim::fail_next_mallocs();
+        *p = nullptr;
+        return hipErrorOutOfMemory;
+    }
+    return hipshim::alloc(p, n);
+}
+inline hipError_t hipFree(void *p) { hipshim::release(p); return hipSuccess; }
+inline hipError_t hipHostMalloc(void **p, size_t n, unsigned) { return hipshim::alloc(p, n); }
+inline hipError_t hipHostFree(void *p) { hipshim::release(p); return hipSuccess; }
 inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = new hipshim::Stream(); return hipSuccess; }
 inline hipError_t hipStreamDestroy(hipStream_t s) { delete s; return hipSuccess; }
 inline hipError_t hipStreamSynchronize(hipStream_t s) { if (s) s->drain(); return hipSuccess; }

@@ -856,3 +856,46 @@ def test_period_round_in_mixed_batches(pkg, oracle):
             assert rounds <= most, (name, rounds)  # (without the round: 14, the doubling runs to the blocks' length)
     finally:
         eng.close()
+
+
+def test_engine_lifecycle_frees_and_recreates(pkg, oracle, capfd):
+    """Engines made and destroyed in one process: six times an engine of 8 blocks in flight encodes 1.2 MB of text at
+    level 1 (13 blocks: two batches, the second one smaller than the first) and is closed -- its device buffers, its
+    streams and their mailboxes go with it, and the next engine may be handed the same stream handles.  One more engine
+    then encodes, decodes its own output (the decode workspace) and runs a Deflate encode (the Deflate workspace) before
+    it is closed and the cached resources are released.  Every stream is the oracle's, and the library (whose messages
+    all begin with its name) says nothing on stderr."""
+    import torch
+    import corpus
+    d = corpus.chapter(2, 1_200_000)
+    want = oracle.encode(d, 1)
+    tin = torch.frombuffer(bytearray(d) + bytearray(64), dtype=torch.uint8).cuda()
+    cap = (pkg.encode_bound(len(d)) + 15) & ~15
+    tout = torch.empty(cap, dtype=torch.uint8, device="cuda")
+    for cycle in range(6):
+        e = pkg.GpuEngine(0, 8)
+        try:
+            n = e.encode_device(1, tin.data_ptr(), len(d), tout.data_ptr(), cap)
+            assert len(e.block_stats()) > 8
+            assert bytes(tout[:n].cpu().numpy()) == want, cycle
+        finally:
+            e.close()
+    e = pkg.GpuEngine(0, 8)
+    try:
+        n = e.encode_device(1, tin.data_ptr(), len(d), tout.data_ptr(), cap)
+        z = bytes(tout[:n].cpu().numpy())
+        assert z == want
+        tz = torch.frombuffer(bytearray(z) + bytearray(64), dtype=torch.uint8).cuda()
+        tback = torch.empty(len(d) + 64, dtype=torch.uint8, device="cuda")
+        m, verdict = e.decode_device(tz.data_ptr(), len(z), tback.data_ptr(), len(d) + 64)
+        assert (bytes(tback[:m].cpu().numpy()), verdict) == oracle.decode(z) == (d, 0)
+        dcap = (pkg.deflate_bound(len(d)) + 64 + 15) & ~15
+        tdf = torch.empty(dcap, dtype=torch.uint8, device="cuda")
+        k = e.deflate_encode_device(pkg.ZLIB, tin.data_ptr(), len(d), tdf.data_ptr(), dcap)
+        assert bytes(tdf[:k].cpu().numpy()) == oracle.deflate_encode(d, pkg.ZLIB)
+    finally:
+        e.close()
+    pkg.release_cached_resources()
+    torch.cuda.synchronize()
+    err = capfd.readouterr().err
+    assert "bz2_mi355x" not in err, err[-2000:]
