@@ -20,6 +20,8 @@ constexpr u32 kSortTile = 8192;             // elements per radix tile: 8 waves 
 constexpr u32 kSortThreads = 512;
 constexpr u32 kTilesPerBlock = 110;         // ceil(900000 / 8192)
 constexpr u32 kSlot = kTilesPerBlock * kSortTile; // 901120: per-block stride of the u32 work arrays
+constexpr u32 kPtSlot = kSlot / 8u * 10u;   // 1126400: per-block stride of the packed text (up to 10 bits per position)
+constexpr u32 kPairWords = 65536u / 32u;    // words of a block's map of the byte pairs in use
 constexpr u32 kMaxBins = 2048;              // 11-bit digits for the initial 32-bit key sort
 constexpr u32 kPerK = 8;                    // distances per block the period round orders copies by (round 5: one before)
 constexpr u32 kGSize = 50;                  // BZ_G_SIZE, src/bzip2/mod.rs:20
@@ -342,10 +344,12 @@ struct BwtArgs {
     u32 *loc_stats;                  // [64] k_surv_local's counters (LOC_STAT_*), the phase timers of the instrumented builds
     u8 *L;                           // [nb * kSlot] last column, written as rotations become final
     u32 *orig_ptr;                   // [nb] position of rotation 0 in the sorted order
-    u8 *ptext;                       // [nb * kSlot] the blocks' symbols packed for pkey() (k_pack_text); borrowed: the
-                                     //   MTF stage's rank bytes live here once the sort is done
+    u8 *ptext;                       // [nb * kPtSlot] the blocks' symbols (or symbol pairs) packed for pkey() (k_pack_text);
+                                     //   once the init is over the period and link rounds keep a byte per list position
+                                     //   here (`impure`, stride kSlot)
+    u32 *pair_bits;                  // [nb][kPairWords] the byte pairs (T[i], T[i+1]) in use; nullptr: symbol keys only
     const u8 *sym_code;              // [nb][256] byte -> code (rank among the bytes in use)
-    const u8 *keyinfo;               // [nb] KeyInfo {bits per symbol, symbols per key}
+    const u8 *keyinfo;               // [nb] KeyInfo {bits per code, symbols per key, form}
     // fused radix passes (no per-pass histogram kernel; tile offsets by decoupled look-back)
     u32 *gh_tiles;                   // [nb][kTilesPerBlock][3][kMaxBins] per-tile digit counts of a whole phase
     u32 *gbase;                      // [nb][3][kMaxBins] digits smaller, per digit position

@@ -49,6 +49,13 @@ static void spans_collect(bz_gpu_engine *g)
     g->t_stage[5] = g->t_stage[0] + g->t_stage[1] + g->t_stage[2] + g->t_stage[3] + g->t_stage[4];
 }
 
+// BZ_PAIR_KEYS=0: every block sorts by keys of single symbols, as before round 7 (tests/test_gpu_pair_keys.py)
+static bool pair_keys_wanted()
+{
+    static const bool on = !(getenv("BZ_PAIR_KEYS") && atoi(getenv("BZ_PAIR_KEYS")) == 0);
+    return on;
+}
+
 // BZ_ONESWEEP=0: the three-kernel radix passes from the start (tests/test_gpu_parity.py::test_radix_pass_flavours_agree)
 static bool fused_wanted()
 {
@@ -99,6 +106,10 @@ static constexpr WsBuf kWorkspace[] = {
     {&bz_gpu_engine::summ_len, (size_t)kMaxMtfChunks * 2, 0, false},
     {&bz_gpu_engine::init_state, (size_t)kMaxMtfChunks * 256, 0, false},
     {&bz_gpu_engine::rank8, kSlot, 64, false},
+    // the packed text has its own buffer: in the pair form it takes up to 10 bits per position, more than rank8's bytes
+    // (which it borrowed until round 7); `impure` of the period and link rounds still fits, its stride is kSlot
+    {&bz_gpu_engine::ptext, kPtSlot, 64, false},
+    {&bz_gpu_engine::pair_bits, (size_t)kPairWords * 4, 0, false},
     {&bz_gpu_engine::ztile_last, (size_t)kTilesPerBlock * 4, 0, false},
     {&bz_gpu_engine::ztile_cnt, (size_t)kTilesPerBlock * 4, 0, false},
     {&bz_gpu_engine::zstate, (size_t)kTilesPerBlock * 16, 0, false},
@@ -123,9 +134,9 @@ static constexpr WsBuf kWorkspace[] = {
     {&bz_gpu_engine::tile_state, (size_t)kTilesPerBlock * kMaxBins * 4, 0, true},
     {&bz_gpu_engine::tickets, 0, (size_t)kSortEpochs * 8 * 4 + 64, true},
 };
-// Per block in flight, before DevBuf's slack of one eighth: 34 179 820 bytes (30 550 764 without the fused radix passes).
+// Per block in flight, before DevBuf's slack of one eighth: 35 314 412 bytes (31 685 356 without the fused radix passes).
 // The batch workspace holds `ws_blocks` blocks in flight: as many as the call at hand needs (up to max_blocks, the batch
-// size), grown when a later call needs more -- a context that only ever sees small inputs does not take 34.2 MB x max_blocks.
+// size), grown when a later call needs more -- a context that only ever sees small inputs does not take 35.3 MB x max_blocks.
 static int ensure_workspace(bz_gpu_engine *g, size_t need_blocks)
 {
     if (need_blocks > g->max_blocks) need_blocks = g->max_blocks;
@@ -693,7 +704,8 @@ static BwtArgs make_bwt_args(bz_gpu_engine *g, u32 nb)
     x.loc_stats = g->pb_gate.as<u32>() + g->ws_blocks; // (behind the gates)
     x.L = g->L.as<u8>();
     x.orig_ptr = g->orig_ptr.as<u32>();
-    x.ptext = g->rank8.as<u8>(); // (free until launch_mtf writes the batch's ranks)
+    x.ptext = g->ptext.as<u8>();
+    x.pair_bits = pair_keys_wanted() ? g->pair_bits.as<u32>() : nullptr;
     x.sym_code = g->sym_code.as<u8>();
     x.keyinfo = g->keyinfo.as<u8>();
     x.gh_tiles = g->gh_tiles.as<u32>();
@@ -788,7 +800,7 @@ static int sort_batch(bz_gpu_engine *g, const BwtArgs &ba, u32 max_n, u64 total_
     bool wide = false;
     u32 min_chars = 8;
     for (u32 i = 0; i < ba.nb; ++i) {
-        if (ki[(size_t)i * 4] >= 8) wide = true;
+        if (ki[(size_t)i * 4 + 2] == 0 && ki[(size_t)i * 4] >= 8) wide = true; // (a pair-form key is never wider than 30 bits)
         if (ki[(size_t)i * 4 + 1] < min_chars) min_chars = ki[(size_t)i * 4 + 1];
     }
     return run_bwt(g->st, ba, max_n, total_n, g->h_active, sorted, prof, round_active, wide, min_chars);

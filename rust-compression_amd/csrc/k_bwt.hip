@@ -16,6 +16,9 @@
 //            the sequence stably by key(j) again (3 more passes): the result is ordered by the
 //            first 2c symbols without ever holding more than 8 bytes per element.  Text of 36
 //            symbols gets c = 5, i.e. the first 10 bytes, from six 10-bit passes.
+//            (round 7) A block that uses at most 1024 of its byte PAIRS keeps the code of the pair (T[j], T[j+1])
+//            per position instead, p = ceil(log2(#pairs in use)) bits, and a key is the codes at j, j+2, ..: text
+//            of 36 symbols uses ~800 pairs and gets c = 6 -- the first 12 bytes from the same six passes (pkey).
 //            Groups of equal 2c-prefixes get rank R[j] = group head position,
 //            bit31 = "group is a singleton, rotation j is final".
 //   round h: (Manber-Myers step) walk SA in order, i -> j = SA[i]-h; the non-final j
@@ -59,24 +62,59 @@ template <int SRC> struct src_is_list {
 
 // per-block key geometry, produced by k_key_params
 struct KeyInfo {
-    u8 bits;   // bits per re-coded symbol
+    u8 bits;   // bits per code of the packed string: a re-coded symbol, or (pair form) a pair of symbols
     u8 chars;  // symbols per key
-    u8 pad[2];
+    u8 form;   // 0: one code per symbol; 1: one code per PAIR of neighbouring symbols (round 7)
+    u8 pad;
 };
 
 // key(j): `chars` re-coded symbols of the rotation starting at j, first symbol most significant.
-// The block's symbols are kept a second time as a PACKED string (k_pack_text): `bits` bits per symbol, first
-// symbol in the most significant bits of the first byte, and the first 16 symbols once more behind the last one
-// (rotations are cyclic).  A key is then `chars * bits` consecutive bits of that string: one unaligned 8-byte
-// load, a byte swap and a shift -- instead of three dword loads, a look-up per symbol in a byte -> code table in
-// LDS and the shifts that put the codes together (and 0.68 MB per block in the L2 instead of 0.9).
-__device__ __forceinline__ u32 pkey(const u8 *__restrict__ pt, u32 j, u32 bits, u32 chars)
+// The block's symbols are kept a second time as a PACKED string (k_pack_text): `bits` bits per position, first
+// position in the most significant bits of the first byte, and the first 16 positions once more behind the last one
+// (rotations are cyclic).  One unaligned 8-byte load and a byte swap bring every bit of a key -- instead of three
+// dword loads, a look-up per symbol in a byte -> code table in LDS and the shifts that put the codes together.
+//   symbol form: position j holds the code of T[j]; a key is `chars * bits` consecutive bits (0.68 MB of text in the L2)
+//   pair form  : position j holds the dense, order-preserving code of the pair (T[j], T[j+1]); the codes at j, j+2, ..
+//                (chars / 2 of them: three, or four when bits <= 7) put together compare like `chars` symbols, and a
+//                text block uses so few of its alphabet's pairs that this is one symbol more per 30-bit key.  The load
+//                suffices: the last code ends (chars - 1) * bits + 7 <= 57 bits behind the load's first.
+// The form is a property of the block, so the branch is uniform for a workgroup.  pkey_rows takes it ONCE for the
+// rows of a lane: a branch per row would make every row wait for its own load (the rows' loads go out back to back).
+template <bool PAIR>
+__device__ __forceinline__ u32 pkey_form(const u8 *__restrict__ pt, u32 j, KeyInfo ki)
 {
-    const u32 bitpos = j * bits, kb = bits * chars; // (kb <= 32, bitpos < 2^23)
+    const u32 bits = ki.bits, bitpos = j * bits; // (bitpos < 2^24: 900 016 positions of at most 10 bits)
     u64 v;
     __builtin_memcpy(&v, pt + (bitpos >> 3), 8); // (one global_load_dwordx2: unaligned access is on for HSA code objects)
     v = __builtin_bswap64(v);
-    return (u32)(v >> (64u - (bitpos & 7u) - kb)) & (u32)((1ull << kb) - 1ull);
+    if (!PAIR) {
+        const u32 kb = bits * ki.chars; // (kb <= 32)
+        return (u32)(v >> (64u - (bitpos & 7u) - kb)) & (u32)((1ull << kb) - 1ull);
+    }
+    v <<= (bitpos & 7u);
+    const u32 m = (1u << bits) - 1u;
+    u32 key = ((u32)(v >> (64u - bits)) << (2u * bits)) | (((u32)(v >> (64u - 3u * bits)) & m) << bits) |
+              ((u32)(v >> (64u - 5u * bits)) & m);
+    // the fourth code, when there is one (chars == 8, bits <= 7) -- in arithmetic: a branch here, uniform as it is, would
+    // again stand between the rows' loads
+    const bool four = ki.chars == 8;
+    return (key << (four ? bits : 0u)) | ((u32)(v >> (four ? 64u - 7u * bits : 0u)) & (four ? m : 0u));
+}
+__device__ __forceinline__ u32 pkey(const u8 *__restrict__ pt, u32 j, KeyInfo ki)
+{
+    return ki.form ? pkey_form<true>(pt, j, ki) : pkey_form<false>(pt, j, ki);
+}
+// key[r] = key(j[r]) for the rows of a lane (`key` and `j` may be the same array)
+template <int ROWS>
+__device__ __forceinline__ void pkey_rows(const u8 *__restrict__ pt, const u32 (&j)[ROWS], KeyInfo ki, u32 (&key)[ROWS])
+{
+    if (ki.form) {
+#pragma unroll
+        for (u32 r = 0; r < (u32)ROWS; ++r) key[r] = pkey_form<true>(pt, j[r], ki);
+    } else {
+#pragma unroll
+        for (u32 r = 0; r < (u32)ROWS; ++r) key[r] = pkey_form<false>(pt, j[r], ki);
+    }
 }
 
 // The new-group starts of a refined list as a BITMAP: one 64-bit word per row of 64 list elements (the ballot a
@@ -215,10 +253,10 @@ __device__ __forceinline__ u32 fetch_rows(const BwtArgs &a, u32 lb, const u8 *__
         for (u32 r = 0; r < (u32)ROWS; ++r) {
             const u32 idx = first + r * 64u;
             const u32 c = idx < cnt ? idx : cnt - 1u;
-            key[r] = pkey(pt, c, ki.bits, ki.chars);
             val[r] = c;
             ok |= (idx < cnt ? 1u : 0u) << r;
         }
+        pkey_rows(pt, val, ki, key);
     } else if (SRC == SRC_WALK) {
         // phase B of the init: walk the key order of phase A, step back `chars` symbols
         const u32 cm = ki.chars % n;
@@ -230,8 +268,7 @@ __device__ __forceinline__ u32 fetch_rows(const BwtArgs &a, u32 lb, const u8 *__
             val[r] = (s >= cm) ? s - cm : s + n - cm;
             ok |= (idx < cnt ? 1u : 0u) << r;
         }
-#pragma unroll
-        for (u32 r = 0; r < (u32)ROWS; ++r) key[r] = pkey(pt, val[r], ki.bits, ki.chars);
+        pkey_rows(pt, val, ki, key);
     } else if (SRC == SRC_TEXTK) {
 #pragma unroll
         for (u32 r = 0; r < (u32)ROWS; ++r) {
@@ -404,7 +441,7 @@ __global__ __launch_bounds__(kSortThreads) void k_radix_hist(BwtArgs a, u32 shif
     const u32 start = tile * kSortTile;
     if (start >= cnt) return;
     const u8 *text = a.rle + d.rle_off;
-    const u8 *pt = a.ptext + (size_t)lb * kSlot;
+    const u8 *pt = a.ptext + (size_t)lb * kPtSlot;
     const KeyInfo ki = reinterpret_cast<const KeyInfo *>(a.keyinfo)[lb];
     const u32 hm = (SRC == SRC_MM || SRC == SRC_MMK || SRC == SRC_SURV) ? (((u32)ki.chars * 2u) << h) % n
                    : (SRC == SRC_PERJ ? (u32)((((u64)ki.chars * 2u) << h) < n ? (((u64)ki.chars * 2u) << h) : n) : 0u);
@@ -531,7 +568,7 @@ __global__ __launch_bounds__(kSortThreads) void k_radix_scatter(BwtArgs a, u32 s
     const u32 start = tile * kSortTile;
     if (start >= cnt) return;
     const u8 *text = a.rle + d.rle_off;
-    const u8 *pt = a.ptext + (size_t)lb * kSlot;
+    const u8 *pt = a.ptext + (size_t)lb * kPtSlot;
     const KeyInfo ki = reinterpret_cast<const KeyInfo *>(a.keyinfo)[lb];
     const u32 hm = (SRC == SRC_MM || SRC == SRC_MMK || SRC == SRC_SURV) ? (((u32)ki.chars * 2u) << h) % n : 0u;
     const size_t base = (size_t)lb * kSlot;
@@ -660,7 +697,7 @@ __global__ __launch_bounds__(kSortThreads) void k_ghist_text(BwtArgs a, u32 *__r
     const u32 start0 = tile * kGhSpan * kSortTile;
     if (start0 >= n) return;
     const u8 *text = a.rle + d.rle_off;
-    const u8 *pt = a.ptext + (size_t)lb * kSlot;
+    const u8 *pt = a.ptext + (size_t)lb * kPtSlot;
     const KeyInfo ki = reinterpret_cast<const KeyInfo *>(a.keyinfo)[lb];
     for (u32 i = threadIdx.x; i < 2 * NB0; i += kSortThreads) (&s_h0[0][0])[i] = 0;
     for (u32 i = threadIdx.x; i < 2 * NB1; i += kSortThreads) (&s_h1[0][0])[i] = 0;
@@ -801,7 +838,7 @@ __global__ __launch_bounds__(TILE / ROWS) void k_radix_scatter_lb(BwtArgs a, u32
     const u32 start = tile * (u32)TILE;
     if (start >= cnt) return;
     const u8 *text = a.rle + d.rle_off;
-    const u8 *pt = a.ptext + (size_t)lb * kSlot;
+    const u8 *pt = a.ptext + (size_t)lb * kPtSlot;
     const KeyInfo ki = reinterpret_cast<const KeyInfo *>(a.keyinfo)[lb];
     const u32 hm = (SRC == SRC_MM || SRC == SRC_MMC || SRC == SRC_MMK || SRC == SRC_SURV) ? (((u32)ki.chars * 2u) << h) % n : 0u;
     const size_t base = (size_t)lb * kSlot;
@@ -1342,7 +1379,7 @@ __global__ __launch_bounds__(kSortThreads) void k_group_flags(BwtArgs a, u32 ste
     const KeyInfo ki = reinterpret_cast<const KeyInfo *>(a.keyinfo)[lb];
     const u32 hm = INIT ? (u32)ki.chars % n : (((u32)ki.chars * 2u) << step) % n;
     const u8 *text = a.rle + d.rle_off;
-    const u8 *pt = a.ptext + (size_t)lb * kSlot;
+    const u8 *pt = a.ptext + (size_t)lb * kPtSlot;
     const size_t base = (size_t)lb * kSlot;
     if (INIT && a.pb_gate[lb] == 0u) K = a.KA; // phase B was done in LDS: phase A's keys are the list's keys
     if (threadIdx.x == 0) {
@@ -1382,9 +1419,8 @@ __global__ __launch_bounds__(kSortThreads) void k_group_flags(BwtArgs a, u32 ste
         if (INIT) {
             // (a table of the packed keys, one gather instead of three plus the re-coding, was measured: the flags
             // gain 0.6 ms, the walk pass loses 2.5 -- the table is 3.6 MB per block against 0.9 MB of text in the L2)
-#pragma unroll
-            for (u32 r = 0; r < 16; ++r) s2[r] = pkey(pt, jj[r], ki.bits, ki.chars);
-            if (need_prev) ps20 = pkey(pt, pj, ki.bits, ki.chars);
+            pkey_rows(pt, jj, ki, s2);
+            if (need_prev) ps20 = pkey(pt, pj, ki);
         } else if (impure) {
             const bool per = a.lin_p[(size_t)lb * kPerK] != 0u;
             const u64 d64 = ((u64)ki.chars * 2u) << step;
@@ -1735,7 +1771,7 @@ __global__ __launch_bounds__(kSortThreads, 4) void k_group_refine(BwtArgs a, u32
     if (start >= cnt) return;
     const KeyInfo ki = reinterpret_cast<const KeyInfo *>(a.keyinfo)[lb];
     const u32 hm = INIT ? (u32)ki.chars % n : (((u32)ki.chars * 2u) << step) % n;
-    const u8 *pt = a.ptext + (size_t)lb * kSlot;
+    const u8 *pt = a.ptext + (size_t)lb * kPtSlot;
     const size_t base = (size_t)lb * kSlot;
     if (INIT && a.pb_gate[lb] == 0u) K = a.KA; // phase B was done in LDS: phase A's keys are the list's keys
     for (u32 i = threadIdx.x; i < 3072u; i += kSortThreads) s_stage[i] = 0; // (s_gh and s_bcnt)
@@ -1787,10 +1823,9 @@ __global__ __launch_bounds__(kSortThreads, 4) void k_group_refine(BwtArgs a, u32
             nj = t >= n ? t - n : t;
         }
         if (INIT) {
-#pragma unroll
-            for (u32 r = 0; r < 16; ++r) s2[r] = pkey(pt, s2[r], ki.bits, ki.chars);
-            if (need_prev) ps20 = pkey(pt, pj, ki.bits, ki.chars);
-            if (need_next) ns20 = pkey(pt, nj, ki.bits, ki.chars);
+            pkey_rows(pt, s2, ki, s2);
+            if (need_prev) ps20 = pkey(pt, pj, ki);
+            if (need_next) ns20 = pkey(pt, nj, ki);
         }
     }
     RF_T(1);
@@ -3036,9 +3071,15 @@ __global__ __launch_bounds__(kSortThreads) void k_period_mark(BwtArgs a, u32 ste
 }
 
 // ---- symbols in use and key geometry (before the sort) ----------------------------------------------
-__global__ __launch_bounds__(kSortThreads) void k_block_symbols(BwtArgs a, u32 *__restrict__ inuse_bits /*[nb][8]*/)
+// pair_bits != nullptr: also the map of the byte pairs (T[i], T[(i + 1) mod n]) in use, 65 536 bits per block, bit
+// (first << 8 | second).  A workgroup keeps its map in LDS and looks at a bit before it sets it -- text has a few
+// hundred pairs, the map is full after a few thousand positions and the rest only read -- and ORs the words that
+// are not zero into the block's map.
+__global__ __launch_bounds__(kSortThreads) void k_block_symbols(BwtArgs a, u32 *__restrict__ inuse_bits /*[nb][8]*/,
+                                                                u32 *__restrict__ pair_bits /*[nb][kPairWords] or null*/)
 {
     __shared__ u32 s_bits[8];
+    __shared__ u32 s_pair[kPairWords];
     u32 tile, lb;
     xcd_remap(gridDim.x, a.nb, tile, lb);
     if (lb == 0xFFFFFFFFu) return;
@@ -3050,8 +3091,9 @@ __global__ __launch_bounds__(kSortThreads) void k_block_symbols(BwtArgs a, u32 *
     const u32 start = tile * kSpan;
     if (start >= n) return;
     const u8 *text = a.rle + d.rle_off;
-    const u8 *pt = a.ptext + (size_t)lb * kSlot;
     if (threadIdx.x < 8) s_bits[threadIdx.x] = 0;
+    if (pair_bits)
+        for (u32 i = threadIdx.x; i < kPairWords; i += kSortThreads) s_pair[i] = 0;
     __syncthreads();
     // 16 bytes per load, from the 16-byte boundary in front of the tile (the image is padded at both ends of a block's
     // bytes by its neighbours or by the buffer's slack); four 64-bit sets, picked with selects
@@ -3059,18 +3101,29 @@ __global__ __launch_bounds__(kSortThreads) void k_block_symbols(BwtArgs a, u32 *
     const uintptr_t p0 = reinterpret_cast<uintptr_t>(text + start);
     const u32 lead = (u32)(p0 & 15u);
     const uint4 *src = reinterpret_cast<const uint4 *>(p0 - lead);
+    const u32 t0 = text[0];
     u64 set[4] = {0, 0, 0, 0};
     for (u32 c = threadIdx.x; c * 16u < lead + cnt; c += kSortThreads) {
         const uint4 v = src[c];
         const u32 w[4] = {v.x, v.y, v.z, v.w};
+        // the byte behind the sixteen: the pair of the last one (the block's first byte behind its last)
+        const u32 behind = start + c * 16u + 16u - lead;
+        const u32 nxt = (pair_bits && behind < n) ? (u32)text[behind] : t0;
 #pragma unroll
         for (u32 k = 0; k < 16; ++k) {
             const u32 pos = c * 16u + k;
             const u32 b = (w[k >> 2] >> ((k & 3u) * 8u)) & 0xFFu;
-            const u64 bit = (pos >= lead && pos < lead + cnt) ? (1ull << (b & 63u)) : 0ull;
+            const bool in = pos >= lead && pos < lead + cnt;
+            const u64 bit = in ? (1ull << (b & 63u)) : 0ull;
             const u32 hi = b >> 6;
 #pragma unroll
             for (u32 q = 0; q < 4; ++q) set[q] |= (hi == q) ? bit : 0ull;
+            if (pair_bits && in) {
+                u32 b2 = (k < 15u) ? ((w[(k + 1u) >> 2] >> (((k + 1u) & 3u) * 8u)) & 0xFFu) : nxt;
+                if (start + (pos - lead) + 1u == n) b2 = t0;
+                const u32 pr = (b << 8) | b2;
+                if (!((s_pair[pr >> 5] >> (pr & 31u)) & 1u)) atomicOr(&s_pair[pr >> 5], 1u << (pr & 31u));
+            }
         }
     }
     u32 seen[8];
@@ -3088,13 +3141,20 @@ __global__ __launch_bounds__(kSortThreads) void k_block_symbols(BwtArgs a, u32 *
     }
     __syncthreads();
     if (threadIdx.x < 8 && s_bits[threadIdx.x]) atomicOr(&inuse_bits[lb * 8 + threadIdx.x], s_bits[threadIdx.x]);
+    if (pair_bits)
+        for (u32 i = threadIdx.x; i < kPairWords; i += kSortThreads)
+            if (s_pair[i]) atomicOr(&pair_bits[(size_t)lb * kPairWords + i], s_pair[i]);
 }
 
 // one 256-thread workgroup per block: byte -> code table (rank among the bytes in use, the
-// reference's unseq2seq, src/bzip2/encoder.rs:304-314) and the key geometry
-__global__ __launch_bounds__(256) void k_key_params(const u32 *__restrict__ inuse_bits, u8 *__restrict__ sym_code,
-                                                     u8 *__restrict__ keyinfo)
+// reference's unseq2seq, src/bzip2/encoder.rs:304-314) and the key geometry.
+// Symbol form: b = ceil(log2 S) bits per symbol, c = 30 / b symbols per key (4 when b = 8).  Pair form, when the block
+// uses P <= 1024 of its byte pairs: p = ceil(log2 P) bits per pair code, c_pair = min(8, 2 * (30 / p)) symbols per key.
+// The block takes the pair form iff that is MORE symbols per key; otherwise it is handled exactly as before round 7.
+__global__ __launch_bounds__(256) void k_key_params(const u32 *__restrict__ inuse_bits, const u32 *__restrict__ pair_bits,
+                                                     u8 *__restrict__ sym_code, u8 *__restrict__ keyinfo)
 {
+    __shared__ u32 s_pairs[4];
     const u32 lb = blockIdx.x;
     const u32 *bits = inuse_bits + lb * 8;
     const u32 v = threadIdx.x;
@@ -3102,6 +3162,13 @@ __global__ __launch_bounds__(256) void k_key_params(const u32 *__restrict__ inus
     for (u32 q = 0; q < (v >> 5); ++q) before += __popc(bits[q]);
     before += __popc(bits[v >> 5] & ((1u << (v & 31u)) - 1u));
     sym_code[(size_t)lb * 256 + v] = (u8)before;
+    if (pair_bits) {
+        u32 mine = 0;
+        for (u32 i = v; i < kPairWords; i += 256u) mine += __popc(pair_bits[(size_t)lb * kPairWords + i]);
+        mine = wave_incl_sum(mine);
+        if ((v & 63u) == 63u) s_pairs[v >> 6] = mine;
+    }
+    __syncthreads();
     if (v == 0) {
         u32 alpha = 0;
         for (u32 q = 0; q < 8; ++q) alpha += __popc(bits[q]);
@@ -3112,18 +3179,35 @@ __global__ __launch_bounds__(256) void k_key_params(const u32 *__restrict__ inus
         KeyInfo ki;
         ki.bits = (u8)nbits;
         ki.chars = (u8)chars;
-        ki.pad[0] = ki.pad[1] = 0;
+        ki.form = 0;
+        ki.pad = 0;
+        if (pair_bits) {
+            const u32 npairs = s_pairs[0] + s_pairs[1] + s_pairs[2] + s_pairs[3];
+            u32 pbits = 1;
+            while (pbits < 11u && (1u << pbits) < npairs) ++pbits;
+            const u32 cpair = 2u * (30u / pbits) < 8u ? 2u * (30u / pbits) : 8u;
+            if (pbits <= 10u && cpair > chars) {
+                ki.bits = (u8)pbits;
+                ki.chars = (u8)cpair;
+                ki.form = 1;
+            }
+        }
         reinterpret_cast<KeyInfo *>(keyinfo)[lb] = ki;
     }
 }
 
-// The block's symbols as a packed string for pkey(): `bits` bits per re-coded symbol, most significant bit first,
-// symbols n .. n+15 = symbols 0 .. 15 of the cyclic text.  A thread packs groups of eight symbols (= `bits` whole
-// bytes); a tile's bytes leave through LDS as dwords.
+// The block as a packed string for pkey(): `bits` bits per position, most significant bit first, positions
+// n .. n+15 = positions 0 .. 15 of the cyclic text.  Symbol form: the code of the position's byte.  Pair form: the rank of
+// the pair (T[i], T[i+1]) among the pairs in use, in (first, second) byte order -- the set bits of the block's pair map
+// in front of its own, from the map and the counts of the words in front (both in LDS).  A thread packs groups of eight
+// positions (= `bits` whole bytes); a tile's bytes leave through LDS as dwords.
 __global__ __launch_bounds__(kSortThreads) void k_pack_text(BwtArgs a, u8 *__restrict__ ptext)
 {
     __shared__ u8 s_code[256];
-    __shared__ u32 s_out[kSortTile / 4]; // 1024 groups x at most 8 bytes
+    __shared__ u32 s_out[kSortTile / 32 * 10]; // 1024 groups x at most 10 bytes
+    __shared__ u32 s_pair[kPairWords];
+    __shared__ u16 s_before[kPairWords];       // (a block in the pair form has at most 1024 pairs)
+    __shared__ u32 s_wsum[kSortThreads / 64];
     u32 tile, lb;
     xcd_remap(gridDim.x, a.nb, tile, lb);
     if (lb == 0xFFFFFFFFu) return;
@@ -3132,40 +3216,77 @@ __global__ __launch_bounds__(kSortThreads) void k_pack_text(BwtArgs a, u8 *__res
     const u32 start = tile * kSortTile;
     if (n == 0 || start >= n + 16u) return;
     const u8 *text = a.rle + d.rle_off;
-    const u32 bits = reinterpret_cast<const KeyInfo *>(a.keyinfo)[lb].bits;
-    for (u32 i = threadIdx.x; i < 256; i += kSortThreads) s_code[i] = a.sym_code[(size_t)lb * 256 + i];
+    const KeyInfo ki = reinterpret_cast<const KeyInfo *>(a.keyinfo)[lb];
+    const u32 bits = ki.bits;
+    const bool pairs = ki.form != 0;
+    if (pairs) {
+        static_assert(kPairWords == 4 * kSortThreads, "four words of the pair map per thread");
+        const uint4 w4 = reinterpret_cast<const uint4 *>(a.pair_bits + (size_t)lb * kPairWords)[threadIdx.x];
+        const u32 w[4] = {w4.x, w4.y, w4.z, w4.w};
+        const u32 mine = __popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]);
+        const u32 inc = wave_incl_sum(mine);
+        if ((threadIdx.x & 63u) == 63u) s_wsum[threadIdx.x >> 6] = inc;
+        __syncthreads();
+        u32 run = inc - mine;
+        for (u32 k = 0; k < (threadIdx.x >> 6); ++k) run += s_wsum[k];
+#pragma unroll
+        for (u32 q = 0; q < 4; ++q) {
+            s_pair[threadIdx.x * 4u + q] = w[q];
+            s_before[threadIdx.x * 4u + q] = (u16)run;
+            run += __popc(w[q]);
+        }
+    } else {
+        for (u32 i = threadIdx.x; i < 256; i += kSortThreads) s_code[i] = a.sym_code[(size_t)lb * 256 + i];
+    }
     __syncthreads();
     u8 *s_bytes = reinterpret_cast<u8 *>(s_out);
 #pragma unroll
     for (u32 h = 0; h < 2; ++h) {
         const u32 g = h * kSortThreads + threadIdx.x; // group inside the tile
         const u32 i0 = start + g * 8u;
-        u32 lo = 0, hi = 0;
-        if (i0 + 8u <= n) {
+        u32 lo = 0, hi = 0, ninth = 0; // the group's eight bytes and the one behind them
+        if (i0 + 9u <= n) {
             const uintptr_t p = reinterpret_cast<uintptr_t>(text + i0);
             const u32 *ap = reinterpret_cast<const u32 *>(p & ~(uintptr_t)3);
             const u32 w0 = ap[0], w1 = ap[1], w2 = ap[2];
             lo = __builtin_amdgcn_alignbyte(w1, w0, (u32)(p & 3u));
             hi = __builtin_amdgcn_alignbyte(w2, w1, (u32)(p & 3u));
+            ninth = (w2 >> (8u * (u32)(p & 3u))) & 0xFFu;
         } else if (i0 < n + 16u) {
-            for (u32 q = 0; q < 8; ++q) {
+            for (u32 q = 0; q < 9; ++q) {
                 const u32 i = i0 + q;
-                const u32 c = (i < n + 16u) ? (u32)text[i < n ? i : (i - n) % n] : 0u;
+                const u32 c = (i < n + 16u + (q >> 3)) ? (u32)text[i < n ? i : (i - n) % n] : 0u;
                 if (q < 4) lo |= c << (8u * q);
-                else hi |= c << (8u * (q - 4u));
+                else if (q < 8) hi |= c << (8u * (q - 4u));
+                else ninth = c;
             }
         }
-        u64 v = 0;
+        // the 8 * bits bits of the group, most significant byte first: two halves of four codes (at most 40 bits each)
+        u64 va = 0, vb = 0;
 #pragma unroll
         for (u32 q = 0; q < 8; ++q) {
             const u32 byte = ((q < 4 ? lo >> (8u * q) : hi >> (8u * (q - 4u)))) & 0xFFu;
-            v = (v << bits) | (u64)s_code[byte];
+            u32 code;
+            if (pairs) {
+                const u32 b2 = q == 7 ? ninth : (((q + 1 < 4 ? lo >> (8u * (q + 1)) : hi >> (8u * (q + 1 - 4u)))) & 0xFFu);
+                const u32 pr = (byte << 8) | b2;
+                code = (u32)s_before[pr >> 5] + __popc(s_pair[pr >> 5] & ((1u << (pr & 31u)) - 1u));
+                if (i0 + q >= n + 16u) code = 0; // (a position nobody reads; its bytes are no pair of the map)
+            } else {
+                code = s_code[byte];
+            }
+            if (q < 4) va = (va << bits) | (u64)code;
+            else vb = (vb << bits) | (u64)code;
         }
-        // the 8 * bits bits of v, most significant byte first
-        for (u32 k = 0; k < bits; ++k) s_bytes[g * bits + k] = (u8)(v >> (8u * (bits - 1u - k)));
+        for (u32 k = 0; k < bits; ++k) {
+            // byte k of (va << 4 * bits | vb), an 8 * bits bit number: its bits [sh, sh + 8), sh = 8 * (bits - 1 - k)
+            const u32 sh = 8u * (bits - 1u - k), half = 4u * bits;
+            u32 o = sh >= half ? (u32)(va >> (sh - half)) : ((u32)(vb >> sh) | (u32)(va << (half - sh)));
+            s_bytes[g * bits + k] = (u8)o;
+        }
     }
     __syncthreads();
-    u32 *dst = reinterpret_cast<u32 *>(ptext + (size_t)lb * kSlot + (size_t)tile * 1024u * bits);
+    u32 *dst = reinterpret_cast<u32 *>(ptext + (size_t)lb * kPtSlot + (size_t)tile * 1024u * bits);
     for (u32 i = threadIdx.x; i < 256u * bits; i += kSortThreads) dst[i] = s_out[i];
 }
 
@@ -3351,8 +3472,9 @@ void launch_block_symbols(hipStream_t st, const BwtArgs &a, u32 *inuse_bits, u8 
 {
     const dim3 grid(kTilesPerBlock, xcd_grid_y(a.nb));
     (void)hipMemsetAsync(inuse_bits, 0, (size_t)a.nb * 8 * sizeof(u32), st);
-    hipLaunchKernelGGL(k_block_symbols, dim3((a.tiles + kSymSpan - 1u) / kSymSpan, xcd_grid_y(a.nb)), dim3(kSortThreads), 0, st, a, inuse_bits);
-    hipLaunchKernelGGL(k_key_params, dim3(a.nb), dim3(256), 0, st, inuse_bits, sym_code, keyinfo);
+    if (a.pair_bits) (void)hipMemsetAsync(a.pair_bits, 0, (size_t)a.nb * kPairWords * sizeof(u32), st);
+    hipLaunchKernelGGL(k_block_symbols, dim3((a.tiles + kSymSpan - 1u) / kSymSpan, xcd_grid_y(a.nb)), dim3(kSortThreads), 0, st, a, inuse_bits, a.pair_bits);
+    hipLaunchKernelGGL(k_key_params, dim3(a.nb), dim3(256), 0, st, inuse_bits, a.pair_bits, sym_code, keyinfo);
     hipLaunchKernelGGL(k_pack_text, grid, dim3(kSortThreads), 0, st, a, a.ptext);
 }
 
