@@ -296,6 +296,10 @@ struct RleBuffers {
     u64 *total;       // [1]
     u64 *cut_result;  // [3] number of blocks, input bytes consumed, tail-block flag
     u64 *scan_part;   // [ntiles / 1024 + 2] workgroup totals of the tile scans
+    // k_rle_onepass (one look-back word per span of eight tiles: epoch | state | value)
+    u32 *lb_ctl;      // [4] spans handed out, a look-back gave up; cleared before every launch
+    u64 *lb_rs;       // [spans] latest run start (+ 1) up to the span's end
+    u64 *lb_off;      // [spans] image bytes up to the span's end
 };
 
 // the cuts from tables (k_rle1.hip, "kernels H"); offsets are those of the image of the WHOLE input
@@ -524,6 +528,9 @@ enum KernelId {
     KID_DEC_PLACE,   // rank_samples + seg_copy + walk_write + fixups
     KID_DEC_RLE,     // rle_sub + rle_chain + rle_expand
     KID_DEC_CRC,
+    // RLE1 front end (k_rle1.hip): which of its two forms wrote the image
+    KID_RLE_ONEPASS,
+    KID_RLE_SCATTER,
     KID_COUNT
 };
 struct KernelProf {
@@ -556,6 +563,10 @@ void launch_rle_prefix(hipStream_t st, u64 tb, u64 t1, const RleBuffers &rb, boo
 void launch_rle_cuts(hipStream_t st, const u8 *d_in, u64 n, u64 tb, u64 t1, u64 in_begin, const RleBuffers &rb,
                      u32 block_max_len, int emit_tail, BlockDesc *d_blocks, u32 max_blocks);
 void launch_rle_image(hipStream_t st, const u8 *d_in, u64 n, u64 tb, u64 t1, u64 in_begin, const RleBuffers &rb, u8 *d_rle);
+u64 rle_onepass_spans(u64 ntiles);
+u32 rle_onepass_epochs();
+void launch_rle_onepass(hipStream_t st, const u8 *d_in, u64 n, u64 ntiles, u32 epoch, const u32 *crc_tab, const u32 *xp16,
+                        const RleBuffers &rb, u8 *d_rle, i64 *d_out_last);
 u64 cut_table_entries(const CutPlan &pl);
 void cut_groups(const CutPlan &pl, u64 *g_lo, u64 *g_hi, u64 *entries);
 u32 cut_seg_cap();

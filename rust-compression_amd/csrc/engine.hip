@@ -257,7 +257,68 @@ static RleBuffers rle_buffers(bz_gpu_engine *g)
     rb.total = g->scal.as<u64>();
     rb.cut_result = g->scal.as<u64>() + 2;
     rb.scan_part = g->scan_part.as<u64>();
+    rb.lb_ctl = g->rle_lb.as<u32>();
+    rb.lb_rs = g->rle_lb.p ? reinterpret_cast<u64 *>(g->rle_lb.as<u8>() + 64) : nullptr;
+    rb.lb_off = g->rle_lb.p ? rb.lb_rs + g->rle_lb_spans : nullptr;
     return rb;
+}
+
+// BZ_RLE_ONEPASS=0: the three-kernel front end from the start; BZ_RLE_ONEPASS_FAILTEST=1: the host treats the first
+// one-pass split of every engine as failed and redoes it (tests/test_gpu_rle_onepass.py)
+static bool onepass_wanted()
+{
+    static const bool on = !(getenv("BZ_RLE_ONEPASS") && atoi(getenv("BZ_RLE_ONEPASS")) == 0);
+    return on;
+}
+static bool onepass_failtest()
+{
+    static const bool on = getenv("BZ_RLE_ONEPASS_FAILTEST") && atoi(getenv("BZ_RLE_ONEPASS_FAILTEST")) != 0;
+    return on;
+}
+// the image by the three-kernel path (the profile tells the two forms of the front end apart)
+static void image_launch(bz_gpu_engine *g, hipStream_t st, u64 tb, u64 t1, u64 in_begin, const RleBuffers &rb, u8 *d_rle)
+{
+    if (t1 <= tb) return;
+    const int pi = g->prof.begin(st, KID_RLE_SCATTER, std::min<u64>(g->n_in, t1 * (u64)kRleTile) - tb * (u64)kRleTile);
+    launch_rle_image(st, g->d_in, g->n_in, tb, t1, in_begin, rb, d_rle);
+    g->prof.end(st, pi);
+}
+// The front end in one pass over the whole input: tables, image (g->rle, sized by RLE1's bound: the image is written
+// before its length reaches the host) and *last.  false in *done: not taken, or it failed and the engine is off it.
+static int onepass_split(bz_gpu_engine *g, u64 ntiles, i64 *d_last, i64 *last, bool *done)
+{
+    *done = false;
+    const u64 n = g->n_in, spans = rle_onepass_spans(ntiles);
+    if (g->rle_lb.ensure(64 + spans * 16) || g->rle.ensure(n + n / 4 + 256)) {
+        (void)hipGetLastError(); // (the three kernels need neither)
+        return BZ_OK;
+    }
+    // (a fresh or regrown buffer holds anything, and so may a tag of 65 535 launches ago: clear, and count from 1)
+    if (g->rle_lb_spans < spans || g->rle_epoch == 0 || g->rle_epoch >= rle_onepass_epochs()) {
+        g->rle_lb_spans = (g->rle_lb.cap - 64) / 16;
+        HIPCHK(hipMemsetAsync(g->rle_lb.p, 0, g->rle_lb.cap, g->st));
+        g->rle_epoch = 0;
+    }
+    ++g->rle_epoch;
+    const RleBuffers rb = rle_buffers(g);
+    const int pi = g->prof.begin(g->st, KID_RLE_ONEPASS, n);
+    launch_rle_onepass(g->st, g->d_in, n, ntiles, g->rle_epoch, g->crc_tab.as<u32>(), g->xp16.as<u32>(), rb, g->rle.as<u8>(), d_last);
+    g->prof.end(g->st, pi);
+    u32 ctl[2] = {0, 0};
+    u64 total = 0;
+    MAILCHK(g->st, {last, d_last, 8}, {&total, rb.total, 8}, {ctl, rb.lb_ctl, 8});
+    HIPCHK(hipGetLastError());
+    if (ctl[0] != (u32)spans || ctl[1] != 0 || onepass_failtest()) {
+        fprintf(stderr, "bz2_mi355x: the one-pass RLE1 front end did not complete (%u of %llu spans, error word %u); the three kernels take over\n",
+                ctl[0], (unsigned long long)spans, ctl[1]);
+        g->rle_onepass_broken = true;
+        g->rle_epoch = 0; // (words of a launch that stopped half way: cleared before anybody reads them again)
+        *last = -1;
+        return BZ_OK;
+    }
+    g->onepass_total = total;
+    *done = true;
+    return BZ_OK;
 }
 
 // ---- the split, in three steps (a slab of tiles per rank; one rank = the whole input) ------------
@@ -289,11 +350,27 @@ extern "C" int bz_gpu_partition_slab_begin(bz_gpu_engine *g, int level, const vo
         (rc = g->sub_rs.ensure(ntiles * 128)) || (rc = g->scal.ensure(128)) ||
         (rc = g->scan_part.ensure((ntiles / 1024 + 2) * 8)))
         return rc;
-    const RleBuffers rb = rle_buffers(g);
     const int sp = span_begin(g, 0);
+    i64 *d_last = reinterpret_cast<i64 *>(g->scal.as<u64>() + 8);
+    // one engine codes the whole input: scan, carries, counts, offsets and the image in one pass over it
+    g->onepass_done = false;
+    if (tile0 == 0 && tile1 == ntiles && onepass_wanted() && !g->rle_onepass_broken) {
+        i64 last = -1;
+        bool done = false;
+        if ((rc = onepass_split(g, ntiles, d_last, &last, &done)) != BZ_OK) {
+            span_end(g, sp);
+            return rc;
+        }
+        if (done) {
+            g->onepass_done = true;
+            span_end(g, sp);
+            if (slab_last_start) *slab_last_start = last;
+            return BZ_OK;
+        }
+    }
+    const RleBuffers rb = rle_buffers(g);
     launch_rle_scan(g->st, g->d_in, n, tile0, tile1, 0, g->crc_tab.as<u32>(), g->xp16.as<u32>(), rb);
     // the range's last run start falls out of the carry scan (its carries are redone in _count)
-    i64 *d_last = reinterpret_cast<i64 *>(g->scal.as<u64>() + 8);
     if (tile1 > tile0) {
         launch_slab_last(g->st, rb, tile0, tile1, d_last);
         i64 last = -1;
@@ -312,6 +389,8 @@ extern "C" int bz_gpu_partition_slab_count(bz_gpu_engine *g, int64_t carry_run)
     if (!g) return BZ_E_PARAM;
     HIPCHK(hipSetDevice(g->device));
     if (g->slab_t1 <= g->slab_t0) return BZ_OK;
+    if (g->onepass_done && carry_run == -1) return BZ_OK; // (k_rle_onepass wrote the carries and the counts)
+    g->onepass_done = false;
     const RleBuffers rb = rle_buffers(g);
     const int sp = span_begin(g, 0);
     // (the run start live at the first byte BEHIND the slab goes to carry_in[slab_t1]: the cut tables look at that tile)
@@ -440,9 +519,14 @@ static int slab_cuts(bz_gpu_engine *g, uint64_t start_in, int is_last, bool imag
         launch_rle_scan(g->st, g->d_in, n, tb, t0, start_in, g->crc_tab.as<u32>(), g->xp16.as<u32>(), rb);
         launch_rle_count(g->st, g->d_in, n, tb, t0, start_in, -1, rb, nullptr);
     }
-    launch_rle_prefix(g->st, tb, t1, rb);
-    u64 total = 0;
-    MAILCHK(g->st, {&total, rb.total, 8});
+    // (the one pass has written the offsets and the image, and its total came with its tickets)
+    const bool onepass = g->onepass_done && start_in == 0 && t0 == 0;
+    u64 total = g->onepass_total;
+    if (!onepass) {
+        g->onepass_done = false;
+        launch_rle_prefix(g->st, tb, t1, rb);
+        MAILCHK(g->st, {&total, rb.total, 8});
+    }
     const size_t max_blocks = (size_t)(total / block_max_len + 2);
     int rc;
     if ((rc = g->rle.ensure(total + 256)) || (rc = g->blocks_all.ensure(max_blocks * sizeof(BlockDesc))) ||
@@ -455,10 +539,14 @@ static int slab_cuts(bz_gpu_engine *g, uint64_t start_in, int is_last, bool imag
     // From the first byte of the input every cut is one of 4 j + 1 known candidates: the tables (k_rle1.hip, "kernels
     // H") answer them all at once; the chain kernel is what a caller with a start_in of its own gets, and the fallback.
     const bool tables = start_in == 0 && t0 == 0 && cut_tables_enabled();
+    if (onepass) {
+        sc.image_done = true;
+        image_beside = false;
+    }
     if (image_beside) {
         if (!g->ev_aux) HIPCHK(hipEventCreateWithFlags(&g->ev_aux, hipEventDisableTiming));
         if (tables) { // (the table kernels are small launches: the image goes first and they run beside it)
-            launch_rle_image(g->st2, g->d_in, n, tb, t1, start_in, rb, g->rle.as<u8>());
+            image_launch(g, g->st2, tb, t1, start_in, rb, g->rle.as<u8>());
             HIPCHK(hipEventRecord(g->ev_aux, g->st2));
             sc.image_done = true;
         }
@@ -478,7 +566,7 @@ static int slab_cuts(bz_gpu_engine *g, uint64_t start_in, int is_last, bool imag
         launch_rle_cuts(g->st, g->d_in, n, tb, t1, start_in, rb, block_max_len, is_last ? 1 : 0,
                         g->blocks_all.as<BlockDesc>(), (u32)max_blocks);
         if (image_beside && !sc.image_done) {
-            launch_rle_image(g->st2, g->d_in, n, tb, t1, start_in, rb, g->rle.as<u8>());
+            image_launch(g, g->st2, tb, t1, start_in, rb, g->rle.as<u8>());
             HIPCHK(hipEventRecord(g->ev_aux, g->st2));
             sc.image_done = true;
         }
@@ -501,7 +589,7 @@ static int slab_image(bz_gpu_engine *g, SlabCuts &sc)
     if (!sc.pending) return BZ_OK;
     sc.pending = false;
     const RleBuffers rb = rle_buffers(g);
-    if (!sc.image_done) launch_rle_image(g->st, g->d_in, g->n_in, sc.tb, g->slab_t1, sc.start_in, rb, g->rle.as<u8>());
+    if (!sc.image_done) image_launch(g, g->st, sc.tb, g->slab_t1, sc.start_in, rb, g->rle.as<u8>());
     const size_t nb = sc.nb;
     g->h_blocks.resize(nb);
     g->h_crc.resize(nb);
@@ -534,6 +622,7 @@ static int slab_spec_total(bz_gpu_engine *g, SlabSpec &sp)
     sp = SlabSpec();
     if (g->n_in == 0) return BZ_OK;
     HIPCHK(hipSetDevice(g->device));
+    g->onepass_done = false; // (a rank of a sharded job lays its image out behind a halo: the slab's own offsets and image)
     const RleBuffers rb = rle_buffers(g);
     const int span = span_begin(g, 0);
     launch_rle_prefix(g->st, g->slab_t0, g->slab_t1, rb);
@@ -556,7 +645,7 @@ static int slab_spec_tables(bz_gpu_engine *g, SlabSpec &sp, u64 g_base)
     const RleBuffers rb = rle_buffers(g);
     const int span = span_begin(g, 0);
     if (!g->ev_aux) HIPCHK(hipEventCreateWithFlags(&g->ev_aux, hipEventDisableTiming));
-    launch_rle_image(g->st2, g->d_in, g->n_in, g->slab_t0, g->slab_t1, 0, rb, g->rle.as<u8>() + sp.halo_cap);
+    image_launch(g, g->st2, g->slab_t0, g->slab_t1, 0, rb, g->rle.as<u8>() + sp.halo_cap);
     HIPCHK(hipEventRecord(g->ev_aux, g->st2));
     sp.image_done = true;
     rc = cut_tables_prepare(g, g_base, sp.total, g->slab_t0, g->slab_t1);
@@ -630,7 +719,7 @@ static int slab_spec_finish(bz_gpu_engine *g, SlabSpec &sp, SlabCuts &sc)
         launch_rle_count(g->st, g->d_in, g->n_in, sc.tb, t0, sc.start_in, -1, rb, nullptr);
         launch_rle_prefix(g->st, sc.tb, t0, rb, false);
         HIPCHK(hipMemcpyAsync(&g->h_halo_total, rb.total, 8, hipMemcpyDeviceToHost, g->st)); // (checked by the caller once the stream has been waited for)
-        launch_rle_image(g->st, g->d_in, g->n_in, sc.tb, t0, sc.start_in, rb, g->rle.as<u8>() + sp.halo_cap - sp.want_halo_total);
+        image_launch(g, g->st, sc.tb, t0, sc.start_in, rb, g->rle.as<u8>() + sp.halo_cap - sp.want_halo_total);
     }
     HIPCHK(hipStreamWaitEvent(g->st, g->ev_aux, 0)); // the slab's image (st2)
     return slab_image(g, sc);
@@ -1693,7 +1782,7 @@ static const char *kKernelNames[KID_COUNT] = {"k_radix_hist", "k_radix_scan", "k
                                               "k_group_flags", "k_group_apply", "k_last_column",
                                               "k_radix_scatter_lb", "k_ghist_text", "k_ghist_scan", "k_rank_place", "k_phase_b_local", "k_group_refine",
                                               "k_dec_block", "k_dec_mtf", "k_dec_tsort", "k_dec_walk_lengths",
-                                              "k_dec_place", "k_dec_rle", "k_dec_crc"};
+                                              "k_dec_place", "k_dec_rle", "k_dec_crc", "k_rle_onepass", "k_rle_scatter"};
 
 extern "C" int bz_gpu_profile_enable(bz_gpu_engine *g, int on)
 {

@@ -51,6 +51,13 @@ struct bz_gpu_engine {
     u64 h_halo_total = 0;         // sharded job: the image bytes a rank found in front of its slab (a D2H copy queued on st lands here:
                                   // the engine outlives every return path of the call, a stack frame does not)
     u64 cut_stats[2] = {0, 0};    // since creation: partitions cut from tables, partitions that fell back to the chain kernel
+    // the front end in one pass (k_rle_onepass): its look-back words, their epoch, and what the current split has of it
+    DevBuf rle_lb;                // [64 bytes: tickets, error word][spans] run starts [spans] image offsets
+    u64 rle_lb_spans = 0;         // spans the words are laid out for
+    u32 rle_epoch = 0;            // tag of the last launch (1 .. rle_onepass_epochs(); the words are cleared when it wraps)
+    bool rle_onepass_broken = false; // it misbehaved on this engine once: the engine stays on the three kernels
+    bool onepass_done = false;    // the tables and the image of the current input came from it
+    u64 onepass_total = 0;        // ... and the image has this many bytes
     std::vector<BlockDesc> h_blocks;
     std::vector<u32> h_crc;
     const u8 *d_in = nullptr;

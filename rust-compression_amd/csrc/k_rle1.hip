@@ -15,7 +15,9 @@
 // a serial chain (about 1200 per GiB).
 //
 // HBM traffic: the input is read 3x (tile scan+CRC, count, scatter) and the
-// image written once -- all coalesced 16 B/lane.
+// image written once -- all coalesced 16 B/lane.  An engine that codes the whole
+// input reads it once (k_rle_onepass); the three kernels are the path of sharded
+// slabs and the fallback.
 #include "bzgpu.h"
 
 namespace bzgpu {
@@ -390,6 +392,403 @@ __global__ __launch_bounds__(RT) void k_rle_scatter(const u8 *__restrict__ in, u
     const u32 end = a0 + tot, nlines = (end + 15u) >> 4;
     for (u32 j = threadIdx.x; j < nlines; j += RT) {
         const u32 lo = j * 16u;
+        if (lo >= a0 && lo + 16u <= end) {
+            *reinterpret_cast<uint4 *>(line0 + lo) = *reinterpret_cast<const uint4 *>(s_out + lo);
+        } else {
+            const u32 b0 = lo > a0 ? lo : a0, b1 = lo + 16u < end ? lo + 16u : end;
+            for (u32 b = b0; b < b1; ++b) line0[b] = s_out[b];
+        }
+    }
+}
+
+// ---- kernel A+C+E in one: the whole front end in one pass over the input ---------------------------------
+// For an engine that codes the whole input from byte 0.  A workgroup takes a SPAN of eight consecutive tiles (32 KB),
+// handed out in order by a ticket, and writes for them exactly what k_rle_tile_scan, the two tile scans, k_rle_count
+// and k_rle_scatter write: the input is read once instead of three times.  What a span needs from the spans in front
+// of it -- the run start live at its first byte and the image offset of its first byte -- comes by decoupled
+// look-back.  A ticket's predecessors all hold a lower ticket, so they are running or done: a wait ends.
+//
+// Look-back words.  Spans run on all XCDs, whose L2s are not coherent with each other, so the words are read and
+// written with agent-scope atomics (st_sc1_x4 / ld_sc1_x4, for all their name, reach the XCD's own L2 only: the
+// sort's and the ZLE stage's tickets keep producer and consumer on one XCD, a span's predecessor is anywhere).  The
+// widest single access those give is 8 bytes, so tag, state and value share ONE 64-bit word,
+//     epoch << 48 | state << 46 | value        (46 bits: 64 TiB)
+// and a word is never seen half-written.  The epoch is the engine's call counter (1 .. 65535; the host clears the
+// words when it wraps), so nothing is cleared between calls.  One wave asks for 64 predecessors' words at once.
+constexpr u32 kSpanTiles = 8;
+constexpr u32 kSpan = kSpanTiles * kRleTile;
+constexpr u64 kOpValMask = (1ull << 46) - 1u;
+constexpr u32 kOpAgg = 1, kOpIncl = 2; // the span's own figure / the figure of everything up to the span's end
+constexpr u32 kOpEpochs = 65535;
+
+__device__ __forceinline__ u64 op_word(u32 epoch, u32 state, u64 v)
+{
+    return ((u64)epoch << 48) | ((u64)state << 46) | (v & kOpValMask);
+}
+__device__ __forceinline__ void op_publish(u64 *p, u64 w) { __hip_atomic_store(p, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// Every lane of ONE wave calls this.  IS_MAX: the latest run start published in front of `span` (values are position
+// + 1, 0 = the span holds none: such a span is passed over until it has looked back itself and says kOpIncl); else the
+// sum of the spans' byte counts.  Span 0 always says kOpIncl.  false: gave up (*err is set).
+template <bool IS_MAX> __device__ __forceinline__ bool span_look_back(const u64 *words, u64 span, u32 epoch, u32 *err, u64 &result)
+{
+    const u32 l = lane_id();
+    u64 acc = 0, hi = span; // words [0, hi) are still in front
+    u32 spins = 0;
+    while (hi > 0) {
+        const bool have = (u64)l < hi;
+        u64 w = 0;
+        if (have) w = __hip_atomic_load(words + (hi - 1u - l), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const u32 state = (u32)(w >> 46) & 3u;
+        const u64 val = w & kOpValMask;
+        const bool ready = have && (u32)(w >> 48) == epoch && state != 0u;
+        const bool term = ready && (state == kOpIncl || (IS_MAX && val != 0u));
+        const u64 m_wait = __ballot(have && !ready), m_term = __ballot(term);
+        const u64 m_stop = m_wait | m_term;
+        const u32 first = m_stop ? (u32)__builtin_ctzll(m_stop) : 64u; // the lanes below it hold settled, passable words
+        if (!IS_MAX) {
+            u64 c = (have && l < first) ? val : 0u;
+#pragma unroll
+            for (u32 d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+            acc += c;
+        }
+        if (first < 64u && ((m_term >> first) & 1u)) {
+            const u64 tv = __shfl(val, (int)first, 64);
+            result = IS_MAX ? tv : acc + tv;
+            return true;
+        }
+        const u64 step = first < 64u ? first : 64u;
+        hi -= step < hi ? step : hi;
+        if (first < 64u) { // a predecessor has not published yet
+            if (lb_give_up(spins, err, kLbSpinMax >> 3)) {
+                if (l == 0) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                return false;
+            }
+            __builtin_amdgcn_s_sleep(2);
+        }
+    }
+    result = acc; // (not reached: span 0 ends every walk)
+    return true;
+}
+
+// RLE1 over the 16 bytes of a segment as bit masks (bit k = byte k).  eval_seg's rule, position by position, is: c = the
+// byte's distance from its run's start modulo 255; it emits itself if c < 4 and a count byte (c - 3) if it is the last of
+// its chunk (the next byte differs, or c = 254) and c >= 3.  Inside a segment a byte's distance from a run start OF THE
+// SEGMENT is below 16, so only the bytes in front of the segment's first run start need the phase c0 of byte 0.
+// bit k: byte k equals the byte before it (byte 0: `prev`, -1 = there is none)
+__device__ __forceinline__ u32 seg_eq_mask(const uint4 &v, int prev)
+{
+    const u32 w[4] = {v.x, v.y, v.z, v.w};
+    u32 m = 0, carry = (u32)prev & 0xFFu;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const u32 y = w[q] ^ ((w[q] << 8) | carry); // a byte of y is zero where the byte equals the one before it
+        carry = w[q] >> 24;
+        u32 t = (y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
+        t = ~(t | y | 0x7F7F7F7Fu); // 0x80 in every zero byte of y
+        const u32 u = t >> 7;
+        m |= ((u | (u >> 7) | (u >> 14) | (u >> 21)) & 0xFu) << (4 * q);
+    }
+    return prev < 0 ? m & ~1u : m;
+}
+// E: seg_eq_mask, V: the valid bytes, c0: phase of byte 0 if it continues a run, next_differs: the byte behind the last
+// valid one is another (or the input ends).  lt4: the bytes that emit themselves, cg: those that emit a count byte.
+__device__ __forceinline__ void seg_emit_masks(u32 E, u32 V, u32 c0, bool next_differs, u32 &lt4, u32 &cg)
+{
+    const u32 S = ~E & V;                                       // run starts
+    const u32 P = (S ? (1u << __builtin_ctz(S)) - 1u : 0xFFFFu) & V; // the bytes in front of the first one: c = (c0 + k) % 255
+    const u32 wrap = 255u - c0;                                 // k at which c0 + k comes round to 0 (>= 16: not in this segment)
+    const u32 w4 = wrap < 16u ? (0xFu << wrap) : 0u, w3 = wrap < 16u ? (0x7u << wrap) : 0u;
+    const u32 p4 = (c0 < 4u ? (1u << (4u - c0)) - 1u : 0u) | w4, p3 = (c0 < 3u ? (1u << (3u - c0)) - 1u : 0u) | w3;
+    lt4 = ((p4 & P) | S | (S << 1) | (S << 2) | (S << 3)) & V;
+    const u32 lt3 = ((p3 & P) | S | (S << 1) | (S << 2)) & V;
+    const u32 c254 = wrap >= 1u && wrap <= 16u ? (1u << (wrap - 1u)) & P : 0u;
+    const u32 top = V ^ (V >> 1);                               // the last valid byte
+    const u32 ce = ((S >> 1) | (next_differs ? top : 0u) | c254) & V; // last byte of its chunk
+    cg = ce & ~lt3;
+}
+
+__global__ __launch_bounds__(RT, 3) void k_rle_onepass(const u8 *__restrict__ in, u64 n, u64 ntiles, u32 nspans, u32 epoch,
+                                                     const u32 *__restrict__ crc_tab, const u32 *__restrict__ xp16,
+                                                     RleBuffers rb, u8 *__restrict__ rle, i64 *__restrict__ out_last)
+{
+    __shared__ u32 s_tab[256];
+    __shared__ int s_wmax[kSpanTiles][RT / 64];  // per tile and wave: last run start, relative to the span (-1: none)
+    __shared__ u32 s_wx[kSpanTiles][RT / 64];    // ... CRC
+    __shared__ u32 s_wsum[kSpanTiles][RT / 64];  // ... bytes emitted
+    __shared__ int s_fb[kSpanTiles][RT / 64], s_lb[kSpanTiles][RT / 64]; // ... first byte of lane 0, last byte of lane 63
+    __shared__ int s_edge[2]; // the byte in front of the span and the byte behind it (-1: none)
+    __shared__ u32 s_ticket, s_fail;
+    __shared__ i64 s_carry;   // run start live at the span's first byte
+    __shared__ u32 s_cphase;  // ... and the span's first byte's distance from it, modulo 255
+    __shared__ u64 s_base;    // image offset of the span's first byte
+    __shared__ __attribute__((aligned(16))) u8 s_out[kSpan / 4 * 5 + 64]; // (a span that begins inside a chunk can emit a byte more than 5/4 of its own)
+
+    const u32 tid = threadIdx.x, l = lane_id(), wv = tid >> 6;
+    if (tid == 0) {
+        s_ticket = __hip_atomic_fetch_add(rb.lb_ctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_fail = 0;
+    }
+    s_tab[tid] = crc_tab[tid];
+    __syncthreads();
+    const u64 span = s_ticket;
+    if (span >= nspans) return;
+    const u64 B = span * (u64)kSpan;
+    u64 *w_rs = rb.lb_rs + span, *w_off = rb.lb_off + span;
+
+    // ---- the span's bytes: eight 16-byte loads per lane, back to back ------------------------------------
+    uint4 v[kSpanTiles];
+    if (B + kSpan <= n) {
+#pragma unroll
+        for (u32 j = 0; j < kSpanTiles; ++j) v[j] = *reinterpret_cast<const uint4 *>(in + B + j * kRleTile + tid * 16u);
+    } else {
+#pragma unroll
+        for (u32 j = 0; j < kSpanTiles; ++j) {
+            const u64 p0 = B + j * kRleTile + tid * 16u;
+            if (p0 + 16 <= n) {
+                v[j] = *reinterpret_cast<const uint4 *>(in + p0);
+            } else {
+                u32 t[4] = {0, 0, 0, 0};
+                const u32 valid = p0 < n ? (u32)(n - p0) : 0u;
+                for (u32 k = 0; k < valid; ++k) t[k >> 2] |= (u32)in[p0 + k] << ((k & 3u) * 8u);
+                v[j] = make_uint4(t[0], t[1], t[2], t[3]);
+            }
+        }
+    }
+    if (tid == 0) {
+        s_edge[0] = B > 0 ? (int)in[B - 1] : -1;
+        s_edge[1] = B + kSpan < n ? (int)in[B + kSpan] : -1;
+    }
+#pragma unroll
+    for (u32 j = 0; j < kSpanTiles; ++j) {
+        if (l == 0) s_fb[j][wv] = (int)(v[j].x & 0xFFu);
+        if (l == 63) s_lb[j][wv] = (int)(v[j].w >> 24);
+    }
+    __syncthreads();
+    // the byte before and behind every segment: the neighbouring lane's, the neighbouring wave's, the neighbouring tile's
+    u32 pn[kSpanTiles];
+#pragma unroll
+    for (u32 j = 0; j < kSpanTiles; ++j) {
+        const u64 p0 = B + j * kRleTile + tid * 16u;
+        const u32 valid = p0 + 16 <= n ? 16u : (p0 < n ? (u32)(n - p0) : 0u);
+        int pb = __shfl_up((int)(v[j].w >> 24), 1, 64);
+        int nb = __shfl_down((int)(v[j].x & 0xFFu), 1, 64);
+        if (l == 0) pb = wv > 0 ? s_lb[j][wv - 1] : (j > 0 ? s_lb[j > 0 ? j - 1 : 0][RT / 64 - 1] : s_edge[0]);
+        if (l == 63) nb = wv + 1 < RT / 64 ? s_fb[j][wv + 1 < RT / 64 ? wv + 1 : 0] : (j + 1 < kSpanTiles ? s_fb[j + 1 < kSpanTiles ? j + 1 : 0][0] : s_edge[1]);
+        if (!(p0 > 0 && valid > 0)) pb = -1;
+        if (!(valid > 0 && p0 + valid < n)) nb = -1;
+        pn[j] = (u32)(pb + 1) | ((u32)(nb + 1) << 9); // (bits 18 ..: the phase of byte 0, step 4)
+    }
+
+    // ---- 1. per tile: last run start and CRC (k_rle_tile_scan) --------------------------------------------
+    const bool full = B + kSpan <= n;
+    u32 E[kSpanTiles];   // seg_eq_mask of the segment, valid bytes only
+    int inc[kSpanTiles]; // inclusive max over the wave's lanes of the segments' last run starts (relative to the span)
+    u32 crc[kSpanTiles];
+#pragma unroll
+    for (u32 j = 0; j < kSpanTiles; ++j) {
+        const u32 rel = j * kRleTile + tid * 16u;
+        const u32 valid = full ? 16u : (B + rel + 16 <= n ? 16u : (B + rel < n ? (u32)(n - (B + rel)) : 0u));
+        const u32 V = (1u << valid) - 1u;
+        E[j] = seg_eq_mask(v[j], (int)(pn[j] & 0x1FFu) - 1) & V;
+        const u32 S = ~E[j] & V;
+        const int last = S ? (int)(rel + 31u - (u32)__builtin_clz(S)) : -1;
+        inc[j] = wave_incl_max32(last);
+        if (l == 63) s_wmax[j][wv] = inc[j];
+        const u32 w[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+        u32 c = 0;
+#pragma unroll
+        for (u32 k = 0; k < 16; ++k)
+            if (full || k < valid) c = s_tab[(c >> 24) ^ ((w[k >> 2] >> ((k & 3u) * 8u)) & 0xFFu)] ^ (c << 8);
+        crc[j] = c;
+    }
+    if (full) {
+        // the segment's CRC moved to the end of its tile: times x^(8 * 16 * (255 - tid)), the same factor in all eight tiles,
+        // so its 32 shifts are made once: a * b = sum over the bits i of a of b x^i
+        u32 bx = xp16[255u - tid];
+        u32 r[kSpanTiles];
+#pragma unroll
+        for (u32 j = 0; j < kSpanTiles; ++j) r[j] = 0;
+#pragma unroll 4
+        for (u32 i = 0; i < 32; ++i) {
+#pragma unroll
+            for (u32 j = 0; j < kSpanTiles; ++j) r[j] ^= (u32)((int)(crc[j] << (31u - i)) >> 31) & bx;
+            bx = (bx << 1) ^ ((u32)((int)bx >> 31) & kCrcPoly);
+        }
+#pragma unroll
+        for (u32 j = 0; j < kSpanTiles; ++j) crc[j] = r[j];
+    } else {
+#pragma unroll
+        for (u32 j = 0; j < kSpanTiles; ++j) {
+            const u64 tile_beg = B + (u64)j * kRleTile, p0 = tile_beg + tid * 16u;
+            const u32 valid = p0 + 16 <= n ? 16u : (p0 < n ? (u32)(n - p0) : 0u);
+            if (valid > 0) {
+                const u32 tile_len = (u32)((n - tile_beg) < (u64)kRleTile ? (n - tile_beg) : (u64)kRleTile);
+                const u32 after = tile_len - (tid * 16u + valid);
+                u32 m = xp16[after >> 4];
+                for (u32 k = 0; k < (after & 15u); ++k) m = gf_mulmod(m, 0x100u); // * x^8: only in the last, partial tile
+                crc[j] = gf_mulmod(crc[j], m);
+            } else {
+                crc[j] = 0;
+            }
+        }
+    }
+#pragma unroll
+    for (u32 j = 0; j < kSpanTiles; ++j) {
+        const u32 wx = wave_xor(crc[j]);
+        if (l == 0) s_wx[j][wv] = wx;
+    }
+    __syncthreads();
+    if (tid < kSpanTiles && span * kSpanTiles + tid < ntiles) {
+        int m = -1;
+        u32 x = 0;
+        for (u32 k = 0; k < RT / 64; ++k) {
+            m = s_wmax[tid][k] > m ? s_wmax[tid][k] : m;
+            x ^= s_wx[tid][k];
+        }
+        rb.tile_last[span * kSpanTiles + tid] = m >= 0 ? (i64)(B + (u32)m) : (i64)-1;
+        rb.tile_crc[span * kSpanTiles + tid] = x;
+    }
+    // ---- 2., 3. the span's last run start goes out; the run start live at its first byte comes in -----------
+    if (wv == 0) {
+        int m = l < kSpanTiles * (RT / 64) ? s_wmax[l >> 2][l & 3u] : -1;
+#pragma unroll
+        for (u32 d = 32; d >= 1; d >>= 1) {
+            const int o = __shfl_xor(m, d, 64);
+            m = o > m ? o : m;
+        }
+        const u64 own = m >= 0 ? B + (u32)m + 1u : 0u;
+        // (a span with a run start of its own settles what is live behind it; one without passes on what it finds)
+        if (l == 0) op_publish(w_rs, op_word(epoch, own ? kOpIncl : kOpAgg, own));
+        u64 before = 0;
+        bool ok = true;
+        if (span > 0) ok = span_look_back<true>(rb.lb_rs, span, epoch, rb.lb_ctl + 1, before);
+        if (ok && !own && l == 0) op_publish(w_rs, op_word(epoch, kOpIncl, before));
+        if (l == 0) {
+            s_carry = (i64)before - 1;
+            s_cphase = before ? (u32)((B - (before - 1u)) % 255u) : 0u;
+            if (!ok) s_fail = 1;
+            if (ok && span + 1u == nspans && out_last) *out_last = (i64)(own ? own : before) - 1;
+        }
+    }
+    __syncthreads();
+    if (s_fail) return;
+
+    // ---- 4. per tile: carries, RLE1 byte counts, sub-tile index (k_rle_count) ------------------------------
+    const i64 span_carry = s_carry;
+    int tcr[kSpanTiles]; // last run start in the span's tiles in front of tile j (relative to the span, -1: none)
+    {
+        int run = -1;
+#pragma unroll
+        for (u32 j = 0; j < kSpanTiles; ++j) {
+            tcr[j] = __builtin_amdgcn_readfirstlane(run); // (the same in every lane: a scalar register)
+            for (u32 k = 0; k < RT / 64; ++k) run = s_wmax[j][k] > run ? s_wmax[j][k] : run;
+        }
+    }
+    const u32 cphase = s_cphase;
+    u32 exw[kSpanTiles]; // bytes the wave's lanes below this one emit
+    u32 em[kSpanTiles];  // seg_emit_masks: lt4 | cg << 16
+#pragma unroll
+    for (u32 j = 0; j < kSpanTiles; ++j) {
+        const int cr = tcr[j];
+        int ex = __shfl_up(inc[j], 1, 64);
+        if (l == 0) ex = -1;
+        for (u32 k = 0; k < wv; ++k) ex = s_wmax[j][k] > ex ? s_wmax[j][k] : ex;
+        if (cr > ex) ex = cr; // the run start live at the segment's first byte, relative to the span (-1: the span's carry)
+        const u32 rel = j * kRleTile + tid * 16u;
+        const u32 valid = full ? 16u : (B + rel + 16 <= n ? 16u : (B + rel < n ? (u32)(n - (B + rel)) : 0u));
+        const u32 V = (1u << valid) - 1u;
+        const u32 c0 = (ex >= 0 ? rel - (u32)ex : rel + cphase) % 255u;
+        pn[j] |= c0 << 18;
+        const int nxt = (int)((pn[j] >> 9) & 0x1FFu) - 1;
+        u32 lastb = v[j].w >> 24;
+        if (valid != 16u && valid > 0u) {
+            const u32 w[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+            lastb = 0;
+#pragma unroll
+            for (u32 k = 0; k < 16; ++k)
+                if (k + 1u == valid) lastb = (w[k >> 2] >> ((k & 3u) * 8u)) & 0xFFu;
+        }
+        u32 lt4, cg;
+        seg_emit_masks(E[j], V, c0, nxt != (int)lastb, lt4, cg);
+        em[j] = lt4 | (cg << 16);
+        const u32 cnt = (u32)__builtin_popcount(em[j]);
+        const u32 incs = wave_incl_sum(cnt);
+        exw[j] = incs - cnt;
+        if (l == 63) s_wsum[j][wv] = incs;
+        const u64 tile = span * kSpanTiles + j;
+        if (tile < ntiles) {
+            if (tid == 0) rb.carry_in[tile] = cr >= 0 ? (i64)(B + (u32)cr) : span_carry;
+            if ((tid & 15u) == 0) rb.sub_rs[tile * 16u + (tid >> 4)] = ex >= 0 ? (i64)(B + (u32)ex) : span_carry;
+        }
+    }
+    __syncthreads();
+    u32 tile_ex[kSpanTiles]; // bytes the span emits in front of tile j
+    u32 span_total = 0;
+#pragma unroll
+    for (u32 j = 0; j < kSpanTiles; ++j) {
+        tile_ex[j] = span_total;
+        u32 below = 0, tot = 0;
+        for (u32 k = 0; k < RT / 64; ++k) {
+            if (k < wv) below += s_wsum[j][k];
+            tot += s_wsum[j][k];
+        }
+        exw[j] += (u32)__builtin_amdgcn_readfirstlane((int)below); // (wave-uniform, like tot: scalar registers)
+        span_total += (u32)__builtin_amdgcn_readfirstlane((int)tot);
+        const u64 tile = span * kSpanTiles + j;
+        if (tile < ntiles) {
+            if (tid == 0) rb.tile_count[tile] = tot;
+            if ((tid & 15u) == 0) rb.sub_off[tile * 16u + (tid >> 4)] = (u16)exw[j];
+        }
+    }
+    // ---- 5., 6., 7. the span's byte count goes out; the image offset of its first byte comes in ------------
+    if (wv == 0) {
+        if (l == 0) op_publish(w_off, op_word(epoch, span ? kOpAgg : kOpIncl, span_total));
+        u64 base = 0;
+        bool ok = true;
+        if (span > 0) {
+            ok = span_look_back<false>(rb.lb_off, span, epoch, rb.lb_ctl + 1, base);
+            if (ok && l == 0) op_publish(w_off, op_word(epoch, kOpIncl, base + span_total));
+        }
+        if (l == 0) {
+            s_base = base;
+            if (!ok) s_fail = 1;
+            if (ok && span + 1u == nspans) {
+                rb.tile_off[ntiles] = base + span_total;
+                *rb.total = base + span_total;
+            }
+        }
+    }
+    __syncthreads();
+    if (s_fail) return;
+    // ---- 8. tile offsets ------------------------------------------------------------------------------------
+    const u64 base = s_base;
+#pragma unroll
+    for (u32 j = 0; j < kSpanTiles; ++j)
+        if (tid == j && span * kSpanTiles + j < ntiles) rb.tile_off[span * kSpanTiles + j] = base + tile_ex[j];
+
+    // ---- 9. the image (k_rle_scatter): staged at the offset its destination has inside a 16-byte line -------
+    u8 *dst = rle + base;
+    const u32 a0 = (u32)(reinterpret_cast<uintptr_t>(dst) & 15u);
+#pragma unroll
+    for (u32 j = 0; j < kSpanTiles; ++j) {
+        const u32 w[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+        const u32 lt4 = em[j] & 0xFFFFu, cg = em[j] >> 16, S = ~E[j];
+        u32 o = a0 + tile_ex[j] + exw[j];
+        u32 c = pn[j] >> 18; // the phase of the byte at hand
+#pragma unroll
+        for (u32 k = 0; k < 16; ++k) {
+            if ((S >> k) & 1u) c = 0;
+            if ((lt4 >> k) & 1u) s_out[o++] = (u8)(w[k >> 2] >> ((k & 3u) * 8u));
+            if ((cg >> k) & 1u) s_out[o++] = (u8)(c - 3u);
+            c = c == 254u ? 0u : c + 1u;
+        }
+    }
+    __syncthreads();
+    u8 *line0 = dst - a0; // 16-byte aligned
+    const u32 end = a0 + span_total, nlines = (end + 15u) >> 4;
+    for (u32 q = tid; q < nlines; q += RT) {
+        const u32 lo = q * 16u;
         if (lo >= a0 && lo + 16u <= end) {
             *reinterpret_cast<uint4 *>(line0 + lo) = *reinterpret_cast<const uint4 *>(s_out + lo);
         } else {
@@ -1062,6 +1461,19 @@ void launch_rle_image(hipStream_t st, const u8 *d_in, u64 n, u64 tb, u64 t1, u64
     if (t1 <= tb) return;
     hipLaunchKernelGGL(k_rle_scatter, dim3((u32)(t1 - tb)), dim3(RT), 0, st, d_in, n, tb, in_begin, rb.carry_in,
                        rb.tile_off, d_rle);
+}
+
+// The whole front end for an engine that codes the input from byte 0: every table of the three steps above and the
+// image, in one launch (k_rle_onepass).  rb.lb_ctl[0] counts the spans handed out and rb.lb_ctl[1] is set by a look-back
+// that gave up: the caller reads both.  *d_out_last = the input's last run start, rb.total = bytes of the image.
+u64 rle_onepass_spans(u64 ntiles) { return (ntiles + kSpanTiles - 1u) / kSpanTiles; }
+u32 rle_onepass_epochs() { return kOpEpochs; }
+void launch_rle_onepass(hipStream_t st, const u8 *d_in, u64 n, u64 ntiles, u32 epoch, const u32 *crc_tab, const u32 *xp16,
+                        const RleBuffers &rb, u8 *d_rle, i64 *d_out_last)
+{
+    (void)hipMemsetAsync(rb.lb_ctl, 0, 16, st);
+    hipLaunchKernelGGL(k_rle_onepass, dim3((u32)rle_onepass_spans(ntiles)), dim3(RT), 0, st, d_in, n, ntiles,
+                       (u32)rle_onepass_spans(ntiles), epoch, crc_tab, xp16, rb, d_rle, d_out_last);
 }
 
 // The cuts from tables, in three steps (see "kernels H"): the steps' tiles (the caller reads step_w0[nsteps], the number
