@@ -135,6 +135,14 @@ int bz_encode_buffer(int level, int device, const uint8_t *in, size_t in_len,
  * equal chunks, a whole number of rounds over the lanes. */
 int bz_encode_buffer_multi(int level, const int *devices, int n_devices, const uint8_t *in, size_t in_len,
                            uint8_t **out, size_t *out_len);
+/* Many independent inputs in one call: stream i is bz_encode_buffer(level, device, ins[i], lens[i]), bit for bit, and
+ * lies at *out + out_off[i] with out_len[i] bytes (streams in input order, each starting at a multiple of 4 bytes, zeros
+ * between them).  *out is ONE malloc'ed buffer (release with bz_free); out_off and out_len have `count` entries.  The
+ * inputs are packed at 16-byte-aligned offsets into pinned staging memory, uploaded once, encoded by
+ * bz_gpu_encode_batch_device (section 2) on an engine of the per-process cache and downloaded once.  BZ_VERIFY=1
+ * applies.  count == 0: BZ_OK, *out is an empty buffer. */
+int bz_encode_batch(int level, int device, const uint8_t *const *ins, const size_t *lens, size_t count,
+                    uint8_t **out, uint64_t *out_off, uint64_t *out_len);
 void bz_free(void *p);
 /* Contexts and one-shot calls park their engines (batch workspace: about 35.3 MB of HBM per block of the largest
  * chunk seen, i.e. up to ~9 GB per lane with the default 192 MiB chunks, two lanes per listed device), device staging
@@ -190,6 +198,29 @@ size_t bz_encode_bound(size_t n);
  * Equivalent to the one-shot above minus the PCIe copies. */
 int bz_gpu_encode_device(bz_gpu_engine *g, int level, const void *d_in, size_t n,
                          void *d_out, size_t cap, size_t *out_len);
+
+/* Many independent inputs, one stream each, in one pass of the pipeline.  Input i is the h_in_len[i] bytes at
+ * d_in + h_in_off[i] (d_in 16-byte aligned, every offset a multiple of 16, ranges in ascending order without overlap);
+ * stream i is the bytes of bz_gpu_encode_device(g, level, d_in + h_in_off[i], h_in_len[i], ...), bit for bit, and is
+ * written to d_out + h_out_off[i] (h_out_len[i] bytes; d_out 4-byte aligned; streams in input order, each at a multiple
+ * of 4 bytes, zeros between them).  The four arrays are HOST arrays of `count` entries.
+ * An input of n bytes with 5 * (n / 4) + n % 4 <= 100000 * level - 19 is certainly one block (RLE1 grows it by at most
+ * one byte per four, src/bzip2/encoder.rs:699-716, and the cut at :692 only fires behind a run that is not the last):
+ * all such inputs are split by one launch and encoded together as the blocks of one bz_gpu_encode_blocks call, whatever
+ * their number; an empty input is the 14 bytes of header and trailer.  Every other input takes the path of
+ * bz_gpu_encode_device, one at a time.  bz_encode_batch_bound: a `cap` that always suffices (the sum of
+ * bz_encode_bound, each rounded up to 4).
+ * BZ_E_PARAM: level outside 1..9, a null array with count > 0, a misaligned offset, ranges that overlap or are out of
+ * order.  BZ_E_CAPACITY: cap too small (nothing is promised about d_out then).  count == 0: BZ_OK, nothing is touched. */
+size_t bz_encode_batch_bound(const uint64_t *in_len, size_t count);
+int bz_gpu_encode_batch_device(bz_gpu_engine *g, int level, const void *d_in,
+                               const uint64_t *h_in_off, const uint64_t *h_in_len, size_t count,
+                               void *d_out, size_t cap,
+                               uint64_t *h_out_off, uint64_t *h_out_len);
+/* The last bz_gpu_encode_batch_device call: [0] inputs split by the batch front end (k_rle_batch)  [1] inputs that took
+ * the one-input path  [2] blocks of the inputs of [0]  [3] sub-batches the pipeline ran them in (the workspace holds
+ * max_blocks_in_flight blocks). */
+int bz_gpu_last_batch_stats(bz_gpu_engine *g, uint64_t out[4]);
 
 /* ---- the same, split into the three steps a multi-GPU job needs ---------- */
 

@@ -27,7 +27,7 @@ import sys
 from . import _build
 
 __all__ = ["Action", "CompressionError", "BZip2Error", "BZip2Encoder", "BZip2Decoder", "encode", "decode",
-           "compress", "decompress", "GpuEngine", "release_cached_resources", "last_call_phases",
+           "compress", "compress_batch", "encode_batch_bound", "decompress", "GpuEngine", "release_cached_resources", "last_call_phases",
            "build", "lib", "device_count", "encode_bound", "shard_window", "rccl_lib", "rccl_unique_id", "RcclComm"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -79,7 +79,8 @@ def build(force=False):
 EXPORTS = [
     "bz_strerror", "bz_version", "bz_device_count",
     "bz_enc_create", "bz_enc_write", "bz_enc_end", "bz_enc_read", "bz_enc_pending", "bz_enc_destroy",
-    "bz_encode_buffer", "bz_free", "bz_enc_create_multi", "bz_enc_set_verify", "bz_enc_verify_stats", "bz_enc_phase_stats", "bz_encode_buffer_last_phases",
+    "bz_encode_buffer", "bz_encode_batch", "bz_encode_batch_bound", "bz_gpu_encode_batch_device", "bz_gpu_last_batch_stats",
+    "bz_free", "bz_enc_create_multi", "bz_enc_set_verify", "bz_enc_verify_stats", "bz_enc_phase_stats", "bz_encode_buffer_last_phases",
     "bz_gpu_engine_set_verify", "bz_gpu_verify_stats", "bz_encode_buffer_multi", "bz_release_cached_resources", "bz_peer_copy_selftest",
     "bz_gpu_engine_create", "bz_gpu_engine_destroy", "bz_gpu_engine_reserve", "bz_encode_bound", "bz_gpu_encode_device",
     "bz_gpu_partition", "bz_gpu_partition_slab_begin", "bz_gpu_partition_slab_count",
@@ -144,6 +145,11 @@ def lib():
     L.bz_enc_destroy.restype = None
     L.bz_enc_destroy.argtypes = [vp]
     L.bz_encode_buffer.argtypes = [C.c_int, C.c_int, C.c_char_p, sz, C.POINTER(u8p), szp]
+    L.bz_encode_batch.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, sz, C.POINTER(u8p), u64p, u64p]
+    L.bz_encode_batch_bound.restype = sz
+    L.bz_encode_batch_bound.argtypes = [u64p, sz]
+    L.bz_gpu_encode_batch_device.argtypes = [vp, C.c_int, vp, u64p, u64p, sz, vp, sz, u64p, u64p]
+    L.bz_gpu_last_batch_stats.argtypes = [vp, u64p]
     L.bz_enc_create_multi.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(C.c_int), C.c_int]
     L.bz_encode_buffer_multi.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_char_p, sz, C.POINTER(u8p), szp]
     L.bz_enc_phase_stats.argtypes = [vp, C.POINTER(C.c_double)]
@@ -492,6 +498,36 @@ def compress(data, level=9, device=0, devices=None, verify=None):
         lib().bz_free(out)
 
 
+def encode_batch_bound(lens):
+    """An output capacity that always suffices for GpuEngine.encode_batch_device (bz_encode_batch_bound)."""
+    a = (C.c_uint64 * max(len(lens), 1))(*lens)
+    return lib().bz_encode_batch_bound(a, len(lens))
+
+
+def compress_batch(datas, level=9, device=0, verify=None):
+    """Many independent inputs in one call (bz_encode_batch) -> list of streams: element i is compress(datas[i], level),
+    bit for bit.  Inputs that are certain to be one block (at most 719 985 bytes at level 9) are encoded together in one
+    pass of the pipeline, however many there are.  verify given: each input through a streaming context with the
+    self-check switched that way (the batch call takes BZ_VERIFY=1 from the environment); the bytes are the same."""
+    if level < 1 or level > 9:
+        raise ValueError("invalid level")
+    datas = [d if isinstance(d, bytes) else bytes(d) for d in datas]
+    if verify is not None:
+        return [BZip2Encoder(level, device, verify=verify).encode_all(d) for d in datas]
+    k = len(datas)
+    ins = (C.c_char_p * max(k, 1))(*datas)
+    lens = (C.c_size_t * max(k, 1))(*[len(d) for d in datas])
+    off = (C.c_uint64 * max(k, 1))()
+    ln = (C.c_uint64 * max(k, 1))()
+    out = C.POINTER(C.c_uint8)()
+    _check(lib().bz_encode_batch(level, device, ins, lens, k, C.byref(out), off, ln))
+    try:
+        base = C.addressof(out.contents) if k else 0
+        return [C.string_at(base + off[i], ln[i]) for i in range(k)]
+    finally:
+        lib().bz_free(out)
+
+
 # ---------------------------------------------------------------------------- Deflate / zlib / gzip
 DEFLATE, ZLIB, GZIP = 0, 1, 2
 
@@ -744,6 +780,29 @@ class GpuEngine:
         out_len = C.c_size_t(0)
         _check(lib().bz_gpu_encode_device(self._h, level, d_in, n, d_out, cap, C.byref(out_len)))
         return out_len.value
+
+    BATCH_STATS = ("inputs_batched", "inputs_one_by_one", "blocks", "sub_batches")
+
+    def encode_batch_device(self, level, d_in, in_off, in_len, d_out, cap):
+        """Many inputs, one stream each (bz_gpu_encode_batch_device): input i is the in_len[i] bytes at d_in + in_off[i]
+        (offsets multiples of 16, in ascending order); returns (out_off, out_len), stream i at d_out + out_off[i]."""
+        _settle()
+        k = len(in_off)
+        if len(in_len) != k:
+            raise ValueError("encode_batch_device: in_off and in_len differ in length")
+        a_off = (C.c_uint64 * max(k, 1))(*in_off)
+        a_len = (C.c_uint64 * max(k, 1))(*in_len)
+        o_off = (C.c_uint64 * max(k, 1))()
+        o_len = (C.c_uint64 * max(k, 1))()
+        _check(lib().bz_gpu_encode_batch_device(self._h, level, d_in, a_off, a_len, k, d_out, cap, o_off, o_len))
+        return list(o_off[:k]), list(o_len[:k])
+
+    def batch_stats(self):
+        """The last encode_batch_device call: [0] inputs split by the batch front end, [1] inputs that took the one-input
+        path, [2] blocks of the former, [3] sub-batches the pipeline ran them in (bz_gpu_last_batch_stats)."""
+        s = (C.c_uint64 * 4)()
+        _check(lib().bz_gpu_last_batch_stats(self._h, s))
+        return [int(x) for x in s]
 
     def partition(self, level, d_in, n, mode=Action.FINISH):
         _settle()

@@ -434,6 +434,19 @@ struct AsmBlock {
 struct PackBlock {
     u64 src_word, dst_word, nwords;
 };
+// one input of a batch of one-block inputs (k_rle_batch): its bytes in the batch's input and the slot of its RLE1 image
+struct RleBatchItem {
+    u64 in_off;    // first byte, relative to the batch's base (a multiple of 16)
+    u64 len;       // bytes (5 * (len / 4) + len % 4 <= 100000 * level - 19: certainly one block)
+    u64 rle_off;   // the slot in the image buffer (a multiple of 16)
+};
+// one stream of a batch (k_frame_batch)
+struct FrameItem {
+    u64 first_word;   // the stream's first word in the output (streams start at multiples of 4 bytes)
+    u64 trailer_bit;  // position of the end magic, in bits from the output's first bit
+    u32 combined_crc;
+    u32 pad;
+};
 
 // ---- decoder records -------------------------------------------------------------------------------
 constexpr int BZ_DEC_E_DATA = -1; // BZip2Error::DataError (src/bzip2/error.rs:5-11)
@@ -577,6 +590,8 @@ void launch_cut_select(hipStream_t st, const CutPlan &pl, u64 j0, u64 s0, u64 st
                        const RleBuffers &rb, const CutBuffers &cb, BlockDesc *d_blocks, u32 max_blocks);
 void launch_block_crc(hipStream_t st, const u8 *d_in, const BlockDesc *d_blocks, u32 nblocks,
                       const u32 *crc_tab, const u32 *xp2, const u32 *tile_crc, u32 *d_crc);
+void launch_rle_batch(hipStream_t st, const u8 *d_in, const RleBatchItem *d_items, u32 count, const u32 *crc_tab,
+                      const u32 *xp2, u8 *d_rle, BlockDesc *d_blocks, u32 *d_crc);
 void launch_block_symbols(hipStream_t st, const BwtArgs &a, u32 *inuse_bits, u8 *sym_code, u8 *keyinfo);
 int run_bwt(hipStream_t st, const BwtArgs &a, u32 max_n, u64 total_n, unsigned long long *h_active,
             u64 *sorted_elems, KernelProf *prof, u64 *round_active /*[64] or null*/, bool wide_keys,
@@ -603,6 +618,7 @@ void launch_assemble(hipStream_t st, const u32 *packed, const AsmBlock *d_blocks
                      u32 *out_words);
 void launch_frame(hipStream_t st, u32 *out_words, int write_header, u32 level, u32 carry_bits, u32 carry_byte,
                   int write_trailer, u64 trailer_bit, u32 combined_crc);
+void launch_frame_batch(hipStream_t st, u32 *out_words, const FrameItem *d_items, u32 count, u32 level);
 void launch_pack(hipStream_t st, const u32 *src, const PackBlock *d_pb, u32 n_blocks, u32 *dst);
 
 } // namespace bzgpu

@@ -1237,3 +1237,78 @@ extern "C" int bz_encode_buffer(int level, int device, const uint8_t *in, size_t
 {
     return bz_encode_buffer_multi(level, &device, 1, in, in_len, out, out_len);
 }
+
+#ifndef BZ_HOST_PIPELINE_TEST
+// Many inputs, one stream each: the inputs are packed at 16-byte-aligned offsets into the first pinned staging buffer of
+// the cached resources of `device`, go up in ONE copy, are encoded by bz_gpu_encode_batch_device on the first lane's
+// engine (whose workspace a second call finds in place) and come down in ONE copy.
+extern "C" int bz_encode_batch(int level, int device, const uint8_t *const *ins, const size_t *lens, size_t count,
+                               uint8_t **out, uint64_t *out_off, uint64_t *out_len)
+{
+    if (!out) return BZ_E_PARAM;
+    *out = nullptr;
+    if (level < 1 || level > 9) return BZ_E_PARAM;
+    if (count && (!ins || !lens || !out_off || !out_len)) return BZ_E_PARAM;
+    for (size_t i = 0; i < count; ++i)
+        if (lens[i] && !ins[i]) return BZ_E_PARAM;
+    if (count == 0) {
+        *out = (u8 *)malloc(1);
+        return *out ? BZ_OK : BZ_E_NOMEM;
+    }
+    std::vector<uint64_t> in_off(count), in_len(count);
+    u64 total_in = 0;
+    for (size_t i = 0; i < count; ++i) {
+        in_off[i] = total_in;
+        in_len[i] = lens[i];
+        total_in += ((u64)lens[i] + 15u) & ~(u64)15;
+    }
+    CallerDevice keep;
+    EncResources *r = nullptr;
+    int rc = resources_get(std::vector<int>(1, device), &r);
+    if (rc != BZ_OK) return rc;
+    Lane &ln = r->lanes[0];
+    u8 *res = nullptr;
+    u64 total_out = 0;
+    const size_t cap = bz_encode_batch_bound(in_len.data(), count);
+    auto run = [&]() -> int {
+        if (hipSetDevice(ln.device) != hipSuccess) return BZ_E_UNEXPECTED;
+        int rc2;
+        if (!ln.g && (rc2 = bz_gpu_engine_create(&ln.g, ln.device, r->engine_blocks)) != BZ_OK) return rc2;
+        if (r->h_lane[0] >= 0) { // the pinned buffer is free once its last upload has completed
+            const Lane &ul = r->lanes[(size_t)r->h_lane[0]];
+            if (hipSetDevice(ul.device) != hipSuccess || hipEventSynchronize(ul.ev_up) != hipSuccess ||
+                hipSetDevice(ln.device) != hipSuccess)
+                return BZ_E_UNEXPECTED;
+            r->h_lane[0] = -1;
+        }
+        if ((rc2 = grow_pinned(&r->h_in[0], &r->h_cap[0], (size_t)total_in + 16)) != BZ_OK) return rc2;
+        if ((rc2 = grow(&ln.d_buf, &ln.d_buf_cap, (size_t)total_in + 64)) != BZ_OK) return rc2;
+        if ((rc2 = grow(&ln.d_out, &ln.d_out_cap, cap + 64)) != BZ_OK) return rc2;
+        for (size_t i = 0; i < count; ++i)
+            if (lens[i]) copy_in(r->h_in[0] + in_off[i], ins[i], lens[i], 1);
+        if (total_in && (hipMemcpyAsync(ln.d_buf, r->h_in[0], (size_t)total_in, hipMemcpyHostToDevice, ln.st_io) != hipSuccess ||
+                         hipStreamSynchronize(ln.st_io) != hipSuccess))
+            return BZ_E_UNEXPECTED;
+        (void)bz_gpu_engine_set_verify(ln.g, env_verify() ? 1 : 0); // (a lane's engine may come from the cache: BZ_VERIFY decides here)
+        rc2 = bz_gpu_encode_batch_device(ln.g, level, ln.d_buf, in_off.data(), in_len.data(), count, ln.d_out, cap, out_off, out_len);
+        if (rc2 != BZ_OK) return rc2;
+        total_out = out_off[count - 1] + ((out_len[count - 1] + 3u) & ~(u64)3);
+        if ((rc2 = grow_pinned(&ln.h_out, &ln.h_out_cap, (size_t)total_out)) != BZ_OK) return rc2;
+        if (hipMemcpyAsync(ln.h_out, ln.d_out, (size_t)total_out, hipMemcpyDeviceToHost, ln.st_io) != hipSuccess ||
+            hipStreamSynchronize(ln.st_io) != hipSuccess)
+            return BZ_E_UNEXPECTED;
+        res = (u8 *)malloc((size_t)total_out);
+        if (!res) return BZ_E_NOMEM;
+        memcpy(res, ln.h_out, (size_t)total_out);
+        return BZ_OK;
+    };
+    rc = run();
+    if (rc == BZ_OK) {
+        resources_put(r);
+        *out = res;
+    } else {
+        resources_free(r);
+    }
+    return rc;
+}
+#endif

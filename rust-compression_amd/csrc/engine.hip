@@ -1264,6 +1264,178 @@ extern "C" int bz_gpu_encode_device(bz_gpu_engine *g, int level, const void *d_i
                            nullptr, d_out, cap, out_len, nullptr, nullptr);
 }
 
+// ---- many inputs, one stream each -------------------------------------------------------------------------------------
+// The pipeline behind the split takes `nb` independent blocks per launch and does not ask where they come from: the
+// one-block inputs of a batch are split by ONE launch (k_rle_batch, a workgroup per input), become the blocks of ONE
+// bz_gpu_encode_blocks call (sub-batches of ws_blocks, the fused-pass fallbacks, the block statistics and the self-check
+// as for any other call) and are framed by one k_assemble and one k_frame_batch launch over all their streams.
+//
+// One block for certain: RLE1 turns n bytes into at most 5 * (n / 4) + n % 4 (runs of exactly four), and the cut of
+// encoder.rs:692 fires only behind a run that is not the last one, so an image of at most 100000 * level - 19 bytes is
+// never cut.  Image slots: the exclusive sum of those bounds, each rounded up to 16, and 256 bytes of slack behind the
+// last (the single-input path sizes its image the same way).
+//
+// Inputs that may take several blocks go through bz_gpu_encode_device one at a time.  That path overwrites the image,
+// g->h_blocks and g->packed, and the place of a stream in d_out depends on the lengths of ALL streams in front of it.
+// Order chosen: the whole small batch FIRST, up to its bit strings -- they go to a buffer of their own (batch_packed),
+// and their lengths are on the host -- then the inputs in order: a large one is encoded straight into its final slot
+// of d_out (every length in front of it is known by then), a small one only gets its place.  The small streams are
+// written last.  The other order would have to park every large stream somewhere and copy it once the small lengths
+// are known.  (After a batch with large inputs bz_gpu_debug_block_stats describes the last of them, as after any
+// bz_gpu_encode_device call; after a batch of one-block inputs, all its blocks in input order.)
+static bool batch_one_block(u64 n, int level) { return 5u * (n / 4u) + n % 4u <= 100000ull * (u64)level - 19u; }
+
+extern "C" size_t bz_encode_batch_bound(const uint64_t *in_len, size_t count)
+{
+    size_t s = 0;
+    for (size_t i = 0; in_len && i < count; ++i) s += (bz_encode_bound((size_t)in_len[i]) + 3u) & ~(size_t)3;
+    return s;
+}
+
+extern "C" int bz_gpu_last_batch_stats(bz_gpu_engine *g, uint64_t out[4])
+{
+    if (!g || !out) return BZ_E_PARAM;
+    for (int i = 0; i < 4; ++i) out[i] = g->batch_stats[i];
+    return BZ_OK;
+}
+
+extern "C" int bz_gpu_encode_batch_device(bz_gpu_engine *g, int level, const void *d_in, const uint64_t *h_in_off,
+                                          const uint64_t *h_in_len, size_t count, void *d_out, size_t cap,
+                                          uint64_t *h_out_off, uint64_t *h_out_len)
+{
+    if (!g || level < 1 || level > 9) return BZ_E_PARAM;
+    if (count == 0) return BZ_OK;
+    if (!h_in_off || !h_in_len || !h_out_off || !h_out_len || !d_out) return BZ_E_PARAM;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 3u)) return BZ_E_PARAM;
+    u64 in_end = 0;
+    for (size_t i = 0; i < count; ++i) {
+        if ((h_in_off[i] & 15u) || h_in_off[i] < in_end || h_in_off[i] + h_in_len[i] < h_in_off[i]) return BZ_E_PARAM;
+        in_end = h_in_off[i] + h_in_len[i];
+    }
+    if (in_end && !d_in) return BZ_E_PARAM;
+    HIPCHK(hipSetDevice(g->device));
+    for (u64 &s : g->batch_stats) s = 0;
+
+    // ---- the one-block inputs: split, encode -------------------------------------------------------------
+    std::vector<RleBatchItem> items;
+    std::vector<size_t> small; // their input numbers
+    u64 image = 0, packed_words = 16;
+    for (size_t i = 0; i < count; ++i) {
+        if (!batch_one_block(h_in_len[i], level)) continue;
+        const u64 n = h_in_len[i];
+        items.push_back({h_in_off[i], n, image});
+        small.push_back(i);
+        image += (5u * (n / 4u) + n % 4u + 15u) & ~(u64)15;
+        if (n) packed_words += bz_encode_bound((size_t)n) / 4 + 2;
+    }
+    const size_t ns = small.size();
+    g->batch_stats[0] = ns;
+    g->batch_stats[1] = count - ns;
+    // as bz_gpu_partition_slab_begin leaves the engine, with the batch as "the input" (the self-check compares the
+    // decoded blocks with g->d_in + in_off)
+    g->level = level;
+    g->d_in = (const u8 *)d_in;
+    g->n_in = in_end;
+    g->onepass_done = false; // (the image buffer no longer holds what the last partition wrote)
+    g->h_blocks.clear();
+    g->h_crc.clear();
+    g->h_out.clear();
+    g->h_out_nblock.clear();
+    g->h_out_pass.clear();
+    for (double &t : g->t_stage) t = 0;
+    for (u64 &s : g->bwt_stats) s = 0;
+    for (u64 &s : g->round_active) s = 0;
+    std::vector<long long> block_of(count, -1); // input -> its block among the batch's blocks
+    std::vector<BlockDesc> bd(ns);
+    std::vector<u32> bc(ns);
+    int rc;
+    if (ns) {
+        if ((rc = g->rle.ensure(image + 256)) || (rc = g->batch_items.ensure(ns * sizeof(RleBatchItem))) ||
+            (rc = g->blocks_all.ensure(ns * sizeof(BlockDesc))) || (rc = g->crc_all.ensure(ns * 4)))
+            return rc;
+        HIPCHK(hipMemcpyAsync(g->batch_items.p, items.data(), ns * sizeof(RleBatchItem), hipMemcpyHostToDevice, g->st));
+        const int sp = span_begin(g, 0);
+        launch_rle_batch(g->st, g->d_in, g->batch_items.as<RleBatchItem>(), (u32)ns, g->crc_tab.as<u32>(), g->xp2.as<u32>(),
+                         g->rle.as<u8>(), g->blocks_all.as<BlockDesc>(), g->crc_all.as<u32>());
+        span_end(g, sp);
+        MAILCHK(g->st, {bd.data(), g->blocks_all.p, ns * sizeof(BlockDesc)}, {bc.data(), g->crc_all.p, ns * 4});
+        HIPCHK(hipGetLastError());
+        for (size_t j = 0; j < ns; ++j) {
+            if (bd[j].n == 0) continue; // an empty input: no block, a stream of header and trailer
+            block_of[small[j]] = (long long)g->h_blocks.size();
+            g->h_blocks.push_back(bd[j]);
+            g->h_crc.push_back(bc[j]);
+        }
+    }
+    const size_t nb = g->h_blocks.size();
+    std::vector<uint64_t> woff(nb + 1), blen(nb + 1);
+    std::vector<uint32_t> crc(nb + 1);
+    if (nb) {
+        size_t used = 0;
+        if ((rc = g->batch_packed.ensure(packed_words * 4)) != BZ_OK) return rc;
+        rc = bz_gpu_encode_blocks(g, 0, 1, g->batch_packed.p, packed_words, woff.data(), blen.data(), crc.data(), &used);
+        if (rc != BZ_OK) return rc;
+        g->batch_stats[2] = nb;
+        g->batch_stats[3] = (nb + g->ws_blocks - 1) / g->ws_blocks;
+    } else {
+        spans_collect(g);
+    }
+
+    // ---- the streams' places, the large inputs on the way ---------------------------------------------------------
+    std::vector<AsmBlock> ab;
+    std::vector<FrameItem> fr;
+    std::vector<std::pair<u64, u64>> zero; // byte ranges of d_out that hold small streams (runs of neighbours as one)
+    ab.reserve(nb);
+    fr.reserve(ns);
+    u64 cursor = 0, max_words = 0;
+    for (size_t i = 0; i < count; ++i) {
+        h_out_off[i] = cursor;
+        if (batch_one_block(h_in_len[i], level)) {
+            const long long k = block_of[i];
+            const u64 bits = 32u + (k >= 0 ? blen[(size_t)k] : 0u) + 80u, len = (bits + 7u) / 8u, slot = (len + 3u) & ~(u64)3;
+            if (cursor + slot > cap) return BZ_E_CAPACITY;
+            if (k >= 0) {
+                ab.push_back({woff[(size_t)k], blen[(size_t)k], cursor * 8u + 32u});
+                max_words = std::max<u64>(max_words, (blen[(size_t)k] + 31) / 32 + 1);
+            }
+            // the combined CRC of one block: rotl(0, 1) ^ crc (encoder.rs:237-238); of none: 0
+            fr.push_back({cursor / 4u, cursor * 8u + bits - 80u, k >= 0 ? crc[(size_t)k] : 0u, 0u});
+            if (!zero.empty() && zero.back().second == cursor) zero.back().second = cursor + slot;
+            else zero.push_back({cursor, cursor + slot});
+            h_out_len[i] = len;
+            cursor += slot;
+        } else {
+            size_t len = 0;
+            if (cursor >= cap) return BZ_E_CAPACITY;
+            rc = bz_gpu_encode_device(g, level, (const u8 *)d_in + h_in_off[i], (size_t)h_in_len[i], (u8 *)d_out + cursor,
+                                      (size_t)(cap - cursor), &len);
+            if (rc != BZ_OK) return rc;
+            h_out_len[i] = len;
+            cursor += ((u64)len + 3u) & ~(u64)3; // (bz_gpu_assemble has cleared the slot to its last word)
+        }
+    }
+
+    // ---- the small streams: zeros, blocks, frames ------------------------------------------------------------------
+    if (!fr.empty()) {
+        if ((rc = g->batch_frames.ensure(fr.size() * sizeof(FrameItem))) || (rc = g->asmlist.ensure((ab.size() + 1) * sizeof(AsmBlock))))
+            return rc;
+        const int sp = span_begin(g, 4);
+        for (const auto &z : zero) HIPCHK(hipMemsetAsync((u8 *)d_out + z.first, 0, z.second - z.first, g->st)); // (one range unless large inputs lie between)
+        if (!ab.empty()) {
+            HIPCHK(hipMemcpyAsync(g->asmlist.p, ab.data(), ab.size() * sizeof(AsmBlock), hipMemcpyHostToDevice, g->st));
+            for (size_t k0 = 0; k0 < ab.size(); k0 += 65535) // (grid.y is a 16-bit number)
+                launch_assemble(g->st, g->batch_packed.as<u32>(), g->asmlist.as<AsmBlock>() + k0,
+                                (u32)std::min<size_t>(ab.size() - k0, 65535), max_words, (u32 *)d_out);
+        }
+        HIPCHK(hipMemcpyAsync(g->batch_frames.p, fr.data(), fr.size() * sizeof(FrameItem), hipMemcpyHostToDevice, g->st));
+        launch_frame_batch(g->st, (u32 *)d_out, g->batch_frames.as<FrameItem>(), (u32)fr.size(), (u32)level);
+        span_end(g, sp);
+    }
+    spans_collect(g); // (waits for both streams: the host arrays above are free, the streams are in d_out)
+    HIPCHK(hipGetLastError());
+    return BZ_OK;
+}
+
 // ---- the whole stream over several GPUs: one process (one engine) per GPU --------------------------
 // Rank r splits its SLAB of the input (an equal share of the 4 KiB tiles), encodes the blocks that
 // end in it and hands their bit strings to rank 0, which assembles the serial stream.  What crosses

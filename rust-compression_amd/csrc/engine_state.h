@@ -76,6 +76,10 @@ struct bz_gpu_engine {
     size_t ws_blocks = 0; // blocks the batch workspace holds now (<= max_blocks)
     // own packed buffer / assemble list for the single-GPU convenience call
     DevBuf packed, gathered, asmlist;
+    // a batch of inputs (bz_gpu_encode_batch_device): the one-block inputs' records, their streams' frames and their bit
+    // strings (the inputs that may take several blocks go through `packed` one at a time while these are still needed)
+    DevBuf batch_items, batch_frames, batch_packed;
+    u64 batch_stats[4] = {0, 0, 0, 0}; // last batch: inputs through k_rle_batch, through the one-input path, blocks, sub-batches
     unsigned long long *h_active = nullptr; // pinned
     // results of the last encode
     std::vector<BlockOut> h_out;

@@ -82,6 +82,28 @@ __global__ void k_frame(u32 *__restrict__ out_words, int write_header, u32 level
     }
 }
 
+// header and trailer of MANY streams, one lane per stream: "BZh<level>" is the stream's first word, the 48-bit end magic
+// and the combined CRC go to trailer_bit.  The words are shared with nobody but k_assemble's edge words (atomic ORs too).
+__global__ __launch_bounds__(256) void k_frame_batch(u32 *__restrict__ out_words, const FrameItem *__restrict__ items,
+                                                     u32 count, u32 level)
+{
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const FrameItem f = items[i];
+    // `nbits` (<= 32) of v at bit position pos: at most two words
+    auto put = [&](u64 pos, u32 v, u32 nbits) {
+        const u32 sh = (u32)(pos & 31u);
+        const u64 x = (u64)v << (64u - nbits - sh);
+        const u32 hi = (u32)(x >> 32), lo = (u32)x;
+        if (hi) atomicOr(&out_words[pos >> 5], __builtin_bswap32(hi));
+        if (lo) atomicOr(&out_words[(pos >> 5) + 1u], __builtin_bswap32(lo));
+    };
+    put(f.first_word * 32u, 0x425A6830u + level, 32); // encoder.rs:246-250
+    put(f.trailer_bit, 0x177245u, 24);                // :280-285
+    put(f.trailer_bit + 24, 0x385090u, 24);
+    put(f.trailer_bit + 48, f.combined_crc, 32);      // :286-287
+}
+
 __global__ __launch_bounds__(256) void k_pack(const u32 *__restrict__ src, const PackBlock *__restrict__ pb,
                                                u32 *__restrict__ dst)
 {
@@ -103,6 +125,12 @@ void launch_frame(hipStream_t st, u32 *out_words, int write_header, u32 level, u
 {
     hipLaunchKernelGGL(k_frame, dim3(1), dim3(64), 0, st, out_words, write_header, level, carry_bits,
                        carry_byte, write_trailer, trailer_bit, combined_crc);
+}
+
+void launch_frame_batch(hipStream_t st, u32 *out_words, const FrameItem *d_items, u32 count, u32 level)
+{
+    if (count == 0) return;
+    hipLaunchKernelGGL(k_frame_batch, dim3((count + 255u) / 256u), dim3(256), 0, st, out_words, d_items, count, level);
 }
 
 void launch_pack(hipStream_t st, const u32 *src, const PackBlock *d_pb, u32 n_blocks, u32 *dst)

@@ -798,6 +798,160 @@ __global__ __launch_bounds__(RT, 3) void k_rle_onepass(const u8 *__restrict__ in
     }
 }
 
+// ---- the front end of a BATCH of one-block inputs: one workgroup per input --------------------------------
+// Every input of the batch is certain to be one block (5 * (len / 4) + len % 4 <= 100000 * level - 19), so there is no
+// cut to find and nothing to learn from another input: a workgroup walks ITS input in pieces of 4 KiB, 16 bytes per
+// thread, with seg_eq_mask / seg_emit_masks as k_rle_onepass, and carries from piece to piece in registers (the same
+// value in every thread) the run start that is live at the piece's first byte (the phase of a byte that continues it
+// is its distance from there modulo 255), the last byte of the piece in front and the image offset.  No look-back, no
+// ticket, no wait.  Nothing crosses an input's edges: the byte in front of the first piece and the byte behind the last
+// do not exist for the run detection (-1), and no address outside [in_off, in_off + len) is read.
+// Writes the image at rle + rle_off (a slot the host sized by the bound above), the block record and the block CRC =
+// CRC-32/BZIP2 of the input's bytes: every thread folds its own 16-byte segments, which lie 4 KiB apart, by Horner's
+// rule, and shifts the sum to the input's end once.  An empty input gives a record with n = 0.
+__global__ __launch_bounds__(RT) void k_rle_batch(const u8 *__restrict__ in, const RleBatchItem *__restrict__ items,
+                                                   const u32 *__restrict__ crc_tab, const u32 *__restrict__ xp2,
+                                                   u8 *__restrict__ rle, BlockDesc *__restrict__ blocks,
+                                                   u32 *__restrict__ out_crc)
+{
+    __shared__ u32 s_tab[256];
+    __shared__ int s_wmax[RT / 64];                // per wave: last run start of the piece (-1: none)
+    __shared__ u32 s_wsum[RT / 64], s_wx[RT / 64]; // ... bytes emitted; (at the end) CRC
+    __shared__ int s_fb[RT / 64], s_lb[RT / 64];   // ... first byte of lane 0, last byte of lane 63
+    __shared__ int s_next;                         // the first byte of the next piece (-1: the input ends)
+    __shared__ __attribute__((aligned(16))) u8 s_out[kRleTile / 4 * 5 + 64]; // (a piece that begins inside a chunk can emit a byte more than 5/4 of its own)
+
+    const u32 tid = threadIdx.x, l = lane_id(), wv = tid >> 6;
+    s_tab[tid] = crc_tab[tid];
+    const RleBatchItem it = items[blockIdx.x];
+    const u8 *src = in + it.in_off;
+    const u32 n = (u32)it.len;
+    u8 *dst = rle + it.rle_off; // 16-byte aligned
+    int run_start = -1, last_byte = -1; // live at the piece's first byte; the byte in front of it
+    u32 img = 0;                        // image bytes written so far
+    u32 acc = 0, acc_end = 0, crc_part = 0; // CRC of this thread's full segments, moved to position acc_end; of its one short segment
+    const u32 x_piece = xp2[12];        // x^(8 * 4096)
+    __syncthreads();
+
+    for (u32 base = 0; base < n; base += kRleTile) {
+        const u32 p0 = base + tid * 16u;
+        const u32 valid = p0 + 16u <= n ? 16u : (p0 < n ? n - p0 : 0u);
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (valid == 16u) {
+            v = *reinterpret_cast<const uint4 *>(src + p0);
+        } else {
+            u32 t[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (u32 k = 0; k < 16; ++k)
+                if (k < valid) t[k >> 2] |= (u32)src[p0 + k] << ((k & 3u) * 8u);
+            v = make_uint4(t[0], t[1], t[2], t[3]);
+        }
+        if (tid == 0) s_next = base + kRleTile < n ? (int)src[base + kRleTile] : -1;
+        if (l == 0) s_fb[wv] = (int)(v.x & 0xFFu);
+        if (l == 63) s_lb[wv] = (int)(v.w >> 24);
+        __syncthreads();
+        // the byte before and behind the segment: the neighbouring lane's, the neighbouring wave's, the neighbouring piece's
+        int pb = __shfl_up((int)(v.w >> 24), 1, 64);
+        int nb = __shfl_down((int)(v.x & 0xFFu), 1, 64);
+        if (l == 0) pb = wv > 0 ? s_lb[wv > 0 ? wv - 1 : 0] : last_byte;
+        if (l == 63) nb = wv + 1 < RT / 64 ? s_fb[wv + 1 < RT / 64 ? wv + 1 : 0] : s_next;
+        if (valid == 0u || p0 == 0u) pb = -1;
+        if (valid == 0u || p0 + valid >= n) nb = -1;
+        const int piece_last_byte = s_lb[RT / 64 - 1]; // (means something only when another piece follows: this one is full then)
+        const u32 w[4] = {v.x, v.y, v.z, v.w};
+        const u32 V = (1u << valid) - 1u;
+        const u32 E = seg_eq_mask(v, pb) & V;
+        const u32 S = ~E & V;
+        const int last = S ? (int)(p0 + 31u - (u32)__builtin_clz(S)) : -1;
+        const int inc = wave_incl_max32(last);
+        if (l == 63) s_wmax[wv] = inc;
+        // CRC of the segment
+        u32 c = 0, lastb = 0;
+#pragma unroll
+        for (u32 k = 0; k < 16; ++k) {
+            const u32 byte = (w[k >> 2] >> ((k & 3u) * 8u)) & 0xFFu;
+            if (k < valid) c = s_tab[(c >> 24) ^ byte] ^ (c << 8);
+            if (k + 1u == valid) lastb = byte;
+        }
+        if (valid == 16u) {
+            acc = gf_mulmod(acc, x_piece) ^ c;
+            acc_end = p0 + 16u;
+        } else if (valid > 0u) {
+            crc_part = c; // (the input ends with it)
+        }
+        __syncthreads();
+        int ex = __shfl_up(inc, 1, 64); // run start live at the segment's first byte
+        if (l == 0) ex = -1;
+        int piece_max = -1;
+        for (u32 k = 0; k < RT / 64; ++k) {
+            if (k < wv) ex = s_wmax[k] > ex ? s_wmax[k] : ex;
+            piece_max = s_wmax[k] > piece_max ? s_wmax[k] : piece_max;
+        }
+        if (run_start > ex) ex = run_start;
+        const u32 c0 = ex >= 0 ? (p0 - (u32)ex) % 255u : 0u; // (byte 0 of the input is a run start: c0 is not looked at)
+        u32 lt4, cg;
+        seg_emit_masks(E, V, c0, nb != (int)lastb, lt4, cg);
+        const u32 cnt = (u32)__builtin_popcount(lt4) + (u32)__builtin_popcount(cg);
+        const u32 incs = wave_incl_sum(cnt);
+        if (l == 63) s_wsum[wv] = incs;
+        __syncthreads();
+        u32 below = 0, tot = 0;
+        for (u32 k = 0; k < RT / 64; ++k) {
+            if (k < wv) below += s_wsum[k];
+            tot += s_wsum[k];
+        }
+        // the piece's bytes, staged at the offset their destination has inside a 16-byte line (k_rle_scatter)
+        const u32 a0 = img & 15u;
+        {
+            u32 o = a0 + below + incs - cnt;
+            u32 ph = c0; // the phase of the byte at hand
+#pragma unroll
+            for (u32 k = 0; k < 16; ++k) {
+                if ((S >> k) & 1u) ph = 0;
+                if ((lt4 >> k) & 1u) s_out[o++] = (u8)(w[k >> 2] >> ((k & 3u) * 8u));
+                if ((cg >> k) & 1u) s_out[o++] = (u8)(ph - 3u);
+                ph = ph == 254u ? 0u : ph + 1u;
+            }
+        }
+        __syncthreads();
+        u8 *line0 = dst + (img - a0); // 16-byte aligned
+        const u32 end = a0 + tot, nlines = (end + 15u) >> 4;
+        for (u32 q = tid; q < nlines; q += RT) {
+            const u32 lo = q * 16u;
+            if (lo >= a0 && lo + 16u <= end) {
+                *reinterpret_cast<uint4 *>(line0 + lo) = *reinterpret_cast<const uint4 *>(s_out + lo);
+            } else {
+                const u32 b0 = lo > a0 ? lo : a0, b1 = lo + 16u < end ? lo + 16u : end;
+                for (u32 b = b0; b < b1; ++b) line0[b] = s_out[b];
+            }
+        }
+        // what the next piece needs (its first barrier stands between these reads of s_out and its writes)
+        if (piece_max > run_start) run_start = piece_max;
+        last_byte = piece_last_byte;
+        img += tot;
+    }
+
+    // the CRC: every thread's sum moved to the input's end, all of them folded, init and final NOT (k_block_crc)
+    u32 x = crc_part;
+    if (acc_end) x ^= gf_mulmod(acc, gf_xpow_bytes(n - acc_end, xp2));
+    x = wave_xor(x);
+    if (l == 0) s_wx[wv] = x;
+    __syncthreads();
+    if (tid == 0) {
+        u32 r = 0;
+        for (u32 k = 0; k < RT / 64; ++k) r ^= s_wx[k];
+        r ^= gf_mulmod(0xFFFFFFFFu, gf_xpow_bytes(n, xp2));
+        out_crc[blockIdx.x] = ~r;
+        BlockDesc d;
+        d.rle_off = it.rle_off;
+        d.in_off = it.in_off;
+        d.in_end = it.in_off + it.len;
+        d.n = img;
+        d.pad = 0;
+        blocks[blockIdx.x] = d;
+    }
+}
+
 // ---- kernel F: the chain of block cuts (one workgroup) -------------------------------------
 // A cut depends on the previous one, but only weakly: a block holds between L and L+4 bytes
 // (L = 100000*level-19; the last chunk adds at most 5), so the k-th next block starts inside
@@ -1535,6 +1689,15 @@ void launch_block_crc(hipStream_t st, const u8 *d_in, const BlockDesc *d_blocks,
     if (nblocks == 0) return;
     hipLaunchKernelGGL(k_block_crc, dim3(nblocks), dim3(RT), 0, st, d_in, d_blocks, crc_tab, xp2, tile_crc,
                        d_crc);
+}
+
+
+// The front end of a batch of one-block inputs: one workgroup per input, a record and a CRC per input (k_rle_batch).
+void launch_rle_batch(hipStream_t st, const u8 *d_in, const RleBatchItem *d_items, u32 count, const u32 *crc_tab,
+                      const u32 *xp2, u8 *d_rle, BlockDesc *d_blocks, u32 *d_crc)
+{
+    if (count == 0) return;
+    hipLaunchKernelGGL(k_rle_batch, dim3(count), dim3(RT), 0, st, d_in, d_items, crc_tab, xp2, d_rle, d_blocks, d_crc);
 }
 
 } // namespace bzgpu

@@ -122,6 +122,31 @@ class BZip2Encoder {
     }
     void verify_stats(uint64_t out[4]) { bz_enc_verify_stats(h_, out); }
 
+    // Many independent inputs in one call (bz_encode_batch): element i of the result is the stream a
+    // BZip2Encoder(level) makes of inputs[i] with Action::Finish, bit for bit; inputs that are certain to be one block
+    // are encoded together.  `inputs`: any range of byte ranges with data() and size() (a span of spans, a vector of
+    // vectors).
+    template <class Spans>
+    static Result<std::vector<std::vector<uint8_t>>> encode_batch(int level, const Spans &inputs, int device = 0)
+    {
+        using R = Result<std::vector<std::vector<uint8_t>>>;
+        std::vector<const uint8_t *> ptrs;
+        std::vector<size_t> lens;
+        for (const auto &x : inputs) {
+            ptrs.push_back(reinterpret_cast<const uint8_t *>(x.data()));
+            lens.push_back(x.size());
+        }
+        std::vector<uint64_t> off(ptrs.size()), len(ptrs.size());
+        uint8_t *out = nullptr;
+        const int rc = bz_encode_batch(level, device, ptrs.data(), lens.data(), ptrs.size(), &out, off.data(), len.data());
+        if (rc == BZ_E_PARAM) throw std::invalid_argument("invalid level"); // the reference panics
+        if (rc != BZ_OK) return R::Err(from_status(rc));
+        std::vector<std::vector<uint8_t>> streams(ptrs.size());
+        for (size_t i = 0; i < ptrs.size(); ++i) streams[i].assign(out + off[i], out + off[i] + len[i]);
+        bz_free(out);
+        return R::Ok(std::move(streams));
+    }
+
     // Encoder::next (src/traits/encoder.rs:87-92, src/bzip2/encoder.rs:120-158)
     template <class I, class S> std::optional<Result<uint8_t>> next(I &it, const S &end, Action action)
     {

@@ -30,6 +30,9 @@ extern "C" {
     pub fn bz_enc_destroy(e: *mut bz_enc);
     pub fn bz_enc_set_verify(e: *mut bz_enc, on: i32) -> i32;
     pub fn bz_enc_verify_stats(e: *mut bz_enc, out: *mut u64) -> i32;
+    // many inputs, one stream each, in one pass of the pipeline; *out is released with bz_free
+    pub fn bz_encode_batch(level: i32, device: i32, ins: *const *const u8, lens: *const usize, count: usize, out: *mut *mut u8, out_off: *mut u64, out_len: *mut u64) -> i32;
+    pub fn bz_free(p: *mut c_void);
 
     // section 3: BZip2Decoder (src/bzip2/decoder.rs:583-612)
     pub fn bz_dec_create(out: *mut *mut bz_dec, device: i32) -> i32;

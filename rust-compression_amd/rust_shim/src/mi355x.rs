@@ -2,6 +2,9 @@
 //! one of `CompressionError`'s three variants.
 use core::sync::atomic::{AtomicI32, Ordering};
 
+use alloc::vec::Vec;
+
+use crate::error::CompressionError;
 use crate::ffi;
 
 static LAST_STATUS: AtomicI32 = AtomicI32::new(0);
@@ -43,6 +46,31 @@ pub fn last_status() -> Option<Status> {
         0 => None,
         rc => Some(Status::from_code(rc)),
     }
+}
+
+/// Many independent inputs in one call (`bz_encode_batch`, device 0): element `i` of the result is the stream
+/// `inputs[i].iter().cloned().encode(&mut BZip2Encoder::new(level), Action::Finish)` collects, bit for bit.  Inputs that
+/// are certain to be one block are encoded together, however many there are.  Panics on a level outside 1..=9, as
+/// `BZip2Encoder::new` does.
+pub fn encode_batch(level: usize, inputs: &[&[u8]]) -> Result<Vec<Vec<u8>>, CompressionError> {
+    assert!((1..=9).contains(&level), "invalid level");
+    let ptrs: Vec<*const u8> = inputs.iter().map(|x| x.as_ptr()).collect();
+    let lens: Vec<usize> = inputs.iter().map(|x| x.len()).collect();
+    let mut off: Vec<u64> = Vec::new();
+    off.resize(inputs.len(), 0);
+    let mut len = off.clone();
+    let mut out: *mut u8 = core::ptr::null_mut();
+    let rc = unsafe {
+        ffi::bz_encode_batch(level as i32, 0, ptrs.as_ptr(), lens.as_ptr(), inputs.len(), &mut out, off.as_mut_ptr(), len.as_mut_ptr())
+    };
+    if rc != ffi::BZ_OK {
+        return Err(CompressionError::from_status(rc));
+    }
+    let streams = (0..inputs.len())
+        .map(|i| unsafe { core::slice::from_raw_parts(out.add(off[i] as usize), len[i] as usize) }.to_vec())
+        .collect();
+    unsafe { ffi::bz_free(out as *mut core::ffi::c_void) };
+    Ok(streams)
 }
 
 pub(crate) fn note_status(rc: i32) {
