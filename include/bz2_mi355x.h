@@ -474,6 +474,38 @@ int bz_gpu_last_decode_timings(bz_gpu_engine *g, double out_seconds[5]);
  * started without the full 48-bit magic */
 int bz_gpu_last_decode_stats(bz_gpu_engine *g, uint64_t out[4]);
 
+/* Many independent streams in one call.  Entry i is the h_in_len[i] bytes at d_in + h_in_off[i] (d_in 4-byte aligned,
+ * every offset a multiple of 4, ranges in ascending order without overlap, the allocation reaches to the next multiple
+ * of 4 behind the last entry; bytes between entries are never read as input of any entry) -- exactly what
+ * bz_gpu_encode_batch_device writes: its (d_out, h_out_off, h_out_len) are valid (d_in, h_in_off, h_in_len) here.
+ * The result of entry i is that of bz_gpu_decode_device on its bytes ALONE: the same bytes in front of the verdict
+ * (those of a block whose CRC is wrong included), written to d_out + h_out_off[i] (h_out_len[i] bytes), and the same
+ * verdict -- BZ_OK, BZ_E_DATA, BZ_E_MAGIC_FIRST or BZ_E_MAGIC -- in h_verdict[i].  An entry may hold several streams (its
+ * stream count starts at 1); an empty entry is BZ_E_MAGIC_FIRST without bytes; no entry's verdict changes another
+ * entry's result.  The RETURN VALUE is the infrastructure status only: BZ_OK also when entries carry decoder errors.
+ * The five arrays are HOST arrays of `count` entries.
+ * Every h_out_off[i] is a multiple of 16 and the ranges do not overlap, so (d_out, h_out_off, h_out_len) are valid
+ * inputs of bz_gpu_encode_batch_device.  Offsets follow each entry's rebuilt length BEFORE its CRCs are looked at.
+ * The scan, the Huffman stage and the record chains run over all entries of a GROUP (consecutive entries whose
+ * block-magic candidates fit the workspace: BZ_DEC_BATCH, default 4096) in one launch each, and their true blocks are
+ * rebuilt together; these entries lie in input order.  An entry with more candidates than a group holds, or with a
+ * block that lacks its full 48-bit magic, takes the path of bz_gpu_decode_device on its own range: those lie behind all
+ * the others, in input order among themselves.  Bytes of d_out outside the reported ranges are unspecified; nothing is
+ * written at or behind d_out + cap.
+ * d_out == NULL: sizes only (nothing is written, CRCs are not checked): h_out_off are those of the real call,
+ * h_out_len[i] can exceed the real call's only for entries that a CRC turns into BZ_E_DATA, and the capacity the real
+ * call needs is the largest h_out_off[i] + h_out_len[i] of this one.
+ * BZ_E_CAPACITY: cap too small.  BZ_E_PARAM: a null engine, a null array with count > 0, a misaligned d_in or offset,
+ * ranges that overlap or are out of order.  count == 0: BZ_OK, nothing is touched.
+ * bz_gpu_last_decode_timings and bz_gpu_last_decode_stats hold sums over the call afterwards. */
+int bz_gpu_decode_batch_device(bz_gpu_engine *g, const void *d_in,
+                               const uint64_t *h_in_off, const uint64_t *h_in_len, size_t count,
+                               void *d_out, size_t cap,
+                               uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_verdict);
+/* The last bz_gpu_decode_batch_device call: [0] entries decoded by the batch path  [1] entries that took the
+ * one-stream path  [2] blocks rebuilt for the entries of [0]  [3] groups. */
+int bz_gpu_last_decode_batch_stats(bz_gpu_engine *g, uint64_t out[4]);
+
 /* One-shot over host buffers: `in.iter().cloned().decode(&mut BZip2Decoder::new())`
  * collected until None or the first Err.  *out (malloc'ed, release with
  * bz_free) holds the bytes yielded before the verdict, also when that is an error.
@@ -482,6 +514,15 @@ int bz_gpu_last_decode_stats(bz_gpu_engine *g, uint64_t out[4]);
  * sub-batch by sub-batch beside the kernels of the next one. */
 int bz_decode_buffer(int device, const uint8_t *in, size_t in_len,
                      uint8_t **out, size_t *out_len);
+
+/* The same for many independent streams (the host form of bz_gpu_decode_batch_device, mirroring bz_encode_batch):
+ * entry i is bz_decode_buffer(device, ins[i], lens[i]) -- its bytes at *out + out_off[i] (out_len[i] of them), its
+ * verdict in verdict[i]; the return value is the infrastructure status only.  The entries are packed at 4-byte-aligned
+ * offsets, uploaded once and decoded on an engine of the decode cache; the bytes come down group by group into ONE
+ * malloc'ed buffer (release with bz_free; offsets are multiples of 16, relative to it).  count == 0: BZ_OK, *out is an
+ * empty buffer, no device is touched. */
+int bz_decode_batch(int device, const uint8_t *const *ins, const size_t *lens, size_t count,
+                    uint8_t **out, uint64_t *out_off, uint64_t *out_len, int32_t *verdict);
 
 /* Streaming context == BZip2Decoder as the DecodeIterator drives it
  * (src/traits/decoder.rs:73-86): compressed bytes in (bz_dec_write), end of

@@ -27,7 +27,7 @@ import sys
 from . import _build
 
 __all__ = ["Action", "CompressionError", "BZip2Error", "BZip2Encoder", "BZip2Decoder", "encode", "decode",
-           "compress", "compress_batch", "encode_batch_bound", "decompress", "GpuEngine", "release_cached_resources", "last_call_phases",
+           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "GpuEngine", "release_cached_resources", "last_call_phases",
            "build", "lib", "device_count", "encode_bound", "shard_window", "rccl_lib", "rccl_unique_id", "RcclComm"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -89,6 +89,7 @@ EXPORTS = [
     "bz_gpu_last_bwt_stats", "bz_gpu_cut_stats", "bz_gpu_last_bwt_rounds", "bz_gpu_profile_enable", "bz_gpu_profile_kernels", "bz_gpu_profile_get",
     "bz_gpu_debug_bwt", "bz_gpu_debug_code_lengths", "bz_gpu_debug_block_stats", "bz_gpu_debug_block_sections",
     "bz_gpu_decode_device", "bz_gpu_decode_device_sharded", "bz_gpu_last_decode_timings", "bz_gpu_last_decode_stats", "bz_decode_buffer",
+    "bz_gpu_decode_batch_device", "bz_gpu_last_decode_batch_stats", "bz_decode_batch",
     "bz_dec_create", "bz_dec_write", "bz_dec_end", "bz_dec_read", "bz_dec_pending", "bz_dec_destroy",
     "df_encode_bound", "df_gpu_encode_device", "df_gpu_last_timings", "df_gpu_last_stats", "df_gpu_debug_codes",
     "df_gpu_debug_blocks", "df_encode_buffer", "df_gpu_encode_device_dict", "df_encode_buffer_dict", "df_enc_create_dict",
@@ -205,6 +206,10 @@ def lib():
     L.bz_gpu_last_decode_timings.argtypes = [vp, C.POINTER(C.c_double)]
     L.bz_gpu_last_decode_stats.argtypes = [vp, u64p]
     L.bz_decode_buffer.argtypes = [C.c_int, C.c_char_p, sz, C.POINTER(u8p), szp]
+    i32p = C.POINTER(C.c_int32)
+    L.bz_gpu_decode_batch_device.argtypes = [vp, vp, u64p, u64p, sz, vp, sz, u64p, u64p, i32p]
+    L.bz_gpu_last_decode_batch_stats.argtypes = [vp, u64p]
+    L.bz_decode_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), szp, sz, C.POINTER(u8p), u64p, u64p, i32p]
     L.bz_dec_create.argtypes = [C.POINTER(vp), C.c_int]
     L.bz_dec_write.argtypes = [vp, C.c_char_p, sz]
     L.bz_dec_end.argtypes = [vp]
@@ -749,6 +754,26 @@ def decompress(data, device=0):
         lib().bz_free(out)
 
 
+def decompress_batch(datas, device=0):
+    """Many independent streams in one call (bz_decode_batch) -> list of (bytes yielded, verdict code): element i is
+    decompress(datas[i]).  An entry's verdict is its own -- a bad record hides nothing behind it; CompressionError is
+    raised for infrastructure errors only."""
+    datas = [d if isinstance(d, bytes) else bytes(d) for d in datas]
+    k = len(datas)
+    ins = (C.c_char_p * max(k, 1))(*datas)
+    lens = (C.c_size_t * max(k, 1))(*[len(d) for d in datas])
+    off = (C.c_uint64 * max(k, 1))()
+    ln = (C.c_uint64 * max(k, 1))()
+    verdicts = (C.c_int32 * max(k, 1))()
+    out = C.POINTER(C.c_uint8)()
+    _check(lib().bz_decode_batch(device, ins, lens, k, C.byref(out), off, ln, verdicts))
+    try:
+        base = C.addressof(out.contents) if k else 0
+        return [(C.string_at(base + off[i], ln[i]), int(verdicts[i])) for i in range(k)]
+    finally:
+        lib().bz_free(out)
+
+
 class GpuEngine:
     """Device-resident engine (section 2 of the C ABI).  Pointers are plain ints
     (e.g. torch.Tensor.data_ptr())."""
@@ -901,6 +926,29 @@ class GpuEngine:
         if rc != BZ_OK and rc not in _DECODER_VERDICTS:
             raise CompressionError(rc)
         return out_len.value, rc
+
+    def decode_batch_device(self, d_in, in_off, in_len, d_out, cap):
+        """Many independent streams (bz_gpu_decode_batch_device): entry i is the in_len[i] bytes at d_in + in_off[i]
+        (offsets multiples of 4, in ascending order -- what encode_batch_device returns); -> (out_off, out_len, verdicts),
+        the bytes of entry i at d_out + out_off[i] (multiples of 16).  d_out = None: sizes only."""
+        _settle()
+        k = len(in_off)
+        if len(in_len) != k:
+            raise ValueError("decode_batch_device: in_off and in_len differ in length")
+        a_off = (C.c_uint64 * max(k, 1))(*in_off)
+        a_len = (C.c_uint64 * max(k, 1))(*in_len)
+        o_off = (C.c_uint64 * max(k, 1))()
+        o_len = (C.c_uint64 * max(k, 1))()
+        verdicts = (C.c_int32 * max(k, 1))()
+        _check(lib().bz_gpu_decode_batch_device(self._h, d_in, a_off, a_len, k, d_out, cap, o_off, o_len, verdicts))
+        return list(o_off[:k]), list(o_len[:k]), [int(v) for v in verdicts[:k]]
+
+    def decode_batch_stats(self):
+        """The last decode_batch_device call: [0] entries decoded by the batch path, [1] entries that took the
+        one-stream path, [2] blocks rebuilt for the former, [3] groups (bz_gpu_last_decode_batch_stats)."""
+        s = (C.c_uint64 * 4)()
+        _check(lib().bz_gpu_last_decode_batch_stats(self._h, s))
+        return [int(x) for x in s]
 
     def decode_device_sharded(self, d_in, n, d_out, cap, rank, world, allgather):
         """One rank of a multi-GPU decode.  `allgather(send: bytes) -> bytes` returns the concatenation of

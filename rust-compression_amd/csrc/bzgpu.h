@@ -508,6 +508,33 @@ struct DecArgs {
 void launch_dec_scan(hipStream_t st, const u8 *in, u64 nbytes, DecCand *cands, u32 cap, u32 *count);
 void launch_dec_blocks(hipStream_t st, const u8 *in, u64 nbytes, const DecCand *cands, u32 ncand, DecBlockInfo *info,
                        u16 *sym, u8 *sel_scratch);
+// ---- many independent streams in one call (bz_gpu_decode_batch_device) ----
+// One entry of the call: its bytes (off is a multiple of 4, len > 0: empty entries never reach the device) and its
+// candidates in the list sorted by (entry, bitpos).  ncand == kDecEntrySkip: the entry is not chained here (it has more
+// candidates than a group holds and takes the one-stream path).
+constexpr u32 kDecEntrySkip = 0xFFFFFFFFu;
+struct DecEntry {
+    u64 off, len;
+    u32 first_cand, ncand;
+};
+// what k_dec_chain_batch says about an entry, and about a candidate
+enum : u32 { kChainOk = 0, kChainData = 1, kChainMagicFirst = 2, kChainMagic = 3 }; // -> BZ_OK, BZ_E_DATA, BZ_E_MAGIC_FIRST, BZ_E_MAGIC
+struct DecChainEntry {
+    u32 verdict;   // kChain*: what the record chain ends with
+    u32 streams;   // stream number the chain ended in (starts at 1)
+    u32 irregular; // 1: a block without its full magic -- the chain stopped, the entry takes the one-stream path
+    u32 ntrue;     // true blocks
+};
+struct DecChainCand {
+    u32 is_true, max_len; // a block of the chain, and 100000 * level of its stream
+    u32 stored_crc, nsym; // (copied from its DecBlockInfo: one copy back per group serves the host)
+};
+void launch_dec_scan_batch(hipStream_t st, const u8 *in, u64 span0, u64 span_end, const DecEntry *ents, u32 nent,
+                           DecCand *cands, u32 cap, u32 *count);
+void launch_dec_blocks_batch(hipStream_t st, const u8 *in, const DecEntry *ents, const DecCand *cands, u32 ncand,
+                             DecBlockInfo *info, u16 *sym, u8 *sel_scratch);
+void launch_dec_chain_batch(hipStream_t st, const u8 *in, const DecEntry *ents, u32 e0, u32 ne, const DecCand *cands,
+                            u32 cand0, const DecBlockInfo *info, DecChainEntry *out_ent, DecChainCand *out_cand);
 void launch_dec_mtf(hipStream_t st, const DecArgs &a, KernelProf *prof, int *rec);
 void launch_dec_gather_windows(hipStream_t st, const u8 *in, u64 nbytes, const u64 *bases, u32 nw, u8 *out);
 void launch_dec_walks(hipStream_t st, const DecArgs &a, u32 walk_wgs, hipStream_t st2, hipEvent_t ev_a, hipEvent_t ev_b,

@@ -47,8 +47,10 @@ struct DecWorkspace {
     DevBuf cands, count, info, sym, sel, slot, nbmax, perm, chunk_emit, tt_len, err, L, T, X, samp_next, samp_len,
         samp_off, cycle_len, sub_trans, sub_off, sub_state, work_ctr, walk_meta, seg_buf, seg_cont, long_list, out_len, thist, tbase, crc, out_base, staging, staging2, cand_all;
     hipEvent_t ev_a = nullptr, ev_b = nullptr; // fork / join of the second walk
+    DevBuf ents, chain;                        // batched decode: the entry table, a group's chain results
     double t_stage[5] = {0, 0, 0, 0, 0};
     u64 stats[4] = {0, 0, 0, 0}; // candidates, blocks, streams, forced blocks
+    u64 bstats[4] = {0, 0, 0, 0}; // last batch call: entries on the batch path, on the one-stream path, blocks, groups
 };
 
 void dec_workspace_free(DecWorkspace *w)
@@ -255,6 +257,73 @@ struct Shard {
 };
 } // namespace
 
+// blocks in flight per D1 launch: BZ_DEC_BATCH, default 4096 (about 13 MB of workspace each)
+static u32 dec_batch_slots()
+{
+    u32 B = 4096;
+    if (const char *e = getenv("BZ_DEC_BATCH")) {
+        const long v = atol(e);
+        if (v >= 1 && v <= 65536) B = (u32)v;
+    }
+    return B;
+}
+// ... and never more of them than about half of the free HBM holds (the decoded bytes need room too)
+static u32 dec_fit_slots(const DecWorkspace *w, u32 B)
+{
+    const size_t per_slot = sizeof(DecCand) + sizeof(DecBlockInfo) + (size_t)kMtfStride * 2 + 32768 + 8 +
+                            (size_t)kMaxMtfChunks * 260 + (size_t)kSlot * 6 + (size_t)kDecSamples * (16 + kSegCap) +
+                            (size_t)kDecSubs * 21 + (size_t)kTilesPerBlock * 1024 + 2048;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && w->slots < (size_t)B + kForcedSlots) {
+        const size_t have = w->slots * per_slot; // what the workspace already holds is free to reuse
+        const size_t fit = (free_b / 2 + have) / per_slot;
+        if (fit < (size_t)B + kForcedSlots) B = fit > kForcedSlots + 1 ? (u32)(fit - kForcedSlots) : 1u;
+    }
+    return B;
+}
+// the workspace behind a DecArgs (the caller sets nb, slot and nblock_max), and the launch shapes that follow the
+// largest block of the blocks at hand
+static void dec_args_bind(const DecWorkspace *w, DecArgs &a)
+{
+    a.info = w->info.as<DecBlockInfo>();
+    a.sym = w->sym.as<u16>();
+    a.perm = w->perm.as<u8>();
+    a.chunk_emit = w->chunk_emit.as<u32>();
+    a.tt_len = w->tt_len.as<u32>();
+    a.err = w->err.as<u32>();
+    a.L = w->L.as<u8>();
+    a.T = w->T.as<u32>();
+    a.X = w->X.as<u8>();
+    a.samp_next = w->samp_next.as<u32>();
+    a.samp_len = w->samp_len.as<u32>();
+    a.samp_off = w->samp_off.as<u32>();
+    a.cycle_len = w->cycle_len.as<u32>();
+    a.sub_trans = w->sub_trans.as<uint4>();
+    a.sub_off = w->sub_off.as<u32>();
+    a.sub_state = w->sub_state.as<u8>();
+    a.work_ctr = w->work_ctr.as<u32>();
+    a.walk_meta = w->walk_meta.as<uint4>();
+    a.seg_buf = w->seg_buf.as<u8>();
+    a.seg_cont = w->seg_cont.as<u32>();
+    a.long_list = w->long_list.as<u32>();
+    a.out_len = w->out_len.as<u32>();
+    a.thist = w->thist.as<u32>();
+    a.tbase = w->tbase.as<u32>();
+    a.crc = w->crc.as<u32>();
+}
+static void dec_args_shape(DecArgs &a, u32 max_bytes, u32 max_nsym)
+{
+    // The chunk kernels: the workgroups the largest block's chunks need, made ODD.  Workgroups go round the eight
+    // XCDs and, inside an XCD, round its four shader engines: with FEW filled workgroups per block at a stride
+    // that shares a factor with 4 (level 1: one filled workgroup per block, the other 13 of a full slot's 14
+    // idle) the filled ones met on half or a quarter of the shader engines -- MTF stage of 1 GiB at level 1:
+    // 15.3 ms with 1 workgroup per block, 30 with 2, 59 with 4, 17 with 3 or 7, 32 with 14, 123 with 56.
+    const u32 cw_full = (kMaxMtfChunks + 255) / 256, chunks = (max_nsym + kMtfChunk - 1) / kMtfChunk;
+    a.cw = std::min<u32>(cw_full, std::max<u32>(1u, (chunks + 255) / 256)) | 1u;
+    a.tiles = std::min<u32>(kTilesPerBlock, (max_bytes + kSortTile - 1) / kSortTile);
+    a.sub_wgs = std::min<u32>((kDecSubs + 255) / 256, ((max_bytes + 63) / 64 + 255) / 256);
+}
+
 // Decodes d_in[n].  Returns an infrastructure status (BZ_OK, BZ_E_NOMEM, BZ_E_UNEXPECTED,
 // BZ_E_CAPACITY); the decoder's own verdict goes to *verdict (BZ_OK, BZ_E_DATA, BZ_E_MAGIC_FIRST,
 // BZ_E_MAGIC) and the bytes produced in front of it to sink.produced.
@@ -320,11 +389,7 @@ static int decode_core(bz_gpu_engine *g, const u8 *d_in, u64 n, Sink &sink, int 
     const size_t nc = cands.size();
     w->stats[0] = nc;
 
-    u32 B = 4096; // about 13 MB of workspace per block in flight
-    if (const char *e = getenv("BZ_DEC_BATCH")) {
-        const long v = atol(e);
-        if (v >= 1 && v <= 65536) B = (u32)v;
-    }
+    u32 B = dec_batch_slots();
     const u32 walk_wgs = 256; // persistent walker workgroups (bounds the window of blocks being walked; 128 ... 1024 measured: profiles/r04_decode_walk_schedule.md)
     size_t c0 = 0, c1 = nc; // this rank's candidates
     if (sh) {
@@ -334,18 +399,7 @@ static int decode_core(bz_gpu_engine *g, const u8 *d_in, u64 n, Sink &sink, int 
     }
     if (nc < B) B = (u32)(nc ? nc : 1);
     const u32 B_want = B;
-    {
-        // never plan for more than about half of the free HBM (the decoded bytes need room too)
-        const size_t per_slot = sizeof(DecCand) + sizeof(DecBlockInfo) + (size_t)kMtfStride * 2 + 32768 + 8 +
-                                (size_t)kMaxMtfChunks * 260 + (size_t)kSlot * 6 + (size_t)kDecSamples * (16 + kSegCap) +
-                                (size_t)kDecSubs * 21 + (size_t)kTilesPerBlock * 1024 + 2048;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && w->slots < (size_t)B + kForcedSlots) {
-            const size_t have = w->slots * per_slot; // what the workspace already holds is free to reuse
-            const size_t fit = (free_b / 2 + have) / per_slot;
-            if (fit < (size_t)B + kForcedSlots) B = fit > kForcedSlots + 1 ? (u32)(fit - kForcedSlots) : 1u;
-        }
-    }
+    B = dec_fit_slots(w, B);
     if (sh && B < B_want) return BZ_E_NOMEM; // a rank's share has to fit one batch (reported to the peers by the caller)
     int inject_rank = -1, inject_phase = -1; // (tests) BZ_DEC_SHARD_FAIL=<rank>:<phase>: that rank fails on its own there
     if (sh)
@@ -681,43 +735,11 @@ static int decode_core(bz_gpu_engine *g, const u8 *d_in, u64 n, Sink &sink, int 
                     max_bytes = std::max(max_bytes, bmax[s0 + i]);
                     max_nsym = std::max(max_nsym, hslot[bslot[s0 + i]].nsym);
                 }
-                // The chunk kernels: the workgroups the largest block's chunks need, made ODD.  Workgroups go round the eight
-                // XCDs and, inside an XCD, round its four shader engines: with FEW filled workgroups per block at a stride
-                // that shares a factor with 4 (level 1: one filled workgroup per block, the other 13 of a full slot's 14
-                // idle) the filled ones met on half or a quarter of the shader engines -- MTF stage of 1 GiB at level 1:
-                // 15.3 ms with 1 workgroup per block, 30 with 2, 59 with 4, 17 with 3 or 7, 32 with 14, 123 with 56.
-                const u32 cw_full = (kMaxMtfChunks + 255) / 256, chunks = (max_nsym + kMtfChunk - 1) / kMtfChunk;
-                a.cw = std::min<u32>(cw_full, std::max<u32>(1u, (chunks + 255) / 256)) | 1u;
-                a.tiles = std::min<u32>(kTilesPerBlock, (max_bytes + kSortTile - 1) / kSortTile);
-                a.sub_wgs = std::min<u32>((kDecSubs + 255) / 256, ((max_bytes + 63) / 64 + 255) / 256);
+                dec_args_shape(a, max_bytes, max_nsym);
             }
             a.slot = w->slot.as<u32>() + s0;
-            a.info = w->info.as<DecBlockInfo>();
-            a.sym = w->sym.as<u16>();
             a.nblock_max = w->nbmax.as<u32>() + s0;
-            a.perm = w->perm.as<u8>();
-            a.chunk_emit = w->chunk_emit.as<u32>();
-            a.tt_len = w->tt_len.as<u32>();
-            a.err = w->err.as<u32>();
-            a.L = w->L.as<u8>();
-            a.T = w->T.as<u32>();
-            a.X = w->X.as<u8>();
-            a.samp_next = w->samp_next.as<u32>();
-            a.samp_len = w->samp_len.as<u32>();
-            a.samp_off = w->samp_off.as<u32>();
-            a.cycle_len = w->cycle_len.as<u32>();
-            a.sub_trans = w->sub_trans.as<uint4>();
-            a.sub_off = w->sub_off.as<u32>();
-            a.sub_state = w->sub_state.as<u8>();
-            a.work_ctr = w->work_ctr.as<u32>();
-            a.walk_meta = w->walk_meta.as<uint4>();
-            a.seg_buf = w->seg_buf.as<u8>();
-            a.seg_cont = w->seg_cont.as<u32>();
-            a.long_list = w->long_list.as<u32>();
-            a.out_len = w->out_len.as<u32>();
-            a.thist = w->thist.as<u32>();
-            a.tbase = w->tbase.as<u32>();
-            a.crc = w->crc.as<u32>();
+            dec_args_bind(w, a);
             HIPDEC(hipMemsetAsync(w->err.p, 0, (size_t)nb * 4, st));
             HIPDEC(hipMemsetAsync(w->out_len.p, 0, (size_t)nb * 4, st));
             HIPDEC(hipEventRecord(ev[0], st));
@@ -947,6 +969,361 @@ static int decode_core(bz_gpu_engine *g, const u8 *d_in, u64 n, Sink &sink, int 
     return BZ_OK;
 }
 
+// ---- many independent streams in one call ------------------------------------------------------------------
+// Entry i is in_len[i] bytes at d_in + in_off[i]; its result is that of decode_core on those bytes alone.  What reaches
+// across entries in decode_core -- one (in, nbytes) for the scan and for D1, one serial record chain on the host -- is
+// replaced by a front end that knows about entries (k_dec_scan_batch, k_dec_block<true>, k_dec_chain_batch: k_dec.hip);
+// D2..D4 run on the true blocks of all entries of a GROUP together: a maximal run of consecutive entries whose
+// candidates fit the D1 workspace.  Where decode_core stops at the first failing block, this driver stops only that
+// block's ENTRY.  An entry with more candidates than a group holds, and one whose chain meets a block without its full
+// magic (no candidate: `irregular`), is decoded by decode_core on its own range behind the batch path's output.
+namespace {
+struct BatchOut {
+    u8 *d_out = nullptr; // device destination ...
+    u64 cap = 0;
+    bool dry = false;    // ... or sizes only
+    HostBuf *host = nullptr; // host destination: one buffer that grows group by group (offsets are relative to it)
+};
+inline u64 up16(u64 x) { return (x + 15ull) & ~15ull; }
+} // namespace
+
+static int decode_batch_core(bz_gpu_engine *g, const u8 *d_in, const u64 *in_off, const u64 *in_len, size_t count,
+                             BatchOut &o, u64 *out_off, u64 *out_len, int32_t *verdict)
+{
+    HIPDEC(hipSetDevice(g->device));
+    if (!g->dec) g->dec = new DecWorkspace();
+    DecWorkspace *w = g->dec;
+    if (!w->ev_a) {
+        HIPDEC(hipEventCreateWithFlags(&w->ev_a, hipEventDisableTiming));
+        HIPDEC(hipEventCreateWithFlags(&w->ev_b, hipEventDisableTiming));
+    }
+    hipStream_t st = g->st;
+    // timings and stats of the call: sums over its groups and its one-stream decodes (decode_core clears the workspace's)
+    double t_sum[4] = {0, 0, 0, 0};
+    u64 s_sum[4] = {0, 0, 0, 0}, b_sum[4] = {0, 0, 0, 0};
+    struct Totals {
+        DecWorkspace *w;
+        double *t;
+        u64 *s, *b;
+        ~Totals()
+        {
+            for (int i = 0; i < 4; ++i) w->t_stage[i] = t[i], w->stats[i] = s[i], w->bstats[i] = b[i];
+        }
+    } totals{w, t_sum, s_sum, b_sum};
+    hipEvent_t ev[2];
+    HIPDEC(hipEventCreate(&ev[0]));
+    HIPDEC(hipEventCreate(&ev[1]));
+    struct EvGuard {
+        hipEvent_t *e;
+        ~EvGuard()
+        {
+            (void)hipEventDestroy(e[0]);
+            (void)hipEventDestroy(e[1]);
+        }
+    } ev_guard{ev};
+    auto stage_time = [&](int stage) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) t_sum[stage] += ms * 1e-3;
+    };
+
+    // the entries that hold bytes (an empty one is BZ_E_MAGIC_FIRST without a look at the device)
+    std::vector<DecEntry> ents;
+    std::vector<size_t> orig; // their indices in the call
+    for (size_t i = 0; i < count; ++i) {
+        out_off[i] = out_len[i] = 0;
+        verdict[i] = BZ_E_MAGIC_FIRST;
+        if (in_len[i]) {
+            DecEntry e;
+            e.off = in_off[i];
+            e.len = in_len[i];
+            e.first_cand = e.ncand = 0;
+            ents.push_back(e);
+            orig.push_back(i);
+        }
+    }
+    const u32 nent = (u32)ents.size();
+
+    // ---- D0: one scan over the span of all entries; candidates sorted by (entry, bit position)
+    std::vector<DecCand> cands;
+    if (nent) {
+        int rc;
+        if ((rc = w->count.ensure(16)) || (rc = w->ents.ensure((size_t)nent * sizeof(DecEntry)))) return rc;
+        const u64 span0 = ents.front().off, span_end = ents.back().off + ents.back().len;
+        if ((span_end - span0 + 1023u) / 1024u > 0x7FFFFFFFull) return BZ_E_PARAM;
+        HIPDEC(hipMemcpyAsync(w->ents.p, ents.data(), (size_t)nent * sizeof(DecEntry), hipMemcpyHostToDevice, st));
+        // (a tiny stream holds two magics in a few dozen bytes: room for those of every entry on top of decode_core's guess)
+        u32 cap = (u32)std::min<u64>((span_end - span0) / 2048 + 2ull * nent + 1024, 0x7FFFFFFFu);
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            if ((rc = w->cand_all.ensure((size_t)cap * sizeof(DecCand)))) return rc;
+            HIPDEC(hipEventRecord(ev[0], st));
+            launch_dec_scan_batch(st, d_in, span0, span_end, w->ents.as<DecEntry>(), nent, w->cand_all.as<DecCand>(), cap, w->count.as<u32>());
+            HIPDEC(hipEventRecord(ev[1], st));
+            u32 cnt = 0;
+            HIPDEC(hipMemcpyAsync(&cnt, w->count.p, 4, hipMemcpyDeviceToHost, st));
+            HIPDEC(hipStreamSynchronize(st));
+            stage_time(0);
+            if (cnt <= cap) {
+                cands.resize(cnt);
+                if (cnt) HIPDEC(hipMemcpy(cands.data(), w->cand_all.p, (size_t)cnt * sizeof(DecCand), hipMemcpyDeviceToHost));
+                break;
+            }
+            cap = cnt;
+        }
+        cands.erase(std::remove_if(cands.begin(), cands.end(), [](const DecCand &c) { return c.type != 1u; }), cands.end());
+        std::sort(cands.begin(), cands.end(), [](const DecCand &a, const DecCand &b) {
+            return a.pad != b.pad ? a.pad < b.pad : a.bitpos < b.bitpos;
+        });
+        if (cands.size() > 0xFFFFFFF0ull) return BZ_E_NOMEM;
+        for (size_t c = 0; c < cands.size(); ++c) {
+            if (cands[c].pad >= nent) return BZ_E_UNEXPECTED;
+            DecEntry &e = ents[cands[c].pad];
+            if (e.ncand++ == 0) e.first_cand = (u32)c;
+        }
+    }
+    const size_t nc = cands.size();
+    s_sum[0] = nc;
+
+    // the D1 workspace, as decode_core computes it
+    u32 B = dec_batch_slots();
+    if (nc < B) B = (u32)(nc ? nc : 1);
+    B = dec_fit_slots(w, B);
+    {
+        const int rc = dec_ensure(w, (size_t)B + kForcedSlots);
+        if (rc) return rc;
+    }
+    std::vector<u32> one; // entries (indices into ents) of the one-stream path
+    for (u32 k = 0; k < nent; ++k)
+        if (ents[k].ncand > B) {
+            one.push_back(k);
+            ents[k].ncand = kDecEntrySkip;
+        }
+    if (nent) HIPDEC(hipMemcpyAsync(w->ents.p, ents.data(), (size_t)nent * sizeof(DecEntry), hipMemcpyHostToDevice, st));
+
+    u64 run = 0;       // end of the output so far
+    size_t next_i = 0; // entries of the call in front of this one have their offsets (or wait for the one-stream path)
+    auto place_empties = [&](size_t upto) {
+        for (; next_i < upto; ++next_i)
+            if (!in_len[next_i]) {
+                out_off[next_i] = up16(run);
+                b_sum[0] += 1;
+            }
+    };
+    const u32 walk_wgs = 256;
+
+    for (u32 k0 = 0; k0 < nent;) {
+        if (ents[k0].ncand == kDecEntrySkip) { // (no group reaches across it: a group's candidates are one range of the list)
+            place_empties(orig[k0]);
+            next_i = orig[k0] + 1;
+            ++k0;
+            continue;
+        }
+        u32 k1 = k0, n = 0;
+        while (k1 < nent && ents[k1].ncand != kDecEntrySkip && n + ents[k1].ncand <= B) n += ents[k1++].ncand;
+        const u32 ne = k1 - k0;
+        u32 cand0 = 0; // the group's first candidate in the sorted list
+        for (u32 k = k0; k < k1; ++k)
+            if (ents[k].ncand) {
+                cand0 = ents[k].first_cand;
+                break;
+            }
+        b_sum[3] += 1;
+
+        // ---- D1 over the group's candidates, each inside its own entry; then the record chain of every entry
+        std::vector<u8> hchain((size_t)ne * sizeof(DecChainEntry) + (size_t)n * sizeof(DecChainCand));
+        {
+            int rc;
+            if ((rc = w->chain.ensure(hchain.size()))) return rc;
+        }
+        DecChainEntry *d_ce = w->chain.as<DecChainEntry>();
+        DecChainCand *d_cc = reinterpret_cast<DecChainCand *>(d_ce + ne);
+        if (n) HIPDEC(hipMemcpyAsync(w->cands.p, cands.data() + cand0, (size_t)n * sizeof(DecCand), hipMemcpyHostToDevice, st));
+        HIPDEC(hipMemsetAsync(w->chain.p, 0, hchain.size(), st));
+        HIPDEC(hipEventRecord(ev[0], st));
+        launch_dec_blocks_batch(st, d_in, w->ents.as<DecEntry>(), w->cands.as<DecCand>(), n, w->info.as<DecBlockInfo>(), w->sym.as<u16>(),
+                                w->sel.as<u8>());
+        launch_dec_chain_batch(st, d_in, w->ents.as<DecEntry>(), k0, ne, w->cands.as<DecCand>(), cand0, w->info.as<DecBlockInfo>(), d_ce, d_cc);
+        HIPDEC(hipEventRecord(ev[1], st));
+        HIPDEC(hipMemcpyAsync(hchain.data(), w->chain.p, hchain.size(), hipMemcpyDeviceToHost, st));
+        HIPDEC(hipStreamSynchronize(st));
+        stage_time(0);
+        const DecChainEntry *ce = reinterpret_cast<const DecChainEntry *>(hchain.data());
+        const DecChainCand *cc = reinterpret_cast<const DecChainCand *>(hchain.data() + (size_t)ne * sizeof(DecChainEntry));
+
+        // the true blocks of the group in entry order, and where each entry's begin
+        std::vector<u32> bslot, bmax, bcrc, bfirst((size_t)ne + 1, 0);
+        u32 max_bytes = 1, max_nsym = 1;
+        for (u32 k = k0; k < k1; ++k) {
+            bfirst[k - k0] = (u32)bslot.size();
+            if (ce[k - k0].irregular) {
+                one.push_back(k);
+                continue;
+            }
+            s_sum[2] += ce[k - k0].streams;
+            for (u32 c = ents[k].first_cand - cand0, c_end = c + ents[k].ncand; ents[k].ncand && c < c_end; ++c)
+                if (cc[c].is_true) {
+                    bslot.push_back(c);
+                    bmax.push_back(cc[c].max_len);
+                    bcrc.push_back(cc[c].stored_crc);
+                    max_bytes = std::max(max_bytes, cc[c].max_len);
+                    max_nsym = std::max(max_nsym, cc[c].nsym);
+                }
+        }
+        bfirst[ne] = (u32)bslot.size();
+        const u32 nb = (u32)bslot.size();
+        b_sum[2] += nb;
+        s_sum[1] += nb;
+
+        // ---- D2, D3 for all of them
+        DecArgs a;
+        a.nb = nb;
+        dec_args_shape(a, max_bytes, max_nsym);
+        dec_args_bind(w, a);
+        a.slot = w->slot.as<u32>();
+        a.nblock_max = w->nbmax.as<u32>();
+        std::vector<u32> h_err(nb), h_len(nb);
+        if (nb) {
+            HIPDEC(hipMemcpyAsync(w->slot.p, bslot.data(), (size_t)nb * 4, hipMemcpyHostToDevice, st));
+            HIPDEC(hipMemcpyAsync(w->nbmax.p, bmax.data(), (size_t)nb * 4, hipMemcpyHostToDevice, st));
+            HIPDEC(hipMemsetAsync(w->err.p, 0, (size_t)nb * 4, st));
+            HIPDEC(hipMemsetAsync(w->out_len.p, 0, (size_t)nb * 4, st));
+            HIPDEC(hipEventRecord(ev[0], st));
+            int mtf_rec = -1, wrec[4] = {-1, -1, -1, -1};
+            launch_dec_mtf(st, a, nullptr, &mtf_rec);
+            HIPDEC(hipEventRecord(ev[1], st));
+            HIPDEC(hipStreamSynchronize(st));
+            stage_time(1);
+            HIPDEC(hipEventRecord(ev[0], st));
+            launch_dec_walks(st, a, walk_wgs, g->st2, w->ev_a, w->ev_b, nullptr, wrec);
+            HIPDEC(hipEventRecord(ev[1], st));
+            HIPDEC(hipMemcpyAsync(h_err.data(), w->err.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+            HIPDEC(hipMemcpyAsync(h_len.data(), w->out_len.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+            HIPDEC(hipStreamSynchronize(st));
+            stage_time(2);
+        }
+
+        // ---- every entry's place, from the lengths of the blocks in front of its first failing one (before any CRC is
+        // looked at: a sizes-only call assigns the same offsets)
+        const u64 grp_start = up16(run);
+        std::vector<u64> h_base(nb, 0);
+        std::vector<u32> good((size_t)ne, 0); // blocks of the entry that were rebuilt
+        u32 max_len = 0;
+        u64 bytes = 0;
+        for (u32 k = k0; k < k1; ++k) {
+            const size_t i = orig[k];
+            place_empties(i);
+            next_i = i + 1;
+            if (ce[k - k0].irregular) continue;
+            b_sum[0] += 1;
+            const u32 b0 = bfirst[k - k0], b1 = bfirst[k - k0 + 1];
+            u32 gd = b1 - b0;
+            for (u32 b = b0; b < b1; ++b)
+                if (h_err[b]) {
+                    gd = b - b0;
+                    break;
+                }
+            good[k - k0] = gd;
+            const u64 off = up16(run);
+            u64 len = 0;
+            for (u32 b = b0; b < b0 + gd; ++b) {
+                h_base[b] = off + len - (o.host ? grp_start : 0ull);
+                len += h_len[b];
+                max_len = std::max(max_len, h_len[b]);
+            }
+            for (u32 b = b0 + gd; b < b1; ++b) h_err[b] = 1u; // the blocks behind a failing one are not the entry's any more
+            out_off[i] = off;
+            out_len[i] = len;
+            static const int kVerdict[4] = {BZ_OK, BZ_E_DATA, BZ_E_MAGIC_FIRST, BZ_E_MAGIC};
+            verdict[i] = gd < b1 - b0 ? BZ_E_DATA : kVerdict[ce[k - k0].verdict & 3u];
+            run = off + len;
+            bytes += len;
+        }
+        k0 = k1;
+        if (o.dry || !bytes) continue;
+        u8 *dst = o.d_out;
+        if (o.host) {
+            int rc;
+            if ((rc = w->staging.ensure((size_t)(run - grp_start) + 64)) || (rc = o.host->reserve((size_t)run))) return rc;
+            dst = w->staging.as<u8>();
+        } else if (run > o.cap) {
+            return BZ_E_CAPACITY;
+        }
+
+        // ---- D4: the bytes and their CRCs
+        HIPDEC(hipMemcpyAsync(w->err.p, h_err.data(), (size_t)nb * 4, hipMemcpyHostToDevice, st));
+        HIPDEC(hipMemcpyAsync(w->out_base.p, h_base.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
+        HIPDEC(hipEventRecord(ev[0], st));
+        launch_dec_expand(st, a, w->out_base.as<u64>(), dst);
+        launch_dec_crc(st, a, w->out_base.as<u64>(), dst, max_len, g->crc_tab.as<u32>(), g->xp2.as<u32>(), g->xp16.as<u32>());
+        HIPDEC(hipEventRecord(ev[1], st));
+        std::vector<u32> h_crc(nb);
+        HIPDEC(hipMemcpyAsync(h_crc.data(), w->crc.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+        HIPDEC(hipStreamSynchronize(st));
+        stage_time(3);
+        for (u32 k = k1 - ne; k < k1; ++k) {
+            const u32 e = k - (k1 - ne);
+            if (ce[e].irregular) continue;
+            const size_t i = orig[k];
+            const u32 b0 = bfirst[e];
+            u64 len = 0;
+            for (u32 b = b0; b < b0 + good[e]; ++b) {
+                len += h_len[b];
+                if (~h_crc[b] != bcrc[b]) { // decoder.rs:189-198: noticed after the block's bytes went out
+                    out_len[i] = len;
+                    verdict[i] = BZ_E_DATA;
+                    break;
+                }
+            }
+        }
+        if (o.host) {
+            HIPDEC(hipMemcpy(o.host->p + grp_start, dst, (size_t)(run - grp_start), hipMemcpyDeviceToHost));
+            o.host->len = (size_t)run;
+        }
+    }
+
+    // ---- the one-stream path: decode_core on the entry's range, behind everything the batch path wrote
+    std::sort(one.begin(), one.end());
+    for (const u32 k : one) {
+        const size_t i = orig[k];
+        const u64 off = up16(run);
+        Sink sink;
+        if (o.host) {
+            const int rc = o.host->reserve((size_t)off);
+            if (rc) return rc;
+            o.host->len = (size_t)off; // (decode_core appends)
+            sink.host = o.host;
+            sink.staging[0] = &w->staging;
+            sink.staging[1] = &w->staging2;
+        } else {
+            sink.dry = o.dry;
+            sink.d_out = o.dry ? nullptr : o.d_out + std::min(off, o.cap);
+            sink.cap = o.cap > off ? o.cap - off : 0;
+        }
+        int v = BZ_OK;
+        int rc = decode_core(g, d_in + ents[k].off, ents[k].len, sink, &v);
+        for (int q = 0; q < 4; ++q) t_sum[q] += w->t_stage[q], s_sum[q] += w->stats[q];
+        if (rc) return rc;
+        u64 adv = sink.produced;
+        if (!o.host && !o.dry && v == BZ_E_DATA) {
+            // a CRC verdict cuts the entry short of what a sizes-only call counts: the entries behind keep its offsets
+            Sink sizes;
+            sizes.dry = true;
+            int v2 = BZ_OK;
+            rc = decode_core(g, d_in + ents[k].off, ents[k].len, sizes, &v2);
+            for (int q = 0; q < 4; ++q) t_sum[q] += w->t_stage[q];
+            if (rc) return rc;
+            adv = std::max(adv, sizes.produced);
+        }
+        out_off[i] = off;
+        out_len[i] = sink.produced;
+        verdict[i] = v;
+        run = off + adv;
+        if (o.host) o.host->len = (size_t)(off + sink.produced);
+        b_sum[1] += 1;
+    }
+    place_empties(count);
+    return BZ_OK;
+}
+
 int dec_decode_for_verify(bz_gpu_engine *g, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap,
                           uint64_t *produced, int *verdict)
 {
@@ -1034,6 +1411,36 @@ extern "C" int bz_gpu_last_decode_stats(bz_gpu_engine *g, uint64_t out[4])
 {
     if (!g || !out) return BZ_E_PARAM;
     for (int i = 0; i < 4; ++i) out[i] = g->dec ? g->dec->stats[i] : 0;
+    return BZ_OK;
+}
+
+extern "C" int bz_gpu_decode_batch_device(bz_gpu_engine *g, const void *d_in, const uint64_t *h_in_off,
+                                          const uint64_t *h_in_len, size_t count, void *d_out, size_t cap,
+                                          uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_verdict)
+{
+    if (!g) return BZ_E_PARAM;
+    if (count == 0) return BZ_OK;
+    if (!h_in_off || !h_in_len || !h_out_off || !h_out_len || !h_verdict) return BZ_E_PARAM;
+    if (count > 0xFFFFFFF0ull || ((uintptr_t)d_in & 3u)) return BZ_E_PARAM;
+    u64 end = 0;
+    bool bytes = false;
+    for (size_t i = 0; i < count; ++i) {
+        if ((h_in_off[i] & 3u) || h_in_off[i] < end || h_in_off[i] + h_in_len[i] < h_in_off[i]) return BZ_E_PARAM;
+        end = h_in_off[i] + h_in_len[i];
+        bytes = bytes || h_in_len[i];
+    }
+    if (bytes && !d_in) return BZ_E_PARAM;
+    BatchOut o;
+    o.d_out = static_cast<u8 *>(d_out);
+    o.cap = cap;
+    o.dry = (d_out == nullptr);
+    return decode_batch_core(g, static_cast<const u8 *>(d_in), h_in_off, h_in_len, count, o, h_out_off, h_out_len, h_verdict);
+}
+
+extern "C" int bz_gpu_last_decode_batch_stats(bz_gpu_engine *g, uint64_t out[4])
+{
+    if (!g || !out) return BZ_E_PARAM;
+    for (int i = 0; i < 4; ++i) out[i] = g->dec ? g->dec->bstats[i] : 0;
     return BZ_OK;
 }
 
@@ -1137,6 +1544,56 @@ extern "C" int bz_decode_buffer(int device, const uint8_t *in, size_t in_len, ui
     if (!h) return BZ_E_NOMEM;
     *out = h;
     return verdict;
+}
+
+// The same for many independent streams (mirrors bz_encode_batch): the entries packed at 4-byte-aligned offsets, one
+// upload, decode_batch_core on a cached engine, the bytes down group by group into ONE buffer.
+extern "C" int bz_decode_batch(int device, const uint8_t *const *ins, const size_t *lens, size_t count, uint8_t **out,
+                               uint64_t *out_off, uint64_t *out_len, int32_t *verdict)
+{
+    if (!out) return BZ_E_PARAM;
+    *out = nullptr;
+    if (count == 0) {
+        *out = (uint8_t *)malloc(1);
+        return *out ? BZ_OK : BZ_E_NOMEM;
+    }
+    if (!ins || !lens || !out_off || !out_len || !verdict || count > 0xFFFFFFF0ull) return BZ_E_PARAM;
+    std::vector<u64> off(count), len(count);
+    u64 total = 0;
+    for (size_t i = 0; i < count; ++i) {
+        if (!ins[i] && lens[i]) return BZ_E_PARAM;
+        off[i] = total;
+        len[i] = lens[i];
+        total = (total + lens[i] + 3ull) & ~3ull;
+    }
+    int caller_device = -1;
+    (void)hipGetDevice(&caller_device);
+    bz_gpu_engine *g = dec_cache_take(device, 1);
+    int rc = g ? BZ_OK : bz_gpu_engine_create(&g, device, 0);
+    if (rc != BZ_OK) return rc;
+    HostBuf host;
+    rc = hipSetDevice(device) == hipSuccess ? g->dec_in.ensure((size_t)total + 64) : BZ_E_UNEXPECTED;
+    if (rc == BZ_OK) {
+        // packed on the host first: one upload, whatever the number of entries
+        std::vector<u8> packed((size_t)total, 0);
+        for (size_t i = 0; i < count; ++i)
+            if (lens[i]) memcpy(packed.data() + off[i], ins[i], lens[i]);
+        rc = BZ_E_UNEXPECTED;
+        if ((!total || hipMemcpyAsync(g->dec_in.p, packed.data(), (size_t)total, hipMemcpyHostToDevice, g->st) == hipSuccess) &&
+            hipStreamSynchronize(g->st) == hipSuccess) {
+            BatchOut o;
+            o.host = &host;
+            rc = decode_batch_core(g, static_cast<const u8 *>(g->dec_in.p), off.data(), len.data(), count, o, out_off, out_len, verdict);
+        }
+    }
+    if (rc == BZ_OK) dec_cache_put(device, g);
+    else bz_gpu_engine_destroy(g); // (an engine that met an infrastructure error is not kept)
+    if (caller_device >= 0) (void)hipSetDevice(caller_device);
+    if (rc != BZ_OK) return rc;
+    uint8_t *h = host.len ? host.release() : (uint8_t *)malloc(1);
+    if (!h) return BZ_E_NOMEM;
+    *out = h;
+    return BZ_OK;
 }
 
 // ---- streaming mirror of BZip2Decoder (decoder.rs:583-612) ------------------------------------------------

@@ -275,10 +275,14 @@ __device__ void d1_selectors(const BitCur &bc, u8 *__restrict__ sel, u64 p0, u32
 // ---- D1: header + Huffman decode of one candidate -------------------------------------------------------
 // One workgroup of four waves per candidate.  Thread 0 parses the header; all threads build the
 // decode tables; the symbols are then found 256 candidate code starts at a time (below).
+// kBatch (bz_gpu_decode_batch_device): the candidate belongs to entry cands[c].pad of `ents`, its bit position counts
+// from that entry's first byte and the input ENDS with the entry -- a cut-off block meets the end of its own input
+// (short numbers, status codes: all as below), not the bytes of the entry behind it.  !kBatch: `ents` is not looked at.
+template <bool kBatch>
 __global__ __launch_bounds__(kD1Threads) void k_dec_block(const u8 *__restrict__ in, u64 nbytes,
                                                    const DecCand *__restrict__ cands, u32 ncand,
                                                    DecBlockInfo *__restrict__ info, u16 *__restrict__ sym_out,
-                                                   u8 *__restrict__ sel_scratch)
+                                                   u8 *__restrict__ sel_scratch, const DecEntry *__restrict__ ents)
 {
     __shared__ u16 s_lut[6][1u << kLutBits];
     __shared__ u8 s_len[6][260];
@@ -297,6 +301,11 @@ __global__ __launch_bounds__(kD1Threads) void k_dec_block(const u8 *__restrict__
     if (c >= ncand) return;
     const u32 l = threadIdx.x;
 #define BZ_T(i)
+    if (kBatch) {
+        const DecEntry en = ents[cands[c].pad];
+        in += en.off;
+        nbytes = en.len;
+    }
     DecBlockInfo &bi = info[c];
     BitCur bc;
     bc.open(in, nbytes);
@@ -1658,7 +1667,223 @@ void launch_dec_blocks(hipStream_t st, const u8 *in, u64 nbytes, const DecCand *
                        u16 *sym, u8 *sel_scratch)
 {
     if (ncand == 0) return;
-    hipLaunchKernelGGL(k_dec_block, dim3(ncand), dim3(kD1Threads), 0, st, in, nbytes, cands, ncand, info, sym, sel_scratch);
+    hipLaunchKernelGGL(k_dec_block<false>, dim3(ncand), dim3(kD1Threads), 0, st, in, nbytes, cands, ncand, info, sym, sel_scratch,
+                       static_cast<const DecEntry *>(nullptr));
+}
+
+// ---- many independent streams in one call: the front end that knows about entries ----------------------------------
+// The magic scan over the span of all entries, in the shape of k_dec_scan4: a tile is 1 KiB (256 threads x one aligned
+// word), entries are non-empty, start at multiples of 4 and lie in ascending order, so a tile meets at most 256 of them
+// (the one that reaches into it and 255 starts): thread 0 finds the first by an upper-bound search in the table, the
+// tile's slice of the table is staged in LDS, and every thread finds the entry of its word by an upper-bound search
+// there (the four byte positions of a word lie in one entry or in one gap).  Bytes behind an entry's end read as zero,
+// positions in gaps produce nothing, a candidate needs its 48 bits inside its entry; bitpos counts from the entry's
+// first byte and `pad` carries the entry.
+constexpr u32 kScanStage = 257;
+__global__ __launch_bounds__(256) void k_dec_scan_batch(const u8 *__restrict__ in, u64 span0, u64 span_end,
+                                                         const DecEntry *__restrict__ ents, u32 nent,
+                                                         DecCand *__restrict__ cands, u32 cap, u32 *__restrict__ count)
+{
+    __shared__ u64 s_off[kScanStage], s_len[kScanStage];
+    __shared__ u32 s_first;
+    const u64 t0 = span0 + (u64)blockIdx.x * 1024u;
+    if (threadIdx.x == 0) {
+        u32 lo = 0, hi = nent; // entries that start at or in front of the tile
+        while (lo < hi) {
+            const u32 mid = (lo + hi) >> 1;
+            if (ents[mid].off <= t0) lo = mid + 1; else hi = mid;
+        }
+        s_first = lo ? lo - 1u : 0u;
+    }
+    __syncthreads();
+    const u32 first = s_first;
+    for (u32 i = threadIdx.x; i < kScanStage; i += 256u) {
+        const u32 e = first + i;
+        s_off[i] = e < nent ? ents[e].off : ~0ull;
+        s_len[i] = e < nent ? ents[e].len : 0ull;
+    }
+    __syncthreads();
+    const u64 a0 = t0 + (u64)threadIdx.x * 4u; // this thread's word, as a byte offset from `in`
+    if (a0 >= span_end) return;
+    u32 lo = 0, hi = kScanStage;
+    while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (s_off[mid] <= a0) lo = mid + 1; else hi = mid;
+    }
+    if (lo == 0) return;
+    const u64 off = s_off[lo - 1], len = s_len[lo - 1], end = off + len;
+    if (a0 >= end) return; // a gap
+    const u32 *w = reinterpret_cast<const u32 *>(in);
+    u32 x[3];
+#pragma unroll
+    for (u32 k = 0; k < 3; ++k) {
+        const u64 a = a0 + 4u * k;
+        u32 v = 0;
+        if (a < end) { // (a word that holds a byte of an entry lies inside the allocation)
+            v = __builtin_bswap32(w[a >> 2]);
+            if (end - a < 4u) v &= ~(0xFFFFFFFFu >> (8u * (u32)(end - a)));
+        }
+        x[k] = v;
+    }
+    const u64 p0 = a0 - off; // byte position inside the entry
+    const u64 hi64 = ((u64)x[0] << 32) | x[1];
+#pragma unroll
+    for (u32 j = 0; j < 4; ++j) {
+        const u64 p = p0 + j;
+        if (p >= len) break;
+        const u64 top = j ? ((hi64 << (8u * j)) | ((u64)x[2] >> (32u - 8u * j))) : hi64;
+        const u64 wdw = top >> 8;
+#pragma unroll
+        for (u32 s = 0; s < 8; ++s) {
+            const u64 v = (wdw >> (8u - s)) & 0xFFFFFFFFFFFFull;
+            const u32 type = (v == kBlockMagic) ? 1u : (v == kEosMagic ? 2u : 0u);
+            if (type && p * 8 + s + 48 <= len * 8) {
+                const u32 i = atomicAdd(count, 1u);
+                if (i < cap) {
+                    cands[i].bitpos = p * 8 + s;
+                    cands[i].type = type;
+                    cands[i].pad = first + lo - 1u;
+                }
+            }
+        }
+    }
+}
+
+void launch_dec_scan_batch(hipStream_t st, const u8 *in, u64 span0, u64 span_end, const DecEntry *ents, u32 nent,
+                           DecCand *cands, u32 cap, u32 *count)
+{
+    (void)hipMemsetAsync(count, 0, 4, st);
+    if (nent == 0 || span_end <= span0) return;
+    hipLaunchKernelGGL(k_dec_scan_batch, dim3((u32)((span_end - span0 + 1023u) / 1024u)), dim3(256), 0, st, in, span0, span_end, ents,
+                       nent, cands, cap, count);
+}
+
+void launch_dec_blocks_batch(hipStream_t st, const u8 *in, const DecEntry *ents, const DecCand *cands, u32 ncand,
+                             DecBlockInfo *info, u16 *sym, u8 *sel_scratch)
+{
+    if (ncand == 0) return;
+    hipLaunchKernelGGL(k_dec_block<true>, dim3(ncand), dim3(kD1Threads), 0, st, in, (u64)0, cands, ncand, info, sym, sel_scratch, ents);
+}
+
+// up to 32 bits at `pos` of an entry, read like DevBits::read (dec_engine.hip): at the end of the entry the bits that
+// are left come back as a shorter number
+__device__ __forceinline__ u32 ent_read(const u8 *__restrict__ p, u64 nbytes, u64 &pos, u32 nbits)
+{
+    const u64 total = nbytes * 8ull;
+    const u64 avail = total > pos ? total - pos : 0ull;
+    const u32 k = avail < nbits ? (u32)avail : nbits;
+    if (k == 0) return 0u;
+    const u64 b0 = pos >> 3;
+    u64 acc = 0; // the 40 bits from byte b0 on
+#pragma unroll
+    for (u32 i = 0; i < 5; ++i) acc = (acc << 8) | (u64)(b0 + i < nbytes ? p[b0 + i] : 0);
+    const u32 sh = (u32)pos & 7u;
+    pos += k;
+    return (u32)((acc >> (40u - sh - k)) & ((1ull << k) - 1ull));
+}
+
+// The record chain (stream header, blocks, end-of-stream record, next stream ...) of every entry of a group, one lane
+// per entry: the unsharded chain of decode_core (dec_engine.hip, the loop that opens with `rec_pos = pos`) with the
+// entry as the whole input.  cands[] / info[] are the group's (candidate `cand0` of the sorted list is their first);
+// out_cand[] was cleared by the launcher's caller.  A block that starts without its full 48-bit magic has no candidate
+// (the reference compares the first byte only, decoder.rs:204-221): the entry is marked irregular and left to the
+// one-stream path.
+__global__ __launch_bounds__(64) void k_dec_chain_batch(const u8 *__restrict__ in, const DecEntry *__restrict__ ents, u32 e0, u32 ne,
+                                                         const DecCand *__restrict__ cands, u32 cand0,
+                                                         const DecBlockInfo *__restrict__ info,
+                                                         DecChainEntry *__restrict__ out_ent, DecChainCand *__restrict__ out_cand)
+{
+    const u32 i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= ne) return;
+    const DecEntry en = ents[e0 + i];
+    DecChainEntry r;
+    r.verdict = kChainOk;
+    r.streams = 1;
+    r.irregular = 0;
+    r.ntrue = 0;
+    if (en.ncand == kDecEntrySkip) {
+        r.irregular = 1;
+        out_ent[i] = r;
+        return;
+    }
+    const u8 *p = in + en.off;
+    const u64 n = en.len, nbits = n * 8ull;
+    const u32 c0 = en.first_cand - cand0;
+    u64 pos = 0;
+    u32 level = 0, combined = 0, cj = 0, next_head = 0, next_bits = 0;
+    bool need_header = true, have_next = false;
+    while (true) {
+        if (need_header) { // 'B','Z','h' are read, not compared; the level digit is (decoder.rs:171-187)
+            (void)ent_read(p, n, pos, 24);
+            const u32 lv = ent_read(p, n, pos, 8);
+            if (lv < 0x31u || lv > 0x39u) {
+                r.verdict = r.streams == 1 ? kChainMagicFirst : kChainMagic;
+                break;
+            }
+            level = lv - 0x30u;
+            need_header = false;
+        }
+        u64 q = pos;
+        u32 head;
+        if (have_next) { // the block in front already looked at these 8 bits
+            head = next_head;
+            q = pos + next_bits;
+            have_next = false;
+        } else {
+            head = ent_read(p, n, q, 8);
+        }
+        if (head == 0x31u) {
+            while (cj < en.ncand && cands[c0 + cj].bitpos < pos) ++cj;
+            if (!(cj < en.ncand && cands[c0 + cj].bitpos == pos)) {
+                r.irregular = 1;
+                break;
+            }
+            const DecBlockInfo &bi = info[c0 + cj];
+            if (bi.status) {
+                r.verdict = kChainData;
+                break;
+            }
+            DecChainCand cc;
+            cc.is_true = 1;
+            cc.max_len = 100000u * level;
+            cc.stored_crc = bi.stored_crc;
+            cc.nsym = bi.nsym;
+            out_cand[c0 + cj] = cc;
+            r.ntrue += 1;
+            combined = ((combined << 1) | (combined >> 31)) ^ bi.stored_crc; // decoder.rs:199-200
+            pos = bi.end_bit;
+            have_next = true;
+            next_head = bi.next_head;
+            next_bits = bi.next_bits;
+        } else if (head == 0x17u) { // end of stream, decoder.rs:487-520
+            pos = q;
+            (void)ent_read(p, n, pos, 24);
+            (void)ent_read(p, n, pos, 16);
+            const u32 stored = ent_read(p, n, pos, 32);
+            if (stored != combined) {
+                r.verdict = kChainData;
+                break;
+            }
+            pos = (pos + 7ull) & ~7ull;
+            if (pos > nbits) pos = nbits;
+            if (nbits - pos < 8) break; // the clean end
+            need_header = true;
+            combined = 0;
+            r.streams += 1;
+        } else {
+            r.verdict = kChainData;
+            break;
+        }
+    }
+    out_ent[i] = r;
+}
+
+void launch_dec_chain_batch(hipStream_t st, const u8 *in, const DecEntry *ents, u32 e0, u32 ne, const DecCand *cands,
+                            u32 cand0, const DecBlockInfo *info, DecChainEntry *out_ent, DecChainCand *out_cand)
+{
+    if (ne == 0) return;
+    hipLaunchKernelGGL(k_dec_chain_batch, dim3((ne + 63u) / 64u), dim3(64), 0, st, in, ents, e0, ne, cands, cand0, info, out_ent,
+                       out_cand);
 }
 
 // 64-byte windows of the input at the given (16-byte aligned) offsets, zeros behind the end of the input: what the host's

@@ -346,6 +346,37 @@ class BZip2Decoder {
         return Result<uint8_t, BZip2Error>::Ok(buf_[pos_++]);
     }
 
+    // Many independent streams in one call (bz_decode_batch): element i of the result is what
+    // `inputs[i].decode(&mut BZip2Decoder::new())` yields -- the bytes in front of the verdict, and the Err item if the
+    // entry is bad (an entry's verdict is its own: a bad one hides nothing behind it).  The outer Err is an
+    // infrastructure failure.  `inputs`: any range of byte ranges with data() and size().
+    struct Entry {
+        std::vector<uint8_t> bytes;
+        std::optional<BZip2Error> error;
+    };
+    template <class Spans> static Result<std::vector<Entry>> decode_batch(const Spans &inputs, int device = 0)
+    {
+        using R = Result<std::vector<Entry>>;
+        std::vector<const uint8_t *> ptrs;
+        std::vector<size_t> lens;
+        for (const auto &x : inputs) {
+            ptrs.push_back(reinterpret_cast<const uint8_t *>(x.data()));
+            lens.push_back(x.size());
+        }
+        std::vector<uint64_t> off(ptrs.size()), len(ptrs.size());
+        std::vector<int32_t> verdict(ptrs.size());
+        uint8_t *out = nullptr;
+        const int rc = bz_decode_batch(device, ptrs.data(), lens.data(), ptrs.size(), &out, off.data(), len.data(), verdict.data());
+        if (rc != BZ_OK) return R::Err(from_status(rc));
+        std::vector<Entry> entries(ptrs.size());
+        for (size_t i = 0; i < ptrs.size(); ++i) {
+            entries[i].bytes.assign(out + off[i], out + off[i] + len[i]);
+            if (verdict[i] != BZ_OK) entries[i].error = bzip2_error_from_status(verdict[i]);
+        }
+        bz_free(out);
+        return R::Ok(std::move(entries));
+    }
+
   private:
     static constexpr size_t kChunk = 1 << 20;
     bz_dec *h_ = nullptr;

@@ -40,6 +40,8 @@ extern "C" {
     pub fn bz_dec_end(d: *mut bz_dec) -> i32;
     pub fn bz_dec_read(d: *mut bz_dec, out: *mut u8, cap: usize) -> isize;
     pub fn bz_dec_destroy(d: *mut bz_dec);
+    // many streams in one call: bytes and verdict per entry; *out is released with bz_free
+    pub fn bz_decode_batch(device: i32, ins: *const *const u8, lens: *const usize, count: usize, out: *mut *mut u8, out_off: *mut u64, out_len: *mut u64, verdict: *mut i32) -> i32;
 
     // section 4: Inflater / ZlibEncoder / GZipEncoder
     pub fn df_enc_create(out: *mut *mut df_enc, kind: i32, device: i32) -> i32;

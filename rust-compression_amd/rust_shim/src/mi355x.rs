@@ -4,6 +4,8 @@ use core::sync::atomic::{AtomicI32, Ordering};
 
 use alloc::vec::Vec;
 
+#[cfg(feature = "bzip2")]
+use crate::bzip2::error::BZip2Error;
 use crate::error::CompressionError;
 use crate::ffi;
 
@@ -71,6 +73,37 @@ pub fn encode_batch(level: usize, inputs: &[&[u8]]) -> Result<Vec<Vec<u8>>, Comp
         .collect();
     unsafe { ffi::bz_free(out as *mut core::ffi::c_void) };
     Ok(streams)
+}
+
+/// Many independent streams in one call (`bz_decode_batch`, device 0): element `i` of the result is what
+/// `inputs[i].iter().cloned().decode(&mut BZip2Decoder::new())` yields -- `Ok(bytes)`, or the `BZip2Error` with the bytes
+/// the iterator hands out in front of it.  An entry's verdict is its own: a bad one hides nothing behind it.  The outer
+/// `Err` is an infrastructure failure (`last_status` says which).
+#[cfg(feature = "bzip2")]
+pub fn decode_batch(inputs: &[&[u8]]) -> Result<Vec<Result<Vec<u8>, (BZip2Error, Vec<u8>)>>, CompressionError> {
+    let ptrs: Vec<*const u8> = inputs.iter().map(|x| x.as_ptr()).collect();
+    let lens: Vec<usize> = inputs.iter().map(|x| x.len()).collect();
+    let mut off: Vec<u64> = Vec::new();
+    off.resize(inputs.len(), 0);
+    let mut len = off.clone();
+    let mut verdict: Vec<i32> = Vec::new();
+    verdict.resize(inputs.len(), 0);
+    let mut out: *mut u8 = core::ptr::null_mut();
+    let rc = unsafe {
+        ffi::bz_decode_batch(0, ptrs.as_ptr(), lens.as_ptr(), inputs.len(), &mut out, off.as_mut_ptr(), len.as_mut_ptr(), verdict.as_mut_ptr())
+    };
+    if rc != ffi::BZ_OK {
+        note_status(rc);
+        return Err(CompressionError::from_status(rc));
+    }
+    let entries = (0..inputs.len())
+        .map(|i| {
+            let bytes = unsafe { core::slice::from_raw_parts(out.add(off[i] as usize), len[i] as usize) }.to_vec();
+            if verdict[i] == ffi::BZ_OK { Ok(bytes) } else { Err((BZip2Error::from_status(verdict[i]), bytes)) }
+        })
+        .collect();
+    unsafe { ffi::bz_free(out as *mut core::ffi::c_void) };
+    Ok(entries)
 }
 
 pub(crate) fn note_status(rc: i32) {

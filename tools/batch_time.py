@@ -10,7 +10,15 @@ Per workload and run, alternating the two forms (batch, loop, batch, loop, ...):
 bz_encode_batch calls, the median of `loops` warm passes of the bz_encode_buffer loop (the parent commit's code), and
 the oracle on one CPU thread for a sample of the inputs, scaled to all of them.  The streams of the two forms are
 compared byte for byte before anything is timed.  Every call ends with its bytes on the host, so a host clock around
-it is the call's time.  Prints one line of JSON per workload.  Needs a GPU (no fallback)."""
+it is the call's time.  Prints one line of JSON per workload.  Needs a GPU (no fallback).
+
+    tools/batch_time.py --decode [--workload ...] [--runs 3] [--calls 5] [--loops 3]
+
+The same two workloads, compressed once with compress_batch: one bz_decode_batch call (decompress_batch) against a loop
+of bz_decode_buffer calls (the parent commit's code) over the same streams, alternating, both warm, medians as above;
+the outputs of the two forms are compared byte for byte (and with the inputs) before anything is timed.  The line also
+carries bz_gpu_last_decode_timings and bz_gpu_last_decode_batch_stats of one bz_gpu_decode_batch_device call over the
+same streams in HBM."""
 import argparse
 import ctypes as C
 import importlib
@@ -36,8 +44,73 @@ def workload(name):
     raise SystemExit("unknown workload %s" % name)
 
 
+def decode_mode(pkg, a, names):
+    L = pkg.lib()
+
+    def loop(streams):
+        out = []
+        for z in streams:
+            p, n = C.POINTER(C.c_uint8)(), C.c_size_t(0)
+            rc = L.bz_decode_buffer(0, z, len(z), C.byref(p), C.byref(n))
+            out.append((C.string_at(p, n.value), rc))
+            L.bz_free(p)
+        return out
+
+    def device_call(streams):
+        """one bz_gpu_decode_batch_device call over the streams in HBM: its stage timings and stats"""
+        import torch
+        off, buf = [], bytearray()
+        for z in streams:
+            off.append(len(buf))
+            buf += z
+            buf += bytes(-len(buf) % 4)
+        lens = [len(z) for z in streams]
+        t = torch.frombuffer(buf, dtype=torch.uint8).cuda()
+        eng = pkg.GpuEngine(0, 8)
+        try:
+            o_off, o_len, _ = eng.decode_batch_device(t.data_ptr(), off, lens, None, 0)
+            cap = max(x + n for x, n in zip(o_off, o_len))
+            o = torch.empty((cap + 64,), dtype=torch.uint8, device="cuda")
+            eng.decode_batch_device(t.data_ptr(), off, lens, o.data_ptr(), cap)   # (warm)
+            eng.decode_batch_device(t.data_ptr(), off, lens, o.data_ptr(), cap)
+            return {k: round(v * 1e3, 3) for k, v in eng.decode_timings().items()}, eng.decode_batch_stats()
+        finally:
+            eng.close()
+
+    for name in names:
+        datas = workload(name)
+        total = sum(len(d) for d in datas)
+        streams = pkg.compress_batch(datas, a.level)
+        batch = pkg.decompress_batch(streams)        # (warms the engine's workspace too)
+        same = batch == loop(streams) and batch == [(d, 0) for d in datas]
+        runs = []
+        for _ in range(a.runs):
+            tb, tl = [], []
+            for _ in range(a.calls):
+                t0 = time.perf_counter()
+                pkg.decompress_batch(streams)
+                tb.append(time.perf_counter() - t0)
+            for _ in range(a.loops):
+                t0 = time.perf_counter()
+                loop(streams)
+                tl.append(time.perf_counter() - t0)
+            runs.append({"batch_ms": round(statistics.median(tb) * 1e3, 2), "loop_ms": round(statistics.median(tl) * 1e3, 2),
+                         "batch_all_ms": [round(t * 1e3, 2) for t in tb], "loop_all_ms": [round(t * 1e3, 2) for t in tl]})
+        bm = statistics.median(r["batch_ms"] for r in runs)
+        lm = statistics.median(r["loop_ms"] for r in runs)
+        stage_ms, stats = device_call(streams)
+        print(json.dumps({"mode": "decode", "workload": name, "streams": len(streams), "bytes": total,
+                          "compressed_bytes": sum(len(z) for z in streams), "level": a.level, "outputs_equal": same,
+                          "batch_ms": bm, "loop_ms": lm, "loop_over_batch": round(lm / bm, 2),
+                          "batch_GBps": round(total / bm / 1e6, 3), "loop_GBps": round(total / lm / 1e6, 3),
+                          "device_call_stage_ms": stage_ms, "device_call_batch_stats": stats, "runs": runs}), flush=True)
+        if not same:
+            raise SystemExit("batch_time.py: the batch's outputs differ from the loop's or from the inputs")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--decode", action="store_true", help="time decompress_batch against a loop of bz_decode_buffer")
     ap.add_argument("--workload", default="all")
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--calls", type=int, default=5)
@@ -62,6 +135,8 @@ def main():
         return out
 
     names = ["sample1x256", "corpus16k"] if a.workload == "all" else [a.workload]
+    if a.decode:
+        return decode_mode(pkg, a, names)
     for name in names:
         datas = workload(name)
         total = sum(len(d) for d in datas)
