@@ -11,6 +11,7 @@
 // is only noticed after that block's bytes were handed out, decoder.rs:189-201).
 #include "engine_state.h"
 #include "copy_pool.h"
+#include "dec_chain.h"
 
 #include <chrono>
 #include <condition_variable>
@@ -25,11 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 
-namespace {
-
-constexpr u32 kForcedSlots = 16; // blocks per batch that start without a full 48-bit magic
-
-} // namespace
+static constexpr u32 kForcedSlots = 16; // blocks per batch that start without a full 48-bit magic
 
 static bool dec_trace()
 {
@@ -186,10 +183,7 @@ struct HostBuf {
 // more input may follow.  A call that is not the last one stops in front of the first record it
 // cannot be sure about (not wholly inside the bytes it has, or failing -- which near the end of a
 // buffer may just mean "cut off"); the caller keeps the input from `pos` on and calls again.
-struct Resume {
-    u64 pos = 0; // bit position of the next record (in: inside the buffer handed in; out: likewise)
-    u32 stream_no = 1, level = 0, combined = 0;
-    bool need_header = true;
+struct Resume : ChainState { // pos: bit position of the next record (in: inside the buffer handed in; out: likewise)
     bool final = true;    // no more input will come
     bool stopped = false; // out: stopped in front of an unsure record, nothing wrong so far
 };
@@ -230,8 +224,6 @@ struct Sink {
         }                                                                                             \
     } while (0)
 
-static inline u32 rotl1(u32 x) { return (x << 1) | (x >> 31); }
-
 // Multi-GPU decode: every rank holds the whole compressed file, scans it, and runs D1 on its own
 // contiguous range of block candidates.  What the record chain needs from every candidate is
 // exchanged with one all-gather; each rank then links the chain (the same, cheap host loop) and
@@ -257,19 +249,18 @@ struct Shard {
 };
 } // namespace
 
-// blocks in flight per D1 launch: BZ_DEC_BATCH, default 4096 (about 13 MB of workspace each)
-static u32 dec_batch_slots()
+// The D1 workspace for `nc` candidates: blocks in flight per D1 launch -- BZ_DEC_BATCH (read on every call), default 4096,
+// about 13 MB of workspace each; or exactly `want` of them: a rank's share of a sharded decode has to fit one batch
+// (BZ_E_NOMEM otherwise, reported to the peers by the caller) -- and kForcedSlots on top.  Never more of them than about
+// half of the free HBM holds (the decoded bytes need room too).
+static int dec_plan_slots(DecWorkspace *w, size_t nc, u32 want, u32 *slots)
 {
-    u32 B = 4096;
-    if (const char *e = getenv("BZ_DEC_BATCH")) {
+    u32 B = want ? want : 4096;
+    if (const char *e = want ? nullptr : getenv("BZ_DEC_BATCH")) {
         const long v = atol(e);
         if (v >= 1 && v <= 65536) B = (u32)v;
     }
-    return B;
-}
-// ... and never more of them than about half of the free HBM holds (the decoded bytes need room too)
-static u32 dec_fit_slots(const DecWorkspace *w, u32 B)
-{
+    if (nc < B) B = (u32)(nc ? nc : 1);
     const size_t per_slot = sizeof(DecCand) + sizeof(DecBlockInfo) + (size_t)kMtfStride * 2 + 32768 + 8 +
                             (size_t)kMaxMtfChunks * 260 + (size_t)kSlot * 6 + (size_t)kDecSamples * (16 + kSegCap) +
                             (size_t)kDecSubs * 21 + (size_t)kTilesPerBlock * 1024 + 2048;
@@ -277,9 +268,14 @@ static u32 dec_fit_slots(const DecWorkspace *w, u32 B)
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && w->slots < (size_t)B + kForcedSlots) {
         const size_t have = w->slots * per_slot; // what the workspace already holds is free to reuse
         const size_t fit = (free_b / 2 + have) / per_slot;
-        if (fit < (size_t)B + kForcedSlots) B = fit > kForcedSlots + 1 ? (u32)(fit - kForcedSlots) : 1u;
+        if (fit < (size_t)B + kForcedSlots) {
+            const u32 fits = fit > kForcedSlots + 1 ? (u32)(fit - kForcedSlots) : 1u;
+            if (want && fits < B) return BZ_E_NOMEM;
+            B = fits;
+        }
     }
-    return B;
+    *slots = B;
+    return dec_ensure(w, (size_t)B + kForcedSlots);
 }
 // the workspace behind a DecArgs (the caller sets nb, slot and nblock_max), and the launch shapes that follow the
 // largest block of the blocks at hand
@@ -324,52 +320,72 @@ static void dec_args_shape(DecArgs &a, u32 max_bytes, u32 max_nsym)
     a.sub_wgs = std::min<u32>((kDecSubs + 255) / 256, ((max_bytes + 63) / 64 + 255) / 256);
 }
 
-// Decodes d_in[n].  Returns an infrastructure status (BZ_OK, BZ_E_NOMEM, BZ_E_UNEXPECTED,
-// BZ_E_CAPACITY); the decoder's own verdict goes to *verdict (BZ_OK, BZ_E_DATA, BZ_E_MAGIC_FIRST,
-// BZ_E_MAGIC) and the bytes produced in front of it to sink.produced.
-static int decode_core(bz_gpu_engine *g, const u8 *d_in, u64 n, Sink &sink, int *verdict, Shard *sh = nullptr,
-                       Resume *rs = nullptr)
-{
-    HIPDEC(hipSetDevice(g->device));
-    if (!g->dec) g->dec = new DecWorkspace();
-    DecWorkspace *w = g->dec;
-    if (!w->ev_a) {
-        HIPDEC(hipEventCreateWithFlags(&w->ev_a, hipEventDisableTiming));
-        HIPDEC(hipEventCreateWithFlags(&w->ev_b, hipEventDisableTiming));
-    }
-    hipStream_t st = g->st;
-    for (double &t : w->t_stage) t = 0;
-    for (u64 &s : w->stats) s = 0;
-    *verdict = BZ_OK;
-    sink.produced = 0;
-    const u64 nbits = n * 8ull;
+// ---- what the two drivers share: the frame of a call, and the stages D0, D2 + D3, D4 ---------------------------
+namespace {
 
-    hipEvent_t ev[2];
-    HIPDEC(hipEventCreate(&ev[0]));
-    HIPDEC(hipEventCreate(&ev[1]));
-    auto stage_time = [&](int stage) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) w->t_stage[stage] += ms * 1e-3;
-    };
-    struct EvGuard {
-        hipEvent_t *e;
-        ~EvGuard()
-        {
-            (void)hipEventDestroy(e[0]);
-            (void)hipEventDestroy(e[1]);
+constexpr u32 kWalkWgs = 256; // persistent walker workgroups (bounds the window of blocks being walked; 128 ... 1024 measured: profiles/r04_decode_walk_schedule.md)
+
+// the true blocks of a batch or group in stream order: device slot, 100000 * level, stored CRC, symbols
+struct TrueBlock {
+    u32 slot, max_len, crc, nsym;
+};
+typedef std::vector<TrueBlock> TrueBlocks;
+
+// D2 + D3 of `nb` blocks: their launch arguments, and what came back
+struct Rebuilt {
+    DecArgs a;
+    std::vector<u32> err, len;
+};
+
+// The frame of one decode call: device, workspace, the fork / join events of the second walk, and two timing events
+// around every stage (destroyed whatever way the call is left).
+struct DecCall {
+    bz_gpu_engine *g = nullptr;
+    DecWorkspace *w = nullptr;
+    hipStream_t st = nullptr;
+    KernelProf *prof = nullptr; // per-kernel records (the one-stream driver sets it when the engine's profiler is on)
+    double *t_acc = nullptr;    // where stage times add up: the workspace's t_stage, or the sums of a batch call
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int open(bz_gpu_engine *g_, double *sums = nullptr)
+    {
+        g = g_;
+        HIPDEC(hipSetDevice(g->device));
+        if (!g->dec) g->dec = new DecWorkspace();
+        w = g->dec;
+        if (!w->ev_a) {
+            HIPDEC(hipEventCreateWithFlags(&w->ev_a, hipEventDisableTiming));
+            HIPDEC(hipEventCreateWithFlags(&w->ev_b, hipEventDisableTiming));
         }
-    } ev_guard{ev};
+        st = g->st;
+        for (double &t : w->t_stage) t = 0;
+        for (u64 &s : w->stats) s = 0;
+        t_acc = sums ? sums : w->t_stage;
+        HIPDEC(hipEventCreate(&ev[0]));
+        HIPDEC(hipEventCreate(&ev[1]));
+        return BZ_OK;
+    }
+    ~DecCall()
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    void stage_time(int stage)
+    {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) t_acc[stage] += ms * 1e-3;
+    }
 
-    // ---- D0: every bit position that carries the 48-bit block magic
-    std::vector<DecCand> cands;
+    // ---- D0: every bit position that carries the 48-bit block magic, in the order `less`.  launch(cands, cap, count)
+    // scans; a first attempt that finds more than `cap` is repeated once with the count it reported.
+    template <class Launch, class Less>
+    int dec_scan_candidates(u32 cap, Launch launch, Less less, std::vector<DecCand> &cands)
     {
         int rc;
         if ((rc = w->count.ensure(16))) return rc;
-        u32 cap = (u32)std::min<u64>(n / 2048 + 1024, 0x7FFFFFFFu);
         for (int attempt = 0; attempt < 2; ++attempt) {
             if ((rc = w->cand_all.ensure((size_t)cap * sizeof(DecCand)))) return rc;
             HIPDEC(hipEventRecord(ev[0], st));
-            launch_dec_scan(st, d_in, n, w->cand_all.as<DecCand>(), cap, w->count.as<u32>());
+            launch(w->cand_all.as<DecCand>(), cap, w->count.as<u32>());
             HIPDEC(hipEventRecord(ev[1], st));
             u32 cnt = 0;
             HIPDEC(hipMemcpyAsync(&cnt, w->count.p, 4, hipMemcpyDeviceToHost, st));
@@ -382,397 +398,340 @@ static int decode_core(bz_gpu_engine *g, const u8 *d_in, u64 n, Sink &sink, int 
             }
             cap = cnt;
         }
-        cands.erase(std::remove_if(cands.begin(), cands.end(), [](const DecCand &c) { return c.type != 1u; }),
-                    cands.end());
-        std::sort(cands.begin(), cands.end(), [](const DecCand &a, const DecCand &b) { return a.bitpos < b.bitpos; });
+        cands.erase(std::remove_if(cands.begin(), cands.end(), [](const DecCand &x) { return x.type != 1u; }), cands.end());
+        std::sort(cands.begin(), cands.end(), less);
+        return BZ_OK;
     }
-    const size_t nc = cands.size();
-    w->stats[0] = nc;
 
-    u32 B = dec_batch_slots();
-    const u32 walk_wgs = 256; // persistent walker workgroups (bounds the window of blocks being walked; 128 ... 1024 measured: profiles/r04_decode_walk_schedule.md)
-    size_t c0 = 0, c1 = nc; // this rank's candidates
-    if (sh) {
-        c0 = nc * (size_t)sh->rank / (size_t)sh->world;
-        c1 = nc * (size_t)(sh->rank + 1) / (size_t)sh->world;
-        B = (u32)std::max<size_t>(c1 - c0, 1);
-    }
-    if (nc < B) B = (u32)(nc ? nc : 1);
-    const u32 B_want = B;
-    B = dec_fit_slots(w, B);
-    if (sh && B < B_want) return BZ_E_NOMEM; // a rank's share has to fit one batch (reported to the peers by the caller)
-    int inject_rank = -1, inject_phase = -1; // (tests) BZ_DEC_SHARD_FAIL=<rank>:<phase>: that rank fails on its own there
-    if (sh)
-        if (const char *e = getenv("BZ_DEC_SHARD_FAIL")) (void)sscanf(e, "%d:%d", &inject_rank, &inject_phase);
-    if (sh && inject_rank == sh->rank && inject_phase == 0) return BZ_E_NOMEM;
+    // ---- D2, D3: the blocks tb[s0, s0 + nb) from Huffman symbols to the RLE1 image.  (s0 == 0 uploads the whole list.)
+    int dec_rebuild(const TrueBlocks &tb, u32 s0, u32 nb, Rebuilt &r)
     {
-        const int rc = dec_ensure(w, (size_t)B + kForcedSlots);
-        if (rc) return rc;
-    }
-    const u32 Bphys = B; // device slots
-    if (sh) B = (u32)(nc ? nc : 1); // the chain below sees all candidates as one batch
-
-    DevBits rd;
-    rd.d = d_in;
-    rd.nbytes = n;
-    std::vector<DecBlockInfo> hinfo((size_t)B + kForcedSlots);
-    std::vector<DecBlockInfo> hphys(sh ? (size_t)Bphys : 0);
-
-    // BZip2DecoderBase state (decoder.rs:93-108) as far as the record chain needs it
-    u64 pos = rs ? rs->pos : 0;
-    u32 stream_no = rs ? rs->stream_no : 1, level = rs ? rs->level : 0, combined = rs ? rs->combined : 0;
-    KernelProf *prof = g->prof.on ? &g->prof : nullptr;
-    int d1_rec = -1;
-    bool need_header = rs ? rs->need_header : true;
-    const bool partial = rs && !rs->final; // more input may follow: do not judge what is near the end
-    if (rs) rs->stopped = false;
-    // state at the start of the record being looked at (what a partial call falls back to)
-    u64 rec_pos = pos;
-    u32 rec_combined = combined, rec_stream_no = stream_no;
-    bool rec_need_header = need_header;
-    bool have_next = false;
-    u32 next_head = 0, next_bits = 0;
-    size_t ci = 0;
-    bool finished = false;
-    // host destination: the copies out of the two staging buffers (see Sink); whatever way this function is left, the
-    // copies in flight are over when it returns (the staging buffers and the caller's buffer outlive them)
-    struct PoolGuard {
-        CopyPool *p;
-        ~PoolGuard()
-        {
-            if (p) p->wait_all();
+        r.err.assign(nb, 0);
+        r.len.assign(nb, 0);
+        DecArgs &a = r.a;
+        a.nb = nb;
+        // The launches of the T-vector sort and of the RLE1 undo follow the largest block at hand (bytes from the
+        // stream's level); small gain, low levels only (level 1: 64.3 -> 63 ms per GiB).
+        u32 max_bytes = 1, max_nsym = 1;
+        for (u32 i = s0; i < s0 + nb; ++i) {
+            max_bytes = std::max(max_bytes, tb[i].max_len);
+            max_nsym = std::max(max_nsym, tb[i].nsym);
         }
-    } pool_guard{sink.to_host() ? sink.pool : nullptr};
+        dec_args_shape(a, max_bytes, max_nsym);
+        dec_args_bind(w, a);
+        a.slot = w->slot.as<u32>() + s0;
+        a.nblock_max = w->nbmax.as<u32>() + s0;
+        if (!nb) return BZ_OK;
+        std::vector<u32> up; // (lives until the stream has been waited for)
+        if (s0 == 0) {
+            up.resize(2 * tb.size()); // slots, then lengths
+            for (size_t i = 0; i < tb.size(); ++i) up[i] = tb[i].slot, up[tb.size() + i] = tb[i].max_len;
+            HIPDEC(hipMemcpyAsync(w->slot.p, up.data(), tb.size() * 4, hipMemcpyHostToDevice, st));
+            HIPDEC(hipMemcpyAsync(w->nbmax.p, up.data() + tb.size(), tb.size() * 4, hipMemcpyHostToDevice, st));
+        }
+        HIPDEC(hipMemsetAsync(w->err.p, 0, (size_t)nb * 4, st));
+        HIPDEC(hipMemsetAsync(w->out_len.p, 0, (size_t)nb * 4, st));
+        HIPDEC(hipEventRecord(ev[0], st));
+        int mtf_rec = -1, wrec[4] = {-1, -1, -1, -1};
+        launch_dec_mtf(st, a, prof, &mtf_rec);
+        HIPDEC(hipEventRecord(ev[1], st));
+        HIPDEC(hipStreamSynchronize(st));
+        stage_time(1);
+        HIPDEC(hipEventRecord(ev[0], st));
+        launch_dec_walks(st, a, kWalkWgs, g->st2, w->ev_a, w->ev_b, prof, wrec);
+        HIPDEC(hipEventRecord(ev[1], st));
+        std::vector<u32> h_tt(prof ? nb : 0);
+        if (prof) HIPDEC(hipMemcpyAsync(h_tt.data(), w->tt_len.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+        HIPDEC(hipMemcpyAsync(r.err.data(), w->err.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+        HIPDEC(hipMemcpyAsync(r.len.data(), w->out_len.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+        HIPDEC(hipStreamSynchronize(st));
+        stage_time(2);
+        if (prof) { // algorithmic bytes per stage, now that symbol counts and block lengths are known
+            u64 nsym = 0, ntt = 0;
+            for (u32 i = 0; i < nb; ++i) {
+                nsym += tb[s0 + i].nsym;
+                ntt += r.err[i] ? 0 : h_tt[i];
+            }
+            prof->set_bytes(mtf_rec, nsym * 4 + ntt);    // symbols read twice (2 B), column written
+            prof->set_bytes(wrec[0], ntt * (1 + 1 + 4)); // column read twice, T written
+            prof->set_bytes(wrec[1], ntt * (4 + 1));     // one T entry read, one byte kept per step
+            prof->set_bytes(wrec[2], ntt * 2);           // rows read, image written
+            prof->set_bytes(wrec[3], ntt * (1 + 16.0 / 64 + 1)); // image read twice + tables
+        }
+        return BZ_OK;
+    }
+
+    // ---- D4: the bytes of the rebuilt blocks at dst + base[i], and their CRCs.  r.err[first_mark ...] goes up first:
+    // a block marked there writes nothing.
+    int dec_emit(const Rebuilt &r, u32 first_mark, const std::vector<u64> &base, u64 bytes, u32 max_len, u8 *dst, std::vector<u32> &h_crc)
+    {
+        const u32 nb = r.a.nb;
+        if (first_mark < nb)
+            HIPDEC(hipMemcpyAsync(w->err.as<u32>() + first_mark, r.err.data() + first_mark, (size_t)(nb - first_mark) * 4, hipMemcpyHostToDevice, st));
+        HIPDEC(hipMemcpyAsync(w->out_base.p, base.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
+        HIPDEC(hipEventRecord(ev[0], st));
+        int xrec = prof ? prof->begin(st, KID_DEC_RLE, bytes) : -1;
+        launch_dec_expand(st, r.a, w->out_base.as<u64>(), dst);
+        if (prof) prof->end(st, xrec);
+        xrec = prof ? prof->begin(st, KID_DEC_CRC, bytes) : -1;
+        launch_dec_crc(st, r.a, w->out_base.as<u64>(), dst, max_len, g->crc_tab.as<u32>(), g->xp2.as<u32>(), g->xp16.as<u32>());
+        if (prof) prof->end(st, xrec);
+        HIPDEC(hipEventRecord(ev[1], st));
+        h_crc.resize(nb);
+        HIPDEC(hipMemcpyAsync(h_crc.data(), w->crc.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+        HIPDEC(hipStreamSynchronize(st));
+        stage_time(3);
+        return BZ_OK;
+    }
+};
+
+} // namespace
+
+// ---- one stream (or a file of concatenated streams) ------------------------------------------------------------
+namespace {
+
+// The state of one decode_core call.  run() reads as the stages of a batch: D1, (sharded) the exchange of candidate
+// records, the record chain, D2..D4 with delivery, (sharded) the exchange of results.
+struct DecRun : DecCall {
+    const u8 *d_in;
+    u64 n;
+    Sink &sink;
+    int *verdict;
+    Shard *sh;
+    Resume *rs;
+    const u64 nbits = n * 8ull;
+    std::vector<DecCand> cands;
+    size_t nc = 0, c0 = 0, c1 = 0; // candidates; [c0, c1) are this rank's
+    size_t ci = 0;                 // first candidate of the batch at hand
+    u32 B = 0, Bphys = 0;          // blocks per batch as the chain sees them, and device slots
+    int inject_rank = -1, inject_phase = -1; // (tests) BZ_DEC_SHARD_FAIL=<rank>:<phase>: that rank fails on its own there
+    DevBits rd;
+    std::vector<DecBlockInfo> hinfo, hphys; // D1's results by chain slot, and (sharded) by device slot
+    ChainState cs, rec; // the chain, and its state at the start of the record being looked at (what a partial call falls back to)
+    bool partial = false; // more input may follow: do not judge what is near the end
+    // host destination: sub-batches leave through the two staging buffers in turn (see Sink)
     u32 batch_no = 0;
-    bool chain_told = false, out_open = false;
     size_t stage_ticket[2] = {0, 0};
     bool stage_busy[2] = {false, false};
+    // whatever way the call is left, the copies in flight are over when it returns (the staging buffers and the caller's
+    // buffer outlive them)
+    ~DecRun()
+    {
+        if (sink.to_host() && sink.pool) sink.pool->wait_all();
+    }
 
-    while (!finished) {
-        // ---- D1 over the next batch of candidates
-        while (ci < nc && cands[ci].bitpos < pos) ++ci;
-        const u32 nb1 = (u32)std::min<size_t>(B, nc - ci);
+    // ---- D1 over the batch's candidates (sharded: over this rank's share of all of them)
+    int d1_batch(u32 nb1)
+    {
         const size_t d1_first = sh ? c0 : ci;
         const u32 d1_count = sh ? (u32)(c1 - c0) : nb1;
         DecBlockInfo *d1_host = sh ? hphys.data() : hinfo.data();
-        if (d1_count) {
-            HIPDEC(hipMemcpyAsync(w->cands.p, cands.data() + d1_first, (size_t)d1_count * sizeof(DecCand), hipMemcpyHostToDevice, st));
-            HIPDEC(hipEventRecord(ev[0], st));
-            const int prec = prof ? prof->begin(st, KID_DEC_BLOCK, 0) : -1;
-            launch_dec_blocks(st, d_in, n, w->cands.as<DecCand>(), d1_count, w->info.as<DecBlockInfo>(), w->sym.as<u16>(),
-                              w->sel.as<u8>());
-            if (prof) prof->end(st, prec);
-            d1_rec = prec;
-            HIPDEC(hipEventRecord(ev[1], st));
-            HIPDEC(hipMemcpyAsync(d1_host, w->info.p, (size_t)d1_count * sizeof(DecBlockInfo), hipMemcpyDeviceToHost, st));
-            HIPDEC(hipStreamSynchronize(st));
-            stage_time(0);
-            // the 64 bytes behind every candidate's end, in one copy: what the chain below reads at stream ends
-            {
-                std::vector<u64> bases;
-                bases.reserve(d1_count);
-                for (u32 i = 0; i < d1_count; ++i) {
-                    const u64 b = (d1_host[i].end_bit >> 3) & ~(u64)15;
-                    if (b < n && (bases.empty() || bases.back() != b)) bases.push_back(b);
-                }
-                std::sort(bases.begin(), bases.end());
-                bases.erase(std::unique(bases.begin(), bases.end()), bases.end());
-                rd.pre_base.clear();
-                rd.pre_bytes.clear();
-                if (bases.size() >= 4) { // (a handful of streams: the copies on demand are as cheap)
-                    int prc;
-                    if ((prc = w->win_base.ensure(bases.size() * 8)) || (prc = w->win_bytes.ensure(bases.size() * 64))) return prc;
-                    HIPDEC(hipMemcpyAsync(w->win_base.p, bases.data(), bases.size() * 8, hipMemcpyHostToDevice, st));
-                    launch_dec_gather_windows(st, d_in, n, w->win_base.as<u64>(), (u32)bases.size(), w->win_bytes.as<u8>());
-                    rd.pre_bytes.resize(bases.size() * 64);
-                    HIPDEC(hipMemcpyAsync(rd.pre_bytes.data(), w->win_bytes.p, bases.size() * 64, hipMemcpyDeviceToHost, st));
-                    HIPDEC(hipStreamSynchronize(st));
-                    rd.pre_base.swap(bases);
-                }
-            }
-        }
-        if (d1_rec >= 0) { // algorithmic bytes of D1: the compressed bits of its candidates + 2 B per symbol
+        if (!d1_count) return BZ_OK;
+        HIPDEC(hipMemcpyAsync(w->cands.p, cands.data() + d1_first, (size_t)d1_count * sizeof(DecCand), hipMemcpyHostToDevice, st));
+        HIPDEC(hipEventRecord(ev[0], st));
+        const int prec = prof ? prof->begin(st, KID_DEC_BLOCK, 0) : -1;
+        launch_dec_blocks(st, d_in, n, w->cands.as<DecCand>(), d1_count, w->info.as<DecBlockInfo>(), w->sym.as<u16>(), w->sel.as<u8>());
+        if (prof) prof->end(st, prec);
+        HIPDEC(hipEventRecord(ev[1], st));
+        HIPDEC(hipMemcpyAsync(d1_host, w->info.p, (size_t)d1_count * sizeof(DecBlockInfo), hipMemcpyDeviceToHost, st));
+        HIPDEC(hipStreamSynchronize(st));
+        stage_time(0);
+        const int rc = prefetch_windows(d1_host, d1_count);
+        if (rc) return rc;
+        if (prec >= 0) { // algorithmic bytes of D1: the compressed bits of its candidates + 2 B per symbol
             u64 by = 0;
             for (u32 i = 0; i < d1_count; ++i)
                 by += (d1_host[i].end_bit > cands[d1_first + i].bitpos ? (d1_host[i].end_bit - cands[d1_first + i].bitpos) / 8 : 0) +
                       2ull * d1_host[i].nsym;
-            prof->set_bytes(d1_rec, by);
-            d1_rec = -1;
+            prof->set_bytes(prec, by);
         }
-        if (sh) {
-            // Before the exchange whose size depends on the scan: 8 bytes of status per rank.  A rank that
-            // failed on its own before this point (memory, a HIP error) reports it here (the caller of
-            // decode_core does, bz_gpu_decode_device_sharded) and every rank returns that error instead of
-            // waiting in a collective its peer never enters.
-            {
-                int64_t st0 = 0;
-                std::vector<int64_t> sts((size_t)sh->world, 0);
-                if (sh->allgather(sh->ctx, &st0, 8, sts.data()) != 0) {
-                    sh->phase = 2;
-                    return BZ_E_UNEXPECTED;
-                }
-                for (int r = 0; r < sh->world; ++r)
-                    if (sts[(size_t)r] != 0) {
-                        sh->phase = 2;
-                        return (int)sts[(size_t)r];
-                    }
-            }
-            // exchange: every rank learns what the chain needs about every candidate
-            const size_t maxc = (nc + (size_t)sh->world - 1) / (size_t)sh->world;
-            std::vector<ShardRec> mine(maxc ? maxc : 1), all((maxc ? maxc : 1) * (size_t)sh->world);
-            memset(mine.data(), 0, mine.size() * sizeof(ShardRec));
-            for (size_t i = 0; i < c1 - c0; ++i) {
-                mine[i].end_bit = hphys[i].end_bit;
-                mine[i].status = hphys[i].status;
-                mine[i].stored_crc = hphys[i].stored_crc;
-                mine[i].next_head = hphys[i].next_head;
-                mine[i].next_bits = hphys[i].next_bits;
-            }
-            if (sh->allgather(sh->ctx, mine.data(), mine.size() * sizeof(ShardRec), all.data()) != 0) {
+        return BZ_OK;
+    }
+
+    // the 64 bytes behind every candidate's end, in one copy: what the chain reads at stream ends (see DevBits)
+    int prefetch_windows(const DecBlockInfo *info, u32 count)
+    {
+        std::vector<u64> bases;
+        bases.reserve(count);
+        for (u32 i = 0; i < count; ++i) {
+            const u64 b = (info[i].end_bit >> 3) & ~(u64)15;
+            if (b < n && (bases.empty() || bases.back() != b)) bases.push_back(b);
+        }
+        std::sort(bases.begin(), bases.end());
+        bases.erase(std::unique(bases.begin(), bases.end()), bases.end());
+        rd.pre_base.clear();
+        rd.pre_bytes.clear();
+        if (bases.size() < 4) return BZ_OK; // (a handful of streams: the copies on demand are as cheap)
+        int rc;
+        if ((rc = w->win_base.ensure(bases.size() * 8)) || (rc = w->win_bytes.ensure(bases.size() * 64))) return rc;
+        HIPDEC(hipMemcpyAsync(w->win_base.p, bases.data(), bases.size() * 8, hipMemcpyHostToDevice, st));
+        launch_dec_gather_windows(st, d_in, n, w->win_base.as<u64>(), (u32)bases.size(), w->win_bytes.as<u8>());
+        rd.pre_bytes.resize(bases.size() * 64);
+        HIPDEC(hipMemcpyAsync(rd.pre_bytes.data(), w->win_bytes.p, bases.size() * 64, hipMemcpyDeviceToHost, st));
+        HIPDEC(hipStreamSynchronize(st));
+        rd.pre_base.swap(bases);
+        return BZ_OK;
+    }
+
+    // (sharded) the status round, then every rank learns what the chain needs about every candidate
+    int exchange_records()
+    {
+        // Before the exchange whose size depends on the scan: 8 bytes of status per rank.  A rank that
+        // failed on its own before this point (memory, a HIP error) reports it here (the caller of
+        // decode_core does, bz_gpu_decode_device_sharded) and every rank returns that error instead of
+        // waiting in a collective its peer never enters.
+        int64_t st0 = 0;
+        std::vector<int64_t> sts((size_t)sh->world, 0);
+        if (sh->allgather(sh->ctx, &st0, 8, sts.data()) != 0) {
+            sh->phase = 2;
+            return BZ_E_UNEXPECTED;
+        }
+        for (int r = 0; r < sh->world; ++r)
+            if (sts[(size_t)r] != 0) {
                 sh->phase = 2;
-                return BZ_E_UNEXPECTED;
+                return (int)sts[(size_t)r];
             }
-            sh->phase = 1; // from here on a rank-local error travels in the second exchange (ShardSum.pad)
-            if (inject_rank == sh->rank && inject_phase == 1) return BZ_E_UNEXPECTED;
-            for (int r = 0; r < sh->world; ++r) {
-                const size_t r0 = nc * (size_t)r / (size_t)sh->world, r1 = nc * (size_t)(r + 1) / (size_t)sh->world;
-                for (size_t i = r0; i < r1; ++i) {
-                    const ShardRec &s = all[(size_t)r * mine.size() + (i - r0)];
-                    DecBlockInfo &bi = hinfo[i];
-                    bi.end_bit = s.end_bit;
-                    bi.status = s.status;
-                    bi.stored_crc = s.stored_crc;
-                    bi.next_head = s.next_head;
-                    bi.next_bits = s.next_bits;
-                    bi.nsym = (i >= c0 && i < c1) ? hphys[i - c0].nsym : 0;
-                }
+        const size_t maxc = (nc + (size_t)sh->world - 1) / (size_t)sh->world;
+        std::vector<ShardRec> mine(maxc ? maxc : 1), all((maxc ? maxc : 1) * (size_t)sh->world);
+        memset(mine.data(), 0, mine.size() * sizeof(ShardRec));
+        for (size_t i = 0; i < c1 - c0; ++i)
+            mine[i] = ShardRec{hphys[i].end_bit, hphys[i].status, hphys[i].stored_crc, hphys[i].next_head, hphys[i].next_bits};
+        if (sh->allgather(sh->ctx, mine.data(), mine.size() * sizeof(ShardRec), all.data()) != 0) {
+            sh->phase = 2;
+            return BZ_E_UNEXPECTED;
+        }
+        sh->phase = 1; // from here on a rank-local error travels in the second exchange (ShardSum.pad)
+        if (inject_rank == sh->rank && inject_phase == 1) return BZ_E_UNEXPECTED;
+        for (int r = 0; r < sh->world; ++r) {
+            const size_t r0 = nc * (size_t)r / (size_t)sh->world, r1 = nc * (size_t)(r + 1) / (size_t)sh->world;
+            for (size_t i = r0; i < r1; ++i) {
+                const ShardRec &s = all[(size_t)r * mine.size() + (i - r0)];
+                DecBlockInfo &bi = hinfo[i];
+                bi.end_bit = s.end_bit;
+                bi.status = s.status;
+                bi.stored_crc = s.stored_crc;
+                bi.next_head = s.next_head;
+                bi.next_bits = s.next_bits;
+                bi.nsym = (i >= c0 && i < c1) ? hphys[i - c0].nsym : 0;
             }
         }
-        // ---- the record chain through this batch
-        std::vector<u32> bslot, bmax, bcrc;
+        return BZ_OK;
+    }
+
+    // a block that starts without its full 48-bit magic has no candidate: D1 for it alone, into a forced slot
+    int decode_forced(u32 slot)
+    {
+        const DecCand fc = {cs.pos, 1, 0};
+        HIPDEC(hipMemcpyAsync(w->cands.as<DecCand>() + slot, &fc, sizeof(fc), hipMemcpyHostToDevice, st));
+        HIPDEC(hipEventRecord(ev[0], st));
+        launch_dec_blocks(st, d_in, n, w->cands.as<DecCand>() + slot, 1, w->info.as<DecBlockInfo>() + slot,
+                          w->sym.as<u16>() + (size_t)slot * kMtfStride, w->sel.as<u8>() + (size_t)slot * 32768u);
+        HIPDEC(hipEventRecord(ev[1], st));
+        HIPDEC(hipMemcpyAsync(&hinfo[slot], w->info.as<DecBlockInfo>() + slot, sizeof(DecBlockInfo), hipMemcpyDeviceToHost, st));
+        HIPDEC(hipStreamSynchronize(st));
+        stage_time(0);
+        w->stats[3] += 1;
+        return BZ_OK;
+    }
+
+    // ---- the record chain through this batch (the rules: dec_chain.h; the policy of batches, forced slots and partial
+    // input: here).  term 0: the batch ended, more to come; 1: the end of the input, cleanly; 2: (partial) stopped in
+    // front of the record at `rec`; < 0: the decoder's verdict
+    int walk_chain(u32 nb1, TrueBlocks &tb, int &term)
+    {
         u32 nforced = 0;
-        int term = 0; // 0: batch ended, more to come; 1: end of input reached cleanly; <0: error
         size_t cj = ci;
-        bool stop = false;
-        while (!stop) {
-            rec_pos = pos;
-            rec_combined = combined;
-            rec_stream_no = stream_no;
-            rec_need_header = need_header;
-            if (partial && nbits - pos < 256) { // a header, a trailer or a block start may be cut off here
+        for (;;) {
+            rec = cs;
+            if (partial && nbits - cs.pos < 256) { // a header, a trailer or a block start may be cut off here
                 term = 2;
                 break;
             }
-            if (need_header) { // decoder.rs:171-187: 'B','Z','h' are read, not compared; the level digit is
-                (void)rd.read(pos, 8);
-                (void)rd.read(pos, 8);
-                (void)rd.read(pos, 8);
-                const u32 lv = rd.read(pos, 8);
-                if (lv < 0x31u || lv > 0x39u) {
-                    term = (stream_no == 1) ? BZ_E_MAGIC_FIRST : BZ_E_MAGIC;
-                    break;
-                }
-                level = lv - 0x30u;
-                need_header = false;
+            const ChainEvent ev = chain_open_record(cs, rd, nbits);
+            if (ev == ChainEvent::StreamEnd) continue;
+            if (ev != ChainEvent::Block) {
+                term = ev == ChainEvent::End ? 1 : ev == ChainEvent::Data ? BZ_E_DATA : ev == ChainEvent::MagicFirst ? BZ_E_MAGIC_FIRST : BZ_E_MAGIC;
+                break;
             }
-            u64 p = pos;
-            u32 head;
-            if (have_next) { // the block in front of this record already looked at these 8 bits
-                head = next_head;
-                p = pos + next_bits;
-                have_next = false;
+            while (cj < nc && cands[cj].bitpos < cs.pos) ++cj;
+            u32 slot;
+            if (cj < nc && cands[cj].bitpos == cs.pos) {
+                if (cj >= ci + nb1) break; // decoded by the next batch
+                slot = (u32)(cj - ci);
             } else {
-                head = rd.read(p, 8);
+                if (sh) return BZ_E_UNEXPECTED; // (a sharded decode needs every block to carry its full magic)
+                if (nforced == kForcedSlots) break;
+                slot = B + nforced++;
+                const int rc = decode_forced(slot);
+                if (rc) return rc;
             }
-            if (head == 0x31u) {
-                while (cj < nc && cands[cj].bitpos < pos) ++cj;
-                int slot = -1;
-                if (cj < nc && cands[cj].bitpos == pos) {
-                    if (cj < ci + nb1) slot = (int)(cj - ci);
-                    else {
-                        stop = true; // decoded by the next batch
-                        break;
-                    }
-                } else {
-                    // only the first byte of the block magic is compared (decoder.rs:204-221): decode here
-                    if (sh) return BZ_E_UNEXPECTED; // (a sharded decode needs every block to carry its full magic)
-                    if (nforced == kForcedSlots) {
-                        stop = true;
-                        break;
-                    }
-                    slot = (int)(B + nforced++);
-                    DecCand fc;
-                    fc.bitpos = pos;
-                    fc.type = 1;
-                    fc.pad = 0;
-                    HIPDEC(hipMemcpyAsync(w->cands.as<DecCand>() + slot, &fc, sizeof(fc), hipMemcpyHostToDevice, st));
-                    HIPDEC(hipEventRecord(ev[0], st));
-                    launch_dec_blocks(st, d_in, n, w->cands.as<DecCand>() + slot, 1, w->info.as<DecBlockInfo>() + slot,
-                                      w->sym.as<u16>() + (size_t)slot * kMtfStride, w->sel.as<u8>() + (size_t)slot * 32768u);
-                    HIPDEC(hipEventRecord(ev[1], st));
-                    HIPDEC(hipMemcpyAsync(&hinfo[slot], w->info.as<DecBlockInfo>() + slot, sizeof(DecBlockInfo),
-                                          hipMemcpyDeviceToHost, st));
-                    HIPDEC(hipStreamSynchronize(st));
-                    stage_time(0);
-                    w->stats[3] += 1;
-                }
-                const DecBlockInfo &bi = hinfo[slot];
-                // (partial) a block that ends at the edge of what has arrived, or fails and starts within one
-                // maximal block of that edge, may just be cut off: look again with more input.  A block that
-                // fails further in front cannot be repaired by more input (a record is at most a header of
-                // < 2^16 bits and 900001 codes of <= 20 bits): its verdict is final now, and the context does
-                // not keep -- and re-scan -- everything behind it until the input ends.
-                // (header: magic 48 + CRC 32 + randomised 1 + origPtr 24 + in-use maps 16 + 256 + tables 3 + selectors 15,
-                // 18002 selectors of <= 6 bits, six tables of 5 + 258 * (up to 39 delta bits) -- about 170 Kbit)
-                constexpr u64 kMaxRecordBits = (48 + 32 + 1 + 24 + 16 + 256 + 3 + 15) + 18002ull * 6ull + 6ull * (5ull + 258ull * 39ull) +
-                                               900001ull * 20ull;
-                if (partial && (bi.end_bit + 64 > nbits || (bi.status && nbits - rec_pos <= kMaxRecordBits))) {
-                    term = 2;
-                    break;
-                }
-                if (bi.status) {
-                    term = BZ_E_DATA;
-                    break;
-                }
-                bslot.push_back((u32)slot);
-                bmax.push_back(100000u * level);
-                bcrc.push_back(bi.stored_crc);
-                combined = rotl1(combined) ^ bi.stored_crc; // decoder.rs:199-200 (done when the next record is opened)
-                pos = bi.end_bit;
-                have_next = true;
-                next_head = bi.next_head;
-                next_bits = bi.next_bits;
-                if (!sh && bslot.size() >= (size_t)B) stop = true; // (sharded: the chain is not batched)
-            } else if (head == 0x17u) { // end of stream, decoder.rs:487-520
-                pos = p;
-                for (int k = 0; k < 5; ++k) (void)rd.read(pos, 8);
-                const u32 stored = rd.read(pos, 32);
-                if (stored != combined) {
-                    term = BZ_E_DATA;
-                    break;
-                }
-                pos = (pos + 7ull) & ~7ull;
-                if (pos > nbits) pos = nbits;
-                if (nbits - pos >= 8) {
-                    need_header = true;
-                    combined = 0;
-                    stream_no += 1;
-                } else {
-                    term = 1;
-                    break;
-                }
-            } else {
+            const DecBlockInfo &bi = hinfo[slot];
+            // (partial) a block that ends at the edge of what has arrived, or fails and starts within one
+            // maximal block of that edge, may just be cut off: look again with more input.  A block that
+            // fails further in front cannot be repaired by more input (a record is at most a header of
+            // < 2^16 bits and 900001 codes of <= 20 bits): its verdict is final now, and the context does
+            // not keep -- and re-scan -- everything behind it until the input ends.
+            // (header: magic 48 + CRC 32 + randomised 1 + origPtr 24 + in-use maps 16 + 256 + tables 3 + selectors 15,
+            // 18002 selectors of <= 6 bits, six tables of 5 + 258 * (up to 39 delta bits) -- about 170 Kbit)
+            constexpr u64 kMaxRecordBits = (48 + 32 + 1 + 24 + 16 + 256 + 3 + 15) + 18002ull * 6ull + 6ull * (5ull + 258ull * 39ull) +
+                                           900001ull * 20ull;
+            if (partial && (bi.end_bit + 64 > nbits || (bi.status && nbits - rec.pos <= kMaxRecordBits))) {
+                term = 2;
+                break;
+            }
+            if (bi.status) {
                 term = BZ_E_DATA;
                 break;
             }
+            tb.push_back({slot, 100000u * cs.level, bi.stored_crc, bi.nsym});
+            chain_take_block(cs, bi.end_bit, bi.stored_crc, bi.next_head, bi.next_bits);
+            if (!sh && tb.size() >= B) break; // (sharded: the chain is not batched)
         }
         if (rd.failed) return BZ_E_UNEXPECTED;
         ci = cj;
-        if (term != 0 && sink.chain_final && !chain_told) {
-            chain_told = true;
-            Resume fin;
-            fin.stopped = term == 2;
-            fin.pos = term == 2 ? rec_pos : pos;
-            fin.combined = term == 2 ? rec_combined : combined;
-            fin.stream_no = term == 2 ? rec_stream_no : stream_no;
-            fin.need_header = term == 2 ? rec_need_header : need_header;
-            fin.level = level;
-            sink.chain_final(fin);
-        }
-        if (sink.before_output && !out_open) {
-            out_open = true;
-            if (!sink.before_output()) {
-                sink.aborted = true;
-                return BZ_OK;
-            }
-        }
-        u64 my_first_ord = ~0ull; // stream ordinal of this rank's first block
-        const u64 n_true = bslot.size();
-        if (sh) {
-            std::vector<u32> ks, km, kc;
-            for (size_t i = 0; i < bslot.size(); ++i)
-                if (bslot[i] >= c0 && bslot[i] < c1) {
-                    if (my_first_ord == ~0ull) my_first_ord = i;
-                    ks.push_back((u32)(bslot[i] - c0));
-                    km.push_back(bmax[i]);
-                    kc.push_back(bcrc[i]);
-                }
-            bslot.swap(ks);
-            bmax.swap(km);
-            bcrc.swap(kc);
-        }
-        const std::vector<DecBlockInfo> &hslot = sh ? hphys : hinfo; // indexed by device slot
-        u64 local_fail = ~0ull; // index (in this rank's list) of its first failing block
-        int shard_rc = BZ_OK;   // an infrastructure error of this rank, told to the others
+        return BZ_OK;
+    }
 
-        // ---- D2..D4 for the true blocks of the batch
-        // Host destination: the blocks are rebuilt in SUB-BATCHES, so that the copy of sub-batch k to the caller's memory
-        // (sink.pool's thread) runs beside the kernels of sub-batch k + 1 -- with everything in one go the download stood
-        // behind the whole decode (118 ms per GiB host to host against 48 ms of kernels).  D1 stays one
-        // launch over the whole batch: it takes the time of ONE block's Huffman decode however many blocks there are
-        // (11 ms; four batches of 300 blocks paid it four times: measured, profiles/r05_host_copies.md).
-        const u32 nb_all = (u32)bslot.size();
+    // (sharded) of all true blocks, the ones this rank rebuilds, by device slot
+    void keep_own_blocks(TrueBlocks &tb, u64 &my_first_ord) const
+    {
+        TrueBlocks own;
+        for (size_t i = 0; i < tb.size(); ++i)
+            if (tb[i].slot >= c0 && tb[i].slot < c1) {
+                if (my_first_ord == ~0ull) my_first_ord = i;
+                own.push_back(tb[i]);
+                own.back().slot -= (u32)c0;
+            }
+        tb.swap(own);
+    }
+
+    // ---- D2..D4 for the true blocks of the batch
+    // Host destination: the blocks are rebuilt in SUB-BATCHES, so that the copy of sub-batch k to the caller's memory
+    // (sink.pool's thread) runs beside the kernels of sub-batch k + 1 -- with everything in one go the download stood
+    // behind the whole decode (118 ms per GiB host to host against 48 ms of kernels).  D1 stays one
+    // launch over the whole batch: it takes the time of ONE block's Huffman decode however many blocks there are
+    // (11 ms; four batches of 300 blocks paid it four times: measured, profiles/r05_host_copies.md).
+    // local_fail: index (in this rank's list) of its first failing block; shard_rc: an infrastructure error of this rank,
+    // told to the others.
+    int rebuild_batch(const TrueBlocks &tb, int term, u64 &local_fail, int &shard_rc, bool &finished)
+    {
+        const u32 nb_all = (u32)tb.size();
         u32 sub_max = nb_all;
         if (sink.to_host() && sink.pool && !sh && nb_all) {
             const u32 hb = 320;
             const u32 nbat = (nb_all + hb - 1) / hb; // (equal sub-batches: 1189 blocks are 4 x 298, not 3 x 320 + 229)
             sub_max = (nb_all + nbat - 1) / nbat;
         }
-        if (nb_all) {
-            w->stats[1] += nb_all;
-            HIPDEC(hipMemcpyAsync(w->slot.p, bslot.data(), (size_t)nb_all * 4, hipMemcpyHostToDevice, st));
-            HIPDEC(hipMemcpyAsync(w->nbmax.p, bmax.data(), (size_t)nb_all * 4, hipMemcpyHostToDevice, st));
-        }
+        w->stats[1] += nb_all;
         for (u32 s0 = 0; s0 < nb_all && !finished && local_fail == ~0ull && shard_rc == BZ_OK; s0 += sub_max) {
             const u32 nb = std::min(sub_max, nb_all - s0);
-            DecArgs a;
-            a.nb = nb;
-            {
-                // The launches of the T-vector sort and of the RLE1 undo follow the batch's largest block (bytes from the
-                // stream's level); small gain, low levels only (level 1: 64.3 -> 63 ms per GiB).
-                u32 max_bytes = 1, max_nsym = 1;
-                for (u32 i = 0; i < nb; ++i) {
-                    max_bytes = std::max(max_bytes, bmax[s0 + i]);
-                    max_nsym = std::max(max_nsym, hslot[bslot[s0 + i]].nsym);
-                }
-                dec_args_shape(a, max_bytes, max_nsym);
-            }
-            a.slot = w->slot.as<u32>() + s0;
-            a.nblock_max = w->nbmax.as<u32>() + s0;
-            dec_args_bind(w, a);
-            HIPDEC(hipMemsetAsync(w->err.p, 0, (size_t)nb * 4, st));
-            HIPDEC(hipMemsetAsync(w->out_len.p, 0, (size_t)nb * 4, st));
-            HIPDEC(hipEventRecord(ev[0], st));
-            int mtf_rec = -1, wrec[4] = {-1, -1, -1, -1};
-            launch_dec_mtf(st, a, prof, &mtf_rec);
-            HIPDEC(hipEventRecord(ev[1], st));
-            HIPDEC(hipStreamSynchronize(st));
-            stage_time(1);
-            HIPDEC(hipEventRecord(ev[0], st));
-            launch_dec_walks(st, a, walk_wgs, g->st2, w->ev_a, w->ev_b, prof, wrec);
-            HIPDEC(hipEventRecord(ev[1], st));
-            std::vector<u32> h_err(nb), h_len(nb), h_tt(prof ? nb : 0);
-            if (prof) HIPDEC(hipMemcpyAsync(h_tt.data(), w->tt_len.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-            HIPDEC(hipMemcpyAsync(h_err.data(), w->err.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-            HIPDEC(hipMemcpyAsync(h_len.data(), w->out_len.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-            HIPDEC(hipStreamSynchronize(st));
-            stage_time(2);
-            if (prof) { // algorithmic bytes per stage, now that symbol counts and block lengths are known
-                u64 nsym = 0, ntt = 0;
-                for (u32 i = 0; i < nb; ++i) {
-                    nsym += hslot[bslot[s0 + i]].nsym;
-                    ntt += h_err[i] ? 0 : h_tt[i];
-                }
-                prof->set_bytes(mtf_rec, nsym * 4 + ntt);    // symbols read twice (2 B), column written
-                prof->set_bytes(wrec[0], ntt * (1 + 1 + 4)); // column read twice, T written
-                prof->set_bytes(wrec[1], ntt * (4 + 1));     // one T entry read, one byte kept per step
-                prof->set_bytes(wrec[2], ntt * 2);           // rows read, image written
-                prof->set_bytes(wrec[3], ntt * (1 + 16.0 / 64 + 1)); // image read twice + tables
-            }
+            Rebuilt r;
+            int rc = dec_rebuild(tb, s0, nb, r);
+            if (rc) return rc;
             // blocks in front of the first one that failed to rebuild
             u32 good = nb;
             for (u32 i = 0; i < nb; ++i)
-                if (h_err[i]) {
+                if (r.err[i]) {
                     good = i;
                     break;
                 }
@@ -781,123 +740,32 @@ static int decode_core(bz_gpu_engine *g, const u8 *d_in, u64 n, Sink &sink, int 
             u32 max_len = 0;
             for (u32 i = 0; i < good; ++i) {
                 h_base[i] = bytes;
-                bytes += h_len[i];
-                max_len = std::max(max_len, h_len[i]);
+                bytes += r.len[i];
+                max_len = std::max(max_len, r.len[i]);
             }
             u32 keep = good; // blocks whose bytes are handed out
             bool crc_bad = false;
-            if (sink.dry) {
-                sink.produced += bytes;
-            } else if (good) {
-                u8 *dst = nullptr;
-                if (sink.to_host()) {
-                    const u32 sb = batch_no & 1u;
-                    if (stage_busy[sb]) { // the copy of the batch before the last one reads this buffer
-                        sink.pool->wait(stage_ticket[sb]);
-                        stage_busy[sb] = false;
-                    }
-                    const int rc = sink.staging[sb]->ensure(bytes + 64);
-                    if (rc) return rc;
-                    dst = sink.staging[sb]->as<u8>();
-                } else {
-                    if (sink.produced + bytes > sink.cap) {
-                        if (!sh) return BZ_E_CAPACITY;
-                        shard_rc = BZ_E_CAPACITY; // reported after the exchange: peers are waiting in it
-                    }
-                    dst = sink.d_out + sink.produced;
-                }
-                if (shard_rc == BZ_OK) {
-                // blocks behind `good` keep err != 0 or are skipped by clearing their length
-                if (good < nb) {
-                    std::vector<u32> ones(nb - good, 1u);
-                    HIPDEC(hipMemcpyAsync(w->err.as<u32>() + good, ones.data(), (size_t)(nb - good) * 4, hipMemcpyHostToDevice, st));
-                }
-                HIPDEC(hipMemcpyAsync(w->out_base.p, h_base.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
-                HIPDEC(hipEventRecord(ev[0], st));
-                int xrec = prof ? prof->begin(st, KID_DEC_RLE, bytes) : -1;
-                launch_dec_expand(st, a, w->out_base.as<u64>(), dst);
-                if (prof) prof->end(st, xrec);
-                xrec = prof ? prof->begin(st, KID_DEC_CRC, bytes) : -1;
-                launch_dec_crc(st, a, w->out_base.as<u64>(), dst, max_len, g->crc_tab.as<u32>(), g->xp2.as<u32>(), g->xp16.as<u32>());
-                if (prof) prof->end(st, xrec);
-                HIPDEC(hipEventRecord(ev[1], st));
-                std::vector<u32> h_crc(nb);
-                HIPDEC(hipMemcpyAsync(h_crc.data(), w->crc.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-                HIPDEC(hipStreamSynchronize(st));
-                stage_time(3);
+            u8 *dst = nullptr;
+            const bool emit = !sink.dry && good;
+            if (sink.dry) sink.produced += bytes;
+            if (emit && (rc = emit_dst(bytes, dst, shard_rc))) return rc;
+            if (emit && shard_rc == BZ_OK) {
+                for (u32 i = good; i < nb; ++i) r.err[i] = 1u; // blocks behind `good` write nothing
+                std::vector<u32> h_crc;
+                if ((rc = dec_emit(r, good, h_base, bytes, max_len, dst, h_crc))) return rc;
                 u64 valid = bytes;
                 for (u32 i = 0; i < good; ++i) {
-                    if (~h_crc[i] != bcrc[s0 + i]) { // decoder.rs:189-198: noticed after the block's bytes went out
+                    if (~h_crc[i] != tb[s0 + i].crc) { // decoder.rs:189-198: noticed after the block's bytes went out
                         crc_bad = true;
                         keep = i + 1;
-                        valid = h_base[i] + h_len[i];
+                        valid = h_base[i] + r.len[i];
                         break;
                     }
                 }
-                if (sink.seg_alloc) {
-                    if (valid) {
-                        u8 *hp = sink.seg_alloc((size_t)valid);
-                        if (!hp) return BZ_E_NOMEM;
-                        if (sink.pool) {
-                            const u32 sb = batch_no & 1u;
-                            auto done_cb = sink.seg_done;
-                            const size_t vb = (size_t)valid;
-                            const bool fresh = sink.seg_fresh ? sink.seg_fresh(hp) : true;
-                            stage_ticket[sb] = sink.pool->submit(hp, dst, vb, hipMemcpyDeviceToHost, fresh, [done_cb, hp, vb](bool ok) { done_cb(hp, vb, ok); });
-                            stage_busy[sb] = true;
-                        } else {
-                            const bool ok = hipMemcpy(hp, dst, valid, hipMemcpyDeviceToHost) == hipSuccess;
-                            sink.seg_done(hp, (size_t)valid, ok);
-                            if (!ok) return BZ_E_UNEXPECTED;
-                        }
-                    }
-                    if (dec_trace())
-                        fprintf(stderr, "bz decode sub-batch %u: %u blocks, %llu bytes; stages so far D0+D1 %.2f, MTF %.2f, walks %.2f, expand+CRC %.2f ms (at %.1f)\n",
-                                batch_no, nb, (unsigned long long)valid, w->t_stage[0] * 1e3, w->t_stage[1] * 1e3, w->t_stage[2] * 1e3,
-                                w->t_stage[3] * 1e3, dec_now_ms());
-                    batch_no += 1;
-                } else if (sink.host) {
-                    const size_t old = sink.host->len;
-                    if (old + valid > sink.host->cap) {
-                        // room for the rest of the file too, going by this batch's bytes per block (growing moves the
-                        // buffer: copies in flight are waited for, and every growth copies what is there)
-                        if (sink.pool) sink.pool->wait_all();
-                        stage_busy[0] = stage_busy[1] = false;
-                        size_t want = old + valid;
-                        // blocks behind this sub-batch, and -- while the chain has not ended -- the candidates behind the batch,
-                        // but no more of them than the input left can hold (a block record is 80 bits and more; junk behind
-                        // a stream may hold magic patterns by the million, and a chain that has ended takes none of them)
-                        size_t rest = (size_t)(nb_all - s0 - nb);
-                        if (term == 0 && nc > ci) {
-                            const u64 bits_left = nbits > pos ? nbits - pos : 0ull;
-                            rest += std::min<size_t>(nc - ci, (size_t)(bits_left / 80ull));
-                        }
-                        if (rest && keep) {
-                            const double per_block = std::min((double)valid / (double)keep, 900000.0 * 1.25 + 64.0);
-                            want += (size_t)(per_block * (double)rest * 1.02) + ((size_t)1 << 20);
-                        }
-                        int hrc = sink.host->reserve(want);
-                        if (hrc != BZ_OK && want > old + valid) hrc = sink.host->reserve(old + valid); // (the guess was too much: what is needed now)
-                        if (hrc != BZ_OK) return hrc;
-                    }
-                    if (valid) {
-                        if (sink.pool) {
-                            const u32 sb = batch_no & 1u;
-                            stage_ticket[sb] = sink.pool->submit(sink.host->p + old, dst, valid, hipMemcpyDeviceToHost, true); // (fresh pages: touched first, on several threads)
-                            stage_busy[sb] = true;
-                        } else {
-                            HIPDEC(hipMemcpy(sink.host->p + old, dst, valid, hipMemcpyDeviceToHost));
-                        }
-                    }
-                    sink.host->len = old + valid; // (bytes whose copies may still be in flight: settled before this function returns)
-                    if (dec_trace())
-                        fprintf(stderr, "bz decode batch %u: %u blocks, %llu bytes; stages so far D0+D1 %.2f, MTF %.2f, walks %.2f, expand+CRC %.2f ms (at %.1f)\n",
-                                batch_no, nb, (unsigned long long)valid, w->t_stage[0] * 1e3, w->t_stage[1] * 1e3, w->t_stage[2] * 1e3,
-                                w->t_stage[3] * 1e3, dec_now_ms());
-                    batch_no += 1;
-                }
+                if (sink.seg_alloc) rc = deliver_segment(dst, valid, nb);
+                else if (sink.host) rc = deliver_host(dst, valid, nb, keep, (size_t)(nb_all - s0 - nb), term);
+                if (rc) return rc;
                 sink.produced += valid;
-                } // shard_rc == BZ_OK
             }
             if (crc_bad) local_fail = s0 + keep - 1;
             else if (good < nb) local_fail = s0 + good;
@@ -906,219 +774,305 @@ static int decode_core(bz_gpu_engine *g, const u8 *d_in, u64 n, Sink &sink, int 
                 finished = true;
             }
         }
-        if (finished) continue;
-        if (sh) {
-            // settle the verdict and the place of every slice
-            std::vector<ShardSum> sums((size_t)sh->world);
-            ShardSum mine;
-            mine.bytes = sink.produced;
-            mine.fail_ord = (local_fail == ~0ull) ? ~0ull : my_first_ord + local_fail;
-            mine.first_ord = my_first_ord;
-            mine.pad = (u64)(u32)(-shard_rc);
-            sh->phase = 2;
-            if (sh->allgather(sh->ctx, &mine, sizeof(mine), sums.data()) != 0) return BZ_E_UNEXPECTED;
-            for (const ShardSum &s : sums)
-                if (s.pad) return -(int)s.pad; // some rank could not hold its slice (BZ_E_CAPACITY ...)
-            u64 fail = ~0ull;
-            for (const ShardSum &s : sums) fail = std::min(fail, s.fail_ord);
-            u64 off = 0, tot = 0;
-            for (int r = 0; r < sh->world; ++r) {
-                // a rank whose blocks all lie behind the failing one contributes nothing
-                const u64 by = (sums[r].first_ord == ~0ull || sums[r].first_ord > fail) ? 0 : sums[r].bytes;
-                if (r < sh->rank) off += by;
-                if (r == sh->rank) sink.produced = by;
-                tot += by;
+        return BZ_OK;
+    }
+
+    // where D4 writes `bytes` bytes: a staging buffer (host destination) or the caller's device memory
+    int emit_dst(u64 bytes, u8 *&dst, int &shard_rc)
+    {
+        if (sink.to_host()) {
+            const u32 sb = batch_no & 1u;
+            if (stage_busy[sb]) { // the copy of the batch before the last one reads this buffer
+                sink.pool->wait(stage_ticket[sb]);
+                stage_busy[sb] = false;
             }
-            sh->out_offset = off;
-            sh->total_len = tot;
-            w->stats[1] = n_true;
-            w->stats[2] = stream_no;
-            if (fail != ~0ull) *verdict = BZ_E_DATA;
-            else if (term < 0) *verdict = term;
-            finished = true;
-            continue;
+            const int rc = sink.staging[sb]->ensure(bytes + 64);
+            if (rc) return rc;
+            dst = sink.staging[sb]->as<u8>();
+            return BZ_OK;
         }
-        if (term == 2) { // (partial) stopped in front of a record: everything before it is decoded
-            rs->stopped = true;
-            pos = rec_pos;
-            combined = rec_combined;
-            stream_no = rec_stream_no;
-            need_header = rec_need_header;
-            finished = true;
-        } else if (term == 1) {
-            w->stats[2] = stream_no;
-            finished = true;
-        } else if (term < 0) {
-            *verdict = term;
-            w->stats[2] = stream_no;
-            finished = true;
+        if (sink.produced + bytes > sink.cap) {
+            if (!sh) return BZ_E_CAPACITY;
+            shard_rc = BZ_E_CAPACITY; // reported after the exchange: peers are waiting in it
         }
+        dst = sink.d_out + sink.produced;
+        return BZ_OK;
     }
-    if (sink.to_host() && sink.pool) {
-        sink.pool->wait_all();
-        if (sink.pool->failed()) return BZ_E_UNEXPECTED;
+
+    void trace_batch(const char *what, u32 nb, u64 valid) const
+    {
+        if (dec_trace())
+            fprintf(stderr, "bz decode %s %u: %u blocks, %llu bytes; stages so far D0+D1 %.2f, MTF %.2f, walks %.2f, expand+CRC %.2f ms (at %.1f)\n",
+                    what, batch_no, nb, (unsigned long long)valid, w->t_stage[0] * 1e3, w->t_stage[1] * 1e3, w->t_stage[2] * 1e3,
+                    w->t_stage[3] * 1e3, dec_now_ms());
     }
-    if (prof) prof->collect();
-    if (rs) {
-        rs->pos = pos;
-        rs->stream_no = stream_no;
-        rs->level = level;
-        rs->combined = combined;
-        rs->need_header = need_header;
+
+    // host destination, a buffer of its own for every sub-batch (the streaming context)
+    int deliver_segment(const u8 *dst, u64 valid, u32 nb)
+    {
+        if (valid) {
+            u8 *hp = sink.seg_alloc((size_t)valid);
+            if (!hp) return BZ_E_NOMEM;
+            if (sink.pool) {
+                const u32 sb = batch_no & 1u;
+                auto done_cb = sink.seg_done;
+                const size_t vb = (size_t)valid;
+                const bool fresh = sink.seg_fresh ? sink.seg_fresh(hp) : true;
+                stage_ticket[sb] = sink.pool->submit(hp, dst, vb, hipMemcpyDeviceToHost, fresh, [done_cb, hp, vb](bool ok) { done_cb(hp, vb, ok); });
+                stage_busy[sb] = true;
+            } else {
+                const bool ok = hipMemcpy(hp, dst, valid, hipMemcpyDeviceToHost) == hipSuccess;
+                sink.seg_done(hp, (size_t)valid, ok);
+                if (!ok) return BZ_E_UNEXPECTED;
+            }
+        }
+        trace_batch("sub-batch", nb, valid);
+        batch_no += 1;
+        return BZ_OK;
     }
-    return BZ_OK;
+
+    // host destination, one growing buffer (the one-shot call over host buffers)
+    int deliver_host(const u8 *dst, u64 valid, u32 nb, u32 keep, size_t blocks_behind, int term)
+    {
+        const size_t old = sink.host->len;
+        if (old + valid > sink.host->cap) {
+            // room for the rest of the file too, going by this batch's bytes per block (growing moves the
+            // buffer: copies in flight are waited for, and every growth copies what is there)
+            if (sink.pool) sink.pool->wait_all();
+            stage_busy[0] = stage_busy[1] = false;
+            size_t want = old + valid;
+            // blocks behind this sub-batch, and -- while the chain has not ended -- the candidates behind the batch,
+            // but no more of them than the input left can hold (a block record is 80 bits and more; junk behind
+            // a stream may hold magic patterns by the million, and a chain that has ended takes none of them)
+            size_t rest = blocks_behind;
+            if (term == 0 && nc > ci) {
+                const u64 bits_left = nbits > cs.pos ? nbits - cs.pos : 0ull;
+                rest += std::min<size_t>(nc - ci, (size_t)(bits_left / 80ull));
+            }
+            if (rest && keep) {
+                const double per_block = std::min((double)valid / (double)keep, 900000.0 * 1.25 + 64.0);
+                want += (size_t)(per_block * (double)rest * 1.02) + ((size_t)1 << 20);
+            }
+            int hrc = sink.host->reserve(want);
+            if (hrc != BZ_OK && want > old + valid) hrc = sink.host->reserve(old + valid); // (the guess was too much: what is needed now)
+            if (hrc != BZ_OK) return hrc;
+        }
+        if (valid) {
+            if (sink.pool) {
+                const u32 sb = batch_no & 1u;
+                stage_ticket[sb] = sink.pool->submit(sink.host->p + old, dst, valid, hipMemcpyDeviceToHost, true); // (fresh pages: touched first, on several threads)
+                stage_busy[sb] = true;
+            } else {
+                HIPDEC(hipMemcpy(sink.host->p + old, dst, valid, hipMemcpyDeviceToHost));
+            }
+        }
+        sink.host->len = old + valid; // (bytes whose copies may still be in flight: settled before decode_core returns)
+        trace_batch("batch", nb, valid);
+        batch_no += 1;
+        return BZ_OK;
+    }
+
+    // (sharded) settle the verdict and the place of every slice
+    int settle_shards(u64 my_first_ord, u64 local_fail, int shard_rc, u64 n_true, int term)
+    {
+        std::vector<ShardSum> sums((size_t)sh->world);
+        const ShardSum mine = {sink.produced, (local_fail == ~0ull) ? ~0ull : my_first_ord + local_fail, my_first_ord, (u64)(u32)(-shard_rc)};
+        sh->phase = 2;
+        if (sh->allgather(sh->ctx, &mine, sizeof(mine), sums.data()) != 0) return BZ_E_UNEXPECTED;
+        for (const ShardSum &s : sums)
+            if (s.pad) return -(int)s.pad; // some rank could not hold its slice (BZ_E_CAPACITY ...)
+        u64 fail = ~0ull;
+        for (const ShardSum &s : sums) fail = std::min(fail, s.fail_ord);
+        u64 off = 0, tot = 0;
+        for (int r = 0; r < sh->world; ++r) {
+            // a rank whose blocks all lie behind the failing one contributes nothing
+            const u64 by = (sums[r].first_ord == ~0ull || sums[r].first_ord > fail) ? 0 : sums[r].bytes;
+            if (r < sh->rank) off += by;
+            if (r == sh->rank) sink.produced = by;
+            tot += by;
+        }
+        sh->out_offset = off;
+        sh->total_len = tot;
+        w->stats[1] = n_true;
+        w->stats[2] = cs.stream_no;
+        if (fail != ~0ull) *verdict = BZ_E_DATA;
+        else if (term < 0) *verdict = term;
+        return BZ_OK;
+    }
+
+    int run(bz_gpu_engine *g_)
+    {
+        int rc;
+        if ((rc = open(g_))) return rc;
+        prof = g->prof.on ? &g->prof : nullptr;
+        if ((rc = dec_scan_candidates(
+                 (u32)std::min<u64>(n / 2048 + 1024, 0x7FFFFFFFu),
+                 [&](DecCand *out, u32 cap, u32 *count) { launch_dec_scan(st, d_in, n, out, cap, count); },
+                 [](const DecCand &a, const DecCand &b) { return a.bitpos < b.bitpos; }, cands)))
+            return rc;
+        nc = c1 = cands.size();
+        w->stats[0] = nc;
+        u32 want = 0;
+        if (sh) { // every rank runs D1 on its own contiguous range of candidates, in one batch
+            c0 = nc * (size_t)sh->rank / (size_t)sh->world;
+            c1 = nc * (size_t)(sh->rank + 1) / (size_t)sh->world;
+            want = (u32)std::max<size_t>(c1 - c0, 1);
+            if (const char *e = getenv("BZ_DEC_SHARD_FAIL")) (void)sscanf(e, "%d:%d", &inject_rank, &inject_phase);
+        }
+        if (sh && inject_rank == sh->rank && inject_phase == 0) return BZ_E_NOMEM;
+        if ((rc = dec_plan_slots(w, nc, want, &B))) return rc;
+        Bphys = B;
+        if (sh) B = (u32)(nc ? nc : 1); // the chain sees all candidates as one batch
+        rd.d = d_in;
+        rd.nbytes = n;
+        hinfo.resize((size_t)B + kForcedSlots);
+        hphys.resize(sh ? (size_t)Bphys : 0);
+        if (rs) {
+            cs = *rs;
+            cs.have_next = false; // (the head byte of the next record is read from the bytes handed in)
+            partial = !rs->final;
+            rs->stopped = false;
+        }
+        rec = cs;
+        bool chain_told = false, out_open = false, finished = false;
+        while (!finished) {
+            while (ci < nc && cands[ci].bitpos < cs.pos) ++ci;
+            const u32 nb1 = (u32)std::min<size_t>(B, nc - ci);
+            if ((rc = d1_batch(nb1))) return rc;
+            if (sh && (rc = exchange_records())) return rc;
+            TrueBlocks tb;
+            int term = 0;
+            if ((rc = walk_chain(nb1, tb, term))) return rc;
+            if (term != 0 && sink.chain_final && !chain_told) {
+                chain_told = true;
+                Resume fin;
+                static_cast<ChainState &>(fin) = term == 2 ? rec : cs;
+                fin.stopped = term == 2;
+                sink.chain_final(fin);
+            }
+            if (sink.before_output && !out_open) {
+                out_open = true;
+                if (!sink.before_output()) {
+                    sink.aborted = true;
+                    return BZ_OK;
+                }
+            }
+            u64 my_first_ord = ~0ull; // stream ordinal of this rank's first block
+            const u64 n_true = tb.size();
+            if (sh) keep_own_blocks(tb, my_first_ord);
+            u64 local_fail = ~0ull;
+            int shard_rc = BZ_OK;
+            if ((rc = rebuild_batch(tb, term, local_fail, shard_rc, finished))) return rc;
+            if (finished) continue;
+            if (sh) {
+                if ((rc = settle_shards(my_first_ord, local_fail, shard_rc, n_true, term))) return rc;
+                finished = true;
+            } else if (term == 2) { // (partial) stopped in front of a record: everything before it is decoded
+                rs->stopped = true;
+                cs = rec;
+                finished = true;
+            } else if (term != 0) {
+                if (term < 0) *verdict = term;
+                w->stats[2] = cs.stream_no;
+                finished = true;
+            }
+        }
+        if (sink.to_host() && sink.pool) {
+            sink.pool->wait_all();
+            if (sink.pool->failed()) return BZ_E_UNEXPECTED;
+        }
+        if (prof) prof->collect();
+        if (rs) static_cast<ChainState &>(*rs) = cs;
+        return BZ_OK;
+    }
+};
+
+} // namespace
+
+// Decodes d_in[n].  Returns an infrastructure status (BZ_OK, BZ_E_NOMEM, BZ_E_UNEXPECTED,
+// BZ_E_CAPACITY); the decoder's own verdict goes to *verdict (BZ_OK, BZ_E_DATA, BZ_E_MAGIC_FIRST,
+// BZ_E_MAGIC) and the bytes produced in front of it to sink.produced.
+static int decode_core(bz_gpu_engine *g, const u8 *d_in, u64 n, Sink &sink, int *verdict, Shard *sh = nullptr,
+                       Resume *rs = nullptr)
+{
+    *verdict = BZ_OK;
+    sink.produced = 0;
+    DecRun run{{}, d_in, n, sink, verdict, sh, rs};
+    return run.run(g);
 }
 
 // ---- many independent streams in one call ------------------------------------------------------------------
 // Entry i is in_len[i] bytes at d_in + in_off[i]; its result is that of decode_core on those bytes alone.  What reaches
 // across entries in decode_core -- one (in, nbytes) for the scan and for D1, one serial record chain on the host -- is
 // replaced by a front end that knows about entries (k_dec_scan_batch, k_dec_block<true>, k_dec_chain_batch: k_dec.hip);
-// D2..D4 run on the true blocks of all entries of a GROUP together: a maximal run of consecutive entries whose
-// candidates fit the D1 workspace.  Where decode_core stops at the first failing block, this driver stops only that
-// block's ENTRY.  An entry with more candidates than a group holds, and one whose chain meets a block without its full
-// magic (no candidate: `irregular`), is decoded by decode_core on its own range behind the batch path's output.
+// D2..D4 (dec_rebuild, dec_emit) run on the true blocks of all entries of a GROUP together: a maximal run of consecutive
+// entries whose candidates fit the D1 workspace.  Where decode_core stops at the first failing block, this driver stops
+// only that block's ENTRY.  An entry with more candidates than a group holds, and one whose chain meets a block without
+// its full magic (no candidate: `irregular`), is decoded by decode_core on its own range behind the batch path's output.
+// Of the Sink `o` the driver takes d_out / cap, dry, or host: one buffer that grows group by group (offsets are relative to it).
 namespace {
-struct BatchOut {
-    u8 *d_out = nullptr; // device destination ...
-    u64 cap = 0;
-    bool dry = false;    // ... or sizes only
-    HostBuf *host = nullptr; // host destination: one buffer that grows group by group (offsets are relative to it)
-};
 inline u64 up16(u64 x) { return (x + 15ull) & ~15ull; }
-} // namespace
 
-static int decode_batch_core(bz_gpu_engine *g, const u8 *d_in, const u64 *in_off, const u64 *in_len, size_t count,
-                             BatchOut &o, u64 *out_off, u64 *out_len, int32_t *verdict)
-{
-    HIPDEC(hipSetDevice(g->device));
-    if (!g->dec) g->dec = new DecWorkspace();
-    DecWorkspace *w = g->dec;
-    if (!w->ev_a) {
-        HIPDEC(hipEventCreateWithFlags(&w->ev_a, hipEventDisableTiming));
-        HIPDEC(hipEventCreateWithFlags(&w->ev_b, hipEventDisableTiming));
-    }
-    hipStream_t st = g->st;
+// The state of one decode_batch_core call.
+struct DecBatchRun : DecCall {
+    const u8 *d_in;
+    const u64 *in_len;
+    size_t count;
+    Sink &o;
+    u64 *out_off, *out_len;
+    int32_t *verdict;
     // timings and stats of the call: sums over its groups and its one-stream decodes (decode_core clears the workspace's)
     double t_sum[4] = {0, 0, 0, 0};
     u64 s_sum[4] = {0, 0, 0, 0}, b_sum[4] = {0, 0, 0, 0};
-    struct Totals {
-        DecWorkspace *w;
-        double *t;
-        u64 *s, *b;
-        ~Totals()
-        {
-            for (int i = 0; i < 4; ++i) w->t_stage[i] = t[i], w->stats[i] = s[i], w->bstats[i] = b[i];
-        }
-    } totals{w, t_sum, s_sum, b_sum};
-    hipEvent_t ev[2];
-    HIPDEC(hipEventCreate(&ev[0]));
-    HIPDEC(hipEventCreate(&ev[1]));
-    struct EvGuard {
-        hipEvent_t *e;
-        ~EvGuard()
-        {
-            (void)hipEventDestroy(e[0]);
-            (void)hipEventDestroy(e[1]);
-        }
-    } ev_guard{ev};
-    auto stage_time = [&](int stage) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) t_sum[stage] += ms * 1e-3;
-    };
+    std::vector<DecEntry> ents; // the entries that hold bytes (an empty one is BZ_E_MAGIC_FIRST without a look at the device)
+    std::vector<size_t> orig;   // their indices in the call
+    std::vector<DecCand> cands; // sorted by (entry, bit position)
+    std::vector<u32> one;       // entries (indices into ents) of the one-stream path
+    u32 B = 0;
+    u64 run_end = 0;   // end of the output so far
+    size_t next_i = 0; // entries of the call in front of this one have their offsets (or wait for the one-stream path)
 
-    // the entries that hold bytes (an empty one is BZ_E_MAGIC_FIRST without a look at the device)
-    std::vector<DecEntry> ents;
-    std::vector<size_t> orig; // their indices in the call
-    for (size_t i = 0; i < count; ++i) {
-        out_off[i] = out_len[i] = 0;
-        verdict[i] = BZ_E_MAGIC_FIRST;
-        if (in_len[i]) {
-            DecEntry e;
-            e.off = in_off[i];
-            e.len = in_len[i];
-            e.first_cand = e.ncand = 0;
-            ents.push_back(e);
-            orig.push_back(i);
-        }
+    ~DecBatchRun()
+    {
+        if (w)
+            for (int i = 0; i < 4; ++i) w->t_stage[i] = t_sum[i], w->stats[i] = s_sum[i], w->bstats[i] = b_sum[i];
     }
-    const u32 nent = (u32)ents.size();
+    void place_empties(size_t upto)
+    {
+        for (; next_i < upto; ++next_i)
+            if (!in_len[next_i]) {
+                out_off[next_i] = up16(run_end);
+                b_sum[0] += 1;
+            }
+    }
 
-    // ---- D0: one scan over the span of all entries; candidates sorted by (entry, bit position)
-    std::vector<DecCand> cands;
-    if (nent) {
+    // ---- D0: one scan over the span of all entries; every entry learns its range of the candidate list
+    int scan()
+    {
+        const u32 nent = (u32)ents.size();
         int rc;
-        if ((rc = w->count.ensure(16)) || (rc = w->ents.ensure((size_t)nent * sizeof(DecEntry)))) return rc;
+        if ((rc = w->ents.ensure((size_t)nent * sizeof(DecEntry)))) return rc;
         const u64 span0 = ents.front().off, span_end = ents.back().off + ents.back().len;
         if ((span_end - span0 + 1023u) / 1024u > 0x7FFFFFFFull) return BZ_E_PARAM;
         HIPDEC(hipMemcpyAsync(w->ents.p, ents.data(), (size_t)nent * sizeof(DecEntry), hipMemcpyHostToDevice, st));
         // (a tiny stream holds two magics in a few dozen bytes: room for those of every entry on top of decode_core's guess)
-        u32 cap = (u32)std::min<u64>((span_end - span0) / 2048 + 2ull * nent + 1024, 0x7FFFFFFFu);
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            if ((rc = w->cand_all.ensure((size_t)cap * sizeof(DecCand)))) return rc;
-            HIPDEC(hipEventRecord(ev[0], st));
-            launch_dec_scan_batch(st, d_in, span0, span_end, w->ents.as<DecEntry>(), nent, w->cand_all.as<DecCand>(), cap, w->count.as<u32>());
-            HIPDEC(hipEventRecord(ev[1], st));
-            u32 cnt = 0;
-            HIPDEC(hipMemcpyAsync(&cnt, w->count.p, 4, hipMemcpyDeviceToHost, st));
-            HIPDEC(hipStreamSynchronize(st));
-            stage_time(0);
-            if (cnt <= cap) {
-                cands.resize(cnt);
-                if (cnt) HIPDEC(hipMemcpy(cands.data(), w->cand_all.p, (size_t)cnt * sizeof(DecCand), hipMemcpyDeviceToHost));
-                break;
-            }
-            cap = cnt;
-        }
-        cands.erase(std::remove_if(cands.begin(), cands.end(), [](const DecCand &c) { return c.type != 1u; }), cands.end());
-        std::sort(cands.begin(), cands.end(), [](const DecCand &a, const DecCand &b) {
-            return a.pad != b.pad ? a.pad < b.pad : a.bitpos < b.bitpos;
-        });
+        if ((rc = dec_scan_candidates(
+                 (u32)std::min<u64>((span_end - span0) / 2048 + 2ull * nent + 1024, 0x7FFFFFFFu),
+                 [&](DecCand *out, u32 cap, u32 *cnt) { launch_dec_scan_batch(st, d_in, span0, span_end, w->ents.as<DecEntry>(), nent, out, cap, cnt); },
+                 [](const DecCand &a, const DecCand &b) { return a.pad != b.pad ? a.pad < b.pad : a.bitpos < b.bitpos; }, cands)))
+            return rc;
         if (cands.size() > 0xFFFFFFF0ull) return BZ_E_NOMEM;
-        for (size_t c = 0; c < cands.size(); ++c) {
-            if (cands[c].pad >= nent) return BZ_E_UNEXPECTED;
-            DecEntry &e = ents[cands[c].pad];
-            if (e.ncand++ == 0) e.first_cand = (u32)c;
+        for (size_t k = 0; k < cands.size(); ++k) {
+            if (cands[k].pad >= nent) return BZ_E_UNEXPECTED;
+            DecEntry &e = ents[cands[k].pad];
+            if (e.ncand++ == 0) e.first_cand = (u32)k;
         }
+        return BZ_OK;
     }
-    const size_t nc = cands.size();
-    s_sum[0] = nc;
 
-    // the D1 workspace, as decode_core computes it
-    u32 B = dec_batch_slots();
-    if (nc < B) B = (u32)(nc ? nc : 1);
-    B = dec_fit_slots(w, B);
+    // ---- the group of entries [k0, k1) with n candidates: D1 inside each entry, every entry's record chain, D2..D4
+    int group(u32 k0, u32 k1, u32 n)
     {
-        const int rc = dec_ensure(w, (size_t)B + kForcedSlots);
-        if (rc) return rc;
-    }
-    std::vector<u32> one; // entries (indices into ents) of the one-stream path
-    for (u32 k = 0; k < nent; ++k)
-        if (ents[k].ncand > B) {
-            one.push_back(k);
-            ents[k].ncand = kDecEntrySkip;
-        }
-    if (nent) HIPDEC(hipMemcpyAsync(w->ents.p, ents.data(), (size_t)nent * sizeof(DecEntry), hipMemcpyHostToDevice, st));
-
-    u64 run = 0;       // end of the output so far
-    size_t next_i = 0; // entries of the call in front of this one have their offsets (or wait for the one-stream path)
-    auto place_empties = [&](size_t upto) {
-        for (; next_i < upto; ++next_i)
-            if (!in_len[next_i]) {
-                out_off[next_i] = up16(run);
-                b_sum[0] += 1;
-            }
-    };
-    const u32 walk_wgs = 256;
-
-    for (u32 k0 = 0; k0 < nent;) {
-        if (ents[k0].ncand == kDecEntrySkip) { // (no group reaches across it: a group's candidates are one range of the list)
-            place_empties(orig[k0]);
-            next_i = orig[k0] + 1;
-            ++k0;
-            continue;
-        }
-        u32 k1 = k0, n = 0;
-        while (k1 < nent && ents[k1].ncand != kDecEntrySkip && n + ents[k1].ncand <= B) n += ents[k1++].ncand;
         const u32 ne = k1 - k0;
         u32 cand0 = 0; // the group's first candidate in the sorted list
         for (u32 k = k0; k < k1; ++k)
@@ -1128,12 +1082,9 @@ static int decode_batch_core(bz_gpu_engine *g, const u8 *d_in, const u64 *in_off
             }
         b_sum[3] += 1;
 
-        // ---- D1 over the group's candidates, each inside its own entry; then the record chain of every entry
         std::vector<u8> hchain((size_t)ne * sizeof(DecChainEntry) + (size_t)n * sizeof(DecChainCand));
-        {
-            int rc;
-            if ((rc = w->chain.ensure(hchain.size()))) return rc;
-        }
+        int rc;
+        if ((rc = w->chain.ensure(hchain.size()))) return rc;
         DecChainEntry *d_ce = w->chain.as<DecChainEntry>();
         DecChainCand *d_cc = reinterpret_cast<DecChainCand *>(d_ce + ne);
         if (n) HIPDEC(hipMemcpyAsync(w->cands.p, cands.data() + cand0, (size_t)n * sizeof(DecCand), hipMemcpyHostToDevice, st));
@@ -1150,60 +1101,27 @@ static int decode_batch_core(bz_gpu_engine *g, const u8 *d_in, const u64 *in_off
         const DecChainCand *cc = reinterpret_cast<const DecChainCand *>(hchain.data() + (size_t)ne * sizeof(DecChainEntry));
 
         // the true blocks of the group in entry order, and where each entry's begin
-        std::vector<u32> bslot, bmax, bcrc, bfirst((size_t)ne + 1, 0);
-        u32 max_bytes = 1, max_nsym = 1;
+        TrueBlocks tb;
+        std::vector<u32> bfirst((size_t)ne + 1, 0);
         for (u32 k = k0; k < k1; ++k) {
-            bfirst[k - k0] = (u32)bslot.size();
+            bfirst[k - k0] = (u32)tb.size();
             if (ce[k - k0].irregular) {
                 one.push_back(k);
                 continue;
             }
             s_sum[2] += ce[k - k0].streams;
-            for (u32 c = ents[k].first_cand - cand0, c_end = c + ents[k].ncand; ents[k].ncand && c < c_end; ++c)
-                if (cc[c].is_true) {
-                    bslot.push_back(c);
-                    bmax.push_back(cc[c].max_len);
-                    bcrc.push_back(cc[c].stored_crc);
-                    max_bytes = std::max(max_bytes, cc[c].max_len);
-                    max_nsym = std::max(max_nsym, cc[c].nsym);
-                }
+            for (u32 q = ents[k].first_cand - cand0, q_end = q + ents[k].ncand; ents[k].ncand && q < q_end; ++q)
+                if (cc[q].is_true) tb.push_back({q, cc[q].max_len, cc[q].stored_crc, cc[q].nsym});
         }
-        bfirst[ne] = (u32)bslot.size();
-        const u32 nb = (u32)bslot.size();
+        const u32 nb = bfirst[ne] = (u32)tb.size();
         b_sum[2] += nb;
         s_sum[1] += nb;
-
-        // ---- D2, D3 for all of them
-        DecArgs a;
-        a.nb = nb;
-        dec_args_shape(a, max_bytes, max_nsym);
-        dec_args_bind(w, a);
-        a.slot = w->slot.as<u32>();
-        a.nblock_max = w->nbmax.as<u32>();
-        std::vector<u32> h_err(nb), h_len(nb);
-        if (nb) {
-            HIPDEC(hipMemcpyAsync(w->slot.p, bslot.data(), (size_t)nb * 4, hipMemcpyHostToDevice, st));
-            HIPDEC(hipMemcpyAsync(w->nbmax.p, bmax.data(), (size_t)nb * 4, hipMemcpyHostToDevice, st));
-            HIPDEC(hipMemsetAsync(w->err.p, 0, (size_t)nb * 4, st));
-            HIPDEC(hipMemsetAsync(w->out_len.p, 0, (size_t)nb * 4, st));
-            HIPDEC(hipEventRecord(ev[0], st));
-            int mtf_rec = -1, wrec[4] = {-1, -1, -1, -1};
-            launch_dec_mtf(st, a, nullptr, &mtf_rec);
-            HIPDEC(hipEventRecord(ev[1], st));
-            HIPDEC(hipStreamSynchronize(st));
-            stage_time(1);
-            HIPDEC(hipEventRecord(ev[0], st));
-            launch_dec_walks(st, a, walk_wgs, g->st2, w->ev_a, w->ev_b, nullptr, wrec);
-            HIPDEC(hipEventRecord(ev[1], st));
-            HIPDEC(hipMemcpyAsync(h_err.data(), w->err.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-            HIPDEC(hipMemcpyAsync(h_len.data(), w->out_len.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-            HIPDEC(hipStreamSynchronize(st));
-            stage_time(2);
-        }
+        Rebuilt r;
+        if ((rc = dec_rebuild(tb, 0, nb, r))) return rc;
 
         // ---- every entry's place, from the lengths of the blocks in front of its first failing one (before any CRC is
         // looked at: a sizes-only call assigns the same offsets)
-        const u64 grp_start = up16(run);
+        const u64 grp_start = up16(run_end);
         std::vector<u64> h_base(nb, 0);
         std::vector<u32> good((size_t)ne, 0); // blocks of the entry that were rebuilt
         u32 max_len = 0;
@@ -1217,57 +1135,45 @@ static int decode_batch_core(bz_gpu_engine *g, const u8 *d_in, const u64 *in_off
             const u32 b0 = bfirst[k - k0], b1 = bfirst[k - k0 + 1];
             u32 gd = b1 - b0;
             for (u32 b = b0; b < b1; ++b)
-                if (h_err[b]) {
+                if (r.err[b]) {
                     gd = b - b0;
                     break;
                 }
             good[k - k0] = gd;
-            const u64 off = up16(run);
+            const u64 off = up16(run_end);
             u64 len = 0;
             for (u32 b = b0; b < b0 + gd; ++b) {
                 h_base[b] = off + len - (o.host ? grp_start : 0ull);
-                len += h_len[b];
-                max_len = std::max(max_len, h_len[b]);
+                len += r.len[b];
+                max_len = std::max(max_len, r.len[b]);
             }
-            for (u32 b = b0 + gd; b < b1; ++b) h_err[b] = 1u; // the blocks behind a failing one are not the entry's any more
+            for (u32 b = b0 + gd; b < b1; ++b) r.err[b] = 1u; // the blocks behind a failing one are not the entry's any more
             out_off[i] = off;
             out_len[i] = len;
             static const int kVerdict[4] = {BZ_OK, BZ_E_DATA, BZ_E_MAGIC_FIRST, BZ_E_MAGIC};
             verdict[i] = gd < b1 - b0 ? BZ_E_DATA : kVerdict[ce[k - k0].verdict & 3u];
-            run = off + len;
+            run_end = off + len;
             bytes += len;
         }
-        k0 = k1;
-        if (o.dry || !bytes) continue;
+        if (o.dry || !bytes) return BZ_OK;
         u8 *dst = o.d_out;
         if (o.host) {
-            int rc;
-            if ((rc = w->staging.ensure((size_t)(run - grp_start) + 64)) || (rc = o.host->reserve((size_t)run))) return rc;
+            if ((rc = w->staging.ensure((size_t)(run_end - grp_start) + 64)) || (rc = o.host->reserve((size_t)run_end))) return rc;
             dst = w->staging.as<u8>();
-        } else if (run > o.cap) {
+        } else if (run_end > o.cap) {
             return BZ_E_CAPACITY;
         }
 
-        // ---- D4: the bytes and their CRCs
-        HIPDEC(hipMemcpyAsync(w->err.p, h_err.data(), (size_t)nb * 4, hipMemcpyHostToDevice, st));
-        HIPDEC(hipMemcpyAsync(w->out_base.p, h_base.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
-        HIPDEC(hipEventRecord(ev[0], st));
-        launch_dec_expand(st, a, w->out_base.as<u64>(), dst);
-        launch_dec_crc(st, a, w->out_base.as<u64>(), dst, max_len, g->crc_tab.as<u32>(), g->xp2.as<u32>(), g->xp16.as<u32>());
-        HIPDEC(hipEventRecord(ev[1], st));
-        std::vector<u32> h_crc(nb);
-        HIPDEC(hipMemcpyAsync(h_crc.data(), w->crc.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-        HIPDEC(hipStreamSynchronize(st));
-        stage_time(3);
-        for (u32 k = k1 - ne; k < k1; ++k) {
-            const u32 e = k - (k1 - ne);
+        std::vector<u32> h_crc;
+        if ((rc = dec_emit(r, 0, h_base, bytes, max_len, dst, h_crc))) return rc;
+        for (u32 k = k0; k < k1; ++k) {
+            const u32 e = k - k0;
             if (ce[e].irregular) continue;
             const size_t i = orig[k];
-            const u32 b0 = bfirst[e];
             u64 len = 0;
-            for (u32 b = b0; b < b0 + good[e]; ++b) {
-                len += h_len[b];
-                if (~h_crc[b] != bcrc[b]) { // decoder.rs:189-198: noticed after the block's bytes went out
+            for (u32 b = bfirst[e]; b < bfirst[e] + good[e]; ++b) {
+                len += r.len[b];
+                if (~h_crc[b] != tb[b].crc) { // decoder.rs:189-198: noticed after the block's bytes went out
                     out_len[i] = len;
                     verdict[i] = BZ_E_DATA;
                     break;
@@ -1275,16 +1181,17 @@ static int decode_batch_core(bz_gpu_engine *g, const u8 *d_in, const u64 *in_off
             }
         }
         if (o.host) {
-            HIPDEC(hipMemcpy(o.host->p + grp_start, dst, (size_t)(run - grp_start), hipMemcpyDeviceToHost));
-            o.host->len = (size_t)run;
+            HIPDEC(hipMemcpy(o.host->p + grp_start, dst, (size_t)(run_end - grp_start), hipMemcpyDeviceToHost));
+            o.host->len = (size_t)run_end;
         }
+        return BZ_OK;
     }
 
     // ---- the one-stream path: decode_core on the entry's range, behind everything the batch path wrote
-    std::sort(one.begin(), one.end());
-    for (const u32 k : one) {
+    int one_stream(u32 k)
+    {
         const size_t i = orig[k];
-        const u64 off = up16(run);
+        const u64 off = up16(run_end);
         Sink sink;
         if (o.host) {
             const int rc = o.host->reserve((size_t)off);
@@ -1316,12 +1223,61 @@ static int decode_batch_core(bz_gpu_engine *g, const u8 *d_in, const u64 *in_off
         out_off[i] = off;
         out_len[i] = sink.produced;
         verdict[i] = v;
-        run = off + adv;
+        run_end = off + adv;
         if (o.host) o.host->len = (size_t)(off + sink.produced);
         b_sum[1] += 1;
+        return BZ_OK;
     }
-    place_empties(count);
-    return BZ_OK;
+
+    int run(bz_gpu_engine *g_, const u64 *in_off)
+    {
+        int rc;
+        if ((rc = open(g_, t_sum))) return rc;
+        for (size_t i = 0; i < count; ++i) {
+            out_off[i] = out_len[i] = 0;
+            verdict[i] = BZ_E_MAGIC_FIRST;
+            if (in_len[i]) {
+                ents.push_back(DecEntry{in_off[i], in_len[i], 0, 0});
+                orig.push_back(i);
+            }
+        }
+        const u32 nent = (u32)ents.size();
+        if (nent && (rc = scan())) return rc;
+        s_sum[0] = cands.size();
+        if ((rc = dec_plan_slots(w, cands.size(), 0, &B))) return rc;
+        for (u32 k = 0; k < nent; ++k)
+            if (ents[k].ncand > B) {
+                one.push_back(k);
+                ents[k].ncand = kDecEntrySkip;
+            }
+        if (nent) HIPDEC(hipMemcpyAsync(w->ents.p, ents.data(), (size_t)nent * sizeof(DecEntry), hipMemcpyHostToDevice, st));
+
+        for (u32 k0 = 0; k0 < nent;) {
+            if (ents[k0].ncand == kDecEntrySkip) { // (no group reaches across it: a group's candidates are one range of the list)
+                place_empties(orig[k0]);
+                next_i = orig[k0] + 1;
+                ++k0;
+                continue;
+            }
+            u32 k1 = k0, n = 0;
+            while (k1 < nent && ents[k1].ncand != kDecEntrySkip && n + ents[k1].ncand <= B) n += ents[k1++].ncand;
+            if ((rc = group(k0, k1, n))) return rc;
+            k0 = k1;
+        }
+        std::sort(one.begin(), one.end());
+        for (const u32 k : one)
+            if ((rc = one_stream(k))) return rc;
+        place_empties(count);
+        return BZ_OK;
+    }
+};
+} // namespace
+
+static int decode_batch_core(bz_gpu_engine *g, const u8 *d_in, const u64 *in_off, const u64 *in_len, size_t count,
+                             Sink &o, u64 *out_off, u64 *out_len, int32_t *verdict)
+{
+    DecBatchRun run{{}, d_in, in_len, count, o, out_off, out_len, verdict};
+    return run.run(g, in_off);
 }
 
 int dec_decode_for_verify(bz_gpu_engine *g, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap,
@@ -1430,7 +1386,7 @@ extern "C" int bz_gpu_decode_batch_device(bz_gpu_engine *g, const void *d_in, co
         bytes = bytes || h_in_len[i];
     }
     if (bytes && !d_in) return BZ_E_PARAM;
-    BatchOut o;
+    Sink o;
     o.d_out = static_cast<u8 *>(d_out);
     o.cap = cap;
     o.dry = (d_out == nullptr);
@@ -1581,7 +1537,7 @@ extern "C" int bz_decode_batch(int device, const uint8_t *const *ins, const size
         rc = BZ_E_UNEXPECTED;
         if ((!total || hipMemcpyAsync(g->dec_in.p, packed.data(), (size_t)total, hipMemcpyHostToDevice, g->st) == hipSuccess) &&
             hipStreamSynchronize(g->st) == hipSuccess) {
-            BatchOut o;
+            Sink o;
             o.host = &host;
             rc = decode_batch_core(g, static_cast<const u8 *>(g->dec_in.p), off.data(), len.data(), count, o, out_off, out_len, verdict);
         }

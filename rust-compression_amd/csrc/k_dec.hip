@@ -24,6 +24,7 @@
 //       pieces folded in GF(2).
 #include "bzgpu.h"
 #include "bz2_rnums.h"
+#include "dec_chain.h"
 
 namespace bzgpu {
 
@@ -1765,29 +1766,32 @@ void launch_dec_blocks_batch(hipStream_t st, const u8 *in, const DecEntry *ents,
     hipLaunchKernelGGL(k_dec_block<true>, dim3(ncand), dim3(kD1Threads), 0, st, in, (u64)0, cands, ncand, info, sym, sel_scratch, ents);
 }
 
-// up to 32 bits at `pos` of an entry, read like DevBits::read (dec_engine.hip): at the end of the entry the bits that
-// are left come back as a shorter number
-__device__ __forceinline__ u32 ent_read(const u8 *__restrict__ p, u64 nbytes, u64 &pos, u32 nbits)
-{
-    const u64 total = nbytes * 8ull;
-    const u64 avail = total > pos ? total - pos : 0ull;
-    const u32 k = avail < nbits ? (u32)avail : nbits;
-    if (k == 0) return 0u;
-    const u64 b0 = pos >> 3;
-    u64 acc = 0; // the 40 bits from byte b0 on
+// BitReader over one entry, for chain_open_record (dec_chain.h): up to 32 bits at `pos`; at the end of the entry the
+// bits that are left come back as a shorter number
+struct EntBits {
+    const u8 *__restrict__ p;
+    u64 nbytes;
+    __device__ __forceinline__ u32 read(u64 &pos, u32 nbits) const
+    {
+        const u64 total = nbytes * 8ull;
+        const u64 avail = total > pos ? total - pos : 0ull;
+        const u32 k = avail < nbits ? (u32)avail : nbits;
+        if (k == 0) return 0u;
+        const u64 b0 = pos >> 3;
+        u64 acc = 0; // the 40 bits from byte b0 on
 #pragma unroll
-    for (u32 i = 0; i < 5; ++i) acc = (acc << 8) | (u64)(b0 + i < nbytes ? p[b0 + i] : 0);
-    const u32 sh = (u32)pos & 7u;
-    pos += k;
-    return (u32)((acc >> (40u - sh - k)) & ((1ull << k) - 1ull));
-}
+        for (u32 i = 0; i < 5; ++i) acc = (acc << 8) | (u64)(b0 + i < nbytes ? p[b0 + i] : 0);
+        const u32 sh = (u32)pos & 7u;
+        pos += k;
+        return (u32)((acc >> (40u - sh - k)) & ((1ull << k) - 1ull));
+    }
+};
 
-// The record chain (stream header, blocks, end-of-stream record, next stream ...) of every entry of a group, one lane
-// per entry: the unsharded chain of decode_core (dec_engine.hip, the loop that opens with `rec_pos = pos`) with the
-// entry as the whole input.  cands[] / info[] are the group's (candidate `cand0` of the sorted list is their first);
-// out_cand[] was cleared by the launcher's caller.  A block that starts without its full 48-bit magic has no candidate
-// (the reference compares the first byte only, decoder.rs:204-221): the entry is marked irregular and left to the
-// one-stream path.
+// The record chain of every entry of a group, one lane per entry, with the entry as the whole input: the rules are
+// chain_open_record's (dec_chain.h, shared with the host loop of decode_core); this kernel finds each block's candidate
+// and says what it found.  cands[] / info[] are the group's (candidate `cand0` of the sorted list is their first);
+// out_cand[] was cleared by the launcher's caller.  A block that starts without its full 48-bit magic has no candidate:
+// the entry is marked irregular and left to the one-stream path.
 __global__ __launch_bounds__(64) void k_dec_chain_batch(const u8 *__restrict__ in, const DecEntry *__restrict__ ents, u32 e0, u32 ne,
                                                          const DecCand *__restrict__ cands, u32 cand0,
                                                          const DecBlockInfo *__restrict__ info,
@@ -1796,85 +1800,39 @@ __global__ __launch_bounds__(64) void k_dec_chain_batch(const u8 *__restrict__ i
     const u32 i = blockIdx.x * 64u + threadIdx.x;
     if (i >= ne) return;
     const DecEntry en = ents[e0 + i];
-    DecChainEntry r;
-    r.verdict = kChainOk;
-    r.streams = 1;
-    r.irregular = 0;
-    r.ntrue = 0;
+    DecChainEntry r = {kChainOk, 1, 0, 0}; // verdict, streams, irregular, true blocks
     if (en.ncand == kDecEntrySkip) {
         r.irregular = 1;
         out_ent[i] = r;
         return;
     }
-    const u8 *p = in + en.off;
-    const u64 n = en.len, nbits = n * 8ull;
+    EntBits rd{in + en.off, en.len};
+    const u64 nbits = en.len * 8ull;
     const u32 c0 = en.first_cand - cand0;
-    u64 pos = 0;
-    u32 level = 0, combined = 0, cj = 0, next_head = 0, next_bits = 0;
-    bool need_header = true, have_next = false;
+    ChainState s;
+    u32 cj = 0;
     while (true) {
-        if (need_header) { // 'B','Z','h' are read, not compared; the level digit is (decoder.rs:171-187)
-            (void)ent_read(p, n, pos, 24);
-            const u32 lv = ent_read(p, n, pos, 8);
-            if (lv < 0x31u || lv > 0x39u) {
-                r.verdict = r.streams == 1 ? kChainMagicFirst : kChainMagic;
-                break;
-            }
-            level = lv - 0x30u;
-            need_header = false;
+        const ChainEvent ev = chain_open_record(s, rd, nbits);
+        if (ev == ChainEvent::StreamEnd) continue;
+        if (ev != ChainEvent::Block) {
+            r.verdict = ev == ChainEvent::End ? kChainOk : ev == ChainEvent::Data ? kChainData : ev == ChainEvent::MagicFirst ? kChainMagicFirst : kChainMagic;
+            break;
         }
-        u64 q = pos;
-        u32 head;
-        if (have_next) { // the block in front already looked at these 8 bits
-            head = next_head;
-            q = pos + next_bits;
-            have_next = false;
-        } else {
-            head = ent_read(p, n, q, 8);
+        while (cj < en.ncand && cands[c0 + cj].bitpos < s.pos) ++cj;
+        if (!(cj < en.ncand && cands[c0 + cj].bitpos == s.pos)) {
+            r.irregular = 1;
+            break;
         }
-        if (head == 0x31u) {
-            while (cj < en.ncand && cands[c0 + cj].bitpos < pos) ++cj;
-            if (!(cj < en.ncand && cands[c0 + cj].bitpos == pos)) {
-                r.irregular = 1;
-                break;
-            }
-            const DecBlockInfo &bi = info[c0 + cj];
-            if (bi.status) {
-                r.verdict = kChainData;
-                break;
-            }
-            DecChainCand cc;
-            cc.is_true = 1;
-            cc.max_len = 100000u * level;
-            cc.stored_crc = bi.stored_crc;
-            cc.nsym = bi.nsym;
-            out_cand[c0 + cj] = cc;
-            r.ntrue += 1;
-            combined = ((combined << 1) | (combined >> 31)) ^ bi.stored_crc; // decoder.rs:199-200
-            pos = bi.end_bit;
-            have_next = true;
-            next_head = bi.next_head;
-            next_bits = bi.next_bits;
-        } else if (head == 0x17u) { // end of stream, decoder.rs:487-520
-            pos = q;
-            (void)ent_read(p, n, pos, 24);
-            (void)ent_read(p, n, pos, 16);
-            const u32 stored = ent_read(p, n, pos, 32);
-            if (stored != combined) {
-                r.verdict = kChainData;
-                break;
-            }
-            pos = (pos + 7ull) & ~7ull;
-            if (pos > nbits) pos = nbits;
-            if (nbits - pos < 8) break; // the clean end
-            need_header = true;
-            combined = 0;
-            r.streams += 1;
-        } else {
+        const DecBlockInfo &bi = info[c0 + cj];
+        if (bi.status) {
             r.verdict = kChainData;
             break;
         }
+        out_cand[c0 + cj] = DecChainCand{1u, 100000u * s.level, bi.stored_crc, bi.nsym}; // is_true, max_len, ...
+        r.ntrue += 1;
+        chain_take_block(s, bi.end_bit, bi.stored_crc, bi.next_head, bi.next_bits);
     }
+    r.streams = s.stream_no;
     out_ent[i] = r;
 }
 

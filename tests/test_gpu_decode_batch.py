@@ -232,6 +232,49 @@ def test_irregular_entry_takes_the_one_stream_path(eng, oracle):
     assert dev.o_off[1] >= dev.o_off[0] + dev.o_len[0] and dev.o_off[1] >= dev.o_off[2] + dev.o_len[2]
 
 
+def test_chain_on_the_device_and_on_the_host_agree(eng, oracle, monkeypatch):
+    """The record chain's rules live in csrc/dec_chain.h once; k_dec_chain_batch (the batch path) and the host loop of
+    decode_core (the one-stream path) both walk with them.  The same entries through both: at the default every entry is
+    chained on the device; with a D1 workspace of ONE block every entry that holds two block magics or more is chained
+    on the host.  Same bytes, lengths and verdicts -- the oracle's -- either way.  Offsets follow the path (a one-stream
+    entry lies behind everything the batch path wrote): each run's are the running sum, rounded up to 16, of the lengths
+    a sizes-only call reports, over the batch path's entries in call order and then the one-stream path's."""
+    d2, z2 = two_blocks()
+    three = z2 * 3
+    digit, comb = bytearray(three), bytearray(three)
+    assert digit[len(z2):len(z2) + 4] == b"BZh1"
+    digit[len(z2) + 3] = ord("0")                             # the second stream's level digit
+    comb[-3] ^= 1                                             # the last combined CRC
+    main = [z2, three, bytes(digit), bytes(comb), three[:-1], three[:-5], three[:-11]]
+    ents = []
+    for i, z in enumerate(main):
+        ents += [z, bz2.compress(sample(2)[97 * i:97 * i + 200 + i], 1)]
+    ents.pop()                                                # a valid one-block neighbour BETWEEN each
+    assert len(ents) == 13
+    slow = list(range(0, 13, 2))                              # the entries with two magics or more
+
+    def run(order):
+        dev = Dev(ents)
+        _, s_len, _ = dev.sizes(eng)
+        got = dev.check(eng, oracle)
+        want_off, end = [0] * len(ents), 0
+        for i in order:
+            want_off[i] = (end + 15) & ~15
+            end = want_off[i] + s_len[i]
+        assert dev.o_off == want_off
+        return got, dev.o_len, eng.decode_batch_stats()
+
+    got_a, len_a, stats_a = run(list(range(13)))
+    assert stats_a[0] == 13 and stats_a[1] == 0
+    monkeypatch.setenv("BZ_DEC_BATCH", "1")
+    got_b, len_b, stats_b = run([i for i in range(13) if i not in slow] + slow)
+    assert stats_b[1] == len(slow) > 0 and stats_b[0] == 13 - len(slow)
+    assert got_a == got_b and len_a == len_b
+    assert got_a[0] == (d2, 0) and got_a[2] == (d2 * 3, 0)
+    assert got_a[4] == (d2, E_MAGIC) and got_a[6] == (d2 * 3, E_DATA)
+    assert [v for _, v in got_a[8::2]] == [E_DATA] * 3 and [v for _, v in got_a[1::2]] == [0] * 6
+
+
 def test_group_seams(eng, oracle, monkeypatch):
     """a workspace of three blocks: groups end where the next entry does not fit, and the entry of four blocks fits none"""
     monkeypatch.setenv("BZ_DEC_BATCH", "3")
