@@ -624,6 +624,35 @@ int df_encode_buffer_dict(int kind, int device, const uint8_t *in, size_t in_len
                           const uint8_t *dict, size_t dict_len,
                           uint8_t **out, size_t *out_len);
 
+/* Many independent inputs, one stream each, in one call (the Deflate counterpart of bz_gpu_encode_batch_device).
+ * Input i is the h_in_len[i] bytes at d_in + h_in_off[i]: d_in 16-byte aligned, every offset a multiple of 16, the ranges
+ * ascending and disjoint; bytes outside the ranges are never read as part of any input.  Stream i -- the bytes of
+ * df_gpu_encode_device(g, kind, d_in + h_in_off[i], h_in_len[i], ...), bit for bit -- is written at d_out + h_out_off[i]
+ * (h_out_len[i] bytes): input order, each stream at a multiple of 4 bytes, zeros between them, nothing at or behind
+ * d_out + cap.  One `kind` for the call, no dictionary.  Inputs of at most 0xFFFF bytes are exactly one Deflate block
+ * (MAX_BLOCK_SIZE, src/deflate/encoder.rs:577-597) and are encoded together, whatever their number, in sub-batches of
+ * BZ_DF_BATCH_MIB (default 64) MiB of 4 KiB-aligned slots: one pass of the pipeline, one host round trip and one placement
+ * per sub-batch, the container checksums, headers and trailers written on the device.  Every other input takes the path
+ * of df_gpu_encode_device, in its turn, inside the same call.  BZ_E_PARAM: kind outside 0..2, a null engine, a null array
+ * with count > 0, a misaligned d_in or offset, ranges that overlap or are out of order; BZ_E_CAPACITY: cap too small
+ * (df_encode_batch_bound always suffices: the sum of df_encode_bound, each rounded up to 4); count == 0: BZ_OK, nothing
+ * touched.  BZ_DF_MATCH=walk and BZ_DF_PARSE=doubling do not apply to the batch path. */
+size_t df_encode_batch_bound(const uint64_t *in_len, size_t count);
+int df_gpu_encode_batch_device(bz_gpu_engine *g, int kind, const void *d_in,
+                               const uint64_t *h_in_off, const uint64_t *h_in_len, size_t count,
+                               void *d_out, size_t cap, uint64_t *h_out_off, uint64_t *h_out_len);
+/* The last df_gpu_encode_batch_device call: [0] inputs taken by the batch path [1] inputs that took the one-input path
+ * [2] sub-batches, and of the batch-path inputs' blocks [3] stored [4] fixed [5] dynamic [6] tables on the length-limited
+ * path [7] dynamic blocks without any match (see df_gpu_last_stats [6]).  After such a call df_gpu_last_timings holds the
+ * batch path's stages summed over the sub-batches. */
+int df_gpu_last_batch_stats(bz_gpu_engine *g, uint64_t out[8]);
+/* The host form (mirrors bz_encode_batch): the inputs are packed at 16-byte-aligned offsets, uploaded once, encoded by one
+ * df_gpu_encode_batch_device call on an engine of the per-process cache and downloaded once.  Stream i is
+ * (*out)[out_off[i] .. + out_len[i]); *out is one malloc'ed buffer, release with bz_free.  count == 0: BZ_OK, *out an
+ * empty buffer, no device is touched. */
+int df_encode_batch(int kind, int device, const uint8_t *const *ins, const size_t *lens, size_t count,
+                    uint8_t **out, uint64_t *out_off, uint64_t *out_len);
+
 /* Streaming context == the Encoder::next contract of the three encoders:
  * df_enc_write feeds bytes, df_enc_end(action) marks the end of an input
  * iterator (0 Run, kind 0: nothing comes out yet -- the blocks the reference hands out while it

@@ -94,6 +94,7 @@ EXPORTS = [
     "df_encode_bound", "df_gpu_encode_device", "df_gpu_last_timings", "df_gpu_last_stats", "df_gpu_debug_codes",
     "df_gpu_debug_blocks", "df_encode_buffer", "df_gpu_encode_device_dict", "df_encode_buffer_dict", "df_enc_create_dict",
     "df_enc_create", "df_enc_write", "df_enc_end", "df_enc_read", "df_enc_pending", "df_enc_destroy", "df_enc_finished",
+    "df_encode_batch_bound", "df_gpu_encode_batch_device", "df_gpu_last_batch_stats", "df_encode_batch",
 ]
 
 
@@ -240,6 +241,11 @@ def lib():
     L.df_enc_pending.argtypes = [vp]
     L.df_enc_destroy.restype = None
     L.df_enc_destroy.argtypes = [vp]
+    L.df_encode_batch_bound.restype = sz
+    L.df_encode_batch_bound.argtypes = [u64p, sz]
+    L.df_gpu_encode_batch_device.argtypes = [vp, C.c_int, vp, u64p, u64p, sz, vp, sz, u64p, u64p]
+    L.df_gpu_last_batch_stats.argtypes = [vp, u64p]
+    L.df_encode_batch.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, sz, C.POINTER(u8p), u64p, u64p]
     _LIB = L
     return L
 
@@ -642,6 +648,33 @@ def deflate_bound(n):
     return lib().df_encode_bound(n)
 
 
+def deflate_encode_batch_bound(lens):
+    """An output capacity that always suffices for GpuEngine.deflate_encode_batch_device (df_encode_batch_bound)."""
+    a = (C.c_uint64 * max(len(lens), 1))(*lens)
+    return lib().df_encode_batch_bound(a, len(lens))
+
+
+def deflate_compress_batch(datas, kind=DEFLATE, device=0):
+    """Many independent inputs in one call (df_encode_batch) -> list of streams: element i is
+    deflate_compress(datas[i], kind), bit for bit.  Inputs of at most 65 535 bytes (one Deflate block for certain) are
+    encoded together in one pass of the pipeline, however many there are."""
+    if kind not in (DEFLATE, ZLIB, GZIP):
+        raise ValueError("invalid kind")
+    datas = [d if isinstance(d, bytes) else bytes(d) for d in datas]
+    k = len(datas)
+    ins = (C.c_char_p * max(k, 1))(*datas)
+    lens = (C.c_size_t * max(k, 1))(*[len(d) for d in datas])
+    off = (C.c_uint64 * max(k, 1))()
+    ln = (C.c_uint64 * max(k, 1))()
+    out = C.POINTER(C.c_uint8)()
+    _check(lib().df_encode_batch(kind, device, ins, lens, k, C.byref(out), off, ln))
+    try:
+        base = C.addressof(out.contents) if k else 0
+        return [C.string_at(base + off[i], ln[i]) for i in range(k)]
+    finally:
+        lib().bz_free(out)
+
+
 _DECODER_VERDICTS = (BZ_E_DATA, BZ_E_MAGIC_FIRST, BZ_E_MAGIC)
 
 
@@ -980,6 +1013,30 @@ class GpuEngine:
         dict_ = bytes(dict_)
         _check(lib().df_gpu_encode_device_dict(self._h, kind, d_in, n, dict_, len(dict_), d_out, cap, C.byref(out_len)))
         return out_len.value
+
+    DEFLATE_BATCH_STATS = ("inputs_batched", "inputs_one_by_one", "sub_batches", "stored", "fixed", "dynamic", "limited_tables",
+                           "dynamic_without_distances")
+
+    def deflate_encode_batch_device(self, kind, d_in, in_off, in_len, d_out, cap):
+        """Many inputs, one stream each (df_gpu_encode_batch_device): input i is the in_len[i] bytes at d_in + in_off[i]
+        (offsets multiples of 16, in ascending order); returns (out_off, out_len), stream i at d_out + out_off[i]."""
+        _settle()
+        k = len(in_off)
+        if len(in_len) != k:
+            raise ValueError("deflate_encode_batch_device: in_off and in_len differ in length")
+        a_off = (C.c_uint64 * max(k, 1))(*in_off)
+        a_len = (C.c_uint64 * max(k, 1))(*in_len)
+        o_off = (C.c_uint64 * max(k, 1))()
+        o_len = (C.c_uint64 * max(k, 1))()
+        _check(lib().df_gpu_encode_batch_device(self._h, kind, d_in, a_off, a_len, k, d_out, cap, o_off, o_len))
+        return list(o_off[:k]), list(o_len[:k])
+
+    def deflate_batch_stats(self):
+        """The last deflate_encode_batch_device call, in the order of DEFLATE_BATCH_STATS (df_gpu_last_batch_stats);
+        the block counts are those of the batch-path inputs."""
+        s = (C.c_uint64 * 8)()
+        _check(lib().df_gpu_last_batch_stats(self._h, s))
+        return [int(x) for x in s]
 
     def deflate_timings(self):
         t = (C.c_double * 6)()

@@ -23,6 +23,8 @@ using namespace dfgpu;
 struct DfWorkspace {
     DevBuf keys_in, keys_out, vals_in, vals_out, sort_tmp, prevd, est, segoff, concat, bitmap, canon, tabs, ents, bstart, nb, blocks, lens, hdr, lm, total,
         stream, asum, bsum, crc, part_res;
+    DevBuf b_slots, b_tile_slot, b_bse, b_outs, b_stats; // a sub-batch of df_gpu_encode_batch_device: slot tables, block ends, streams' places
+    u64 batch_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // df_gpu_last_batch_stats
     double t_stage[6] = {0, 0, 0, 0, 0, 0}; // chains, matches, parse, blocks, emit, total
     u64 stats[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // blocks, stored, fixed, dynamic, limited tables, stream bytes, dynamic w/o distances
     hipEvent_t ev[7] = {};
@@ -522,6 +524,293 @@ static int df_encode_parts(bz_gpu_engine *g, int kind, const u8 *d_in, u64 n, co
         seg.bit0 = po.end_bits;
         seg.carry_byte = po.end_byte;
     }
+}
+
+// ---- many inputs in one call ----------------------------------------------------------------------------------
+// An input of at most kBlockMax bytes without a dictionary is exactly one block (InflaterInner::next closes a block only when
+// the next code would take it past 0xFFFF bytes, deflate/encoder.rs:577-597): it starts at the input's first byte with
+// decompress_len 0 and is final.  Such inputs are encoded together, a sub-batch at a time: gathered into an image with
+// every input at a multiple of kPTile, one pass of the chain sort, the match kernel (slot rules: k_df_match2<true>), the parse
+// and one block per input; the streams' places come from a scan on the device, the containers are written there too, and the
+// host looks at the device once per sub-batch.  Every other input goes through df_encode_parts, in its turn.
+static u64 df_batch_image_bytes()
+{
+    const char *s = getenv("BZ_DF_BATCH_MIB"); // slot image per sub-batch (a fraction is taken too), read per call
+    double mib = s ? atof(s) : 64.0;
+    if (!(mib >= 1.0 / 16)) mib = 1.0 / 16; // (an input has up to 16 tiles)
+    if (mib > 1024) mib = 1024;
+    return (u64)(mib * 1048576.0);
+}
+constexpr u32 kBatchSlots = 8192; // inputs per sub-batch at most (k_df_block's scratch is 147 KB per block)
+static u32 df_slot_tiles(u64 n) { return n ? (u32)((n + kPTile - 1) / kPTile) : 1u; }
+
+// inputs [first, first + ns) of the call, all of at most kBlockMax bytes, ntiles tiles together; their streams go to
+// d_out + cursor .. in input order, *used = bytes taken there (a multiple of 4)
+static int df_batch_run(bz_gpu_engine *g, int kind, const u8 *d_in, const uint64_t *h_in_off, const uint64_t *h_in_len, size_t first,
+                        u32 ns, u32 ntiles, u8 *d_out, size_t cap, u64 cursor, uint64_t *h_out_off, uint64_t *h_out_len, u64 *used,
+                        double t_acc[6])
+{
+    DfWorkspace *w = g->df;
+    hipStream_t st = g->st;
+    const u64 nimg = (u64)ntiles * kPTile, npad = nimg + 16;
+    std::vector<DfSlot> slots(ns);
+    std::vector<u32> tile_slot(ntiles);
+    std::vector<u64> bse(2 * (size_t)ns);
+    size_t bound = 0;
+    {
+        u32 t = 0;
+        for (u32 j = 0; j < ns; ++j) {
+            const u64 n = h_in_len[first + j];
+            slots[j].src = h_in_off[first + j];
+            slots[j].lo = t * kPTile;
+            slots[j].len = (u32)n;
+            bse[2 * (size_t)j] = slots[j].lo;
+            bse[2 * (size_t)j + 1] = slots[j].lo + n;
+            for (u32 k = df_slot_tiles(n); k; --k) tile_slot[t++] = j;
+            bound += (df_encode_bound((size_t)n) + 3u) & ~(size_t)3;
+        }
+    }
+    int rc;
+    const u64 nchunks = df_chunks(nimg);
+    const u64 nsort = nchunks * kChunkStride + 16;
+    if ((rc = w->concat.ensure(nimg + 64)) != BZ_OK) return rc;                            // the image
+    if ((rc = w->keys_in.ensure(npad * 2)) != BZ_OK) return rc;                            // step[]
+    if ((rc = w->vals_in.ensure((nsort > npad ? nsort : npad) * 4)) != BZ_OK) return rc;   // pass 0 output, later M[]
+    if ((rc = w->vals_out.ensure((nsort > npad ? nsort : npad) * 4)) != BZ_OK) return rc;  // sorted positions, later code[]
+    if ((rc = w->sort_tmp.ensure((nchunks * kChunkTiles + 1) * 256 * 4)) != BZ_OK) return rc;
+    if ((rc = w->keys_out.ensure(2 * (nchunks + 1) * 256 * 4)) != BZ_OK) return rc;
+    if ((rc = w->canon.ensure((size_t)ntiles * 64 * 8 + 64)) != BZ_OK) return rc;
+    if ((rc = w->tabs.ensure((size_t)ntiles * kEntries * 2 + 64)) != BZ_OK) return rc;
+    if ((rc = w->ents.ensure(((size_t)ntiles + 8) * 2 + 64)) != BZ_OK) return rc;
+    if ((rc = w->bitmap.ensure((nimg / 64 + 8) * 8)) != BZ_OK) return rc;
+    if ((rc = w->nb.ensure(64)) != BZ_OK) return rc;
+    if ((rc = w->blocks.ensure((size_t)ns * sizeof(DfBlock))) != BZ_OK) return rc;
+    if ((rc = w->lens.ensure((size_t)ns * 320)) != BZ_OK) return rc;
+    if ((rc = w->hdr.ensure((size_t)ns * kHdrWords * 4)) != BZ_OK) return rc;
+    if ((rc = w->lm.ensure((size_t)ns * kDfLmWords * 4)) != BZ_OK) return rc;
+    if ((rc = w->total.ensure(128)) != BZ_OK) return rc;
+    if ((rc = w->stream.ensure(bound + 64)) != BZ_OK) return rc;
+    if ((rc = w->b_slots.ensure((size_t)ns * sizeof(DfSlot))) != BZ_OK) return rc;
+    if ((rc = w->b_tile_slot.ensure((size_t)ntiles * 4)) != BZ_OK) return rc;
+    if ((rc = w->b_bse.ensure((size_t)ns * 16)) != BZ_OK) return rc;
+    if ((rc = w->b_outs.ensure((size_t)ns * sizeof(DfBatchOut))) != BZ_OK) return rc;
+    if ((rc = w->b_stats.ensure(64)) != BZ_OK) return rc;
+    u8 *image = w->concat.as<u8>();
+    u32 *M = w->vals_in.as<u32>(), *code = w->vals_out.as<u32>();
+    const DfSlot *d_slots = w->b_slots.as<DfSlot>();
+    const u32 *d_tile_slot = w->b_tile_slot.as<u32>();
+    const u64 *d_bse = w->b_bse.as<u64>();
+    const u32 head = kind == 1 ? 2u : (kind == 2 ? 10u : 0u), tail = kind == 1 ? 4u : (kind == 2 ? 8u : 0u);
+    const u32 ns_word = ns;
+    // (the host arrays live on this stack frame: the wait below)
+    HIPCHK(hipMemcpyAsync(w->b_slots.p, slots.data(), (size_t)ns * sizeof(DfSlot), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(w->b_tile_slot.p, tile_slot.data(), (size_t)ntiles * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(w->b_bse.p, bse.data(), (size_t)ns * 16, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(w->nb.p, &ns_word, 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(w->b_stats.p, 0, 64, st));
+    HIPCHK(hipEventRecord(w->ev[0], st));
+    HIPCHK(hipMemsetAsync(w->stream.p, 0, bound + 64, st));
+    if (df_launch_gather(st, d_in, d_slots, d_tile_slot, ntiles, image) != 0) return BZ_E_UNEXPECTED;
+    if (df_launch_chains(st, image, nimg, w->vals_in.as<u32>(), w->vals_out.as<u32>(), nullptr, w->sort_tmp.as<u32>(), w->keys_out.as<u32>(),
+                         nullptr) != 0)
+        return BZ_E_UNEXPECTED;
+    HIPCHK(hipEventRecord(w->ev[1], st));
+    if (df_launch_match2_batch(st, image, nimg, w->vals_out.as<u32>(), M, d_tile_slot, d_slots) != 0) return BZ_E_UNEXPECTED;
+    HIPCHK(hipEventRecord(w->ev[2], st));
+    if (df_launch_parse_batch(st, M, nimg, ntiles, d_slots, ns, w->keys_in.as<u16>(), w->tabs.as<u16>(), w->ents.as<u16>(), code,
+                              w->bitmap.as<u64>(), w->canon.as<u64>()) != 0)
+        return BZ_E_UNEXPECTED;
+    HIPCHK(hipEventRecord(w->ev[3], st));
+    if (df_launch_blocks_batch(st, image, code, d_bse, w->nb.as<u32>(), ns, w->blocks.as<DfBlock>(), w->lens.as<u8>(), w->hdr.as<u32>(),
+                               w->lm.as<u32>()) != 0)
+        return BZ_E_UNEXPECTED;
+    if (df_launch_batch_offsets(st, w->blocks.as<DfBlock>(), ns, head, tail, w->b_outs.as<DfBatchOut>(), w->total.as<u64>()) != 0)
+        return BZ_E_UNEXPECTED;
+    HIPCHK(hipEventRecord(w->ev[4], st));
+    if (df_launch_emit_batch(st, image, code, d_bse, w->nb.as<u32>(), ns, w->blocks.as<DfBlock>(), w->lens.as<u8>(), w->hdr.as<u32>(),
+                             w->stream.as<u32>()) != 0)
+        return BZ_E_UNEXPECTED;
+    DfCrcShifts xk;
+    for (u32 k = 0; k < 8; ++k) xk.x[k] = gf_xpow8_reflected(256ull << k);
+    if (df_launch_batch_wrap(st, image, d_slots, ns, w->blocks.as<DfBlock>(), w->b_outs.as<DfBatchOut>(), kind, xk, w->stream.as<u8>(),
+                             w->b_stats.as<u32>()) != 0)
+        return BZ_E_UNEXPECTED;
+    HIPCHK(hipEventRecord(w->ev[5], st));
+    std::vector<DfBatchOut> outs(ns);
+    u64 total = 0;
+    u32 bst[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(outs.data(), w->b_outs.p, (size_t)ns * sizeof(DfBatchOut), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&total, w->total.p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(bst, w->b_stats.p, 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st)); // the one look at the device per sub-batch
+    HIPCHK(hipGetLastError());
+    if (total > bound) return BZ_E_UNEXPECTED;
+    if (cursor + total > cap) return BZ_E_CAPACITY;
+    if (total) HIPCHK(hipMemcpyAsync(d_out + cursor, w->stream.p, (size_t)total, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipEventRecord(w->ev[6], st));
+    for (u32 j = 0; j < ns; ++j) {
+        h_out_off[first + j] = cursor + outs[j].off;
+        h_out_len[first + j] = outs[j].len;
+    }
+    for (int i = 0; i < 5; ++i) w->batch_stats[3 + i] += bst[i];
+    HIPCHK(hipStreamSynchronize(st)); // (the workspace is free for the next sub-batch, the events are over)
+    for (int i = 0; i < 5; ++i) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, w->ev[i], w->ev[i + 1]);
+        t_acc[i] += ms * 1e-3;
+    }
+    {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, w->ev[0], w->ev[6]);
+        t_acc[5] += ms * 1e-3;
+    }
+    *used = total;
+    return BZ_OK;
+}
+
+extern "C" size_t df_encode_batch_bound(const uint64_t *in_len, size_t count)
+{
+    size_t s = 0;
+    for (size_t i = 0; in_len && i < count; ++i) s += (df_encode_bound((size_t)in_len[i]) + 3u) & ~(size_t)3;
+    return s;
+}
+
+extern "C" int df_gpu_last_batch_stats(bz_gpu_engine *g, uint64_t out[8])
+{
+    if (!g || !out) return BZ_E_PARAM;
+    for (int i = 0; i < 8; ++i) out[i] = g->df ? g->df->batch_stats[i] : 0;
+    return BZ_OK;
+}
+
+extern "C" int df_gpu_encode_batch_device(bz_gpu_engine *g, int kind, const void *d_in, const uint64_t *h_in_off,
+                                          const uint64_t *h_in_len, size_t count, void *d_out, size_t cap, uint64_t *h_out_off,
+                                          uint64_t *h_out_len)
+{
+    if (!g || kind < 0 || kind > 2) return BZ_E_PARAM;
+    if (count == 0) return BZ_OK;
+    if (!h_in_off || !h_in_len || !h_out_off || !h_out_len || !d_out) return BZ_E_PARAM;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 3u)) return BZ_E_PARAM;
+    u64 in_end = 0;
+    for (size_t i = 0; i < count; ++i) {
+        if ((h_in_off[i] & 15u) || h_in_off[i] < in_end || h_in_off[i] + h_in_len[i] < h_in_off[i]) return BZ_E_PARAM;
+        in_end = h_in_off[i] + h_in_len[i];
+    }
+    if (in_end && !d_in) return BZ_E_PARAM;
+    HIPCHK(hipSetDevice(g->device));
+    if (!g->df) g->df = new DfWorkspace();
+    DfWorkspace *w = g->df;
+    if (!w->ev_ready) {
+        for (hipEvent_t &e : w->ev) HIPCHK(hipEventCreate(&e));
+        for (hipEvent_t &e : w->evq) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        w->ev_ready = true;
+    }
+    for (u64 &s : w->batch_stats) s = 0;
+    const u8 *in8 = static_cast<const u8 *>(d_in);
+    u8 *out8 = static_cast<u8 *>(d_out);
+    const u64 image_max = df_batch_image_bytes();
+    double t_acc[6] = {0, 0, 0, 0, 0, 0};
+    u64 cursor = 0;
+    bool batched = false;
+    for (size_t i = 0; i < count;) {
+        if (h_in_len[i] > kBlockMax) { // more than one block: the one-input path, in its place
+            size_t got = 0;
+            if (cursor > cap) return BZ_E_CAPACITY;
+            const int rc = df_encode_parts(g, kind, in8 + h_in_off[i], h_in_len[i], nullptr, 0, out8 + cursor, cap - cursor, &got);
+            if (rc != BZ_OK) return rc;
+            const u64 slot = ((u64)got + 3u) & ~(u64)3;
+            if (cursor + slot > cap) return BZ_E_CAPACITY;
+            if (slot > got) HIPCHK(hipMemsetAsync(out8 + cursor + got, 0, (size_t)(slot - got), g->st));
+            h_out_off[i] = cursor;
+            h_out_len[i] = got;
+            cursor += slot;
+            w->batch_stats[1] += 1;
+            ++i;
+            continue;
+        }
+        size_t j = i;
+        u64 tiles = 0;
+        while (j < count && h_in_len[j] <= kBlockMax && j - i < kBatchSlots &&
+               (j == i || (tiles + df_slot_tiles(h_in_len[j])) * kPTile <= image_max)) {
+            tiles += df_slot_tiles(h_in_len[j]);
+            ++j;
+        }
+        u64 used = 0;
+        const int rc = df_batch_run(g, kind, in8, h_in_off, h_in_len, i, (u32)(j - i), (u32)tiles, out8, cap, cursor, h_out_off, h_out_len,
+                                    &used, t_acc);
+        if (rc != BZ_OK) return rc;
+        cursor += used;
+        w->batch_stats[0] += j - i;
+        w->batch_stats[2] += 1;
+        batched = true;
+        i = j;
+    }
+    HIPCHK(hipStreamSynchronize(g->st));
+    if (batched) { // df_gpu_last_timings: the stages of the batch path, summed over the sub-batches
+        for (int k = 0; k < 6; ++k) w->t_stage[k] = t_acc[k];
+        w->h_nb = 0; // (df_gpu_debug_blocks describes one-stream calls)
+        w->h_fetched = true;
+        w->h_blocks.clear();
+        w->h_bstart.assign(1, 0);
+    }
+    return BZ_OK;
+}
+
+// The host form (mirrors bz_encode_batch): the inputs packed at 16-byte-aligned offsets, one upload, one device call on an
+// engine of the Deflate cache, one download.
+extern "C" int df_encode_batch(int kind, int device, const uint8_t *const *ins, const size_t *lens, size_t count, uint8_t **out,
+                               uint64_t *out_off, uint64_t *out_len)
+{
+    if (!out) return BZ_E_PARAM;
+    *out = nullptr;
+    if (kind < 0 || kind > 2) return BZ_E_PARAM;
+    if (count && (!ins || !lens || !out_off || !out_len)) return BZ_E_PARAM;
+    for (size_t i = 0; i < count; ++i)
+        if (lens[i] && !ins[i]) return BZ_E_PARAM;
+    if (count == 0) {
+        *out = (uint8_t *)malloc(1);
+        return *out ? BZ_OK : BZ_E_NOMEM;
+    }
+    std::vector<uint64_t> in_off(count), in_len(count);
+    u64 total_in = 0;
+    for (size_t i = 0; i < count; ++i) {
+        in_off[i] = total_in;
+        in_len[i] = lens[i];
+        total_in += ((u64)lens[i] + 15u) & ~(u64)15;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return BZ_E_NOGPU;
+    int caller_device = -1;
+    (void)hipGetDevice(&caller_device);
+    bz_gpu_engine *g = dec_cache_take(device, 2);
+    int rc = g ? BZ_OK : bz_gpu_engine_create(&g, device, 1);
+    if (rc != BZ_OK) return rc;
+    const size_t cap = df_encode_batch_bound(in_len.data(), count);
+    uint8_t *h = nullptr;
+    std::vector<uint8_t> packed((size_t)total_in + 16);
+    for (size_t i = 0; i < count; ++i)
+        if (lens[i]) memcpy(packed.data() + in_off[i], ins[i], lens[i]);
+    rc = hipSetDevice(device) == hipSuccess ? BZ_OK : BZ_E_UNEXPECTED;
+    if (rc == BZ_OK) rc = g->dec_in.ensure((size_t)total_in + 64);
+    if (rc == BZ_OK) rc = g->oneshot_out.ensure(cap + 64);
+    if (rc == BZ_OK && total_in && hipMemcpy(g->dec_in.p, packed.data(), (size_t)total_in, hipMemcpyHostToDevice) != hipSuccess)
+        rc = BZ_E_UNEXPECTED;
+    if (rc == BZ_OK) rc = df_gpu_encode_batch_device(g, kind, g->dec_in.p, in_off.data(), in_len.data(), count, g->oneshot_out.p, cap, out_off, out_len);
+    if (rc == BZ_OK) {
+        const size_t total_out = (size_t)(out_off[count - 1] + ((out_len[count - 1] + 3u) & ~(u64)3));
+        h = (uint8_t *)malloc(total_out ? total_out : 1);
+        if (!h) rc = BZ_E_NOMEM;
+        else if (hipMemcpy(h, g->oneshot_out.p, total_out, hipMemcpyDeviceToHost) != hipSuccess) {
+            free(h);
+            h = nullptr;
+            rc = BZ_E_UNEXPECTED;
+        }
+    }
+    if (rc == BZ_OK) dec_cache_put(device, g);
+    else bz_gpu_engine_destroy(g); // (an engine that met an error is not kept)
+    if (caller_device >= 0) (void)hipSetDevice(caller_device);
+    if (rc != BZ_OK) return rc;
+    *out = h;
+    return BZ_OK;
 }
 
 // ---- C ABI ------------------------------------------------------------------------------------------------

@@ -26,6 +26,9 @@
 //     symbol counts: k_df_block replays make_table (huffman/cano_huff_table.rs, the serial heap
 //     procedure -- in the registers of a wave -- and the package-merge fallback) and the code-length run
 //     coding (:318-452) exactly; k_df_emit writes the bits LSB first (bitio/writer.rs, Right).
+//   * Many inputs of at most 0xFFFF bytes each (one block for certain) share one pass: an image with every input in
+//     a slot of whole parse tiles, k_df_match2<true> / k_df_block<true> / k_df_emit<true> and the kernels at the end of
+//     this file (DESIGN_deflate.md, "Many inputs in one call").
 #include <cstdlib>
 #include <cstring>
 
@@ -508,8 +511,15 @@ __device__ __forceinline__ u32 df_diff16(df_u32x4 x, df_u32x4 y)
     return r < r2 ? r : r2;
 }
 
+// BATCH (df_gpu_encode_batch_device): the text is an image of many inputs, each in a slot of whole parse tiles.  An entry's
+// candidates are those of its own input: the run in front of it has descending positions, so the first candidate in
+// front of the slot's start ends the chain like the start of the chunk does (the window and the 255 candidates then
+// count own candidates only); the text ends at the input's end; positions without a trigram inside their input (its
+// last two bytes, the gap behind it) have no candidates at all and get "no match".
+template <bool BATCH>
 __global__ __launch_bounds__(kM2Threads) void k_df_match2(const u8 *__restrict__ in, u64 n, u64 ntri, const u32 *__restrict__ S,
-                                                          u32 *__restrict__ M)
+                                                          u32 *__restrict__ M, const u32 *__restrict__ tile_slot,
+                                                          const DfSlot *__restrict__ slots)
 {
     typedef df_u32x4 u32x4;
     __shared__ u32x4 s_snip[kM2Hist + kM2Threads];
@@ -559,21 +569,28 @@ __global__ __launch_bounds__(kM2Threads) void k_df_match2(const u8 *__restrict__
     const u32 p = s_pos[li], h = s_key[li];
     const u32x4 a = s_snip[li];
     const bool own = i0 + tid < count && (u64)p >= (u64)c * kChunk; // a history entry is written by the chunk that owns it
+    u32 slo = 0, tend = n32; // BATCH: the entry's input is image[slo, tend)
+    if (BATCH) {
+        const DfSlot sl = slots[tile_slot[p / kPTile]];
+        slo = sl.lo;
+        tend = sl.lo + sl.len;
+    }
+    const bool live = BATCH ? (own && p + kMinMatch <= tend) : own; // (its trigram lies inside its input)
     // chain length: the entries in front with the same hash and within the window form one run (monotone in j)
     u32 e = 0;
-    if (own && s_key[li - 1] == h && p - s_pos[li - 1] <= kWin) {
+    if (live && s_key[li - 1] == h && p - s_pos[li - 1] <= kWin && (!BATCH || s_pos[li - 1] >= slo)) {
         u32 lo = li - kChain, hi = li - 1;
         while (lo < hi) {
             const u32 mid = (lo + hi) >> 1;
-            if (s_key[mid] == h && s_pos[mid] + kWin >= p) hi = mid; else lo = mid + 1;
+            if (s_key[mid] == h && s_pos[mid] + kWin >= p && (!BATCH || s_pos[mid] >= slo)) hi = mid; else lo = mid + 1;
         }
         e = li - lo;
     }
     // Where the chain ends because the entries in front have another hash, running on does no harm (another hash is
     // another trigram: fewer than three bytes agree, which never beats "no match"); only a chain cut by the window, by
     // the 255 candidates or by the start of the chunk's entries has to be masked.  em: the step a lane is masked from.
-    const u32 em = (own && !(s_key[li - e - 1] != 0xFFFFFFFFu && s_key[li - e - 1] != h)) ? e : 0xFFFFFFFFu;
-    const u32 limit = (n32 - p) < kMaxMatch ? n32 - p : kMaxMatch; // search_dic :228
+    const u32 em = (live && !(s_key[li - e - 1] != 0xFFFFFFFFu && s_key[li - e - 1] != h)) ? e : 0xFFFFFFFFu;
+    const u32 limit = (BATCH && !live) ? 0u : ((tend - p) < kMaxMatch ? tend - p : kMaxMatch); // search_dic :228
     // A step gives r = first differing bit of the 16 bytes, at most `cap` (the limit where it lies inside them, else
     // 128: "all 16 agree, the rest is to be measured").  What a lane keeps is the greatest key
     //     (r | 7) << 24 | (255 - k) << 16
@@ -717,7 +734,7 @@ __global__ __launch_bounds__(kM2Threads) void k_df_match2(const u8 *__restrict__
     if (own) {
         u32 best_len = best >> 27, best_k = 255u - ((best >> 16) & 0xFFu);
         if (mkey) { best_len = mkey >> 8; best_k = 255u - (mkey & 0xFFu); }
-        M[p] = best_len >= kMinMatch ? (best_len | ((p - s_pos[li - best_k] - 1) << 9)) : 0u;
+        M[p] = (live && best_len >= kMinMatch) ? (best_len | ((p - s_pos[li - best_k] - 1) << 9)) : 0u;
     }
 }
 
@@ -1443,6 +1460,8 @@ __device__ __forceinline__ u32 df_tab_runs(const u8 *tab, u32 n, u8 *ls, u8 *le,
 }
 
 // one workgroup per Deflate block: symbol counts, the three tables, the header, the choice of block type
+// BATCH: block k is bstart[2k] .. bstart[2k + 1] (slot k of the image) and the final block of a stream of its own
+template <bool BATCH>
 __global__ __launch_bounds__(kBThreads) void k_df_block(const u8 *__restrict__ in, const u32 *__restrict__ code,
                                                         const u64 *__restrict__ bstart, const u32 *__restrict__ nb_p,
                                                         DfBlock *__restrict__ blocks, u8 *__restrict__ lens,
@@ -1473,8 +1492,8 @@ __global__ __launch_bounds__(kBThreads) void k_df_block(const u8 *__restrict__ i
         nblocks = *nb_p;
         if (nblocks == 0xFFFFFFFFu || k >= nblocks) return;
     }
-    const u64 b0 = bstart[k], b1 = bstart[k + 1];
-    const bool is_final = (k + 1 == nblocks) && last_is_final; // (a flushed segment ends with a non-final block)
+    const u64 b0 = BATCH ? bstart[2 * (size_t)k] : bstart[k], b1 = BATCH ? bstart[2 * (size_t)k + 1] : bstart[k + 1];
+    const bool is_final = BATCH ? last_is_final != 0 : ((k + 1 == nblocks) && last_is_final); // (a flushed segment ends with a non-final block)
     for (u32 i = tid; i < 288; i += kBThreads) s_sf[i] = 0;
     if (tid < 32) s_of[tid] = 0;
     if (tid == 0) s_lm = 0;
@@ -1590,7 +1609,7 @@ __global__ __launch_bounds__(kBThreads) void k_df_block(const u8 *__restrict__ i
         }
         // decompress_len: the bytes of this block's codes -- and, for the first block of a segment behind a
         // flush, the dl0 bytes the counter still holds (a stored block then repeats them, :488-501)
-        const u64 dlen = b1 - b0 + (k == 0 ? dl0 : 0u);
+        const u64 dlen = b1 - b0 + ((!BATCH && k == 0) ? dl0 : 0u);
         const u64 original = (dlen << 3) + 2 + 16 + 16;
         DfBlock o;
         o.bytes = (u32)dlen;
@@ -1684,6 +1703,7 @@ __device__ __forceinline__ void or_bits(u32 *out, u64 bit, u64 v, u32 nbits)
     if (hi) atomicOr(&out[w + 2], hi);
 }
 
+template <bool BATCH> // (BATCH: block k is bstart[2k] .. bstart[2k + 1], as in k_df_block)
 __global__ __launch_bounds__(kEThreads) void k_df_emit(const u8 *__restrict__ in, const u32 *__restrict__ code,
                                                        const u64 *__restrict__ bstart, const u32 *__restrict__ nb_p,
                                                        const DfBlock *__restrict__ blocks, const u8 *__restrict__ lens,
@@ -1697,7 +1717,7 @@ __global__ __launch_bounds__(kEThreads) void k_df_emit(const u8 *__restrict__ in
     const u32 nblocks = *nb_p;
     if (nblocks == 0xFFFFFFFFu || k >= nblocks) return;
     const DfBlock bi = blocks[k];
-    const u64 b0 = bstart[k], b1 = bstart[k + 1];
+    const u64 b0 = BATCH ? bstart[2 * (size_t)k] : bstart[k], b1 = BATCH ? bstart[2 * (size_t)k + 1] : bstart[k + 1];
     u8 *out8 = reinterpret_cast<u8 *>(out);
     if (bi.btype == 0) {
         if (tid == 0) or_bits(out, bi.bit_off, hdr[(size_t)k * kHdrWords] & 7u, 3);
@@ -1908,7 +1928,18 @@ int df_launch_match2(hipStream_t st, const u8 *in, u64 n, const u32 *s, u32 *M)
     const u64 ntri = n >= 3 ? n - 2 : 0;
     DFCHK(hipMemsetAsync(M + ntri, 0, (n - ntri + 8) * sizeof(u32), st)); // the last two positions have no trigram
     if (!ntri) return 0;
-    hipLaunchKernelGGL(k_df_match2, dim3(df_chunks(n) * kM2Span), dim3(kM2Threads), 0, st, in, n, ntri, s, M);
+    hipLaunchKernelGGL((k_df_match2<false>), dim3(df_chunks(n) * kM2Span), dim3(kM2Threads), 0, st, in, n, ntri, s, M, (const u32 *)nullptr,
+                       (const DfSlot *)nullptr);
+    return 0;
+}
+
+int df_launch_match2_batch(hipStream_t st, const u8 *image, u64 n, const u32 *s, u32 *M, const u32 *tile_slot, const DfSlot *slots)
+{
+    if (!n) return 0;
+    const u64 ntri = n >= 3 ? n - 2 : 0;
+    DFCHK(hipMemsetAsync(M + ntri, 0, (n - ntri + 8) * sizeof(u32), st));
+    if (!ntri) return 0;
+    hipLaunchKernelGGL((k_df_match2<true>), dim3(df_chunks(n) * kM2Span), dim3(kM2Threads), 0, st, image, n, ntri, s, M, tile_slot, slots);
     return 0;
 }
 
@@ -1973,7 +2004,7 @@ u32 df_cut_pieces(u32 ntiles) { return ntiles < kCutPieces * 64 ? 1u : kCutPiece
 int df_launch_blocks_piece(hipStream_t st, const u8 *in, const u32 *code, u64 *bstart, u32 *nb, u32 cap, DfBlock *blocks, u8 *lens,
                            u32 *hdr, u32 *lm_scratch, u32 dl0, u32 last_is_final, const u32 *kr, u32 piece_last)
 {
-    hipLaunchKernelGGL(k_df_block, dim3(cap), dim3(kBThreads), 0, st, in, code, bstart, nb, blocks, lens, hdr, lm_scratch, dl0,
+    hipLaunchKernelGGL((k_df_block<false>), dim3(cap), dim3(kBThreads), 0, st, in, code, bstart, nb, blocks, lens, hdr, lm_scratch, dl0,
                        last_is_final, kr, piece_last);
     return 0;
 }
@@ -1986,7 +2017,7 @@ int df_launch_block_offsets(hipStream_t st, DfBlock *blocks, const u32 *nb, u64 
 int df_launch_blocks(hipStream_t st, const u8 *in, const u32 *code, u64 *bstart, u32 *nb, u32 cap,
                      DfBlock *blocks, u8 *lens, u32 *hdr, u32 *lm_scratch, u64 *total_bits, u32 dl0, u32 last_is_final, u32 bit0)
 {
-    hipLaunchKernelGGL(k_df_block, dim3(cap), dim3(kBThreads), 0, st, in, code, bstart, nb, blocks, lens, hdr, lm_scratch, dl0,
+    hipLaunchKernelGGL((k_df_block<false>), dim3(cap), dim3(kBThreads), 0, st, in, code, bstart, nb, blocks, lens, hdr, lm_scratch, dl0,
                        last_is_final, (const u32 *)nullptr, 1u);
     hipLaunchKernelGGL(k_df_offsets, dim3(1), dim3(256), 0, st, blocks, nb, total_bits, bit0);
     return 0;
@@ -1995,7 +2026,7 @@ int df_launch_blocks(hipStream_t st, const u8 *in, const u32 *code, u64 *bstart,
 int df_launch_emit(hipStream_t st, const u8 *in, const u32 *code, const u64 *bstart, const u32 *nb, u32 cap,
                    const DfBlock *blocks, const u8 *lens, const u32 *hdr, u32 *out)
 {
-    hipLaunchKernelGGL(k_df_emit, dim3(cap), dim3(kEThreads), 0, st, in, code, bstart, nb, blocks, lens, hdr, out);
+    hipLaunchKernelGGL((k_df_emit<false>), dim3(cap), dim3(kEThreads), 0, st, in, code, bstart, nb, blocks, lens, hdr, out);
     return 0;
 }
 
@@ -2085,6 +2116,224 @@ int df_launch_part_keep(hipStream_t st, const u64 *bstart, u32 *nb, u32 bcap, co
 int df_launch_part_tail(hipStream_t st, const DfBlock *blocks, const u64 *bstart, const u32 *nb, const u64 *total_bits, const u8 *stream, DfPartRes *res)
 {
     hipLaunchKernelGGL(k_df_part_tail, dim3(1), dim3(256), 0, st, blocks, bstart, nb, total_bits, stream, res);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------- many inputs in one pass
+// (df_gpu_encode_batch_device, deflate_engine.hip)  The stages above run once over an image of all inputs of a sub-batch:
+// the chunk sort as it is (its order is (hash, position), whoever owns the position), k_df_match2<true> with the
+// slot rules, k_df_adv / k_df_tile_orbit / k_df_mark2 as they are (a gap holds "no match", so no step crosses an input's
+// end and a slot is entered at offset 0 of its first tile), k_df_block<true> / k_df_emit<true> with one block per slot.
+
+// one workgroup per tile of the image, 16 bytes per thread: the input's bytes, zeros behind its end
+__global__ __launch_bounds__(256) void k_df_gather(const u8 *__restrict__ d_in, const DfSlot *__restrict__ slots,
+                                                   const u32 *__restrict__ tile_slot, u8 *__restrict__ image)
+{
+    const u32 tile = blockIdx.x;
+    const DfSlot sl = slots[tile_slot[tile]];
+    const u32 off = tile * kPTile - sl.lo + threadIdx.x * 16u; // offset inside the input
+    u8 *dst = image + (size_t)tile * kPTile + threadIdx.x * 16u;
+    df_u32x4 v = {0, 0, 0, 0};
+    if (off + 16u <= sl.len) v = *reinterpret_cast<const df_u32x4 *>(d_in + sl.src + off); // (src is a multiple of 16)
+    *reinterpret_cast<df_u32x4 *>(dst) = v;
+    if (off < sl.len && off + 16u > sl.len) // the input ends inside these 16 bytes: nothing behind its end is read
+        for (u32 b = 0; off + b < sl.len; ++b) dst[b] = d_in[sl.src + off + b];
+}
+
+// entry offset of every tile of a slot: 0 for the first one, the exit of tile t for tile t + 1 (k_df_compose /
+// k_df_resolve of the one-stream path; a slot has at most 16 tiles)
+__global__ __launch_bounds__(64) void k_df_slot_entries(const DfSlot *__restrict__ slots, u32 nslots, const u16 *__restrict__ tab,
+                                                        u16 *__restrict__ ent)
+{
+    const u32 j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= nslots) return;
+    const DfSlot sl = slots[j];
+    const u32 t0 = sl.lo / kPTile, nt = sl.len ? (sl.len + kPTile - 1) / kPTile : 1u;
+    u32 v = 0;
+    for (u32 t = 0; t < nt; ++t) {
+        ent[t0 + t] = (u16)v;
+        v = tab[(size_t)(t0 + t) * kEntries + v];
+        if (v >= kEntries) v = 0; // (a step is at most 260 positions long: cannot happen)
+    }
+}
+
+// bytes of a stream: container header, the block (a stored block: 3 bits, padding, LEN, NLEN, the bytes), trailer
+__device__ __forceinline__ u32 df_stream_bytes(const DfBlock &b, u32 head, u32 tail)
+{
+    const u32 body = b.btype == 0 ? 5u + b.bytes : (u32)((b.bits + 7) >> 3);
+    return head + body + tail;
+}
+
+__global__ __launch_bounds__(256) void k_df_batch_offsets(DfBlock *__restrict__ blocks, u32 nslots, u32 head, u32 tail,
+                                                          DfBatchOut *__restrict__ outs, u64 *__restrict__ total)
+{
+    __shared__ u64 s_sum[256];
+    const u32 tid = threadIdx.x;
+    const u32 per = (nslots + 255u) / 256u, j0 = tid * per, j1 = (j0 + per < nslots) ? j0 + per : nslots;
+    u64 sum = 0;
+    for (u32 j = j0; j < j1; ++j) sum += (df_stream_bytes(blocks[j], head, tail) + 3u) & ~3u;
+    s_sum[tid] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        u64 run = 0;
+        for (u32 t = 0; t < 256; ++t) { const u64 v = s_sum[t]; s_sum[t] = run; run += v; }
+        *total = run;
+    }
+    __syncthreads();
+    u64 off = s_sum[tid];
+    for (u32 j = j0; j < j1; ++j) {
+        const u32 len = df_stream_bytes(blocks[j], head, tail);
+        outs[j].off = (u32)off;
+        outs[j].len = len;
+        blocks[j].bit_off = (off + head) * 8u;
+        off += (len + 3u) & ~3u;
+    }
+}
+
+__device__ __forceinline__ u32 df_gf_mul(u32 a, u32 b) // a * b in GF(2)[x] / P, reflected (bit 31 = x^0)
+{
+    u32 pr = 0;
+    for (u32 m = 1u << 31; m != 0 && a != 0; m >>= 1) {
+        if (a & m) { pr ^= b; a &= ~m; }
+        b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
+    }
+    return pr;
+}
+__device__ __forceinline__ u32 df_gf_xpow8(u32 nbytes) // x^(8 * nbytes) mod P
+{
+    u32 r = 1u << 31, sq = 1u << 23;
+    while (nbytes) {
+        if (nbytes & 1u) r = df_gf_mul(r, sq);
+        sq = df_gf_mul(sq, sq);
+        nbytes >>= 1;
+    }
+    return r;
+}
+
+// one workgroup per stream: the container around its block (zlib/encoder.rs:63-72,118-156; gzip/encoder.rs:62-75,88-134).
+// The input's full 256-byte pieces go to the LAST threads (piece j of m to thread 256 - m + j), so that the fold of
+// k_df_sums applies whatever m is: the threads in front hold a zero register, which stays zero; thread 0 (an input has
+// at most 255 full pieces) takes the bytes behind the last full piece.
+__global__ __launch_bounds__(256) void k_df_batch_wrap(const u8 *__restrict__ image, const DfSlot *__restrict__ slots,
+                                                       const DfBlock *__restrict__ blocks, const DfBatchOut *__restrict__ outs,
+                                                       int kind, DfCrcShifts xk, u8 *__restrict__ out, u32 *__restrict__ stats)
+{
+    __shared__ u32 s_tab[256];
+    __shared__ u64 s_a[256], s_b[256];
+    __shared__ u32 s_c[256];
+    __shared__ u32 s_tail;
+    const u32 tid = threadIdx.x, j = blockIdx.x;
+    const DfSlot sl = slots[j];
+    const DfBatchOut o = outs[j];
+    if (tid == 0) {
+        const DfBlock b = blocks[j];
+        atomicAdd(&stats[b.btype < 3u ? b.btype : 0u], 1u);
+        if (b.lm & 0xFFu) atomicAdd(&stats[3], b.lm & 0xFFu);
+        if ((b.lm >> 8) & 1u) atomicAdd(&stats[4], 1u);
+    }
+    if (kind == 0) return;
+    {
+        u32 c = tid;
+        for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
+        s_tab[tid] = c;
+    }
+    __syncthreads();
+    const u32 len = sl.len, mfull = len >> 8, rest = len & 255u;
+    const u8 *src = image + sl.lo;
+    u64 a = 0, b = 0;
+    u32 c = 0;
+    if (tid >= 256u - mfull) {
+        const u32 i0 = (tid - (256u - mfull)) << 8;
+        for (u32 q = 0; q < 16; ++q) {
+            const df_u32x4 v = *reinterpret_cast<const df_u32x4 *>(src + i0 + q * 16u); // (slots start at multiples of 4096)
+            const u32 w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (u32 k = 0; k < 16; ++k) {
+                const u32 d = (w[k >> 2] >> (8 * (k & 3u))) & 0xFFu;
+                a += d;
+                b += (u64)(len - (i0 + q * 16u + k)) * d;
+                c = s_tab[(c ^ d) & 0xFFu] ^ (c >> 8);
+            }
+        }
+    } else if (tid == 0) {
+        for (u32 i = len - rest; i < len; ++i) {
+            const u32 d = src[i];
+            a += d;
+            b += (u64)(len - i) * d;
+            c = s_tab[(c ^ d) & 0xFFu] ^ (c >> 8);
+        }
+        s_tail = c;
+        c = 0; // (its place in the fold is a piece in front of the input)
+    }
+    s_a[tid] = a; s_b[tid] = b; s_c[tid] = c;
+    __syncthreads();
+    for (u32 lv = 0; lv < 8; ++lv) {
+        const u32 stride = 1u << lv;
+        if ((tid & (2 * stride - 1)) == 0) s_c[tid] = df_gf_mul(s_c[tid], xk.x[lv]) ^ s_c[tid + stride];
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    u8 *p = out + o.off;
+    if (kind == 1) {
+        u64 sa = 0, sb = 0;
+        for (u32 t = 0; t < 256; ++t) { sa += s_a[t]; sb += s_b[t]; }
+        const u32 A = (u32)((1 + sa) % 65521), B = (u32)((len + sb) % 65521); // adler32.rs:20-66 from (1, 0)
+        const u32 h = (B << 16) | A;
+        p[0] = 0x78; p[1] = 0xDA;
+        u8 *t = p + o.len - 4;
+        t[0] = (u8)(h >> 24); t[1] = (u8)(h >> 16); t[2] = (u8)(h >> 8); t[3] = (u8)h;
+    } else {
+        const u32 raw = df_gf_mul(s_c[0], df_gf_xpow8(rest)) ^ s_tail; // register for a zero initial value
+        const u32 crc = raw ^ df_gf_mul(0xFFFFFFFFu, df_gf_xpow8(len)) ^ 0xFFFFFFFFu;
+        p[0] = 0x1F; p[1] = 0x8B; p[2] = 0x08; p[3] = 0; p[4] = 0; p[5] = 0; p[6] = 0; p[7] = 0; p[8] = 0; p[9] = 0xFF;
+        u8 *t = p + o.len - 8;
+        for (u32 i = 0; i < 4; ++i) { t[i] = (u8)(crc >> (8 * i)); t[4 + i] = (u8)(len >> (8 * i)); }
+    }
+}
+
+int df_launch_gather(hipStream_t st, const u8 *d_in, const DfSlot *slots, const u32 *tile_slot, u32 ntiles, u8 *image)
+{
+    hipLaunchKernelGGL(k_df_gather, dim3(ntiles), dim3(256), 0, st, d_in, slots, tile_slot, image);
+    DFCHK(hipMemsetAsync(image + (size_t)ntiles * kPTile, 0, 64, st));
+    return 0;
+}
+
+int df_launch_parse_batch(hipStream_t st, const u32 *M, u64 n, u32 ntiles, const DfSlot *slots, u32 nslots, u16 *step, u16 *tab,
+                          u16 *ent, u32 *code, u64 *bm, u64 *canon)
+{
+    DFCHK(hipMemsetAsync(bm, 0, ((n + 63) / 64 + 2) * sizeof(u64), st));
+    hipLaunchKernelGGL(k_df_adv, dim3((u32)((n + 1023) / 1024)), dim3(256), 0, st, M, n, step);
+    hipLaunchKernelGGL(k_df_tile_orbit, dim3(ntiles), dim3(kOrbThreads), 0, st, step, n, tab, canon);
+    hipLaunchKernelGGL(k_df_slot_entries, dim3((nslots + 63) / 64), dim3(64), 0, st, slots, nslots, tab, ent);
+    hipLaunchKernelGGL(k_df_mark2, dim3(ntiles), dim3(kMark2Threads), 0, st, step, M, ent, tab, canon, n, code, bm, 0u);
+    return 0;
+}
+
+int df_launch_blocks_batch(hipStream_t st, const u8 *image, const u32 *code, const u64 *bse, const u32 *nb, u32 nslots, DfBlock *blocks,
+                           u8 *lens, u32 *hdr, u32 *lm_scratch)
+{
+    hipLaunchKernelGGL((k_df_block<true>), dim3(nslots), dim3(kBThreads), 0, st, image, code, bse, nb, blocks, lens, hdr, lm_scratch, 0u, 1u,
+                       (const u32 *)nullptr, 1u);
+    return 0;
+}
+
+int df_launch_batch_offsets(hipStream_t st, DfBlock *blocks, u32 nslots, u32 head, u32 tail, DfBatchOut *outs, u64 *total)
+{
+    hipLaunchKernelGGL(k_df_batch_offsets, dim3(1), dim3(256), 0, st, blocks, nslots, head, tail, outs, total);
+    return 0;
+}
+
+int df_launch_emit_batch(hipStream_t st, const u8 *image, const u32 *code, const u64 *bse, const u32 *nb, u32 nslots, const DfBlock *blocks,
+                         const u8 *lens, const u32 *hdr, u32 *out)
+{
+    hipLaunchKernelGGL((k_df_emit<true>), dim3(nslots), dim3(kEThreads), 0, st, image, code, bse, nb, blocks, lens, hdr, out);
+    return 0;
+}
+
+int df_launch_batch_wrap(hipStream_t st, const u8 *image, const DfSlot *slots, u32 nslots, const DfBlock *blocks, const DfBatchOut *outs,
+                         int kind, DfCrcShifts xk, u8 *out, u32 *stats)
+{
+    hipLaunchKernelGGL(k_df_batch_wrap, dim3(nslots), dim3(256), 0, st, image, slots, blocks, outs, kind, xk, out, stats);
     return 0;
 }
 

@@ -51,4 +51,8 @@ extern "C" {
     pub fn df_enc_finished(e: *const df_enc) -> i32;
     pub fn df_enc_read(e: *mut df_enc, out: *mut u8, cap: usize) -> isize;
     pub fn df_enc_destroy(e: *mut df_enc);
+    pub fn df_encode_batch_bound(in_len: *const u64, count: usize) -> usize;
+    pub fn df_gpu_encode_batch_device(g: *mut c_void, kind: i32, d_in: *const c_void, h_in_off: *const u64, h_in_len: *const u64, count: usize, d_out: *mut c_void, cap: usize, h_out_off: *mut u64, h_out_len: *mut u64) -> i32;
+    pub fn df_gpu_last_batch_stats(g: *mut c_void, out: *mut u64) -> i32;
+    pub fn df_encode_batch(kind: i32, device: i32, ins: *const *const u8, lens: *const usize, count: usize, out: *mut *mut u8, out_off: *mut u64, out_len: *mut u64) -> i32;
 }

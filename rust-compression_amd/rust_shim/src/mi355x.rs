@@ -75,6 +75,32 @@ pub fn encode_batch(level: usize, inputs: &[&[u8]]) -> Result<Vec<Vec<u8>>, Comp
     Ok(streams)
 }
 
+/// Many independent inputs in one call (`df_encode_batch`, device 0), `kind` 0 raw Deflate, 1 zlib, 2 gzip: element `i` of
+/// the result is the stream `inputs[i].iter().cloned().encode(&mut Inflater::new(), Action::Finish)` (or `ZlibEncoder` /
+/// `GZipEncoder`) collects, bit for bit.  Inputs of at most 65 535 bytes are one block for certain and are encoded together,
+/// however many there are.  Panics on a kind outside 0..=2.
+pub fn deflate_encode_batch(kind: usize, inputs: &[&[u8]]) -> Result<Vec<Vec<u8>>, CompressionError> {
+    assert!(kind <= 2, "invalid kind");
+    let ptrs: Vec<*const u8> = inputs.iter().map(|x| x.as_ptr()).collect();
+    let lens: Vec<usize> = inputs.iter().map(|x| x.len()).collect();
+    let mut off: Vec<u64> = Vec::new();
+    off.resize(inputs.len(), 0);
+    let mut len = off.clone();
+    let mut out: *mut u8 = core::ptr::null_mut();
+    let rc = unsafe {
+        ffi::df_encode_batch(kind as i32, 0, ptrs.as_ptr(), lens.as_ptr(), inputs.len(), &mut out, off.as_mut_ptr(), len.as_mut_ptr())
+    };
+    if rc != ffi::BZ_OK {
+        note_status(rc);
+        return Err(CompressionError::from_status(rc));
+    }
+    let streams = (0..inputs.len())
+        .map(|i| unsafe { core::slice::from_raw_parts(out.add(off[i] as usize), len[i] as usize) }.to_vec())
+        .collect();
+    unsafe { ffi::bz_free(out as *mut core::ffi::c_void) };
+    Ok(streams)
+}
+
 /// Many independent streams in one call (`bz_decode_batch`, device 0): element `i` of the result is what
 /// `inputs[i].iter().cloned().decode(&mut BZip2Decoder::new())` yields -- `Ok(bytes)`, or the `BZip2Error` with the bytes
 /// the iterator hands out in front of it.  An entry's verdict is its own: a bad one hides nothing behind it.  The outer

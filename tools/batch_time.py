@@ -18,7 +18,16 @@ The same two workloads, compressed once with compress_batch: one bz_decode_batch
 of bz_decode_buffer calls (the parent commit's code) over the same streams, alternating, both warm, medians as above;
 the outputs of the two forms are compared byte for byte (and with the inputs) before anything is timed.  The line also
 carries bz_gpu_last_decode_timings and bz_gpu_last_decode_batch_stats of one bz_gpu_decode_batch_device call over the
-same streams in HBM."""
+same streams in HBM.
+
+    tools/batch_time.py --deflate [--kind deflate|zlib|gzip] [--workload ...] [--runs 3] [--calls 5] [--loops 3]
+
+The same two workloads through the Deflate encoders: one df_encode_batch call (deflate_compress_batch) against a loop of
+df_encode_buffer calls (the parent commit's code), alternating, both warm, medians as above; the streams of the two forms
+are compared byte for byte before anything is timed.  sample1x256 (98 696 bytes each: two blocks) takes the one-input
+path inside the batch call and is the control; corpus16k takes the batch path.  The line also carries
+df_gpu_last_timings and df_gpu_last_batch_stats of one df_gpu_encode_batch_device call over the same inputs in HBM.
+BZ_DF_BATCH_MIB sets the sub-batch size."""
 import argparse
 import ctypes as C
 import importlib
@@ -108,8 +117,78 @@ def decode_mode(pkg, a, names):
             raise SystemExit("batch_time.py: the batch's outputs differ from the loop's or from the inputs")
 
 
+def deflate_mode(pkg, a, names):
+    L = pkg.lib()
+    kind = {"deflate": pkg.DEFLATE, "zlib": pkg.ZLIB, "gzip": pkg.GZIP}[a.kind]
+
+    def loop(datas):
+        out = []
+        for d in datas:
+            p, n = C.POINTER(C.c_uint8)(), C.c_size_t(0)
+            rc = L.df_encode_buffer(kind, 0, d, len(d), C.byref(p), C.byref(n))
+            if rc != 0:
+                raise SystemExit("df_encode_buffer: %d" % rc)
+            out.append(C.string_at(p, n.value))
+            L.bz_free(p)
+        return out
+
+    def device_call(datas):
+        """one df_gpu_encode_batch_device call over the inputs in HBM: its stage timings and stats"""
+        import torch
+        off, buf = [], bytearray()
+        for d in datas:
+            off.append(len(buf))
+            buf += d
+            buf += bytes(-len(buf) % 16)
+        lens = [len(d) for d in datas]
+        t = torch.frombuffer(buf + bytes(16), dtype=torch.uint8).cuda()
+        cap = pkg.deflate_encode_batch_bound(lens)
+        o = torch.empty((cap + 64,), dtype=torch.uint8, device="cuda")
+        eng = pkg.GpuEngine(0, 1)
+        try:
+            eng.deflate_encode_batch_device(kind, t.data_ptr(), off, lens, o.data_ptr(), cap)   # (warm)
+            t0 = time.perf_counter()
+            eng.deflate_encode_batch_device(kind, t.data_ptr(), off, lens, o.data_ptr(), cap)
+            wall = time.perf_counter() - t0
+            return ({k: round(v * 1e3, 3) for k, v in eng.deflate_timings().items()}, eng.deflate_batch_stats(), round(wall * 1e3, 3))
+        finally:
+            eng.close()
+
+    for name in names:
+        datas = workload(name)
+        total = sum(len(d) for d in datas)
+        batch = pkg.deflate_compress_batch(datas, kind)   # (warms the engine's workspace too)
+        same = batch == loop(datas)
+        runs = []
+        for _ in range(a.runs):
+            tb, tl = [], []
+            for _ in range(a.calls):
+                t0 = time.perf_counter()
+                pkg.deflate_compress_batch(datas, kind)
+                tb.append(time.perf_counter() - t0)
+            for _ in range(a.loops):
+                t0 = time.perf_counter()
+                loop(datas)
+                tl.append(time.perf_counter() - t0)
+            runs.append({"batch_ms": round(statistics.median(tb) * 1e3, 2), "loop_ms": round(statistics.median(tl) * 1e3, 2),
+                         "batch_all_ms": [round(t * 1e3, 2) for t in tb], "loop_all_ms": [round(t * 1e3, 2) for t in tl]})
+        bm = statistics.median(r["batch_ms"] for r in runs)
+        lm = statistics.median(r["loop_ms"] for r in runs)
+        stage_ms, stats, wall_ms = device_call(datas)
+        print(json.dumps({"mode": "deflate", "kind": a.kind, "workload": name, "inputs": len(datas), "bytes": total,
+                          "compressed_bytes": sum(len(z) for z in batch), "batch_mib": os.environ.get("BZ_DF_BATCH_MIB", "default"),
+                          "streams_equal": same, "batch_ms": bm, "loop_ms": lm, "loop_over_batch": round(lm / bm, 2),
+                          "batch_GBps": round(total / bm / 1e6, 3), "loop_GBps": round(total / lm / 1e6, 3),
+                          "device_call_ms": wall_ms, "device_call_stage_ms": stage_ms, "device_call_batch_stats": stats,
+                          "runs": runs}), flush=True)
+        if not same:
+            raise SystemExit("batch_time.py: the batch's streams differ from the loop's")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--deflate", action="store_true", help="time deflate_compress_batch against a loop of df_encode_buffer")
+    ap.add_argument("--kind", default="deflate", choices=["deflate", "zlib", "gzip"])
     ap.add_argument("--decode", action="store_true", help="time decompress_batch against a loop of bz_decode_buffer")
     ap.add_argument("--workload", default="all")
     ap.add_argument("--runs", type=int, default=3)
@@ -137,6 +216,8 @@ def main():
     names = ["sample1x256", "corpus16k"] if a.workload == "all" else [a.workload]
     if a.decode:
         return decode_mode(pkg, a, names)
+    if a.deflate:
+        return deflate_mode(pkg, a, names)
     for name in names:
         datas = workload(name)
         total = sum(len(d) for d in datas)
