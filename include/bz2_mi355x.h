@@ -675,6 +675,78 @@ long df_enc_read(df_enc *e, uint8_t *out, size_t cap);
 size_t df_enc_pending(const df_enc *e);
 void df_enc_destroy(df_enc *e);
 
+/* ========================================================================
+ * 5. Deflate / zlib / gzip DECODE  ==  `Deflater`, `ZlibDecoder`, `GZipDecoder`
+ *    (src/deflate/decoder.rs, src/zlib/decoder.rs, src/gzip/decoder.rs) on
+ *    streams that are well-formed; RFC 1951 / 1950 / 1952 decide everywhere else.
+ *
+ * Many independent streams in one call, one wave per stream; the parallelism is
+ * over the entries, a single huge stream decodes at one wave's speed.  `kind` as
+ * in section 4 (one kind per call, no preset dictionary).
+ *
+ * THE CONTRACT (DESIGN_deflate.md, "Decoding many streams in one call", says why
+ * the reference's decoder cannot be the standard on malformed input):
+ * (a) a stream that is well-formed under RFC 1951 (kind 1: inside an RFC 1950
+ *     container, kind 2: an RFC 1952 member) gets BZ_OK and its bytes -- what
+ *     zlib's inflate yields for it.  Bytes behind the end of the stream or its
+ *     trailer are ignored, and only the first gzip member is decoded.
+ * (b) every other entry gets an error verdict and the bytes produced in front of
+ *     the failing code or block header.  BZ_E_EOF: the entry ends before the
+ *     final block's end-of-block code (kinds 1 / 2: before the trailer is
+ *     complete, or inside the container header: no bytes).  BZ_E_DATA: BTYPE 3; a
+ *     stored block with LEN ^ NLEN != 0xFFFF; more than 286 literal/length or 30
+ *     distance code lengths; a repeat code 16 with nothing in front of it; a run
+ *     past HLIT + HDIST; an over-subscribed code-length set; an incomplete one
+ *     (accepted: no distance code at all, and exactly one distance code of
+ *     length 1); no end-of-block code; a length symbol 286 / 287; a distance
+ *     symbol 30 / 31; a distance that reaches in front of the entry's output; a
+ *     container header the reference rejects (zlib: CM != 8, CINFO > 7, FCHECK;
+ *     gzip: ID1, ID2, CM != 8, a reserved FLG bit, a wrong header CRC); FDICT
+ *     set; a wrong Adler-32; a wrong CRC-32 or ISIZE -- with a wrong trailer
+ *     value all bytes have been produced and h_out_len is the full length.
+ *     A failure that only the zero bits behind the entry's end made possible is
+ *     BZ_E_EOF, never BZ_E_DATA.  A stored block that the entry's end cuts short
+ *     yields none of its bytes.
+ * ======================================================================== */
+
+/* Entry i is the h_in_len[i] bytes at d_in + h_in_off[i]: d_in 16-byte aligned, every offset a multiple of 4, the ranges
+ * ascending and disjoint, each shorter than 4 GiB -- exactly what df_gpu_encode_batch_device writes: its (d_out, h_out_off,
+ * h_out_len) go in unchanged.  No bit outside an entry's range influences that entry, and nothing at or behind the end of
+ * the last range is read (an entry's last, partial 4-byte word is read byte by byte).
+ * Entry i's bytes go to d_out + h_out_off[i] (h_out_len[i] of them): input order, every offset a multiple of 16 (d_out
+ * itself 16-byte aligned), the ranges disjoint -- valid input of df_gpu_encode_batch_device and
+ * bz_gpu_encode_batch_device.  NOTHING outside the reported ranges is written: the bytes between them, and everything at
+ * or behind d_out + cap, keep what they held.  h_verdict[i] is BZ_OK, BZ_E_DATA or BZ_E_EOF (CompressionError::DataError /
+ * UnexpectedEof); no entry's verdict or bytes change another entry's.  The RETURN VALUE is the infrastructure status only:
+ * BZ_OK also when entries carry errors.  The five arrays are HOST arrays of `count` entries.
+ * Two launches: the first decodes every entry and writes only its length and verdict; the host places the outputs (one
+ * round trip, in which cap is checked: BZ_E_CAPACITY leaves d_out untouched); the second decodes again and writes.
+ * Kinds 1 / 2: a third kernel sums the decoded bytes and compares with the trailers.
+ * d_out == NULL: sizes only -- the offsets, lengths and verdicts of the real call, except that Adler-32, CRC-32 and ISIZE
+ * are not looked at (such an entry is BZ_OK here); the capacity the real call needs is the largest h_out_off[i] +
+ * h_out_len[i].  Positions inside an entry are 32-bit: an entry whose output would reach 4 GiB makes the call return
+ * BZ_E_PARAM.  BZ_E_PARAM also: kind outside 0..2, a null engine, a null array with count > 0, a misaligned d_in, d_out or
+ * offset, ranges that overlap or are out of order.  count == 0: BZ_OK, nothing touched.
+ * Afterwards df_gpu_last_timings holds [0] the sizes launch [1] the writing launch [2] the checksum kernel [5] their sum. */
+int df_gpu_decode_batch_device(bz_gpu_engine *g, int kind, const void *d_in,
+                               const uint64_t *h_in_off, const uint64_t *h_in_len, size_t count,
+                               void *d_out, size_t cap,
+                               uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_verdict);
+/* The last df_gpu_decode_batch_device call: [0] entries decoded clean [1] entries with an error verdict, and of the
+ * blocks decoded whole [2] stored [3] fixed [4] dynamic; [5] decoded bytes [6] compressed bytes consumed (to the end of
+ * the stream or trailer, or to the failing code) [7] kernel launches. */
+int df_gpu_last_decode_batch_stats(bz_gpu_engine *g, uint64_t out[8]);
+/* The host form (mirrors bz_decode_batch): the entries are packed at 4-byte-aligned offsets, uploaded once and decoded by
+ * one device call on an engine of the per-process cache; entry i's bytes are (*out)[out_off[i] .. + out_len[i]), its
+ * verdict verdict[i]; *out is ONE malloc'ed buffer (release with bz_free; offsets are multiples of 16, relative to it).
+ * count == 0: BZ_OK, *out an empty buffer, no device is touched.  Without a GPU: BZ_E_NOGPU (there is no CPU path). */
+int df_decode_batch(int kind, int device, const uint8_t *const *ins, const size_t *lens, size_t count,
+                    uint8_t **out, uint64_t *out_off, uint64_t *out_len, int32_t *verdict);
+/* The batch of one == `in.iter().cloned().decode(&mut Deflater::new())` (ZlibDecoder / GZipDecoder) collected until None
+ * or the first Err under the contract above: returns BZ_OK with the bytes, or the verdict with the bytes in front of it
+ * (as bz_decode_buffer does). */
+int df_decode_buffer(int kind, int device, const uint8_t *in, size_t in_len, uint8_t **out, size_t *out_len);
+
 #ifdef __cplusplus
 }
 #endif

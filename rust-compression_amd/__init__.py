@@ -12,6 +12,7 @@ Host-side mirror (Python flavour) of the reference's interface for this one path
     BZip2Error                   bzip2/error.rs:5-11   BZip2Error(kind)  (a CompressionError, bzip2/error.rs:45-53)
     BZip2Decoder::new()          bzip2/decoder.rs:588  BZip2Decoder()
     Decoder::next(iter)          traits/decoder.rs:95  BZip2Decoder.next(iter) -> int | None, raises BZip2Error
+    Deflater / ZlibDecoder / GZipDecoder               Deflater() / ZlibDecoder() / GZipDecoder(): .next(iter), .decode_all(data)
     iter.decode(&mut dec)        traits/decoder.rs:15  decode(iterable, dec) -> iterator of ints
 
 Everything below the iterator plumbing happens in the HIP library (csrc/, C ABI in
@@ -27,7 +28,7 @@ import sys
 from . import _build
 
 __all__ = ["Action", "CompressionError", "BZip2Error", "BZip2Encoder", "BZip2Decoder", "encode", "decode",
-           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "GpuEngine", "release_cached_resources", "last_call_phases",
+           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "deflate_decompress", "deflate_decompress_batch", "Deflater", "ZlibDecoder", "GZipDecoder", "GpuEngine", "release_cached_resources", "last_call_phases",
            "build", "lib", "device_count", "encode_bound", "shard_window", "rccl_lib", "rccl_unique_id", "RcclComm"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -95,6 +96,7 @@ EXPORTS = [
     "df_gpu_debug_blocks", "df_encode_buffer", "df_gpu_encode_device_dict", "df_encode_buffer_dict", "df_enc_create_dict",
     "df_enc_create", "df_enc_write", "df_enc_end", "df_enc_read", "df_enc_pending", "df_enc_destroy", "df_enc_finished",
     "df_encode_batch_bound", "df_gpu_encode_batch_device", "df_gpu_last_batch_stats", "df_encode_batch",
+    "df_gpu_decode_batch_device", "df_gpu_last_decode_batch_stats", "df_decode_batch", "df_decode_buffer",
 ]
 
 
@@ -246,6 +248,10 @@ def lib():
     L.df_gpu_encode_batch_device.argtypes = [vp, C.c_int, vp, u64p, u64p, sz, vp, sz, u64p, u64p]
     L.df_gpu_last_batch_stats.argtypes = [vp, u64p]
     L.df_encode_batch.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, sz, C.POINTER(u8p), u64p, u64p]
+    L.df_gpu_decode_batch_device.argtypes = [vp, C.c_int, vp, u64p, u64p, sz, vp, sz, u64p, u64p, i32p]
+    L.df_gpu_last_decode_batch_stats.argtypes = [vp, u64p]
+    L.df_decode_batch.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, sz, C.POINTER(u8p), u64p, u64p, i32p]
+    L.df_decode_buffer.argtypes = [C.c_int, C.c_int, C.c_char_p, sz, C.POINTER(u8p), szp]
     _LIB = L
     return L
 
@@ -807,6 +813,98 @@ def decompress_batch(datas, device=0):
         lib().bz_free(out)
 
 
+_DF_VERDICTS = (BZ_E_DATA, BZ_E_EOF)
+
+
+def deflate_decompress(data, kind=DEFLATE, device=0):
+    """One-shot over host buffers (df_decode_buffer) -> (bytes yielded, verdict code): BZ_OK, BZ_E_DATA or BZ_E_EOF under
+    the contract of section 5 of the header (RFC 1951 / 1950 / 1952; zlib's inflate is the arbiter)."""
+    if kind not in (DEFLATE, ZLIB, GZIP):
+        raise ValueError("invalid kind")
+    data = bytes(data)
+    out = C.POINTER(C.c_uint8)()
+    n = C.c_size_t(0)
+    rc = lib().df_decode_buffer(kind, device, data, len(data), C.byref(out), C.byref(n))
+    if rc != BZ_OK and rc not in _DF_VERDICTS:
+        raise CompressionError(rc)
+    try:
+        return C.string_at(out, n.value), rc
+    finally:
+        lib().bz_free(out)
+
+
+def deflate_decompress_batch(datas, kind=DEFLATE, device=0):
+    """Many independent streams in one call (df_decode_batch) -> list of (bytes yielded, verdict code): element i is
+    deflate_decompress(datas[i], kind).  An entry's verdict is its own; CompressionError is raised for infrastructure
+    errors only."""
+    if kind not in (DEFLATE, ZLIB, GZIP):
+        raise ValueError("invalid kind")
+    datas = [d if isinstance(d, bytes) else bytes(d) for d in datas]
+    k = len(datas)
+    ins = (C.c_char_p * max(k, 1))(*datas)
+    lens = (C.c_size_t * max(k, 1))(*[len(d) for d in datas])
+    off = (C.c_uint64 * max(k, 1))()
+    ln = (C.c_uint64 * max(k, 1))()
+    verdicts = (C.c_int32 * max(k, 1))()
+    out = C.POINTER(C.c_uint8)()
+    _check(lib().df_decode_batch(kind, device, ins, lens, k, C.byref(out), off, ln, verdicts))
+    try:
+        base = C.addressof(out.contents) if k else 0
+        return [(C.string_at(base + off[i], ln[i]), int(verdicts[i])) for i in range(k)]
+    finally:
+        lib().bz_free(out)
+
+
+class Deflater:
+    """`Deflater` (src/deflate/decoder.rs) with the `next(it)` / `decode_all(data)` surface of BZip2Decoder, over
+    df_decode_buffer: the first `next` collects the input iterator and decodes it in one call; the bytes are handed out,
+    then CompressionError (kind DataError / UnexpectedEof, `.partial` = the bytes in front of it) is raised once.
+    Creating one does not touch the device."""
+    KIND = DEFLATE
+
+    def __init__(self, device=0):
+        self._device = device
+        self._ready = None
+        self._pos = 0
+        self._verdict = BZ_OK
+
+    def _error(self):
+        e = CompressionError(self._verdict)
+        e.partial = self._ready
+        self._verdict = BZ_OK
+        return e
+
+    def next(self, it):
+        """One `Decoder::next(iter)` call: an int byte, None at the end, raises CompressionError for Err."""
+        if self._ready is None:
+            self._ready, self._verdict = deflate_decompress(bytes(bytearray(it)), self.KIND, self._device)
+        if self._pos < len(self._ready):
+            self._pos += 1
+            return self._ready[self._pos - 1]
+        if self._verdict != BZ_OK:
+            raise self._error()
+        return None
+
+    def decode_all(self, data):
+        """`data.decode(&mut self).collect::<Result<Vec<_>, _>>()`; CompressionError.partial holds the bytes yielded
+        before an Err."""
+        self._ready, self._verdict = deflate_decompress(data, self.KIND, self._device)
+        self._pos = len(self._ready)
+        if self._verdict != BZ_OK:
+            raise self._error()
+        return self._ready
+
+
+class ZlibDecoder(Deflater):
+    """`ZlibDecoder` (src/zlib/decoder.rs), without a preset dictionary."""
+    KIND = ZLIB
+
+
+class GZipDecoder(Deflater):
+    """`GZipDecoder` (src/gzip/decoder.rs): the first member."""
+    KIND = GZIP
+
+
 class GpuEngine:
     """Device-resident engine (section 2 of the C ABI).  Pointers are plain ints
     (e.g. torch.Tensor.data_ptr())."""
@@ -1036,6 +1134,31 @@ class GpuEngine:
         the block counts are those of the batch-path inputs."""
         s = (C.c_uint64 * 8)()
         _check(lib().df_gpu_last_batch_stats(self._h, s))
+        return [int(x) for x in s]
+
+    DEFLATE_DECODE_BATCH_STATS = ("clean", "errors", "stored", "fixed", "dynamic", "decoded_bytes", "consumed_bytes", "launches")
+
+    def deflate_decode_batch_device(self, kind, d_in, in_off, in_len, d_out, cap):
+        """Many streams in one call (df_gpu_decode_batch_device): entry i is the in_len[i] bytes at d_in + in_off[i] (offsets
+        multiples of 4, ascending -- what deflate_encode_batch_device returns); returns (out_off, out_len, verdicts), entry i's
+        bytes at d_out + out_off[i].  d_out = None: sizes only."""
+        _settle()
+        k = len(in_off)
+        if len(in_len) != k:
+            raise ValueError("deflate_decode_batch_device: in_off and in_len differ in length")
+        a_off = (C.c_uint64 * max(k, 1))(*in_off)
+        a_len = (C.c_uint64 * max(k, 1))(*in_len)
+        o_off = (C.c_uint64 * max(k, 1))()
+        o_len = (C.c_uint64 * max(k, 1))()
+        verdicts = (C.c_int32 * max(k, 1))()
+        _check(lib().df_gpu_decode_batch_device(self._h, kind, d_in, a_off, a_len, k, d_out, cap, o_off, o_len, verdicts))
+        return list(o_off[:k]), list(o_len[:k]), [int(v) for v in verdicts[:k]]
+
+    def deflate_decode_batch_stats(self):
+        """The last deflate_decode_batch_device call, in the order of DEFLATE_DECODE_BATCH_STATS
+        (df_gpu_last_decode_batch_stats)."""
+        s = (C.c_uint64 * 8)()
+        _check(lib().df_gpu_last_decode_batch_stats(self._h, s))
         return [int(x) for x in s]
 
     def deflate_timings(self):

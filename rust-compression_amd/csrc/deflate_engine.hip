@@ -25,6 +25,8 @@ struct DfWorkspace {
         stream, asum, bsum, crc, part_res;
     DevBuf b_slots, b_tile_slot, b_bse, b_outs, b_stats; // a sub-batch of df_gpu_encode_batch_device: slot tables, block ends, streams' places
     u64 batch_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // df_gpu_last_batch_stats
+    DevBuf i_in, i_ooff, i_rec;                        // df_gpu_decode_batch_device: the entries' ranges, their outputs' places, their records
+    u64 inf_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // df_gpu_last_decode_batch_stats
     double t_stage[6] = {0, 0, 0, 0, 0, 0}; // chains, matches, parse, blocks, emit, total
     u64 stats[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // blocks, stored, fixed, dynamic, limited tables, stream bytes, dynamic w/o distances
     hipEvent_t ev[7] = {};
@@ -811,6 +813,181 @@ extern "C" int df_encode_batch(int kind, int device, const uint8_t *const *ins, 
     if (rc != BZ_OK) return rc;
     *out = h;
     return BZ_OK;
+}
+
+// ---- decode of many streams (section 5 of the header; kernels: k_inflate.hip) -------------------------------
+extern "C" int df_gpu_last_decode_batch_stats(bz_gpu_engine *g, uint64_t out[8])
+{
+    if (!g || !out) return BZ_E_PARAM;
+    for (int i = 0; i < 8; ++i) out[i] = g->df ? g->df->inf_stats[i] : 0;
+    return BZ_OK;
+}
+
+// grow != nullptr: the output is the engine's own buffer, sized between the two launches (the host forms)
+static int df_decode_batch_core(bz_gpu_engine *g, int kind, const void *d_in, const uint64_t *h_in_off, const uint64_t *h_in_len, size_t count,
+                                void *d_out, size_t cap, DevBuf *grow, uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_verdict)
+{
+    if (!g || kind < 0 || kind > 2) return BZ_E_PARAM;
+    if (count == 0) return BZ_OK;
+    if (!h_in_off || !h_in_len || !h_out_off || !h_out_len || !h_verdict || count > 0x7FFFFFFFu) return BZ_E_PARAM;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u)) return BZ_E_PARAM;
+    u64 in_end = 0;
+    for (size_t i = 0; i < count; ++i) {
+        if ((h_in_off[i] & 3u) || h_in_off[i] < in_end || h_in_off[i] + h_in_len[i] < h_in_off[i] || h_in_len[i] > 0xFFFFFFFFull) return BZ_E_PARAM;
+        in_end = h_in_off[i] + h_in_len[i];
+    }
+    if (in_end && !d_in) return BZ_E_PARAM;
+    HIPCHK(hipSetDevice(g->device));
+    if (!g->df) g->df = new DfWorkspace();
+    DfWorkspace *w = g->df;
+    if (!w->ev_ready) {
+        for (hipEvent_t &e : w->ev) HIPCHK(hipEventCreate(&e));
+        for (hipEvent_t &e : w->evq) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        w->ev_ready = true;
+    }
+    for (u64 &s : w->inf_stats) s = 0;
+    int rc = w->i_in.ensure(2 * count * sizeof(u64));
+    if (rc == BZ_OK) rc = w->i_ooff.ensure(count * sizeof(u64));
+    if (rc == BZ_OK) rc = w->i_rec.ensure(count * sizeof(DfInfRec));
+    if (rc != BZ_OK) return rc;
+    u64 *d_off = w->i_in.as<u64>(), *d_len = d_off + count, *d_ooff = w->i_ooff.as<u64>();
+    DfInfRec *d_rec = w->i_rec.as<DfInfRec>();
+    const u8 *in8 = static_cast<const u8 *>(d_in);
+    HIPCHK(hipMemcpyAsync(d_off, h_in_off, count * sizeof(u64), hipMemcpyHostToDevice, g->st));
+    HIPCHK(hipMemcpyAsync(d_len, h_in_len, count * sizeof(u64), hipMemcpyHostToDevice, g->st));
+    HIPCHK(hipEventRecord(w->ev[0], g->st));
+    if (df_launch_inflate(g->st, false, in8, d_off, d_len, (u32)count, kind, nullptr, nullptr, d_rec) != 0) return BZ_E_UNEXPECTED;
+    HIPCHK(hipEventRecord(w->ev[1], g->st));
+    std::vector<DfInfRec> rec(count);
+    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, count * sizeof(DfInfRec), hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipStreamSynchronize(g->st));
+    // the outputs' places: input order, each at a multiple of 16
+    u64 cursor = 0, need = 0;
+    for (size_t i = 0; i < count; ++i) {
+        if (rec[i].flags & 1u) return BZ_E_PARAM; // an entry of 4 GiB or more of output
+        h_out_off[i] = cursor;
+        h_out_len[i] = rec[i].len;
+        h_verdict[i] = rec[i].verdict;
+        need = cursor + rec[i].len; // (the largest off + len: offsets ascend, so the last entry's, empty or not)
+        cursor += ((u64)rec[i].len + 15u) & ~(u64)15;
+    }
+    u8 *out8 = static_cast<u8 *>(d_out);
+    if (grow) {
+        rc = grow->ensure((size_t)need + 64);
+        if (rc != BZ_OK) return rc;
+        out8 = grow->as<u8>();
+    } else if (d_out && need > cap) return BZ_E_CAPACITY;
+    float ms[3] = {0, 0, 0};
+    if (out8) {
+        HIPCHK(hipMemcpyAsync(d_ooff, h_out_off, count * sizeof(u64), hipMemcpyHostToDevice, g->st));
+        HIPCHK(hipEventRecord(w->ev[2], g->st));
+        if (df_launch_inflate(g->st, true, in8, d_off, d_len, (u32)count, kind, out8, d_ooff, d_rec) != 0) return BZ_E_UNEXPECTED;
+        HIPCHK(hipEventRecord(w->ev[3], g->st));
+        if (kind != 0) {
+            if (df_launch_inflate_check(g->st, out8, d_ooff, (u32)count, d_rec, kind) != 0) return BZ_E_UNEXPECTED;
+            HIPCHK(hipMemcpyAsync(rec.data(), d_rec, count * sizeof(DfInfRec), hipMemcpyDeviceToHost, g->st));
+        }
+        HIPCHK(hipEventRecord(w->ev[4], g->st));
+        HIPCHK(hipStreamSynchronize(g->st));
+        for (size_t i = 0; i < count; ++i) h_verdict[i] = rec[i].verdict;
+        (void)hipEventElapsedTime(&ms[1], w->ev[2], w->ev[3]);
+        (void)hipEventElapsedTime(&ms[2], w->ev[3], w->ev[4]);
+        w->inf_stats[7] = kind != 0 ? 3 : 2;
+    } else w->inf_stats[7] = 1;
+    (void)hipEventElapsedTime(&ms[0], w->ev[0], w->ev[1]);
+    for (size_t i = 0; i < count; ++i) {
+        w->inf_stats[rec[i].verdict == BZ_OK ? 0 : 1] += 1;
+        for (int k = 0; k < 3; ++k) w->inf_stats[2 + k] += rec[i].nblk[k];
+        w->inf_stats[5] += rec[i].len;
+        w->inf_stats[6] += (rec[i].end_bit + 7u) >> 3;
+    }
+    // df_gpu_last_timings: [0] the sizes launch [1] the writing launch [2] the checksum kernel [5] their sum
+    for (double &t : w->t_stage) t = 0;
+    for (int k = 0; k < 3; ++k) {
+        w->t_stage[k] = ms[k] * 1e-3;
+        w->t_stage[5] += ms[k] * 1e-3;
+    }
+    return BZ_OK;
+}
+
+extern "C" int df_gpu_decode_batch_device(bz_gpu_engine *g, int kind, const void *d_in, const uint64_t *h_in_off, const uint64_t *h_in_len,
+                                          size_t count, void *d_out, size_t cap, uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_verdict)
+{
+    return df_decode_batch_core(g, kind, d_in, h_in_off, h_in_len, count, d_out, cap, nullptr, h_out_off, h_out_len, h_verdict);
+}
+
+// The host form (mirrors bz_decode_batch): the entries packed at 4-byte-aligned offsets, one upload, one device call on an
+// engine of the per-process cache (its output buffer sized between the two launches), one download.
+extern "C" int df_decode_batch(int kind, int device, const uint8_t *const *ins, const size_t *lens, size_t count, uint8_t **out,
+                               uint64_t *out_off, uint64_t *out_len, int32_t *verdict)
+{
+    if (!out) return BZ_E_PARAM;
+    *out = nullptr;
+    if (kind < 0 || kind > 2) return BZ_E_PARAM;
+    if (count && (!ins || !lens || !out_off || !out_len || !verdict)) return BZ_E_PARAM;
+    for (size_t i = 0; i < count; ++i)
+        if (lens[i] && !ins[i]) return BZ_E_PARAM;
+    if (count == 0) {
+        *out = (uint8_t *)malloc(1);
+        return *out ? BZ_OK : BZ_E_NOMEM;
+    }
+    std::vector<uint64_t> in_off(count), in_len(count);
+    u64 total_in = 0;
+    for (size_t i = 0; i < count; ++i) {
+        in_off[i] = total_in;
+        in_len[i] = lens[i];
+        total_in += ((u64)lens[i] + 3u) & ~(u64)3;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return BZ_E_NOGPU;
+    int caller_device = -1;
+    (void)hipGetDevice(&caller_device);
+    bz_gpu_engine *g = dec_cache_take(device, 2);
+    int rc = g ? BZ_OK : bz_gpu_engine_create(&g, device, 1);
+    if (rc != BZ_OK) return rc;
+    uint8_t *h = nullptr;
+    std::vector<uint8_t> packed((size_t)total_in + 16);
+    for (size_t i = 0; i < count; ++i)
+        if (lens[i]) memcpy(packed.data() + in_off[i], ins[i], lens[i]);
+    rc = hipSetDevice(device) == hipSuccess ? BZ_OK : BZ_E_UNEXPECTED;
+    if (rc == BZ_OK) rc = g->dec_in.ensure((size_t)total_in + 64);
+    if (rc == BZ_OK && total_in && hipMemcpy(g->dec_in.p, packed.data(), (size_t)total_in, hipMemcpyHostToDevice) != hipSuccess)
+        rc = BZ_E_UNEXPECTED;
+    if (rc == BZ_OK)
+        rc = df_decode_batch_core(g, kind, g->dec_in.p, in_off.data(), in_len.data(), count, nullptr, 0, &g->oneshot_out, out_off, out_len, verdict);
+    if (rc == BZ_OK) {
+        size_t total_out = 0;
+        total_out = (size_t)(out_off[count - 1] + out_len[count - 1]);
+        h = (uint8_t *)malloc(total_out ? total_out : 1);
+        if (!h) rc = BZ_E_NOMEM;
+        else if (total_out && hipMemcpy(h, g->oneshot_out.p, total_out, hipMemcpyDeviceToHost) != hipSuccess) {
+            free(h);
+            h = nullptr;
+            rc = BZ_E_UNEXPECTED;
+        }
+    }
+    if (rc == BZ_OK) dec_cache_put(device, g);
+    else bz_gpu_engine_destroy(g); // (an engine that met an error is not kept)
+    if (caller_device >= 0) (void)hipSetDevice(caller_device);
+    if (rc != BZ_OK) return rc;
+    *out = h;
+    return BZ_OK;
+}
+
+// The batch of one: BZ_OK with the bytes, or the entry's verdict with the bytes in front of it (as bz_decode_buffer).
+extern "C" int df_decode_buffer(int kind, int device, const uint8_t *in, size_t in_len, uint8_t **out, size_t *out_len)
+{
+    if (!out || !out_len || (in_len && !in)) return BZ_E_PARAM;
+    *out = nullptr;
+    *out_len = 0;
+    uint64_t off = 0, len = 0;
+    int32_t verdict = BZ_OK;
+    const uint8_t *ins[1] = {in};
+    const size_t lens[1] = {in_len};
+    const int rc = df_decode_batch(kind, device, ins, lens, 1, out, &off, &len, &verdict);
+    if (rc != BZ_OK) return rc;
+    *out_len = (size_t)len; // (the one entry lies at offset 0)
+    return verdict;
 }
 
 // ---- C ABI ------------------------------------------------------------------------------------------------

@@ -132,4 +132,19 @@ int df_launch_sums(hipStream_t st, const u8 *in, u64 n, u64 *asum, u64 *bsum, u3
 // what kinds of blocks there were: stats[0..4] += stored, fixed, dynamic, limited tables, dynamic without distances
 int df_launch_batch_wrap(hipStream_t st, const u8 *image, const DfSlot *slots, u32 nslots, const DfBlock *blocks, const DfBatchOut *outs,
                          int kind, DfCrcShifts xk, u8 *out, u32 *stats);
+// ---- decode of many streams (df_gpu_decode_batch_device; k_inflate.hip): what the sizes launch leaves per entry
+struct DfInfRec {
+    u64 end_bit;  // bits of the entry consumed: to the end of the stream or its trailer, or to the failing code
+    u32 len;      // bytes produced in front of the verdict
+    int verdict;  // BZ_OK, BZ_E_DATA, BZ_E_EOF
+    u32 nblk[3];  // stored, fixed, dynamic blocks decoded whole
+    u32 check;    // the trailer's Adler-32 (kind 1) / CRC-32 (kind 2)
+    u32 isize;    // the trailer's ISIZE (kind 2)
+    u32 flags;    // bit 0: the output would reach 4 GiB
+    u32 pad[2];
+};
+// write = false: sizes only (out, out_off unused); write = true: the bytes of entry i go to out + out_off[i], at most rec[i].len
+int df_launch_inflate(hipStream_t st, bool write, const u8 *in, const u64 *in_off, const u64 *in_len, u32 count, int kind, u8 *out,
+                      const u64 *out_off, DfInfRec *rec);
+int df_launch_inflate_check(hipStream_t st, const u8 *out, const u64 *out_off, u32 count, DfInfRec *rec, int kind);
 } // namespace dfgpu

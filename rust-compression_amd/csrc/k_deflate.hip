@@ -34,6 +34,7 @@
 
 #include "bzgpu.h"
 #include "k_deflate.h"
+#include "k_df_fold.h"
 
 namespace dfgpu {
 using namespace bzgpu;
@@ -2188,26 +2189,6 @@ __global__ __launch_bounds__(256) void k_df_batch_offsets(DfBlock *__restrict__ 
         blocks[j].bit_off = (off + head) * 8u;
         off += (len + 3u) & ~3u;
     }
-}
-
-__device__ __forceinline__ u32 df_gf_mul(u32 a, u32 b) // a * b in GF(2)[x] / P, reflected (bit 31 = x^0)
-{
-    u32 pr = 0;
-    for (u32 m = 1u << 31; m != 0 && a != 0; m >>= 1) {
-        if (a & m) { pr ^= b; a &= ~m; }
-        b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
-    }
-    return pr;
-}
-__device__ __forceinline__ u32 df_gf_xpow8(u32 nbytes) // x^(8 * nbytes) mod P
-{
-    u32 r = 1u << 31, sq = 1u << 23;
-    while (nbytes) {
-        if (nbytes & 1u) r = df_gf_mul(r, sq);
-        sq = df_gf_mul(sq, sq);
-        nbytes >>= 1;
-    }
-    return r;
 }
 
 // one workgroup per stream: the container around its block (zlib/encoder.rs:63-72,118-156; gzip/encoder.rs:62-75,88-134).

@@ -1,0 +1,527 @@
+// k_inflate.hip -- Deflate / zlib / gzip DECODE of many independent streams (include/bz2_mi355x.h section 5,
+// DESIGN_deflate.md "Decoding many streams in one call").  The standard is RFC 1951 / 1950 / 1952, not the reference's
+// decoder (src/deflate/decoder.rs), which swallows errors; the container header checks are the reference's
+// (src/zlib/decoder.rs:78-90, src/gzip/decoder.rs:92-108, 175-191).
+//
+// k_df_inflate<WRITE>: one 64-lane workgroup (one wave) per entry, from the entry's first bit to its last.  Everything that
+// steers the decode -- bit buffer, positions, the symbol just decoded -- is wave-uniform; the lanes share the work that
+// has width: building the tables, staging the input, storing literals, copying matches.
+//   <false> sums the output length and writes nothing but the entry's record;
+//   <true>  decodes again and writes the bytes at the place the driver gave the entry (never at or behind the length the
+//           first launch reported: `limit`).
+//
+// INPUT.  The bit buffer (64 bits) is refilled in 32-bit words.  A word comes from a 64-word stage the lanes load together
+// (lane l holds word cbase + l; the word wanted is read with readlane).  Words that lie whole inside the entry are loaded
+// as words (d_in is 16-byte aligned, every offset a multiple of 4); the entry's last, partial word is put together from
+// byte loads, so no byte behind in_off + in_len is ever touched; every word behind that is zero.  The bits consumed are
+// 32 * nextw - cnt; having consumed more than 8 * in_len bits is the BZ_E_EOF condition, looked at behind every code and
+// header field before its result is used (so a failure that padding bits caused is an EOF, never a data error).
+//
+// TABLES (LDS, 4.6 KiB per workgroup; no per-thread arrays): a first-level table indexed by the next 10 (literal/length),
+// 9 (distance) or 7 (code-length code) bits, entry = symbol << 4 | length, 0 = "not here"; behind a miss the canonical walk
+// over the per-length counts and the symbols sorted by (length, symbol) (codes of up to 15 bits).  Built by the wave:
+// counts with LDS atomics, first codes and offsets in a serial sweep over the 15 lengths held in lanes 1..15, ranks by one
+// ballot per length and 64 symbols, fill in parallel.
+//
+// LITERALS wait in a register (lane k holds the k-th pending byte) and leave with one store instruction per 64 bytes or
+// when a match or a stored block needs the position settled.
+//
+// MATCHES are copied by the whole wave: byte i of the copy is out[p - d + (i mod d)] -- for d >= length that is the plain
+// out[p + i - d], for shorter distances the period of d bytes replicated -- so EVERY source byte lies in front of p and was
+// stored before this code was decoded; no lane reads what another lane stores in the same copy, whatever d and the length
+// are.  What it may read is a byte that another lane of this wave stored an instruction earlier (a literal flush, the
+// previous copy).  Those stores and these loads are ordered by a fence at workgroup scope (__threadfence_block()): the
+// workgroup is one wave on one CU, its stores and loads go through that CU's one L1 in program order, and workgroup scope
+// is exactly the scope at which that L1 is coherent.  The fence is skipped when the source ends at or in front of the
+// position up to which an earlier fence has already ordered the stores (`fenced`).
+#include <hip/hip_runtime.h>
+
+#include "../../include/bz2_mi355x.h"
+#include "bzgpu.h"
+#include "k_deflate.h"
+#include "k_df_fold.h"
+
+namespace dfgpu {
+using namespace bzgpu;
+
+namespace {
+constexpr u32 kLBits = 10, kDBits = 9, kCBits = 7;
+
+__constant__ u8 c_cl_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+__constant__ u16 c_len_base[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
+__constant__ u8 c_len_extra[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
+__constant__ u16 c_dist_base[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
+__constant__ u8 c_dist_extra[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
+
+__device__ __forceinline__ u32 uni(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
+
+struct InfIn {
+    const u8 *base; // the entry's first byte (a multiple of 4 from a 16-byte-aligned pointer)
+    u32 len;        // its bytes
+    u64 buf;        // the next bits, bit 0 first; bits at and above cnt are zero
+    u32 cnt;        // valid bits in buf
+    u32 nextw;      // the next word to enter buf
+    u32 cw;         // PER LANE: word cbase + lane of the entry
+    u32 cbase;
+};
+
+__device__ __forceinline__ u32 inf_word(InfIn &r, u32 w, u32 lane)
+{
+    if (w - r.cbase >= 64u) { // (wave-uniform)
+        r.cbase = w;
+        const u64 byte = 4ull * ((u64)w + lane);
+        u32 v = 0;
+        if (byte + 4 <= r.len) v = *reinterpret_cast<const u32 *>(r.base + byte);
+        else
+            for (u32 k = 0; k < 4 && byte + k < r.len; ++k) v |= (u32)r.base[byte + k] << (8 * k);
+        r.cw = v;
+    }
+    return (u32)__builtin_amdgcn_readlane((int)r.cw, (int)uni(w - r.cbase));
+}
+// at least 33 valid bits behind this (zeros behind the entry's end)
+__device__ __forceinline__ void inf_fill(InfIn &r, u32 lane)
+{
+    while (r.cnt <= 32u) {
+        r.buf |= (u64)inf_word(r, r.nextw, lane) << r.cnt;
+        r.cnt += 32u;
+        ++r.nextw;
+    }
+}
+__device__ __forceinline__ u32 inf_take(InfIn &r, u32 n) // n <= 32 <= cnt
+{
+    const u32 v = (u32)(r.buf & ((1ull << n) - 1ull));
+    r.buf >>= n;
+    r.cnt -= n;
+    return v;
+}
+__device__ __forceinline__ u64 inf_consumed(const InfIn &r) { return 32ull * r.nextw - r.cnt; }
+__device__ __forceinline__ void inf_seek(InfIn &r, u32 bytepos, u32 lane)
+{
+    r.nextw = bytepos >> 2;
+    r.buf = 0;
+    r.cnt = 0;
+    inf_fill(r, lane);
+    (void)inf_take(r, 8u * (bytepos & 3u));
+}
+
+// One code: the symbol, or -1 when the next bits are no code of the set (an incomplete set's unused code).
+__device__ __forceinline__ int inf_sym(InfIn &r, const u16 *tab, u32 tbits, const u32 *cnt, const u16 *syms)
+{
+    const u32 e = uni(tab[(u32)r.buf & ((1u << tbits) - 1u)]);
+    if (e & 15u) {
+        (void)inf_take(r, e & 15u);
+        return (int)(e >> 4);
+    }
+    u32 code = 0, first = 0, index = 0;
+    for (u32 l = 1; l <= 15u; ++l) {
+        code |= (u32)(r.buf >> (l - 1)) & 1u;
+        const u32 c = uni(cnt[l]);
+        if (code < first + c) {
+            (void)inf_take(r, l);
+            return (int)uni(syms[index + (code - first)]);
+        }
+        index += c;
+        first = (first + c) << 1;
+        code <<= 1;
+    }
+    return -1;
+}
+
+// The decode tables of one code-length set: lens[0 .. n) in LDS -> tab (1 << tbits entries), cnt[16], syms.
+// Returns 0, 1 (over-subscribed) or 2 (incomplete); nsyms = codes in use, maxlen = the longest.
+__device__ __forceinline__ int inf_build(const u8 *lens, u32 n, u16 *tab, u32 tbits, u32 *cnt, u16 *syms, u32 lane, u32 &nsyms, u32 &maxlen)
+{
+    if (lane < 16u) cnt[lane] = 0;
+    for (u32 i = lane; i < (1u << tbits); i += 64u) tab[i] = 0;
+    __syncthreads();
+    for (u32 i = lane; i < n; i += 64u) {
+        const u32 l = lens[i];
+        if (l) atomicAdd(&cnt[l], 1u);
+    }
+    __syncthreads();
+    const u32 myc = (lane >= 1u && lane < 16u) ? cnt[lane] : 0u; // lane l: codes of length l
+    u32 myoff = 0, myadj = 0; // lane l: where its symbols start in syms; first code of length l minus that
+    int left = 1;
+    u32 o = 0, code = 0, prev = 0;
+    maxlen = 0;
+    for (u32 l = 1; l <= 15u; ++l) {
+        const u32 c = (u32)__builtin_amdgcn_readlane((int)myc, (int)l);
+        left = (left << 1) - (int)c;
+        if (left < 0) return 1;
+        code = (code + prev) << 1;
+        if (lane == l) {
+            myoff = o;
+            myadj = code - o;
+        }
+        o += c;
+        prev = c;
+        if (c) maxlen = l;
+    }
+    nsyms = o;
+    for (u32 base = 0; base < n; base += 64u) {
+        const u32 i = base + lane;
+        const u32 l = i < n ? lens[i] : 0u;
+        u32 rank = 0, cd = 0;
+        for (u32 ll = 1; ll <= maxlen; ++ll) {
+            const u64 m = __ballot(l == ll);
+            if (m == 0) continue;
+            const u32 o2 = (u32)__builtin_amdgcn_readlane((int)myoff, (int)ll);
+            const u32 adj = (u32)__builtin_amdgcn_readlane((int)myadj, (int)ll);
+            if (l == ll) {
+                rank = o2 + (u32)__popcll(m & ((1ull << lane) - 1ull));
+                cd = rank + adj;
+            }
+            if (lane == ll) myoff += (u32)__popcll(m);
+        }
+        if (l) {
+            syms[rank] = (u16)i;
+            if (l <= tbits) {
+                const u16 e = (u16)((i << 4) | l);
+                for (u32 j = __brev(cd) >> (32u - l); j < (1u << tbits); j += 1u << l) tab[j] = e;
+            }
+        }
+    }
+    __syncthreads();
+    return left > 0 ? 2 : 0;
+}
+} // namespace
+
+template <bool WRITE>
+__global__ __launch_bounds__(64) void k_df_inflate(const u8 *__restrict__ in, const u64 *__restrict__ in_off, const u64 *__restrict__ in_len,
+                                                   int kind, u8 *out_all, const u64 *__restrict__ out_off, DfInfRec *rec)
+{
+    __shared__ u16 s_tl[1u << kLBits], s_td[1u << kDBits], s_tc[1u << kCBits];
+    __shared__ u16 s_sl[288], s_sd[32], s_sc[32];
+    __shared__ u32 s_nl[16], s_nd[16], s_nc[16];
+    __shared__ u8 s_cl[320], s_clen[32];
+    const u32 lane = threadIdx.x, j = blockIdx.x;
+    InfIn r;
+    r.base = in + in_off[j];
+    r.len = (u32)in_len[j];
+    r.buf = 0;
+    r.cnt = 0;
+    r.nextw = 0;
+    r.cw = 0;
+    r.cbase = 0xFFFFFF00u;
+    const u64 total = 8ull * r.len;
+    u8 *out = WRITE ? out_all + out_off[j] : nullptr;
+    const u32 limit = WRITE ? rec[j].len : 0u;
+    u32 p = 0;       // bytes produced, pending literals included
+    u32 npend = 0;   // literals waiting in `lit`
+    u32 lit = 0;     // PER LANE: pending literal number `lane`
+    u32 fenced = 0;  // stores below this position are ordered before every later load
+    u32 nblk0 = 0, nblk1 = 0, nblk2 = 0, check = 0, isize = 0, flags = 0;
+    u64 end_bit = 0;
+    int verdict = BZ_OK;
+    bool fixed_ready = false;
+    u32 maxl = 0, maxd = 0;
+
+#define INF_FLUSH()                                                                   \
+    do {                                                                              \
+        if (WRITE && npend) {                                                         \
+            const u32 q_ = p - npend + lane;                                          \
+            if (lane < npend && q_ < limit) out[q_] = (u8)lit;                        \
+        }                                                                             \
+        npend = 0;                                                                    \
+    } while (0)
+// a failure: BZ_E_EOF if the bits looked at (those consumed and `extra` more) reach behind the entry, else BZ_E_DATA
+#define INF_FAIL(extra)                                                               \
+    do {                                                                              \
+        verdict = (inf_consumed(r) + (extra)) > total ? BZ_E_EOF : BZ_E_DATA;         \
+        goto done;                                                                    \
+    } while (0)
+#define INF_EOF_CHECK()                                                               \
+    do {                                                                              \
+        if (inf_consumed(r) > total) {                                                \
+            verdict = BZ_E_EOF;                                                       \
+            goto done;                                                                \
+        }                                                                             \
+    } while (0)
+
+    // ---- container header
+    if (kind == 1) {
+        inf_fill(r, lane);
+        const u32 cmf = inf_take(r, 8), flg = inf_take(r, 8);
+        INF_EOF_CHECK();
+        if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 0x20u)) INF_FAIL(0);
+    } else if (kind == 2) {
+        u32 hc = 0xFFFFFFFFu, flg = 0, xlen = 0;
+#define INF_HBYTE(v)                                                                  \
+    do {                                                                              \
+        inf_fill(r, lane);                                                            \
+        (v) = inf_take(r, 8);                                                         \
+        INF_EOF_CHECK();                                                              \
+        hc ^= (v);                                                                    \
+        for (int k_ = 0; k_ < 8; ++k_) hc = (hc & 1u) ? (hc >> 1) ^ 0xEDB88320u : hc >> 1; \
+    } while (0)
+        for (u32 k = 0; k < 10; ++k) {
+            u32 b;
+            INF_HBYTE(b);
+            if ((k == 0 && b != 0x1Fu) || (k == 1 && b != 0x8Bu) || (k == 2 && b != 8u) || (k == 3 && (b & 0xE0u))) INF_FAIL(0);
+            if (k == 3) flg = b;
+        }
+        if (flg & 4u) {
+            u32 b0, b1;
+            INF_HBYTE(b0);
+            INF_HBYTE(b1);
+            xlen = b0 | (b1 << 8);
+            for (u32 k = 0; k < xlen; ++k) INF_HBYTE(b0);
+        }
+        for (u32 f = 8u; f <= 16u; f <<= 1) // FNAME, FCOMMENT: up to the zero byte
+            if (flg & f) {
+                u32 b;
+                do INF_HBYTE(b);
+                while (b != 0);
+            }
+        if (flg & 2u) {
+            const u32 want = (hc ^ 0xFFFFFFFFu) & 0xFFFFu;
+            inf_fill(r, lane);
+            const u32 got = inf_take(r, 16);
+            INF_EOF_CHECK();
+            if (got != want) INF_FAIL(0);
+        }
+#undef INF_HBYTE
+    }
+
+    // ---- blocks
+    for (;;) {
+        inf_fill(r, lane);
+        const u32 bfinal = inf_take(r, 1), btype = inf_take(r, 2);
+        INF_EOF_CHECK();
+        if (btype == 3u) INF_FAIL(0);
+        if (btype == 0u) {
+            (void)inf_take(r, r.cnt & 7u);
+            inf_fill(r, lane);
+            const u32 ln = inf_take(r, 16), nl = inf_take(r, 16);
+            INF_EOF_CHECK();
+            if ((ln ^ nl) != 0xFFFFu) INF_FAIL(0);
+            const u32 bytepos = (u32)(inf_consumed(r) >> 3);
+            if ((u64)bytepos + ln > r.len) {
+                verdict = BZ_E_EOF;
+                goto done;
+            }
+            if (p > 0xFFFFFFFFu - 0x10000u) {
+                flags |= 1u;
+                INF_FAIL(0);
+            }
+            INF_FLUSH();
+            if (WRITE)
+                for (u32 i = lane; i < ln; i += 64u)
+                    if (p + i < limit) out[p + i] = r.base[bytepos + i];
+            p += ln;
+            inf_seek(r, bytepos + ln, lane);
+            ++nblk0;
+        } else {
+            if (btype == 1u) {
+                if (!fixed_ready) {
+                    __syncthreads();
+                    for (u32 i = lane; i < 320u; i += 64u) s_cl[i] = (u8)(i < 144u ? 8u : i < 256u ? 9u : i < 280u ? 7u : i < 288u ? 8u : 5u);
+                    __syncthreads();
+                    u32 ns;
+                    (void)inf_build(s_cl, 288, s_tl, kLBits, s_nl, s_sl, lane, ns, maxl);
+                    (void)inf_build(s_cl + 288, 32, s_td, kDBits, s_nd, s_sd, lane, ns, maxd);
+                    fixed_ready = true;
+                }
+            } else {
+                fixed_ready = false;
+                const u32 hlit = inf_take(r, 5) + 257u, hdist = inf_take(r, 5) + 1u, hclen = inf_take(r, 4) + 4u;
+                INF_EOF_CHECK();
+                if (hlit > 286u || hdist > 30u) INF_FAIL(0);
+                __syncthreads();
+                if (lane < 19u) s_clen[lane] = 0;
+                __syncthreads();
+                for (u32 k = 0; k < hclen; ++k) {
+                    inf_fill(r, lane);
+                    const u32 v = inf_take(r, 3);
+                    if (lane == 0) s_clen[c_cl_order[k]] = (u8)v;
+                }
+                INF_EOF_CHECK();
+                __syncthreads();
+                u32 ns, maxc;
+                if (inf_build(s_clen, 19, s_tc, kCBits, s_nc, s_sc, lane, ns, maxc) != 0) INF_FAIL(0);
+                const u32 ncl = hlit + hdist;
+                u32 i = 0, prev = 0;
+                while (i < ncl) {
+                    inf_fill(r, lane);
+                    const int sy = inf_sym(r, s_tc, kCBits, s_nc, s_sc);
+                    if (sy < 0) INF_FAIL(maxc);
+                    if (sy < 16) {
+                        INF_EOF_CHECK();
+                        if (lane == 0) s_cl[i] = (u8)sy;
+                        prev = (u32)sy;
+                        ++i;
+                        continue;
+                    }
+                    u32 rep, val = 0;
+                    if (sy == 16) {
+                        rep = 3u + inf_take(r, 2);
+                        val = prev;
+                    } else if (sy == 17) rep = 3u + inf_take(r, 3);
+                    else rep = 11u + inf_take(r, 7);
+                    INF_EOF_CHECK();
+                    if ((sy == 16 && i == 0) || i + rep > ncl) INF_FAIL(0);
+                    for (u32 q = lane; q < rep; q += 64u) s_cl[i + q] = (u8)val;
+                    prev = val;
+                    i += rep;
+                }
+                __syncthreads();
+                if (s_cl[256] == 0) INF_FAIL(0); // no end-of-block code
+                // (one sequence of hlit + hdist lengths: a run may cross from one alphabet into the other)
+                const int rl = inf_build(s_cl, hlit, s_tl, kLBits, s_nl, s_sl, lane, ns, maxl);
+                if (rl != 0) INF_FAIL(0);
+                const int rd = inf_build(s_cl + hlit, hdist, s_td, kDBits, s_nd, s_sd, lane, ns, maxd);
+                if (rd == 1 || (rd == 2 && !(ns == 0u || (ns == 1u && maxd == 1u)))) INF_FAIL(0);
+            }
+            // ---- the codes of the block
+            for (;;) {
+                inf_fill(r, lane);
+                const int sy = inf_sym(r, s_tl, kLBits, s_nl, s_sl);
+                if (sy < 0) INF_FAIL(maxl);
+                if (sy < 256) {
+                    INF_EOF_CHECK();
+                    if (lane == npend) lit = (u32)sy;
+                    ++npend;
+                    ++p;
+                    if (npend == 64u) INF_FLUSH();
+                    continue;
+                }
+                if (sy == 256) {
+                    INF_EOF_CHECK();
+                    break;
+                }
+                if (sy > 285) INF_FAIL(0);
+                const u32 len = c_len_base[sy - 257] + inf_take(r, c_len_extra[sy - 257]);
+                inf_fill(r, lane);
+                const int ds = inf_sym(r, s_td, kDBits, s_nd, s_sd);
+                if (ds < 0) INF_FAIL(maxd);
+                if (ds > 29) INF_FAIL(0);
+                const u32 d = c_dist_base[ds] + inf_take(r, c_dist_extra[ds]);
+                INF_EOF_CHECK();
+                if (d > p) INF_FAIL(0);
+                if (p > 0xFFFFFFFFu - 0x10000u) {
+                    flags |= 1u;
+                    INF_FAIL(0);
+                }
+                INF_FLUSH();
+                if (WRITE) {
+                    const u32 span = d < len ? d : len;
+                    if (p - d + span > fenced) {
+                        __threadfence_block();
+                        fenced = p;
+                    }
+                    const u8 *src = out + (p - d);
+                    for (u32 b = 0; b < len; b += 64u) {
+                        const u32 i = b + lane;
+                        if (i < len && p + i < limit) out[p + i] = src[d >= len ? i : i % d];
+                    }
+                }
+                p += len;
+            }
+            if (btype == 1u) ++nblk1;
+            else ++nblk2;
+        }
+        if (bfinal) break;
+    }
+    // ---- container trailer
+    (void)inf_take(r, r.cnt & 7u);
+    if (kind == 1) {
+        inf_fill(r, lane);
+        const u32 v = inf_take(r, 32);
+        INF_EOF_CHECK();
+        check = (v >> 24) | ((v >> 8) & 0xFF00u) | ((v << 8) & 0xFF0000u) | (v << 24);
+    } else if (kind == 2) {
+        inf_fill(r, lane);
+        check = inf_take(r, 32);
+        inf_fill(r, lane);
+        isize = inf_take(r, 32);
+        INF_EOF_CHECK();
+    }
+done:
+    INF_FLUSH();
+    end_bit = inf_consumed(r) < total ? inf_consumed(r) : total;
+    if (!WRITE && lane == 0) {
+        DfInfRec o;
+        o.end_bit = end_bit;
+        o.len = p;
+        o.verdict = verdict;
+        o.nblk[0] = nblk0;
+        o.nblk[1] = nblk1;
+        o.nblk[2] = nblk2;
+        o.check = check;
+        o.isize = isize;
+        o.flags = flags;
+        o.pad[0] = o.pad[1] = 0;
+        rec[j] = o;
+    }
+#undef INF_FLUSH
+#undef INF_FAIL
+#undef INF_EOF_CHECK
+}
+
+// The container checksums of the decoded bytes, a workgroup per entry: thread t folds the t-th slice of the entry (a
+// multiple of 16 bytes), the slices are combined as k_df_batch_wrap combines its pieces (k_df_fold.h).  A mismatch with the
+// trailer -- Adler-32 (kind 1), CRC-32 or ISIZE (kind 2) -- turns the entry's verdict to BZ_E_DATA.
+__global__ __launch_bounds__(256) void k_df_inflate_check(const u8 *__restrict__ out_all, const u64 *__restrict__ out_off, DfInfRec *rec, int kind)
+{
+    __shared__ u32 s_tab[256];
+    __shared__ u64 s_a[256], s_b[256];
+    __shared__ u32 s_c[256];
+    const u32 tid = threadIdx.x, j = blockIdx.x;
+    if (rec[j].verdict != BZ_OK) return;
+    const u32 len = rec[j].len;
+    {
+        u32 c = tid;
+        for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
+        s_tab[tid] = c;
+    }
+    __syncthreads();
+    const u8 *src = out_all + out_off[j]; // (a multiple of 16)
+    const u64 slice = ((((u64)len + 255u) >> 8) + 15u) & ~15ull;
+    const u64 lo = (u64)tid * slice < len ? (u64)tid * slice : len;
+    const u64 hi = lo + slice < len ? lo + slice : len;
+    u64 a = 0, b = 0;
+    u32 c = 0;
+    u64 i = lo;
+    for (; i + 16 <= hi; i += 16) {
+        const u32x4_t v = *reinterpret_cast<const u32x4_t *>(src + i);
+        const u32 w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (u32 k = 0; k < 16; ++k) df_fold_byte((w[k >> 2] >> (8 * (k & 3u))) & 0xFFu, hi - (i + k), s_tab, a, b, c);
+    }
+    for (; i < hi; ++i) df_fold_byte(src[i], hi - i, s_tab, a, b, c);
+    const u64 after = len - hi;
+    s_a[tid] = a % 65521u;
+    s_b[tid] = (b % 65521u + (a % 65521u) * (after % 65521u)) % 65521u;
+    s_c[tid] = df_gf_mul(c, df_gf_xpow8((u32)after));
+    __syncthreads();
+    if (tid != 0) return;
+    u64 sa = 0, sb = 0;
+    u32 raw = 0;
+    for (u32 t = 0; t < 256; ++t) {
+        sa += s_a[t];
+        sb += s_b[t];
+        raw ^= s_c[t];
+    }
+    bool ok;
+    if (kind == 1) {
+        const u32 A = (u32)((1 + sa) % 65521u), B = (u32)((len + sb) % 65521u); // adler32.rs:20-66 from (1, 0)
+        ok = ((B << 16) | A) == rec[j].check;
+    } else ok = df_crc_finish(raw, len) == rec[j].check && rec[j].isize == len;
+    if (!ok) rec[j].verdict = BZ_E_DATA;
+}
+
+int df_launch_inflate(hipStream_t st, bool write, const u8 *in, const u64 *in_off, const u64 *in_len, u32 count, int kind, u8 *out,
+                      const u64 *out_off, DfInfRec *rec)
+{
+    if (write) hipLaunchKernelGGL((k_df_inflate<true>), dim3(count), dim3(64), 0, st, in, in_off, in_len, kind, out, out_off, rec);
+    else hipLaunchKernelGGL((k_df_inflate<false>), dim3(count), dim3(64), 0, st, in, in_off, in_len, kind, out, out_off, rec);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int df_launch_inflate_check(hipStream_t st, const u8 *out, const u64 *out_off, u32 count, DfInfRec *rec, int kind)
+{
+    hipLaunchKernelGGL(k_df_inflate_check, dim3(count), dim3(256), 0, st, out, out_off, rec, kind);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+} // namespace dfgpu

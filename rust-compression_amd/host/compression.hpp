@@ -385,6 +385,81 @@ class BZip2Decoder {
     bool ended_ = false, failed_ = false;
 };
 
+// Deflate / zlib / gzip decoders (include/bz2_mi355x.h section 5):
+//   Deflater     src/deflate/decoder.rs   (the reference's name for its Deflate DECODER)
+//   ZlibDecoder  src/zlib/decoder.rs      GZipDecoder  src/gzip/decoder.rs
+// The first next() collects the input range and decodes it in one df_decode_buffer call; the bytes come out in order,
+// then the Err item if the stream is bad (RFC 1951 / 1950 / 1952 decide, see the header), then None.
+template <int Kind> class DeflateFamilyDecoder {
+  public:
+    using Input = uint8_t;
+    using Output = uint8_t;
+    using Error = CompressionError;
+
+    explicit DeflateFamilyDecoder(int device = 0) : device_(device) {} // (does not touch the device)
+
+    template <class I, class S> std::optional<Result<uint8_t>> next(I &it, const S &end)
+    {
+        if (!ran_) {
+            ran_ = true;
+            std::vector<uint8_t> in;
+            for (; it != end; ++it) in.push_back(static_cast<uint8_t>(*it));
+            uint8_t *out = nullptr;
+            size_t n = 0;
+            verdict_ = df_decode_buffer(Kind, device_, in.data(), in.size(), &out, &n);
+            if (out) {
+                buf_.assign(out, out + n);
+                bz_free(out);
+            }
+        }
+        if (pos_ < buf_.size()) return Result<uint8_t>::Ok(buf_[pos_++]);
+        if (verdict_ != BZ_OK) {
+            const int rc = verdict_;
+            verdict_ = BZ_OK;
+            return Result<uint8_t>::Err(from_status(rc));
+        }
+        return std::nullopt;
+    }
+
+    // Many independent streams in one call (df_decode_batch): element i is what `inputs[i].decode(..)` yields.
+    struct Entry {
+        std::vector<uint8_t> bytes;
+        std::optional<CompressionError> error;
+    };
+    template <class Spans> static Result<std::vector<Entry>> decode_batch(const Spans &inputs, int device = 0)
+    {
+        using R = Result<std::vector<Entry>>;
+        std::vector<const uint8_t *> ptrs;
+        std::vector<size_t> lens;
+        for (const auto &x : inputs) {
+            ptrs.push_back(reinterpret_cast<const uint8_t *>(x.data()));
+            lens.push_back(x.size());
+        }
+        std::vector<uint64_t> off(ptrs.size()), len(ptrs.size());
+        std::vector<int32_t> verdict(ptrs.size());
+        uint8_t *out = nullptr;
+        const int rc = df_decode_batch(Kind, device, ptrs.data(), lens.data(), ptrs.size(), &out, off.data(), len.data(), verdict.data());
+        if (rc != BZ_OK) return R::Err(from_status(rc));
+        std::vector<Entry> entries(ptrs.size());
+        for (size_t i = 0; i < ptrs.size(); ++i) {
+            entries[i].bytes.assign(out + off[i], out + off[i] + len[i]);
+            if (verdict[i] != BZ_OK) entries[i].error = from_status(verdict[i]);
+        }
+        bz_free(out);
+        return R::Ok(std::move(entries));
+    }
+
+  private:
+    int device_;
+    bool ran_ = false;
+    int verdict_ = BZ_OK;
+    std::vector<uint8_t> buf_;
+    size_t pos_ = 0;
+};
+using Deflater = DeflateFamilyDecoder<DF_KIND_DEFLATE>;
+using ZlibDecoder = DeflateFamilyDecoder<DF_KIND_ZLIB>;
+using GZipDecoder = DeflateFamilyDecoder<DF_KIND_GZIP>;
+
 // DecodeIterator (src/traits/decoder.rs:45-86)
 template <class I, class S, class D> class DecodeIterator {
   public:

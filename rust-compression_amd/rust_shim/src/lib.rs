@@ -11,8 +11,9 @@
 //! Output is bit-identical to the reference's encoders / decoders (checked against the C oracle in
 //! this repository).  NOT compiled in this repository's image (no Rust toolchain there); module
 //! layout, feature flags and `prelude` follow the reference (its `src/lib.rs:48-117`, `Cargo.toml:28-38`).
-//! What the reference has and this crate does not: `lzhuf`, the standalone `LzssEncoder` /
-//! `LzssDecoder`, and the Deflate-family DECODERS (`Deflater`, `GZipDecoder`, `ZlibDecoder`).
+//! What the reference has and this crate does not: `lzhuf` and the standalone `LzssEncoder` /
+//! `LzssDecoder`.  The Deflate-family decoders (`Deflater`, `GZipDecoder`, `ZlibDecoder`) follow RFC 1951 /
+//! 1950 / 1952 on malformed input, where the reference's swallow errors (see `src/deflate/decoder.rs` here).
 #![cfg_attr(not(feature = "std"), no_std)]
 #[cfg(not(feature = "std"))]
 extern crate alloc;
@@ -47,9 +48,15 @@ pub mod prelude {
     pub use crate::bzip2::error::BZip2Error;
 
     #[cfg(all(feature = "deflate", feature = "mi355x"))]
+    pub use crate::deflate::decoder::Deflater;
+    #[cfg(all(feature = "deflate", feature = "mi355x"))]
     pub use crate::deflate::encoder::Inflater;
     #[cfg(all(feature = "gzip", feature = "mi355x"))]
+    pub use crate::gzip::decoder::GZipDecoder;
+    #[cfg(all(feature = "gzip", feature = "mi355x"))]
     pub use crate::gzip::encoder::GZipEncoder;
+    #[cfg(all(feature = "zlib", feature = "mi355x"))]
+    pub use crate::zlib::decoder::ZlibDecoder;
     #[cfg(all(feature = "zlib", feature = "mi355x"))]
     pub use crate::zlib::encoder::ZlibEncoder;
 

@@ -27,7 +27,16 @@ df_encode_buffer calls (the parent commit's code), alternating, both warm, media
 are compared byte for byte before anything is timed.  sample1x256 (98 696 bytes each: two blocks) takes the one-input
 path inside the batch call and is the control; corpus16k takes the batch path.  The line also carries
 df_gpu_last_timings and df_gpu_last_batch_stats of one df_gpu_encode_batch_device call over the same inputs in HBM.
-BZ_DF_BATCH_MIB sets the sub-batch size."""
+BZ_DF_BATCH_MIB sets the sub-batch size.
+
+    tools/batch_time.py --inflate [--kind deflate|zlib|gzip] [--workload ...|text64m] [--runs 3] [--calls 5] [--loops 3]
+
+The same workloads, compressed once with deflate_compress_batch: one df_decode_batch call (deflate_decompress_batch), host
+to host, against a loop of Python's zlib.decompress over the same streams on one host thread (the yardstick: a decoder
+that shares no code with this one), alternating, medians as above; the outputs are compared with the inputs before
+anything is timed.  The line also carries one df_gpu_decode_batch_device call over the streams in HBM: its wall time, the
+split between the sizes launch, the writing launch and the checksum kernel (df_gpu_last_timings) and
+df_gpu_last_decode_batch_stats.  text64m is ONE entry of 64 MiB of the bench corpus: what a single stream costs."""
 import argparse
 import ctypes as C
 import importlib
@@ -50,6 +59,9 @@ def workload(name):
         import corpus
         data = corpus.corpus_bytes(4096 * 16384)
         return [data[i * 16384:(i + 1) * 16384] for i in range(4096)]
+    if name == "text64m":
+        import corpus
+        return [corpus.corpus_bytes(64 << 20)]
     raise SystemExit("unknown workload %s" % name)
 
 
@@ -185,9 +197,76 @@ def deflate_mode(pkg, a, names):
             raise SystemExit("batch_time.py: the batch's streams differ from the loop's")
 
 
+def inflate_mode(pkg, a, names):
+    import zlib
+    kind = {"deflate": pkg.DEFLATE, "zlib": pkg.ZLIB, "gzip": pkg.GZIP}[a.kind]
+    wbits = {"deflate": -15, "zlib": 15, "gzip": 31}[a.kind]
+
+    def loop(streams):
+        return [zlib.decompress(z, wbits) for z in streams]
+
+    def device_call(streams):
+        """one df_gpu_decode_batch_device call over the streams in HBM: wall time, the launches' times, stats"""
+        import torch
+        off, buf = [], bytearray()
+        for z in streams:
+            off.append(len(buf))
+            buf += z
+            buf += bytes(-len(buf) % 4)
+        lens = [len(z) for z in streams]
+        t = torch.frombuffer(buf, dtype=torch.uint8).cuda()
+        eng = pkg.GpuEngine(0, 1)
+        try:
+            o_off, o_len, _ = eng.deflate_decode_batch_device(kind, t.data_ptr(), off, lens, None, 0)
+            cap = max(x + n for x, n in zip(o_off, o_len))
+            o = torch.empty((cap + 64,), dtype=torch.uint8, device="cuda")
+            eng.deflate_decode_batch_device(kind, t.data_ptr(), off, lens, o.data_ptr(), cap)   # (warm)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.deflate_decode_batch_device(kind, t.data_ptr(), off, lens, o.data_ptr(), cap)
+            wall = time.perf_counter() - t0
+            tm = eng.deflate_timings()
+            stage = {"sizes_launch": tm["hash_chains"], "write_launch": tm["matches"], "checksums": tm["parse"], "total": tm["total"]}
+            return {k: round(v * 1e3, 3) for k, v in stage.items()}, eng.deflate_decode_batch_stats(), round(wall * 1e3, 3)
+        finally:
+            eng.close()
+
+    for name in names:
+        datas = workload(name)
+        total = sum(len(d) for d in datas)
+        streams = pkg.deflate_compress_batch(datas, kind)
+        batch = pkg.deflate_decompress_batch(streams, kind)      # (warms the engine's workspace too)
+        same = batch == [(d, 0) for d in datas] and loop(streams) == datas
+        runs = []
+        for _ in range(a.runs):
+            tb, tl = [], []
+            for _ in range(a.calls):
+                t0 = time.perf_counter()
+                pkg.deflate_decompress_batch(streams, kind)
+                tb.append(time.perf_counter() - t0)
+            for _ in range(a.loops):
+                t0 = time.perf_counter()
+                loop(streams)
+                tl.append(time.perf_counter() - t0)
+            runs.append({"batch_ms": round(statistics.median(tb) * 1e3, 2), "zlib_loop_ms": round(statistics.median(tl) * 1e3, 2),
+                         "batch_all_ms": [round(t * 1e3, 2) for t in tb], "zlib_loop_all_ms": [round(t * 1e3, 2) for t in tl]})
+        bm = statistics.median(r["batch_ms"] for r in runs)
+        lm = statistics.median(r["zlib_loop_ms"] for r in runs)
+        stage_ms, stats, wall_ms = device_call(streams)
+        print(json.dumps({"mode": "inflate", "kind": a.kind, "workload": name, "streams": len(streams), "bytes": total,
+                          "compressed_bytes": sum(len(z) for z in streams), "outputs_equal": same,
+                          "batch_ms": bm, "zlib_loop_ms": lm, "zlib_loop_over_batch": round(lm / bm, 2),
+                          "batch_GBps": round(total / bm / 1e6, 3), "zlib_loop_GBps": round(total / lm / 1e6, 3),
+                          "device_call_ms": wall_ms, "device_call_GBps": round(total / wall_ms / 1e6, 3),
+                          "device_call_stage_ms": stage_ms, "device_call_batch_stats": stats, "runs": runs}), flush=True)
+        if not same:
+            raise SystemExit("batch_time.py: the batch's outputs differ from the inputs")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--deflate", action="store_true", help="time deflate_compress_batch against a loop of df_encode_buffer")
+    ap.add_argument("--inflate", action="store_true", help="time deflate_decompress_batch against a loop of zlib.decompress")
     ap.add_argument("--kind", default="deflate", choices=["deflate", "zlib", "gzip"])
     ap.add_argument("--decode", action="store_true", help="time decompress_batch against a loop of bz_decode_buffer")
     ap.add_argument("--workload", default="all")
@@ -218,6 +297,8 @@ def main():
         return decode_mode(pkg, a, names)
     if a.deflate:
         return deflate_mode(pkg, a, names)
+    if a.inflate:
+        return inflate_mode(pkg, a, names)
     for name in names:
         datas = workload(name)
         total = sum(len(d) for d in datas)
