@@ -491,6 +491,42 @@ def release_cached_resources():
     lib().bz_release_cached_resources()
 
 
+def _batch_call(fn, head_args, datas, verdicts):
+    """One host-to-host batch entry point (bz_encode_batch and its three siblings): the ctypes arrays, the call, the
+    result cut into its entries, the buffer freed.  verdicts: the call also fills one verdict per entry, and an entry of
+    the result is (bytes, verdict)."""
+    datas = [d if isinstance(d, bytes) else bytes(d) for d in datas]
+    k = len(datas)
+    ins = (C.c_char_p * max(k, 1))(*datas)
+    lens = (C.c_size_t * max(k, 1))(*[len(d) for d in datas])
+    off = (C.c_uint64 * max(k, 1))()
+    ln = (C.c_uint64 * max(k, 1))()
+    v = (C.c_int32 * max(k, 1))()
+    out = C.POINTER(C.c_uint8)()
+    _check(fn(*head_args, ins, lens, k, C.byref(out), off, ln, *((v,) if verdicts else ())))
+    try:
+        base = C.addressof(out.contents) if k else 0
+        parts = [C.string_at(base + off[i], ln[i]) for i in range(k)]
+        return [(p, int(v[i])) for i, p in enumerate(parts)] if verdicts else parts
+    finally:
+        lib().bz_free(out)
+
+
+def _decode_call(fn, head_args, data, data_verdicts):
+    """One host-to-host one-shot decode (bz_decode_buffer, df_decode_buffer) -> (bytes yielded, verdict code); a status
+    that is not one of the decoder's verdicts is raised."""
+    data = bytes(data)
+    out = C.POINTER(C.c_uint8)()
+    n = C.c_size_t(0)
+    rc = fn(*head_args, data, len(data), C.byref(out), C.byref(n))
+    if rc != BZ_OK and rc not in data_verdicts:
+        raise CompressionError(rc)
+    try:
+        return C.string_at(out, n.value), rc
+    finally:
+        lib().bz_free(out)
+
+
 def compress(data, level=9, device=0, devices=None, verify=None):
     """One-shot over host buffers (bz_encode_buffer; `devices`: bz_encode_buffer_multi over that list of GPUs).
     verify=True: through a streaming context with the self-check on (the one-shot entry points take BZ_VERIFY=1
@@ -531,18 +567,7 @@ def compress_batch(datas, level=9, device=0, verify=None):
     datas = [d if isinstance(d, bytes) else bytes(d) for d in datas]
     if verify is not None:
         return [BZip2Encoder(level, device, verify=verify).encode_all(d) for d in datas]
-    k = len(datas)
-    ins = (C.c_char_p * max(k, 1))(*datas)
-    lens = (C.c_size_t * max(k, 1))(*[len(d) for d in datas])
-    off = (C.c_uint64 * max(k, 1))()
-    ln = (C.c_uint64 * max(k, 1))()
-    out = C.POINTER(C.c_uint8)()
-    _check(lib().bz_encode_batch(level, device, ins, lens, k, C.byref(out), off, ln))
-    try:
-        base = C.addressof(out.contents) if k else 0
-        return [C.string_at(base + off[i], ln[i]) for i in range(k)]
-    finally:
-        lib().bz_free(out)
+    return _batch_call(lib().bz_encode_batch, (level, device), datas, False)
 
 
 # ---------------------------------------------------------------------------- Deflate / zlib / gzip
@@ -666,19 +691,7 @@ def deflate_compress_batch(datas, kind=DEFLATE, device=0):
     encoded together in one pass of the pipeline, however many there are."""
     if kind not in (DEFLATE, ZLIB, GZIP):
         raise ValueError("invalid kind")
-    datas = [d if isinstance(d, bytes) else bytes(d) for d in datas]
-    k = len(datas)
-    ins = (C.c_char_p * max(k, 1))(*datas)
-    lens = (C.c_size_t * max(k, 1))(*[len(d) for d in datas])
-    off = (C.c_uint64 * max(k, 1))()
-    ln = (C.c_uint64 * max(k, 1))()
-    out = C.POINTER(C.c_uint8)()
-    _check(lib().df_encode_batch(kind, device, ins, lens, k, C.byref(out), off, ln))
-    try:
-        base = C.addressof(out.contents) if k else 0
-        return [C.string_at(base + off[i], ln[i]) for i in range(k)]
-    finally:
-        lib().bz_free(out)
+    return _batch_call(lib().df_encode_batch, (kind, device), datas, False)
 
 
 _DECODER_VERDICTS = (BZ_E_DATA, BZ_E_MAGIC_FIRST, BZ_E_MAGIC)
@@ -781,36 +794,14 @@ def decode(iterable, decoder):
 
 def decompress(data, device=0):
     """One-shot over host buffers (bz_decode_buffer) -> (bytes yielded, verdict code)."""
-    data = bytes(data)
-    out = C.POINTER(C.c_uint8)()
-    n = C.c_size_t(0)
-    rc = lib().bz_decode_buffer(device, data, len(data), C.byref(out), C.byref(n))
-    if rc != BZ_OK and rc not in _DECODER_VERDICTS:
-        raise CompressionError(rc)
-    try:
-        return C.string_at(out, n.value), rc
-    finally:
-        lib().bz_free(out)
+    return _decode_call(lib().bz_decode_buffer, (device,), data, _DECODER_VERDICTS)
 
 
 def decompress_batch(datas, device=0):
     """Many independent streams in one call (bz_decode_batch) -> list of (bytes yielded, verdict code): element i is
     decompress(datas[i]).  An entry's verdict is its own -- a bad record hides nothing behind it; CompressionError is
     raised for infrastructure errors only."""
-    datas = [d if isinstance(d, bytes) else bytes(d) for d in datas]
-    k = len(datas)
-    ins = (C.c_char_p * max(k, 1))(*datas)
-    lens = (C.c_size_t * max(k, 1))(*[len(d) for d in datas])
-    off = (C.c_uint64 * max(k, 1))()
-    ln = (C.c_uint64 * max(k, 1))()
-    verdicts = (C.c_int32 * max(k, 1))()
-    out = C.POINTER(C.c_uint8)()
-    _check(lib().bz_decode_batch(device, ins, lens, k, C.byref(out), off, ln, verdicts))
-    try:
-        base = C.addressof(out.contents) if k else 0
-        return [(C.string_at(base + off[i], ln[i]), int(verdicts[i])) for i in range(k)]
-    finally:
-        lib().bz_free(out)
+    return _batch_call(lib().bz_decode_batch, (device,), datas, True)
 
 
 _DF_VERDICTS = (BZ_E_DATA, BZ_E_EOF)
@@ -821,16 +812,7 @@ def deflate_decompress(data, kind=DEFLATE, device=0):
     the contract of section 5 of the header (RFC 1951 / 1950 / 1952; zlib's inflate is the arbiter)."""
     if kind not in (DEFLATE, ZLIB, GZIP):
         raise ValueError("invalid kind")
-    data = bytes(data)
-    out = C.POINTER(C.c_uint8)()
-    n = C.c_size_t(0)
-    rc = lib().df_decode_buffer(kind, device, data, len(data), C.byref(out), C.byref(n))
-    if rc != BZ_OK and rc not in _DF_VERDICTS:
-        raise CompressionError(rc)
-    try:
-        return C.string_at(out, n.value), rc
-    finally:
-        lib().bz_free(out)
+    return _decode_call(lib().df_decode_buffer, (kind, device), data, _DF_VERDICTS)
 
 
 def deflate_decompress_batch(datas, kind=DEFLATE, device=0):
@@ -839,20 +821,7 @@ def deflate_decompress_batch(datas, kind=DEFLATE, device=0):
     errors only."""
     if kind not in (DEFLATE, ZLIB, GZIP):
         raise ValueError("invalid kind")
-    datas = [d if isinstance(d, bytes) else bytes(d) for d in datas]
-    k = len(datas)
-    ins = (C.c_char_p * max(k, 1))(*datas)
-    lens = (C.c_size_t * max(k, 1))(*[len(d) for d in datas])
-    off = (C.c_uint64 * max(k, 1))()
-    ln = (C.c_uint64 * max(k, 1))()
-    verdicts = (C.c_int32 * max(k, 1))()
-    out = C.POINTER(C.c_uint8)()
-    _check(lib().df_decode_batch(kind, device, ins, lens, k, C.byref(out), off, ln, verdicts))
-    try:
-        base = C.addressof(out.contents) if k else 0
-        return [(C.string_at(base + off[i], ln[i]), int(verdicts[i])) for i in range(k)]
-    finally:
-        lib().bz_free(out)
+    return _batch_call(lib().df_decode_batch, (kind, device), datas, True)
 
 
 class Deflater:

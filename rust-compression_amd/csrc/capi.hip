@@ -27,8 +27,8 @@ inline bool env_verify() { return false; } // (bzgpu.h: BZ_VERIFY; the stub engi
 } // namespace bzgpu
 #else
 #include "bzgpu.h"
-void dec_release_cached(); // dec_engine.hip: the engines bz_decode_buffer keeps between calls
 #endif
+#include "host_call.h" // CallerDevice, BatchLayout; dec_release_cached
 
 #include <algorithm>
 #include <atomic>
@@ -126,17 +126,6 @@ static double now_ms()
     using namespace std::chrono;
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
-
-// The calling thread's current HIP device is the caller's business: the entry points below switch devices (lanes of a
-// multi-device context live on different GPUs) and put the caller's device back when they return.  Worker threads
-// keep their own.
-struct CallerDevice {
-    int dev = -1;
-    CallerDevice() { if (hipGetDevice(&dev) != hipSuccess) dev = -1; }
-    ~CallerDevice() { if (dev >= 0) (void)hipSetDevice(dev); }
-    CallerDevice(const CallerDevice &) = delete;
-    CallerDevice &operator=(const CallerDevice &) = delete;
-};
 
 static std::mutex g_cache_mu;
 static std::vector<EncResources *> g_cache; // resources of destroyed contexts, ready for reuse
@@ -354,7 +343,7 @@ extern "C" void bz_release_cached_resources(void)
     }
     for (EncResources *r : all) resources_free(r);
 #ifndef BZ_HOST_PIPELINE_TEST
-    dec_release_cached(); // (the engines bz_decode_buffer keeps)
+    dec_release_cached(); // (the engines the decode and Deflate calls keep: engine_cache.hip)
 #endif
 }
 
@@ -1249,18 +1238,11 @@ extern "C" int bz_encode_batch(int level, int device, const uint8_t *const *ins,
     *out = nullptr;
     if (level < 1 || level > 9) return BZ_E_PARAM;
     if (count && (!ins || !lens || !out_off || !out_len)) return BZ_E_PARAM;
-    for (size_t i = 0; i < count; ++i)
-        if (lens[i] && !ins[i]) return BZ_E_PARAM;
+    const BatchLayout lay(ins, lens, count, 16);
+    if (lay.status != BZ_OK) return lay.status;
     if (count == 0) {
         *out = (u8 *)malloc(1);
         return *out ? BZ_OK : BZ_E_NOMEM;
-    }
-    std::vector<uint64_t> in_off(count), in_len(count);
-    u64 total_in = 0;
-    for (size_t i = 0; i < count; ++i) {
-        in_off[i] = total_in;
-        in_len[i] = lens[i];
-        total_in += ((u64)lens[i] + 15u) & ~(u64)15;
     }
     CallerDevice keep;
     EncResources *r = nullptr;
@@ -1269,7 +1251,7 @@ extern "C" int bz_encode_batch(int level, int device, const uint8_t *const *ins,
     Lane &ln = r->lanes[0];
     u8 *res = nullptr;
     u64 total_out = 0;
-    const size_t cap = bz_encode_batch_bound(in_len.data(), count);
+    const size_t cap = bz_encode_batch_bound(lay.in_len.data(), count);
     auto run = [&]() -> int {
         if (hipSetDevice(ln.device) != hipSuccess) return BZ_E_UNEXPECTED;
         int rc2;
@@ -1281,16 +1263,15 @@ extern "C" int bz_encode_batch(int level, int device, const uint8_t *const *ins,
                 return BZ_E_UNEXPECTED;
             r->h_lane[0] = -1;
         }
-        if ((rc2 = grow_pinned(&r->h_in[0], &r->h_cap[0], (size_t)total_in + 16)) != BZ_OK) return rc2;
-        if ((rc2 = grow(&ln.d_buf, &ln.d_buf_cap, (size_t)total_in + 64)) != BZ_OK) return rc2;
+        if ((rc2 = grow_pinned(&r->h_in[0], &r->h_cap[0], (size_t)lay.total + 16)) != BZ_OK) return rc2;
+        if ((rc2 = grow(&ln.d_buf, &ln.d_buf_cap, (size_t)lay.total + 64)) != BZ_OK) return rc2;
         if ((rc2 = grow(&ln.d_out, &ln.d_out_cap, cap + 64)) != BZ_OK) return rc2;
-        for (size_t i = 0; i < count; ++i)
-            if (lens[i]) copy_in(r->h_in[0] + in_off[i], ins[i], lens[i], 1);
-        if (total_in && (hipMemcpyAsync(ln.d_buf, r->h_in[0], (size_t)total_in, hipMemcpyHostToDevice, ln.st_io) != hipSuccess ||
+        lay.pack_into(r->h_in[0], [](u8 *d, const u8 *src, size_t n) { copy_in(d, src, n, 1); });
+        if (lay.total && (hipMemcpyAsync(ln.d_buf, r->h_in[0], (size_t)lay.total, hipMemcpyHostToDevice, ln.st_io) != hipSuccess ||
                          hipStreamSynchronize(ln.st_io) != hipSuccess))
             return BZ_E_UNEXPECTED;
         (void)bz_gpu_engine_set_verify(ln.g, env_verify() ? 1 : 0); // (a lane's engine may come from the cache: BZ_VERIFY decides here)
-        rc2 = bz_gpu_encode_batch_device(ln.g, level, ln.d_buf, in_off.data(), in_len.data(), count, ln.d_out, cap, out_off, out_len);
+        rc2 = bz_gpu_encode_batch_device(ln.g, level, ln.d_buf, lay.in_off.data(), lay.in_len.data(), count, ln.d_out, cap, out_off, out_len);
         if (rc2 != BZ_OK) return rc2;
         total_out = out_off[count - 1] + ((out_len[count - 1] + 3u) & ~(u64)3);
         if ((rc2 = grow_pinned(&ln.h_out, &ln.h_out_cap, (size_t)total_out)) != BZ_OK) return rc2;

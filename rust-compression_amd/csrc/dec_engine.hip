@@ -1400,76 +1400,18 @@ extern "C" int bz_gpu_last_decode_batch_stats(bz_gpu_engine *g, uint64_t out[4])
     return BZ_OK;
 }
 
-// Two engines per device are kept between one-shot calls and contexts (its decode workspace -- 13 MB per block in flight -- and the
-// buffer for the compressed bytes cost more to make than a GiB costs to decode); bz_release_cached_resources frees them.
-namespace {
-std::mutex g_dec_cache_mu;
-std::vector<std::pair<int, bz_gpu_engine *>> g_dec_cache;
-} // namespace
-static void dec_spare_bufs_clear();
-// prefer: 1 = an engine that has decoded before (it holds the decode workspace), 2 = one that has a Deflate workspace;
-// otherwise the engine that was put back last (two engines are kept since the streaming decoder has two lanes: taking the
-// OLDEST one made consecutive one-shot calls alternate between them, each paying for a workspace of its own)
-bz_gpu_engine *dec_cache_take(int device, int prefer)
-{
-    std::lock_guard<std::mutex> lk(g_dec_cache_mu);
-    size_t pick = ~(size_t)0;
-    for (size_t i = g_dec_cache.size(); i-- > 0;) {
-        if (g_dec_cache[i].first != device) continue;
-        const bz_gpu_engine *c = g_dec_cache[i].second;
-        const bool match = prefer == 1 ? c->dec != nullptr : (prefer == 2 ? c->df != nullptr : true);
-        if (pick == ~(size_t)0) pick = i; // (the newest one of the device)
-        if (match) {
-            pick = i;
-            break;
-        }
-    }
-    if (pick == ~(size_t)0) return nullptr;
-    bz_gpu_engine *g = g_dec_cache[pick].second;
-    g_dec_cache.erase(g_dec_cache.begin() + (ptrdiff_t)pick);
-    return g;
-}
-void dec_cache_put(int device, bz_gpu_engine *g)
-{
-    {
-        std::lock_guard<std::mutex> lk(g_dec_cache_mu);
-        size_t have = 0;
-        for (const auto &e : g_dec_cache) have += e.first == device ? 1 : 0;
-        if (have < 2) { // (two: the lanes of a streaming context)
-            g_dec_cache.emplace_back(device, g);
-            return;
-        }
-    }
-    bz_gpu_engine_destroy(g); // (more calls side by side on one device: their engines are not kept)
-}
-void dec_release_cached()
-{
-    std::vector<std::pair<int, bz_gpu_engine *>> all;
-    {
-        std::lock_guard<std::mutex> lk(g_dec_cache_mu);
-        all.swap(g_dec_cache);
-    }
-    for (auto &e : all) {
-        (void)hipSetDevice(e.first);
-        bz_gpu_engine_destroy(e.second);
-    }
-    dec_spare_bufs_clear();
-}
-
 extern "C" int bz_decode_buffer(int device, const uint8_t *in, size_t in_len, uint8_t **out, size_t *out_len)
 {
     if (!out || !out_len || (!in && in_len)) return BZ_E_PARAM;
     *out = nullptr;
     *out_len = 0;
     const double t_enter = dec_now_ms();
-    int caller_device = -1;
-    (void)hipGetDevice(&caller_device); // (put back on return: ADVICE r3, the same rule as the encoder's entry points)
-    bz_gpu_engine *g = dec_cache_take(device, 1);
-    int rc = g ? BZ_OK : bz_gpu_engine_create(&g, device, 0);
-    if (rc != BZ_OK) return rc;
+    EngineLease lease(device, 1, 0); // (a parked engine that has decoded before, or a new one; host_call.h)
+    if (lease.status() != BZ_OK) return lease.status();
+    bz_gpu_engine *g = lease.engine();
     HostBuf host;
     int verdict = BZ_OK;
-    rc = hipSetDevice(device) == hipSuccess ? g->dec_in.ensure(in_len + 64) : BZ_E_UNEXPECTED;
+    int rc = g->dec_in.ensure(in_len + 64);
     if (rc == BZ_OK) {
         // The decoded bytes leave batch by batch beside the kernels of the next batch (copy_pool.h: one copying thread, the
         // fresh pages of the caller's buffer touched on several threads in front of it); the compressed bytes go up in one
@@ -1490,9 +1432,7 @@ extern "C" int bz_decode_buffer(int device, const uint8_t *in, size_t in_len, ui
         }
     }
     if (dec_trace()) fprintf(stderr, "bz_decode_buffer: %zu -> %zu bytes, rc %d, done at %.1f (entered at %.1f)\n", in_len, host.len, rc, dec_now_ms(), t_enter);
-    if (rc == BZ_OK) dec_cache_put(device, g);
-    else bz_gpu_engine_destroy(g); // (an engine that met an infrastructure error is not kept)
-    if (caller_device >= 0) (void)hipSetDevice(caller_device);
+    lease.settle(rc); // (`verdict`, the stream's, is not the engine's business)
     if (rc != BZ_OK) return rc;
     // the bytes in front of an error are handed over too, as the reference's iterator yields them
     *out_len = host.len;
@@ -1502,7 +1442,7 @@ extern "C" int bz_decode_buffer(int device, const uint8_t *in, size_t in_len, ui
     return verdict;
 }
 
-// The same for many independent streams (mirrors bz_encode_batch): the entries packed at 4-byte-aligned offsets, one
+// The same for many independent streams: the entries packed at 4-byte-aligned offsets (BatchLayout, host_call.h), one
 // upload, decode_batch_core on a cached engine, the bytes down group by group into ONE buffer.
 extern "C" int bz_decode_batch(int device, const uint8_t *const *ins, const size_t *lens, size_t count, uint8_t **out,
                                uint64_t *out_off, uint64_t *out_len, int32_t *verdict)
@@ -1514,37 +1454,27 @@ extern "C" int bz_decode_batch(int device, const uint8_t *const *ins, const size
         return *out ? BZ_OK : BZ_E_NOMEM;
     }
     if (!ins || !lens || !out_off || !out_len || !verdict || count > 0xFFFFFFF0ull) return BZ_E_PARAM;
-    std::vector<u64> off(count), len(count);
-    u64 total = 0;
-    for (size_t i = 0; i < count; ++i) {
-        if (!ins[i] && lens[i]) return BZ_E_PARAM;
-        off[i] = total;
-        len[i] = lens[i];
-        total = (total + lens[i] + 3ull) & ~3ull;
-    }
-    int caller_device = -1;
-    (void)hipGetDevice(&caller_device);
-    bz_gpu_engine *g = dec_cache_take(device, 1);
-    int rc = g ? BZ_OK : bz_gpu_engine_create(&g, device, 0);
-    if (rc != BZ_OK) return rc;
+    const BatchLayout lay(ins, lens, count, 4);
+    if (lay.status != BZ_OK) return lay.status;
+    EngineLease lease(device, 1, 0);
+    if (lease.status() != BZ_OK) return lease.status();
+    bz_gpu_engine *g = lease.engine();
     HostBuf host;
-    rc = hipSetDevice(device) == hipSuccess ? g->dec_in.ensure((size_t)total + 64) : BZ_E_UNEXPECTED;
+    int rc = g->dec_in.ensure((size_t)lay.total + 64);
     if (rc == BZ_OK) {
         // packed on the host first: one upload, whatever the number of entries
-        std::vector<u8> packed((size_t)total, 0);
-        for (size_t i = 0; i < count; ++i)
-            if (lens[i]) memcpy(packed.data() + off[i], ins[i], lens[i]);
+        std::vector<u8> packed((size_t)lay.total, 0);
+        lay.pack_into(packed.data());
         rc = BZ_E_UNEXPECTED;
-        if ((!total || hipMemcpyAsync(g->dec_in.p, packed.data(), (size_t)total, hipMemcpyHostToDevice, g->st) == hipSuccess) &&
+        if ((!lay.total || hipMemcpyAsync(g->dec_in.p, packed.data(), (size_t)lay.total, hipMemcpyHostToDevice, g->st) == hipSuccess) &&
             hipStreamSynchronize(g->st) == hipSuccess) {
             Sink o;
             o.host = &host;
-            rc = decode_batch_core(g, static_cast<const u8 *>(g->dec_in.p), off.data(), len.data(), count, o, out_off, out_len, verdict);
+            rc = decode_batch_core(g, static_cast<const u8 *>(g->dec_in.p), lay.in_off.data(), lay.in_len.data(), count, o, out_off, out_len,
+                                   verdict);
         }
     }
-    if (rc == BZ_OK) dec_cache_put(device, g);
-    else bz_gpu_engine_destroy(g); // (an engine that met an infrastructure error is not kept)
-    if (caller_device >= 0) (void)hipSetDevice(caller_device);
+    lease.settle(rc); // (the entries' verdicts are not the engine's business)
     if (rc != BZ_OK) return rc;
     uint8_t *h = host.len ? host.release() : (uint8_t *)malloc(1);
     if (!h) return BZ_E_NOMEM;
@@ -1640,7 +1570,7 @@ struct DecSeg { // decoded bytes of one sub-batch, handed out from `pos` on
 // are touched already); bz_release_cached_resources frees them with the engines.
 static std::mutex g_dec_spare_mu;
 static std::vector<ByteBuf> g_dec_spare_bufs;
-static void dec_spare_bufs_clear()
+void dec_spare_bufs_clear()
 {
     std::vector<ByteBuf> all;
     {
@@ -1735,13 +1665,13 @@ static void dec_process(bz_dec *d, bz_dec::Lane &ln, DecJob &j, u64 no)
         return d->out_turn == no && !d->done;
     };
     if (!ln.g) { // (an engine kept by an earlier one-shot call or context, with its workspace, or a new one)
-        ln.g = dec_cache_take(d->device, 1);
-        const int rc = ln.g ? BZ_OK : bz_gpu_engine_create(&ln.g, d->device, 0);
-        if (rc != BZ_OK) {
+        EngineLease lease(d->device, 1, 0);
+        if (lease.status() != BZ_OK) {
             pass_chain();
-            if (wait_out_turn()) finish(rc);
+            if (wait_out_turn()) finish(lease.status());
             return;
         }
+        ln.g = lease.release(); // (the lane holds it until bz_dec_destroy ends it through a lease that adopts it)
     }
     const double t0 = dec_now_ms();
     // the device holds [carry | new bytes]: two uploads, no copy of the chunk on the host; room for a whole chunk and a
@@ -2049,8 +1979,6 @@ extern "C" size_t bz_dec_pending(const bz_dec *d)
 extern "C" void bz_dec_destroy(bz_dec *d)
 {
     if (!d) return;
-    int caller_device = -1;
-    (void)hipGetDevice(&caller_device);
     {
         std::lock_guard<std::mutex> lk(d->mu);
         d->stop = true;
@@ -2066,14 +1994,12 @@ extern "C" void bz_dec_destroy(bz_dec *d)
     for (DecSeg *sg : d->spare_segs) delete sg;
     for (auto &ln : d->lane) {
         if (!ln.g) continue;
-        (void)hipSetDevice(d->device);
+        EngineLease lease(d->device, ln.g);
         ln.d_in.release();
         // (kept for the next context or one-shot call unless the context met an infrastructure error)
         const bool data_verdict = d->verdict == BZ_OK || d->verdict == BZ_E_DATA || d->verdict == BZ_E_MAGIC_FIRST || d->verdict == BZ_E_MAGIC ||
                                   d->verdict == BZ_E_EOF;
-        if (data_verdict) dec_cache_put(d->device, ln.g);
-        else bz_gpu_engine_destroy(ln.g);
+        lease.settle(data_verdict ? BZ_OK : d->verdict);
     }
-    if (caller_device >= 0) (void)hipSetDevice(caller_device);
     delete d;
 }

@@ -49,6 +49,55 @@ void df_workspace_free(DfWorkspace *w)
     delete w;
 }
 
+// the engine's Deflate workspace with its events, made by the first call that needs it; selects the engine's device
+static int df_workspace(bz_gpu_engine *g, DfWorkspace **out)
+{
+    HIPCHK(hipSetDevice(g->device));
+    if (!g->df) g->df = new DfWorkspace();
+    DfWorkspace *w = g->df;
+    if (!w->ev_ready) {
+        for (hipEvent_t &e : w->ev) HIPCHK(hipEventCreate(&e));
+        for (hipEvent_t &e : w->evq) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        w->ev_ready = true;
+    }
+    *out = w;
+    return BZ_OK;
+}
+
+// ev[0..6] as six stage times in seconds (five stages and the whole), assigned to t[] or added to it
+static void df_stage_times(const DfWorkspace *w, double t[6], bool add)
+{
+    for (int i = 0; i < 6; ++i) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, w->ev[i < 5 ? i : 0], w->ev[i < 5 ? i + 1 : 6]);
+        t[i] = (add ? t[i] : 0.0) + ms * 1e-3;
+    }
+}
+
+// The buffers that one stream (df_encode_core) and a sub-batch of one-block inputs (df_batch_run) size alike: `positions`
+// bytes go through the chain sort, the match kernel and the parse, in `tiles` tiles with a canonical orbit each (0: the
+// parse by doubling has none), for at most `blocks` blocks and `stream_bytes` bytes of stream.
+static int df_reserve_pipeline(DfWorkspace *w, u64 positions, u32 tiles, size_t blocks, size_t stream_bytes)
+{
+    const u64 npad = positions + 16, nchunks = df_chunks(positions);
+    const u64 nsort = nchunks * kChunkStride + 16; // words of a sorted-position array
+    int rc;
+    if ((rc = w->keys_in.ensure(npad * 2)) != BZ_OK) return rc;                           // step[]
+    if ((rc = w->vals_in.ensure((nsort > npad ? nsort : npad) * 4)) != BZ_OK) return rc;  // pass 0 output, later M[]
+    if ((rc = w->vals_out.ensure((nsort > npad ? nsort : npad) * 4)) != BZ_OK) return rc; // sorted positions, later code[]
+    if ((rc = w->sort_tmp.ensure((nchunks * kChunkTiles + 1) * 256 * 4)) != BZ_OK) return rc; // per-tile digit counts
+    if ((rc = w->keys_out.ensure(2 * (nchunks + 1) * 256 * 4)) != BZ_OK) return rc;       // per-chunk digit bases, both passes
+    if (tiles && (rc = w->canon.ensure((size_t)tiles * 64 * 8 + 64)) != BZ_OK) return rc; // a tile's canonical orbit, one bit per position
+    if ((rc = w->bitmap.ensure((positions / 64 + 8) * 8)) != BZ_OK) return rc;
+    if ((rc = w->nb.ensure(64)) != BZ_OK) return rc;
+    if ((rc = w->blocks.ensure(blocks * sizeof(DfBlock))) != BZ_OK) return rc;
+    if ((rc = w->lens.ensure(blocks * 320)) != BZ_OK) return rc;
+    if ((rc = w->hdr.ensure(blocks * kHdrWords * 4)) != BZ_OK) return rc;
+    if ((rc = w->lm.ensure(blocks * kDfLmWords * 4)) != BZ_OK) return rc;
+    if ((rc = w->total.ensure(128)) != BZ_OK) return rc; // the stream's bit count, the chain's state, its pieces' block counts
+    return w->stream.ensure(stream_bytes + 64);
+}
+
 extern "C" size_t df_encode_bound(size_t n)
 {
     // stored blocks are the worst case: 5 bytes per 0xFFFF, plus container, plus word slack for the bit writer
@@ -77,6 +126,12 @@ static u32 gf_xpow8_reflected(u64 nbytes) // x^(8 * nbytes) mod P
         nbytes >>= 1;
     }
     return r;
+}
+static DfCrcShifts df_crc_shifts() // x^(8 * 256 * 2^k): what the device folds a piece's sub-pieces with
+{
+    DfCrcShifts xk;
+    for (u32 k = 0; k < 8; ++k) xk.x[k] = gf_xpow8_reflected(256ull << k);
+    return xk;
 }
 
 // dict (host memory, may be NULL): Inflater::with_dict / ZlibEncoder::with_dict (deflate/encoder.rs:134-153,
@@ -129,15 +184,10 @@ static int df_encode_core(bz_gpu_engine *g, int kind, const u8 *d_in, u64 n, con
     if (n >= (1ull << 31) - kWin) return BZ_E_PARAM; // positions and bit offsets are sized for < 2 GiB per call
     if (dict_len && kind == 2) return BZ_E_PARAM;    // GZipEncoder has no with_dict
     if (seg.dl0 > kBlockMax || seg.dl0 > seg.prior) return BZ_E_PARAM;
-    HIPCHK(hipSetDevice(g->device));
-    if (!g->df) g->df = new DfWorkspace();
-    DfWorkspace *w = g->df;
+    int rc;
+    DfWorkspace *w = nullptr;
+    if ((rc = df_workspace(g, &w)) != BZ_OK) return rc;
     hipStream_t st = g->st;
-    if (!w->ev_ready) {
-        for (hipEvent_t &e : w->ev) HIPCHK(hipEventCreate(&e));
-        for (hipEvent_t &e : w->evq) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        w->ev_ready = true;
-    }
     // history in front of the segment: the last 32 KiB of (dictionary, then the stream so far)
     const u64 hist_dev = seg.prior < kWin ? seg.prior : kWin;
     const u64 hist_dict = dict_len < kWin - hist_dev ? dict_len : kWin - hist_dev;
@@ -153,14 +203,6 @@ static int df_encode_core(bz_gpu_engine *g, int kind, const u8 *d_in, u64 n, con
     for (u32 c : counts) { tab_words += (size_t)c * kEntries; ent_words += c + 8; }
     const u32 bcap = (u32)(n / (kBlockMax - 300) + 2);
 
-    int rc;
-    const u64 nchunks = df_chunks(nall);
-    const u64 nsort = nchunks * kChunkStride + 16; // words of a sorted-position array
-    if ((rc = w->keys_in.ensure(npad * 2)) != BZ_OK) return rc;                          // step[]
-    if ((rc = w->vals_in.ensure((nsort > npad ? nsort : npad) * 4)) != BZ_OK) return rc;  // pass 0 output, later M[]
-    if ((rc = w->vals_out.ensure((nsort > npad ? nsort : npad) * 4)) != BZ_OK) return rc; // sorted positions, later code[]
-    if ((rc = w->sort_tmp.ensure((nchunks * kChunkTiles + 1) * 256 * 4)) != BZ_OK) return rc; // per-tile digit counts
-    if ((rc = w->keys_out.ensure(2 * (nchunks + 1) * 256 * 4)) != BZ_OK) return rc;       // per-chunk digit bases, both passes
     // BZ_DF_MATCH=walk: the chain-walking match kernel of rounds 1 and 2 (k_df_prev + k_df_match) instead of the one
     // that reads the candidates off the sorted order (k_df_match2); same match words either way
     const char *mv = getenv("BZ_DF_MATCH");
@@ -169,25 +211,17 @@ static int df_encode_core(bz_gpu_engine *g, int kind, const u8 *d_in, u64 n, con
     // the canonical orbits (k_df_tile_orbit / k_df_mark2); same code words either way
     const char *pv = getenv("BZ_DF_PARSE");
     const bool doubling = pv && strcmp(pv, "doubling") == 0;
-    if (!doubling && (rc = w->canon.ensure((size_t)ntiles * 64 * 8 + 64)) != BZ_OK) return rc; // a tile's canonical orbit, one bit per position
+    const size_t bound = df_encode_bound(n);
+    if ((rc = df_reserve_pipeline(w, nall, doubling ? 0u : ntiles, bcap, bound)) != BZ_OK) return rc;
     if (walk) {
-        if ((rc = w->est.ensure(nsort * 2)) != BZ_OK) return rc;  // hashes of the sorted positions
+        if ((rc = w->est.ensure((df_chunks(nall) * kChunkStride + 16) * 2)) != BZ_OK) return rc; // hashes of the sorted positions
         if ((rc = w->prevd.ensure(npad * 4)) != BZ_OK) return rc; // per position: chain distance | chain length << 16
     }
     if (hist && (rc = w->concat.ensure(nall + 64)) != BZ_OK) return rc;
     if ((rc = w->tabs.ensure(tab_words * 2 + 64)) != BZ_OK) return rc;
     if ((rc = w->ents.ensure(ent_words * 2 + 64)) != BZ_OK) return rc;
     if ((rc = w->bstart.ensure(((size_t)bcap + 2) * 8)) != BZ_OK) return rc;
-    if ((rc = w->bitmap.ensure((n / 64 + 8) * 8)) != BZ_OK) return rc;
-    if ((rc = w->nb.ensure(64)) != BZ_OK) return rc;
-    if ((rc = w->blocks.ensure((size_t)bcap * sizeof(DfBlock))) != BZ_OK) return rc;
-    if ((rc = w->lens.ensure((size_t)bcap * 320)) != BZ_OK) return rc;
-    if ((rc = w->hdr.ensure((size_t)bcap * kHdrWords * 4)) != BZ_OK) return rc;
-    if ((rc = w->lm.ensure((size_t)bcap * kDfLmWords * 4)) != BZ_OK) return rc;
-    if ((rc = w->total.ensure(128)) != BZ_OK) return rc; // the stream's bit count, the chain's state, its pieces' block counts
     if ((rc = w->part_res.ensure(sizeof(DfPartRes))) != BZ_OK) return rc;
-    const size_t bound = df_encode_bound(n);
-    if ((rc = w->stream.ensure(bound + 64)) != BZ_OK) return rc;
     const u64 ntot = seg.prior + n; // bytes the container's checksums cover
     const u32 npieces = (u32)((ntot + kSumPiece - 1) / kSumPiece);
     if (kind != 0) {
@@ -308,9 +342,8 @@ static int df_encode_core(bz_gpu_engine *g, int kind, const u8 *d_in, u64 n, con
                        w->hdr.as<u32>(), w->stream.as<u32>()) != 0)
         return BZ_E_UNEXPECTED;
     if (kind != 0 && seg.tail) {
-        DfCrcShifts xk;
-        for (u32 k = 0; k < 8; ++k) xk.x[k] = gf_xpow8_reflected(256ull << k);
-        if (df_launch_sums(st, d_in - seg.prior, ntot, w->asum.as<u64>(), w->bsum.as<u64>(), w->crc.as<u32>(), w->crc.as<u32>() + npieces + 1, xk) != 0)
+        if (df_launch_sums(st, d_in - seg.prior, ntot, w->asum.as<u64>(), w->bsum.as<u64>(), w->crc.as<u32>(), w->crc.as<u32>() + npieces + 1,
+                           df_crc_shifts()) != 0)
             return BZ_E_UNEXPECTED;
     }
     HIPCHK(hipEventRecord(w->ev[5], st));
@@ -406,16 +439,7 @@ static int df_encode_core(bz_gpu_engine *g, int kind, const u8 *d_in, u64 n, con
     }
     HIPCHK(hipEventRecord(w->ev[6], st));
     HIPCHK(hipStreamSynchronize(st));
-    for (int i = 0; i < 5; ++i) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, w->ev[i], w->ev[i + 1]);
-        w->t_stage[i] = ms * 1e-3;
-    }
-    {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, w->ev[0], w->ev[6]);
-        w->t_stage[5] = ms * 1e-3;
-    }
+    df_stage_times(w, w->t_stage, false);
     // statistics of the last call (tests, bench): counted by k_df_part_tail; the block list itself is fetched when asked for
     w->h_nb = nb;
     w->h_fetched = false;
@@ -554,7 +578,7 @@ static int df_batch_run(bz_gpu_engine *g, int kind, const u8 *d_in, const uint64
 {
     DfWorkspace *w = g->df;
     hipStream_t st = g->st;
-    const u64 nimg = (u64)ntiles * kPTile, npad = nimg + 16;
+    const u64 nimg = (u64)ntiles * kPTile;
     std::vector<DfSlot> slots(ns);
     std::vector<u32> tile_slot(ntiles);
     std::vector<u64> bse(2 * (size_t)ns);
@@ -573,25 +597,10 @@ static int df_batch_run(bz_gpu_engine *g, int kind, const u8 *d_in, const uint64
         }
     }
     int rc;
-    const u64 nchunks = df_chunks(nimg);
-    const u64 nsort = nchunks * kChunkStride + 16;
+    if ((rc = df_reserve_pipeline(w, nimg, ntiles, ns, bound)) != BZ_OK) return rc;
     if ((rc = w->concat.ensure(nimg + 64)) != BZ_OK) return rc;                            // the image
-    if ((rc = w->keys_in.ensure(npad * 2)) != BZ_OK) return rc;                            // step[]
-    if ((rc = w->vals_in.ensure((nsort > npad ? nsort : npad) * 4)) != BZ_OK) return rc;   // pass 0 output, later M[]
-    if ((rc = w->vals_out.ensure((nsort > npad ? nsort : npad) * 4)) != BZ_OK) return rc;  // sorted positions, later code[]
-    if ((rc = w->sort_tmp.ensure((nchunks * kChunkTiles + 1) * 256 * 4)) != BZ_OK) return rc;
-    if ((rc = w->keys_out.ensure(2 * (nchunks + 1) * 256 * 4)) != BZ_OK) return rc;
-    if ((rc = w->canon.ensure((size_t)ntiles * 64 * 8 + 64)) != BZ_OK) return rc;
     if ((rc = w->tabs.ensure((size_t)ntiles * kEntries * 2 + 64)) != BZ_OK) return rc;
     if ((rc = w->ents.ensure(((size_t)ntiles + 8) * 2 + 64)) != BZ_OK) return rc;
-    if ((rc = w->bitmap.ensure((nimg / 64 + 8) * 8)) != BZ_OK) return rc;
-    if ((rc = w->nb.ensure(64)) != BZ_OK) return rc;
-    if ((rc = w->blocks.ensure((size_t)ns * sizeof(DfBlock))) != BZ_OK) return rc;
-    if ((rc = w->lens.ensure((size_t)ns * 320)) != BZ_OK) return rc;
-    if ((rc = w->hdr.ensure((size_t)ns * kHdrWords * 4)) != BZ_OK) return rc;
-    if ((rc = w->lm.ensure((size_t)ns * kDfLmWords * 4)) != BZ_OK) return rc;
-    if ((rc = w->total.ensure(128)) != BZ_OK) return rc;
-    if ((rc = w->stream.ensure(bound + 64)) != BZ_OK) return rc;
     if ((rc = w->b_slots.ensure((size_t)ns * sizeof(DfSlot))) != BZ_OK) return rc;
     if ((rc = w->b_tile_slot.ensure((size_t)ntiles * 4)) != BZ_OK) return rc;
     if ((rc = w->b_bse.ensure((size_t)ns * 16)) != BZ_OK) return rc;
@@ -632,9 +641,7 @@ static int df_batch_run(bz_gpu_engine *g, int kind, const u8 *d_in, const uint64
     if (df_launch_emit_batch(st, image, code, d_bse, w->nb.as<u32>(), ns, w->blocks.as<DfBlock>(), w->lens.as<u8>(), w->hdr.as<u32>(),
                              w->stream.as<u32>()) != 0)
         return BZ_E_UNEXPECTED;
-    DfCrcShifts xk;
-    for (u32 k = 0; k < 8; ++k) xk.x[k] = gf_xpow8_reflected(256ull << k);
-    if (df_launch_batch_wrap(st, image, d_slots, ns, w->blocks.as<DfBlock>(), w->b_outs.as<DfBatchOut>(), kind, xk, w->stream.as<u8>(),
+    if (df_launch_batch_wrap(st, image, d_slots, ns, w->blocks.as<DfBlock>(), w->b_outs.as<DfBatchOut>(), kind, df_crc_shifts(), w->stream.as<u8>(),
                              w->b_stats.as<u32>()) != 0)
         return BZ_E_UNEXPECTED;
     HIPCHK(hipEventRecord(w->ev[5], st));
@@ -656,16 +663,7 @@ static int df_batch_run(bz_gpu_engine *g, int kind, const u8 *d_in, const uint64
     }
     for (int i = 0; i < 5; ++i) w->batch_stats[3 + i] += bst[i];
     HIPCHK(hipStreamSynchronize(st)); // (the workspace is free for the next sub-batch, the events are over)
-    for (int i = 0; i < 5; ++i) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, w->ev[i], w->ev[i + 1]);
-        t_acc[i] += ms * 1e-3;
-    }
-    {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, w->ev[0], w->ev[6]);
-        t_acc[5] += ms * 1e-3;
-    }
+    df_stage_times(w, t_acc, true);
     *used = total;
     return BZ_OK;
 }
@@ -698,14 +696,9 @@ extern "C" int df_gpu_encode_batch_device(bz_gpu_engine *g, int kind, const void
         in_end = h_in_off[i] + h_in_len[i];
     }
     if (in_end && !d_in) return BZ_E_PARAM;
-    HIPCHK(hipSetDevice(g->device));
-    if (!g->df) g->df = new DfWorkspace();
-    DfWorkspace *w = g->df;
-    if (!w->ev_ready) {
-        for (hipEvent_t &e : w->ev) HIPCHK(hipEventCreate(&e));
-        for (hipEvent_t &e : w->evq) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        w->ev_ready = true;
-    }
+    DfWorkspace *w = nullptr;
+    const int wrc = df_workspace(g, &w);
+    if (wrc != BZ_OK) return wrc;
     for (u64 &s : w->batch_stats) s = 0;
     const u8 *in8 = static_cast<const u8 *>(d_in);
     u8 *out8 = static_cast<u8 *>(d_out);
@@ -757,8 +750,28 @@ extern "C" int df_gpu_encode_batch_device(bz_gpu_engine *g, int kind, const void
     return BZ_OK;
 }
 
-// The host form (mirrors bz_encode_batch): the inputs packed at 16-byte-aligned offsets, one upload, one device call on an
-// engine of the Deflate cache, one download.
+// ---- the host-to-host forms: an engine of the cache for the length of the call (EngineLease, host_call.h) ----------
+// A device number out of range is BZ_E_NOGPU for the entry points that ask here first (df_encode_batch, df_decode_batch and
+// with it df_decode_buffer, df_enc_create); the others pass on what bz_gpu_engine_create answers (BZ_E_PARAM).
+static int df_device_in_range(int device)
+{
+    int ndev = 0;
+    return hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && device >= 0 && device < ndev ? BZ_OK : BZ_E_NOGPU;
+}
+// the result: `total` bytes of device memory in a malloc'ed block (bz_free), one byte for none
+static int df_download(uint8_t **out, const void *d_src, size_t total)
+{
+    uint8_t *h = (uint8_t *)malloc(total ? total : 1);
+    if (!h) return BZ_E_NOMEM;
+    if (total && hipMemcpy(h, d_src, total, hipMemcpyDeviceToHost) != hipSuccess) {
+        free(h);
+        return BZ_E_UNEXPECTED;
+    }
+    *out = h;
+    return BZ_OK;
+}
+
+// Many inputs: packed at 16-byte-aligned offsets (BatchLayout), one upload, one device call, one download.
 extern "C" int df_encode_batch(int kind, int device, const uint8_t *const *ins, const size_t *lens, size_t count, uint8_t **out,
                                uint64_t *out_off, uint64_t *out_len)
 {
@@ -766,53 +779,28 @@ extern "C" int df_encode_batch(int kind, int device, const uint8_t *const *ins, 
     *out = nullptr;
     if (kind < 0 || kind > 2) return BZ_E_PARAM;
     if (count && (!ins || !lens || !out_off || !out_len)) return BZ_E_PARAM;
-    for (size_t i = 0; i < count; ++i)
-        if (lens[i] && !ins[i]) return BZ_E_PARAM;
+    const BatchLayout lay(ins, lens, count, 16);
+    if (lay.status != BZ_OK) return lay.status;
     if (count == 0) {
         *out = (uint8_t *)malloc(1);
         return *out ? BZ_OK : BZ_E_NOMEM;
     }
-    std::vector<uint64_t> in_off(count), in_len(count);
-    u64 total_in = 0;
-    for (size_t i = 0; i < count; ++i) {
-        in_off[i] = total_in;
-        in_len[i] = lens[i];
-        total_in += ((u64)lens[i] + 15u) & ~(u64)15;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return BZ_E_NOGPU;
-    int caller_device = -1;
-    (void)hipGetDevice(&caller_device);
-    bz_gpu_engine *g = dec_cache_take(device, 2);
-    int rc = g ? BZ_OK : bz_gpu_engine_create(&g, device, 1);
-    if (rc != BZ_OK) return rc;
-    const size_t cap = df_encode_batch_bound(in_len.data(), count);
-    uint8_t *h = nullptr;
-    std::vector<uint8_t> packed((size_t)total_in + 16);
-    for (size_t i = 0; i < count; ++i)
-        if (lens[i]) memcpy(packed.data() + in_off[i], ins[i], lens[i]);
-    rc = hipSetDevice(device) == hipSuccess ? BZ_OK : BZ_E_UNEXPECTED;
-    if (rc == BZ_OK) rc = g->dec_in.ensure((size_t)total_in + 64);
+    if (df_device_in_range(device) != BZ_OK) return BZ_E_NOGPU;
+    EngineLease lease(device, 2, 1);
+    if (lease.status() != BZ_OK) return lease.status();
+    bz_gpu_engine *g = lease.engine();
+    const size_t cap = df_encode_batch_bound(lay.in_len.data(), count);
+    std::vector<uint8_t> packed((size_t)lay.total + 16);
+    lay.pack_into(packed.data());
+    int rc = g->dec_in.ensure((size_t)lay.total + 64);
     if (rc == BZ_OK) rc = g->oneshot_out.ensure(cap + 64);
-    if (rc == BZ_OK && total_in && hipMemcpy(g->dec_in.p, packed.data(), (size_t)total_in, hipMemcpyHostToDevice) != hipSuccess)
+    if (rc == BZ_OK && lay.total && hipMemcpy(g->dec_in.p, packed.data(), (size_t)lay.total, hipMemcpyHostToDevice) != hipSuccess)
         rc = BZ_E_UNEXPECTED;
-    if (rc == BZ_OK) rc = df_gpu_encode_batch_device(g, kind, g->dec_in.p, in_off.data(), in_len.data(), count, g->oneshot_out.p, cap, out_off, out_len);
-    if (rc == BZ_OK) {
-        const size_t total_out = (size_t)(out_off[count - 1] + ((out_len[count - 1] + 3u) & ~(u64)3));
-        h = (uint8_t *)malloc(total_out ? total_out : 1);
-        if (!h) rc = BZ_E_NOMEM;
-        else if (hipMemcpy(h, g->oneshot_out.p, total_out, hipMemcpyDeviceToHost) != hipSuccess) {
-            free(h);
-            h = nullptr;
-            rc = BZ_E_UNEXPECTED;
-        }
-    }
-    if (rc == BZ_OK) dec_cache_put(device, g);
-    else bz_gpu_engine_destroy(g); // (an engine that met an error is not kept)
-    if (caller_device >= 0) (void)hipSetDevice(caller_device);
-    if (rc != BZ_OK) return rc;
-    *out = h;
-    return BZ_OK;
+    if (rc == BZ_OK)
+        rc = df_gpu_encode_batch_device(g, kind, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), count, g->oneshot_out.p, cap, out_off, out_len);
+    if (rc == BZ_OK) rc = df_download(out, g->oneshot_out.p, (size_t)(out_off[count - 1] + ((out_len[count - 1] + 3u) & ~(u64)3)));
+    lease.settle(rc);
+    return rc;
 }
 
 // ---- decode of many streams (section 5 of the header; kernels: k_inflate.hip) -------------------------------
@@ -837,16 +825,11 @@ static int df_decode_batch_core(bz_gpu_engine *g, int kind, const void *d_in, co
         in_end = h_in_off[i] + h_in_len[i];
     }
     if (in_end && !d_in) return BZ_E_PARAM;
-    HIPCHK(hipSetDevice(g->device));
-    if (!g->df) g->df = new DfWorkspace();
-    DfWorkspace *w = g->df;
-    if (!w->ev_ready) {
-        for (hipEvent_t &e : w->ev) HIPCHK(hipEventCreate(&e));
-        for (hipEvent_t &e : w->evq) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        w->ev_ready = true;
-    }
+    DfWorkspace *w = nullptr;
+    int rc = df_workspace(g, &w);
+    if (rc != BZ_OK) return rc;
     for (u64 &s : w->inf_stats) s = 0;
-    int rc = w->i_in.ensure(2 * count * sizeof(u64));
+    rc = w->i_in.ensure(2 * count * sizeof(u64));
     if (rc == BZ_OK) rc = w->i_ooff.ensure(count * sizeof(u64));
     if (rc == BZ_OK) rc = w->i_rec.ensure(count * sizeof(DfInfRec));
     if (rc != BZ_OK) return rc;
@@ -916,8 +899,8 @@ extern "C" int df_gpu_decode_batch_device(bz_gpu_engine *g, int kind, const void
     return df_decode_batch_core(g, kind, d_in, h_in_off, h_in_len, count, d_out, cap, nullptr, h_out_off, h_out_len, h_verdict);
 }
 
-// The host form (mirrors bz_decode_batch): the entries packed at 4-byte-aligned offsets, one upload, one device call on an
-// engine of the per-process cache (its output buffer sized between the two launches), one download.
+// Many streams: packed at 4-byte-aligned offsets (BatchLayout), one upload, one device call (the engine's output buffer
+// sized between its two launches), one download.
 extern "C" int df_decode_batch(int kind, int device, const uint8_t *const *ins, const size_t *lens, size_t count, uint8_t **out,
                                uint64_t *out_off, uint64_t *out_len, int32_t *verdict)
 {
@@ -925,53 +908,27 @@ extern "C" int df_decode_batch(int kind, int device, const uint8_t *const *ins, 
     *out = nullptr;
     if (kind < 0 || kind > 2) return BZ_E_PARAM;
     if (count && (!ins || !lens || !out_off || !out_len || !verdict)) return BZ_E_PARAM;
-    for (size_t i = 0; i < count; ++i)
-        if (lens[i] && !ins[i]) return BZ_E_PARAM;
+    const BatchLayout lay(ins, lens, count, 4);
+    if (lay.status != BZ_OK) return lay.status;
     if (count == 0) {
         *out = (uint8_t *)malloc(1);
         return *out ? BZ_OK : BZ_E_NOMEM;
     }
-    std::vector<uint64_t> in_off(count), in_len(count);
-    u64 total_in = 0;
-    for (size_t i = 0; i < count; ++i) {
-        in_off[i] = total_in;
-        in_len[i] = lens[i];
-        total_in += ((u64)lens[i] + 3u) & ~(u64)3;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return BZ_E_NOGPU;
-    int caller_device = -1;
-    (void)hipGetDevice(&caller_device);
-    bz_gpu_engine *g = dec_cache_take(device, 2);
-    int rc = g ? BZ_OK : bz_gpu_engine_create(&g, device, 1);
-    if (rc != BZ_OK) return rc;
-    uint8_t *h = nullptr;
-    std::vector<uint8_t> packed((size_t)total_in + 16);
-    for (size_t i = 0; i < count; ++i)
-        if (lens[i]) memcpy(packed.data() + in_off[i], ins[i], lens[i]);
-    rc = hipSetDevice(device) == hipSuccess ? BZ_OK : BZ_E_UNEXPECTED;
-    if (rc == BZ_OK) rc = g->dec_in.ensure((size_t)total_in + 64);
-    if (rc == BZ_OK && total_in && hipMemcpy(g->dec_in.p, packed.data(), (size_t)total_in, hipMemcpyHostToDevice) != hipSuccess)
+    if (df_device_in_range(device) != BZ_OK) return BZ_E_NOGPU;
+    EngineLease lease(device, 2, 1);
+    if (lease.status() != BZ_OK) return lease.status();
+    bz_gpu_engine *g = lease.engine();
+    std::vector<uint8_t> packed((size_t)lay.total + 16);
+    lay.pack_into(packed.data());
+    int rc = g->dec_in.ensure((size_t)lay.total + 64);
+    if (rc == BZ_OK && lay.total && hipMemcpy(g->dec_in.p, packed.data(), (size_t)lay.total, hipMemcpyHostToDevice) != hipSuccess)
         rc = BZ_E_UNEXPECTED;
     if (rc == BZ_OK)
-        rc = df_decode_batch_core(g, kind, g->dec_in.p, in_off.data(), in_len.data(), count, nullptr, 0, &g->oneshot_out, out_off, out_len, verdict);
-    if (rc == BZ_OK) {
-        size_t total_out = 0;
-        total_out = (size_t)(out_off[count - 1] + out_len[count - 1]);
-        h = (uint8_t *)malloc(total_out ? total_out : 1);
-        if (!h) rc = BZ_E_NOMEM;
-        else if (total_out && hipMemcpy(h, g->oneshot_out.p, total_out, hipMemcpyDeviceToHost) != hipSuccess) {
-            free(h);
-            h = nullptr;
-            rc = BZ_E_UNEXPECTED;
-        }
-    }
-    if (rc == BZ_OK) dec_cache_put(device, g);
-    else bz_gpu_engine_destroy(g); // (an engine that met an error is not kept)
-    if (caller_device >= 0) (void)hipSetDevice(caller_device);
-    if (rc != BZ_OK) return rc;
-    *out = h;
-    return BZ_OK;
+        rc = df_decode_batch_core(g, kind, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), count, nullptr, 0, &g->oneshot_out, out_off, out_len,
+                                  verdict);
+    if (rc == BZ_OK) rc = df_download(out, g->oneshot_out.p, (size_t)(out_off[count - 1] + out_len[count - 1]));
+    lease.settle(rc); // (the entries' verdicts are not the engine's business)
+    return rc;
 }
 
 // The batch of one: BZ_OK with the bytes, or the entry's verdict with the bytes in front of it (as bz_decode_buffer).
@@ -1087,19 +1044,16 @@ extern "C" int df_encode_buffer_dict(int kind, int device, const uint8_t *in, si
     if (!out || !out_len || (!in && in_len) || kind < 0 || kind > 2 || (!dict && dict_len)) return BZ_E_PARAM;
     *out = nullptr;
     *out_len = 0;
+    if (df_trace()) fprintf(stderr, "bz2_mi355x: df_encode_buffer entered at %.1f\n", df_now_ms());
     // (an engine per device is kept between one-shot calls, with its workspace and the two buffers below:
     // bz_release_cached_resources frees it)
-    int caller_device = -1;
-    (void)hipGetDevice(&caller_device);
-    if (df_trace()) fprintf(stderr, "bz2_mi355x: df_encode_buffer entered at %.1f\n", df_now_ms());
-    bz_gpu_engine *g = dec_cache_take(device, 2);
-    int rc = g ? BZ_OK : bz_gpu_engine_create(&g, device, 1);
-    if (rc != BZ_OK) return rc;
+    EngineLease lease(device, 2, 1);
+    if (lease.status() != BZ_OK) return lease.status();
+    bz_gpu_engine *g = lease.engine();
     const size_t cap = df_encode_bound(in_len) + 8;
     uint8_t *h = nullptr;
     size_t n_out = 0;
-    rc = hipSetDevice(device) == hipSuccess ? BZ_OK : BZ_E_UNEXPECTED;
-    if (rc == BZ_OK) rc = g->dec_in.ensure(in_len + 64);
+    int rc = g->dec_in.ensure(in_len + 64);
     if (rc == BZ_OK) rc = g->oneshot_out.ensure(cap);
     // Large inputs: the call's two copies run beside its kernels (copy_pool.h).  The input goes up in 32 MiB slices from one
     // thread, in order; the encode runs in parts (the bytes do not depend
@@ -1152,21 +1106,11 @@ extern "C" int df_encode_buffer_dict(int kind, int device, const uint8_t *in, si
             h = nullptr;
         }
     } else {
-    if (rc == BZ_OK && in_len && hipMemcpy(g->dec_in.p, in, in_len, hipMemcpyHostToDevice) != hipSuccess) rc = BZ_E_UNEXPECTED;
-    if (rc == BZ_OK) rc = df_gpu_encode_device_dict(g, kind, g->dec_in.p, in_len, dict, dict_len, g->oneshot_out.p, cap, &n_out);
-    if (rc == BZ_OK) {
-        h = (uint8_t *)malloc(n_out ? n_out : 1);
-        if (!h) rc = BZ_E_NOMEM;
-        else if (hipMemcpy(h, g->oneshot_out.p, n_out, hipMemcpyDeviceToHost) != hipSuccess) {
-            free(h);
-            h = nullptr;
-            rc = BZ_E_UNEXPECTED;
-        }
+        if (rc == BZ_OK && in_len && hipMemcpy(g->dec_in.p, in, in_len, hipMemcpyHostToDevice) != hipSuccess) rc = BZ_E_UNEXPECTED;
+        if (rc == BZ_OK) rc = df_gpu_encode_device_dict(g, kind, g->dec_in.p, in_len, dict, dict_len, g->oneshot_out.p, cap, &n_out);
+        if (rc == BZ_OK) rc = df_download(&h, g->oneshot_out.p, n_out);
     }
-    }
-    if (rc == BZ_OK) dec_cache_put(device, g);
-    else bz_gpu_engine_destroy(g); // (an engine that met an error is not kept)
-    if (caller_device >= 0) (void)hipSetDevice(caller_device);
+    lease.settle(rc);
     if (rc != BZ_OK) return rc;
     *out = h;
     *out_len = n_out;
@@ -1195,8 +1139,7 @@ struct df_enc {
 extern "C" int df_enc_create(df_enc **out, int kind, int device)
 {
     if (!out || kind < 0 || kind > 2) return BZ_E_PARAM;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return BZ_E_NOGPU;
+    if (df_device_in_range(device) != BZ_OK) return BZ_E_NOGPU;
     df_enc *e = new df_enc();
     e->kind = kind;
     e->device = device;
@@ -1215,17 +1158,9 @@ extern "C" int df_enc_create_dict(df_enc **out, int kind, int device, const uint
 extern "C" void df_enc_destroy(df_enc *e)
 {
     if (!e) return;
-    if (e->g) {
-        int caller_device = -1;
-        (void)hipGetDevice(&caller_device);
-        (void)hipSetDevice(e->device);
-        // kept, with its workspace, for the next context or one-shot call on the device -- unless the context met an
-        // infrastructure error (a sticky HIP error, a half-grown workspace): bz_decode_buffer, df_encode_buffer and
-        // bz_dec_destroy do the same
-        if (e->last_status == BZ_OK) dec_cache_put(e->device, e->g);
-        else bz_gpu_engine_destroy(e->g);
-        if (caller_device >= 0) (void)hipSetDevice(caller_device);
-    }
+    // (the engine is kept, with its workspace, for the next context or one-shot call on the device -- unless the context's
+    // last df_enc_end met an infrastructure error: the lease's rule, host_call.h)
+    if (e->g) EngineLease(e->device, e->g).settle(e->last_status);
     delete e;
 }
 
@@ -1250,28 +1185,21 @@ static int df_enc_end_impl(df_enc *e, int action);
 extern "C" int df_enc_end(df_enc *e, int action)
 {
     if (!e || action < 0 || action > 2) return BZ_E_PARAM;
-    int caller_device = -1;
-    (void)hipGetDevice(&caller_device);
-    const int rc = df_enc_end_impl(e, action);
-    e->last_status = rc;
-    if (caller_device >= 0) (void)hipSetDevice(caller_device);
-    return rc;
+    // flush() / finish() behind the final block do nothing (:636-660), nor does Run on a bare Inflater
+    if ((action == 0 && e->kind == 0) || e->finished) return e->last_status = BZ_OK;
+    // the context's engine: the one it holds, a parked one or a new one; it stays with the context (df_enc_destroy ends it)
+    EngineLease lease = e->g ? EngineLease(e->device, e->g) : EngineLease(e->device, 2, 0);
+    e->g = lease.release();
+    return e->last_status = lease.status() == BZ_OK ? df_enc_end_impl(e, action) : lease.status();
 }
 static int df_enc_end_impl(df_enc *e, int action)
 {
-    if (action == 0 && e->kind == 0) return BZ_OK;
-    if (e->finished) return BZ_OK; // flush() / finish() behind the final block do nothing (:636-660)
     // zlib / gzip: the container ends at the first None of the inner Inflater whatever the Action
     // (zlib/encoder.rs:146-150, gzip/encoder.rs:129-133): header + what the Inflater yields under this Action
     // (Run: the whole bytes of the blocks it has closed; Flush: the flushed segment) + the trailer over everything
     // the iterator handed over; afterwards the encoder yields None and leaves its caller's iterator alone.
     const bool ends_container = e->kind != 0;
     int rc;
-    if (!e->g) {
-        e->g = dec_cache_take(e->device, 2);
-        if (!e->g && (rc = bz_gpu_engine_create(&e->g, e->device, 0)) != BZ_OK) return rc;
-    }
-    HIPCHK(hipSetDevice(e->device));
     const size_t add = e->in.size();
     if (e->total + add + 64 > e->d_data.cap) { // grow, keeping the stream so far
         DevBuf bigger;

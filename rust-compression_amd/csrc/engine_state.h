@@ -4,6 +4,7 @@
 #include "../../include/bz2_mi355x.h"
 #include "bzgpu.h"
 #include "dev_buf.h"
+#include "host_call.h"
 
 #include <cstdio>
 #include <vector>
@@ -16,11 +17,9 @@ void dec_workspace_free(DecWorkspace *w);
 // returns an infrastructure status, the decoder's verdict in *verdict and the bytes it produced in *produced
 int dec_decode_for_verify(struct bz_gpu_engine *g, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap,
                           uint64_t *produced, int *verdict);
-// the engines the one-shot calls over host buffers keep between calls (bz_decode_buffer, df_encode_buffer; one per
-// device; bz_release_cached_resources frees them)
-struct bz_gpu_engine *dec_cache_take(int device, int prefer = 0);
-void dec_cache_put(int device, struct bz_gpu_engine *g);
-void dec_release_cached();
+// (the engines that calls and contexts of both codecs park between uses: dec_cache_take / dec_cache_put /
+// dec_release_cached, declared in host_call.h with the lease that is their one user, defined in engine_cache.hip)
+void dec_spare_bufs_clear(); // dec_engine.hip: the byte buffers finished bz_dec contexts leave for the next one
 struct DfWorkspace;
 void df_workspace_free(DfWorkspace *w);
 

@@ -44,6 +44,30 @@ def test_one_shot_calls_share_the_parked_engine(pkg, oracle):
         pkg.release_cached_resources()  # ... and the next round starts without one
 
 
+def test_batch_calls_share_the_parked_engine(pkg, oracle):
+    """The four batch forms in the rotation: each borrows an engine through the same lease as the one-shot calls
+    (csrc/host_call.h), so a bzip2 decode batch, a Deflate encode batch, a Deflate decode batch and a one-shot decode that
+    ends in a data verdict hand the engines on to one another; results are the oracle's streams or the inputs, entry by
+    entry, and the calling thread's current device is left as it was.  The 70 000-byte entry is more than one Deflate
+    block: the one-input path inside the Deflate batch."""
+    import torch
+    torch.cuda.set_device(0)
+    datas = [b"", b"a", _text(20_000, 3), _text(70_000, 4)]
+    bz = [oracle.encode(d, 9) for d in datas]
+    gz = [oracle.deflate_encode(d, pkg.GZIP) for d in datas]
+    for round_ in range(2):
+        assert pkg.compress_batch(datas) == bz
+        assert pkg.decompress_batch(bz) == [(d, 0) for d in datas]
+        assert pkg.deflate_compress_batch(datas, pkg.GZIP) == gz
+        assert pkg.deflate_decompress_batch(gz, pkg.GZIP) == [(d, 0) for d in datas]
+        # a truncated stream: a data verdict, and the engine it ran on is still good for the next batch
+        back, verdict = pkg.decompress(bz[3][:len(bz[3]) // 2])
+        assert verdict != 0 and datas[3].startswith(back)
+        assert pkg.decompress_batch(bz) == [(d, 0) for d in datas]
+        pkg.release_cached_resources()  # ... and the next round starts without one
+    assert torch.cuda.current_device() == 0
+
+
 def test_decode_buffer_hands_out_memory_free_takes(pkg, oracle):
     """bz_decode_buffer's result lives in posix_memalign'ed memory (2 MiB-aligned, huge pages asked for) from 4 MiB on and
     in malloc'ed memory below: bz_free (= free) takes both; an empty result is a 1-byte allocation."""
