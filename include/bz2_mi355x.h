@@ -680,9 +680,15 @@ void df_enc_destroy(df_enc *e);
  *    (src/deflate/decoder.rs, src/zlib/decoder.rs, src/gzip/decoder.rs) on
  *    streams that are well-formed; RFC 1951 / 1950 / 1952 decide everywhere else.
  *
- * Many independent streams in one call, one wave per stream; the parallelism is
- * over the entries, a single huge stream decodes at one wave's speed.  `kind` as
- * in section 4 (one kind per call, no preset dictionary).
+ * Many independent streams in one call, one wave per stream; an entry of
+ * BZ_DF_INF_SPLIT_KIB KiB or more (default 1024, 0 = never; read per call) is
+ * split: its compressed bytes are cut into pieces of BZ_DF_INF_PIECE_KIB KiB
+ * (default 16: profiles/r14_inflate_split.md), a search finds a block header in every piece,
+ * one wave decodes from each, and a chain keeps exactly the pieces that start
+ * where the piece in front of them ended (DESIGN_deflate.md, "One large stream
+ * across many waves").  A split entry gets the bytes, the length and the verdict
+ * of the one-wave path under every clause of the contract below.  `kind` as in
+ * section 4 (one kind per call, no preset dictionary).
  *
  * THE CONTRACT (DESIGN_deflate.md, "Decoding many streams in one call", says why
  * the reference's decoder cannot be the standard on malformed input):
@@ -736,6 +742,15 @@ int df_gpu_decode_batch_device(bz_gpu_engine *g, int kind, const void *d_in,
  * blocks decoded whole [2] stored [3] fixed [4] dynamic; [5] decoded bytes [6] compressed bytes consumed (to the end of
  * the stream or trailer, or to the failing code) [7] kernel launches. */
 int df_gpu_last_decode_batch_stats(bz_gpu_engine *g, uint64_t out[8]);
+/* The split entries of the last df_gpu_decode_batch_device call: [0] entries split [1] pieces with a candidate [2] pieces
+ * confirmed without repair (every entry's first piece is one) [3] repair rounds [4] output bytes decoded by the serial tail
+ * [5] bytes the writing launch left unresolved (their value lies in an earlier piece) [6] jump rounds [7] kernel launches
+ * of the split entries (not counted in df_gpu_last_decode_batch_stats [7]).  df_gpu_last_timings [0] / [1] / [2] include
+ * their search, sizes and repair / writing, jump rounds and gather / checksum. */
+int df_gpu_last_decode_split_stats(bz_gpu_engine *g, uint64_t out[8]);
+/* ... and their phases in seconds, summed over the split entries (a host clock around launches that are waited for):
+ * [0] search [1] sizes [2] chain and repair [3] writing [4] jump rounds [5] gather [6] checksum. */
+int df_gpu_last_decode_split_timings(bz_gpu_engine *g, double out_seconds[7]);
 /* The host form (mirrors bz_decode_batch): the entries are packed at 4-byte-aligned offsets, uploaded once and decoded by
  * one device call on an engine of the per-process cache; entry i's bytes are (*out)[out_off[i] .. + out_len[i]), its
  * verdict verdict[i]; *out is ONE malloc'ed buffer (release with bz_free; offsets are multiples of 16, relative to it).

@@ -96,7 +96,7 @@ EXPORTS = [
     "df_gpu_debug_blocks", "df_encode_buffer", "df_gpu_encode_device_dict", "df_encode_buffer_dict", "df_enc_create_dict",
     "df_enc_create", "df_enc_write", "df_enc_end", "df_enc_read", "df_enc_pending", "df_enc_destroy", "df_enc_finished",
     "df_encode_batch_bound", "df_gpu_encode_batch_device", "df_gpu_last_batch_stats", "df_encode_batch",
-    "df_gpu_decode_batch_device", "df_gpu_last_decode_batch_stats", "df_decode_batch", "df_decode_buffer",
+    "df_gpu_decode_batch_device", "df_gpu_last_decode_batch_stats", "df_gpu_last_decode_split_stats", "df_gpu_last_decode_split_timings", "df_decode_batch", "df_decode_buffer",
 ]
 
 
@@ -250,6 +250,8 @@ def lib():
     L.df_encode_batch.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, sz, C.POINTER(u8p), u64p, u64p]
     L.df_gpu_decode_batch_device.argtypes = [vp, C.c_int, vp, u64p, u64p, sz, vp, sz, u64p, u64p, i32p]
     L.df_gpu_last_decode_batch_stats.argtypes = [vp, u64p]
+    L.df_gpu_last_decode_split_stats.argtypes = [vp, u64p]
+    L.df_gpu_last_decode_split_timings.argtypes = [vp, C.POINTER(C.c_double)]
     L.df_decode_batch.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, sz, C.POINTER(u8p), u64p, u64p, i32p]
     L.df_decode_buffer.argtypes = [C.c_int, C.c_int, C.c_char_p, sz, C.POINTER(u8p), szp]
     _LIB = L
@@ -1129,6 +1131,23 @@ class GpuEngine:
         s = (C.c_uint64 * 8)()
         _check(lib().df_gpu_last_decode_batch_stats(self._h, s))
         return [int(x) for x in s]
+
+    def deflate_decode_split_stats(self):
+        """The entries of the last deflate_decode_batch_device call that were split across many waves: [0] entries split
+        [1] pieces with a candidate [2] pieces confirmed without repair [3] repair rounds [4] output bytes of the serial tail
+        [5] bytes left unresolved by the writing launch [6] jump rounds [7] kernel launches (df_gpu_last_decode_split_stats)."""
+        s = (C.c_uint64 * 8)()
+        _check(lib().df_gpu_last_decode_split_stats(self._h, s))
+        return [int(x) for x in s]
+
+    DEFLATE_DECODE_SPLIT_PHASES = ("search", "sizes", "repair", "writing", "jump_rounds", "gather", "checksum")
+
+    def deflate_decode_split_timings(self):
+        """Seconds per phase of the split entries of the last deflate_decode_batch_device call
+        (df_gpu_last_decode_split_timings)."""
+        t = (C.c_double * 7)()
+        _check(lib().df_gpu_last_decode_split_timings(self._h, t))
+        return dict(zip(self.DEFLATE_DECODE_SPLIT_PHASES, t))
 
     def deflate_timings(self):
         t = (C.c_double * 6)()

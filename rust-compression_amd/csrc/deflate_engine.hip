@@ -5,6 +5,7 @@
 // (zlib/encoder.rs:55-157), GZipEncoder (gzip/encoder.rs:50-135) driven with Action::Finish (and
 // Action::Run in front of it), with or without a preset dictionary (::with_dict), and -- for Inflater -- with
 // Action::Flush in the middle of a stream (a stream is then a sequence of byte-aligned SEGMENTS, df_enc_end).
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <utility>
@@ -17,6 +18,7 @@
 #include <sys/mman.h>
 #include <functional>
 #include "k_deflate.h"
+#include "inf_split.h"
 
 using namespace dfgpu;
 
@@ -27,6 +29,9 @@ struct DfWorkspace {
     u64 batch_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // df_gpu_last_batch_stats
     DevBuf i_in, i_ooff, i_rec;                        // df_gpu_decode_batch_device: the entries' ranges, their outputs' places, their records
     u64 inf_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // df_gpu_last_decode_batch_stats
+    DevBuf s_cand, s_piece, s_prec, s_map, s_cnt;      // an entry across many waves: candidates, pieces, their records, the source map
+    u64 split_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // df_gpu_last_decode_split_stats
+    double split_ms[7] = {0, 0, 0, 0, 0, 0, 0};        // search, sizes, repair, writing, jump rounds, gather, checksum
     double t_stage[6] = {0, 0, 0, 0, 0, 0}; // chains, matches, parse, blocks, emit, total
     u64 stats[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // blocks, stored, fixed, dynamic, limited tables, stream bytes, dynamic w/o distances
     hipEvent_t ev[7] = {};
@@ -811,6 +816,237 @@ extern "C" int df_gpu_last_decode_batch_stats(bz_gpu_engine *g, uint64_t out[8])
     return BZ_OK;
 }
 
+
+// ---- one large entry across many waves (inf_split.h; DESIGN_deflate.md "One large stream across many waves") ----------
+// An entry of BZ_DF_INF_SPLIT_KIB or more compressed bytes is cut into pieces of BZ_DF_INF_PIECE_KIB; both are read per call.
+static u64 df_env_kib(const char *name, u64 dflt)
+{
+    const char *s = getenv(name);
+    if (!s || !*s) return dflt;
+    char *end = nullptr;
+    const unsigned long long v = strtoull(s, &end, 10);
+    return end == s ? dflt : (u64)v;
+}
+extern "C" int df_gpu_last_decode_split_stats(bz_gpu_engine *g, uint64_t out[8])
+{
+    if (!g || !out) return BZ_E_PARAM;
+    for (int i = 0; i < 8; ++i) out[i] = g->df ? g->df->split_stats[i] : 0;
+    return BZ_OK;
+}
+
+extern "C" int df_gpu_last_decode_split_timings(bz_gpu_engine *g, double out_seconds[7])
+{
+    if (!g || !out_seconds) return BZ_E_PARAM;
+    for (int i = 0; i < 7; ++i) out_seconds[i] = g->df ? g->df->split_ms[i] * 1e-3 : 0.0;
+    return BZ_OK;
+}
+
+struct DfSplitEntry {
+    size_t index = 0;           // of the entry in the call
+    std::vector<DfPiece> chain; // the confirmed pieces in stream order, each with its place in the entry's output and its length
+    DfInfRec rec;               // what the one-wave path would have left for the entry
+    // its share of df_gpu_last_decode_split_stats and of the phases search, sizes, repair: counted in once the entry is
+    // known to stay split
+    u64 st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double ms[3] = {0, 0, 0};
+};
+
+// the sizes launch over n pieces, and their records
+static int df_split_pieces(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *ebase, u32 elen, const DfPiece *pcs, u32 n, DfPieceRec *out,
+                           u64 *launches)
+{
+    int rc = w->s_piece.ensure((size_t)n * sizeof(DfPiece));
+    if (rc == BZ_OK) rc = w->s_prec.ensure((size_t)n * sizeof(DfPieceRec));
+    if (rc != BZ_OK) return rc;
+    HIPCHK(hipMemcpyAsync(w->s_piece.p, pcs, (size_t)n * sizeof(DfPiece), hipMemcpyHostToDevice, g->st));
+    if (df_launch_inflate_piece(g->st, false, ebase, elen, kind, w->s_piece.as<DfPiece>(), n, w->s_prec.as<DfPieceRec>(), nullptr, nullptr) != 0)
+        return BZ_E_UNEXPECTED;
+    HIPCHK(hipMemcpyAsync(out, w->s_prec.p, (size_t)n * sizeof(DfPieceRec), hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipStreamSynchronize(g->st));
+    *launches += 1;
+    return BZ_OK;
+}
+
+// Search, sizes, chain and repair of one entry.  *fallback: the entry takes the one-wave path (an output of 2 GiB or more).
+static int df_split_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *ebase, u32 elen, DfSplitEntry &e, bool *fallback)
+{
+    using namespace infsplit;
+    *fallback = false;
+    u64 piece = df_env_kib("BZ_DF_INF_PIECE_KIB", 16);
+    piece = (piece < 1 ? 1 : piece > (1u << 20) ? (1u << 20) : piece) * 1024;
+    while (elen / piece > (1u << 20)) piece *= 2;
+    const u32 npieces = (u32)((elen + piece - 1) / piece);
+    double t0 = df_now_ms();
+    std::vector<Cand> cands;
+    int rc;
+    if (npieces > 1) {
+        std::vector<Cand> all(npieces - 1);
+        if ((rc = w->s_cand.ensure(all.size() * sizeof(Cand))) != BZ_OK) return rc;
+        if (df_launch_split_search(g->st, ebase, elen, (u32)piece, npieces, w->s_cand.p) != 0) return BZ_E_UNEXPECTED;
+        HIPCHK(hipMemcpyAsync(all.data(), w->s_cand.p, all.size() * sizeof(Cand), hipMemcpyDeviceToHost, g->st));
+        HIPCHK(hipStreamSynchronize(g->st));
+        e.st[7] += 1;
+        for (const Cand &c : all)
+            if (c.pos != kNoStop) cands.push_back(c);
+    }
+    e.st[1] += cands.size();
+    double t1 = df_now_ms();
+    e.ms[0] += t1 - t0;
+    // every piece at once: the entry's first bit and every candidate, each to the next candidate
+    std::vector<DfPiece> pcs(1 + cands.size());
+    for (size_t k = 0; k < pcs.size(); ++k) {
+        DfPiece &q = pcs[k];
+        q.start = k ? cands[k - 1].pos : 0;
+        q.stop = k < cands.size() ? cands[k].pos : kNoStop;
+        q.mode = k ? cands[k - 1].mode : 2u;
+        q.base = k ? kBaseUnknown : 0u;
+        q.len = q.pad = 0;
+    }
+    std::vector<DfPieceRec> prs(pcs.size());
+    if ((rc = df_split_pieces(g, w, kind, ebase, elen, pcs.data(), (u32)pcs.size(), prs.data(), &e.st[7])) != BZ_OK) return rc;
+    t0 = df_now_ms();
+    e.ms[1] += t0 - t1;
+    // the chain: a candidate's piece counts if and only if the confirmed piece in front of it ended exactly there
+    std::vector<DfPieceRec> crec;
+    e.chain.clear();
+    DfPiece cur = pcs[0];
+    DfPieceRec cr = prs[0];
+    u64 j = 0;
+    u32 repairs = 0;
+    for (;;) {
+        e.chain.push_back(cur);
+        crec.push_back(cr);
+        const PieceEnd end{cr.r.end_bit, cr.end_mode, cr.ended != 0};
+        u64 stop = kNoStop;
+        const Next nx = chain_next(cands.data(), cands.size(), end, repairs, j, stop);
+        if (nx == Next::Done) break;
+        if (nx == Next::Confirmed) {
+            cur = pcs[1 + j];
+            cr = prs[1 + j];
+            ++j;
+            e.st[2] += 1;
+            continue;
+        }
+        cur = DfPiece{end.pos, stop, end.mode, kBaseUnknown, 0, 0};
+        if ((rc = df_split_pieces(g, w, kind, ebase, elen, &cur, 1, &cr, &e.st[7])) != BZ_OK) return rc;
+        if (nx == Next::Repair) {
+            ++repairs;
+            e.st[3] += 1;
+        } else e.st[4] += cr.r.len; // the serial tail
+    }
+    e.st[2] += 1; // (the first piece)
+    // the pieces' places; a piece whose matches reach further back than its place is decoded once more knowing it: the
+    // stream ends at the failing code
+    u64 sum = 0;
+    for (size_t k = 0; k < e.chain.size(); ++k) {
+        if (sum >= (1ull << 31)) break;
+        e.chain[k].base = (u32)sum;
+        if (k > 0 && crec[k].reach > sum) {
+            if ((rc = df_split_pieces(g, w, kind, ebase, elen, &e.chain[k], 1, &crec[k], &e.st[7])) != BZ_OK) return rc;
+            if (!crec[k].ended || crec[k].r.verdict == BZ_OK) return BZ_E_UNEXPECTED;
+            e.chain.resize(k + 1);
+            crec.resize(k + 1);
+        }
+        e.chain[k].len = crec[k].r.len;
+        sum += crec[k].r.len;
+        if (crec[k].r.flags & 1u) sum = 1ull << 32;
+    }
+    e.ms[2] += df_now_ms() - t0;
+    if (sum >= (1ull << 31)) {
+        *fallback = true;
+        return BZ_OK;
+    }
+    e.rec = crec.back().r;
+    e.rec.len = (u32)sum;
+    for (int b = 0; b < 3; ++b) {
+        e.rec.nblk[b] = 0;
+        for (const DfPieceRec &q : crec) e.rec.nblk[b] += q.r.nblk[b];
+    }
+    e.st[0] = 1;
+    return BZ_OK;
+}
+
+// The bytes of one split entry at `eout`: the writing launch with its source map, pointer jumping, the gather; for kinds 1 / 2
+// the checksum of a clean stream, folded piecewise (k_df_sums) and combined here as df_encode_core combines it.
+static int df_split_write(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *ebase, u32 elen, u8 *eout, DfSplitEntry &e)
+{
+    const u32 n = e.rec.len, np = (u32)e.chain.size();
+    u32 *map = w->s_map.as<u32>(), *cnt = w->s_cnt.as<u32>();
+    int rc = w->s_piece.ensure((size_t)np * sizeof(DfPiece));
+    if (rc != BZ_OK) return rc;
+    double t0 = df_now_ms();
+    HIPCHK(hipMemcpyAsync(w->s_piece.p, e.chain.data(), (size_t)np * sizeof(DfPiece), hipMemcpyHostToDevice, g->st));
+    if (df_launch_inflate_piece(g->st, true, ebase, elen, kind, w->s_piece.as<DfPiece>(), np, nullptr, eout, map) != 0) return BZ_E_UNEXPECTED;
+    HIPCHK(hipStreamSynchronize(g->st));
+    w->split_stats[7] += 1;
+    double t1 = df_now_ms();
+    w->split_ms[3] += t1 - t0;
+    u32 left = 0;
+    for (u32 round = 0; n && np > 1; ++round) {
+        u32 h[2] = {0, 0};
+        HIPCHK(hipMemsetAsync(cnt, 0, 8, g->st));
+        if (df_launch_split_jump(g->st, map, n, cnt) != 0) return BZ_E_UNEXPECTED;
+        HIPCHK(hipMemcpyAsync(h, cnt, 8, hipMemcpyDeviceToHost, g->st));
+        HIPCHK(hipStreamSynchronize(g->st));
+        w->split_stats[7] += 1;
+        w->split_stats[6] += 1;
+        if (round == 0) left = h[0];
+        if (h[1] == 0) break;
+    }
+    w->split_stats[5] += left;
+    t0 = df_now_ms();
+    w->split_ms[4] += t0 - t1;
+    if (left) {
+        if (df_launch_split_gather(g->st, eout, map, n) != 0) return BZ_E_UNEXPECTED;
+        HIPCHK(hipStreamSynchronize(g->st));
+        w->split_stats[7] += 1;
+    }
+    t1 = df_now_ms();
+    w->split_ms[5] += t1 - t0;
+    if (kind == 0 || e.rec.verdict != BZ_OK) return BZ_OK;
+    const u32 npieces = (u32)(((u64)n + kSumPiece - 1) / kSumPiece);
+    if ((rc = w->asum.ensure((size_t)(npieces + 1) * 8)) != BZ_OK) return rc;
+    if ((rc = w->bsum.ensure((size_t)(npieces + 1) * 8)) != BZ_OK) return rc;
+    if ((rc = w->crc.ensure((size_t)(npieces + 1) * 4 + 256 * 4)) != BZ_OK) return rc;
+    std::vector<u64> a(npieces), b(npieces);
+    std::vector<u32> c((size_t)npieces + 1 + 256);
+    if (npieces) {
+        if (df_launch_sums(g->st, eout, n, w->asum.as<u64>(), w->bsum.as<u64>(), w->crc.as<u32>(), w->crc.as<u32>() + npieces + 1, df_crc_shifts()) != 0)
+            return BZ_E_UNEXPECTED;
+        HIPCHK(hipMemcpyAsync(a.data(), w->asum.p, (size_t)npieces * 8, hipMemcpyDeviceToHost, g->st));
+        HIPCHK(hipMemcpyAsync(b.data(), w->bsum.p, (size_t)npieces * 8, hipMemcpyDeviceToHost, g->st));
+        HIPCHK(hipMemcpyAsync(c.data(), w->crc.p, c.size() * 4, hipMemcpyDeviceToHost, g->st));
+        HIPCHK(hipStreamSynchronize(g->st));
+        w->split_stats[7] += 1;
+    }
+    bool ok;
+    if (kind == 1) {
+        u64 A = 1, B = 0;
+        for (u32 t = 0; t < npieces; ++t) {
+            const u64 len = (t + 1 == npieces) ? n - (u64)t * kSumPiece : kSumPiece;
+            B = (B + (len % 65521) * A + b[t]) % 65521;
+            A = (A + a[t]) % 65521;
+        }
+        ok = (u32)((B << 16) | A) == e.rec.check;
+    } else {
+        const u32 xpiece = gf_xpow8_reflected(kSumPiece);
+        u32 raw = 0;
+        for (u32 t = 0; t < npieces; ++t) {
+            const u64 len = (t + 1 == npieces) ? n - (u64)t * kSumPiece : kSumPiece;
+            if (len == kSumPiece) raw = gf_mul_reflected(raw, xpiece) ^ c[t];
+            else
+                for (u32 s = 0; (u64)s * 256 < len; ++s) {
+                    const u64 sl = (len - (u64)s * 256) < 256 ? (len - (u64)s * 256) : 256;
+                    raw = gf_mul_reflected(raw, gf_xpow8_reflected(sl)) ^ c[(size_t)npieces + 1 + s];
+                }
+        }
+        ok = (raw ^ gf_mul_reflected(0xFFFFFFFFu, gf_xpow8_reflected(n)) ^ 0xFFFFFFFFu) == e.rec.check && e.rec.isize == n;
+    }
+    if (!ok) e.rec.verdict = BZ_E_DATA;
+    w->split_ms[6] += df_now_ms() - t1;
+    return BZ_OK;
+}
+
 // grow != nullptr: the output is the engine's own buffer, sized between the two launches (the host forms)
 static int df_decode_batch_core(bz_gpu_engine *g, int kind, const void *d_in, const uint64_t *h_in_off, const uint64_t *h_in_len, size_t count,
                                 void *d_out, size_t cap, DevBuf *grow, uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_verdict)
@@ -829,21 +1065,55 @@ static int df_decode_batch_core(bz_gpu_engine *g, int kind, const void *d_in, co
     int rc = df_workspace(g, &w);
     if (rc != BZ_OK) return rc;
     for (u64 &s : w->inf_stats) s = 0;
+    for (u64 &s : w->split_stats) s = 0;
+    for (double &t : w->split_ms) t = 0;
+    const u8 *in8 = static_cast<const u8 *>(d_in);
+    // the entries that go across many waves; in the launches over all entries they are entries of no bytes
+    const u64 split_min = df_env_kib("BZ_DF_INF_SPLIT_KIB", 1024) * 1024;
+    std::vector<DfSplitEntry> splits;
+    std::vector<u64> len_small;
+    for (size_t i = 0; split_min && i < count; ++i) {
+        if (h_in_len[i] < split_min) continue;
+        DfSplitEntry e;
+        bool fallback = false;
+        e.index = i;
+        rc = df_split_sizes(g, w, kind, in8 + h_in_off[i], (u32)h_in_len[i], e, &fallback);
+        if (rc != BZ_OK) return rc;
+        if (!fallback) splits.push_back(std::move(e));
+    }
+    // ONE source map for all of them, one after the other: sized here, before any entry is committed to the split path.  If
+    // it cannot be had, every entry takes the one-wave path (and the failed allocation's error is not the next launch's).
+    if (!splits.empty() && (d_out != nullptr || grow != nullptr)) {
+        size_t map_bytes = 0;
+        for (const DfSplitEntry &e : splits) map_bytes = std::max(map_bytes, (size_t)e.rec.len * 4 + 64);
+        if (w->s_map.ensure(map_bytes) != BZ_OK || w->s_cnt.ensure(64) != BZ_OK) {
+            (void)hipGetLastError();
+            splits.clear();
+        }
+    }
+    for (const DfSplitEntry &e : splits) {
+        for (int k = 0; k < 8; ++k) w->split_stats[k] += e.st[k];
+        for (int k = 0; k < 3; ++k) w->split_ms[k] += e.ms[k];
+    }
+    if (!splits.empty()) {
+        len_small.assign(h_in_len, h_in_len + count);
+        for (const DfSplitEntry &e : splits) len_small[e.index] = 0;
+    }
     rc = w->i_in.ensure(2 * count * sizeof(u64));
     if (rc == BZ_OK) rc = w->i_ooff.ensure(count * sizeof(u64));
     if (rc == BZ_OK) rc = w->i_rec.ensure(count * sizeof(DfInfRec));
     if (rc != BZ_OK) return rc;
     u64 *d_off = w->i_in.as<u64>(), *d_len = d_off + count, *d_ooff = w->i_ooff.as<u64>();
     DfInfRec *d_rec = w->i_rec.as<DfInfRec>();
-    const u8 *in8 = static_cast<const u8 *>(d_in);
     HIPCHK(hipMemcpyAsync(d_off, h_in_off, count * sizeof(u64), hipMemcpyHostToDevice, g->st));
-    HIPCHK(hipMemcpyAsync(d_len, h_in_len, count * sizeof(u64), hipMemcpyHostToDevice, g->st));
+    HIPCHK(hipMemcpyAsync(d_len, splits.empty() ? h_in_len : len_small.data(), count * sizeof(u64), hipMemcpyHostToDevice, g->st));
     HIPCHK(hipEventRecord(w->ev[0], g->st));
     if (df_launch_inflate(g->st, false, in8, d_off, d_len, (u32)count, kind, nullptr, nullptr, d_rec) != 0) return BZ_E_UNEXPECTED;
     HIPCHK(hipEventRecord(w->ev[1], g->st));
     std::vector<DfInfRec> rec(count);
     HIPCHK(hipMemcpyAsync(rec.data(), d_rec, count * sizeof(DfInfRec), hipMemcpyDeviceToHost, g->st));
     HIPCHK(hipStreamSynchronize(g->st));
+    for (const DfSplitEntry &e : splits) rec[e.index] = e.rec;
     // the outputs' places: input order, each at a multiple of 16
     u64 cursor = 0, need = 0;
     for (size_t i = 0; i < count; ++i) {
@@ -872,6 +1142,11 @@ static int df_decode_batch_core(bz_gpu_engine *g, int kind, const void *d_in, co
         }
         HIPCHK(hipEventRecord(w->ev[4], g->st));
         HIPCHK(hipStreamSynchronize(g->st));
+        for (DfSplitEntry &e : splits) {
+            rc = df_split_write(g, w, kind, in8 + h_in_off[e.index], (u32)h_in_len[e.index], out8 + h_out_off[e.index], e);
+            if (rc != BZ_OK) return rc;
+            rec[e.index] = e.rec;
+        }
         for (size_t i = 0; i < count; ++i) h_verdict[i] = rec[i].verdict;
         (void)hipEventElapsedTime(&ms[1], w->ev[2], w->ev[3]);
         (void)hipEventElapsedTime(&ms[2], w->ev[3], w->ev[4]);
@@ -884,7 +1159,14 @@ static int df_decode_batch_core(bz_gpu_engine *g, int kind, const void *d_in, co
         w->inf_stats[5] += rec[i].len;
         w->inf_stats[6] += (rec[i].end_bit + 7u) >> 3;
     }
-    // df_gpu_last_timings: [0] the sizes launch [1] the writing launch [2] the checksum kernel [5] their sum
+    // df_gpu_last_timings: [0] the sizes launch [1] the writing launch [2] the checksum kernel [5] their sum; the phases of the
+    // split entries (host clock around launches that are waited for) go where they belong
+    ms[0] += (float)(w->split_ms[0] + w->split_ms[1] + w->split_ms[2]);
+    ms[1] += (float)(w->split_ms[3] + w->split_ms[4] + w->split_ms[5]);
+    ms[2] += (float)w->split_ms[6];
+    if (df_trace() && !splits.empty())
+        fprintf(stderr, "bz2_mi355x: inflate split: %zu entries; search %.3f sizes %.3f repair %.3f writing %.3f jump %.3f gather %.3f checksum %.3f ms\n",
+                splits.size(), w->split_ms[0], w->split_ms[1], w->split_ms[2], w->split_ms[3], w->split_ms[4], w->split_ms[5], w->split_ms[6]);
     for (double &t : w->t_stage) t = 0;
     for (int k = 0; k < 3; ++k) {
         w->t_stage[k] = ms[k] * 1e-3;

@@ -147,4 +147,26 @@ struct DfInfRec {
 int df_launch_inflate(hipStream_t st, bool write, const u8 *in, const u64 *in_off, const u64 *in_len, u32 count, int kind, u8 *out,
                       const u64 *out_off, DfInfRec *rec);
 int df_launch_inflate_check(hipStream_t st, const u8 *out, const u64 *out_off, u32 count, DfInfRec *rec, int kind);
+// ---- one large entry across many waves (inf_split.h): a piece runs from a bit of the entry to the first block boundary at
+// or behind `stop`
+struct DfPiece {
+    u64 start; // bit of the entry: a block header, or (mode bit 0) the LEN field of a stored block
+    u64 stop;  // infsplit::kNoStop: to the end of the stream
+    u32 mode;  // bit 0: starts at LEN; bit 1: the entry's first piece, the container header comes first
+    u32 base;  // where its output starts inside the entry's (infsplit::kBaseUnknown: not known yet)
+    u32 len;   // the writing launch: bytes to write
+    u32 pad;
+};
+struct DfPieceRec {
+    DfInfRec r;   // as of an entry; r.end_bit of a piece that stopped at a boundary: that boundary (see end_mode)
+    u32 reach;    // the furthest a match reached in front of the piece's own output
+    u32 end_mode; // the boundary is 0: a block header, 1: the LEN field of a non-final stored block
+    u32 ended;    // the stream ended in the piece: the final block, an error, the entry's end
+    u32 pad;
+};
+int df_launch_split_search(hipStream_t st, const u8 *ebase, u32 elen, u32 piece_bytes, u32 npieces, void *cand);
+int df_launch_inflate_piece(hipStream_t st, bool write, const u8 *ebase, u32 elen, int kind, const DfPiece *pc, u32 count, DfPieceRec *rec,
+                            u8 *eout, u32 *emap);
+int df_launch_split_jump(hipStream_t st, u32 *src, u32 n, u32 *cnt);
+int df_launch_split_gather(hipStream_t st, u8 *out, const u32 *src, u32 n);
 } // namespace dfgpu

@@ -40,6 +40,7 @@
 #include "bzgpu.h"
 #include "k_deflate.h"
 #include "k_df_fold.h"
+#include "inf_split.h"
 
 namespace dfgpu {
 using namespace bzgpu;
@@ -458,6 +459,451 @@ done:
 #undef INF_EOF_CHECK
 }
 
+namespace {
+// the tables of one wave (LDS)
+struct InfTabs {
+    u16 tl[1u << kLBits], td[1u << kDBits], tc[1u << kCBits];
+    u16 sl[288], sd[32], sc[32];
+    u32 nl[16], nd[16], nc[16];
+    u8 cl[320], clen[32];
+};
+// what a decode leaves behind
+struct InfOut {
+    u64 end_bit;
+    u32 p, nblk0, nblk1, nblk2, check, isize, flags;
+    int verdict;
+    u32 reach, end_mode, ended; // of a piece (k_df_inflate_piece)
+};
+
+// The decode loop of a PIECE of a split entry (k_df_inflate_piece, inf_split.h).  It is k_df_inflate's loop, code for code --
+// a copy, so that the one-wave kernel stays the text and the machine code it was; what one of them learns the other must be
+// taught -- from the reader's position (`head`: the container header comes first, `at_len`: the position is the LEN field of
+// a stored block) to the first block boundary at or behind `stop`; `base` is where the piece's output starts inside the
+// entry's (infsplit::kBaseUnknown: not known yet, a distance that reaches in front of the piece is recorded in `reach` and
+// believed); with WRITE every byte i gets smap[i]: i itself when out[i] holds its value, else the position inside the
+// entry's output (in front of the piece) that does.
+template <bool WRITE>
+__device__ __forceinline__ void inf_decode(InfTabs &t, InfIn &r, const u32 lane, const int kind, const bool head, u8 *out, const u32 limit,
+                                           u32 *smap, const u32 base, const u64 stop, bool at_len, InfOut &o)
+{
+    u16 *const s_tl = t.tl, *const s_td = t.td, *const s_tc = t.tc, *const s_sl = t.sl, *const s_sd = t.sd, *const s_sc = t.sc;
+    u32 *const s_nl = t.nl, *const s_nd = t.nd, *const s_nc = t.nc;
+    u8 *const s_cl = t.cl, *const s_clen = t.clen;
+    const u64 total = 8ull * r.len;
+    u32 p = 0;       // bytes produced, pending literals included
+    u32 npend = 0;   // literals waiting in `lit`
+    u32 lit = 0;     // PER LANE: pending literal number `lane`
+    u32 fenced = 0;  // stores below this position are ordered before every later load
+    u32 nblk0 = 0, nblk1 = 0, nblk2 = 0, check = 0, isize = 0, flags = 0;
+    u32 reach = 0, end_mode = 0, ended = 1;
+    u64 end_key = 0;
+    int verdict = BZ_OK;
+    bool fixed_ready = false;
+    u32 maxl = 0, maxd = 0;
+
+#define INF_FLUSH()                                                                   \
+    do {                                                                              \
+        if (WRITE && npend) {                                                         \
+            const u32 q_ = p - npend + lane;                                          \
+            if (lane < npend && q_ < limit) {                                         \
+                out[q_] = (u8)lit;                                                    \
+                smap[q_] = base + q_;                                                 \
+            }                                                                         \
+        }                                                                             \
+        npend = 0;                                                                    \
+    } while (0)
+// a failure: BZ_E_EOF if the bits looked at (those consumed and `extra` more) reach behind the entry, else BZ_E_DATA
+#define INF_FAIL(extra)                                                               \
+    do {                                                                              \
+        verdict = (inf_consumed(r) + (extra)) > total ? BZ_E_EOF : BZ_E_DATA;         \
+        goto done;                                                                    \
+    } while (0)
+#define INF_EOF_CHECK()                                                               \
+    do {                                                                              \
+        if (inf_consumed(r) > total) {                                                \
+            verdict = BZ_E_EOF;                                                       \
+            goto done;                                                                \
+        }                                                                             \
+    } while (0)
+
+    // ---- container header
+    if (head && kind == 1) {
+        inf_fill(r, lane);
+        const u32 cmf = inf_take(r, 8), flg = inf_take(r, 8);
+        INF_EOF_CHECK();
+        if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 0x20u)) INF_FAIL(0);
+    } else if (head && kind == 2) {
+        u32 hc = 0xFFFFFFFFu, flg = 0, xlen = 0;
+#define INF_HBYTE(v)                                                                  \
+    do {                                                                              \
+        inf_fill(r, lane);                                                            \
+        (v) = inf_take(r, 8);                                                         \
+        INF_EOF_CHECK();                                                              \
+        hc ^= (v);                                                                    \
+        for (int k_ = 0; k_ < 8; ++k_) hc = (hc & 1u) ? (hc >> 1) ^ 0xEDB88320u : hc >> 1; \
+    } while (0)
+        for (u32 k = 0; k < 10; ++k) {
+            u32 b;
+            INF_HBYTE(b);
+            if ((k == 0 && b != 0x1Fu) || (k == 1 && b != 0x8Bu) || (k == 2 && b != 8u) || (k == 3 && (b & 0xE0u))) INF_FAIL(0);
+            if (k == 3) flg = b;
+        }
+        if (flg & 4u) {
+            u32 b0, b1;
+            INF_HBYTE(b0);
+            INF_HBYTE(b1);
+            xlen = b0 | (b1 << 8);
+            for (u32 k = 0; k < xlen; ++k) INF_HBYTE(b0);
+        }
+        for (u32 f = 8u; f <= 16u; f <<= 1) // FNAME, FCOMMENT: up to the zero byte
+            if (flg & f) {
+                u32 b;
+                do INF_HBYTE(b);
+                while (b != 0);
+            }
+        if (flg & 2u) {
+            const u32 want = (hc ^ 0xFFFFFFFFu) & 0xFFFFu;
+            inf_fill(r, lane);
+            const u32 got = inf_take(r, 16);
+            INF_EOF_CHECK();
+            if (got != want) INF_FAIL(0);
+        }
+#undef INF_HBYTE
+    }
+
+    // ---- blocks
+    for (;;) {
+        u32 bfinal = 0, btype = 0;
+        const bool from_len = at_len; // (a piece that starts at a stored block's LEN: its header bits lie in front)
+        at_len = false;
+        if (!from_len) {
+            // a boundary: the block behind it is the next piece's if it starts at or behind `stop`
+            const u64 h = inf_consumed(r);
+            inf_fill(r, lane);
+            const bool st0 = h + 3 <= total && ((u32)r.buf & 7u) == 0u; // a non-final stored block: known by its LEN
+            const u64 key = st0 ? (h + 10) & ~7ull : h;
+            if (key >= stop) {
+                end_key = key;
+                end_mode = st0 ? 1u : 0u;
+                ended = 0;
+                goto done;
+            }
+            bfinal = inf_take(r, 1);
+            btype = inf_take(r, 2);
+            INF_EOF_CHECK();
+            if (btype == 3u) INF_FAIL(0);
+        }
+        if (btype == 0u) {
+            if (!from_len) (void)inf_take(r, r.cnt & 7u);
+            inf_fill(r, lane);
+            const u32 ln = inf_take(r, 16), nl = inf_take(r, 16);
+            INF_EOF_CHECK();
+            if ((ln ^ nl) != 0xFFFFu) INF_FAIL(0);
+            const u32 bytepos = (u32)(inf_consumed(r) >> 3);
+            if ((u64)bytepos + ln > r.len) {
+                verdict = BZ_E_EOF;
+                goto done;
+            }
+            if (p > 0xFFFFFFFFu - 0x10000u) {
+                flags |= 1u;
+                INF_FAIL(0);
+            }
+            INF_FLUSH();
+            if (WRITE)
+                for (u32 i = lane; i < ln; i += 64u)
+                    if (p + i < limit) {
+                        out[p + i] = r.base[bytepos + i];
+                        smap[p + i] = base + p + i;
+                    }
+            p += ln;
+            inf_seek(r, bytepos + ln, lane);
+            ++nblk0;
+        } else {
+            if (btype == 1u) {
+                if (!fixed_ready) {
+                    __syncthreads();
+                    for (u32 i = lane; i < 320u; i += 64u) s_cl[i] = (u8)(i < 144u ? 8u : i < 256u ? 9u : i < 280u ? 7u : i < 288u ? 8u : 5u);
+                    __syncthreads();
+                    u32 ns;
+                    (void)inf_build(s_cl, 288, s_tl, kLBits, s_nl, s_sl, lane, ns, maxl);
+                    (void)inf_build(s_cl + 288, 32, s_td, kDBits, s_nd, s_sd, lane, ns, maxd);
+                    fixed_ready = true;
+                }
+            } else {
+                fixed_ready = false;
+                const u32 hlit = inf_take(r, 5) + 257u, hdist = inf_take(r, 5) + 1u, hclen = inf_take(r, 4) + 4u;
+                INF_EOF_CHECK();
+                if (hlit > 286u || hdist > 30u) INF_FAIL(0);
+                __syncthreads();
+                if (lane < 19u) s_clen[lane] = 0;
+                __syncthreads();
+                for (u32 k = 0; k < hclen; ++k) {
+                    inf_fill(r, lane);
+                    const u32 v = inf_take(r, 3);
+                    if (lane == 0) s_clen[c_cl_order[k]] = (u8)v;
+                }
+                INF_EOF_CHECK();
+                __syncthreads();
+                u32 ns, maxc;
+                if (inf_build(s_clen, 19, s_tc, kCBits, s_nc, s_sc, lane, ns, maxc) != 0) INF_FAIL(0);
+                const u32 ncl = hlit + hdist;
+                u32 i = 0, prev = 0;
+                while (i < ncl) {
+                    inf_fill(r, lane);
+                    const int sy = inf_sym(r, s_tc, kCBits, s_nc, s_sc);
+                    if (sy < 0) INF_FAIL(maxc);
+                    if (sy < 16) {
+                        INF_EOF_CHECK();
+                        if (lane == 0) s_cl[i] = (u8)sy;
+                        prev = (u32)sy;
+                        ++i;
+                        continue;
+                    }
+                    u32 rep, val = 0;
+                    if (sy == 16) {
+                        rep = 3u + inf_take(r, 2);
+                        val = prev;
+                    } else if (sy == 17) rep = 3u + inf_take(r, 3);
+                    else rep = 11u + inf_take(r, 7);
+                    INF_EOF_CHECK();
+                    if ((sy == 16 && i == 0) || i + rep > ncl) INF_FAIL(0);
+                    for (u32 q = lane; q < rep; q += 64u) s_cl[i + q] = (u8)val;
+                    prev = val;
+                    i += rep;
+                }
+                __syncthreads();
+                if (s_cl[256] == 0) INF_FAIL(0); // no end-of-block code
+                // (one sequence of hlit + hdist lengths: a run may cross from one alphabet into the other)
+                const int rl = inf_build(s_cl, hlit, s_tl, kLBits, s_nl, s_sl, lane, ns, maxl);
+                if (rl != 0) INF_FAIL(0);
+                const int rd = inf_build(s_cl + hlit, hdist, s_td, kDBits, s_nd, s_sd, lane, ns, maxd);
+                if (rd == 1 || (rd == 2 && !(ns == 0u || (ns == 1u && maxd == 1u)))) INF_FAIL(0);
+            }
+            // ---- the codes of the block
+            for (;;) {
+                inf_fill(r, lane);
+                const int sy = inf_sym(r, s_tl, kLBits, s_nl, s_sl);
+                if (sy < 0) INF_FAIL(maxl);
+                if (sy < 256) {
+                    INF_EOF_CHECK();
+                    if (lane == npend) lit = (u32)sy;
+                    ++npend;
+                    ++p;
+                    if (npend == 64u) INF_FLUSH();
+                    continue;
+                }
+                if (sy == 256) {
+                    INF_EOF_CHECK();
+                    break;
+                }
+                if (sy > 285) INF_FAIL(0);
+                const u32 len = c_len_base[sy - 257] + inf_take(r, c_len_extra[sy - 257]);
+                inf_fill(r, lane);
+                const int ds = inf_sym(r, s_td, kDBits, s_nd, s_sd);
+                if (ds < 0) INF_FAIL(maxd);
+                if (ds > 29) INF_FAIL(0);
+                const u32 d = c_dist_base[ds] + inf_take(r, c_dist_extra[ds]);
+                INF_EOF_CHECK();
+                if (d > p) { // in front of the piece: inside the entry's output if the piece knows where it lies
+                    if (base != infsplit::kBaseUnknown && (u64)d > (u64)base + p) INF_FAIL(0);
+                    if (d - p > reach) reach = d - p;
+                }
+                if (p > 0xFFFFFFFFu - 0x10000u) {
+                    flags |= 1u;
+                    INF_FAIL(0);
+                }
+                INF_FLUSH();
+                if (WRITE) {
+                    const u32 span = d < len ? d : len;
+                    if ((long long)p - d + span > (long long)fenced) {
+                        __threadfence_block();
+                        fenced = p;
+                    }
+                    for (u32 b = 0; b < len; b += 64u) {
+                        const u32 i = b + lane;
+                        if (i < len && p + i < limit) {
+                            const long long q = (long long)p - d + (d >= len ? i : i % d);
+                            if (q < 0) smap[p + i] = (u32)((long long)base + q); // (no byte: the gather brings it)
+                            else {
+                                const u32 sv = smap[q];
+                                out[p + i] = out[q];
+                                smap[p + i] = sv == base + (u32)q ? base + p + i : sv;
+                            }
+                        }
+                    }
+                }
+                p += len;
+            }
+            if (btype == 1u) ++nblk1;
+            else ++nblk2;
+        }
+        if (bfinal) break;
+    }
+    // ---- container trailer
+    (void)inf_take(r, r.cnt & 7u);
+    if (kind == 1) {
+        inf_fill(r, lane);
+        const u32 v = inf_take(r, 32);
+        INF_EOF_CHECK();
+        check = (v >> 24) | ((v >> 8) & 0xFF00u) | ((v << 8) & 0xFF0000u) | (v << 24);
+    } else if (kind == 2) {
+        inf_fill(r, lane);
+        check = inf_take(r, 32);
+        inf_fill(r, lane);
+        isize = inf_take(r, 32);
+        INF_EOF_CHECK();
+    }
+done:
+    INF_FLUSH();
+    o.end_bit = !ended ? end_key : inf_consumed(r) < total ? inf_consumed(r) : total;
+    o.p = p;
+    o.verdict = verdict;
+    o.nblk0 = nblk0;
+    o.nblk1 = nblk1;
+    o.nblk2 = nblk2;
+    o.check = check;
+    o.isize = isize;
+    o.flags = flags;
+    o.reach = reach;
+    o.end_mode = end_mode;
+    o.ended = ended;
+#undef INF_FLUSH
+#undef INF_FAIL
+#undef INF_EOF_CHECK
+}
+
+__device__ __forceinline__ DfInfRec inf_record(const InfOut &o)
+{
+    DfInfRec q;
+    q.end_bit = o.end_bit;
+    q.len = o.p;
+    q.verdict = o.verdict;
+    q.nblk[0] = o.nblk0;
+    q.nblk[1] = o.nblk1;
+    q.nblk[2] = o.nblk2;
+    q.check = o.check;
+    q.isize = o.isize;
+    q.flags = o.flags;
+    q.pad[0] = q.pad[1] = 0;
+    return q;
+}
+} // namespace
+
+// ---- one large entry across many waves (inf_split.h; DESIGN_deflate.md "One large stream across many waves")
+// The first candidate of every piece but the first: 64 bit offsets per step, one per lane.
+__global__ __launch_bounds__(64) void k_df_split_search(const u8 *__restrict__ ebase, u32 elen, u32 piece_bytes, infsplit::Cand *cand)
+{
+    const u32 lane = threadIdx.x, k = blockIdx.x + 1;
+    const infsplit::BitSrc src{ebase, elen};
+    const u64 lo = 8ull * k * piece_bytes, total = 8ull * elen;
+    const u64 hi = lo + 8ull * piece_bytes < total ? lo + 8ull * piece_bytes : total;
+    infsplit::Cand c;
+    c.pos = infsplit::kNoStop;
+    c.mode = 0;
+    c.pad = 0;
+    for (u64 o = lo; o < hi; o += 64u) {
+        const u64 bit = o + lane;
+        u32 w[5]; // (unrolled: registers) the words that hold bits [bit, bit + 128)
+#pragma unroll
+        for (u32 q = 0; q < 5; ++q) {
+            const u64 byte = 4ull * ((bit >> 5) + q);
+            u32 v = 0;
+            if (byte + 4 <= elen) v = *reinterpret_cast<const u32 *>(ebase + byte);
+            else
+                for (u32 b = 0; b < 4 && byte + b < elen; ++b) v |= (u32)ebase[byte + b] << (8 * b);
+            w[q] = v;
+        }
+        const u32 sh = (u32)bit & 31u;
+        const u64 a0 = (u64)w[0] | (u64)w[1] << 32, a1 = (u64)w[2] | (u64)w[3] << 32;
+        const u64 blo = sh ? a0 >> sh | a1 << (64u - sh) : a0;
+        const u64 bhi = sh ? a1 >> sh | (u64)w[4] << (64u - sh) : a1;
+        u32 found = 0;
+        if (bit < hi) {
+            if (infsplit::dyn_prefilter(blo, bhi) && infsplit::dyn_header_ok(src, bit, false)) found = 1;
+            else if ((bit & 7u) == 0 && (((u32)blo ^ (u32)(blo >> 16)) & 0xFFFFu) == 0xFFFFu && infsplit::stored_ok(src, bit)) found = 2;
+        }
+        const u64 m = __ballot(found != 0);
+        if (m) {
+            const u32 first = (u32)__ffsll((long long)m) - 1u;
+            c.pos = o + first;
+            c.mode = (u32)__builtin_amdgcn_readlane((int)found, (int)first) - 1u;
+            break;
+        }
+    }
+    if (lane == 0) cand[blockIdx.x] = c;
+}
+
+// One wave per piece.  <false>: what the piece is (DfPieceRec); <true>: its bytes and their source map, below pc.len.
+template <bool WRITE>
+__global__ __launch_bounds__(64) void k_df_inflate_piece(const u8 *__restrict__ ebase, u32 elen, int kind, const DfPiece *__restrict__ pc,
+                                                         DfPieceRec *rec, u8 *eout, u32 *emap)
+{
+    __shared__ InfTabs t;
+    const u32 lane = threadIdx.x, j = blockIdx.x;
+    const DfPiece q = pc[j];
+    InfIn r;
+    r.base = ebase;
+    r.len = elen;
+    r.buf = 0;
+    r.cnt = 0;
+    r.nextw = 0;
+    r.cw = 0;
+    r.cbase = 0xFFFFFF00u;
+    const bool head = (q.mode & 2u) != 0, at_len = (q.mode & 1u) != 0;
+    if (at_len) inf_seek(r, (u32)(q.start >> 3), lane);
+    else if (!head) {
+        r.nextw = (u32)(q.start >> 5);
+        inf_fill(r, lane);
+        (void)inf_take(r, (u32)q.start & 31u);
+    }
+    InfOut o;
+    inf_decode<WRITE>(t, r, lane, kind, head, WRITE ? eout + q.base : nullptr, WRITE ? q.len : 0u, WRITE ? emap + q.base : nullptr, q.base,
+                            q.stop, at_len, o);
+    if (!WRITE && lane == 0) {
+        DfPieceRec x;
+        x.r = inf_record(o);
+        x.reach = o.reach;
+        x.end_mode = o.end_mode;
+        x.ended = o.ended;
+        x.pad = 0;
+        rec[j] = x;
+    }
+}
+
+// src[i] = src[src[i]] over the bytes whose value lies elsewhere; cnt[0] += such bytes, cnt[1] += pointers moved.  A racing
+// read sees an older or a newer ancestor: both are valid, pointers only move toward the root.
+__global__ __launch_bounds__(256) void k_df_split_jump(u32 *src, u32 n, u32 *cnt)
+{
+    __shared__ u32 s_n[2];
+    if (threadIdx.x < 2) s_n[threadIdx.x] = 0;
+    __syncthreads();
+    u32 un = 0, ch = 0;
+    for (u64 i = (u64)blockIdx.x * 256u + threadIdx.x; i < n; i += (u64)gridDim.x * 256u) {
+        const u32 s = __hip_atomic_load(&src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (s < i) {
+            ++un;
+            const u32 a = __hip_atomic_load(&src[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (a < s) {
+                __hip_atomic_store(&src[i], a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ++ch;
+            }
+        }
+    }
+    if (un) atomicAdd(&s_n[0], un);
+    if (ch) atomicAdd(&s_n[1], ch);
+    __syncthreads();
+    if (threadIdx.x < 2 && s_n[threadIdx.x]) atomicAdd(&cnt[threadIdx.x], s_n[threadIdx.x]);
+}
+
+// out[i] = out[src[i]]: every src[i] is a root by now, a byte that the writing launch stored and nothing overwrites
+__global__ __launch_bounds__(256) void k_df_split_gather(u8 *out, const u32 *__restrict__ src, u32 n)
+{
+    for (u64 i = (u64)blockIdx.x * 256u + threadIdx.x; i < n; i += (u64)gridDim.x * 256u) {
+        const u32 s = src[i];
+        if (s < i) out[i] = out[s];
+    }
+}
+
 // The container checksums of the decoded bytes, a workgroup per entry: thread t folds the t-th slice of the entry (a
 // multiple of 16 bytes), the slices are combined as k_df_batch_wrap combines its pieces (k_df_fold.h).  A mismatch with the
 // trailer -- Adler-32 (kind 1), CRC-32 or ISIZE (kind 2) -- turns the entry's verdict to BZ_E_DATA.
@@ -521,6 +967,36 @@ int df_launch_inflate(hipStream_t st, bool write, const u8 *in, const u64 *in_of
 int df_launch_inflate_check(hipStream_t st, const u8 *out, const u64 *out_off, u32 count, DfInfRec *rec, int kind)
 {
     hipLaunchKernelGGL(k_df_inflate_check, dim3(count), dim3(256), 0, st, out, out_off, rec, kind);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// cand: npieces - 1 infsplit::Cand, of pieces 1 .. npieces - 1
+int df_launch_split_search(hipStream_t st, const u8 *ebase, u32 elen, u32 piece_bytes, u32 npieces, void *cand)
+{
+    if (npieces < 2) return 0;
+    hipLaunchKernelGGL(k_df_split_search, dim3(npieces - 1), dim3(64), 0, st, ebase, elen, piece_bytes, static_cast<infsplit::Cand *>(cand));
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int df_launch_inflate_piece(hipStream_t st, bool write, const u8 *ebase, u32 elen, int kind, const DfPiece *pc, u32 count, DfPieceRec *rec,
+                            u8 *eout, u32 *emap)
+{
+    if (write) hipLaunchKernelGGL((k_df_inflate_piece<true>), dim3(count), dim3(64), 0, st, ebase, elen, kind, pc, rec, eout, emap);
+    else hipLaunchKernelGGL((k_df_inflate_piece<false>), dim3(count), dim3(64), 0, st, ebase, elen, kind, pc, rec, eout, emap);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+static u32 df_split_grid(u32 n) { return n / 1024u + 1u < 8192u ? n / 1024u + 1u : 8192u; }
+
+int df_launch_split_jump(hipStream_t st, u32 *src, u32 n, u32 *cnt)
+{
+    hipLaunchKernelGGL(k_df_split_jump, dim3(df_split_grid(n)), dim3(256), 0, st, src, n, cnt);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int df_launch_split_gather(hipStream_t st, u8 *out, const u32 *src, u32 n)
+{
+    hipLaunchKernelGGL(k_df_split_gather, dim3(df_split_grid(n)), dim3(256), 0, st, out, src, n);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

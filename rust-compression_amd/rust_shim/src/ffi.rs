@@ -59,6 +59,8 @@ extern "C" {
     // section 5: Deflater / ZlibDecoder / GZipDecoder (many streams in one call; *out is released with bz_free)
     pub fn df_gpu_decode_batch_device(g: *mut c_void, kind: i32, d_in: *const c_void, h_in_off: *const u64, h_in_len: *const u64, count: usize, d_out: *mut c_void, cap: usize, h_out_off: *mut u64, h_out_len: *mut u64, h_verdict: *mut i32) -> i32;
     pub fn df_gpu_last_decode_batch_stats(g: *mut c_void, out: *mut u64) -> i32;
+    pub fn df_gpu_last_decode_split_stats(g: *mut c_void, out: *mut u64) -> i32;
+    pub fn df_gpu_last_decode_split_timings(g: *mut c_void, out_seconds: *mut f64) -> i32;
     pub fn df_decode_batch(kind: i32, device: i32, ins: *const *const u8, lens: *const usize, count: usize, out: *mut *mut u8, out_off: *mut u64, out_len: *mut u64, verdict: *mut i32) -> i32;
     pub fn df_decode_buffer(kind: i32, device: i32, input: *const u8, in_len: usize, out: *mut *mut u8, out_len: *mut usize) -> i32;
 }

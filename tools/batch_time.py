@@ -36,7 +36,17 @@ to host, against a loop of Python's zlib.decompress over the same streams on one
 that shares no code with this one), alternating, medians as above; the outputs are compared with the inputs before
 anything is timed.  The line also carries one df_gpu_decode_batch_device call over the streams in HBM: its wall time, the
 split between the sizes launch, the writing launch and the checksum kernel (df_gpu_last_timings) and
-df_gpu_last_decode_batch_stats.  text64m is ONE entry of 64 MiB of the bench corpus: what a single stream costs."""
+df_gpu_last_decode_batch_stats.  text64m is ONE entry of 64 MiB of the bench corpus: what a single stream costs.
+
+    tools/batch_time.py --inflate-one SIZE_MIB [--calls 5] [--one-wave]
+
+ONE raw Deflate stream of SIZE_MIB MiB of the bench corpus (written by deflate_compress_batch), decoded by the split path
+(BZ_DF_INF_SPLIT_KIB / BZ_DF_INF_PIECE_KIB as the environment has them): host to host (deflate_decompress_batch) and
+HBM-resident (one deflate_decode_batch_device call: it returns with the device idle; timed by a host clock and by a pair of
+hipEvents recorded on the idle device around it), the median of `calls` calls after a warm one each, the phases of the split entry
+(df_gpu_last_decode_split_timings), the split stats, and zlib.decompress on one host thread over the same stream.
+--one-wave adds ONE HBM-resident call with BZ_DF_INF_SPLIT_KIB=0: this build's one-wave path (12.6 s for 64 MiB; the parent
+commit's library is timed by running its own `--inflate --workload text64m`)."""
 import argparse
 import ctypes as C
 import importlib
@@ -263,10 +273,74 @@ def inflate_mode(pkg, a, names):
             raise SystemExit("batch_time.py: the batch's outputs differ from the inputs")
 
 
+def inflate_one_mode(pkg, a):
+    import zlib
+    import torch
+    import corpus
+    data = corpus.corpus_bytes(int(a.inflate_one * (1 << 20)))
+    (z,) = pkg.deflate_compress_batch([data], pkg.DEFLATE)
+    same = zlib.decompress(z, -15) == data                                              # (warm)
+    tz = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        zlib.decompress(z, -15)
+        tz.append((time.perf_counter() - t0) * 1e3)
+    zlib_ms = statistics.median(tz)
+    same = same and pkg.deflate_decompress_batch([z], pkg.DEFLATE) == [(data, 0)]      # (warm)
+    th = []
+    for _ in range(a.calls):
+        t0 = time.perf_counter()
+        pkg.deflate_decompress_batch([z], pkg.DEFLATE)
+        th.append((time.perf_counter() - t0) * 1e3)
+    t = torch.frombuffer(bytearray(z) + bytes(-len(z) % 4 + 4), dtype=torch.uint8).cuda()
+    eng = pkg.GpuEngine(0, 1)
+    try:
+        call = lambda o, cap: eng.deflate_decode_batch_device(pkg.DEFLATE, t.data_ptr(), [0], [len(z)], o, cap)
+        o_off, o_len, _ = call(None, 0)
+        o = torch.empty((o_len[0] + 64,), dtype=torch.uint8, device="cuda")
+        call(o.data_ptr(), o_len[0])                                                    # (warm)
+        td, te, phases = [], [], []
+        for _ in range(a.calls):
+            torch.cuda.synchronize()
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()                                      # (hipEvents on the idle device around the synchronous call)
+            t0 = time.perf_counter()
+            call(o.data_ptr(), o_len[0])
+            td.append((time.perf_counter() - t0) * 1e3)
+            ev1.record()
+            ev1.synchronize()
+            te.append(ev0.elapsed_time(ev1))
+            phases.append(eng.deflate_decode_split_timings())
+        stats = eng.deflate_decode_split_stats()
+        same = same and o[:o_len[0]].cpu().numpy().tobytes() == data
+        one_wave = None
+        if a.one_wave:
+            os.environ["BZ_DF_INF_SPLIT_KIB"] = "0"
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            call(o.data_ptr(), o_len[0])
+            one_wave = round((time.perf_counter() - t0) * 1e3, 1)
+            del os.environ["BZ_DF_INF_SPLIT_KIB"]
+    finally:
+        eng.close()
+    hm, dm = statistics.median(th), statistics.median(td)
+    print(json.dumps({"mode": "inflate-one", "bytes": len(data), "compressed_bytes": len(z), "outputs_equal": same,
+                      "split_kib": os.environ.get("BZ_DF_INF_SPLIT_KIB", "default"), "piece_kib": os.environ.get("BZ_DF_INF_PIECE_KIB", "default"),
+                      "host_to_host_ms": round(hm, 2), "host_to_host_GBps": round(len(data) / hm / 1e6, 3),
+                      "device_call_ms": round(dm, 2), "device_call_GBps": round(len(data) / dm / 1e6, 3),
+                      "device_call_all_ms": [round(x, 2) for x in td], "device_call_event_ms": round(statistics.median(te), 2),
+                      "phase_ms": {k: round(statistics.median(p[k] for p in phases) * 1e3, 3) for k in phases[0]},
+                      "split_stats": stats, "zlib_one_thread_ms": round(zlib_ms, 1), "one_wave_device_call_ms": one_wave}), flush=True)
+    if not same:
+        raise SystemExit("batch_time.py: the output differs from the input")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--deflate", action="store_true", help="time deflate_compress_batch against a loop of df_encode_buffer")
     ap.add_argument("--inflate", action="store_true", help="time deflate_decompress_batch against a loop of zlib.decompress")
+    ap.add_argument("--inflate-one", type=float, default=0, metavar="SIZE_MIB", help="time ONE Deflate stream of that many MiB of text")
+    ap.add_argument("--one-wave", action="store_true", help="--inflate-one: one more call on the one-wave path")
     ap.add_argument("--kind", default="deflate", choices=["deflate", "zlib", "gzip"])
     ap.add_argument("--decode", action="store_true", help="time decompress_batch against a loop of bz_decode_buffer")
     ap.add_argument("--workload", default="all")
@@ -297,6 +371,8 @@ def main():
         return decode_mode(pkg, a, names)
     if a.deflate:
         return deflate_mode(pkg, a, names)
+    if a.inflate_one:
+        return inflate_one_mode(pkg, a)
     if a.inflate:
         return inflate_mode(pkg, a, names)
     for name in names:
