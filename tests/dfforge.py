@@ -16,7 +16,12 @@ Written from the formats themselves (RFC 1951, 1950, 1952):
 Every builder returns a Case: the stream, the bytes it should decode to -- for a malformed one the bytes in front of the
 failing code or block header -- and the verdict class.  tests/test_dfforge.py pins all of it against Python's zlib before
 any GPU sees a stream.  Pure Python.
+
+Every builder of cases takes the stream to begin from (`begin`, a callable; default: an empty Stream).  preamble() makes
+one whose last block starts at a candidate of csrc/inf_split.h in a later piece of the entry: what a case appends behind
+it is decoded, in a split entry, by a wave that did not start at the entry's first bit (behind(), source_map_cases()).
 """
+import functools
 import zlib
 
 OK, E_DATA, E_EOF = 0, -1, -2
@@ -61,8 +66,8 @@ class Bits:
 
     def code(self, code, length):
         """a Huffman code: most significant bit first"""
-        for i in range(length - 1, -1, -1):
-            self.put((code >> i) & 1, 1)
+        if length:
+            self.put(int(format(code & ((1 << length) - 1), "0%db" % length)[::-1], 2), length)   # (an over-subscribed set's codes overflow)
 
     def align(self, fill=0):
         if self.n:
@@ -152,7 +157,16 @@ class Stream:
     def __init__(self):
         self.w = Bits()
         self.out = bytearray()
+        self.root = []     # per byte of `out`: the position of the literal or stored byte its value was first written at
+        self.marks = []    # (bit, mode, len(out)) of the block starts that to_next_piece() promises as candidates
         self.lit_codes = self.lit_lens = self.dist_codes = self.dist_lens = None
+
+    def clone(self):
+        c = Stream()
+        c.w.acc, c.w.n, c.w.out = self.w.acc, self.w.n, bytearray(self.w.out)
+        c.out, c.root, c.marks = bytearray(self.out), list(self.root), list(self.marks)
+        c.lit_codes, c.lit_lens, c.dist_codes, c.dist_lens = self.lit_codes, self.lit_lens, self.dist_codes, self.dist_lens
+        return c
 
     # -- blocks
     def header(self, final, btype):
@@ -165,8 +179,9 @@ class Stream:
         ln = len(data) if ln is None else ln
         self.w.put(ln, 16)
         self.w.put(ln ^ 0xFFFF if nlen is None else nlen, 16)
-        for b in data:
-            self.w.put(b, 8)
+        assert self.w.n == 0
+        self.w.out += data
+        self.root += range(len(self.out), len(self.out) + len(data))
         self.out += data
         return self
 
@@ -223,6 +238,7 @@ class Stream:
     def lit(self, data):
         for b in (data if isinstance(data, (bytes, bytearray)) else bytes([data])):
             self.sym(b)
+            self.root.append(len(self.out))
             self.out.append(b)
         return self
 
@@ -240,6 +256,7 @@ class Stream:
             assert dist <= len(self.out)
             for _ in range(length):
                 self.out.append(self.out[-dist])
+                self.root.append(self.root[-dist])
         return self
 
     def eob(self):
@@ -294,6 +311,7 @@ def wrap(kind, raw, data, **kw):
 
 
 # ------------------------------------------------------------------------------------------------- the cases
+@functools.lru_cache(maxsize=None)
 def text(n, seed=1):
     """n bytes without any repeat of three bytes in the last 300 (so a forged copy is the only way to get a repeat)"""
     out, x = bytearray(), seed * 2654435761 % (1 << 32)
@@ -307,13 +325,13 @@ COPY_DIST = (1, 2, 3, 4, 7, 8, 63, 64, 65, 127, 128, 129, 258, 259, 32767, 32768
 COPY_LEN = (3, 4, 63, 64, 65, 257, 258)
 
 
-def copy_grid():
+def copy_grid(begin=Stream):
     """every distance x every length, each its own entry behind a literal prefix just long enough (fixed Huffman; the
     prefixes of the two long distances come as stored blocks to keep the streams short)"""
     cases = []
     for d in COPY_DIST:
         for ln in COPY_LEN:
-            s = Stream()
+            s = begin()
             pre = text(d, d + ln)
             if d > 600:
                 s.stored(pre)
@@ -325,7 +343,7 @@ def copy_grid():
     return cases
 
 
-def copy_chains():
+def copy_chains(begin=Stream):
     """overlapping copies whose source is the previous copy's output, with literals between some of them"""
     cases = []
     for k, plan in enumerate((
@@ -333,7 +351,7 @@ def copy_chains():
             [(258, 5), (258, 258), (258, 259), (258, 129), (258, 63), (3, 258)],
             [(5, 4), (7, 5), (9, 7), (64, 9), (65, 64), (66, 65), (130, 66), (131, 130)],
             [(ln, d) for d in (1, 2, 3, 63, 64, 65) for ln in (64, 65, 3)])):
-        s = Stream().fixed(final=True).lit(text(9, k))
+        s = begin().fixed(final=True).lit(text(9, k))
         for i, (ln, d) in enumerate(plan):
             while len(s.out) < d:
                 s.lit(text(1, i))
@@ -345,15 +363,15 @@ def copy_chains():
     return cases
 
 
-def copy_residues():
+def copy_residues(begin=Stream):
     """the destination of a copy at every residue mod 16 (a literal prefix of 0..15 bytes behind 16 stored bytes)"""
     cases = []
     for r in range(16):
-        s = Stream().fixed(final=True).lit(text(16 + r, r))
+        s = begin().fixed(final=True).lit(text(16 + r, r))
         s.match(70, 16).match(200, 3).lit(b"#").match(258, 100).eob()
         cases.append(Case("copy_residue_%d" % r, RAW, s.raw(), s.out))
     for r in range(16):  # ... and a literal run of more than 64 bytes starting there
-        s = Stream().fixed(final=True).lit(text(r + 3, r)).match(3, 3).lit(text(150, 100 + r)).eob()
+        s = begin().fixed(final=True).lit(text(r + 3, r)).match(3, 3).lit(text(150, 100 + r)).eob()
         cases.append(Case("literal_run_residue_%d" % r, RAW, s.raw(), s.out))
     return cases
 
@@ -364,11 +382,11 @@ def _ladder_tables():
     return ladder(lit_syms, 286), ladder(dist_syms, 30)
 
 
-def table_shapes():
+def table_shapes(begin=Stream):
     cases = []
     # codes of up to 15 bits on both alphabets
     ll, dl = _ladder_tables()
-    s = Stream().dynamic(ll, dl, final=True)
+    s = begin().dynamic(ll, dl, final=True)
     s.lit(b"etaoinshrdluetaoinshrdlu" * 3)
     for ln, d in ((3, 1), (3, 2), (3, 3), (3, 4), (3, 5), (3, 7), (3, 9), (3, 17), (3, 33), (11, 65), (12, 40), (258, 3)):
         s.match(ln, d)
@@ -378,31 +396,33 @@ def table_shapes():
     # one literal and end-of-block; no distance code at all (one length of zero)
     lens = [0] * 257
     lens[ord("x")] = lens[256] = 1
-    s = Stream().dynamic(lens, [0], final=True).lit(b"x" * 77).eob()
+    s = begin().dynamic(lens, [0], final=True).lit(b"x" * 77).eob()
     cases.append(Case("single_literal_plus_eob", RAW, s.raw(), s.out))
     # exactly one distance code of length 1 (zlib's exception to "incomplete")
     lens = balanced([ord("a"), ord("b"), 256, 257, 258], 259)
-    s = Stream().dynamic(lens, [0, 0, 1], final=True).lit(b"aba").match(3, 3).match(4, 3).lit(b"b").eob()
+    s = begin().dynamic(lens, [0, 0, 1], final=True).lit(b"aba").match(3, 3).match(4, 3).lit(b"b").eob()
     cases.append(Case("one_distance_code_of_length_1", RAW, s.raw(), s.out))
     # HLIT = 286, HDIST = 30; HCLEN = 19 and the smallest HCLEN that can carry a non-zero length (5: symbols 16 17 18 0 8)
     lit8 = [8] * 255 + [0, 8] + [0] * 29      # 256 codes of 8 bits: literals 0..254 and end-of-block
     cl5 = [0] * 19
     cl5[16] = cl5[17] = 3
     cl5[18] = cl5[0] = cl5[8] = 2
-    s = Stream().dynamic(lit8, [0] * 30, final=True, cl_lens=cl5).lit(bytes(range(255))).eob()
-    assert int.from_bytes(s.raw()[:3], "little") >> 13 & 15 == 1   # HCLEN field 1: five lengths
+    s = begin()
+    at = s.w.bit_length
+    s.dynamic(lit8, [0] * 30, final=True, cl_lens=cl5).lit(bytes(range(255))).eob()
+    assert int.from_bytes(s.raw()[at >> 3:(at >> 3) + 4], "little") >> (at & 7) >> 13 & 15 == 1   # HCLEN field 1: five lengths
     cases.append(Case("hlit286_hdist30_hclen5", RAW, s.raw(), s.out))
     full = balanced(list(range(256)) + list(range(256, 286)), 286)
     cl19 = [5] * 6 + [4] * 13
     assert kraft(cl19) == 32768
-    s = Stream().dynamic(full, balanced(list(range(30)), 30), final=True, cl_lens=cl19, hclen=19, runs=False)
+    s = begin().dynamic(full, balanced(list(range(30)), 30), final=True, cl_lens=cl19, hclen=19, runs=False)
     s.lit(bytes(range(256))).match(258, 256).match(3, 1).match(10, 24577 // 64).eob()
     cases.append(Case("hlit286_hdist30_hclen19", RAW, s.raw(), s.out))
     # HCLEN = 4 can only say "zero": no end-of-block code
     cl4 = [0] * 19
     cl4[16] = cl4[17] = cl4[18] = cl4[0] = 2
-    s = Stream().dynamic([0] * 257, [0], final=True, cl_lens=cl4, hclen=4)
-    cases.append(Case("hclen4_all_zero", RAW, s.raw(), b"", E_DATA))
+    s = begin().dynamic([0] * 257, [0], final=True, cl_lens=cl4, hclen=4)
+    cases.append(Case("hclen4_all_zero", RAW, s.raw(), s.out, E_DATA))
     # a run across the HLIT boundary, with each of the three repeat codes (HLIT = 260: symbols 0..259)
     for rep in (16, 17, 18):
         lit = [0] * 260
@@ -420,18 +440,19 @@ def table_shapes():
             ops = rle_ops(lit[:258]) + [(rep, zeros - (3 if rep == 17 else 11)), (1, None), (1, None)]
             far = DIST_BASE[len(dist) - 2]
         assert kraft(lit) == 32768 and kraft(dist) == 32768
-        s = Stream().dynamic(lit, dist, final=True, ops=ops)
+        s = begin().dynamic(lit, dist, final=True, ops=ops)
         s.lit((b"pqqp" * 10)[:far + 1]).match(3, far).lit(b"q").eob()
         cases.append(Case("run_across_hlit_%d" % rep, RAW, s.raw(), s.out))
     # stored blocks: 65 535 bytes, and an empty one between two others
     big = text(65535, 9)
-    cases.append(Case("stored_65535", RAW, Stream().stored(big, final=True).raw(), big))
-    s = Stream().stored(b"abc").stored(b"").fixed().lit(b"de").eob().stored(b"", final=True)
+    s = begin().stored(big, final=True)
+    cases.append(Case("stored_65535", RAW, s.raw(), s.out))
+    s = begin().stored(b"abc").stored(b"").fixed().lit(b"de").eob().stored(b"", final=True)
     cases.append(Case("stored_empty", RAW, s.raw(), s.out))
     # the final bit of the stream at bit 7 and at bit 0 of the entry's last byte
     for want in (7, 0):
         for k in range(8):     # (literals from 144 on take 9 bits: each moves the end by one bit)
-            s = Stream().fixed(final=True).lit(text(5, 3)).lit(bytes([200]) * k).eob()
+            s = begin().fixed(final=True).lit(text(5, 3)).lit(bytes([200]) * k).eob()
             if (s.w.bit_length - 1) % 8 == want:
                 break
         else:
@@ -440,9 +461,9 @@ def table_shapes():
     return cases
 
 
-def containers():
+def containers(begin=Stream):
     body = text(300, 4)
-    s = Stream().fixed(final=True).lit(body[:200]).match(50, 200).lit(body[200:]).eob()
+    s = begin().fixed(final=True).lit(body[:200]).match(50, 200).lit(body[200:]).eob()
     raw, data = s.raw(), bytes(s.out)
     cases = []
     g = lambda label, verdict=OK, d=data, **kw: cases.append(Case("gzip_" + label, GZIP, gzip_wrap(raw, data, **kw), d, verdict))
@@ -480,19 +501,19 @@ def containers():
     for bit in (0, 16, 31):
         z("adler_bit_%d" % bit, E_DATA, adler=adler32(data) ^ (1 << bit))
     # the empty stream in each container
-    e = Stream().fixed(final=True).eob().raw()
-    cases.append(Case("zlib_empty", ZLIB, zlib_wrap(e, b""), b""))
-    cases.append(Case("gzip_empty", GZIP, gzip_wrap(e, b""), b""))
+    e = begin().fixed(final=True).eob()
+    cases.append(Case("zlib_empty", ZLIB, zlib_wrap(e.raw(), e.out), e.out))
+    cases.append(Case("gzip_empty", GZIP, gzip_wrap(e.raw(), e.out), e.out))
     return cases
 
 
-def malformed():
+def malformed(begin=Stream):
     """one stream for every class of BZ_E_DATA in the contract (the container classes are in containers()), each with
     some good bytes in front of the fault, and a few BZ_E_EOF shapes that are not plain cuts of an encoder's stream"""
     cases = []
     pre = text(40, 6)
     add = lambda name, s, verdict=E_DATA, pad=0, note="": cases.append(Case(name, RAW, s.raw(pad), s.out, verdict, note))
-    start = lambda: Stream().fixed().lit(pre).eob()
+    start = lambda: begin().fixed().lit(pre).eob()
     s = start()
     s.header(True, 3)
     add("btype3", s, pad=0xFF)
@@ -539,10 +560,15 @@ def malformed():
         s = start().fixed(final=True).lit(b"zz").sym(257).dsym(sy)
         s.w.put(0x3FFFFFFF, 30)
         add("distance_symbol_%d" % sy, s, pad=0xFF)
-    s = Stream().fixed(final=True).lit(pre).match(5, len(pre) + 1, emit=False).lit(b"never").eob()
-    cases.append(Case("distance_too_far", RAW, s.raw(0xFF), pre, E_DATA))
-    s = Stream().fixed(final=True).match(3, 1, emit=False).eob()
-    cases.append(Case("distance_at_the_start", RAW, s.raw(0xFF), b"", E_DATA))
+    s = begin().fixed(final=True).lit(pre)          # one byte in front of ALL output so far
+    good = bytes(s.out)
+    assert len(good) + 1 <= 32768
+    s.match(5, len(good) + 1, emit=False).lit(b"never").eob()
+    cases.append(Case("distance_too_far", RAW, s.raw(0xFF), good, E_DATA))
+    s = begin().fixed(final=True)                    # one byte in front of the entry's output
+    good = bytes(s.out)
+    s.match(3, len(good) + 1, emit=False).eob()
+    cases.append(Case("distance_at_the_start", RAW, s.raw(0xFF), good, E_DATA))
     # the unused code of a one-code distance set, and a distance code where there is none at all
     lens = balanced([ord("a"), ord("b"), 256, 257], 258)
     s = start().dynamic(lens, [1], final=True).lit(b"ab").sym(257)
@@ -553,37 +579,160 @@ def malformed():
     s.w.put(0x3FFFFFFF, 30)
     add("no_distance_codes", s, pad=0xFF, note="zlib raises before it hands out the last literals")
     # ---- BZ_E_EOF shapes
-    cases.append(Case("empty_entry", RAW, b"", b"", E_EOF))
+    s = begin()
+    cases.append(Case("empty_entry", RAW, s.raw(), s.out, E_EOF))
     s = start()
     cases.append(Case("no_final_block", RAW, s.raw(), s.out, E_EOF))
     s = start()
     s.header(True, 0)
     cases.append(Case("stored_without_len", RAW, s.raw(), s.out, E_EOF))
     s = start().stored(b"0123456789", final=True)
-    cases.append(Case("stored_cut_short", RAW, s.raw()[:-3], pre, E_EOF, note="zlib yields the bytes that are there"))
+    cases.append(Case("stored_cut_short", RAW, s.raw()[:-3], start().out, E_EOF, note="zlib yields the bytes that are there"))
     s = start().fixed(final=True).lit(b"abc")
+    if s.w.n == 1:         # (seven padding bits of zero would BE the end-of-block code: a 9-bit literal leaves six)
+        s.lit(bytes([200]))
     cases.append(Case("no_end_of_block", RAW, s.raw(), s.out, E_EOF))
     s = start().dynamic(ok_lit, [1, 1], final=True)
-    cases.append(Case("cut_in_dynamic_header", RAW, s.raw()[:len(start().raw()) + 3], pre, E_EOF))
+    cases.append(Case("cut_in_dynamic_header", RAW, s.raw()[:len(start().raw()) + 3], start().out, E_EOF))
     return cases
 
 
-def quirk_like():
+def quirk_like(begin=Stream):
     """what the reference's encoder writes for a dynamic block without any match: HDIST = 0 and NO distance code length
     at all (src/deflate/encoder.rs:431-436, 449-451) -- one length short of what the header announces, so the first code
     of the data is read as that length and everything behind it is shifted"""
     lens = balanced([ord("a"), ord("b"), ord("c"), 256], 257)
-    s = Stream().dynamic(lens, [0], final=True, ops=rle_ops(lens))   # (the operations stop after the 257 lengths)
+    s = begin()
+    good = bytes(s.out)
+    s.dynamic(lens, [0], final=True, ops=rle_ops(lens))   # (the operations stop after the 257 lengths)
     s.lit(b"abcabc").eob()
-    return Case("match_free_dynamic_block_of_the_reference", RAW, s.raw(), b"", E_DATA, note="verdict class and prefix are whatever the contract gives")
+    return Case("match_free_dynamic_block_of_the_reference", RAW, s.raw(), good, E_DATA, note="verdict class and prefix are whatever the contract gives")
 
 
-def clean_cases():
-    return copy_grid() + copy_chains() + copy_residues() + [c for c in table_shapes() + containers() if c.verdict == OK]
+# ------------------------------------------------------------------------------------------------- preambles
+# A case built behind a preamble is decoded, in an entry that is split into pieces (csrc/inf_split.h), by a wave that did
+# not start at the entry's first bit: the preamble's last block starts at a candidate of a later piece.
+def piece_tables():
+    """the tables of a preamble's dynamic blocks: printable ASCII, end-of-block, all 29 length and all 30 distance symbols"""
+    return balanced(list(range(32, 127)) + list(range(256, 286)), 286), balanced(list(range(30)), 30)
 
 
-def malformed_cases():
-    return [c for c in table_shapes() + containers() if c.verdict != OK] + malformed()
+def to_next_piece(s, phase, mode, piece=1024, lead=0, skip=0, seed=1):
+    """Behind a closed block of `s`: a stored block of text() -- printable ASCII holds no LEN / NLEN pair -- whose payload
+    runs 40 bytes into the next piece (`skip` pieces further; the entry starts `lead` bytes in front of the stream), then
+    a fixed block: a stored block in front of a fixed one is no candidate, and nothing in a fixed block is.  mode 0: the
+    fixed block's 9-bit literals move the next block header to a bit = phase (mod 32) of the entry.  mode 1: its 8-bit
+    literals move the LEN field of a five-byte stored block behind it to a byte = phase (mod 4); the caller's next block
+    has to be a dynamic one, which makes that LEN field a candidate.  The caller's next block is decoded from the mark."""
+    len_at = lead + (s.w.bit_length + 3 + 7) // 8
+    n = ((len_at + 4) // piece + 1 + skip) * piece - (len_at + 4) + 40
+    s.stored(text(n, seed))
+    s.fixed()
+    if mode == 0:
+        here = 8 * lead + s.w.bit_length + 7          # (+ 7: the end-of-block code)
+        s.lit(bytes([200]) * ((phase - here) * 25 % 32))      # 9 * 25 = 1 (mod 32)
+        s.eob()
+        assert (8 * lead + s.w.bit_length) % 32 == phase
+        s.marks.append((s.w.bit_length, 0, len(s.out)))
+    else:
+        here = lead + (s.w.bit_length + 7 + 3 + 7) // 8     # the LEN field without any literal
+        s.lit(b"=" * ((phase - here) % 4))
+        s.eob()
+        at = (s.w.bit_length + 3 + 7) // 8
+        assert (lead + at) % 4 == phase
+        s.marks.append((8 * at, 1, len(s.out)))
+        s.stored(text(5, seed + 1))
+    return s
+
+
+def preamble(phase, mode, piece=1024, lead=0, skip=0):
+    """A stream of at least one piece and (without skip) about 1 KiB of output whose last block D, a non-final dynamic one,
+    is decoded by a wave that starts at the first candidate of a later piece: mode 0, the header of D at a bit = phase
+    (mod 32); mode 1, the LEN field of a short stored block in front of D at a byte = phase (mod 4).  marks[0] names it."""
+    s = Stream().fixed().lit(b"in front").eob()
+    to_next_piece(s, phase, mode, piece, lead, skip)
+    ll, dl = piece_tables()
+    return s.dynamic(ll, dl).lit(b"a later piece ").match(6, 3).eob()
+
+
+def source_map_cases(piece=1024):
+    """What a piece's source map has to get right at its start.  Behind a preamble a filler to the next piece, then the
+    dynamic block D2: k literals (0, 1, 2), one match of every COPY_DIST x COPY_LEN with a distance above k -- it lies
+    wholly in front of the piece, or for d < len straddles its start: sources in front of the piece and (k > 0) the
+    piece's own literals take turns -- then 70 bytes at distance len, a copy of what that match gave (unresolved bytes,
+    whole or in part), a literal, end of block.  A filler again, and D3 in the third piece copies 40 of those bytes: a
+    pointer to a pointer.  Case.unresolved: the bytes whose value lies in front of the piece they are in."""
+    ll, dl = piece_tables()
+    cases = []
+    for k in (0, 1, 2):
+        for d in COPY_DIST:
+            for ln in COPY_LEN:
+                if d <= k:
+                    continue
+                s = preamble(13, 0, piece, skip=32 if d > 2000 else 0)
+                to_next_piece(s, (7 * d + ln) % 32, 0, piece, seed=2)
+                s.dynamic(ll, dl).lit(text(k, 5))
+                at = len(s.out)
+                s.match(ln, d).match(70, ln).lit(b"+").eob()
+                to_next_piece(s, (3 * d + ln + k) % 32, 0, piece, seed=3)
+                s.dynamic(ll, dl).match(40, len(s.out) - at).lit(b".").eob()
+                s.fixed(final=True).lit(b"end").eob()
+                c = Case("source_map_k%d_d%d_l%d" % (k, d, ln), RAW, s.raw(), s.out)
+                starts = [0] + [m[2] for m in s.marks]
+                c.pieces = len(starts)
+                c.marks = [m[:2] for m in s.marks]
+                c.unresolved = sum(r < max(b for b in starts if b <= i) for i, r in enumerate(s.root))
+                cases.append(c)
+    return cases
+
+
+def clean_cases(begin=Stream):
+    return copy_grid(begin) + copy_chains(begin) + copy_residues(begin) + [c for c in table_shapes(begin) + containers(begin) if c.verdict == OK]
+
+
+def malformed_cases(begin=Stream):
+    return [c for c in table_shapes(begin) + containers(begin) if c.verdict != OK] + malformed(begin)
+
+
+BUILDERS = (copy_grid, copy_chains, copy_residues, table_shapes, containers, malformed)
+
+
+@functools.lru_cache(maxsize=None)
+def _builder_of():
+    return {c.name: b for b in BUILDERS for c in b()}
+
+
+def behind(phase, mode, piece=1024, names=None):
+    """(clean, malformed): the corpus -- or its cases `names` -- built behind preamble(phase, mode), each name with the
+    preamble's in front (Case.base: the name without it); quirk_like() is one of the malformed ones"""
+    first = preamble(phase, mode, piece)
+    begin = first.clone
+    if names is None:
+        clean, bad = clean_cases(begin), malformed_cases(begin) + [quirk_like(begin)]
+    else:
+        made = [c for b in BUILDERS if any(_builder_of()[n] is b for n in names) for c in b(begin)]
+        clean, bad = [c for c in made if c.verdict == OK], [c for c in made if c.verdict != OK]
+    for c in clean + bad:
+        c.base, c.name = c.name, "p%dm%d_%s" % (phase, mode, c.name)
+    keep = lambda cs: [c for c in cs if names is None or c.base in names]
+    return keep(clean), keep(bad)
+
+
+TAILS = (1024, 1025, 2049)
+
+
+def tailed(cases):
+    """the cases (none of them E_EOF) with 0xFF bytes behind their stream, up to 1 024, 1 025 or 2 049 bytes in turn -- a
+    piece, a piece + 1, two pieces + 1; a stream that is longer than that already takes the next of them, or none.  Bytes
+    behind a stream are ignored, behind a fault they could only turn an EOF into the DATA the case names already, and
+    0xFF bytes hold no candidate: neither three header bits 0 1 0 nor a LEN ^ NLEN of 0xFFFF."""
+    out = []
+    for i, c in enumerate(cases):
+        assert c.verdict != E_EOF
+        want = [TAILS[(i + k) % 3] for k in range(3)]
+        n = next((t for t in want if t >= len(c.stream)), len(c.stream))
+        out.append(Case(c.name + "_tail", c.kind, c.stream + b"\xFF" * (n - len(c.stream)), c.data, c.verdict, c.note))
+    return out
 
 
 def cut_points(n):

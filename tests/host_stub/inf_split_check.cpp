@@ -1,6 +1,7 @@
 // inf_split_check.cpp -- csrc/inf_split.h on the CPU (tests/test_inf_split_host.py).
 //
 //   inf_split_check FILE
+//   inf_split_check --first PIECE_BYTES FILE
 //
 // 1. The candidate rules.  FILE holds streams, each with the bit positions the test knows about:
 //        stream NAME NBYTES NPOS
@@ -12,6 +13,10 @@
 //    ("false NAME COUNT").  The prefilter may never reject what the whole check accepts.
 // 2. The chain.  Synthetic streams -- true block boundaries, true and false candidates, an end -- driven through
 //    infsplit::chain_next as the host loop of df_split_sizes drives it, against a straightforward serial walk.
+// --first: the search alone.  For every stream of FILE (the listed positions are read and ignored) and every piece of
+//    PIECE_BYTES but the first, the first position of the piece's own span that the rules accept, as k_df_split_search
+//    finds it (a dynamic header goes before a LEN field at the same bit): "first NAME PIECE POS MODE"; nothing for a piece
+//    without a candidate.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -96,6 +101,52 @@ static void candidate_rules(const char *path)
             if ((bit & 7u) == 0 && stored_ok(s, bit) && !listed.count({bit, 1u})) ++extra;
         }
         printf("false %s %llu\n", name, extra);
+        free(buf);
+    }
+    fclose(f);
+    CHECK(streams > 0, "no stream in %s", path);
+}
+
+static void first_candidates(const char *path, unsigned long long piece_bytes)
+{
+    FILE *f = fopen(path, "r");
+    if (!f || piece_bytes == 0) {
+        printf("FAIL: cannot open %s, or a piece of no bytes\n", path);
+        ++fails;
+        return;
+    }
+    char name[256];
+    unsigned long long nbytes, npos;
+    int streams = 0;
+    while (fscanf(f, " stream %255s %llu %llu", name, &nbytes, &npos) == 3) {
+        ++streams;
+        uint8_t *buf = (uint8_t *)malloc(nbytes ? nbytes : 1);
+        for (unsigned long long i = 0; i < nbytes; ++i) {
+            unsigned v = 0;
+            if (fscanf(f, "%2x", &v) != 1) CHECK(false, "%s: short hex", name);
+            buf[i] = (uint8_t)v;
+        }
+        for (unsigned long long k = 0; k < npos; ++k) {
+            unsigned long long pos;
+            unsigned mode, expect;
+            if (fscanf(f, "%llu %u %u", &pos, &mode, &expect) != 3) {
+                CHECK(false, "%s: short position list", name);
+                break;
+            }
+        }
+        const BitSrc s{buf, nbytes};
+        const uint64_t total = 8 * nbytes;
+        for (uint64_t k = 1; 8 * k * piece_bytes < total; ++k) {
+            const uint64_t lo = 8 * k * piece_bytes, hi = lo + 8 * piece_bytes < total ? lo + 8 * piece_bytes : total;
+            for (uint64_t bit = lo; bit < hi; ++bit) {
+                bool pre = false;
+                const bool dyn = dyn_at(s, bit, pre) && pre;
+                if (dyn || ((bit & 7u) == 0 && stored_ok(s, bit))) {
+                    printf("first %s %llu %llu %u\n", name, (unsigned long long)k, (unsigned long long)bit, dyn ? 0u : 1u);
+                    break;
+                }
+            }
+        }
         free(buf);
     }
     fclose(f);
@@ -269,8 +320,13 @@ static void chain_rules()
 
 int main(int argc, char **argv)
 {
+    if (argc == 4 && strcmp(argv[1], "--first") == 0) {
+        first_candidates(argv[3], strtoull(argv[2], nullptr, 10));
+        if (fails == 0) printf("ok\n");
+        return fails ? 1 : 0;
+    }
     if (argc != 2) {
-        printf("usage: inf_split_check FILE\n");
+        printf("usage: inf_split_check FILE | inf_split_check --first PIECE_BYTES FILE\n");
         return 2;
     }
     candidate_rules(argv[1]);

@@ -31,10 +31,10 @@ def eng():
     e.close()
 
 
-def split_run(eng, monkeypatch, kind, entries, want, piece, need_split=True):
-    """the entries through the split path (threshold 4 KiB) against `want` ([(bytes, verdict)], None: whatever the one-wave
-    path says) and against the one-wave path; returns (results, split stats)"""
-    monkeypatch.setenv("BZ_DF_INF_SPLIT_KIB", "4")
+def split_run(eng, monkeypatch, kind, entries, want, piece, need_split=True, split=4):
+    """the entries through the split path (threshold `split` KiB) against `want` ([(bytes, verdict)], None: whatever the
+    one-wave path says) and against the one-wave path; returns (results, split stats)"""
+    monkeypatch.setenv("BZ_DF_INF_SPLIT_KIB", str(split))
     monkeypatch.setenv("BZ_DF_INF_PIECE_KIB", str(piece))
     got = Pack(entries).decode(eng, kind)
     st = eng.deflate_decode_split_stats()
@@ -52,7 +52,7 @@ def split_run(eng, monkeypatch, kind, entries, want, piece, need_split=True):
             assert g[0] == w[0], "entry %d: %d bytes, expected %d" % (i, len(g[0]), len(w[0]))
     print("split stats", st)
     if need_split:
-        big = sum(len(g[0]) for g, e in zip(got, entries) if len(e) >= 4096)
+        big = sum(len(g[0]) for g, e in zip(got, entries) if len(e) >= split * 1024)
         assert st[0] >= 1 and st[2] >= 2 and st[4] < big / 2, st
     return got, st
 
@@ -176,7 +176,8 @@ def test_window_chain_of_a_repeated_pattern(eng, monkeypatch):
     assert st[5] > 0 and st[6] >= 3
 
 
-def test_window_chain_forged(eng, monkeypatch):
+def window_chain_forged():
+    """(stream, data): a distance-1 run through 400 blocks, 40 pieces of stored bytes, and two far copies"""
     ll, dl = letters()
     s = F.Stream().dynamic(ll, dl).lit(b"z")
     marks = []
@@ -190,7 +191,12 @@ def test_window_chain_forged(eng, monkeypatch):
     s.stored(tail)                                   # 40 pieces of which 39 have no candidate
     s.dynamic(ll, dl).lit(b"far ").match(258, 32768).match(10, 32767).lit(b" away").eob()
     s.fixed(final=True).lit(b".").eob()
-    got, st = split_run(eng, monkeypatch, 0, [s.raw()], [(bytes(s.out), OK)], 1)
+    return s.raw(), bytes(s.out)
+
+
+def test_window_chain_forged(eng, monkeypatch):
+    z, data = window_chain_forged()
+    got, st = split_run(eng, monkeypatch, 0, [z], [(data, OK)], 1)
     assert st[5] > 0 and st[6] >= 3
 
 
