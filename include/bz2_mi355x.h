@@ -144,7 +144,7 @@ int bz_encode_buffer_multi(int level, const int *devices, int n_devices, const u
 int bz_encode_batch(int level, int device, const uint8_t *const *ins, const size_t *lens, size_t count,
                     uint8_t **out, uint64_t *out_off, uint64_t *out_len);
 void bz_free(void *p);
-/* Contexts and one-shot calls park their engines (batch workspace: about 35.3 MB of HBM per block of the largest
+/* Contexts and one-shot calls park their engines (batch workspace: about 36.3 MB of HBM per block of the largest
  * chunk seen, i.e. up to ~9 GB per lane with the default 192 MiB chunks, two lanes per listed device), device staging
  * buffers and 2 x BZ_ENC_CHUNK_MIB of pinned host memory in a per-process cache (two device lists at most) when they
  * end, so that the next one does not pay hipMalloc / hipHostMalloc again (fresh device memory costs about 40 ms per
@@ -175,11 +175,11 @@ int bz_peer_copy_selftest(const int *devices, int n_devices, size_t bytes, int *
  * ======================================================================== */
 typedef struct bz_gpu_engine bz_gpu_engine;
 
-/* max_blocks_in_flight bounds the workspace (about 35.3 MB of HBM per
+/* max_blocks_in_flight bounds the workspace (about 36.3 MB of HBM per
  * block); inputs with more blocks are processed in several batches. */
 int bz_gpu_engine_create(bz_gpu_engine **out, int device, size_t max_blocks_in_flight);
 void bz_gpu_engine_destroy(bz_gpu_engine *g);
-/* The batch workspace (about 35.3 MB per block in flight) is made by the first call that needs it and grows with the
+/* The batch workspace (about 36.3 MB per block in flight) is made by the first call that needs it and grows with the
  * largest call seen; a caller who knows the size of the calls to come reserves it once (fresh device memory costs about
  * 40 ms per GiB here: growing means freeing and paying again). */
 int bz_gpu_engine_reserve(bz_gpu_engine *g, size_t blocks);
@@ -410,6 +410,14 @@ int bz_gpu_profile_get(bz_gpu_engine *g, int idx, const char **name, uint64_t *l
 
 /* Rotation order of ONE block (src/suffix_array/sais.rs:266 `bwt`). */
 int bz_gpu_debug_bwt(bz_gpu_engine *g, const uint8_t *h_block, size_t n, uint32_t *h_sa);
+/* The MTF + zero-run stage alone on `nb` last columns (column i: h_cols + h_off[i], h_len[i] bytes, 1 .. 900000),
+ * run as an encode runs it on a batch of nb blocks; the bytes in use are taken from the columns.  heads: 1 / 0 force
+ * the form that ranks only the run heads / every position, -1 follows BZ_MTF_HEADS.  Per column: its symbols (RUNA 0,
+ * RUNB 1, rank r > 0 as r + 1, EOB last) at h_sym + i * sym_stride (sym_stride > every h_len[i]), their number, the
+ * number of bytes in use and the 258 symbol counts at h_freq + 258 i.  nb is bounded by max_blocks_in_flight. */
+int bz_gpu_debug_mtf(bz_gpu_engine *g, size_t nb, const uint8_t *h_cols, const uint64_t *h_off, const uint32_t *h_len,
+                     int heads, uint16_t *h_sym, size_t sym_stride, uint32_t *h_mtf_count, uint32_t *h_in_use,
+                     uint32_t *h_freq);
 /* Code lengths of one table (EncoderInner::create_huffman,
  * src/bzip2/encoder.rs:641-651) through the device code.  alpha <= 258 and a total of
  * less than 2^20 occurrences (a block holds 900 001 symbols at most; the device's weights

@@ -88,7 +88,7 @@ EXPORTS = [
     "bz_gpu_partition_slab_finish", "bz_gpu_block_count", "bz_gpu_encode_blocks", "bz_gpu_assemble", "bz_gpu_encode_sharded",
     "bz_shard_comm_selftest", "bz_gpu_last_timings", "bz_shard_halo_bytes", "bz_shard_window", "bz_shard_slab_tiles", "bz_gpu_encode_sharded_window", "bz_gpu_last_shard_timings", "bz_gpu_last_shard_phases",
     "bz_gpu_last_bwt_stats", "bz_gpu_cut_stats", "bz_gpu_last_bwt_rounds", "bz_gpu_profile_enable", "bz_gpu_profile_kernels", "bz_gpu_profile_get",
-    "bz_gpu_debug_bwt", "bz_gpu_debug_code_lengths", "bz_gpu_debug_block_stats", "bz_gpu_debug_block_sections",
+    "bz_gpu_debug_bwt", "bz_gpu_debug_mtf", "bz_gpu_debug_code_lengths", "bz_gpu_debug_block_stats", "bz_gpu_debug_block_sections",
     "bz_gpu_decode_device", "bz_gpu_decode_device_sharded", "bz_gpu_last_decode_timings", "bz_gpu_last_decode_stats", "bz_decode_buffer",
     "bz_gpu_decode_batch_device", "bz_gpu_last_decode_batch_stats", "bz_decode_batch",
     "bz_dec_create", "bz_dec_write", "bz_dec_end", "bz_dec_read", "bz_dec_pending", "bz_dec_destroy",
@@ -201,6 +201,7 @@ def lib():
     L.bz_gpu_profile_kernels.argtypes = [vp]
     L.bz_gpu_profile_get.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), u64p, C.POINTER(C.c_double), u64p]
     L.bz_gpu_debug_bwt.argtypes = [vp, C.c_char_p, sz, u32p]
+    L.bz_gpu_debug_mtf.argtypes = [vp, sz, C.c_char_p, u64p, u32p, C.c_int, C.POINTER(C.c_uint16), sz, u32p, u32p, u32p]
     L.bz_gpu_debug_code_lengths.argtypes = [vp, u32p, sz, u8p, C.POINTER(C.c_int)]
     L.bz_gpu_debug_block_stats.argtypes = [vp, u32p, sz, szp]
     L.bz_gpu_debug_block_sections.argtypes = [vp, u32p, sz, szp]
@@ -1253,6 +1254,24 @@ class GpuEngine:
         sa = (C.c_uint32 * len(block))()
         _check(lib().bz_gpu_debug_bwt(self._h, block, len(block), sa))
         return list(sa)
+
+    def debug_mtf(self, columns, heads=-1):
+        """The MTF + zero-run stage on a batch of last columns: [(symbols, mtf_count, in_use_count, mtf_freq)] per column.
+        heads: 1 / 0 force the form that ranks only the run heads / every position, -1 follows BZ_MTF_HEADS."""
+        columns = [bytes(c) for c in columns]
+        nb = len(columns)
+        off, lens, pos = (C.c_uint64 * nb)(), (C.c_uint32 * nb)(), 0
+        for i, c in enumerate(columns):
+            off[i], lens[i] = pos, len(c)
+            pos += len(c)
+        stride = max(len(c) for c in columns) + 1
+        sym = (C.c_uint16 * (nb * stride))()
+        cnt, use, freq = (C.c_uint32 * nb)(), (C.c_uint32 * nb)(), (C.c_uint32 * (nb * 258))()
+        _check(lib().bz_gpu_debug_mtf(self._h, nb, b"".join(columns), off, lens, int(heads), sym, stride, cnt, use, freq))
+        out = []
+        for i in range(nb):
+            out.append((list(sym[i * stride:i * stride + cnt[i]]), int(cnt[i]), int(use[i]), list(freq[i * 258:(i + 1) * 258])))
+        return out
 
     def debug_code_lengths(self, freq):
         n = len(freq)

@@ -382,11 +382,20 @@ struct MtfArgs {
     u32 nb;
     u32 tiles;               // tiles of kSortTile bytes per block the ZLE launches cover (what the largest block needs)
     const u8 *L;             // [nb * kSlot] last column (raw bytes)
+    // the column without its repeats (k_mtf_heads_mark / k_mtf_heads_pack): with heads != 0 the MTF kernels run on
+    // (H, hcount[lb]) instead of (L, n), rank8 holds one rank per head and the ZLE kernels read it through headbits
+    u32 heads;               // 1: the collapsed form; 0: one rank per position (BZ_MTF_HEADS=0)
+    u32 dense_permille;      // a block with more than this many heads per 1000 positions is not collapsed (750; 1000: every block is)
+    u8 *H;                   // [nb * kSlot] the heads: the first byte of every run of equal bytes, in order
+    u16 *headbits;           // [nb * kSlot / 16] one bit per position: it is a head
+    u32 *hcount;             // [nb] heads of the block; bit 31 (kMtfDense, k_mtf.hip): nothing to collapse, the block stays (L, n)
+    u32 *tile_hcnt;          // [nb][kTilesPerBlock] heads inside each tile of kSortTile positions
+    u32 *tile_hbase;         // [nb][kTilesPerBlock] heads in front of each tile
     const u32 *inuse_bits;   // [nb][8]
     u8 *summ;                // [nb][kMaxMtfChunks][256] recency lists
     u16 *summ_len;           // [nb][kMaxMtfChunks]
     u8 *init_state;          // [nb][kMaxMtfChunks][256]
-    u8 *rank8;               // [nb * kSlot]
+    u8 *rank8;               // [nb * kSlot] MTF rank of every position (heads: of every head)
     int *ztile_last;         // [nb][kTilesPerBlock] last position with a non-zero rank
     u32 *ztile_cnt;          // [nb][kTilesPerBlock]
     u32 *zstate;             // [nb][kTilesPerBlock][4] look-back words of k_zle_fused
@@ -571,6 +580,7 @@ enum KernelId {
     // RLE1 front end (k_rle1.hip): which of its two forms wrote the image
     KID_RLE_ONEPASS,
     KID_RLE_SCATTER,
+    KID_MTF_HEADS,        // k_mtf_heads_mark + k_mtf_heads_pack (k_mtf.hip)
     KID_COUNT
 };
 struct KernelProf {
@@ -623,7 +633,7 @@ void launch_block_symbols(hipStream_t st, const BwtArgs &a, u32 *inuse_bits, u8 
 int run_bwt(hipStream_t st, const BwtArgs &a, u32 max_n, u64 total_n, unsigned long long *h_active,
             u64 *sorted_elems, KernelProf *prof, u64 *round_active /*[64] or null*/, bool wide_keys,
             u32 min_chars);
-void launch_mtf(hipStream_t st, const MtfArgs &a);
+void launch_mtf(hipStream_t st, const MtfArgs &a, KernelProf *prof = nullptr, u64 total_n = 0);
 inline bool env_verify() { return getenv("BZ_VERIFY") && atoi(getenv("BZ_VERIFY")) != 0; } // the self-check for every context and engine of the process
 // a few bytes for the host between launches (k_emit.hip): up to four device ranges, 0 = they are there and the stream's
 // earlier work is done

@@ -106,6 +106,14 @@ static constexpr WsBuf kWorkspace[] = {
     {&bz_gpu_engine::summ_len, (size_t)kMaxMtfChunks * 2, 0, false},
     {&bz_gpu_engine::init_state, (size_t)kMaxMtfChunks * 256, 0, false},
     {&bz_gpu_engine::rank8, kSlot, 64, false},
+    // the last column without its repeats (k_mtf.hip "M0"): buffers of their own -- the sort's `flags` and `ptext` are
+    // idle during the tail stages of encode_batch, but bz_gpu_debug_mtf and a redo on the main stream would each need
+    // the same argument, and 1.0 MB beside 35 is not worth one
+    {&bz_gpu_engine::mtf_heads_buf, kSlot, 64, false},
+    {&bz_gpu_engine::headbits, kSlot / 8, 64, false},
+    {&bz_gpu_engine::hcount, 4, 0, false},
+    {&bz_gpu_engine::tile_hcnt, (size_t)kTilesPerBlock * 4, 0, false},
+    {&bz_gpu_engine::tile_hbase, (size_t)kTilesPerBlock * 4, 0, false},
     // the packed text has its own buffer: in the pair form it takes up to 10 bits per position, more than rank8's bytes
     // (which it borrowed until round 7); `impure` of the period and link rounds still fits, its stride is kSlot
     {&bz_gpu_engine::ptext, kPtSlot, 64, false},
@@ -134,9 +142,9 @@ static constexpr WsBuf kWorkspace[] = {
     {&bz_gpu_engine::tile_state, (size_t)kTilesPerBlock * kMaxBins * 4, 0, true},
     {&bz_gpu_engine::tickets, 0, (size_t)kSortEpochs * 8 * 4 + 64, true},
 };
-// Per block in flight, before DevBuf's slack of one eighth: 35 314 412 bytes (31 685 356 without the fused radix passes).
+// Per block in flight, before DevBuf's slack of one eighth: 36 329 056 bytes (32 700 000 without the fused radix passes).
 // The batch workspace holds `ws_blocks` blocks in flight: as many as the call at hand needs (up to max_blocks, the batch
-// size), grown when a later call needs more -- a context that only ever sees small inputs does not take 35.3 MB x max_blocks.
+// size), grown when a later call needs more -- a context that only ever sees small inputs does not take 36.3 MB x max_blocks.
 static int ensure_workspace(bz_gpu_engine *g, size_t need_blocks)
 {
     if (need_blocks > g->max_blocks) need_blocks = g->max_blocks;
@@ -827,6 +835,16 @@ static MtfArgs make_mtf_args(bz_gpu_engine *g, u32 nb)
     ma.summ_len = g->summ_len.as<u16>();
     ma.init_state = g->init_state.as<u8>();
     ma.rank8 = g->rank8.as<u8>();
+    static const bool want_heads = !(getenv("BZ_MTF_HEADS") && atoi(getenv("BZ_MTF_HEADS")) == 0);
+    ma.heads = want_heads ? 1u : 0u;
+    // (measurements and tests: 1000 collapses every block, 0 none; the default's evidence is in profiles/r16_mtf_heads.md)
+    static const u32 dense_permille = getenv("BZ_MTF_DENSE_PERMILLE") ? (u32)std::min(1000, std::max(0, atoi(getenv("BZ_MTF_DENSE_PERMILLE")))) : 750u;
+    ma.dense_permille = dense_permille;
+    ma.H = g->mtf_heads_buf.as<u8>();
+    ma.headbits = g->headbits.as<u16>();
+    ma.hcount = g->hcount.as<u32>();
+    ma.tile_hcnt = g->tile_hcnt.as<u32>();
+    ma.tile_hbase = g->tile_hbase.as<u32>();
     ma.ztile_last = g->ztile_last.as<int>();
     ma.ztile_cnt = g->ztile_cnt.as<u32>();
     ma.zstate = g->zstate.as<u32>();
@@ -938,7 +956,7 @@ static int encode_batch(bz_gpu_engine *g, u32 nb, const std::vector<BlockDesc> &
         (void)hipEventRecord(ev_fork, g->st);
         (void)hipStreamWaitEvent(g->st2, ev_fork, 0);
         sp = span_begin(g, 2, g->st2);
-        launch_mtf(g->st2, ma);
+        launch_mtf(g->st2, ma, &g->prof, total_n);
         span_end(g, sp);
         sp = span_begin(g, 3, g->st2);
         launch_huffman(g->st2, make_huff_args(g, nb));
@@ -1924,6 +1942,71 @@ extern "C" int bz_gpu_debug_bwt(bz_gpu_engine *g, const uint8_t *h_block, size_t
     return BZ_OK;
 }
 
+// The MTF / ZLE stage alone, as encode_batch runs it, on `nb` last columns given by the host (column i: h_cols + h_off[i],
+// h_len[i] bytes).  The bytes in use are taken from the columns (a column is a permutation of its block).
+extern "C" int bz_gpu_debug_mtf(bz_gpu_engine *g, size_t nb, const uint8_t *h_cols, const uint64_t *h_off, const uint32_t *h_len,
+                                int heads, uint16_t *h_sym, size_t sym_stride, uint32_t *h_mtf_count, uint32_t *h_in_use,
+                                uint32_t *h_freq)
+{
+    if (!g || nb == 0 || !h_cols || !h_off || !h_len || !h_sym || !h_mtf_count || !h_in_use || !h_freq) return BZ_E_PARAM;
+    u32 max_n = 0;
+    u64 total_n = 0;
+    for (size_t i = 0; i < nb; ++i) {
+        if (h_len[i] == 0 || h_len[i] > kMaxBlockLen || sym_stride < (size_t)h_len[i] + 1u) return BZ_E_PARAM;
+        max_n = std::max(max_n, h_len[i]);
+        total_n += h_len[i];
+    }
+    HIPCHK(hipSetDevice(g->device));
+    int rc = ensure_workspace(g, nb);
+    if (rc != BZ_OK) return rc;
+    if (nb > g->ws_blocks) return BZ_E_PARAM;
+    std::vector<BlockDesc> descs(nb);
+    for (size_t i = 0; i < nb; ++i) {
+        descs[i].rle_off = (u64)i * kSlot; // (the column's slot: k_block_symbols reads it as the block's image)
+        descs[i].in_off = 0;
+        descs[i].in_end = h_len[i];
+        descs[i].n = h_len[i];
+        descs[i].pad = 0;
+        HIPCHK(hipMemcpyAsync(g->L.as<u8>() + i * kSlot, h_cols + h_off[i], h_len[i], hipMemcpyHostToDevice, g->st));
+    }
+    HIPCHK(hipMemcpyAsync(g->lblocks.p, descs.data(), nb * sizeof(BlockDesc), hipMemcpyHostToDevice, g->st));
+    BwtArgs ba = make_bwt_args(g, (u32)nb);
+    ba.rle = g->L.as<u8>();
+    launch_block_symbols(g->st, ba, g->inuse_bits.as<u32>(), const_cast<u8 *>(ba.sym_code), const_cast<u8 *>(ba.keyinfo));
+    MtfArgs ma = make_mtf_args(g, (u32)nb);
+    if (heads >= 0) ma.heads = heads != 0 ? 1u : 0u;
+    ma.tiles = std::min<u32>(kTilesPerBlock, std::max<u32>(1u, (max_n + kSortTile - 1u) / kSortTile));
+    launch_mtf(g->st, ma, nullptr, total_n);
+    if (ma.fused_zle) { // the ticket check of encode_batch: a one-launch ZLE stage that misbehaved is redone with the three kernels
+        u32 tk[9] = {};
+        const MailSeg sg = {tk, g->ztick.p, sizeof(tk)};
+        if (mail_fetch(g->st, &sg, 1) != 0) return BZ_E_UNEXPECTED;
+        bool bad = tk[8] != 0;
+        for (u32 x = 0; x < 8; ++x)
+            if (tk[x] != ma.tiles * (xcd_grid_y((u32)nb) / 8u)) bad = true;
+        if (bad) {
+            fprintf(stderr, "bz2_mi355x: the one-launch ZLE stage misbehaved (tile tickets / look-back); stage redone with three kernels\n");
+            g->zle_fused_broken = true;
+            ma.fused_zle = 0;
+            launch_mtf(g->st, ma, nullptr, total_n);
+        }
+    }
+    std::vector<BlockOut> outs(nb);
+    HIPCHK(hipMemcpyAsync(outs.data(), g->bout.p, nb * sizeof(BlockOut), hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipMemcpyAsync(h_freq, g->mtf_freq.p, nb * kMaxAlpha * 4, hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipStreamSynchronize(g->st));
+    for (size_t i = 0; i < nb; ++i) {
+        if (outs[i].mtf_count == 0 || outs[i].mtf_count > h_len[i] + 1u) return BZ_E_UNEXPECTED;
+        h_mtf_count[i] = outs[i].mtf_count;
+        h_in_use[i] = outs[i].in_use_count;
+        HIPCHK(hipMemcpyAsync(h_sym + i * sym_stride, g->mtf.as<u16>() + i * kMtfStride, (size_t)outs[i].mtf_count * 2,
+                              hipMemcpyDeviceToHost, g->st));
+    }
+    HIPCHK(hipStreamSynchronize(g->st));
+    HIPCHK(hipGetLastError());
+    return BZ_OK;
+}
+
 extern "C" int bz_gpu_debug_code_lengths(bz_gpu_engine *g, const uint32_t *h_freq, size_t alpha, uint8_t *h_len,
                                          int *took_length_limited_path)
 {
@@ -1954,7 +2037,7 @@ static const char *kKernelNames[KID_COUNT] = {"k_radix_hist", "k_radix_scan", "k
                                               "k_group_flags", "k_group_apply", "k_last_column",
                                               "k_radix_scatter_lb", "k_ghist_text", "k_ghist_scan", "k_rank_place", "k_phase_b_local", "k_group_refine",
                                               "k_dec_block", "k_dec_mtf", "k_dec_tsort", "k_dec_walk_lengths",
-                                              "k_dec_place", "k_dec_rle", "k_dec_crc", "k_rle_onepass", "k_rle_scatter"};
+                                              "k_dec_place", "k_dec_rle", "k_dec_crc", "k_rle_onepass", "k_rle_scatter", "k_mtf_heads"};
 
 extern "C" int bz_gpu_profile_enable(bz_gpu_engine *g, int on)
 {

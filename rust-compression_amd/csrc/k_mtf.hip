@@ -4,13 +4,18 @@
 // loop and zle_write of write_blockdata (src/bzip2/encoder.rs:324-358, 653-669).
 //
 // MTF is a serial recurrence on a <=256-entry list, made parallel the classic way:
-//   M1  every 256-symbol chunk reports its "recency list" (distinct symbols, most
+//   M0  (a.heads, the default) the column is collapsed first: only the first symbol of every run of equal bytes -- a
+//       head -- needs the list, every other position has rank 0.  M1-M3 then run on the heads H[0..m) instead of
+//       L[0..n), rank8 holds one rank per head, and Z1-Z3 find a position's rank through one bit per position;
+//       a block with more than 3/4 of its positions heads stays as it is, (L, n) and one rank per position;
+//   M1  every chunk of kMtfChunk = 512 symbols of the sequence reports its "recency list" (distinct symbols, most
 //       recent first) -- that is exactly the head of the MTF list after the chunk;
-//   M2  one wave per block composes the chunk reports left to right and stores the
-//       list each chunk starts from (3516 chunks/block, 256 B each);
-//   M3  one lane per chunk replays its 256 symbols against its start list held in
-//       LDS (65-dword stride => bank = lane + entry/4), 4 list entries per LDS
-//       access, and writes the rank bytes.
+//   M2  the reports are composed left to right in three short steps (merged prefixes inside groups of 32 chunks, one
+//       wave per block through the group totals, one link per chunk) and every chunk's start list is stored
+//       (at most 1758 chunks per block, 256 B each);
+//   M3  one lane per chunk replays its 512 symbols: rank = number of symbols used more recently, counted with packed
+//       16-bit compares against a table of last-use times in LDS ([pair of symbols][lane]: conflict-free), the same
+//       work for every lane whatever the data, and writes the rank bytes.
 // The list works on raw byte values, initialised with the in-use bytes in
 // increasing order, which is the same thing as the reference's unseq2seq mapping
 // (encoder.rs:304-318) because that mapping is monotone.
@@ -32,12 +37,143 @@ __device__ __forceinline__ u32 popc8(const u32 *b)
     return c;
 }
 
+__device__ __forceinline__ u32 block_excl_sum(u32 v, u32 *sh /*[kSortThreads / 64]*/, u32 &total)
+{
+    const u32 l = lane_id(), w = threadIdx.x >> 6;
+    const u32 inc = wave_incl_sum(v);
+    if (l == 63) sh[w] = inc;
+    __syncthreads();
+    u32 carry = 0, tot = 0;
+    for (u32 k = 0; k < kSortThreads / 64; ++k) {
+        if (k < w) carry += sh[k];
+        tot += sh[k];
+    }
+    total = tot;
+    __syncthreads();
+    return carry + inc - v;
+}
+
+// ---- M0: the last column without its repeats -------------------------------------------------
+// A symbol equal to its predecessor in the column is at the front of the list already: its rank is 0 and the list
+// does not move.  Only the first symbol of a run of equal bytes (a HEAD) needs the list.  With a.heads the kernels
+// M1-M3 below run on the sequence of heads H[0..m) instead of L[0..n): a repeat moves nothing, so the recency report of
+// a stretch of H is the report of the positions it stands for, and lanes that own kMtfChunk heads each do equal work
+// whatever the run lengths are.  The rank of head k goes to rank8[k]; for k >= 1 it is at least 1 (H[k] != H[k-1]).
+// The ZLE kernels find the rank of a position through `headbits` (zload).  Two launches, no device-side wait:
+//   k_mtf_heads_mark  one bit per position (set at 0 and wherever L[i] != L[i-1]; the byte in front of a thread's
+//                     16 positions is read, also across waves and tiles), heads per kSortTile-position tile;
+//   k_mtf_heads_pack  every tile sums the counts of the (at most 109) tiles in front of it, compacts its heads in LDS
+//                     and writes them out as whole words.
+// A block whose column is almost all heads (random bytes: 0.996) has nothing to collapse, and the ZLE load through the
+// bitmap costs more than the load of one rank per position (profiles/r16_mtf_heads.md): k_mtf_heads_pack marks a block
+// with more than a.dense_permille / 1000 (3/4; BZ_MTF_DENSE_PERMILLE) of its positions heads as DENSE in hcount[lb] and leaves it alone; every
+// kernel behind it takes such a block in the old form, (L, n) and one rank per position.  Such a block pays for the head
+// count and nothing else.
+constexpr u32 kMtfDense = 0x80000000u;
+__device__ __forceinline__ bool mtf_collapsed(const MtfArgs &a, u32 lb) { return a.heads && !(a.hcount[lb] & kMtfDense); }
+__device__ __forceinline__ u32 mtf_len(const MtfArgs &a, u32 lb) { return mtf_collapsed(a, lb) ? a.hcount[lb] : a.blocks[lb].n; }
+__device__ __forceinline__ const u8 *mtf_seq(const MtfArgs &a, u32 lb) { return (mtf_collapsed(a, lb) ? a.H : a.L) + (size_t)lb * kSlot; }
+
+__global__ __launch_bounds__(kSortThreads) void k_mtf_heads_mark(MtfArgs a)
+{
+    __shared__ u32 s_cnt[kSortThreads / 64];
+    const u32 lb = blockIdx.y, tile = blockIdx.x;
+    const u32 n = a.blocks[lb].n;
+    if (n == 0u && tile == 0u && threadIdx.x == 0u) a.hcount[lb] = 0u; // (no caller sends an empty block; no stale length if one does)
+    if (tile * kSortTile >= n) return;
+    const u8 *L = a.L + (size_t)lb * kSlot;
+    const u32 p0 = tile * kSortTile + threadIdx.x * 16u;
+    const u32 valid = p0 < n ? ((n - p0) < 16u ? (n - p0) : 16u) : 0u;
+    u32 hb = 0;
+    if (valid) {
+        const uint4 q = *reinterpret_cast<const uint4 *>(L + p0); // (slots are padded)
+        const u32 prev = p0 ? (u32)L[p0 - 1u] : 0u;
+        const u32 wv[4] = {q.x, q.y, q.z, q.w};
+        u32 carry = prev;
+#pragma unroll
+        for (u32 w = 0; w < 4; ++w) {
+            const u32 d = wv[w] ^ ((wv[w] << 8) | carry); // byte k: L[k] ^ L[k-1]
+            carry = wv[w] >> 24;
+#pragma unroll
+            for (u32 k = 0; k < 4; ++k) hb |= ((d >> (8u * k)) & 0xFFu) ? (1u << (4u * w + k)) : 0u;
+        }
+        if (p0 == 0u) hb |= 1u;
+        hb &= 0xFFFFu >> (16u - valid);
+        a.headbits[(((size_t)lb * kSlot) >> 4) + (p0 >> 4)] = (u16)hb;
+    }
+    const u32 c = wave_sum((u32)__popc(hb));
+    if (lane_id() == 0) s_cnt[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u32 t = 0;
+        for (u32 k = 0; k < kSortThreads / 64; ++k) t += s_cnt[k];
+        a.tile_hcnt[lb * kTilesPerBlock + tile] = t;
+    }
+}
+
+__global__ __launch_bounds__(kSortThreads) void k_mtf_heads_pack(MtfArgs a)
+{
+    __shared__ __attribute__((aligned(16))) u8 s_h[kSortTile + 16];
+    __shared__ u32 s_su[kSortThreads / 64];
+    __shared__ u32 s_pre[4];
+    const u32 lb = blockIdx.y, tile = blockIdx.x;
+    const u32 n = a.blocks[lb].n;
+    if (tile * kSortTile >= n) return;
+    const u8 *L = a.L + (size_t)lb * kSlot;
+    const u32 p0 = tile * kSortTile + threadIdx.x * 16u;
+    const bool valid = p0 < n;
+    if (threadIdx.x < 128u) { // heads of the tiles in front (kTilesPerBlock <= 128: the first two waves)
+        static_assert(kTilesPerBlock <= 128, "two waves sum the tiles in front");
+        const u32 ntiles = (n + kSortTile - 1u) / kSortTile;
+        const u32 c = threadIdx.x < ntiles ? a.tile_hcnt[lb * kTilesPerBlock + threadIdx.x] : 0u;
+        const u32 pre = wave_sum(threadIdx.x < tile ? c : 0u), all = wave_sum(c);
+        if (lane_id() == 0) {
+            s_pre[threadIdx.x >> 6] = pre;
+            s_pre[2u + (threadIdx.x >> 6)] = all;
+        }
+    }
+    __syncthreads();
+    const u32 m = s_pre[2] + s_pre[3]; // heads of the whole block
+    if ((u64)m * 1000u > (u64)n * a.dense_permille) { // dense: stays in the old form
+        if (tile == 0u && threadIdx.x == 0u) a.hcount[lb] = kMtfDense | m;
+        return;
+    }
+    const u32 hb = valid ? (u32)a.headbits[(((size_t)lb * kSlot) >> 4) + (p0 >> 4)] : 0u;
+    const uint4 q = valid ? *reinterpret_cast<const uint4 *>(L + p0) : make_uint4(0, 0, 0, 0);
+    u32 total;
+    const u32 excl = block_excl_sum((u32)__popc(hb), s_su, total);
+    const u32 base = s_pre[0] + s_pre[1];
+    const u32 al = base & 3u; // (a block's H starts at a multiple of 16: LDS byte al + i is H byte base + i, words line up)
+    {
+        const u32 wv[4] = {q.x, q.y, q.z, q.w};
+        u32 pos = al + excl;
+#pragma unroll
+        for (u32 k = 0; k < 16; ++k)
+            if ((hb >> k) & 1u) s_h[pos++] = (u8)(wv[k >> 2] >> ((k & 3) * 8));
+    }
+    __syncthreads();
+    u8 *dst = a.H + (size_t)lb * kSlot + (base - al);
+    const u32 endb = al + total;
+    for (u32 j = threadIdx.x; j * 4u < endb; j += kSortThreads) {
+        if (j * 4u >= al && j * 4u + 4u <= endb) {
+            reinterpret_cast<u32 *>(dst)[j] = reinterpret_cast<const u32 *>(s_h)[j];
+        } else {
+            for (u32 b = j * 4u; b < j * 4u + 4u; ++b)
+                if (b >= al && b < endb) dst[b] = s_h[b];
+        }
+    }
+    if (threadIdx.x == 0) {
+        a.tile_hbase[lb * kTilesPerBlock + tile] = base;
+        if (tile == 0u) a.hcount[lb] = m;
+    }
+}
+
 // ---- M1: recency list of each chunk ------------------------------------------------
 __global__ __launch_bounds__(256) void k_mtf_summaries(MtfArgs a)
 {
     __shared__ u32 s_seen[8 * 256]; // [word][thread]: conflict-free
     const u32 lb = blockIdx.y;
-    const u32 n = a.blocks[lb].n;
+    const u32 n = mtf_len(a, lb);
     const u32 chunk = blockIdx.x * 256u + threadIdx.x;
     const u32 beg = chunk * kMtfChunk;
     if (beg >= n) return;
@@ -45,7 +181,7 @@ __global__ __launch_bounds__(256) void k_mtf_summaries(MtfArgs a)
     const u32 alpha = popc8(a.inuse_bits + lb * 8);
 #pragma unroll
     for (int i = 0; i < 8; ++i) s_seen[i * 256 + threadIdx.x] = 0;
-    const u8 *L = a.L + (size_t)lb * kSlot;
+    const u8 *L = mtf_seq(a, lb);
     u8 *out = a.summ + ((size_t)lb * kMaxMtfChunks + chunk) * 256u;
     u32 cnt = 0;
     // walk backwards, 64 bytes per visit (four 16-byte loads issued together: a line is fetched once and used
@@ -134,7 +270,7 @@ __global__ __launch_bounds__(64) void k_mtf_merge_groups(MtfArgs a)
 {
     __shared__ u8 s_cur[256], s_new[256], s_mark[256];
     const u32 lb = blockIdx.y, l = threadIdx.x;
-    const u32 n = a.blocks[lb].n;
+    const u32 n = mtf_len(a, lb);
     const u32 nchunks = (n + kMtfChunk - 1) / kMtfChunk;
     const u32 c0 = blockIdx.x * kMtfGroup;
     if (c0 + 2u > nchunks) return; // (the last chunk's report is never applied)
@@ -166,7 +302,7 @@ __global__ __launch_bounds__(64) void k_mtf_group_starts(MtfArgs a)
 {
     __shared__ u8 s_state[256], s_new[256], s_mark[256];
     const u32 lb = blockIdx.x, l = threadIdx.x;
-    const u32 n = a.blocks[lb].n;
+    const u32 n = mtf_len(a, lb);
     const u32 nchunks = (n + kMtfChunk - 1) / kMtfChunk;
     const u32 *bits = a.inuse_bits + lb * 8;
     { // identity list: in-use byte values ascending (as in k_mtf_compose)
@@ -201,7 +337,7 @@ __global__ __launch_bounds__(256) void k_mtf_chunk_starts(MtfArgs a)
 {
     __shared__ u8 s_state[4][256], s_new[4][256], s_mark[4][256];
     const u32 lb = blockIdx.y, l = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const u32 n = a.blocks[lb].n;
+    const u32 n = mtf_len(a, lb);
     const u32 nchunks = (n + kMtfChunk - 1) / kMtfChunk;
     const u32 c0 = blockIdx.x * kMtfGroup;
     if (c0 + 1u >= nchunks) return;
@@ -252,7 +388,7 @@ __global__ __launch_bounds__(LANES) void k_mtf_ranks_small(MtfArgs a)
     __shared__ u32 s_last[PAIRS * CL];
     __shared__ u8 s_code[256];
     const u32 lb = blockIdx.y;
-    const u32 n = a.blocks[lb].n;
+    const u32 n = mtf_len(a, lb);
     const u32 chunk0 = blockIdx.x * CL;
     const u32 sub = threadIdx.x % SUB;
     if (chunk0 * kMtfChunk >= n) return;
@@ -296,7 +432,7 @@ __global__ __launch_bounds__(LANES) void k_mtf_ranks_small(MtfArgs a)
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         __builtin_amdgcn_wave_barrier();
     }
-    const u8 *L = a.L + (size_t)lb * kSlot;
+    const u8 *L = mtf_seq(a, lb);
     u8 *R8 = a.rank8 + (size_t)lb * kSlot;
     // A lane's chunk is 512 consecutive bytes: it is read 64 bytes at a time (four 16-byte loads issued
     // together, the ranks stored the same way), so a line is fetched once and used while it is there;
@@ -385,10 +521,42 @@ struct ZSeg {
     int next_nonzero; // 1 if the position after the segment holds a non-zero rank or is past the end
 };
 
-__device__ __forceinline__ void zload(const u8 *__restrict__ R8, u32 n, u32 tile, ZSeg &s)
+// The ranks of a thread's 16 positions.  Old form: rank8 holds one rank per position.  With a.heads it holds one rank per
+// HEAD: position p of the tile has r = head(p) ? rank8[tile_hbase + heads of the tile in front of p] : 0.  The tile's
+// head ranks (at most kSortTile bytes from tile_hbase on) are staged in LDS with whole 16-byte loads, a thread picks its
+// own behind an in-tile prefix sum of its head counts.  The position behind the segment holds a non-zero rank exactly if
+// it is a head (it is not position 0).  Every thread of the workgroup calls this.
+__device__ __forceinline__ void zload(const MtfArgs &a, u32 lb, u32 n, u32 tile, ZSeg &s)
 {
+    const u8 *__restrict__ R8 = a.rank8 + (size_t)lb * kSlot;
     s.p0 = tile * kSortTile + threadIdx.x * 16u;
     s.valid = s.p0 < n ? ((n - s.p0) < 16u ? (n - s.p0) : 16u) : 0u;
+    if (mtf_collapsed(a, lb)) {
+        __shared__ __attribute__((aligned(16))) u8 s_hr[kSortTile + 32];
+        __shared__ u32 s_hs[kSortThreads / 64];
+        const u16 *hbits = a.headbits + (((size_t)lb * kSlot) >> 4);
+        const u32 hb = s.valid ? (u32)hbits[s.p0 >> 4] : 0u; // (bits behind the block's end are clear)
+        const u32 hbase = a.tile_hbase[lb * kTilesPerBlock + tile];
+        const u32 m = a.hcount[lb];
+        const u32 a0 = hbase & ~15u;
+        {
+            const u32 off = a0 + threadIdx.x * 16u; // (rank8 is padded: a load that begins in front of m stays inside)
+            if (off < m) *reinterpret_cast<uint4 *>(s_hr + threadIdx.x * 16u) = *reinterpret_cast<const uint4 *>(R8 + off);
+            if (threadIdx.x == 0 && a0 + kSortTile < m)
+                *reinterpret_cast<uint4 *>(s_hr + kSortTile) = *reinterpret_cast<const uint4 *>(R8 + a0 + kSortTile);
+        }
+        u32 total;
+        u32 pos = (hbase - a0) + block_excl_sum((u32)__popc(hb), s_hs, total);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const bool h = (hb >> k) & 1u;
+            s.r[k] = h ? s_hr[pos] : (u8)0;
+            pos += h ? 1u : 0u;
+        }
+        const u32 nx = s.p0 + s.valid;
+        s.next_nonzero = (s.valid == 0u || nx >= n) ? 1 : (int)(hbits[nx >> 4] & 1u);
+        return;
+    }
     if (s.valid) {
         const uint4 q = *reinterpret_cast<const uint4 *>(R8 + s.p0);
         const u32 wv[4] = {q.x, q.y, q.z, q.w};
@@ -415,22 +583,6 @@ __device__ __forceinline__ int block_excl_max_int(int v, int *sh /*[16]*/)
     return ex > carry ? ex : carry;
 }
 
-__device__ __forceinline__ u32 block_excl_sum1024(u32 v, u32 *sh /*[16]*/, u32 &total)
-{
-    const u32 l = lane_id(), w = threadIdx.x >> 6;
-    const u32 inc = wave_incl_sum(v);
-    if (l == 63) sh[w] = inc;
-    __syncthreads();
-    u32 carry = 0, tot = 0;
-    for (u32 k = 0; k < kSortThreads / 64; ++k) {
-        if (k < w) carry += sh[k];
-        tot += sh[k];
-    }
-    total = tot;
-    __syncthreads();
-    return carry + inc - v;
-}
-
 // Z1: last non-zero rank position per tile
 __global__ __launch_bounds__(kSortThreads) void k_zle_last(MtfArgs a)
 {
@@ -441,7 +593,7 @@ __global__ __launch_bounds__(kSortThreads) void k_zle_last(MtfArgs a)
     if (threadIdx.x == 0) s_last = -1;
     __syncthreads();
     ZSeg s;
-    zload(a.rank8 + (size_t)lb * kSlot, n, tile, s);
+    zload(a, lb, n, tile, s);
     int last = -1;
 #pragma unroll
     for (u32 k = 0; k < 16; ++k)
@@ -489,7 +641,7 @@ __global__ __launch_bounds__(kSortThreads) void k_zle_emit(MtfArgs a)
         for (u32 i = threadIdx.x; i < kMaxAlpha + 2; i += kSortThreads) s_freq[i] = 0;
     __syncthreads();
     ZSeg s;
-    zload(a.rank8 + (size_t)lb * kSlot, n, tile, s);
+    zload(a, lb, n, tile, s);
     int last = -1;
 #pragma unroll
     for (u32 k = 0; k < 16; ++k)
@@ -515,7 +667,7 @@ __global__ __launch_bounds__(kSortThreads) void k_zle_emit(MtfArgs a)
         }
     }
     u32 total;
-    u32 off = block_excl_sum1024(cnt, s_su, total);
+    u32 off = block_excl_sum(cnt, s_su, total);
     if (!WRITE) {
         if (threadIdx.x == 0) a.ztile_cnt[lb * kTilesPerBlock + tile] = total;
         return;
@@ -612,7 +764,7 @@ __global__ __launch_bounds__(kSortThreads) void k_zle_fused(MtfArgs a)
     if (tile * kSortTile >= n) return; // (tiles beyond the block publish nothing; nobody looks back at them)
     for (u32 i = threadIdx.x; i < kMaxAlpha + 2; i += kSortThreads) s_freq[i] = 0;
     ZSeg s;
-    zload(a.rank8 + (size_t)lb * kSlot, n, tile, s);
+    zload(a, lb, n, tile, s);
     int last = -1;
 #pragma unroll
     for (u32 k = 0; k < 16; ++k)
@@ -671,7 +823,7 @@ __global__ __launch_bounds__(kSortThreads) void k_zle_fused(MtfArgs a)
         }
     }
     u32 total;
-    const u32 off = block_excl_sum1024(cnt, s_su, total);
+    const u32 off = block_excl_sum(cnt, s_su, total);
     if (threadIdx.x == 0) st_sc1_x4(mystate, make_uint4(w_last, (tile ? kLbAgg : kLbIncl) | total, 0u, 0u));
     // pass 2: the symbols into the staging buffer (as k_zle_emit<true>)
     u16 *out = s_out + off;
@@ -759,9 +911,16 @@ __global__ __launch_bounds__(kSortThreads) void k_zle_fused(MtfArgs a)
         if (s_freq[i]) atomicAdd(&a.mtf_freq[(size_t)lb * kMaxAlpha + i], s_freq[i]);
 }
 
-void launch_mtf(hipStream_t st, const MtfArgs &a)
+void launch_mtf(hipStream_t st, const MtfArgs &a, KernelProf *prof, u64 total_n)
 {
     (void)hipMemsetAsync(a.mtf_freq, 0, (size_t)a.nb * kMaxAlpha * sizeof(u32), st);
+    if (a.heads) {
+        // (bytes: L twice, H and the bit map -- about half a byte per position on text)
+        const int pi = prof ? prof->begin(st, KID_MTF_HEADS, 2u * total_n + total_n / 2u) : -1;
+        hipLaunchKernelGGL(k_mtf_heads_mark, dim3(a.tiles, a.nb), dim3(kSortThreads), 0, st, a);
+        hipLaunchKernelGGL(k_mtf_heads_pack, dim3(a.tiles, a.nb), dim3(kSortThreads), 0, st, a);
+        if (prof) prof->end(st, pi);
+    }
     hipLaunchKernelGGL(k_mtf_summaries, dim3(kChunkWGs, a.nb), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_mtf_merge_groups, dim3(kMtfGroups, a.nb), dim3(64), 0, st, a);
     hipLaunchKernelGGL(k_mtf_group_starts, dim3(a.nb), dim3(64), 0, st, a);
