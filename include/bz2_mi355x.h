@@ -703,7 +703,8 @@ void df_enc_destroy(df_enc *e);
  * (a) a stream that is well-formed under RFC 1951 (kind 1: inside an RFC 1950
  *     container, kind 2: an RFC 1952 member) gets BZ_OK and its bytes -- what
  *     zlib's inflate yields for it.  Bytes behind the end of the stream or its
- *     trailer are ignored, and only the first gzip member is decoded.
+ *     trailer are ignored, and only the first gzip member is decoded
+ *     (section 6 decodes every member).
  * (b) every other entry gets an error verdict and the bytes produced in front of
  *     the failing code or block header.  BZ_E_EOF: the entry ends before the
  *     final block's end-of-block code (kinds 1 / 2: before the trailer is
@@ -769,6 +770,71 @@ int df_decode_batch(int kind, int device, const uint8_t *const *ins, const size_
  * or the first Err under the contract above: returns BZ_OK with the bytes, or the verdict with the bytes in front of it
  * (as bz_decode_buffer does). */
 int df_decode_buffer(int kind, int device, const uint8_t *in, size_t in_len, uint8_t **out, size_t *out_len);
+
+/* ========================================================================
+ * 6. EVERY MEMBER of a gzip file (RFC 1952 section 2.2: a file is a series of
+ *    members) -- what gzip(1), Python's gzip.decompress and flate2's
+ *    MultiGzDecoder yield: BGZF (.bam, .vcf.gz), `cat a.gz b.gz`, pigz -i.
+ *    Section 5 and DF_KIND_GZIP keep decoding the first member only, as the
+ *    reference's GZipDecoder does (src/gzip/decoder.rs:204-216).
+ *
+ * THE CONTRACT.  The stream's bytes and verdict are those of this loop over the
+ * one-member contract of section 5 (zlib is the arbiter of each member):
+ *
+ *     pos = 0
+ *     repeat:
+ *         skip zero bytes at pos          (zero padding between and behind members)
+ *         if pos == len: BZ_OK, stop      (a file of no bytes, or of zeros only: BZ_OK, no bytes)
+ *         decode ONE member from the bytes [pos, len) under section 5, kind 2
+ *         append its bytes                (the bytes in front of the fault, if it fails)
+ *         if its verdict is not BZ_OK: that is the stream's verdict, stop
+ *         pos = the byte behind its trailer
+ *
+ * So: junk behind a member that is neither zeros nor a valid header is
+ * BZ_E_DATA, with every byte of the members in front of it; a file cut inside a
+ * later member's header, body or trailer is BZ_E_EOF with the bytes in front of
+ * the cut; a wrong CRC-32 or ISIZE in member k is BZ_E_DATA with all of member
+ * k's bytes and nothing of member k + 1; an empty member (BGZF's 28-byte EOF
+ * marker) contributes no bytes; a truncated member followed by an intact one is
+ * decoded on into the bytes of the next (the loop knows no other end of a
+ * member).  Input of 4 GiB or more is BZ_E_PARAM, as is a member whose output
+ * would reach 4 GiB; the output length is summed in 64 bits.
+ *
+ * HOW (DESIGN_deflate.md, "Every member of a gzip file").  A search lists every
+ * position that holds 1f 8b 08 and a FLG byte without reserved bits (a
+ * CANDIDATE: every member starts at one, but a stored block may hold some too).
+ * The spans between candidates are decoded as one batch by the kernels of
+ * section 5, BZ_DF_GZ_BATCH candidates (default 16384) per launch; a walk keeps
+ * the candidates at which the member in front ended (zeros skipped), and decodes
+ * a member that a false candidate cut short again over 1, 2, 4, ... candidates
+ * more.  Speculation may cost time, never a byte.  Members of
+ * BZ_DF_INF_SPLIT_KIB or more go across many waves as in section 5.
+ * ======================================================================== */
+
+/* d_in[in_len] (HBM, 16-byte aligned; nothing at or behind d_in + in_len is read) -> the members' bytes side by side at
+ * d_out (any alignment): *out_len bytes, *verdict BZ_OK, BZ_E_DATA or BZ_E_EOF.  NOTHING at or behind d_out + *out_len is
+ * written.  The RETURN VALUE is the infrastructure status only: BZ_OK also when the stream carries an error.
+ * Two passes: the first finds the members and their lengths; cap is then checked (BZ_E_CAPACITY leaves d_out untouched,
+ * *out_len holds the capacity needed); the second decodes the members into a buffer of the engine, compares CRC-32 and
+ * ISIZE, and copies the bytes up to the first member that is not clean into d_out.
+ * d_out == NULL: sizes only -- the trailers are not looked at, so *out_len is the capacity the real call needs (and its
+ * *out_len, unless a trailer value is wrong).  BZ_E_PARAM: a null engine or result pointer, d_in null with in_len > 0
+ * or misaligned, in_len >= 4 GiB.  Afterwards df_gpu_last_timings holds [0] sizes [1] writing [2] checksums [3] search,
+ * gather and zero skip [4] compaction [5] their sum, and df_gpu_last_decode_batch_stats / _split_stats describe the members. */
+int df_gpu_decode_members_device(bz_gpu_engine *g, const void *d_in, size_t in_len,
+                                 void *d_out, size_t cap, uint64_t *out_len, int32_t *verdict);
+/* The last df_gpu_decode_members_device call: [0] members decoded, the first that is not clean included (sizes only: members
+ * found, trailers not looked at) [1] candidates found [2] candidates never confirmed
+ * [3] decodes of a member again after a span extension [4] zero bytes skipped [5] members that took the split path
+ * [6] sub-batches of candidates [7] launches of the kernels of this section (search, gather, zero skip, compaction). */
+int df_gpu_last_decode_members_stats(bz_gpu_engine *g, uint64_t out[8]);
+/* ... and the stages of this section in seconds (a host clock around launches that are waited for): [0] search
+ * [1] gather [2] zero skip [3] compaction. */
+int df_gpu_last_decode_members_timings(bz_gpu_engine *g, double out_seconds[4]);
+/* Host to host: one upload, one device call on an engine of the per-process cache, one download.  Returns BZ_OK with the
+ * bytes, or the stream's verdict with the bytes in front of it (as df_decode_buffer does); *out is malloc'ed, release
+ * with bz_free.  in_len == 0: BZ_OK, an empty buffer, no device is touched.  Without a GPU: BZ_E_NOGPU. */
+int df_decode_members_buffer(int device, const uint8_t *in, size_t in_len, uint8_t **out, size_t *out_len);
 
 #ifdef __cplusplus
 }

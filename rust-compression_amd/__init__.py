@@ -13,6 +13,7 @@ Host-side mirror (Python flavour) of the reference's interface for this one path
     BZip2Decoder::new()          bzip2/decoder.rs:588  BZip2Decoder()
     Decoder::next(iter)          traits/decoder.rs:95  BZip2Decoder.next(iter) -> int | None, raises BZip2Error
     Deflater / ZlibDecoder / GZipDecoder               Deflater() / ZlibDecoder() / GZipDecoder(): .next(iter), .decode_all(data)
+    (every member of a gzip file: no counterpart)      MultiGZipDecoder(), gzip_decompress_members(data)
     iter.decode(&mut dec)        traits/decoder.rs:15  decode(iterable, dec) -> iterator of ints
 
 Everything below the iterator plumbing happens in the HIP library (csrc/, C ABI in
@@ -28,7 +29,7 @@ import sys
 from . import _build
 
 __all__ = ["Action", "CompressionError", "BZip2Error", "BZip2Encoder", "BZip2Decoder", "encode", "decode",
-           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "deflate_decompress", "deflate_decompress_batch", "Deflater", "ZlibDecoder", "GZipDecoder", "GpuEngine", "release_cached_resources", "last_call_phases",
+           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "deflate_decompress", "deflate_decompress_batch", "Deflater", "ZlibDecoder", "GZipDecoder", "gzip_decompress_members", "MultiGZipDecoder", "GpuEngine", "release_cached_resources", "last_call_phases",
            "build", "lib", "device_count", "encode_bound", "shard_window", "rccl_lib", "rccl_unique_id", "RcclComm"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -97,6 +98,7 @@ EXPORTS = [
     "df_enc_create", "df_enc_write", "df_enc_end", "df_enc_read", "df_enc_pending", "df_enc_destroy", "df_enc_finished",
     "df_encode_batch_bound", "df_gpu_encode_batch_device", "df_gpu_last_batch_stats", "df_encode_batch",
     "df_gpu_decode_batch_device", "df_gpu_last_decode_batch_stats", "df_gpu_last_decode_split_stats", "df_gpu_last_decode_split_timings", "df_decode_batch", "df_decode_buffer",
+    "df_gpu_decode_members_device", "df_gpu_last_decode_members_stats", "df_gpu_last_decode_members_timings", "df_decode_members_buffer",
 ]
 
 
@@ -254,6 +256,10 @@ def lib():
     L.df_gpu_last_decode_split_stats.argtypes = [vp, u64p]
     L.df_gpu_last_decode_split_timings.argtypes = [vp, C.POINTER(C.c_double)]
     L.df_decode_batch.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, sz, C.POINTER(u8p), u64p, u64p, i32p]
+    L.df_gpu_decode_members_device.argtypes = [vp, vp, sz, vp, sz, u64p, i32p]
+    L.df_gpu_last_decode_members_stats.argtypes = [vp, u64p]
+    L.df_gpu_last_decode_members_timings.argtypes = [vp, C.POINTER(C.c_double)]
+    L.df_decode_members_buffer.argtypes = [C.c_int, C.c_char_p, sz, C.POINTER(u8p), szp]
     L.df_decode_buffer.argtypes = [C.c_int, C.c_int, C.c_char_p, sz, C.POINTER(u8p), szp]
     _LIB = L
     return L
@@ -840,6 +846,9 @@ class Deflater:
         self._pos = 0
         self._verdict = BZ_OK
 
+    def _decode(self, data):
+        return deflate_decompress(data, self.KIND, self._device)
+
     def _error(self):
         e = CompressionError(self._verdict)
         e.partial = self._ready
@@ -849,7 +858,7 @@ class Deflater:
     def next(self, it):
         """One `Decoder::next(iter)` call: an int byte, None at the end, raises CompressionError for Err."""
         if self._ready is None:
-            self._ready, self._verdict = deflate_decompress(bytes(bytearray(it)), self.KIND, self._device)
+            self._ready, self._verdict = self._decode(bytes(bytearray(it)))
         if self._pos < len(self._ready):
             self._pos += 1
             return self._ready[self._pos - 1]
@@ -860,7 +869,7 @@ class Deflater:
     def decode_all(self, data):
         """`data.decode(&mut self).collect::<Result<Vec<_>, _>>()`; CompressionError.partial holds the bytes yielded
         before an Err."""
-        self._ready, self._verdict = deflate_decompress(data, self.KIND, self._device)
+        self._ready, self._verdict = self._decode(data)
         self._pos = len(self._ready)
         if self._verdict != BZ_OK:
             raise self._error()
@@ -875,6 +884,21 @@ class ZlibDecoder(Deflater):
 class GZipDecoder(Deflater):
     """`GZipDecoder` (src/gzip/decoder.rs): the first member."""
     KIND = GZIP
+
+
+def gzip_decompress_members(data, device=0):
+    """Every member of a gzip file, one after the other (df_decode_members_buffer; section 6 of the header) -> (bytes
+    yielded, verdict code): what gzip(1) and gzip.decompress yield, zero padding between and behind members skipped;
+    BZ_E_DATA / BZ_E_EOF with the bytes in front of the fault."""
+    return _decode_call(lib().df_decode_members_buffer, (device,), data, _DF_VERDICTS)
+
+
+class MultiGZipDecoder(Deflater):
+    """Every member of a gzip file (flate2's MultiGzDecoder); GZipDecoder stops behind the first, as the reference's does."""
+    KIND = GZIP
+
+    def _decode(self, data):
+        return gzip_decompress_members(data, self._device)
 
 
 class GpuEngine:
@@ -1140,6 +1164,30 @@ class GpuEngine:
         s = (C.c_uint64 * 8)()
         _check(lib().df_gpu_last_decode_split_stats(self._h, s))
         return [int(x) for x in s]
+
+    GZIP_MEMBERS_STATS = ("members", "candidates", "never_confirmed", "redecodes", "zero_bytes", "split_members", "sub_batches", "launches")
+    GZIP_MEMBERS_STAGES = ("search", "gather", "zero_skip", "compaction")
+
+    def gzip_decode_members_device(self, d_in, in_len, d_out, cap):
+        """Every member of the gzip file d_in[in_len] (16-byte aligned), side by side at d_out (df_gpu_decode_members_device)
+        -> (out_len, verdict).  d_out = None: sizes only, out_len is the capacity the real call needs."""
+        _settle()
+        n = C.c_uint64(0)
+        v = C.c_int32(0)
+        _check(lib().df_gpu_decode_members_device(self._h, d_in, in_len, d_out, cap, C.byref(n), C.byref(v)))
+        return int(n.value), int(v.value)
+
+    def gzip_decode_members_stats(self):
+        """The last gzip_decode_members_device call, in the order of GZIP_MEMBERS_STATS (df_gpu_last_decode_members_stats)."""
+        s = (C.c_uint64 * 8)()
+        _check(lib().df_gpu_last_decode_members_stats(self._h, s))
+        return [int(x) for x in s]
+
+    def gzip_decode_members_timings(self):
+        """Seconds per stage of the last gzip_decode_members_device call (df_gpu_last_decode_members_timings)."""
+        t = (C.c_double * 4)()
+        _check(lib().df_gpu_last_decode_members_timings(self._h, t))
+        return dict(zip(self.GZIP_MEMBERS_STAGES, t))
 
     DEFLATE_DECODE_SPLIT_PHASES = ("search", "sizes", "repair", "writing", "jump_rounds", "gather", "checksum")
 

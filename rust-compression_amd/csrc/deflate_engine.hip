@@ -19,6 +19,7 @@
 #include <functional>
 #include "k_deflate.h"
 #include "inf_split.h"
+#include "gz_members.h"
 
 using namespace dfgpu;
 
@@ -32,6 +33,10 @@ struct DfWorkspace {
     DevBuf s_cand, s_piece, s_prec, s_map, s_cnt;      // an entry across many waves: candidates, pieces, their records, the source map
     u64 split_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // df_gpu_last_decode_split_stats
     double split_ms[7] = {0, 0, 0, 0, 0, 0, 0};        // search, sizes, repair, writing, jump rounds, gather, checksum
+    DevBuf m_cnt, m_base, m_cand, m_span, m_image, m_zs, m_stage; // every member of a gzip file: candidates per tile and in front of it, a
+                                                       // window of the list, span tables, the batch image, zero skips, the members' bytes
+    u64 mem_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // df_gpu_last_decode_members_stats
+    double mem_ms[4] = {0, 0, 0, 0};                   // search, gather, zero skip, compaction
     double t_stage[6] = {0, 0, 0, 0, 0, 0}; // chains, matches, parse, blocks, emit, total
     u64 stats[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // blocks, stored, fixed, dynamic, limited tables, stream bytes, dynamic w/o distances
     hipEvent_t ev[7] = {};
@@ -1047,6 +1052,123 @@ static int df_split_write(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *
     return BZ_OK;
 }
 
+// What the sizes phase of a batch leaves for its writing phase.
+struct DfSizes {
+    std::vector<DfInfRec> rec;        // every entry's record, the split entries' included
+    std::vector<DfSplitEntry> splits; // the entries that go across many waves
+    std::vector<u64> len_small;       // the entries' lengths with the split entries as entries of no bytes (empty: none is split)
+};
+
+// The sizes phase: the split entries' search, sizes, chain and repair, and the sizes launch over all entries.  will_write:
+// a writing phase follows (the split entries' source map is sized here, before any entry is committed to the split path).
+// The entries' ranges stay in w->i_in and their records in w->i_rec for a writing phase that follows at once.
+static int df_decode_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *in8, const uint64_t *h_in_off, const uint64_t *h_in_len,
+                           size_t count, bool will_write, DfSizes &s)
+{
+    int rc;
+    // the entries that go across many waves; in the launches over all entries they are entries of no bytes
+    const u64 split_min = df_env_kib("BZ_DF_INF_SPLIT_KIB", 1024) * 1024;
+    std::vector<DfSplitEntry> &splits = s.splits;
+    splits.clear();
+    s.len_small.clear();
+    for (size_t i = 0; split_min && i < count; ++i) {
+        if (h_in_len[i] < split_min) continue;
+        DfSplitEntry e;
+        bool fallback = false;
+        e.index = i;
+        rc = df_split_sizes(g, w, kind, in8 + h_in_off[i], (u32)h_in_len[i], e, &fallback);
+        if (rc != BZ_OK) return rc;
+        if (!fallback) splits.push_back(std::move(e));
+    }
+    // ONE source map for all of them, one after the other: sized here, before any entry is committed to the split path.  If
+    // it cannot be had, every entry takes the one-wave path (and the failed allocation's error is not the next launch's).
+    if (!splits.empty() && will_write) {
+        size_t map_bytes = 0;
+        for (const DfSplitEntry &e : splits) map_bytes = std::max(map_bytes, (size_t)e.rec.len * 4 + 64);
+        if (w->s_map.ensure(map_bytes) != BZ_OK || w->s_cnt.ensure(64) != BZ_OK) {
+            (void)hipGetLastError();
+            splits.clear();
+        }
+    }
+    for (const DfSplitEntry &e : splits) {
+        for (int k = 0; k < 8; ++k) w->split_stats[k] += e.st[k];
+        for (int k = 0; k < 3; ++k) w->split_ms[k] += e.ms[k];
+    }
+    if (!splits.empty()) {
+        s.len_small.assign(h_in_len, h_in_len + count);
+        for (const DfSplitEntry &e : splits) s.len_small[e.index] = 0;
+    }
+    rc = w->i_in.ensure(2 * count * sizeof(u64));
+    if (rc == BZ_OK) rc = w->i_ooff.ensure(count * sizeof(u64));
+    if (rc == BZ_OK) rc = w->i_rec.ensure(count * sizeof(DfInfRec));
+    if (rc != BZ_OK) return rc;
+    u64 *d_off = w->i_in.as<u64>(), *d_len = d_off + count;
+    DfInfRec *d_rec = w->i_rec.as<DfInfRec>();
+    HIPCHK(hipMemcpyAsync(d_off, h_in_off, count * sizeof(u64), hipMemcpyHostToDevice, g->st));
+    HIPCHK(hipMemcpyAsync(d_len, splits.empty() ? h_in_len : s.len_small.data(), count * sizeof(u64), hipMemcpyHostToDevice, g->st));
+    HIPCHK(hipEventRecord(w->ev[0], g->st));
+    if (df_launch_inflate(g->st, false, in8, d_off, d_len, (u32)count, kind, nullptr, nullptr, d_rec) != 0) return BZ_E_UNEXPECTED;
+    HIPCHK(hipEventRecord(w->ev[1], g->st));
+    s.rec.resize(count);
+    HIPCHK(hipMemcpyAsync(s.rec.data(), d_rec, count * sizeof(DfInfRec), hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipStreamSynchronize(g->st));
+    for (const DfSplitEntry &e : splits) s.rec[e.index] = e.rec;
+    return BZ_OK;
+}
+
+// The writing phase: entry i's bytes at out8 + h_out_off[i] (multiples of 16), at most s.rec[i].len of them; kinds 1 / 2:
+// the trailers compared, s.rec[i].verdict turned to BZ_E_DATA where they differ.  upload: the sizes phase that ran last was
+// not this batch's, so the ranges and records go to the device first (a split entry's as the entry of no bytes it is there).
+static int df_decode_write(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *in8, const uint64_t *h_in_off, const uint64_t *h_in_len,
+                           size_t count, u8 *out8, const uint64_t *h_out_off, DfSizes &s, bool upload)
+{
+    int rc;
+    u64 *d_off = w->i_in.as<u64>(), *d_len = d_off + count, *d_ooff = w->i_ooff.as<u64>();
+    DfInfRec *d_rec = w->i_rec.as<DfInfRec>();
+    std::vector<DfInfRec> small;
+    if (upload) {
+        rc = w->i_in.ensure(2 * count * sizeof(u64));
+        if (rc == BZ_OK) rc = w->i_ooff.ensure(count * sizeof(u64));
+        if (rc == BZ_OK) rc = w->i_rec.ensure(count * sizeof(DfInfRec));
+        if (rc != BZ_OK) return rc;
+        d_off = w->i_in.as<u64>(), d_len = d_off + count, d_ooff = w->i_ooff.as<u64>();
+        d_rec = w->i_rec.as<DfInfRec>();
+        small = s.rec;
+        for (const DfSplitEntry &e : s.splits) {
+            small[e.index].len = 0;
+            small[e.index].verdict = BZ_E_EOF;
+        }
+        HIPCHK(hipMemcpyAsync(d_off, h_in_off, count * sizeof(u64), hipMemcpyHostToDevice, g->st));
+        HIPCHK(hipMemcpyAsync(d_len, s.splits.empty() ? h_in_len : s.len_small.data(), count * sizeof(u64), hipMemcpyHostToDevice, g->st));
+        HIPCHK(hipMemcpyAsync(d_rec, small.data(), count * sizeof(DfInfRec), hipMemcpyHostToDevice, g->st));
+    }
+    HIPCHK(hipMemcpyAsync(d_ooff, h_out_off, count * sizeof(u64), hipMemcpyHostToDevice, g->st));
+    HIPCHK(hipEventRecord(w->ev[2], g->st));
+    if (df_launch_inflate(g->st, true, in8, d_off, d_len, (u32)count, kind, out8, d_ooff, d_rec) != 0) return BZ_E_UNEXPECTED;
+    HIPCHK(hipEventRecord(w->ev[3], g->st));
+    if (kind != 0) {
+        if (df_launch_inflate_check(g->st, out8, d_ooff, (u32)count, d_rec, kind) != 0) return BZ_E_UNEXPECTED;
+        HIPCHK(hipMemcpyAsync(s.rec.data(), d_rec, count * sizeof(DfInfRec), hipMemcpyDeviceToHost, g->st));
+    }
+    HIPCHK(hipEventRecord(w->ev[4], g->st));
+    HIPCHK(hipStreamSynchronize(g->st));
+    for (DfSplitEntry &e : s.splits) {
+        rc = df_split_write(g, w, kind, in8 + h_in_off[e.index], (u32)h_in_len[e.index], out8 + h_out_off[e.index], e);
+        if (rc != BZ_OK) return rc;
+        s.rec[e.index] = e.rec;
+    }
+    return BZ_OK;
+}
+
+// df_gpu_last_decode_batch_stats [0..6] of one entry
+static void df_inf_stats_add(DfWorkspace *w, const DfInfRec &r)
+{
+    w->inf_stats[r.verdict == BZ_OK ? 0 : 1] += 1;
+    for (int k = 0; k < 3; ++k) w->inf_stats[2 + k] += r.nblk[k];
+    w->inf_stats[5] += r.len;
+    w->inf_stats[6] += (r.end_bit + 7u) >> 3;
+}
+
 // grow != nullptr: the output is the engine's own buffer, sized between the two launches (the host forms)
 static int df_decode_batch_core(bz_gpu_engine *g, int kind, const void *d_in, const uint64_t *h_in_off, const uint64_t *h_in_len, size_t count,
                                 void *d_out, size_t cap, DevBuf *grow, uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_verdict)
@@ -1068,52 +1190,10 @@ static int df_decode_batch_core(bz_gpu_engine *g, int kind, const void *d_in, co
     for (u64 &s : w->split_stats) s = 0;
     for (double &t : w->split_ms) t = 0;
     const u8 *in8 = static_cast<const u8 *>(d_in);
-    // the entries that go across many waves; in the launches over all entries they are entries of no bytes
-    const u64 split_min = df_env_kib("BZ_DF_INF_SPLIT_KIB", 1024) * 1024;
-    std::vector<DfSplitEntry> splits;
-    std::vector<u64> len_small;
-    for (size_t i = 0; split_min && i < count; ++i) {
-        if (h_in_len[i] < split_min) continue;
-        DfSplitEntry e;
-        bool fallback = false;
-        e.index = i;
-        rc = df_split_sizes(g, w, kind, in8 + h_in_off[i], (u32)h_in_len[i], e, &fallback);
-        if (rc != BZ_OK) return rc;
-        if (!fallback) splits.push_back(std::move(e));
-    }
-    // ONE source map for all of them, one after the other: sized here, before any entry is committed to the split path.  If
-    // it cannot be had, every entry takes the one-wave path (and the failed allocation's error is not the next launch's).
-    if (!splits.empty() && (d_out != nullptr || grow != nullptr)) {
-        size_t map_bytes = 0;
-        for (const DfSplitEntry &e : splits) map_bytes = std::max(map_bytes, (size_t)e.rec.len * 4 + 64);
-        if (w->s_map.ensure(map_bytes) != BZ_OK || w->s_cnt.ensure(64) != BZ_OK) {
-            (void)hipGetLastError();
-            splits.clear();
-        }
-    }
-    for (const DfSplitEntry &e : splits) {
-        for (int k = 0; k < 8; ++k) w->split_stats[k] += e.st[k];
-        for (int k = 0; k < 3; ++k) w->split_ms[k] += e.ms[k];
-    }
-    if (!splits.empty()) {
-        len_small.assign(h_in_len, h_in_len + count);
-        for (const DfSplitEntry &e : splits) len_small[e.index] = 0;
-    }
-    rc = w->i_in.ensure(2 * count * sizeof(u64));
-    if (rc == BZ_OK) rc = w->i_ooff.ensure(count * sizeof(u64));
-    if (rc == BZ_OK) rc = w->i_rec.ensure(count * sizeof(DfInfRec));
+    DfSizes sz;
+    rc = df_decode_sizes(g, w, kind, in8, h_in_off, h_in_len, count, d_out != nullptr || grow != nullptr, sz);
     if (rc != BZ_OK) return rc;
-    u64 *d_off = w->i_in.as<u64>(), *d_len = d_off + count, *d_ooff = w->i_ooff.as<u64>();
-    DfInfRec *d_rec = w->i_rec.as<DfInfRec>();
-    HIPCHK(hipMemcpyAsync(d_off, h_in_off, count * sizeof(u64), hipMemcpyHostToDevice, g->st));
-    HIPCHK(hipMemcpyAsync(d_len, splits.empty() ? h_in_len : len_small.data(), count * sizeof(u64), hipMemcpyHostToDevice, g->st));
-    HIPCHK(hipEventRecord(w->ev[0], g->st));
-    if (df_launch_inflate(g->st, false, in8, d_off, d_len, (u32)count, kind, nullptr, nullptr, d_rec) != 0) return BZ_E_UNEXPECTED;
-    HIPCHK(hipEventRecord(w->ev[1], g->st));
-    std::vector<DfInfRec> rec(count);
-    HIPCHK(hipMemcpyAsync(rec.data(), d_rec, count * sizeof(DfInfRec), hipMemcpyDeviceToHost, g->st));
-    HIPCHK(hipStreamSynchronize(g->st));
-    for (const DfSplitEntry &e : splits) rec[e.index] = e.rec;
+    const std::vector<DfInfRec> &rec = sz.rec;
     // the outputs' places: input order, each at a multiple of 16
     u64 cursor = 0, need = 0;
     for (size_t i = 0; i < count; ++i) {
@@ -1132,41 +1212,23 @@ static int df_decode_batch_core(bz_gpu_engine *g, int kind, const void *d_in, co
     } else if (d_out && need > cap) return BZ_E_CAPACITY;
     float ms[3] = {0, 0, 0};
     if (out8) {
-        HIPCHK(hipMemcpyAsync(d_ooff, h_out_off, count * sizeof(u64), hipMemcpyHostToDevice, g->st));
-        HIPCHK(hipEventRecord(w->ev[2], g->st));
-        if (df_launch_inflate(g->st, true, in8, d_off, d_len, (u32)count, kind, out8, d_ooff, d_rec) != 0) return BZ_E_UNEXPECTED;
-        HIPCHK(hipEventRecord(w->ev[3], g->st));
-        if (kind != 0) {
-            if (df_launch_inflate_check(g->st, out8, d_ooff, (u32)count, d_rec, kind) != 0) return BZ_E_UNEXPECTED;
-            HIPCHK(hipMemcpyAsync(rec.data(), d_rec, count * sizeof(DfInfRec), hipMemcpyDeviceToHost, g->st));
-        }
-        HIPCHK(hipEventRecord(w->ev[4], g->st));
-        HIPCHK(hipStreamSynchronize(g->st));
-        for (DfSplitEntry &e : splits) {
-            rc = df_split_write(g, w, kind, in8 + h_in_off[e.index], (u32)h_in_len[e.index], out8 + h_out_off[e.index], e);
-            if (rc != BZ_OK) return rc;
-            rec[e.index] = e.rec;
-        }
+        rc = df_decode_write(g, w, kind, in8, h_in_off, h_in_len, count, out8, h_out_off, sz, false);
+        if (rc != BZ_OK) return rc;
         for (size_t i = 0; i < count; ++i) h_verdict[i] = rec[i].verdict;
         (void)hipEventElapsedTime(&ms[1], w->ev[2], w->ev[3]);
         (void)hipEventElapsedTime(&ms[2], w->ev[3], w->ev[4]);
         w->inf_stats[7] = kind != 0 ? 3 : 2;
     } else w->inf_stats[7] = 1;
     (void)hipEventElapsedTime(&ms[0], w->ev[0], w->ev[1]);
-    for (size_t i = 0; i < count; ++i) {
-        w->inf_stats[rec[i].verdict == BZ_OK ? 0 : 1] += 1;
-        for (int k = 0; k < 3; ++k) w->inf_stats[2 + k] += rec[i].nblk[k];
-        w->inf_stats[5] += rec[i].len;
-        w->inf_stats[6] += (rec[i].end_bit + 7u) >> 3;
-    }
+    for (size_t i = 0; i < count; ++i) df_inf_stats_add(w, rec[i]);
     // df_gpu_last_timings: [0] the sizes launch [1] the writing launch [2] the checksum kernel [5] their sum; the phases of the
     // split entries (host clock around launches that are waited for) go where they belong
     ms[0] += (float)(w->split_ms[0] + w->split_ms[1] + w->split_ms[2]);
     ms[1] += (float)(w->split_ms[3] + w->split_ms[4] + w->split_ms[5]);
     ms[2] += (float)w->split_ms[6];
-    if (df_trace() && !splits.empty())
+    if (df_trace() && !sz.splits.empty())
         fprintf(stderr, "bz2_mi355x: inflate split: %zu entries; search %.3f sizes %.3f repair %.3f writing %.3f jump %.3f gather %.3f checksum %.3f ms\n",
-                splits.size(), w->split_ms[0], w->split_ms[1], w->split_ms[2], w->split_ms[3], w->split_ms[4], w->split_ms[5], w->split_ms[6]);
+                sz.splits.size(), w->split_ms[0], w->split_ms[1], w->split_ms[2], w->split_ms[3], w->split_ms[4], w->split_ms[5], w->split_ms[6]);
     for (double &t : w->t_stage) t = 0;
     for (int k = 0; k < 3; ++k) {
         w->t_stage[k] = ms[k] * 1e-3;
@@ -1227,6 +1289,446 @@ extern "C" int df_decode_buffer(int kind, int device, const uint8_t *in, size_t 
     if (rc != BZ_OK) return rc;
     *out_len = (size_t)len; // (the one entry lies at offset 0)
     return verdict;
+}
+
+// ---- every member of a gzip file (section 6 of the header; gz_members.h, kernels: k_gz_members.hip) ----------------
+// DESIGN_deflate.md "Every member of a gzip file".  Pass 1 (the sizes): candidates, a sub-batch of them at a time as one
+// batch of spans for the sizes phase above, the walk that keeps the members.  Pass 2 (the bytes, once the capacity is
+// known to suffice): the members alone, a sub-batch at a time, through the writing phase into the engine's staging buffer
+// and from there side by side into the caller's.
+static_assert(gzmem::kOk == BZ_OK && gzmem::kEof == BZ_E_EOF, "gz_members.h names the verdicts by value");
+
+extern "C" int df_gpu_last_decode_members_stats(bz_gpu_engine *g, uint64_t out[8])
+{
+    if (!g || !out) return BZ_E_PARAM;
+    for (int i = 0; i < 8; ++i) out[i] = g->df ? g->df->mem_stats[i] : 0;
+    return BZ_OK;
+}
+
+extern "C" int df_gpu_last_decode_members_timings(bz_gpu_engine *g, double out_seconds[4])
+{
+    if (!g || !out_seconds) return BZ_E_PARAM;
+    for (int i = 0; i < 4; ++i) out_seconds[i] = g->df ? g->df->mem_ms[i] * 1e-3 : 0.0;
+    return BZ_OK;
+}
+
+// candidates per sizes launch, members per writing launch; read per call
+static u64 df_gz_sub_batch()
+{
+    const u64 v = df_env_kib("BZ_DF_GZ_BATCH", gzmem::kSubBatch);
+    return v < 1 ? 1 : v > (1u << 20) ? (1u << 20) : v;
+}
+constexpr u64 kGzStageMax = (u64)256 << 20; // bytes of spans, and of decoded members, per writing launch (one member may exceed it)
+
+struct GzMember {
+    u64 start, span; // the bytes the decoder is shown: from the member's first byte to a candidate behind its end, or the input's end
+    DfInfRec rec;
+    int split;       // its DfSplitEntry among the call's, -1: one wave
+};
+
+// The candidate list, a window at a time: the counts per tile are kept, the positions are listed on demand.
+struct GzCands {
+    bz_gpu_engine *g = nullptr;
+    DfWorkspace *w = nullptr;
+    const u8 *in = nullptr;
+    u32 len = 0;
+    std::vector<u64> tpre; // per tile: the candidates in front of it; [ntiles]: all
+    u64 total = 0, sub = 0, first = 0;
+    std::vector<u32> win;  // candidates first .. first + win.size()
+
+    int count()
+    {
+        const u32 ntiles = (u32)(((u64)len + gzmem::kTile - 1) / gzmem::kTile); // (len up to 2^32 - 1: the sum in 64 bits)
+        int rc = w->m_cnt.ensure((size_t)ntiles * 4);
+        if (rc == BZ_OK) rc = w->m_base.ensure((size_t)ntiles * 4);
+        if (rc != BZ_OK) return rc;
+        const double t0 = df_now_ms();
+        std::vector<u32> cnt(ntiles), base(ntiles);
+        if (df_launch_gz_search_count(g->st, in, len, ntiles, w->m_cnt.as<u32>()) != 0) return BZ_E_UNEXPECTED;
+        HIPCHK(hipMemcpyAsync(cnt.data(), w->m_cnt.p, (size_t)ntiles * 4, hipMemcpyDeviceToHost, g->st));
+        HIPCHK(hipStreamSynchronize(g->st));
+        tpre.assign((size_t)ntiles + 1, 0);
+        for (u32 t = 0; t < ntiles; ++t) {
+            base[t] = (u32)tpre[t]; // (fewer than len / 3 candidates: 32 bits)
+            tpre[t + 1] = tpre[t] + cnt[t];
+        }
+        total = tpre[ntiles];
+        HIPCHK(hipMemcpyAsync(w->m_base.p, base.data(), (size_t)ntiles * 4, hipMemcpyHostToDevice, g->st));
+        HIPCHK(hipStreamSynchronize(g->st));
+        w->mem_ms[0] += df_now_ms() - t0;
+        w->mem_stats[7] += 1;
+        return BZ_OK;
+    }
+    // candidates idx .. idx + n (cut at the list's end) become the window
+    int fetch(u64 idx, u64 n)
+    {
+        if (idx >= total) return BZ_E_UNEXPECTED;
+        n = std::min(n, total - idx);
+        const u32 t0 = (u32)(std::upper_bound(tpre.begin(), tpre.end(), idx) - tpre.begin() - 1);
+        const u32 t1 = (u32)(std::upper_bound(tpre.begin(), tpre.end(), idx + n - 1) - tpre.begin() - 1);
+        const int rc = w->m_cand.ensure((size_t)n * 4);
+        if (rc != BZ_OK) return rc;
+        const double c0 = df_now_ms();
+        if (df_launch_gz_search_list(g->st, in, len, t0, t1 - t0 + 1, w->m_base.as<u32>(), (u32)idx, (u32)n, w->m_cand.as<u32>()) != 0)
+            return BZ_E_UNEXPECTED;
+        win.resize((size_t)n);
+        HIPCHK(hipMemcpyAsync(win.data(), w->m_cand.p, (size_t)n * 4, hipMemcpyDeviceToHost, g->st));
+        HIPCHK(hipStreamSynchronize(g->st));
+        first = idx;
+        w->mem_ms[0] += df_now_ms() - c0;
+        w->mem_stats[7] += 1;
+        return BZ_OK;
+    }
+    bool has(u64 idx, u64 n) const { return idx >= first && idx + n <= first + win.size(); }
+    int at(u64 idx, u64 *pos)
+    {
+        if (!has(idx, 1)) {
+            const int rc = fetch(idx, sub + 1);
+            if (rc != BZ_OK) return rc;
+        }
+        *pos = win[(size_t)(idx - first)];
+        return BZ_OK;
+    }
+};
+
+// spans of the input (first byte, bytes) -> the batch image in w->m_image, each at a multiple of 4
+static int df_gz_gather(bz_gpu_engine *g, DfWorkspace *w, const u8 *in8, const std::vector<std::pair<u64, u64>> &sp, std::vector<u64> &ioff,
+                        std::vector<u64> &ilen)
+{
+    const size_t n = sp.size();
+    std::vector<GzSpan> tab(n);
+    ioff.resize(n);
+    ilen.resize(n);
+    u64 cur = 0;
+    u32 max_len = 0;
+    for (size_t i = 0; i < n; ++i) {
+        tab[i] = GzSpan{sp[i].first, cur, (u32)sp[i].second, 0};
+        ioff[i] = cur;
+        ilen[i] = sp[i].second;
+        cur += (sp[i].second + 3u) & ~(u64)3;
+        max_len = std::max(max_len, (u32)sp[i].second);
+    }
+    int rc = w->m_image.ensure((size_t)cur + 64);
+    if (rc == BZ_OK) rc = w->m_span.ensure(n * sizeof(GzSpan));
+    if (rc != BZ_OK) return rc;
+    const double t0 = df_now_ms();
+    HIPCHK(hipMemcpyAsync(w->m_span.p, tab.data(), n * sizeof(GzSpan), hipMemcpyHostToDevice, g->st));
+    if (df_launch_gz_gather(g->st, in8, w->m_span.as<GzSpan>(), (u32)n, max_len, w->m_image.as<u8>()) != 0) return BZ_E_UNEXPECTED;
+    HIPCHK(hipStreamSynchronize(g->st));
+    w->mem_ms[1] += df_now_ms() - t0;
+    w->mem_stats[7] += 1;
+    return BZ_OK;
+}
+
+// ... and their sizes phase, each span a one-member entry (kind 2)
+static int df_gz_sizes(bz_gpu_engine *g, DfWorkspace *w, const u8 *in8, const std::vector<std::pair<u64, u64>> &sp, bool will_write, DfSizes &s,
+                       double *ms_sizes)
+{
+    std::vector<u64> ioff, ilen;
+    int rc = df_gz_gather(g, w, in8, sp, ioff, ilen);
+    if (rc != BZ_OK) return rc;
+    rc = df_decode_sizes(g, w, DF_KIND_GZIP, w->m_image.as<u8>(), ioff.data(), ilen.data(), sp.size(), will_write, s);
+    if (rc != BZ_OK) return rc;
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, w->ev[0], w->ev[1]);
+    *ms_sizes += ms;
+    return BZ_OK;
+}
+
+// out[j] = the first byte in [from[j], bound[j]) that is not zero, or bound[j]
+static int df_gz_zero_skip(bz_gpu_engine *g, DfWorkspace *w, const u8 *in8, const u32 *from, const u32 *bound, u32 n, u32 *out)
+{
+    const int rc = w->m_zs.ensure((size_t)n * 12);
+    if (rc != BZ_OK) return rc;
+    u32 *d = w->m_zs.as<u32>();
+    const double t0 = df_now_ms();
+    HIPCHK(hipMemcpyAsync(d, from, (size_t)n * 4, hipMemcpyHostToDevice, g->st));
+    HIPCHK(hipMemcpyAsync(d + n, bound, (size_t)n * 4, hipMemcpyHostToDevice, g->st));
+    if (df_launch_gz_zero_skip(g->st, in8, d, d + n, n, d + 2 * (size_t)n) != 0) return BZ_E_UNEXPECTED;
+    HIPCHK(hipMemcpyAsync(out, d + 2 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipStreamSynchronize(g->st));
+    w->mem_ms[2] += df_now_ms() - t0;
+    w->mem_stats[7] += 1;
+    return BZ_OK;
+}
+
+// grow != nullptr: the output is the engine's own buffer, sized between the passes (the host form)
+static int df_members_core(bz_gpu_engine *g, const void *d_in, size_t in_len, void *d_out, size_t cap, DevBuf *grow, uint64_t *out_len,
+                           int32_t *verdict)
+{
+    using gzmem::Step;
+    if (!g || !out_len || !verdict) return BZ_E_PARAM;
+    *out_len = 0;
+    *verdict = BZ_OK;
+    if ((in_len && !d_in) || ((uintptr_t)d_in & 15u) || (u64)in_len >= (1ull << 32)) return BZ_E_PARAM;
+    DfWorkspace *w = nullptr;
+    int rc = df_workspace(g, &w);
+    if (rc != BZ_OK) return rc;
+    for (u64 &s : w->inf_stats) s = 0;
+    for (u64 &s : w->split_stats) s = 0;
+    for (double &t : w->split_ms) t = 0;
+    for (u64 &s : w->mem_stats) s = 0;
+    for (double &t : w->mem_ms) t = 0;
+    for (double &t : w->t_stage) t = 0;
+    if (in_len == 0) return BZ_OK;
+    const u8 *in8 = static_cast<const u8 *>(d_in);
+    const u64 len = in_len;
+    const bool will_write = d_out != nullptr || grow != nullptr;
+    u64 *ms = w->mem_stats;
+    double t_sizes = 0, t_write = 0, t_check = 0;
+    GzCands cs;
+    cs.g = g;
+    cs.w = w;
+    cs.in = in8;
+    cs.len = (u32)len;
+    cs.sub = df_gz_sub_batch();
+    if ((rc = cs.count()) != BZ_OK) return rc;
+    ms[1] = cs.total;
+
+    // ---- pass 1: the members, their lengths and the stream's verdict in front of the trailers
+    std::vector<GzMember> mem;
+    std::vector<DfSplitEntry> msplits;
+    int v = BZ_OK;
+    u64 ci = 0; // the first candidate at or behind p
+    u64 p = 0;  // where the next member has to start
+    {
+        u64 b = len;
+        if (cs.total && (rc = cs.at(0, &b)) != BZ_OK) return rc;
+        const u32 from = 0, bound = (u32)b;
+        u32 nz = 0;
+        if ((rc = df_gz_zero_skip(g, w, in8, &from, &bound, 1, &nz)) != BZ_OK) return rc;
+        p = nz == bound && cs.total == 0 ? len : nz; // (a bound of 2^32 - 1 at most: len < 4 GiB)
+        ms[4] += p;
+    }
+    while (p != len) {
+        u64 c0 = len;
+        if (ci < cs.total && (rc = cs.at(ci, &c0)) != BZ_OK) return rc;
+        if (c0 != p) { // no candidate: the one-member decoder's header rules say what it is
+            DfSizes s1;
+            if ((rc = df_gz_sizes(g, w, in8, {{p, std::min<u64>(gzmem::kJunkBytes, len - p)}}, false, s1, &t_sizes)) != BZ_OK) return rc;
+            v = s1.rec[0].verdict;
+            if (v == BZ_OK || s1.rec[0].len != 0) return BZ_E_UNEXPECTED;
+            break;
+        }
+        const u64 n = std::min(cs.sub, cs.total - ci), more = ci + n < cs.total ? 1 : 0;
+        if (!cs.has(ci, n + more) && (rc = cs.fetch(ci, n + more)) != BZ_OK) return rc;
+        std::vector<u64> c((size_t)n + 1);
+        for (u64 j = 0; j < n + more; ++j) c[(size_t)j] = cs.win[(size_t)(ci - cs.first + j)];
+        if (!more) c[(size_t)n] = len;
+        std::vector<std::pair<u64, u64>> sp((size_t)n);
+        for (size_t j = 0; j < n; ++j) sp[j] = {c[j], c[j + 1] - c[j]};
+        DfSizes s;
+        if ((rc = df_gz_sizes(g, w, in8, sp, will_write, s, &t_sizes)) != BZ_OK) return rc;
+        ms[6] += 1;
+        std::vector<int> sidx((size_t)n, -1);
+        for (size_t k = 0; k < s.splits.size(); ++k) sidx[s.splits[k].index] = (int)k;
+        // the zeros behind every span's member, as if each were confirmed
+        std::vector<u32> from((size_t)n), bound((size_t)n), nz((size_t)n);
+        for (size_t j = 0; j < n; ++j) {
+            bound[j] = (u32)c[j + 1];
+            from[j] = s.rec[j].verdict == BZ_OK ? (u32)(c[j] + (s.rec[j].end_bit >> 3)) : bound[j];
+        }
+        if ((rc = df_gz_zero_skip(g, w, in8, from.data(), bound.data(), (u32)n, nz.data())) != BZ_OK) return rc;
+        bool over = false;
+        for (size_t j = 0; j < n;) {
+            DfInfRec r = s.rec[j];
+            DfSplitEntry se;
+            bool split = sidx[j] >= 0;
+            if (split) se = std::move(s.splits[(size_t)sidx[j]]);
+            u64 span_end = c[j + 1], bnd = c[j + 1], nonzero = nz[j], next_ci = ci + j + 1;
+            u64 e = r.verdict == BZ_OK ? c[j] + (r.end_bit >> 3) : span_end;
+            Step st = gzmem::walk_step(r.verdict, span_end, nonzero, bnd, len);
+            if (st == Step::Extend) {
+                for (u32 round = 1;; ++round) { // over 1, 2, 4, ... candidates more
+                    ms[3] += 1;
+                    const u64 ei = gzmem::extend_to(ci + j, round);
+                    span_end = len;
+                    if (ei < cs.total && (rc = cs.at(ei, &span_end)) != BZ_OK) return rc;
+                    DfSizes s1;
+                    if ((rc = df_gz_sizes(g, w, in8, {{c[j], span_end - c[j]}}, will_write, s1, &t_sizes)) != BZ_OK) return rc;
+                    r = s1.rec[0];
+                    split = !s1.splits.empty();
+                    if (split) se = std::move(s1.splits[0]);
+                    if (!(r.verdict == BZ_E_EOF && span_end < len)) break;
+                }
+                // the candidates that lay inside the member, and what bounds the zeros behind it
+                e = r.verdict == BZ_OK ? c[j] + (r.end_bit >> 3) : span_end;
+                next_ci = std::max(next_ci, cs.tpre[(size_t)(e / gzmem::kTile)]);
+                bnd = len;
+                while (next_ci < cs.total) {
+                    if ((rc = cs.at(next_ci, &bnd)) != BZ_OK) return rc;
+                    if (bnd >= e) break;
+                    bnd = len;
+                    ++next_ci;
+                }
+                nonzero = bnd;
+                if (r.verdict == BZ_OK) {
+                    const u32 f1 = (u32)e, b1 = (u32)bnd;
+                    u32 z1 = 0;
+                    if ((rc = df_gz_zero_skip(g, w, in8, &f1, &b1, 1, &z1)) != BZ_OK) return rc;
+                    nonzero = z1;
+                }
+                st = gzmem::walk_step(r.verdict, span_end, nonzero, bnd, len);
+                if (st == Step::Extend) return BZ_E_UNEXPECTED;
+            }
+            if (r.flags & 1u) return BZ_E_PARAM; // a member of 4 GiB or more of output
+            // an extended span may reach far behind the member: the writing phase is shown the member alone, which decodes
+            // alike (unless the long span went across many waves and the member itself would too: its pieces stay as found)
+            const u64 split_min = df_env_kib("BZ_DF_INF_SPLIT_KIB", 1024) * 1024;
+            if (r.verdict == BZ_OK && e < span_end && !(split && e - c[j] >= split_min)) {
+                span_end = e;
+                split = false;
+            }
+            int at = -1;
+            if (split) {
+                at = (int)msplits.size();
+                msplits.push_back(std::move(se));
+            }
+            mem.push_back(GzMember{c[j], span_end - c[j], r, at});
+            if (st == Step::Fault) {
+                v = r.verdict;
+                over = true;
+                break;
+            }
+            ms[4] += nonzero - e;
+            p = st == Step::End ? len : nonzero;
+            if (st == Step::Next && next_ci < ci + n) { // (behind an extension too: the spans of the sub-batch stand as decoded)
+                j = (size_t)(next_ci - ci);
+                continue;
+            }
+            ci = next_ci; // the next sub-batch starts there, or the byte at p is no candidate, or the input is over
+            break;
+        }
+        if (over) break;
+    }
+    ms[0] = mem.size();
+    ms[2] = cs.total - mem.size();
+    u64 need = 0;
+    for (const GzMember &m : mem) {
+        need += m.rec.len;
+        if (m.split >= 0) ms[5] += 1;
+    }
+    *out_len = need;
+    *verdict = v;
+
+    // ---- pass 2: the bytes
+    u8 *out8 = static_cast<u8 *>(d_out);
+    if (grow) {
+        if ((rc = grow->ensure((size_t)need + 64)) != BZ_OK) return rc;
+        out8 = grow->as<u8>();
+    } else if (d_out && need > cap) return BZ_E_CAPACITY;
+    u64 done = 0;
+    bool cut = false;
+    for (size_t a = 0; out8 && a < mem.size() && !cut;) {
+        size_t b = a;
+        u64 img = 0, stg = 0;
+        while (b < mem.size() && b - a < cs.sub && (b == a || (img + mem[b].span <= kGzStageMax && stg + mem[b].rec.len <= kGzStageMax))) {
+            img += mem[b].span;
+            stg += ((u64)mem[b].rec.len + 15u) & ~(u64)15;
+            ++b;
+        }
+        const size_t cnt = b - a;
+        std::vector<std::pair<u64, u64>> sp(cnt);
+        std::vector<u64> ioff, ilen, ooff(cnt);
+        DfSizes s;
+        s.rec.resize(cnt);
+        u64 cur = 0;
+        for (size_t i = 0; i < cnt; ++i) {
+            const GzMember &m = mem[a + i];
+            sp[i] = {m.start, m.span};
+            s.rec[i] = m.rec;
+            ooff[i] = cur;
+            cur += ((u64)m.rec.len + 15u) & ~(u64)15;
+            if (m.split >= 0) {
+                s.splits.push_back(std::move(msplits[(size_t)m.split]));
+                s.splits.back().index = i;
+            }
+        }
+        if ((rc = df_gz_gather(g, w, in8, sp, ioff, ilen)) != BZ_OK) return rc;
+        if (!s.splits.empty()) {
+            s.len_small = ilen;
+            for (const DfSplitEntry &e : s.splits) s.len_small[e.index] = 0;
+        }
+        if ((rc = w->m_stage.ensure((size_t)cur + 64)) != BZ_OK) return rc;
+        if ((rc = df_decode_write(g, w, DF_KIND_GZIP, w->m_image.as<u8>(), ioff.data(), ilen.data(), cnt, w->m_stage.as<u8>(), ooff.data(), s, true)) !=
+            BZ_OK)
+            return rc;
+        float e1 = 0, e2 = 0;
+        (void)hipEventElapsedTime(&e1, w->ev[2], w->ev[3]);
+        (void)hipEventElapsedTime(&e2, w->ev[3], w->ev[4]);
+        t_write += e1;
+        t_check += e2;
+        // the stream ends with the first member that is not clean; its bytes in front of the fault belong to it
+        std::vector<GzSpan> tab;
+        u32 max_len = 0;
+        for (size_t i = 0; i < cnt && !cut; ++i) {
+            mem[a + i].rec = s.rec[i];
+            tab.push_back(GzSpan{ooff[i], done, s.rec[i].len, 0});
+            max_len = std::max(max_len, s.rec[i].len);
+            done += s.rec[i].len;
+            if (s.rec[i].verdict != BZ_OK) {
+                v = s.rec[i].verdict;
+                cut = true;
+                ms[0] = a + i + 1; // (the members behind it were found by pass 1, and are not decoded)
+            }
+        }
+        if ((rc = w->m_span.ensure(tab.size() * sizeof(GzSpan))) != BZ_OK) return rc;
+        const double t0 = df_now_ms();
+        HIPCHK(hipMemcpyAsync(w->m_span.p, tab.data(), tab.size() * sizeof(GzSpan), hipMemcpyHostToDevice, g->st));
+        if (df_launch_gz_compact(g->st, w->m_stage.as<u8>(), w->m_span.as<GzSpan>(), (u32)tab.size(), max_len, out8) != 0) return BZ_E_UNEXPECTED;
+        HIPCHK(hipStreamSynchronize(g->st));
+        w->mem_ms[3] += df_now_ms() - t0;
+        ms[7] += 1;
+        a = b;
+    }
+    if (out8) {
+        *out_len = done;
+        *verdict = v;
+    }
+    for (const GzMember &m : mem) df_inf_stats_add(w, m.rec);
+    // df_gpu_last_timings: [0] sizes [1] writing [2] checksums (the split members' phases where they belong) [3] search,
+    // gather and zero skip [4] compaction [5] their sum
+    w->t_stage[0] = (t_sizes + w->split_ms[0] + w->split_ms[1] + w->split_ms[2]) * 1e-3;
+    w->t_stage[1] = (t_write + w->split_ms[3] + w->split_ms[4] + w->split_ms[5]) * 1e-3;
+    w->t_stage[2] = (t_check + w->split_ms[6]) * 1e-3;
+    w->t_stage[3] = (w->mem_ms[0] + w->mem_ms[1] + w->mem_ms[2]) * 1e-3;
+    w->t_stage[4] = w->mem_ms[3] * 1e-3;
+    for (int k = 0; k < 5; ++k) w->t_stage[5] += w->t_stage[k];
+    return BZ_OK;
+}
+
+extern "C" int df_gpu_decode_members_device(bz_gpu_engine *g, const void *d_in, size_t in_len, void *d_out, size_t cap, uint64_t *out_len,
+                                            int32_t *verdict)
+{
+    return df_members_core(g, d_in, in_len, d_out, cap, nullptr, out_len, verdict);
+}
+
+// One upload, the device call with the engine's output buffer sized between its passes, one download: BZ_OK with the bytes,
+// or the stream's verdict with the bytes in front of it (as df_decode_buffer).
+extern "C" int df_decode_members_buffer(int device, const uint8_t *in, size_t in_len, uint8_t **out, size_t *out_len)
+{
+    if (!out || !out_len || (in_len && !in)) return BZ_E_PARAM;
+    *out = nullptr;
+    *out_len = 0;
+    if ((u64)in_len >= (1ull << 32)) return BZ_E_PARAM;
+    if (in_len == 0) { // (no member: BZ_OK, no bytes, no device)
+        *out = (uint8_t *)malloc(1);
+        return *out ? BZ_OK : BZ_E_NOMEM;
+    }
+    if (df_device_in_range(device) != BZ_OK) return BZ_E_NOGPU;
+    EngineLease lease(device, 2, 1);
+    if (lease.status() != BZ_OK) return lease.status();
+    bz_gpu_engine *g = lease.engine();
+    uint64_t n = 0;
+    int32_t v = BZ_OK;
+    int rc = g->dec_in.ensure(in_len + 64);
+    if (rc == BZ_OK && hipMemcpy(g->dec_in.p, in, in_len, hipMemcpyHostToDevice) != hipSuccess) rc = BZ_E_UNEXPECTED;
+    if (rc == BZ_OK) rc = df_members_core(g, g->dec_in.p, in_len, nullptr, 0, &g->oneshot_out, &n, &v);
+    if (rc == BZ_OK) rc = df_download(out, g->oneshot_out.p, (size_t)n);
+    lease.settle(rc); // (the stream's verdict is not the engine's business)
+    if (rc != BZ_OK) return rc;
+    *out_len = (size_t)n;
+    return v;
 }
 
 // ---- C ABI ------------------------------------------------------------------------------------------------

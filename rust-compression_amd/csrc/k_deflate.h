@@ -169,4 +169,18 @@ int df_launch_inflate_piece(hipStream_t st, bool write, const u8 *ebase, u32 ele
                             u8 *eout, u32 *emap);
 int df_launch_split_jump(hipStream_t st, u32 *src, u32 n, u32 *cnt);
 int df_launch_split_gather(hipStream_t st, u8 *out, const u32 *src, u32 n);
+// ---- every member of a gzip file (gz_members.h; k_gz_members.hip)
+struct GzSpan {
+    u64 src; // where the bytes lie, relative to the source buffer
+    u64 dst; // where they go, relative to the target buffer
+    u32 len;
+    u32 pad;
+};
+int df_launch_gz_search_count(hipStream_t st, const u8 *in, u32 len, u32 ntiles, u32 *cnt);
+// the candidates numbered [first, first + n) of the input, found in the tiles [tile0, tile0 + ntiles); base: per tile of the
+// INPUT, the candidates in front of it
+int df_launch_gz_search_list(hipStream_t st, const u8 *in, u32 len, u32 tile0, u32 ntiles, const u32 *base, u32 first, u32 n, u32 *list);
+int df_launch_gz_gather(hipStream_t st, const u8 *in, const GzSpan *spans, u32 count, u32 max_len, u8 *image);
+int df_launch_gz_zero_skip(hipStream_t st, const u8 *in, const u32 *from, const u32 *bound, u32 count, u32 *out);
+int df_launch_gz_compact(hipStream_t st, const u8 *staged, const GzSpan *spans, u32 count, u32 max_len, u8 *out);
 } // namespace dfgpu

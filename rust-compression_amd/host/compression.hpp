@@ -390,7 +390,9 @@ class BZip2Decoder {
 //   ZlibDecoder  src/zlib/decoder.rs      GZipDecoder  src/gzip/decoder.rs
 // The first next() collects the input range and decodes it in one df_decode_buffer call; the bytes come out in order,
 // then the Err item if the stream is bad (RFC 1951 / 1950 / 1952 decide, see the header), then None.
-template <int Kind> class DeflateFamilyDecoder {
+//   MultiGZipDecoder  every member of a gzip file (section 6, df_decode_members_buffer): what gzip(1) yields; GZipDecoder
+//                     stops behind the first member, as the reference's does
+template <int Kind, bool Members = false> class DeflateFamilyDecoder {
   public:
     using Input = uint8_t;
     using Output = uint8_t;
@@ -406,7 +408,8 @@ template <int Kind> class DeflateFamilyDecoder {
             for (; it != end; ++it) in.push_back(static_cast<uint8_t>(*it));
             uint8_t *out = nullptr;
             size_t n = 0;
-            verdict_ = df_decode_buffer(Kind, device_, in.data(), in.size(), &out, &n);
+            verdict_ = Members ? df_decode_members_buffer(device_, in.data(), in.size(), &out, &n)
+                               : df_decode_buffer(Kind, device_, in.data(), in.size(), &out, &n);
             if (out) {
                 buf_.assign(out, out + n);
                 bz_free(out);
@@ -459,6 +462,7 @@ template <int Kind> class DeflateFamilyDecoder {
 using Deflater = DeflateFamilyDecoder<DF_KIND_DEFLATE>;
 using ZlibDecoder = DeflateFamilyDecoder<DF_KIND_ZLIB>;
 using GZipDecoder = DeflateFamilyDecoder<DF_KIND_GZIP>;
+using MultiGZipDecoder = DeflateFamilyDecoder<DF_KIND_GZIP, true>;
 
 // DecodeIterator (src/traits/decoder.rs:45-86)
 template <class I, class S, class D> class DecodeIterator {

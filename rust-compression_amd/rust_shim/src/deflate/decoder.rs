@@ -3,15 +3,17 @@
 //! an error (if any) after the bytes in front of it.  The verdicts follow RFC 1951 / 1950 / 1952 (the
 //! contract in `include/bz2_mi355x.h`), not the reference's decoder, which swallows the errors of its
 //! block decoder (its `src/deflate/decoder.rs:376-383`).  `ZlibDecoder` and `GZipDecoder` are the same
-//! type with another `kind`.
+//! type with another `kind`; `MultiGZipDecoder` is the gzip kind over section 6 (`df_decode_members_buffer`).
 #[cfg(not(feature = "std"))]
 use alloc::vec::Vec;
 
 use crate::error::CompressionError;
 use crate::ffi;
 
+#[derive(Debug)]
 pub struct DeflateFamilyDecoder {
     kind: i32,
+    members: bool,
     ready: Option<Vec<u8>>,
     pos: usize,
     verdict: i32,
@@ -19,14 +21,23 @@ pub struct DeflateFamilyDecoder {
 
 impl DeflateFamilyDecoder {
     pub(crate) fn with_kind(kind: i32) -> Self {
-        Self { kind, ready: None, pos: 0, verdict: ffi::BZ_OK }
+        Self { kind, members: false, ready: None, pos: 0, verdict: ffi::BZ_OK }
+    }
+
+    /// every member of a gzip file (section 6 of the C ABI)
+    pub(crate) fn with_members() -> Self {
+        Self { kind: ffi::DF_KIND_GZIP, members: true, ready: None, pos: 0, verdict: ffi::BZ_OK }
     }
 
     fn run<I: Iterator<Item = u8>>(&mut self, iter: &mut I) {
         let input: Vec<u8> = iter.collect();
         let mut out: *mut u8 = core::ptr::null_mut();
         let mut n: usize = 0;
-        let rc = unsafe { ffi::df_decode_buffer(self.kind, 0, input.as_ptr(), input.len(), &mut out, &mut n) };
+        let rc = if self.members {
+            unsafe { ffi::df_decode_members_buffer(0, input.as_ptr(), input.len(), &mut out, &mut n) }
+        } else {
+            unsafe { ffi::df_decode_buffer(self.kind, 0, input.as_ptr(), input.len(), &mut out, &mut n) }
+        };
         let mut bytes = Vec::new();
         if !out.is_null() {
             bytes.extend_from_slice(unsafe { core::slice::from_raw_parts(out, n) });

@@ -52,7 +52,7 @@ pub mod prelude {
     #[cfg(all(feature = "deflate", feature = "mi355x"))]
     pub use crate::deflate::encoder::Inflater;
     #[cfg(all(feature = "gzip", feature = "mi355x"))]
-    pub use crate::gzip::decoder::GZipDecoder;
+    pub use crate::gzip::decoder::{GZipDecoder, MultiGZipDecoder};
     #[cfg(all(feature = "gzip", feature = "mi355x"))]
     pub use crate::gzip::encoder::GZipEncoder;
     #[cfg(all(feature = "zlib", feature = "mi355x"))]
