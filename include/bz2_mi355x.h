@@ -144,7 +144,7 @@ int bz_encode_buffer_multi(int level, const int *devices, int n_devices, const u
 int bz_encode_batch(int level, int device, const uint8_t *const *ins, const size_t *lens, size_t count,
                     uint8_t **out, uint64_t *out_off, uint64_t *out_len);
 void bz_free(void *p);
-/* Contexts and one-shot calls park their engines (batch workspace: about 36.3 MB of HBM per block of the largest
+/* Contexts and one-shot calls park their engines (batch workspace: about 36.4 MB of HBM per block of the largest
  * chunk seen, i.e. up to ~9 GB per lane with the default 192 MiB chunks, two lanes per listed device), device staging
  * buffers and 2 x BZ_ENC_CHUNK_MIB of pinned host memory in a per-process cache (two device lists at most) when they
  * end, so that the next one does not pay hipMalloc / hipHostMalloc again (fresh device memory costs about 40 ms per
@@ -175,11 +175,11 @@ int bz_peer_copy_selftest(const int *devices, int n_devices, size_t bytes, int *
  * ======================================================================== */
 typedef struct bz_gpu_engine bz_gpu_engine;
 
-/* max_blocks_in_flight bounds the workspace (about 36.3 MB of HBM per
+/* max_blocks_in_flight bounds the workspace (about 36.4 MB of HBM per
  * block); inputs with more blocks are processed in several batches. */
 int bz_gpu_engine_create(bz_gpu_engine **out, int device, size_t max_blocks_in_flight);
 void bz_gpu_engine_destroy(bz_gpu_engine *g);
-/* The batch workspace (about 36.3 MB per block in flight) is made by the first call that needs it and grows with the
+/* The batch workspace (about 36.4 MB per block in flight) is made by the first call that needs it and grows with the
  * largest call seen; a caller who knows the size of the calls to come reserves it once (fresh device memory costs about
  * 40 ms per GiB here: growing means freeing and paying again). */
 int bz_gpu_engine_reserve(bz_gpu_engine *g, size_t blocks);

@@ -357,6 +357,9 @@ struct BwtArgs {
     // fused radix passes (no per-pass histogram kernel; tile offsets by decoupled look-back)
     u32 *gh_tiles;                   // [nb][kTilesPerBlock][3][kMaxBins] per-tile digit counts of a whole phase
     u32 *gbase;                      // [nb][3][kMaxBins] digits smaller, per digit position
+    u32 pack_blocks;                 // host: blocks of the batch whose digit counts come from k_pack_text (byte accounting only)
+    u64 *abits;                      // [nb * kSlot / 64] init: key(VA[i]) != key(VA[i-1]) along phase A's order, one bit per position
+                                     //   (written by the WALK pass of phase B, read by the first refinement in place of the keys)
     u32 *tile_state;                 // [nb][kTilesPerBlock][kMaxBins] look-back words: epoch | flag | value
     u32 *tickets;                    // [kSortEpochs][8] tile tickets per pass and XCD
     u32 *sort_err;                   // [1] a look-back that gave up

@@ -243,7 +243,7 @@ static void resources_put(EncResources *r)
     else resources_free(r);
 }
 
-// What a finished context leaves behind for the next one -- engines with their batch workspace (about 36.3 MB per
+// What a finished context leaves behind for the next one -- engines with their batch workspace (about 36.4 MB per
 // block of the largest job seen), device staging buffers, 2 x chunk of pinned host memory -- is released here.
 // ---- diagnostic for hosts with several devices -------------------------------------------------------------------------
 // What a context over `devices` does between consecutive lanes when a job's unconsumed tail changes device

@@ -139,12 +139,15 @@ static constexpr WsBuf kWorkspace[] = {
     {&bz_gpu_engine::packlist, sizeof(PackBlock), 0, false},
     {&bz_gpu_engine::gh_tiles, (size_t)kTilesPerBlock * 3 * kMaxBins * 4, 0, true},
     {&bz_gpu_engine::gbase, (size_t)3 * kMaxBins * 4, 0, true},
+    // the key boundaries of the init's order, a bit per position (k_radix_scatter_lb<SRC_WALKA> -> k_group_refine<true, true>).
+    // Not `newbits`: the refinement reads the bit behind a wave's span when another tile may have written that word of newbits.
+    {&bz_gpu_engine::abits, kSlot / 8, 256, true},
     {&bz_gpu_engine::tile_state, (size_t)kTilesPerBlock * kMaxBins * 4, 0, true},
     {&bz_gpu_engine::tickets, 0, (size_t)kSortEpochs * 8 * 4 + 64, true},
 };
-// Per block in flight, before DevBuf's slack of one eighth: 36 329 056 bytes (32 700 000 without the fused radix passes).
+// Per block in flight, before DevBuf's slack of one eighth: 36 441 696 bytes (32 700 000 without the fused radix passes).
 // The batch workspace holds `ws_blocks` blocks in flight: as many as the call at hand needs (up to max_blocks, the batch
-// size), grown when a later call needs more -- a context that only ever sees small inputs does not take 36.3 MB x max_blocks.
+// size), grown when a later call needs more -- a context that only ever sees small inputs does not take 36.4 MB x max_blocks.
 static int ensure_workspace(bz_gpu_engine *g, size_t need_blocks)
 {
     if (need_blocks > g->max_blocks) need_blocks = g->max_blocks;
@@ -807,6 +810,8 @@ static BwtArgs make_bwt_args(bz_gpu_engine *g, u32 nb)
     x.keyinfo = g->keyinfo.as<u8>();
     x.gh_tiles = g->gh_tiles.as<u32>();
     x.gbase = g->gbase.as<u32>();
+    x.abits = g->abits.as<u64>();
+    x.pack_blocks = 0;
     x.tile_state = g->tile_state.as<u32>();
     x.tickets = g->tickets.as<u32>();
     x.sort_err = g->tickets.p ? g->tickets.as<u32>() + (size_t)kSortEpochs * 8 : nullptr; // (no fused passes: not allocated)
@@ -906,11 +911,15 @@ static int sort_batch(bz_gpu_engine *g, const BwtArgs &ba, u32 max_n, u64 total_
     }
     bool wide = false;
     u32 min_chars = 8;
+    u32 pack_blocks = 0; // (KeyInfo {bits, chars, form}: the pair form with 10-bit codes, counts_from_pack in k_bwt.hip)
     for (u32 i = 0; i < ba.nb; ++i) {
         if (ki[(size_t)i * 4 + 2] == 0 && ki[(size_t)i * 4] >= 8) wide = true; // (a pair-form key is never wider than 30 bits)
         if (ki[(size_t)i * 4 + 1] < min_chars) min_chars = ki[(size_t)i * 4 + 1];
+        if (ki[(size_t)i * 4 + 2] != 0 && ki[(size_t)i * 4] == 10) pack_blocks += 1;
     }
-    return run_bwt(g->st, ba, max_n, total_n, g->h_active, sorted, prof, round_active, wide, min_chars);
+    BwtArgs bs = ba;
+    bs.pack_blocks = pack_blocks;
+    return run_bwt(g->st, bs, max_n, total_n, g->h_active, sorted, prof, round_active, wide, min_chars);
 }
 
 // Encode one batch of local blocks (descriptors already in g->lblocks / g->lcrc; `descs` is the host copy).  The whole

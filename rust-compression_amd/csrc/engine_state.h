@@ -66,7 +66,7 @@ struct bz_gpu_engine {
     // batch workspace (sized by max_blocks)
     DevBuf lblocks, lcrc, SA, R, KA, VA, KB, VB, tile_hist, count, flags, tlo, tln, nonfinal, active, per_k,
         per_shift, lin_p, lin_sig, bin_cursor, pb_gate, bin_base, newbits, sym_code, keyinfo, count2, tile_nf, L, orig_ptr, inuse_bits, summ, summ_len, init_state, rank8, mtf_heads_buf, headbits, hcount, tile_hcnt, tile_hbase, ptext, pair_bits, ztile_last, ztile_cnt, zstate, ztick, mtf,
-        mtf_freq, bout, selector, code_len, group_bitoff, lm_scratch, hglen, hpack, hrfreq, hlm, hpass, stream, error_flag, packlist, gh_tiles, gbase,
+        mtf_freq, bout, selector, code_len, group_bitoff, lm_scratch, hglen, hpack, hrfreq, hlm, hpass, stream, error_flag, packlist, gh_tiles, gbase, abits,
         tile_state, tickets;
     u32 sort_epoch = 0; // fused radix passes: tag of the current pass in tile_state / tickets
     bool zle_fused_broken = false; // the one-launch ZLE stage misbehaved on this engine once: it stays on the three kernels

@@ -54,7 +54,8 @@ enum { SRC_TEXT = 0, SRC_PAIRS = 1, SRC_MM = 2, SRC_WALK = 3, SRC_SURV = 4, SRC_
        SRC_PERJ = 10,   // the survivors keyed by their own start (the period round, see k_period_find)
        SRC_PACKED = 11,   // one word per element: the digits still to be sorted by above bit 20, the rotation below (round 4:
                           // the pass in front of the last one of phase A writes these, the last one reads them)
-       SRC_PERJK = 12 };  // PERJ's keys as its histogram kernel kept them (bit 31: the entry takes no part)
+       SRC_PERJK = 12,    // PERJ's keys as its histogram kernel kept them (bit 31: the entry takes no part)
+       SRC_WALKA = 13 };  // WALK that also writes the key boundaries of the order it walks as a bitmap (a.abits; fused init)
 // sources whose sequence is the compacted list (length count[lb]) rather than all n positions
 template <int SRC> struct src_is_list {
     static constexpr bool value = (SRC == SRC_PAIRS || SRC == SRC_SURV || SRC == SRC_LISTG || SRC == SRC_PERJ || SRC == SRC_PERJK || SRC == SRC_PACKED);
@@ -67,6 +68,13 @@ struct KeyInfo {
     u8 form;   // 0: one code per symbol; 1: one code per PAIR of neighbouring symbols (round 7)
     u8 pad;
 };
+
+// A block whose three 10-bit digits are each exactly one code of its packed string (pair form, 10-bit codes: key(j) =
+// code(j) << 20 | code(j + 2) << 10 | code(j + 4)).  j -> j + 2 -> j + 4 (mod n) are bijections of the positions, so the
+// three digit histograms of such a block are one histogram, that of the codes of positions 0 .. n-1: k_pack_text has
+// every code in a register and counts them, k_ghist_text leaves the block alone, k_ghist_scan uses the one set of
+// counts for all three digit positions.  (Only under 10/10/10 digits: a batch with wide keys cuts the key elsewhere.)
+__host__ __device__ __forceinline__ bool counts_from_pack(KeyInfo ki) { return ki.form != 0 && ki.bits == 10; }
 
 // key(j): `chars` re-coded symbols of the rotation starting at j, first symbol most significant.
 // The block's symbols are kept a second time as a PACKED string (k_pack_text): `bits` bits per position, first
@@ -115,6 +123,108 @@ __device__ __forceinline__ void pkey_rows(const u8 *__restrict__ pt, const u32 (
 #pragma unroll
         for (u32 r = 0; r < (u32)ROWS; ++r) key[r] = pkey_form<false>(pt, j[r], ki);
     }
+}
+
+// key(j) and key(j + d), d = chars % n <= 8, from ONE unaligned 16-byte load (the WALK pass of phase B that also writes
+// the key boundaries of phase A's order, SRC_WALKA: it walks i -> VA[i] and needs key(VA[i] - c) for its own sort and
+// key(VA[i]) for the boundary).  The second key begins s = (j * bits & 7) + d * bits <= 7 + 60 = 67 bits behind the load's
+// first bit (d * bits <= 60: pair form 6 x 10, 8 x 7; symbol form chars * bits <= 32) and its last code ends at most
+// 7 + (2 * chars - 1) * bits <= 117 bits behind it (pair form, three 10-bit codes at j + 6, j + 8, j + 10; four 7-bit
+// codes: 7 + 15 * 7 = 112; symbol form: 7 + 2 * 32 = 71).  Position j + d <= n + 7 reads codes up to position
+// n + 14: the packed string repeats positions 0 .. 15 (cyclically) behind position n - 1, so neither the wrap nor a block
+// shorter than a key needs a path of its own.  The load ends inside the block's slot of the packed text.
+static_assert(((size_t)kMaxBlockLen + 16u) * 10u / 8u + 16u <= (size_t)kPtSlot, "a 16-byte load at the last position leaves the packed text's slot");
+// 64 bits of the 128-bit string hi:lo from bit s (counted from the top, s < 128); the bits behind the string are zeros.
+// A key of w bits that begins at bit s is whole in the window iff s + w <= 128: s <= 67 with w <= 50 (pair form: the last
+// code ends (chars - 1) * bits <= 50 bits behind the first) or s <= 39 with w <= 32 (symbol form) -- the geometry of
+// k_key_params (bits * chars <= 32 in the symbol form; 6 symbols of at most 10 bits or 8 of at most 7 in the pair form).
+// A geometry with wider keys needs a third word here.
+__device__ __forceinline__ u64 bits_window(u64 hi, u64 lo, u32 s)
+{
+    const u64 x = s < 64u ? hi : lo, y = s < 64u ? lo : 0ull;
+    const u32 t = s & 63u;
+    return t ? ((x << t) | (y >> (64u - t))) : x;
+}
+// the key whose first bit is bit 63 of v (what pkey_form makes of its load)
+template <bool PAIR>
+__device__ __forceinline__ u32 pkey_window(u64 v, KeyInfo ki)
+{
+    const u32 bits = ki.bits;
+    if (!PAIR) return (u32)(v >> (64u - bits * ki.chars)); // (1 .. 32 bits)
+    const u32 m = (1u << bits) - 1u;
+    u32 key = ((u32)(v >> (64u - bits)) << (2u * bits)) | (((u32)(v >> (64u - 3u * bits)) & m) << bits) |
+              ((u32)(v >> (64u - 5u * bits)) & m);
+    const bool four = ki.chars == 8;
+    return (key << (four ? bits : 0u)) | ((u32)(v >> (four ? 64u - 7u * bits : 0u)) & (four ? m : 0u));
+}
+// The rows of a lane for SRC_WALKA: key[r] = key(j), val[r] = j = VA[i] - c as fetch_rows<SRC_WALK>, and the bitmap
+// abits[i] = (i == 0) || key(VA[i]) != key(VA[i - 1]), a 64-bit word per row of 64 positions (the layout of newbits).
+// The final order of the init is sorted by key(j) first, so the key at its position i is the i-th smallest key of the
+// block -- the key at position i of phase A's order: this bitmap IS the bitmap of the first refinement's primary-key
+// changes, and the passes behind this one need not carry key(j) to the refinement (k_group_refine<true, true>).
+// The neighbour's key comes by wave_shr1, lane 63 of the row in front by a lane read, the element in front of the wave's
+// span (lane 0, row 0) from one extra load -- need_prev of k_group_refine.  Rows at or beyond cnt store nothing.
+// The sixteen 16-byte loads are fetched in two halves of eight: all sixteen in flight are 64 registers where
+// fetch_rows<SRC_WALK> holds 32, and the kernel has to stay under 128 for two workgroups per CU.  The form branch is
+// taken once per half (pkey_rows says why).
+template <int ROWS>
+__device__ __forceinline__ u32 fetch_rows_walk_abits(const BwtArgs &a, u32 lb, const u8 *__restrict__ pt, u32 n,
+                                                     const u32 *__restrict__ Vin, u32 wbase, u32 l, u32 cnt, KeyInfo ki,
+                                                     u32 (&key)[ROWS], u32 (&val)[ROWS])
+{
+    static_assert(ROWS % 2 == 0, "the rows are fetched in two halves");
+    constexpr u32 H = (u32)ROWS / 2u;
+    const size_t base = (size_t)lb * kSlot;
+    const u32 cm = ki.chars % n, dbits = cm * ki.bits, first = wbase + l;
+    u32 ok = 0;
+#pragma unroll
+    for (u32 r = 0; r < (u32)ROWS; ++r) {
+        const u32 idx = first + r * 64u;
+        const u32 c = idx < cnt ? idx : cnt - 1u;
+        const u32 s = ld_stream(Vin + base + c);
+        val[r] = (s >= cm) ? s - cm : s + n - cm;
+        ok |= (idx < cnt ? 1u : 0u) << r;
+    }
+    u32 kprev = 0; // key(VA[wbase - 1]), lane 0
+    if (l == 0 && wbase > 0 && wbase < cnt) kprev = pkey(pt, Vin[base + wbase - 1u], ki);
+    u32 klast = 0; // lane 63's key(VA[i]) of the row in front (wave-uniform)
+#pragma unroll
+    for (u32 h = 0; h < 2; ++h) {
+        u64 hi[H], lo[H];
+        u32 ka[H];
+#pragma unroll
+        for (u32 r = 0; r < H; ++r) {
+            u64 w2[2];
+            __builtin_memcpy(w2, pt + ((val[h * H + r] * (u32)ki.bits) >> 3), 16); // (one global_load_dwordx4)
+            hi[r] = __builtin_bswap64(w2[0]);
+            lo[r] = __builtin_bswap64(w2[1]);
+        }
+        if (ki.form) {
+#pragma unroll
+            for (u32 r = 0; r < H; ++r) {
+                const u32 s0 = (val[h * H + r] * (u32)ki.bits) & 7u;
+                key[h * H + r] = pkey_window<true>(bits_window(hi[r], lo[r], s0), ki);
+                ka[r] = pkey_window<true>(bits_window(hi[r], lo[r], s0 + dbits), ki);
+            }
+        } else {
+#pragma unroll
+            for (u32 r = 0; r < H; ++r) {
+                const u32 s0 = (val[h * H + r] * (u32)ki.bits) & 7u;
+                key[h * H + r] = pkey_window<false>(bits_window(hi[r], lo[r], s0), ki);
+                ka[r] = pkey_window<false>(bits_window(hi[r], lo[r], s0 + dbits), ki);
+            }
+        }
+#pragma unroll
+        for (u32 r = 0; r < H; ++r) {
+            const u32 idx = first + (h * H + r) * 64u;
+            u32 p = wave_shr1(ka[r]);
+            if (l == 0) p = (h == 0 && r == 0) ? kprev : klast;
+            const u64 m = __ballot(idx < cnt && (idx == 0u || ka[r] != p));
+            if (l == 0 && idx < cnt) a.abits[(base + idx) >> 6] = m;
+            klast = wave_lane(ka[r], 63);
+        }
+    }
+    return ok;
 }
 
 // The new-group starts of a refined list as a BITMAP: one 64-bit word per row of 64 list elements (the ballot a
@@ -699,6 +809,7 @@ __global__ __launch_bounds__(kSortThreads) void k_ghist_text(BwtArgs a, u32 *__r
     const u8 *text = a.rle + d.rle_off;
     const u8 *pt = a.ptext + (size_t)lb * kPtSlot;
     const KeyInfo ki = reinterpret_cast<const KeyInfo *>(a.keyinfo)[lb];
+    if (B0 == 10 && B1 == 10 && B2 == 10 && !Kstore && counts_from_pack(ki)) return; // (k_pack_text has counted the block's codes)
     for (u32 i = threadIdx.x; i < 2 * NB0; i += kSortThreads) (&s_h0[0][0])[i] = 0;
     for (u32 i = threadIdx.x; i < 2 * NB1; i += kSortThreads) (&s_h1[0][0])[i] = 0;
     for (u32 i = threadIdx.x; i < 2 * NB2; i += kSortThreads) (&s_h2[0][0])[i] = 0;
@@ -731,8 +842,10 @@ __global__ __launch_bounds__(kSortThreads) void k_ghist_text(BwtArgs a, u32 *__r
 // per block and digit position: digits smaller (exclusive scan of the summed tile counts).
 // ntiles_from_count: the tiles that hold counts are those of the list of length count[lb] (the
 // refinement that took them), else those of the block.  Sets count[lb] to the number of keys.
+// pack_counts: the launch follows k_ghist_text<10, 10, 10>; a counts_from_pack block then has ONE set of counts (digit
+// position 0 of its entries, from k_pack_text), which gives the bases of all three digit positions.
 __global__ __launch_bounds__(kSortThreads) void k_ghist_scan(BwtArgs a, u32 ndig, u32 nbins0, u32 nbins1, u32 nbins2,
-                                                             u32 ntiles_from_count, u32 span = 1u)
+                                                             u32 ntiles_from_count, u32 span = 1u, u32 pack_counts = 0u)
 {
     __shared__ u32 s_wsum[kSortThreads / 64];
     const u32 lb = blockIdx.x;
@@ -741,6 +854,8 @@ __global__ __launch_bounds__(kSortThreads) void k_ghist_scan(BwtArgs a, u32 ndig
     const u32 ntiles = ((len + kSortTile - 1) / kSortTile + span - 1u) / span; // (span: tiles per entry of the counts, k_ghist_text)
     const u32 *gt = a.gh_tiles + (size_t)lb * kTilesPerBlock * 3 * kMaxBins;
     u32 total0 = 0;
+    const bool one_set = pack_counts && counts_from_pack(reinterpret_cast<const KeyInfo *>(a.keyinfo)[lb]);
+    if (one_set) ndig = 1;
     for (u32 dpos = 0; dpos < ndig; ++dpos) {
         const u32 nbins = dpos == 0 ? nbins0 : (dpos == 1 ? nbins1 : nbins2);
         const u32 per = (nbins + kSortThreads - 1) / kSortThreads; // bins per thread, consecutive (<= 4)
@@ -766,7 +881,13 @@ __global__ __launch_bounds__(kSortThreads) void k_ghist_scan(BwtArgs a, u32 ndig
         u32 run = carry + inc - mine;
         for (u32 q = 0; q < per; ++q) {
             const u32 bin = threadIdx.x * per + q;
-            if (bin < nbins) a.gbase[((size_t)lb * 3 + dpos) * kMaxBins + bin] = run;
+            if (bin < nbins) {
+                a.gbase[((size_t)lb * 3 + dpos) * kMaxBins + bin] = run;
+                if (one_set) {
+                    a.gbase[((size_t)lb * 3 + 1) * kMaxBins + bin] = run;
+                    a.gbase[((size_t)lb * 3 + 2) * kMaxBins + bin] = run;
+                }
+            }
             run += tot[q];
         }
         if (dpos == 0) total0 = total;
@@ -851,8 +972,9 @@ __global__ __launch_bounds__(TILE / ROWS) void k_radix_scatter_lb(BwtArgs a, u32
     u16 *my_cnt = s_cnt + w * NB;
     u32 key[kRows], val[kRows];
     u32 rnk[kRows]; // 0xFFFFFFFF = takes no part
-    const u32 okmask =
-        fetch_rows<SRC, ROWS>(a, lb, pt, n, hm, Kin, Vin, start + w * (64u * kRows) + l, cnt, ki, key, val);
+    const u32 okmask = (SRC == SRC_WALKA)
+        ? fetch_rows_walk_abits<ROWS>(a, lb, pt, n, Vin, start + w * (64u * kRows), l, cnt, ki, key, val)
+        : fetch_rows<SRC, ROWS>(a, lb, pt, n, hm, Kin, Vin, start + w * (64u * kRows) + l, cnt, ki, key, val);
     // SRC_MMC (the walk round that follows the first refinement): the list this pass builds is refined by
     // (group of j, rank of rotation j+h), and the rotation j+h of the element walked at position i is SA[i]: its rank
     // is the head of the group position i lies in -- the last new-group start at or before i, which the first
@@ -1730,7 +1852,10 @@ constexpr u32 kLbNone = 0xFFFFFu;
 #else
 #define RF_T(k) do { } while (0)
 #endif
-template <bool INIT>
+// ABITS (with INIT): the primary keys are not read.  The list is the init's final order, sorted by key(j) first, and
+// where key(j) changes along it is known already: a.abits, the bitmap the WALK pass of phase B wrote over phase A's order
+// (fetch_rows_walk_abits).  A row's primary boundaries are its word of that bitmap, read the way newbits words are read.
+template <bool INIT, bool ABITS = false>
 __global__ __launch_bounds__(kSortThreads, 4) void k_group_refine(BwtArgs a, u32 step, u32 next_step, u32 round,
                                                                 const u32 *__restrict__ K,
                                                                 const u32 *__restrict__ V, u32 *__restrict__ W,
@@ -1773,7 +1898,8 @@ __global__ __launch_bounds__(kSortThreads, 4) void k_group_refine(BwtArgs a, u32
     const u32 hm = INIT ? (u32)ki.chars % n : (((u32)ki.chars * 2u) << step) % n;
     const u8 *pt = a.ptext + (size_t)lb * kPtSlot;
     const size_t base = (size_t)lb * kSlot;
-    if (INIT && a.pb_gate[lb] == 0u) K = a.KA; // phase B was done in LDS: phase A's keys are the list's keys
+    static_assert(INIT || !ABITS, "the boundary bitmap belongs to the init");
+    if (INIT && !ABITS && a.pb_gate[lb] == 0u) K = a.KA; // phase B was done in LDS: phase A's keys are the list's keys
     for (u32 i = threadIdx.x; i < 3072u; i += kSortThreads) s_stage[i] = 0; // (s_gh and s_bcnt)
     if (threadIdx.x == 0) s_nonfinal = 0;
     const u32 w = threadIdx.x >> 6, l = threadIdx.x & 63u;
@@ -1787,12 +1913,14 @@ __global__ __launch_bounds__(kSortThreads, 4) void k_group_refine(BwtArgs a, u32
     u32 ng0 = 0, ns10 = 0, ns20 = 0; // the element behind it (lane 63)
     const bool need_prev = (l == 0) && (first > 0) && (first < cnt);
     const bool need_next = (l == 63) && (wbase + 1024u < cnt);
+    // (ABITS) lane r < 17 holds the boundary word of row r; row 16 is the row behind the wave's span
+    const u64 aword = ABITS ? newbits_lane_word(a.abits, base, wbase, cnt, l, false) : 0ull;
     {
 #pragma unroll
         for (u32 r = 0; r < 16; ++r) {
             const u32 idx = first + r * 64u;
             const u32 c = idx < cnt ? idx : cnt - 1u;
-            const u32 kk = ld_stream(K + base + c);
+            const u32 kk = ABITS ? 0u : ld_stream(K + base + c);
             const u32 vv = ld_stream(V + base + c);
             if (INIT) {
                 jv[r] = vv;
@@ -1809,14 +1937,14 @@ __global__ __launch_bounds__(kSortThreads, 4) void k_group_refine(BwtArgs a, u32
         }
         u32 pj = 0, nj = 0;
         if (need_prev) {
-            const u32 kk = K[base + wbase - 1], vv = V[base + wbase - 1];
+            const u32 kk = ABITS ? 0u : K[base + wbase - 1], vv = V[base + wbase - 1];
             pg0 = INIT ? 0u : (kk & 0xFFFFFu);
             ps10 = INIT ? kk : ((kk >> 20) | ((vv >> 20) << 12));
             const u32 t = vv + hm;
             pj = t >= n ? t - n : t;
         }
         if (need_next) {
-            const u32 kk = K[base + wbase + 1024u], vv = V[base + wbase + 1024u];
+            const u32 kk = ABITS ? 0u : K[base + wbase + 1024u], vv = V[base + wbase + 1024u];
             ng0 = INIT ? 0u : (kk & 0xFFFFFu);
             ns10 = INIT ? kk : ((kk >> 20) | ((vv >> 20) << 12));
             const u32 t = vv + hm;
@@ -1846,7 +1974,8 @@ __global__ __launch_bounds__(kSortThreads, 4) void k_group_refine(BwtArgs a, u32
             p2 = q2;
         }
         const bool os = ok && ((idx == 0) || (!INIT && gk[r] != pg));
-        const bool ns = ok && (os || (s1[r] != p1) || (s2[r] != p2));
+        const bool ns = ABITS ? (ok && (os || ((wave_lane64(aword, r) >> l) & 1ull) || (s2[r] != p2)))
+                              : (ok && (os || (s1[r] != p1) || (s2[r] != p2)));
         mn[r] = __ballot(ns);
         if (l == 0 && ok) a.newbits[(base + idx) >> 6] = mn[r];
         if (mn[r]) wl_new = (int)(wbase + r * 64u + 63u - __clzll(mn[r]));
@@ -1857,7 +1986,10 @@ __global__ __launch_bounds__(kSortThreads, 4) void k_group_refine(BwtArgs a, u32
     }
     // does the element behind the wave's span start a new group?  (lane 63 holds both sides)
     bool next_after = true;
-    if (need_next) next_after = (gk[15] != ng0) || (s1[15] != ns10) || (s2[15] != ns20);
+    if (ABITS) {
+        const bool abit_next = wave_lane64(aword, 16) & 1ull; // (the word of position wbase + 1024: loaded when that is inside the list)
+        if (need_next) next_after = abit_next || (s2[15] != ns20);
+    } else if (need_next) next_after = (gk[15] != ng0) || (s1[15] != ns10) || (s2[15] != ns20);
     next_after = wave_lane((u32)next_after, 63) != 0u;
     if (l == 0) {
         s_wold[w] = INIT ? 0 : wl_old;
@@ -3208,17 +3340,26 @@ __global__ __launch_bounds__(kSortThreads) void k_pack_text(BwtArgs a, u8 *__res
     __shared__ u32 s_pair[kPairWords];
     __shared__ u16 s_before[kPairWords];       // (a block in the pair form has at most 1024 pairs)
     __shared__ u32 s_wsum[kSortThreads / 64];
-    u32 tile, lb;
-    xcd_remap(gridDim.x, a.nb, tile, lb);
+    __shared__ u32 s_hist[2][1024];            // (counts_from_pack: the codes of the positions < n, two interleaved copies)
+    u32 span, lb;
+    xcd_remap(gridDim.x, a.nb, span, lb);
     if (lb == 0xFFFFFFFFu) return;
     const BlockDesc d = a.blocks[lb];
     const u32 n = d.n;
-    const u32 start = tile * kSortTile;
-    if (n == 0 || start >= n + 16u) return;
+    // kGhSpan tiles per workgroup, for every block: the pair map and its prefix counts are set up once for them, and the
+    // counts of the codes leave as one set per span -- the layout k_ghist_text writes and k_ghist_scan sums.
+    // (One tile per workgroup for the blocks that are not counted, the counted ones done by the first workgroup of every
+    // eight, was measured and is not kept: the workgroups that stay land on an eighth of the CUs, and the kernel took
+    // 2.57 ms per GiB of text instead of 1.27 -- profiles/r18_init_packed.md.)
+    const u32 start0 = span * kGhSpan * kSortTile;
+    if (n == 0 || start0 >= n + 16u) return;
     const u8 *text = a.rle + d.rle_off;
     const KeyInfo ki = reinterpret_cast<const KeyInfo *>(a.keyinfo)[lb];
     const u32 bits = ki.bits;
     const bool pairs = ki.form != 0;
+    const bool count = a.gh_tiles != nullptr && counts_from_pack(ki);
+    if (count)
+        for (u32 i = threadIdx.x; i < 2u * 1024u; i += kSortThreads) (&s_hist[0][0])[i] = 0;
     if (pairs) {
         static_assert(kPairWords == 4 * kSortThreads, "four words of the pair map per thread");
         const uint4 w4 = reinterpret_cast<const uint4 *>(a.pair_bits + (size_t)lb * kPairWords)[threadIdx.x];
@@ -3240,54 +3381,66 @@ __global__ __launch_bounds__(kSortThreads) void k_pack_text(BwtArgs a, u8 *__res
     }
     __syncthreads();
     u8 *s_bytes = reinterpret_cast<u8 *>(s_out);
+    u32 *const hist = s_hist[threadIdx.x & 1u];
+#pragma unroll 1
+    for (u32 sp = 0; sp < kGhSpan; ++sp) {
+        const u32 tile = span * kGhSpan + sp, start = tile * kSortTile;
+        if (start >= n + 16u) break;
 #pragma unroll
-    for (u32 h = 0; h < 2; ++h) {
-        const u32 g = h * kSortThreads + threadIdx.x; // group inside the tile
-        const u32 i0 = start + g * 8u;
-        u32 lo = 0, hi = 0, ninth = 0; // the group's eight bytes and the one behind them
-        if (i0 + 9u <= n) {
-            const uintptr_t p = reinterpret_cast<uintptr_t>(text + i0);
-            const u32 *ap = reinterpret_cast<const u32 *>(p & ~(uintptr_t)3);
-            const u32 w0 = ap[0], w1 = ap[1], w2 = ap[2];
-            lo = __builtin_amdgcn_alignbyte(w1, w0, (u32)(p & 3u));
-            hi = __builtin_amdgcn_alignbyte(w2, w1, (u32)(p & 3u));
-            ninth = (w2 >> (8u * (u32)(p & 3u))) & 0xFFu;
-        } else if (i0 < n + 16u) {
-            for (u32 q = 0; q < 9; ++q) {
-                const u32 i = i0 + q;
-                const u32 c = (i < n + 16u + (q >> 3)) ? (u32)text[i < n ? i : (i - n) % n] : 0u;
-                if (q < 4) lo |= c << (8u * q);
-                else if (q < 8) hi |= c << (8u * (q - 4u));
-                else ninth = c;
+        for (u32 h = 0; h < 2; ++h) {
+            const u32 g = h * kSortThreads + threadIdx.x; // group inside the tile
+            const u32 i0 = start + g * 8u;
+            u32 lo = 0, hi = 0, ninth = 0; // the group's eight bytes and the one behind them
+            if (i0 + 9u <= n) {
+                const uintptr_t p = reinterpret_cast<uintptr_t>(text + i0);
+                const u32 *ap = reinterpret_cast<const u32 *>(p & ~(uintptr_t)3);
+                const u32 w0 = ap[0], w1 = ap[1], w2 = ap[2];
+                lo = __builtin_amdgcn_alignbyte(w1, w0, (u32)(p & 3u));
+                hi = __builtin_amdgcn_alignbyte(w2, w1, (u32)(p & 3u));
+                ninth = (w2 >> (8u * (u32)(p & 3u))) & 0xFFu;
+            } else if (i0 < n + 16u) {
+                for (u32 q = 0; q < 9; ++q) {
+                    const u32 i = i0 + q;
+                    const u32 c = (i < n + 16u + (q >> 3)) ? (u32)text[i < n ? i : (i - n) % n] : 0u;
+                    if (q < 4) lo |= c << (8u * q);
+                    else if (q < 8) hi |= c << (8u * (q - 4u));
+                    else ninth = c;
+                }
+            }
+            // the 8 * bits bits of the group, most significant byte first: two halves of four codes (at most 40 bits each)
+            u64 va = 0, vb = 0;
+#pragma unroll
+            for (u32 q = 0; q < 8; ++q) {
+                const u32 byte = ((q < 4 ? lo >> (8u * q) : hi >> (8u * (q - 4u)))) & 0xFFu;
+                u32 code;
+                if (pairs) {
+                    const u32 b2 = q == 7 ? ninth : (((q + 1 < 4 ? lo >> (8u * (q + 1)) : hi >> (8u * (q + 1 - 4u)))) & 0xFFu);
+                    const u32 pr = (byte << 8) | b2;
+                    code = (u32)s_before[pr >> 5] + __popc(s_pair[pr >> 5] & ((1u << (pr & 31u)) - 1u));
+                    if (i0 + q >= n + 16u) code = 0; // (a position nobody reads; its bytes are no pair of the map)
+                    if (count && i0 + q < n) atomicAdd(&hist[code], 1u);
+                } else {
+                    code = s_code[byte];
+                }
+                if (q < 4) va = (va << bits) | (u64)code;
+                else vb = (vb << bits) | (u64)code;
+            }
+            for (u32 k = 0; k < bits; ++k) {
+                // byte k of (va << 4 * bits | vb), an 8 * bits bit number: its bits [sh, sh + 8), sh = 8 * (bits - 1 - k)
+                const u32 sh = 8u * (bits - 1u - k), half = 4u * bits;
+                u32 o = sh >= half ? (u32)(va >> (sh - half)) : ((u32)(vb >> sh) | (u32)(va << (half - sh)));
+                s_bytes[g * bits + k] = (u8)o;
             }
         }
-        // the 8 * bits bits of the group, most significant byte first: two halves of four codes (at most 40 bits each)
-        u64 va = 0, vb = 0;
-#pragma unroll
-        for (u32 q = 0; q < 8; ++q) {
-            const u32 byte = ((q < 4 ? lo >> (8u * q) : hi >> (8u * (q - 4u)))) & 0xFFu;
-            u32 code;
-            if (pairs) {
-                const u32 b2 = q == 7 ? ninth : (((q + 1 < 4 ? lo >> (8u * (q + 1)) : hi >> (8u * (q + 1 - 4u)))) & 0xFFu);
-                const u32 pr = (byte << 8) | b2;
-                code = (u32)s_before[pr >> 5] + __popc(s_pair[pr >> 5] & ((1u << (pr & 31u)) - 1u));
-                if (i0 + q >= n + 16u) code = 0; // (a position nobody reads; its bytes are no pair of the map)
-            } else {
-                code = s_code[byte];
-            }
-            if (q < 4) va = (va << bits) | (u64)code;
-            else vb = (vb << bits) | (u64)code;
-        }
-        for (u32 k = 0; k < bits; ++k) {
-            // byte k of (va << 4 * bits | vb), an 8 * bits bit number: its bits [sh, sh + 8), sh = 8 * (bits - 1 - k)
-            const u32 sh = 8u * (bits - 1u - k), half = 4u * bits;
-            u32 o = sh >= half ? (u32)(va >> (sh - half)) : ((u32)(vb >> sh) | (u32)(va << (half - sh)));
-            s_bytes[g * bits + k] = (u8)o;
-        }
+        __syncthreads();
+        u32 *dst = reinterpret_cast<u32 *>(ptext + (size_t)lb * kPtSlot + (size_t)tile * 1024u * bits);
+        for (u32 i = threadIdx.x; i < 256u * bits; i += kSortThreads) dst[i] = s_out[i];
+        __syncthreads(); // (the next tile of the span stages its bytes in s_out again)
     }
-    __syncthreads();
-    u32 *dst = reinterpret_cast<u32 *>(ptext + (size_t)lb * kPtSlot + (size_t)tile * 1024u * bits);
-    for (u32 i = threadIdx.x; i < 256u * bits; i += kSortThreads) dst[i] = s_out[i];
+    if (count) { // (behind a barrier in every case: the loop ends with one, and a span has at least one tile)
+        u32 *out = a.gh_tiles + ((size_t)lb * kTilesPerBlock + span) * 3 * kMaxBins;
+        for (u32 i = threadIdx.x; i < 1024u; i += kSortThreads) out[i] = s_hist[0][i] + s_hist[1][i];
+    }
 }
 
 // ---- host side ------------------------------------------------------------------------------------
@@ -3399,10 +3552,11 @@ static void fused_pass(hipStream_t st, const BwtArgs &a, u32 shift, u32 h, const
                        const u32 *gate = nullptr)
 {
     const dim3 grid(a.tiles, xcd_grid_y(a.nb));
-    const u64 rd = (SRC == SRC_TEXTK || SRC == SRC_PACKED) ? 4 : ((SRC == SRC_TEXT) ? 1 : ((SRC == SRC_WALK) ? 5 : (SRC == SRC_MMC ? 9 : 8)));
+    const u64 rd = (SRC == SRC_TEXTK || SRC == SRC_PACKED) ? 4 : ((SRC == SRC_TEXT) ? 1 : ((SRC == SRC_WALK || SRC == SRC_WALKA) ? 5 : (SRC == SRC_MMC ? 9 : 8)));
+    const u64 wr_bits = (SRC == SRC_WALKA) ? elems / 8u : 0u; // (the boundary bitmap: a bit per element)
     const u32 e = next_epoch(st, a);
     if (out_elems == ~0ull) out_elems = elems;
-    const int p = prof ? prof->begin(st, KID_RADIX_SCATTER_LB, elems * rd + out_elems * ((WRITE_K && !PACK_OUT) ? 8 : 4)) : -1;
+    const int p = prof ? prof->begin(st, KID_RADIX_SCATTER_LB, elems * rd + out_elems * ((WRITE_K && !PACK_OUT) ? 8 : 4) + wr_bits) : -1;
     hipLaunchKernelGGL((k_radix_scatter_lb<SRC, BITS, WRITE_K, PACK_OUT>), grid, dim3(kSortTile / 16), 0, st, a, shift, h, Kin, Vin, Kout, Vout, dpos, e, gate);
     if (prof) prof->end(st, p);
 }
@@ -3431,17 +3585,24 @@ static bool fused_pass_ok(hipStream_t st, const BwtArgs &a, u32 epoch)
 
 // false: the first pass did not behave (workgroups not dealt evenly to the XCDs, or a look-back gave
 // up); nothing of it is used then and the caller sorts with the three-kernel passes
+// abits: the first refinement is k_group_refine<true, true>.  Phase B then takes the forms of phase A -- its WALK pass
+// writes the key boundaries of phase A's order as a bitmap (a.abits), the middle pass leaves one word per element, the
+// last one the order alone -- and nothing stores key(j) for the refinement (BZ_INIT_ABITS=0: the keys go to KB as before).
 template <int B0, int B1, int B2>
-static bool init_sort_fused(hipStream_t st, const BwtArgs &a, u64 total_n, KernelProf *prof)
+static bool init_sort_fused(hipStream_t st, const BwtArgs &a, u64 total_n, KernelProf *prof, bool abits)
 {
     const dim3 grid(a.tiles, xcd_grid_y(a.nb));
     // the digit counts of key(j), once: both init phases sort the same multiset of keys
     // (the keys are not kept: with the packed text a key costs one load, less than a stored key's write and read)
-    int p = prof ? prof->begin(st, KID_GHIST_TEXT, total_n * 1) : -1;
+    // (bytes: a counts_from_pack block is not read by k_ghist_text and has one set of counts, not three, for the scan --
+    // pack_blocks of the batch's nb blocks, taken as that share of its positions)
+    const u32 from_pack = (B0 == 10 && B1 == 10 && B2 == 10) ? a.pack_blocks : 0u;
+    int p = prof ? prof->begin(st, KID_GHIST_TEXT, total_n * (a.nb - from_pack) / a.nb) : -1;
     hipLaunchKernelGGL((k_ghist_text<B0, B1, B2>), dim3((a.tiles + kGhSpan - 1u) / kGhSpan, xcd_grid_y(a.nb)), dim3(kSortThreads), 0, st, a, (u32 *)nullptr);
     if (prof) prof->end(st, p);
-    p = prof ? prof->begin(st, KID_GHIST_SCAN, (u64)a.nb * kTilesPerBlock * 3 * 1024 * 4 / kGhSpan) : -1;
-    hipLaunchKernelGGL(k_ghist_scan, dim3(a.nb), dim3(kSortThreads), 0, st, a, 3u, 1u << B0, 1u << B1, 1u << B2, 0u, kGhSpan);
+    p = prof ? prof->begin(st, KID_GHIST_SCAN, ((u64)(a.nb - from_pack) * 3 + from_pack) * kTilesPerBlock * 1024 * 4 / kGhSpan) : -1;
+    hipLaunchKernelGGL(k_ghist_scan, dim3(a.nb), dim3(kSortThreads), 0, st, a, 3u, 1u << B0, 1u << B1, 1u << B2, 0u, kGhSpan,
+                       (B0 == 10 && B1 == 10 && B2 == 10) ? 1u : 0u);
     if (prof) prof->end(st, p);
     // phase A: order by key(j); phase B: walk it, order by key(j - c) -> 2c symbols
     // (tests) BZ_TEST_STALE_TICKETS=1: the ticket counters of the first pass already stand at a full launch's count (a
@@ -3460,6 +3621,12 @@ static bool init_sort_fused(hipStream_t st, const BwtArgs &a, u64 total_n, Kerne
     fused_pass<SRC_PAIRS, B1, true, true>(st, a, B0, 0, a.KA, a.VA, nullptr, a.VB, 1, total_n, prof);
     (void)hipMemsetAsync(a.pb_gate, 1, a.nb * sizeof(u32), st); // every block: keys in KB, order by the passes
     fused_pass<SRC_PACKED, B2, false>(st, a, 20, 0, nullptr, a.VB, nullptr, a.VA, 2, total_n, prof); // (order only)
+    if (abits) {
+        fused_pass<SRC_WALKA, B0>(st, a, 0, 0, nullptr, a.VA, a.KB, a.VB, 0, total_n, prof);
+        fused_pass<SRC_PAIRS, B1, true, true>(st, a, B0, 0, a.KB, a.VB, nullptr, a.VA, 1, total_n, prof);
+        fused_pass<SRC_PACKED, B2, false>(st, a, 20, 0, nullptr, a.VA, nullptr, a.SA, 2, total_n, prof); // (the order goes straight into SA)
+        return true;
+    }
     const u32 *gate = nullptr;
     fused_pass<SRC_WALK, B0>(st, a, 0, 0, a.KA, a.VA, a.KB, a.VB, 0, total_n, prof, ~0ull, gate);
     fused_pass<SRC_PAIRS, B1>(st, a, B0, 0, a.KB, a.VB, a.KA, a.VA, 1, total_n, prof, ~0ull, gate);
@@ -3470,12 +3637,11 @@ static bool init_sort_fused(hipStream_t st, const BwtArgs &a, u64 total_n, Kerne
 
 void launch_block_symbols(hipStream_t st, const BwtArgs &a, u32 *inuse_bits, u8 *sym_code, u8 *keyinfo)
 {
-    const dim3 grid(kTilesPerBlock, xcd_grid_y(a.nb));
     (void)hipMemsetAsync(inuse_bits, 0, (size_t)a.nb * 8 * sizeof(u32), st);
     if (a.pair_bits) (void)hipMemsetAsync(a.pair_bits, 0, (size_t)a.nb * kPairWords * sizeof(u32), st);
     hipLaunchKernelGGL(k_block_symbols, dim3((a.tiles + kSymSpan - 1u) / kSymSpan, xcd_grid_y(a.nb)), dim3(kSortThreads), 0, st, a, inuse_bits, a.pair_bits);
     hipLaunchKernelGGL(k_key_params, dim3(a.nb), dim3(256), 0, st, inuse_bits, a.pair_bits, sym_code, keyinfo);
-    hipLaunchKernelGGL(k_pack_text, grid, dim3(kSortThreads), 0, st, a, a.ptext);
+    hipLaunchKernelGGL(k_pack_text, dim3((kTilesPerBlock + kGhSpan - 1u) / kGhSpan, xcd_grid_y(a.nb)), dim3(kSortThreads), 0, st, a, a.ptext);
 }
 
 template <int B0, int B1, int B2>
@@ -3522,10 +3688,16 @@ static int run_bwt_once(hipStream_t st, const BwtArgs &a_in, u32 max_n, u64 tota
     // first pass is checked, and the three-kernel passes redo the sort from the block if it fails.
     bool fused = a.fused != 0;
     const u32 epoch_first = *a.epoch + 1u; // (fused) the passes of this call, for the coverage check below
+    // flags + apply in one pass (k_group_refine) whenever the fused radix passes are in use; BZ_FUSED_REFINE=0 keeps
+    // the two kernels (A/B measurements, tests).  With it the init hands the refinement the key boundaries as a bitmap
+    // instead of the keys (init_sort_fused); BZ_INIT_ABITS=0 keeps the keys (A/B measurements, one test).
+    static const bool want_refine = !(getenv("BZ_FUSED_REFINE") && atoi(getenv("BZ_FUSED_REFINE")) == 0);
+    static const bool want_abits = !(getenv("BZ_INIT_ABITS") && atoi(getenv("BZ_INIT_ABITS")) == 0);
+    const bool abits = fused && want_refine && want_abits && a.abits != nullptr;
     if (fused) {
         // (phase B of the init inside LDS was built in round 2 and took 37 ms per GiB of text against 15 ms for the three
         // global passes it replaces: profiles/r02_phase_b_in_lds.md; its machinery lives on in k_surv_local)
-        const bool ok = wide_keys ? init_sort_fused<11, 11, 10>(st, a, total_n, prof) : init_sort_fused<10, 10, 10>(st, a, total_n, prof);
+        const bool ok = wide_keys ? init_sort_fused<11, 11, 10>(st, a, total_n, prof, abits) : init_sort_fused<10, 10, 10>(st, a, total_n, prof, abits);
         if (!ok) {
             fprintf(stderr, "bz2_mi355x: fused radix passes disabled (tile tickets / look-back check failed)\n");
             a.fused_state[0] = 1;
@@ -3540,16 +3712,15 @@ static int run_bwt_once(hipStream_t st, const BwtArgs &a_in, u32 max_n, u64 tota
         if (wide_keys) init_sort<11, 11, 10>(st, a, total_n, prof);
         else init_sort<10, 10, 10>(st, a, total_n, prof);
     }
-    // flags + apply in one pass (k_group_refine) whenever the fused radix passes are in use; BZ_FUSED_REFINE=0 keeps
-    // the two kernels (A/B measurements, tests)
-    static const bool want_refine = !(getenv("BZ_FUSED_REFINE") && atoi(getenv("BZ_FUSED_REFINE")) == 0);
-    const bool refine = fused && want_refine;
+    const bool refine = fused && want_refine; // (fused is false by now if the init's first pass did not behave: then abits was not used either)
     int p;
     (void)hipMemsetAsync(a.bin_cursor, 0, (size_t)a.nb * 1024 * sizeof(u32), st);
     if (refine) {
         const u32 e = next_epoch(st, a);
-        p = prof ? prof->begin(st, KID_GROUP_REFINE, total_n * 14) : -1; // K 4, V 4, flag byte 1, rank word 4, last column 1
-        hipLaunchKernelGGL((k_group_refine<true>), grid, dim3(kSortThreads), 0, st, a, 0u, 0u, 0u, a.KB, a.SA, a.KA, e);
+        // K 4 (abits: a bit instead), V 4, flag byte 1, rank word 4, last column 1
+        p = prof ? prof->begin(st, KID_GROUP_REFINE, abits ? total_n * 10 + total_n / 8 : total_n * 14) : -1;
+        if (abits) hipLaunchKernelGGL((k_group_refine<true, true>), grid, dim3(kSortThreads), 0, st, a, 0u, 0u, 0u, (const u32 *)nullptr, a.SA, a.KA, e);
+        else hipLaunchKernelGGL((k_group_refine<true>), grid, dim3(kSortThreads), 0, st, a, 0u, 0u, 0u, a.KB, a.SA, a.KA, e);
         if (prof) prof->end(st, p);
     } else {
         p = prof ? prof->begin(st, KID_GROUP_FLAGS, total_n * 9) : -1;
