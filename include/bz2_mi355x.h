@@ -696,7 +696,8 @@ void df_enc_destroy(df_enc *e);
  * where the piece in front of them ended (DESIGN_deflate.md, "One large stream
  * across many waves").  A split entry gets the bytes, the length and the verdict
  * of the one-wave path under every clause of the contract below.  `kind` as in
- * section 4 (one kind per call, no preset dictionary).
+ * section 4 (one kind per call; the _dict forms take one preset dictionary for
+ * every entry of the call: clause (c)).
  *
  * THE CONTRACT (DESIGN_deflate.md, "Decoding many streams in one call", says why
  * the reference's decoder cannot be the standard on malformed input):
@@ -722,6 +723,36 @@ void df_enc_destroy(df_enc *e);
  *     A failure that only the zero bits behind the entry's end made possible is
  *     BZ_E_EOF, never BZ_E_DATA.  A stored block that the entry's end cuts short
  *     yields none of its bytes.
+ * (c) WITH A PRESET DICTIONARY (the _dict forms; `Deflater::with_dict`,
+ *     `ZlibDecoder::with_dict`, src/deflate/decoder.rs:358-404,
+ *     src/zlib/decoder.rs:32-39, 66-101) every clause above holds, and:
+ *     dict_len == 0 is exactly the call without one, whatever `dict` is: FDICT
+ *     stays BZ_E_DATA.  (As the encoder, where an empty dictionary writes 78 DA;
+ *     a deliberate difference from the reference's with_dict(b""), which wants
+ *     FDICT and the DICTID 1.)  dict == NULL with dict_len > 0, and kind 2 with
+ *     dict_len > 0 (GZipDecoder has no with_dict), are BZ_E_PARAM; the host forms
+ *     return them before any device is touched.  `dict` is HOST memory; one
+ *     dictionary serves every entry; its last W = min(dict_len, 32768) bytes are
+ *     uploaded once per call, and they are history in front of position 0 of every
+ *     entry's output.
+ *     kind 0: a distance d at output position p is valid iff d <= p + W; d > p + W
+ *     is BZ_E_DATA with the bytes in front of the failing code.  Source byte
+ *     q = p - d + i (p - d + i % d for d < length) with q < 0 is window byte
+ *     W + q.  A wrong dictionary of the same length cannot be detected: BZ_OK with
+ *     the bytes that dictionary gives.  zlib's decompressobj(-15, zdict=dict) is
+ *     the arbiter.
+ *     kind 1: the header is the reference's.  CMF and FLG: fewer than 2 bytes is
+ *     BZ_E_EOF.  FDICT clear is BZ_E_DATA with no bytes (the reference refuses it;
+ *     zlib would ignore the dictionary).  FDICT set: the header is six bytes, and
+ *     fewer than six in the entry is BZ_E_EOF with no bytes even when CM, CINFO or
+ *     FCHECK are wrong already; with all six present CM != 8, CINFO > 7, FCHECK,
+ *     or a DICTID (big endian) that is not the Adler-32 of the WHOLE dictionary is
+ *     BZ_E_DATA with no bytes.  Behind the header the body is decoded as kind 0
+ *     with the window; the trailer's Adler-32 covers the output bytes only.
+ *     The bits and "compressed bytes consumed" of an entry include the six header
+ *     bytes.  No byte of the dictionary is ever written to d_out; placement, cap,
+ *     the sizes-only call, the isolation of the entries' verdicts and "nothing
+ *     outside the reported ranges is written" hold as they are.
  * ======================================================================== */
 
 /* Entry i is the h_in_len[i] bytes at d_in + h_in_off[i]: d_in 16-byte aligned, every offset a multiple of 4, the ranges
@@ -747,6 +778,12 @@ int df_gpu_decode_batch_device(bz_gpu_engine *g, int kind, const void *d_in,
                                const uint64_t *h_in_off, const uint64_t *h_in_len, size_t count,
                                void *d_out, size_t cap,
                                uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_verdict);
+/* ... with a preset dictionary (clause (c)); df_gpu_decode_batch_device is this call with (NULL, 0). */
+int df_gpu_decode_batch_device_dict(bz_gpu_engine *g, int kind, const void *d_in,
+                                    const uint64_t *h_in_off, const uint64_t *h_in_len, size_t count,
+                                    const uint8_t *dict, size_t dict_len,
+                                    void *d_out, size_t cap,
+                                    uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_verdict);
 /* The last df_gpu_decode_batch_device call: [0] entries decoded clean [1] entries with an error verdict, and of the
  * blocks decoded whole [2] stored [3] fixed [4] dynamic; [5] decoded bytes [6] compressed bytes consumed (to the end of
  * the stream or trailer, or to the failing code) [7] kernel launches. */
@@ -770,6 +807,13 @@ int df_decode_batch(int kind, int device, const uint8_t *const *ins, const size_
  * or the first Err under the contract above: returns BZ_OK with the bytes, or the verdict with the bytes in front of it
  * (as bz_decode_buffer does). */
 int df_decode_buffer(int kind, int device, const uint8_t *in, size_t in_len, uint8_t **out, size_t *out_len);
+/* The two host forms with a preset dictionary (clause (c)) == `Deflater::with_dict(dict)` / `ZlibDecoder::with_dict(dict)`;
+ * df_decode_batch and df_decode_buffer are these calls with (NULL, 0). */
+int df_decode_batch_dict(int kind, int device, const uint8_t *const *ins, const size_t *lens, size_t count,
+                         const uint8_t *dict, size_t dict_len,
+                         uint8_t **out, uint64_t *out_off, uint64_t *out_len, int32_t *verdict);
+int df_decode_buffer_dict(int kind, int device, const uint8_t *in, size_t in_len,
+                          const uint8_t *dict, size_t dict_len, uint8_t **out, size_t *out_len);
 
 /* ========================================================================
  * 6. EVERY MEMBER of a gzip file (RFC 1952 section 2.2: a file is a series of

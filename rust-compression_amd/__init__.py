@@ -98,6 +98,7 @@ EXPORTS = [
     "df_enc_create", "df_enc_write", "df_enc_end", "df_enc_read", "df_enc_pending", "df_enc_destroy", "df_enc_finished",
     "df_encode_batch_bound", "df_gpu_encode_batch_device", "df_gpu_last_batch_stats", "df_encode_batch",
     "df_gpu_decode_batch_device", "df_gpu_last_decode_batch_stats", "df_gpu_last_decode_split_stats", "df_gpu_last_decode_split_timings", "df_decode_batch", "df_decode_buffer",
+    "df_gpu_decode_batch_device_dict", "df_decode_batch_dict", "df_decode_buffer_dict",
     "df_gpu_decode_members_device", "df_gpu_last_decode_members_stats", "df_gpu_last_decode_members_timings", "df_decode_members_buffer",
 ]
 
@@ -261,6 +262,9 @@ def lib():
     L.df_gpu_last_decode_members_timings.argtypes = [vp, C.POINTER(C.c_double)]
     L.df_decode_members_buffer.argtypes = [C.c_int, C.c_char_p, sz, C.POINTER(u8p), szp]
     L.df_decode_buffer.argtypes = [C.c_int, C.c_int, C.c_char_p, sz, C.POINTER(u8p), szp]
+    L.df_gpu_decode_batch_device_dict.argtypes = [vp, C.c_int, vp, u64p, u64p, sz, C.c_char_p, sz, vp, sz, u64p, u64p, i32p]
+    L.df_decode_batch_dict.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, sz, C.c_char_p, sz, C.POINTER(u8p), u64p, u64p, i32p]
+    L.df_decode_buffer_dict.argtypes = [C.c_int, C.c_int, C.c_char_p, sz, C.c_char_p, sz, C.POINTER(u8p), szp]
     _LIB = L
     return L
 
@@ -500,10 +504,10 @@ def release_cached_resources():
     lib().bz_release_cached_resources()
 
 
-def _batch_call(fn, head_args, datas, verdicts):
-    """One host-to-host batch entry point (bz_encode_batch and its three siblings): the ctypes arrays, the call, the
+def _batch_call(fn, head_args, datas, verdicts, mid_args=()):
+    """One host-to-host batch entry point (bz_encode_batch and its siblings): the ctypes arrays, the call, the
     result cut into its entries, the buffer freed.  verdicts: the call also fills one verdict per entry, and an entry of
-    the result is (bytes, verdict)."""
+    the result is (bytes, verdict).  mid_args: what the call takes between the inputs and the outputs (a dictionary)."""
     datas = [d if isinstance(d, bytes) else bytes(d) for d in datas]
     k = len(datas)
     ins = (C.c_char_p * max(k, 1))(*datas)
@@ -512,7 +516,7 @@ def _batch_call(fn, head_args, datas, verdicts):
     ln = (C.c_uint64 * max(k, 1))()
     v = (C.c_int32 * max(k, 1))()
     out = C.POINTER(C.c_uint8)()
-    _check(fn(*head_args, ins, lens, k, C.byref(out), off, ln, *((v,) if verdicts else ())))
+    _check(fn(*head_args, ins, lens, k, *mid_args, C.byref(out), off, ln, *((v,) if verdicts else ())))
     try:
         base = C.addressof(out.contents) if k else 0
         parts = [C.string_at(base + off[i], ln[i]) for i in range(k)]
@@ -521,13 +525,13 @@ def _batch_call(fn, head_args, datas, verdicts):
         lib().bz_free(out)
 
 
-def _decode_call(fn, head_args, data, data_verdicts):
+def _decode_call(fn, head_args, data, data_verdicts, mid_args=()):
     """One host-to-host one-shot decode (bz_decode_buffer, df_decode_buffer) -> (bytes yielded, verdict code); a status
-    that is not one of the decoder's verdicts is raised."""
+    that is not one of the decoder's verdicts is raised.  mid_args as in _batch_call."""
     data = bytes(data)
     out = C.POINTER(C.c_uint8)()
     n = C.c_size_t(0)
-    rc = fn(*head_args, data, len(data), C.byref(out), C.byref(n))
+    rc = fn(*head_args, data, len(data), *mid_args, C.byref(out), C.byref(n))
     if rc != BZ_OK and rc not in data_verdicts:
         raise CompressionError(rc)
     try:
@@ -816,38 +820,54 @@ def decompress_batch(datas, device=0):
 _DF_VERDICTS = (BZ_E_DATA, BZ_E_EOF)
 
 
-def deflate_decompress(data, kind=DEFLATE, device=0):
-    """One-shot over host buffers (df_decode_buffer) -> (bytes yielded, verdict code): BZ_OK, BZ_E_DATA or BZ_E_EOF under
-    the contract of section 5 of the header (RFC 1951 / 1950 / 1952; zlib's inflate is the arbiter)."""
+def _decode_dict(kind, dict_):
+    """The dictionary of a decode call as the C ABI takes it; an empty one is no dictionary (clause (c) of section 5)."""
     if kind not in (DEFLATE, ZLIB, GZIP):
         raise ValueError("invalid kind")
-    return _decode_call(lib().df_decode_buffer, (kind, device), data, _DF_VERDICTS)
+    dict_ = bytes(dict_)
+    if dict_ and kind == GZIP:
+        raise ValueError("gzip decoding takes no preset dictionary (GZipDecoder has no with_dict)")
+    return dict_
 
 
-def deflate_decompress_batch(datas, kind=DEFLATE, device=0):
-    """Many independent streams in one call (df_decode_batch) -> list of (bytes yielded, verdict code): element i is
-    deflate_decompress(datas[i], kind).  An entry's verdict is its own; CompressionError is raised for infrastructure
-    errors only."""
-    if kind not in (DEFLATE, ZLIB, GZIP):
-        raise ValueError("invalid kind")
-    return _batch_call(lib().df_decode_batch, (kind, device), datas, True)
+def deflate_decompress(data, kind=DEFLATE, device=0, dict_=b""):
+    """One-shot over host buffers (df_decode_buffer_dict) -> (bytes yielded, verdict code): BZ_OK, BZ_E_DATA or BZ_E_EOF
+    under the contract of section 5 of the header (RFC 1951 / 1950 / 1952; zlib's inflate is the arbiter).  dict_: the
+    preset dictionary of `Deflater::with_dict` / `ZlibDecoder::with_dict` (kinds DEFLATE and ZLIB)."""
+    dict_ = _decode_dict(kind, dict_)
+    return _decode_call(lib().df_decode_buffer_dict, (kind, device), data, _DF_VERDICTS, (dict_, len(dict_)))
+
+
+def deflate_decompress_batch(datas, kind=DEFLATE, device=0, dict_=b""):
+    """Many independent streams in one call (df_decode_batch_dict) -> list of (bytes yielded, verdict code): element i is
+    deflate_decompress(datas[i], kind, dict_=dict_) -- one dictionary serves every entry.  An entry's verdict is its own;
+    CompressionError is raised for infrastructure errors only."""
+    dict_ = _decode_dict(kind, dict_)
+    return _batch_call(lib().df_decode_batch_dict, (kind, device), datas, True, (dict_, len(dict_)))
 
 
 class Deflater:
     """`Deflater` (src/deflate/decoder.rs) with the `next(it)` / `decode_all(data)` surface of BZip2Decoder, over
     df_decode_buffer: the first `next` collects the input iterator and decodes it in one call; the bytes are handed out,
     then CompressionError (kind DataError / UnexpectedEof, `.partial` = the bytes in front of it) is raised once.
+    dict_: `Deflater::with_dict` (deflate/decoder.rs:358-404); an empty one is no dictionary.
     Creating one does not touch the device."""
     KIND = DEFLATE
 
-    def __init__(self, device=0):
+    def __init__(self, device=0, dict_=b""):
         self._device = device
+        self._dict = _decode_dict(self.KIND, dict_)
         self._ready = None
         self._pos = 0
         self._verdict = BZ_OK
 
+    @classmethod
+    def with_dict(cls, dict_, device=0):
+        """`Deflater::with_dict(dict)` / `ZlibDecoder::with_dict(dict)`."""
+        return cls(device, dict_)
+
     def _decode(self, data):
-        return deflate_decompress(data, self.KIND, self._device)
+        return deflate_decompress(data, self.KIND, self._device, self._dict)
 
     def _error(self):
         e = CompressionError(self._verdict)
@@ -877,12 +897,12 @@ class Deflater:
 
 
 class ZlibDecoder(Deflater):
-    """`ZlibDecoder` (src/zlib/decoder.rs), without a preset dictionary."""
+    """`ZlibDecoder` (src/zlib/decoder.rs); with a dictionary the header must carry FDICT and its Adler-32."""
     KIND = ZLIB
 
 
 class GZipDecoder(Deflater):
-    """`GZipDecoder` (src/gzip/decoder.rs): the first member."""
+    """`GZipDecoder` (src/gzip/decoder.rs): the first member.  It has no with_dict: a non-empty dictionary is a ValueError."""
     KIND = GZIP
 
 
@@ -1134,10 +1154,12 @@ class GpuEngine:
 
     DEFLATE_DECODE_BATCH_STATS = ("clean", "errors", "stored", "fixed", "dynamic", "decoded_bytes", "consumed_bytes", "launches")
 
-    def deflate_decode_batch_device(self, kind, d_in, in_off, in_len, d_out, cap):
-        """Many streams in one call (df_gpu_decode_batch_device): entry i is the in_len[i] bytes at d_in + in_off[i] (offsets
-        multiples of 4, ascending -- what deflate_encode_batch_device returns); returns (out_off, out_len, verdicts), entry i's
-        bytes at d_out + out_off[i].  d_out = None: sizes only."""
+    def deflate_decode_batch_device(self, kind, d_in, in_off, in_len, d_out, cap, dict_=b""):
+        """Many streams in one call (df_gpu_decode_batch_device_dict): entry i is the in_len[i] bytes at d_in + in_off[i]
+        (offsets multiples of 4, ascending -- what deflate_encode_batch_device returns); returns (out_off, out_len, verdicts),
+        entry i's bytes at d_out + out_off[i].  d_out = None: sizes only.  dict_ (host bytes): one preset dictionary for every
+        entry, kinds DEFLATE and ZLIB (a kind outside 0..2 is the C call's BZ_E_PARAM, as ever)."""
+        dict_ = _decode_dict(kind, dict_) if kind in (DEFLATE, ZLIB, GZIP) else bytes(dict_)
         _settle()
         k = len(in_off)
         if len(in_len) != k:
@@ -1147,7 +1169,7 @@ class GpuEngine:
         o_off = (C.c_uint64 * max(k, 1))()
         o_len = (C.c_uint64 * max(k, 1))()
         verdicts = (C.c_int32 * max(k, 1))()
-        _check(lib().df_gpu_decode_batch_device(self._h, kind, d_in, a_off, a_len, k, d_out, cap, o_off, o_len, verdicts))
+        _check(lib().df_gpu_decode_batch_device_dict(self._h, kind, d_in, a_off, a_len, k, dict_, len(dict_), d_out, cap, o_off, o_len, verdicts))
         return list(o_off[:k]), list(o_len[:k]), [int(v) for v in verdicts[:k]]
 
     def deflate_decode_batch_stats(self):

@@ -29,6 +29,7 @@ struct DfWorkspace {
     DevBuf b_slots, b_tile_slot, b_bse, b_outs, b_stats; // a sub-batch of df_gpu_encode_batch_device: slot tables, block ends, streams' places
     u64 batch_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // df_gpu_last_batch_stats
     DevBuf i_in, i_ooff, i_rec;                        // df_gpu_decode_batch_device: the entries' ranges, their outputs' places, their records
+    DevBuf i_dict;                                     // ... and the window of a call with a preset dictionary (uploaded per call)
     u64 inf_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // df_gpu_last_decode_batch_stats
     DevBuf s_cand, s_piece, s_prec, s_map, s_cnt;      // an entry across many waves: candidates, pieces, their records, the source map
     u64 split_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // df_gpu_last_decode_split_stats
@@ -857,15 +858,15 @@ struct DfSplitEntry {
 };
 
 // the sizes launch over n pieces, and their records
-static int df_split_pieces(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *ebase, u32 elen, const DfPiece *pcs, u32 n, DfPieceRec *out,
-                           u64 *launches)
+static int df_split_pieces(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *ebase, u32 elen, DfWindow win, const DfPiece *pcs, u32 n,
+                           DfPieceRec *out, u64 *launches)
 {
     int rc = w->s_piece.ensure((size_t)n * sizeof(DfPiece));
     if (rc == BZ_OK) rc = w->s_prec.ensure((size_t)n * sizeof(DfPieceRec));
     if (rc != BZ_OK) return rc;
     HIPCHK(hipMemcpyAsync(w->s_piece.p, pcs, (size_t)n * sizeof(DfPiece), hipMemcpyHostToDevice, g->st));
-    if (df_launch_inflate_piece(g->st, false, ebase, elen, kind, w->s_piece.as<DfPiece>(), n, w->s_prec.as<DfPieceRec>(), nullptr, nullptr) != 0)
-        return BZ_E_UNEXPECTED;
+    DfPieceRec *d_rec = w->s_prec.as<DfPieceRec>();
+    if (df_launch_inflate_piece(g->st, false, ebase, elen, kind, w->s_piece.as<DfPiece>(), n, d_rec, nullptr, nullptr, win) != 0) return BZ_E_UNEXPECTED;
     HIPCHK(hipMemcpyAsync(out, w->s_prec.p, (size_t)n * sizeof(DfPieceRec), hipMemcpyDeviceToHost, g->st));
     HIPCHK(hipStreamSynchronize(g->st));
     *launches += 1;
@@ -873,7 +874,7 @@ static int df_split_pieces(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 
 }
 
 // Search, sizes, chain and repair of one entry.  *fallback: the entry takes the one-wave path (an output of 2 GiB or more).
-static int df_split_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *ebase, u32 elen, DfSplitEntry &e, bool *fallback)
+static int df_split_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *ebase, u32 elen, DfWindow win, DfSplitEntry &e, bool *fallback)
 {
     using namespace infsplit;
     *fallback = false;
@@ -908,7 +909,7 @@ static int df_split_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *
         q.len = q.pad = 0;
     }
     std::vector<DfPieceRec> prs(pcs.size());
-    if ((rc = df_split_pieces(g, w, kind, ebase, elen, pcs.data(), (u32)pcs.size(), prs.data(), &e.st[7])) != BZ_OK) return rc;
+    if ((rc = df_split_pieces(g, w, kind, ebase, elen, win, pcs.data(), (u32)pcs.size(), prs.data(), &e.st[7])) != BZ_OK) return rc;
     t0 = df_now_ms();
     e.ms[1] += t0 - t1;
     // the chain: a candidate's piece counts if and only if the confirmed piece in front of it ended exactly there
@@ -933,21 +934,21 @@ static int df_split_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *
             continue;
         }
         cur = DfPiece{end.pos, stop, end.mode, kBaseUnknown, 0, 0};
-        if ((rc = df_split_pieces(g, w, kind, ebase, elen, &cur, 1, &cr, &e.st[7])) != BZ_OK) return rc;
+        if ((rc = df_split_pieces(g, w, kind, ebase, elen, win, &cur, 1, &cr, &e.st[7])) != BZ_OK) return rc;
         if (nx == Next::Repair) {
             ++repairs;
             e.st[3] += 1;
         } else e.st[4] += cr.r.len; // the serial tail
     }
     e.st[2] += 1; // (the first piece)
-    // the pieces' places; a piece whose matches reach further back than its place is decoded once more knowing it: the
-    // stream ends at the failing code
+    // the pieces' places; a piece whose matches reach further back than its place and the window in front of the entry is
+    // decoded once more knowing it: the stream ends at the failing code
     u64 sum = 0;
     for (size_t k = 0; k < e.chain.size(); ++k) {
         if (sum >= (1ull << 31)) break;
         e.chain[k].base = (u32)sum;
-        if (k > 0 && crec[k].reach > sum) {
-            if ((rc = df_split_pieces(g, w, kind, ebase, elen, &e.chain[k], 1, &crec[k], &e.st[7])) != BZ_OK) return rc;
+        if (k > 0 && crec[k].reach > sum + win.W) {
+            if ((rc = df_split_pieces(g, w, kind, ebase, elen, win, &e.chain[k], 1, &crec[k], &e.st[7])) != BZ_OK) return rc;
             if (!crec[k].ended || crec[k].r.verdict == BZ_OK) return BZ_E_UNEXPECTED;
             e.chain.resize(k + 1);
             crec.resize(k + 1);
@@ -973,7 +974,7 @@ static int df_split_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *
 
 // The bytes of one split entry at `eout`: the writing launch with its source map, pointer jumping, the gather; for kinds 1 / 2
 // the checksum of a clean stream, folded piecewise (k_df_sums) and combined here as df_encode_core combines it.
-static int df_split_write(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *ebase, u32 elen, u8 *eout, DfSplitEntry &e)
+static int df_split_write(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *ebase, u32 elen, DfWindow win, u8 *eout, DfSplitEntry &e)
 {
     const u32 n = e.rec.len, np = (u32)e.chain.size();
     u32 *map = w->s_map.as<u32>(), *cnt = w->s_cnt.as<u32>();
@@ -981,7 +982,8 @@ static int df_split_write(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *
     if (rc != BZ_OK) return rc;
     double t0 = df_now_ms();
     HIPCHK(hipMemcpyAsync(w->s_piece.p, e.chain.data(), (size_t)np * sizeof(DfPiece), hipMemcpyHostToDevice, g->st));
-    if (df_launch_inflate_piece(g->st, true, ebase, elen, kind, w->s_piece.as<DfPiece>(), np, nullptr, eout, map) != 0) return BZ_E_UNEXPECTED;
+    if (df_launch_inflate_piece(g->st, true, ebase, elen, kind, w->s_piece.as<DfPiece>(), np, nullptr, eout, map, win) != 0)
+        return BZ_E_UNEXPECTED;
     HIPCHK(hipStreamSynchronize(g->st));
     w->split_stats[7] += 1;
     double t1 = df_now_ms();
@@ -1063,7 +1065,7 @@ struct DfSizes {
 // a writing phase follows (the split entries' source map is sized here, before any entry is committed to the split path).
 // The entries' ranges stay in w->i_in and their records in w->i_rec for a writing phase that follows at once.
 static int df_decode_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *in8, const uint64_t *h_in_off, const uint64_t *h_in_len,
-                           size_t count, bool will_write, DfSizes &s)
+                           size_t count, DfWindow win, bool will_write, DfSizes &s)
 {
     int rc;
     // the entries that go across many waves; in the launches over all entries they are entries of no bytes
@@ -1076,7 +1078,7 @@ static int df_decode_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 
         DfSplitEntry e;
         bool fallback = false;
         e.index = i;
-        rc = df_split_sizes(g, w, kind, in8 + h_in_off[i], (u32)h_in_len[i], e, &fallback);
+        rc = df_split_sizes(g, w, kind, in8 + h_in_off[i], (u32)h_in_len[i], win, e, &fallback);
         if (rc != BZ_OK) return rc;
         if (!fallback) splits.push_back(std::move(e));
     }
@@ -1107,7 +1109,7 @@ static int df_decode_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 
     HIPCHK(hipMemcpyAsync(d_off, h_in_off, count * sizeof(u64), hipMemcpyHostToDevice, g->st));
     HIPCHK(hipMemcpyAsync(d_len, splits.empty() ? h_in_len : s.len_small.data(), count * sizeof(u64), hipMemcpyHostToDevice, g->st));
     HIPCHK(hipEventRecord(w->ev[0], g->st));
-    if (df_launch_inflate(g->st, false, in8, d_off, d_len, (u32)count, kind, nullptr, nullptr, d_rec) != 0) return BZ_E_UNEXPECTED;
+    if (df_launch_inflate(g->st, false, in8, d_off, d_len, (u32)count, kind, nullptr, nullptr, d_rec, win) != 0) return BZ_E_UNEXPECTED;
     HIPCHK(hipEventRecord(w->ev[1], g->st));
     s.rec.resize(count);
     HIPCHK(hipMemcpyAsync(s.rec.data(), d_rec, count * sizeof(DfInfRec), hipMemcpyDeviceToHost, g->st));
@@ -1120,7 +1122,7 @@ static int df_decode_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 
 // the trailers compared, s.rec[i].verdict turned to BZ_E_DATA where they differ.  upload: the sizes phase that ran last was
 // not this batch's, so the ranges and records go to the device first (a split entry's as the entry of no bytes it is there).
 static int df_decode_write(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *in8, const uint64_t *h_in_off, const uint64_t *h_in_len,
-                           size_t count, u8 *out8, const uint64_t *h_out_off, DfSizes &s, bool upload)
+                           size_t count, DfWindow win, u8 *out8, const uint64_t *h_out_off, DfSizes &s, bool upload)
 {
     int rc;
     u64 *d_off = w->i_in.as<u64>(), *d_len = d_off + count, *d_ooff = w->i_ooff.as<u64>();
@@ -1144,7 +1146,7 @@ static int df_decode_write(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 
     }
     HIPCHK(hipMemcpyAsync(d_ooff, h_out_off, count * sizeof(u64), hipMemcpyHostToDevice, g->st));
     HIPCHK(hipEventRecord(w->ev[2], g->st));
-    if (df_launch_inflate(g->st, true, in8, d_off, d_len, (u32)count, kind, out8, d_ooff, d_rec) != 0) return BZ_E_UNEXPECTED;
+    if (df_launch_inflate(g->st, true, in8, d_off, d_len, (u32)count, kind, out8, d_ooff, d_rec, win) != 0) return BZ_E_UNEXPECTED;
     HIPCHK(hipEventRecord(w->ev[3], g->st));
     if (kind != 0) {
         if (df_launch_inflate_check(g->st, out8, d_ooff, (u32)count, d_rec, kind) != 0) return BZ_E_UNEXPECTED;
@@ -1153,7 +1155,7 @@ static int df_decode_write(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 
     HIPCHK(hipEventRecord(w->ev[4], g->st));
     HIPCHK(hipStreamSynchronize(g->st));
     for (DfSplitEntry &e : s.splits) {
-        rc = df_split_write(g, w, kind, in8 + h_in_off[e.index], (u32)h_in_len[e.index], out8 + h_out_off[e.index], e);
+        rc = df_split_write(g, w, kind, in8 + h_in_off[e.index], (u32)h_in_len[e.index], win, out8 + h_out_off[e.index], e);
         if (rc != BZ_OK) return rc;
         s.rec[e.index] = e.rec;
     }
@@ -1169,11 +1171,45 @@ static void df_inf_stats_add(DfWorkspace *w, const DfInfRec &r)
     w->inf_stats[6] += (r.end_bit + 7u) >> 3;
 }
 
+// the parameter errors of a dictionary, the same in every form: a length without a pointer, and gzip (GZipDecoder has no with_dict)
+static int df_decode_dict_param(int kind, const uint8_t *dict, size_t dict_len)
+{
+    return dict_len && (!dict || kind == 2) ? BZ_E_PARAM : BZ_OK;
+}
+
+// The window of a call: the last min(dict_len, 32768) bytes of the dictionary, uploaded into the workspace (once per call, not
+// kept: 32 KiB), and the Adler-32 of the WHOLE dictionary (adler32.rs:20-66), which is what a zlib header's DICTID holds.
+static int df_decode_window(bz_gpu_engine *g, DfWorkspace *w, const uint8_t *dict, size_t dict_len, DfWindow &win)
+{
+    win = DfWindow{};
+    if (!dict_len) return BZ_OK;
+    const u32 W = (u32)std::min<size_t>(dict_len, 32768);
+    int rc = w->i_dict.ensure(32768);
+    if (rc != BZ_OK) return rc;
+    HIPCHK(hipMemcpyAsync(w->i_dict.p, dict + (dict_len - W), W, hipMemcpyHostToDevice, g->st));
+    u32 a = 1, b = 0;
+    for (size_t i = 0; i < dict_len;) { // (5552 bytes keep b below 2^32: the largest n with 255 n (n + 1) / 2 + (n + 1) 65520 < 2^32)
+        const size_t end = std::min(dict_len, i + 5552);
+        for (; i < end; ++i) {
+            a += dict[i];
+            b += a;
+        }
+        a %= 65521;
+        b %= 65521;
+    }
+    win.p = w->i_dict.as<u8>();
+    win.W = W;
+    win.adler = (b << 16) | a;
+    return BZ_OK;
+}
+
 // grow != nullptr: the output is the engine's own buffer, sized between the two launches (the host forms)
 static int df_decode_batch_core(bz_gpu_engine *g, int kind, const void *d_in, const uint64_t *h_in_off, const uint64_t *h_in_len, size_t count,
-                                void *d_out, size_t cap, DevBuf *grow, uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_verdict)
+                                const uint8_t *dict, size_t dict_len, void *d_out, size_t cap, DevBuf *grow, uint64_t *h_out_off,
+                                uint64_t *h_out_len, int32_t *h_verdict)
 {
     if (!g || kind < 0 || kind > 2) return BZ_E_PARAM;
+    if (df_decode_dict_param(kind, dict, dict_len) != BZ_OK) return BZ_E_PARAM;
     if (count == 0) return BZ_OK;
     if (!h_in_off || !h_in_len || !h_out_off || !h_out_len || !h_verdict || count > 0x7FFFFFFFu) return BZ_E_PARAM;
     if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u)) return BZ_E_PARAM;
@@ -1190,8 +1226,11 @@ static int df_decode_batch_core(bz_gpu_engine *g, int kind, const void *d_in, co
     for (u64 &s : w->split_stats) s = 0;
     for (double &t : w->split_ms) t = 0;
     const u8 *in8 = static_cast<const u8 *>(d_in);
+    DfWindow win;
+    rc = df_decode_window(g, w, dict, dict_len, win);
+    if (rc != BZ_OK) return rc;
     DfSizes sz;
-    rc = df_decode_sizes(g, w, kind, in8, h_in_off, h_in_len, count, d_out != nullptr || grow != nullptr, sz);
+    rc = df_decode_sizes(g, w, kind, in8, h_in_off, h_in_len, count, win, d_out != nullptr || grow != nullptr, sz);
     if (rc != BZ_OK) return rc;
     const std::vector<DfInfRec> &rec = sz.rec;
     // the outputs' places: input order, each at a multiple of 16
@@ -1212,7 +1251,7 @@ static int df_decode_batch_core(bz_gpu_engine *g, int kind, const void *d_in, co
     } else if (d_out && need > cap) return BZ_E_CAPACITY;
     float ms[3] = {0, 0, 0};
     if (out8) {
-        rc = df_decode_write(g, w, kind, in8, h_in_off, h_in_len, count, out8, h_out_off, sz, false);
+        rc = df_decode_write(g, w, kind, in8, h_in_off, h_in_len, count, win, out8, h_out_off, sz, false);
         if (rc != BZ_OK) return rc;
         for (size_t i = 0; i < count; ++i) h_verdict[i] = rec[i].verdict;
         (void)hipEventElapsedTime(&ms[1], w->ev[2], w->ev[3]);
@@ -1240,7 +1279,14 @@ static int df_decode_batch_core(bz_gpu_engine *g, int kind, const void *d_in, co
 extern "C" int df_gpu_decode_batch_device(bz_gpu_engine *g, int kind, const void *d_in, const uint64_t *h_in_off, const uint64_t *h_in_len,
                                           size_t count, void *d_out, size_t cap, uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_verdict)
 {
-    return df_decode_batch_core(g, kind, d_in, h_in_off, h_in_len, count, d_out, cap, nullptr, h_out_off, h_out_len, h_verdict);
+    return df_decode_batch_core(g, kind, d_in, h_in_off, h_in_len, count, nullptr, 0, d_out, cap, nullptr, h_out_off, h_out_len, h_verdict);
+}
+
+extern "C" int df_gpu_decode_batch_device_dict(bz_gpu_engine *g, int kind, const void *d_in, const uint64_t *h_in_off, const uint64_t *h_in_len,
+                                               size_t count, const uint8_t *dict, size_t dict_len, void *d_out, size_t cap, uint64_t *h_out_off,
+                                               uint64_t *h_out_len, int32_t *h_verdict)
+{
+    return df_decode_batch_core(g, kind, d_in, h_in_off, h_in_len, count, dict, dict_len, d_out, cap, nullptr, h_out_off, h_out_len, h_verdict);
 }
 
 // Many streams: packed at 4-byte-aligned offsets (BatchLayout), one upload, one device call (the engine's output buffer
@@ -1248,9 +1294,16 @@ extern "C" int df_gpu_decode_batch_device(bz_gpu_engine *g, int kind, const void
 extern "C" int df_decode_batch(int kind, int device, const uint8_t *const *ins, const size_t *lens, size_t count, uint8_t **out,
                                uint64_t *out_off, uint64_t *out_len, int32_t *verdict)
 {
+    return df_decode_batch_dict(kind, device, ins, lens, count, nullptr, 0, out, out_off, out_len, verdict);
+}
+
+extern "C" int df_decode_batch_dict(int kind, int device, const uint8_t *const *ins, const size_t *lens, size_t count, const uint8_t *dict,
+                                    size_t dict_len, uint8_t **out, uint64_t *out_off, uint64_t *out_len, int32_t *verdict)
+{
     if (!out) return BZ_E_PARAM;
     *out = nullptr;
     if (kind < 0 || kind > 2) return BZ_E_PARAM;
+    if (df_decode_dict_param(kind, dict, dict_len) != BZ_OK) return BZ_E_PARAM;
     if (count && (!ins || !lens || !out_off || !out_len || !verdict)) return BZ_E_PARAM;
     const BatchLayout lay(ins, lens, count, 4);
     if (lay.status != BZ_OK) return lay.status;
@@ -1268,8 +1321,8 @@ extern "C" int df_decode_batch(int kind, int device, const uint8_t *const *ins, 
     if (rc == BZ_OK && lay.total && hipMemcpy(g->dec_in.p, packed.data(), (size_t)lay.total, hipMemcpyHostToDevice) != hipSuccess)
         rc = BZ_E_UNEXPECTED;
     if (rc == BZ_OK)
-        rc = df_decode_batch_core(g, kind, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), count, nullptr, 0, &g->oneshot_out, out_off, out_len,
-                                  verdict);
+        rc = df_decode_batch_core(g, kind, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), count, dict, dict_len, nullptr, 0, &g->oneshot_out,
+                                  out_off, out_len, verdict);
     if (rc == BZ_OK) rc = df_download(out, g->oneshot_out.p, (size_t)(out_off[count - 1] + out_len[count - 1]));
     lease.settle(rc); // (the entries' verdicts are not the engine's business)
     return rc;
@@ -1278,6 +1331,12 @@ extern "C" int df_decode_batch(int kind, int device, const uint8_t *const *ins, 
 // The batch of one: BZ_OK with the bytes, or the entry's verdict with the bytes in front of it (as bz_decode_buffer).
 extern "C" int df_decode_buffer(int kind, int device, const uint8_t *in, size_t in_len, uint8_t **out, size_t *out_len)
 {
+    return df_decode_buffer_dict(kind, device, in, in_len, nullptr, 0, out, out_len);
+}
+
+extern "C" int df_decode_buffer_dict(int kind, int device, const uint8_t *in, size_t in_len, const uint8_t *dict, size_t dict_len, uint8_t **out,
+                                     size_t *out_len)
+{
     if (!out || !out_len || (in_len && !in)) return BZ_E_PARAM;
     *out = nullptr;
     *out_len = 0;
@@ -1285,7 +1344,7 @@ extern "C" int df_decode_buffer(int kind, int device, const uint8_t *in, size_t 
     int32_t verdict = BZ_OK;
     const uint8_t *ins[1] = {in};
     const size_t lens[1] = {in_len};
-    const int rc = df_decode_batch(kind, device, ins, lens, 1, out, &off, &len, &verdict);
+    const int rc = df_decode_batch_dict(kind, device, ins, lens, 1, dict, dict_len, out, &off, &len, &verdict);
     if (rc != BZ_OK) return rc;
     *out_len = (size_t)len; // (the one entry lies at offset 0)
     return verdict;
@@ -1427,7 +1486,7 @@ static int df_gz_sizes(bz_gpu_engine *g, DfWorkspace *w, const u8 *in8, const st
     std::vector<u64> ioff, ilen;
     int rc = df_gz_gather(g, w, in8, sp, ioff, ilen);
     if (rc != BZ_OK) return rc;
-    rc = df_decode_sizes(g, w, DF_KIND_GZIP, w->m_image.as<u8>(), ioff.data(), ilen.data(), sp.size(), will_write, s);
+    rc = df_decode_sizes(g, w, DF_KIND_GZIP, w->m_image.as<u8>(), ioff.data(), ilen.data(), sp.size(), DfWindow{}, will_write, s);
     if (rc != BZ_OK) return rc;
     float ms = 0;
     (void)hipEventElapsedTime(&ms, w->ev[0], w->ev[1]);
@@ -1650,9 +1709,8 @@ static int df_members_core(bz_gpu_engine *g, const void *d_in, size_t in_len, vo
             for (const DfSplitEntry &e : s.splits) s.len_small[e.index] = 0;
         }
         if ((rc = w->m_stage.ensure((size_t)cur + 64)) != BZ_OK) return rc;
-        if ((rc = df_decode_write(g, w, DF_KIND_GZIP, w->m_image.as<u8>(), ioff.data(), ilen.data(), cnt, w->m_stage.as<u8>(), ooff.data(), s, true)) !=
-            BZ_OK)
-            return rc;
+        rc = df_decode_write(g, w, DF_KIND_GZIP, w->m_image.as<u8>(), ioff.data(), ilen.data(), cnt, DfWindow{}, w->m_stage.as<u8>(), ooff.data(), s, true);
+        if (rc != BZ_OK) return rc;
         float e1 = 0, e2 = 0;
         (void)hipEventElapsedTime(&e1, w->ev[2], w->ev[3]);
         (void)hipEventElapsedTime(&e2, w->ev[3], w->ev[4]);

@@ -143,9 +143,16 @@ struct DfInfRec {
     u32 flags;    // bit 0: the output would reach 4 GiB
     u32 pad[2];
 };
+// A preset dictionary as the decoder sees it: the last W <= 32768 bytes of it on the device -- history in front of position 0 of
+// every entry's output -- and the Adler-32 of the whole dictionary (the DICTID of a zlib header).  W == 0: no dictionary.
+struct DfWindow {
+    const u8 *p = nullptr;
+    u32 W = 0;
+    u32 adler = 0;
+};
 // write = false: sizes only (out, out_off unused); write = true: the bytes of entry i go to out + out_off[i], at most rec[i].len
 int df_launch_inflate(hipStream_t st, bool write, const u8 *in, const u64 *in_off, const u64 *in_len, u32 count, int kind, u8 *out,
-                      const u64 *out_off, DfInfRec *rec);
+                      const u64 *out_off, DfInfRec *rec, DfWindow win);
 int df_launch_inflate_check(hipStream_t st, const u8 *out, const u64 *out_off, u32 count, DfInfRec *rec, int kind);
 // ---- one large entry across many waves (inf_split.h): a piece runs from a bit of the entry to the first block boundary at
 // or behind `stop`
@@ -166,7 +173,7 @@ struct DfPieceRec {
 };
 int df_launch_split_search(hipStream_t st, const u8 *ebase, u32 elen, u32 piece_bytes, u32 npieces, void *cand);
 int df_launch_inflate_piece(hipStream_t st, bool write, const u8 *ebase, u32 elen, int kind, const DfPiece *pc, u32 count, DfPieceRec *rec,
-                            u8 *eout, u32 *emap);
+                            u8 *eout, u32 *emap, DfWindow win);
 int df_launch_split_jump(hipStream_t st, u32 *src, u32 n, u32 *cnt);
 int df_launch_split_gather(hipStream_t st, u8 *out, const u32 *src, u32 n);
 // ---- every member of a gzip file (gz_members.h; k_gz_members.hip)

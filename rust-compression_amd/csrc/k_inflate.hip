@@ -3,7 +3,7 @@
 // decoder (src/deflate/decoder.rs), which swallows errors; the container header checks are the reference's
 // (src/zlib/decoder.rs:78-90, src/gzip/decoder.rs:92-108, 175-191).
 //
-// k_df_inflate<WRITE>: one 64-lane workgroup (one wave) per entry, from the entry's first bit to its last.  Everything that
+// k_df_inflate<WRITE, DICT>: one 64-lane workgroup (one wave) per entry, from the entry's first bit to its last.  Everything that
 // steers the decode -- bit buffer, positions, the symbol just decoded -- is wave-uniform; the lanes share the work that
 // has width: building the tables, staging the input, storing literals, copying matches.
 //   <false> sums the output length and writes nothing but the entry's record;
@@ -34,6 +34,14 @@
 // workgroup is one wave on one CU, its stores and loads go through that CU's one L1 in program order, and workgroup scope
 // is exactly the scope at which that L1 is coherent.  The fence is skipped when the source ends at or in front of the
 // position up to which an earlier fence has already ordered the stores (`fenced`).
+//
+// A PRESET DICTIONARY (<.., DICT = true>; clause (c) of section 5; DESIGN_deflate.md "Decoding with a preset dictionary"): the
+// last W <= 32768 bytes of it (`dictw`, global memory: read-only and shared by every wave of the launch, it lives in L2) are
+// history in front of position 0 of the entry's output.  A distance d at position p is valid iff d <= p + W; source byte
+// q = p - d + (i mod d) < 0 is dictw[W + q] -- a signed index per lane; out + (p - d) is never formed for p < d.  Nobody writes
+// the window, so a read from it needs no fence: `fenced` concerns q >= 0 only.  The zlib header then wants FDICT and, as
+// DICTID, the Adler-32 of the whole dictionary (`dict_adler`).  The DICT = false instantiations never look at the three
+// trailing parameters: they are the kernels as they were, instruction for instruction.
 #include <hip/hip_runtime.h>
 
 #include "../../include/bz2_mi355x.h"
@@ -187,9 +195,10 @@ __device__ __forceinline__ int inf_build(const u8 *lens, u32 n, u16 *tab, u32 tb
 }
 } // namespace
 
-template <bool WRITE>
+template <bool WRITE, bool DICT>
 __global__ __launch_bounds__(64) void k_df_inflate(const u8 *__restrict__ in, const u64 *__restrict__ in_off, const u64 *__restrict__ in_len,
-                                                   int kind, u8 *out_all, const u64 *__restrict__ out_off, DfInfRec *rec)
+                                                   int kind, u8 *out_all, const u64 *__restrict__ out_off, DfInfRec *rec,
+                                                   const u8 *__restrict__ dictw, u32 W, u32 dict_adler)
 {
     __shared__ u16 s_tl[1u << kLBits], s_td[1u << kDBits], s_tc[1u << kCBits];
     __shared__ u16 s_sl[288], s_sd[32], s_sc[32];
@@ -244,7 +253,14 @@ __global__ __launch_bounds__(64) void k_df_inflate(const u8 *__restrict__ in, co
         inf_fill(r, lane);
         const u32 cmf = inf_take(r, 8), flg = inf_take(r, 8);
         INF_EOF_CHECK();
-        if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 0x20u)) INF_FAIL(0);
+        if (DICT) { // zlib/decoder.rs:62-101: FDICT first, then the six bytes, then what they hold
+            if (!(flg & 0x20u)) INF_FAIL(0);
+            inf_fill(r, lane);
+            const u32 v = inf_take(r, 32);
+            INF_EOF_CHECK();
+            const u32 id = (v >> 24) | ((v >> 8) & 0xFF00u) | ((v << 8) & 0xFF0000u) | (v << 24);
+            if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || id != dict_adler) INF_FAIL(0);
+        } else if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 0x20u)) INF_FAIL(0);
     } else if (kind == 2) {
         u32 hc = 0xFFFFFFFFu, flg = 0, xlen = 0;
 #define INF_HBYTE(v)                                                                  \
@@ -398,13 +414,28 @@ __global__ __launch_bounds__(64) void k_df_inflate(const u8 *__restrict__ in, co
                 if (ds > 29) INF_FAIL(0);
                 const u32 d = c_dist_base[ds] + inf_take(r, c_dist_extra[ds]);
                 INF_EOF_CHECK();
-                if (d > p) INF_FAIL(0);
+                if (DICT ? d > p && d - p > W : d > p) INF_FAIL(0);
                 if (p > 0xFFFFFFFFu - 0x10000u) {
                     flags |= 1u;
                     INF_FAIL(0);
                 }
                 INF_FLUSH();
-                if (WRITE) {
+                if (WRITE && DICT) {
+                    // source byte q < 0 is window byte W + q: nobody writes the window, so only q >= 0 needs the fence
+                    const u32 span = d < len ? d : len;
+                    const long long q0 = (long long)p - d;
+                    if (q0 + span > (long long)fenced) {
+                        __threadfence_block();
+                        fenced = p;
+                    }
+                    for (u32 b = 0; b < len; b += 64u) {
+                        const u32 i = b + lane;
+                        if (i < len && p + i < limit) {
+                            const long long q = q0 + (d >= len ? i : i % d);
+                            out[p + i] = q < 0 ? dictw[(long long)W + q] : out[q];
+                        }
+                    }
+                } else if (WRITE) {
                     const u32 span = d < len ? d : len;
                     if (p - d + span > fenced) {
                         __threadfence_block();
@@ -481,10 +512,12 @@ struct InfOut {
 // a stored block) to the first block boundary at or behind `stop`; `base` is where the piece's output starts inside the
 // entry's (infsplit::kBaseUnknown: not known yet, a distance that reaches in front of the piece is recorded in `reach` and
 // believed); with WRITE every byte i gets smap[i]: i itself when out[i] holds its value, else the position inside the
-// entry's output (in front of the piece) that does.
-template <bool WRITE>
+// entry's output (in front of the piece) that does.  DICT: a source in front of the ENTRY is a window byte (above): it is
+// stored at once and is its own root -- the source map never points into the window -- and `base + p + W` bounds a distance.
+template <bool WRITE, bool DICT>
 __device__ __forceinline__ void inf_decode(InfTabs &t, InfIn &r, const u32 lane, const int kind, const bool head, u8 *out, const u32 limit,
-                                           u32 *smap, const u32 base, const u64 stop, bool at_len, InfOut &o)
+                                           u32 *smap, const u32 base, const u64 stop, bool at_len, InfOut &o, const u8 *__restrict__ dictw,
+                                           const u32 W, const u32 dict_adler)
 {
     u16 *const s_tl = t.tl, *const s_td = t.td, *const s_tc = t.tc, *const s_sl = t.sl, *const s_sd = t.sd, *const s_sc = t.sc;
     u32 *const s_nl = t.nl, *const s_nd = t.nd, *const s_nc = t.nc;
@@ -531,7 +564,14 @@ __device__ __forceinline__ void inf_decode(InfTabs &t, InfIn &r, const u32 lane,
         inf_fill(r, lane);
         const u32 cmf = inf_take(r, 8), flg = inf_take(r, 8);
         INF_EOF_CHECK();
-        if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 0x20u)) INF_FAIL(0);
+        if (DICT) { // zlib/decoder.rs:62-101: FDICT first, then the six bytes, then what they hold
+            if (!(flg & 0x20u)) INF_FAIL(0);
+            inf_fill(r, lane);
+            const u32 v = inf_take(r, 32);
+            INF_EOF_CHECK();
+            const u32 id = (v >> 24) | ((v >> 8) & 0xFF00u) | ((v << 8) & 0xFF0000u) | (v << 24);
+            if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || id != dict_adler) INF_FAIL(0);
+        } else if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 0x20u)) INF_FAIL(0);
     } else if (head && kind == 2) {
         u32 hc = 0xFFFFFFFFu, flg = 0, xlen = 0;
 #define INF_HBYTE(v)                                                                  \
@@ -705,7 +745,7 @@ __device__ __forceinline__ void inf_decode(InfTabs &t, InfIn &r, const u32 lane,
                 const u32 d = c_dist_base[ds] + inf_take(r, c_dist_extra[ds]);
                 INF_EOF_CHECK();
                 if (d > p) { // in front of the piece: inside the entry's output if the piece knows where it lies
-                    if (base != infsplit::kBaseUnknown && (u64)d > (u64)base + p) INF_FAIL(0);
+                    if (base != infsplit::kBaseUnknown && (u64)d > (u64)base + p + (DICT ? W : 0u)) INF_FAIL(0);
                     if (d - p > reach) reach = d - p;
                 }
                 if (p > 0xFFFFFFFFu - 0x10000u) {
@@ -723,7 +763,10 @@ __device__ __forceinline__ void inf_decode(InfTabs &t, InfIn &r, const u32 lane,
                         const u32 i = b + lane;
                         if (i < len && p + i < limit) {
                             const long long q = (long long)p - d + (d >= len ? i : i % d);
-                            if (q < 0) smap[p + i] = (u32)((long long)base + q); // (no byte: the gather brings it)
+                            if (DICT && (long long)base + q < 0) { // in front of the entry: a window byte, its own root
+                                out[p + i] = dictw[(long long)W + base + q];
+                                smap[p + i] = base + p + i;
+                            } else if (q < 0) smap[p + i] = (u32)((long long)base + q); // (no byte: the gather brings it)
                             else {
                                 const u32 sv = smap[q];
                                 out[p + i] = out[q];
@@ -834,9 +877,10 @@ __global__ __launch_bounds__(64) void k_df_split_search(const u8 *__restrict__ e
 }
 
 // One wave per piece.  <false>: what the piece is (DfPieceRec); <true>: its bytes and their source map, below pc.len.
-template <bool WRITE>
+template <bool WRITE, bool DICT>
 __global__ __launch_bounds__(64) void k_df_inflate_piece(const u8 *__restrict__ ebase, u32 elen, int kind, const DfPiece *__restrict__ pc,
-                                                         DfPieceRec *rec, u8 *eout, u32 *emap)
+                                                         DfPieceRec *rec, u8 *eout, u32 *emap, const u8 *__restrict__ dictw, u32 W,
+                                                         u32 dict_adler)
 {
     __shared__ InfTabs t;
     const u32 lane = threadIdx.x, j = blockIdx.x;
@@ -857,8 +901,8 @@ __global__ __launch_bounds__(64) void k_df_inflate_piece(const u8 *__restrict__ 
         (void)inf_take(r, (u32)q.start & 31u);
     }
     InfOut o;
-    inf_decode<WRITE>(t, r, lane, kind, head, WRITE ? eout + q.base : nullptr, WRITE ? q.len : 0u, WRITE ? emap + q.base : nullptr, q.base,
-                            q.stop, at_len, o);
+    inf_decode<WRITE, DICT>(t, r, lane, kind, head, WRITE ? eout + q.base : nullptr, WRITE ? q.len : 0u, WRITE ? emap + q.base : nullptr,
+                            q.base, q.stop, at_len, o, dictw, W, dict_adler);
     if (!WRITE && lane == 0) {
         DfPieceRec x;
         x.r = inf_record(o);
@@ -957,10 +1001,17 @@ __global__ __launch_bounds__(256) void k_df_inflate_check(const u8 *__restrict__
 }
 
 int df_launch_inflate(hipStream_t st, bool write, const u8 *in, const u64 *in_off, const u64 *in_len, u32 count, int kind, u8 *out,
-                      const u64 *out_off, DfInfRec *rec)
+                      const u64 *out_off, DfInfRec *rec, DfWindow win)
 {
-    if (write) hipLaunchKernelGGL((k_df_inflate<true>), dim3(count), dim3(64), 0, st, in, in_off, in_len, kind, out, out_off, rec);
-    else hipLaunchKernelGGL((k_df_inflate<false>), dim3(count), dim3(64), 0, st, in, in_off, in_len, kind, out, out_off, rec);
+#define INF_LAUNCH(WR, DI)                                                                                                          \
+    hipLaunchKernelGGL((k_df_inflate<WR, DI>), dim3(count), dim3(64), 0, st, in, in_off, in_len, kind, out, out_off, rec, win.p, win.W, \
+                       win.adler)
+    if (win.W) {
+        if (write) INF_LAUNCH(true, true);
+        else INF_LAUNCH(false, true);
+    } else if (write) INF_LAUNCH(true, false);
+    else INF_LAUNCH(false, false);
+#undef INF_LAUNCH
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -979,10 +1030,17 @@ int df_launch_split_search(hipStream_t st, const u8 *ebase, u32 elen, u32 piece_
 }
 
 int df_launch_inflate_piece(hipStream_t st, bool write, const u8 *ebase, u32 elen, int kind, const DfPiece *pc, u32 count, DfPieceRec *rec,
-                            u8 *eout, u32 *emap)
+                            u8 *eout, u32 *emap, DfWindow win)
 {
-    if (write) hipLaunchKernelGGL((k_df_inflate_piece<true>), dim3(count), dim3(64), 0, st, ebase, elen, kind, pc, rec, eout, emap);
-    else hipLaunchKernelGGL((k_df_inflate_piece<false>), dim3(count), dim3(64), 0, st, ebase, elen, kind, pc, rec, eout, emap);
+#define INF_LAUNCH(WR, DI)                                                                                                          \
+    hipLaunchKernelGGL((k_df_inflate_piece<WR, DI>), dim3(count), dim3(64), 0, st, ebase, elen, kind, pc, rec, eout, emap, win.p, win.W, \
+                       win.adler)
+    if (win.W) {
+        if (write) INF_LAUNCH(true, true);
+        else INF_LAUNCH(false, true);
+    } else if (write) INF_LAUNCH(true, false);
+    else INF_LAUNCH(false, false);
+#undef INF_LAUNCH
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -388,8 +388,9 @@ class BZip2Decoder {
 // Deflate / zlib / gzip decoders (include/bz2_mi355x.h section 5):
 //   Deflater     src/deflate/decoder.rs   (the reference's name for its Deflate DECODER)
 //   ZlibDecoder  src/zlib/decoder.rs      GZipDecoder  src/gzip/decoder.rs
-// The first next() collects the input range and decodes it in one df_decode_buffer call; the bytes come out in order,
+// The first next() collects the input range and decodes it in one df_decode_buffer_dict call; the bytes come out in order,
 // then the Err item if the stream is bad (RFC 1951 / 1950 / 1952 decide, see the header), then None.
+//   ::with_dict  Deflater and ZlibDecoder (src/deflate/decoder.rs:358-404, src/zlib/decoder.rs:152-158; GZipDecoder has none)
 //   MultiGZipDecoder  every member of a gzip file (section 6, df_decode_members_buffer): what gzip(1) yields; GZipDecoder
 //                     stops behind the first member, as the reference's does
 template <int Kind, bool Members = false> class DeflateFamilyDecoder {
@@ -399,6 +400,14 @@ template <int Kind, bool Members = false> class DeflateFamilyDecoder {
     using Error = CompressionError;
 
     explicit DeflateFamilyDecoder(int device = 0) : device_(device) {} // (does not touch the device)
+    // the dictionary is copied; an empty one is no dictionary (section 5, clause (c))
+    static DeflateFamilyDecoder with_dict(const uint8_t *dict, size_t dict_len, int device = 0)
+    {
+        static_assert(Kind != DF_KIND_GZIP, "GZipDecoder has no with_dict");
+        DeflateFamilyDecoder d(device);
+        d.dict_.assign(dict, dict + dict_len);
+        return d;
+    }
 
     template <class I, class S> std::optional<Result<uint8_t>> next(I &it, const S &end)
     {
@@ -409,7 +418,7 @@ template <int Kind, bool Members = false> class DeflateFamilyDecoder {
             uint8_t *out = nullptr;
             size_t n = 0;
             verdict_ = Members ? df_decode_members_buffer(device_, in.data(), in.size(), &out, &n)
-                               : df_decode_buffer(Kind, device_, in.data(), in.size(), &out, &n);
+                               : df_decode_buffer_dict(Kind, device_, in.data(), in.size(), dict_.data(), dict_.size(), &out, &n);
             if (out) {
                 buf_.assign(out, out + n);
                 bz_free(out);
@@ -431,6 +440,11 @@ template <int Kind, bool Members = false> class DeflateFamilyDecoder {
     };
     template <class Spans> static Result<std::vector<Entry>> decode_batch(const Spans &inputs, int device = 0)
     {
+        return decode_batch(inputs, nullptr, 0, device);
+    }
+    // ... with one preset dictionary for every stream (df_decode_batch_dict)
+    template <class Spans> static Result<std::vector<Entry>> decode_batch(const Spans &inputs, const uint8_t *dict, size_t dict_len, int device = 0)
+    {
         using R = Result<std::vector<Entry>>;
         std::vector<const uint8_t *> ptrs;
         std::vector<size_t> lens;
@@ -441,7 +455,8 @@ template <int Kind, bool Members = false> class DeflateFamilyDecoder {
         std::vector<uint64_t> off(ptrs.size()), len(ptrs.size());
         std::vector<int32_t> verdict(ptrs.size());
         uint8_t *out = nullptr;
-        const int rc = df_decode_batch(Kind, device, ptrs.data(), lens.data(), ptrs.size(), &out, off.data(), len.data(), verdict.data());
+        const int rc =
+            df_decode_batch_dict(Kind, device, ptrs.data(), lens.data(), ptrs.size(), dict, dict_len, &out, off.data(), len.data(), verdict.data());
         if (rc != BZ_OK) return R::Err(from_status(rc));
         std::vector<Entry> entries(ptrs.size());
         for (size_t i = 0; i < ptrs.size(); ++i) {
@@ -456,7 +471,7 @@ template <int Kind, bool Members = false> class DeflateFamilyDecoder {
     int device_;
     bool ran_ = false;
     int verdict_ = BZ_OK;
-    std::vector<uint8_t> buf_;
+    std::vector<uint8_t> buf_, dict_;
     size_t pos_ = 0;
 };
 using Deflater = DeflateFamilyDecoder<DF_KIND_DEFLATE>;

@@ -38,6 +38,15 @@ anything is timed.  The line also carries one df_gpu_decode_batch_device call ov
 split between the sizes launch, the writing launch and the checksum kernel (df_gpu_last_timings) and
 df_gpu_last_decode_batch_stats.  text64m is ONE entry of 64 MiB of the bench corpus: what a single stream costs.
 
+    tools/batch_time.py --inflate --dict-kib N [--kind deflate|zlib] [--workload ...]
+
+Decoding with a preset dictionary (section 5, clause (c) of the header): the dictionary is N KiB of another chapter of the
+bench corpus, the streams are zlib's (level 6) -- made once with zdict= and once without, since the batched encoder takes no
+dictionary.  Per form ("dict", "plain"), in the same run and alternating: deflate_decompress_batch host to host, the loop
+of zlib.decompressobj(wbits, zdict=) on one host thread, and one deflate_decode_batch_device call over the streams in HBM
+with its launches' times.  With --inflate-one the ONE stream is zlib's, made with the dictionary; --inflate-one --zlib-made
+is its control: zlib's stream of the same bytes without a dictionary.
+
     tools/batch_time.py --inflate-one SIZE_MIB [--calls 5] [--one-wave]
 
 ONE raw Deflate stream of SIZE_MIB MiB of the bench corpus (written by deflate_compress_batch), decoded by the split path
@@ -212,10 +221,12 @@ def inflate_mode(pkg, a, names):
     kind = {"deflate": pkg.DEFLATE, "zlib": pkg.ZLIB, "gzip": pkg.GZIP}[a.kind]
     wbits = {"deflate": -15, "zlib": 15, "gzip": 31}[a.kind]
 
-    def loop(streams):
+    def loop(streams, dict_=b""):
+        if dict_:
+            return [zlib.decompressobj(wbits, zdict=dict_).decompress(z) for z in streams]
         return [zlib.decompress(z, wbits) for z in streams]
 
-    def device_call(streams):
+    def device_call(streams, dict_=b""):
         """one df_gpu_decode_batch_device call over the streams in HBM: wall time, the launches' times, stats"""
         import torch
         off, buf = [], bytearray()
@@ -226,14 +237,15 @@ def inflate_mode(pkg, a, names):
         lens = [len(z) for z in streams]
         t = torch.frombuffer(buf, dtype=torch.uint8).cuda()
         eng = pkg.GpuEngine(0, 1)
+        kw = {"dict_": dict_} if dict_ else {}
         try:
-            o_off, o_len, _ = eng.deflate_decode_batch_device(kind, t.data_ptr(), off, lens, None, 0)
+            o_off, o_len, _ = eng.deflate_decode_batch_device(kind, t.data_ptr(), off, lens, None, 0, **kw)
             cap = max(x + n for x, n in zip(o_off, o_len))
             o = torch.empty((cap + 64,), dtype=torch.uint8, device="cuda")
-            eng.deflate_decode_batch_device(kind, t.data_ptr(), off, lens, o.data_ptr(), cap)   # (warm)
+            eng.deflate_decode_batch_device(kind, t.data_ptr(), off, lens, o.data_ptr(), cap, **kw)   # (warm)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            eng.deflate_decode_batch_device(kind, t.data_ptr(), off, lens, o.data_ptr(), cap)
+            eng.deflate_decode_batch_device(kind, t.data_ptr(), off, lens, o.data_ptr(), cap, **kw)
             wall = time.perf_counter() - t0
             tm = eng.deflate_timings()
             stage = {"sizes_launch": tm["hash_chains"], "write_launch": tm["matches"], "checksums": tm["parse"], "total": tm["total"]}
@@ -241,6 +253,8 @@ def inflate_mode(pkg, a, names):
         finally:
             eng.close()
 
+    if a.dict_kib:
+        return inflate_dict_mode(pkg, a, names, kind, wbits, loop, device_call)
     for name in names:
         datas = workload(name)
         total = sum(len(d) for d in datas)
@@ -273,29 +287,87 @@ def inflate_mode(pkg, a, names):
             raise SystemExit("batch_time.py: the batch's outputs differ from the inputs")
 
 
+def bench_dictionary(kib):
+    """kib KiB of a chapter of the bench corpus that no workload holds: the same vocabulary, other text"""
+    import corpus
+    return bytes(corpus.chapter(1, kib * 1024)[:kib * 1024])
+
+
+def inflate_dict_mode(pkg, a, names, kind, wbits, loop, device_call):
+    import zlib
+    if kind == pkg.GZIP:
+        raise SystemExit("batch_time.py: gzip takes no dictionary")
+    dict_ = bench_dictionary(a.dict_kib)
+    for name in names:
+        datas = workload(name)
+        total = sum(len(d) for d in datas)
+        forms = {}
+        for form, d in (("dict", dict_), ("plain", b"")):
+            streams = []
+            for x in datas:
+                c = zlib.compressobj(6, zlib.DEFLATED, wbits, zdict=d) if d else zlib.compressobj(6, zlib.DEFLATED, wbits)
+                streams.append(c.compress(x) + c.flush())
+            forms[form] = (d, streams)
+        same = all(pkg.deflate_decompress_batch(z, kind, dict_=d) == [(x, 0) for x in datas] and loop(z, d) == datas for d, z in forms.values())
+        times = {form: {"batch": [], "zlib_loop": []} for form in forms}
+        for _ in range(a.runs):
+            for form, (d, z) in forms.items():      # (alternating the two forms)
+                tb, tl = [], []
+                for _ in range(a.calls):
+                    t0 = time.perf_counter()
+                    pkg.deflate_decompress_batch(z, kind, dict_=d)
+                    tb.append(time.perf_counter() - t0)
+                for _ in range(a.loops):
+                    t0 = time.perf_counter()
+                    loop(z, d)
+                    tl.append(time.perf_counter() - t0)
+                times[form]["batch"].append(round(statistics.median(tb) * 1e3, 2))
+                times[form]["zlib_loop"].append(round(statistics.median(tl) * 1e3, 2))
+        line = {"mode": "inflate-dict", "kind": a.kind, "workload": name, "dict_kib": a.dict_kib, "streams": len(datas), "bytes": total,
+                "outputs_equal": same}
+        for form, (d, z) in forms.items():
+            stage_ms, stats, wall_ms = device_call(z, d)
+            bm, lm = statistics.median(times[form]["batch"]), statistics.median(times[form]["zlib_loop"])
+            line[form] = {"compressed_bytes": sum(len(s) for s in z), "batch_ms": bm, "zlib_loop_ms": lm, "batch_GBps": round(total / bm / 1e6, 3),
+                          "zlib_loop_GBps": round(total / lm / 1e6, 3), "batch_runs_ms": times[form]["batch"],
+                          "zlib_loop_runs_ms": times[form]["zlib_loop"], "device_call_ms": wall_ms,
+                          "device_call_GBps": round(total / wall_ms / 1e6, 3), "device_call_stage_ms": stage_ms, "device_call_batch_stats": stats}
+        print(json.dumps(line), flush=True)
+        if not same:
+            raise SystemExit("batch_time.py: the batch's outputs differ from the inputs")
+
+
 def inflate_one_mode(pkg, a):
     import zlib
     import torch
     import corpus
     data = corpus.corpus_bytes(int(a.inflate_one * (1 << 20)))
-    (z,) = pkg.deflate_compress_batch([data], pkg.DEFLATE)
-    same = zlib.decompress(z, -15) == data                                              # (warm)
+    dict_ = bench_dictionary(a.dict_kib) if a.dict_kib else b""
+    kw = {"dict_": dict_} if dict_ else {}
+    if dict_ or a.zlib_made:
+        c = zlib.compressobj(6, zlib.DEFLATED, -15, zdict=dict_) if dict_ else zlib.compressobj(6, zlib.DEFLATED, -15)
+        z = c.compress(data) + c.flush()
+        unzip = lambda: (zlib.decompressobj(-15, zdict=dict_) if dict_ else zlib.decompressobj(-15)).decompress(z)
+    else:
+        (z,) = pkg.deflate_compress_batch([data], pkg.DEFLATE)
+        unzip = lambda: zlib.decompress(z, -15)
+    same = unzip() == data                                                              # (warm)
     tz = []
     for _ in range(3):
         t0 = time.perf_counter()
-        zlib.decompress(z, -15)
+        unzip()
         tz.append((time.perf_counter() - t0) * 1e3)
     zlib_ms = statistics.median(tz)
-    same = same and pkg.deflate_decompress_batch([z], pkg.DEFLATE) == [(data, 0)]      # (warm)
+    same = same and pkg.deflate_decompress_batch([z], pkg.DEFLATE, **kw) == [(data, 0)]      # (warm)
     th = []
     for _ in range(a.calls):
         t0 = time.perf_counter()
-        pkg.deflate_decompress_batch([z], pkg.DEFLATE)
+        pkg.deflate_decompress_batch([z], pkg.DEFLATE, **kw)
         th.append((time.perf_counter() - t0) * 1e3)
     t = torch.frombuffer(bytearray(z) + bytes(-len(z) % 4 + 4), dtype=torch.uint8).cuda()
     eng = pkg.GpuEngine(0, 1)
     try:
-        call = lambda o, cap: eng.deflate_decode_batch_device(pkg.DEFLATE, t.data_ptr(), [0], [len(z)], o, cap)
+        call = lambda o, cap: eng.deflate_decode_batch_device(pkg.DEFLATE, t.data_ptr(), [0], [len(z)], o, cap, **kw)
         o_off, o_len, _ = call(None, 0)
         o = torch.empty((o_len[0] + 64,), dtype=torch.uint8, device="cuda")
         call(o.data_ptr(), o_len[0])                                                    # (warm)
@@ -324,7 +396,8 @@ def inflate_one_mode(pkg, a):
     finally:
         eng.close()
     hm, dm = statistics.median(th), statistics.median(td)
-    print(json.dumps({"mode": "inflate-one", "bytes": len(data), "compressed_bytes": len(z), "outputs_equal": same,
+    print(json.dumps({"mode": "inflate-one", "bytes": len(data), "compressed_bytes": len(z), "outputs_equal": same, "dict_kib": a.dict_kib,
+                      "stream": "zlib level 6" if dict_ or a.zlib_made else "deflate_compress_batch",
                       "split_kib": os.environ.get("BZ_DF_INF_SPLIT_KIB", "default"), "piece_kib": os.environ.get("BZ_DF_INF_PIECE_KIB", "default"),
                       "host_to_host_ms": round(hm, 2), "host_to_host_GBps": round(len(data) / hm / 1e6, 3),
                       "device_call_ms": round(dm, 2), "device_call_GBps": round(len(data) / dm / 1e6, 3),
@@ -341,6 +414,8 @@ def main():
     ap.add_argument("--inflate", action="store_true", help="time deflate_decompress_batch against a loop of zlib.decompress")
     ap.add_argument("--inflate-one", type=float, default=0, metavar="SIZE_MIB", help="time ONE Deflate stream of that many MiB of text")
     ap.add_argument("--one-wave", action="store_true", help="--inflate-one: one more call on the one-wave path")
+    ap.add_argument("--zlib-made", action="store_true", help="--inflate-one: the stream is zlib's (level 6), the control of --dict-kib")
+    ap.add_argument("--dict-kib", type=int, default=0, metavar="N", help="--inflate / --inflate-one: zlib's streams, made with a dictionary of N KiB")
     ap.add_argument("--kind", default="deflate", choices=["deflate", "zlib", "gzip"])
     ap.add_argument("--decode", action="store_true", help="time decompress_batch against a loop of bz_decode_buffer")
     ap.add_argument("--workload", default="all")
