@@ -637,7 +637,7 @@ int df_encode_buffer_dict(int kind, int device, const uint8_t *in, size_t in_len
  * ascending and disjoint; bytes outside the ranges are never read as part of any input.  Stream i -- the bytes of
  * df_gpu_encode_device(g, kind, d_in + h_in_off[i], h_in_len[i], ...), bit for bit -- is written at d_out + h_out_off[i]
  * (h_out_len[i] bytes): input order, each stream at a multiple of 4 bytes, zeros between them, nothing at or behind
- * d_out + cap.  One `kind` for the call, no dictionary.  Inputs of at most 0xFFFF bytes are exactly one Deflate block
+ * d_out + cap.  One `kind` for the call.  Inputs of at most 0xFFFF bytes are exactly one Deflate block
  * (MAX_BLOCK_SIZE, src/deflate/encoder.rs:577-597) and are encoded together, whatever their number, in sub-batches of
  * BZ_DF_BATCH_MIB (default 64) MiB of 4 KiB-aligned slots: one pass of the pipeline, one host round trip and one placement
  * per sub-batch, the container checksums, headers and trailers written on the device.  Every other input takes the path
@@ -660,6 +660,24 @@ int df_gpu_last_batch_stats(bz_gpu_engine *g, uint64_t out[8]);
  * empty buffer, no device is touched. */
 int df_encode_batch(int kind, int device, const uint8_t *const *ins, const size_t *lens, size_t count,
                     uint8_t **out, uint64_t *out_off, uint64_t *out_len);
+/* The same with ONE preset dictionary for every input (`Inflater::with_dict` / `ZlibEncoder::with_dict`; dict is host
+ * memory).  Stream i is, byte for byte, df_encode_buffer_dict(kind, input i, dict, dict_len): the last 32 768 bytes of the
+ * dictionary are history in front of EVERY input; zlib (kind 1) writes the six-byte header 78 F9 + DICTID (the Adler-32 of the
+ * whole dictionary), and its trailer covers the input alone.  dict_len == 0 is no dictionary: the calls above, same bytes
+ * (they ARE these calls with (NULL, 0)).  BZ_E_PARAM: dict == NULL with dict_len > 0; kind 2 with dict_len > 0 (GZipEncoder
+ * has no with_dict).  An input of at most 0xFFFF bytes is still exactly one block (the dictionary is history, not output,
+ * src/deflate/encoder.rs:293-308) and takes the batch path: the dictionary's window lies in the sub-batch's image in front
+ * of every slot, so a sub-batch of BZ_DF_BATCH_MIB holds up to 32 KiB less input per slot.  Layout of the output,
+ * df_encode_batch_bound (its 64 bytes of slack per input cover the longer header), df_gpu_last_batch_stats: as above.
+ * What df_gpu_encode_batch_device_dict writes is valid input of df_gpu_decode_batch_device_dict with the same offsets,
+ * lengths and dictionary. */
+int df_gpu_encode_batch_device_dict(bz_gpu_engine *g, int kind, const void *d_in,
+                                    const uint64_t *h_in_off, const uint64_t *h_in_len, size_t count,
+                                    const uint8_t *dict, size_t dict_len,
+                                    void *d_out, size_t cap, uint64_t *h_out_off, uint64_t *h_out_len);
+int df_encode_batch_dict(int kind, int device, const uint8_t *const *ins, const size_t *lens, size_t count,
+                         const uint8_t *dict, size_t dict_len,
+                         uint8_t **out, uint64_t *out_off, uint64_t *out_len);
 
 /* Streaming context == the Encoder::next contract of the three encoders:
  * df_enc_write feeds bytes, df_enc_end(action) marks the end of an input

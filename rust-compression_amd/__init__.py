@@ -97,6 +97,7 @@ EXPORTS = [
     "df_gpu_debug_blocks", "df_encode_buffer", "df_gpu_encode_device_dict", "df_encode_buffer_dict", "df_enc_create_dict",
     "df_enc_create", "df_enc_write", "df_enc_end", "df_enc_read", "df_enc_pending", "df_enc_destroy", "df_enc_finished",
     "df_encode_batch_bound", "df_gpu_encode_batch_device", "df_gpu_last_batch_stats", "df_encode_batch",
+    "df_gpu_encode_batch_device_dict", "df_encode_batch_dict",
     "df_gpu_decode_batch_device", "df_gpu_last_decode_batch_stats", "df_gpu_last_decode_split_stats", "df_gpu_last_decode_split_timings", "df_decode_batch", "df_decode_buffer",
     "df_gpu_decode_batch_device_dict", "df_decode_batch_dict", "df_decode_buffer_dict",
     "df_gpu_decode_members_device", "df_gpu_last_decode_members_stats", "df_gpu_last_decode_members_timings", "df_decode_members_buffer",
@@ -252,6 +253,8 @@ def lib():
     L.df_gpu_encode_batch_device.argtypes = [vp, C.c_int, vp, u64p, u64p, sz, vp, sz, u64p, u64p]
     L.df_gpu_last_batch_stats.argtypes = [vp, u64p]
     L.df_encode_batch.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, sz, C.POINTER(u8p), u64p, u64p]
+    L.df_gpu_encode_batch_device_dict.argtypes = [vp, C.c_int, vp, u64p, u64p, sz, C.c_char_p, sz, vp, sz, u64p, u64p]
+    L.df_encode_batch_dict.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, sz, C.c_char_p, sz, C.POINTER(u8p), u64p, u64p]
     L.df_gpu_decode_batch_device.argtypes = [vp, C.c_int, vp, u64p, u64p, sz, vp, sz, u64p, u64p, i32p]
     L.df_gpu_last_decode_batch_stats.argtypes = [vp, u64p]
     L.df_gpu_last_decode_split_stats.argtypes = [vp, u64p]
@@ -698,13 +701,23 @@ def deflate_encode_batch_bound(lens):
     return lib().df_encode_batch_bound(a, len(lens))
 
 
-def deflate_compress_batch(datas, kind=DEFLATE, device=0):
-    """Many independent inputs in one call (df_encode_batch) -> list of streams: element i is
-    deflate_compress(datas[i], kind), bit for bit.  Inputs of at most 65 535 bytes (one Deflate block for certain) are
-    encoded together in one pass of the pipeline, however many there are."""
+def _encode_dict(kind, dict_):
+    """The dictionary of a batch encode call as the C ABI takes it; an empty one is no dictionary."""
     if kind not in (DEFLATE, ZLIB, GZIP):
         raise ValueError("invalid kind")
-    return _batch_call(lib().df_encode_batch, (kind, device), datas, False)
+    dict_ = bytes(dict_)
+    if dict_ and kind == GZIP:
+        raise ValueError("gzip encoding takes no preset dictionary (GZipEncoder has no with_dict)")
+    return dict_
+
+
+def deflate_compress_batch(datas, kind=DEFLATE, device=0, dict_=b""):
+    """Many independent inputs in one call (df_encode_batch_dict) -> list of streams: element i is
+    deflate_compress(datas[i], kind, dict_=dict_), bit for bit -- one preset dictionary (`Inflater::with_dict` /
+    `ZlibEncoder::with_dict`, kinds DEFLATE and ZLIB) serves every input.  Inputs of at most 65 535 bytes (one Deflate
+    block for certain) are encoded together in one pass of the pipeline, however many there are."""
+    dict_ = _encode_dict(kind, dict_)
+    return _batch_call(lib().df_encode_batch_dict, (kind, device), datas, False, (dict_, len(dict_)))
 
 
 _DECODER_VERDICTS = (BZ_E_DATA, BZ_E_MAGIC_FIRST, BZ_E_MAGIC)
@@ -1131,9 +1144,12 @@ class GpuEngine:
     DEFLATE_BATCH_STATS = ("inputs_batched", "inputs_one_by_one", "sub_batches", "stored", "fixed", "dynamic", "limited_tables",
                            "dynamic_without_distances")
 
-    def deflate_encode_batch_device(self, kind, d_in, in_off, in_len, d_out, cap):
-        """Many inputs, one stream each (df_gpu_encode_batch_device): input i is the in_len[i] bytes at d_in + in_off[i]
-        (offsets multiples of 16, in ascending order); returns (out_off, out_len), stream i at d_out + out_off[i]."""
+    def deflate_encode_batch_device(self, kind, d_in, in_off, in_len, d_out, cap, dict_=b""):
+        """Many inputs, one stream each (df_gpu_encode_batch_device_dict): input i is the in_len[i] bytes at d_in + in_off[i]
+        (offsets multiples of 16, in ascending order); returns (out_off, out_len), stream i at d_out + out_off[i].  dict_
+        (host bytes): one preset dictionary for every input, kinds DEFLATE and ZLIB (a kind outside 0..2 is the C call's
+        BZ_E_PARAM, as ever)."""
+        dict_ = _encode_dict(kind, dict_) if kind in (DEFLATE, ZLIB, GZIP) else bytes(dict_)
         _settle()
         k = len(in_off)
         if len(in_len) != k:
@@ -1142,7 +1158,7 @@ class GpuEngine:
         a_len = (C.c_uint64 * max(k, 1))(*in_len)
         o_off = (C.c_uint64 * max(k, 1))()
         o_len = (C.c_uint64 * max(k, 1))()
-        _check(lib().df_gpu_encode_batch_device(self._h, kind, d_in, a_off, a_len, k, d_out, cap, o_off, o_len))
+        _check(lib().df_gpu_encode_batch_device_dict(self._h, kind, d_in, a_off, a_len, k, dict_, len(dict_), d_out, cap, o_off, o_len))
         return list(o_off[:k]), list(o_len[:k])
 
     def deflate_batch_stats(self):

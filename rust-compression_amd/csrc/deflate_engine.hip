@@ -27,6 +27,7 @@ struct DfWorkspace {
     DevBuf keys_in, keys_out, vals_in, vals_out, sort_tmp, prevd, est, segoff, concat, bitmap, canon, tabs, ents, bstart, nb, blocks, lens, hdr, lm, total,
         stream, asum, bsum, crc, part_res;
     DevBuf b_slots, b_tile_slot, b_bse, b_outs, b_stats; // a sub-batch of df_gpu_encode_batch_device: slot tables, block ends, streams' places
+    DevBuf b_win;                                      // ... and the window of a call with a preset dictionary (uploaded per call)
     u64 batch_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // df_gpu_last_batch_stats
     DevBuf i_in, i_ooff, i_rec;                        // df_gpu_decode_batch_device: the entries' ranges, their outputs' places, their records
     DevBuf i_dict;                                     // ... and the window of a call with a preset dictionary (uploaded per call)
@@ -137,6 +138,27 @@ static u32 gf_xpow8_reflected(u64 nbytes) // x^(8 * nbytes) mod P
         nbytes >>= 1;
     }
     return r;
+}
+// Adler-32 (adler32.rs:20-66) of a preset dictionary: the DICTID of a zlib header
+static u32 df_adler32_host(const uint8_t *p, size_t n)
+{
+    u32 a = 1, b = 0;
+    for (size_t i = 0; i < n;) { // (5552 bytes keep b below 2^32: the largest n with 255 n (n + 1) / 2 + (n + 1) 65520 < 2^32)
+        const size_t end = std::min(n, i + 5552);
+        for (; i < end; ++i) {
+            a += p[i];
+            b += a;
+        }
+        a %= 65521;
+        b %= 65521;
+    }
+    return (b << 16) | a;
+}
+// the parameter errors of a dictionary, the same in every batch form, encode and decode: a length without a pointer, and gzip
+// (GZipEncoder and GZipDecoder have no with_dict)
+static int df_dict_param(int kind, const uint8_t *dict, size_t dict_len)
+{
+    return dict_len && (!dict || kind == 2) ? BZ_E_PARAM : BZ_OK;
 }
 static DfCrcShifts df_crc_shifts() // x^(8 * 256 * 2^k): what the device folds a piece's sub-pieces with
 {
@@ -564,28 +586,55 @@ static int df_encode_parts(bz_gpu_engine *g, int kind, const u8 *d_in, u64 n, co
 }
 
 // ---- many inputs in one call ----------------------------------------------------------------------------------
-// An input of at most kBlockMax bytes without a dictionary is exactly one block (InflaterInner::next closes a block only when
-// the next code would take it past 0xFFFF bytes, deflate/encoder.rs:577-597): it starts at the input's first byte with
-// decompress_len 0 and is final.  Such inputs are encoded together, a sub-batch at a time: gathered into an image with
-// every input at a multiple of kPTile, one pass of the chain sort, the match kernel (slot rules: k_df_match2<true>), the parse
-// and one block per input; the streams' places come from a scan on the device, the containers are written there too, and the
-// host looks at the device once per sub-batch.  Every other input goes through df_encode_parts, in its turn.
+// An input of at most kBlockMax bytes is exactly one block (InflaterInner::next closes a block only when the next code would
+// take it past 0xFFFF bytes, deflate/encoder.rs:577-597): it starts at the input's first byte with decompress_len 0 -- with
+// a preset dictionary too (InflaterInner::with_dict, :293-308: the dictionary is history, not output) -- and is final.
+// Such inputs are encoded together, a sub-batch at a time: gathered into an image with every input at a multiple of kPTile,
+// one pass of the chain sort, the match kernel (slot rules: k_df_match2<true>), the parse and one block per input; the
+// streams' places come from a scan on the device, the containers are written there too, and the host looks at the device
+// once per sub-batch.  Every other input goes through df_encode_parts, in its turn.
+// A preset dictionary (df_gpu_encode_batch_device_dict): its last W <= 32768 bytes go to the device once per call and into
+// the image in front of EVERY input (DfBatchDict; k_deflate.h "window tiles") -- df_encode_core's history layout, once per slot.
 static u64 df_batch_image_bytes()
 {
     const char *s = getenv("BZ_DF_BATCH_MIB"); // slot image per sub-batch (a fraction is taken too), read per call
     double mib = s ? atof(s) : 64.0;
-    if (!(mib >= 1.0 / 16)) mib = 1.0 / 16; // (an input has up to 16 tiles)
+    if (!(mib >= 1.0 / 16)) mib = 1.0 / 16; // (16 tiles; a slot has up to 16, with a dictionary's window up to 24: the first
+                                            // input of a sub-batch is admitted whatever the limit)
     if (mib > 1024) mib = 1024;
     return (u64)(mib * 1048576.0);
 }
 constexpr u32 kBatchSlots = 8192; // inputs per sub-batch at most (k_df_block's scratch is 147 KB per block)
-static u32 df_slot_tiles(u64 n) { return n ? (u32)((n + kPTile - 1) / kPTile) : 1u; }
+static u32 df_slot_tiles(u64 n) { return n ? (u32)((n + kPTile - 1) / kPTile) : 1u; } // (the input's tiles)
 
-// inputs [first, first + ns) of the call, all of at most kBlockMax bytes, ntiles tiles together; their streams go to
-// d_out + cursor .. in input order, *used = bytes taken there (a multiple of 4)
+// the dictionary of a batch call as its sub-batches see it; W == 0: none
+struct DfBatchDict {
+    const u8 *d_win = nullptr; // the window right-aligned in kWin bytes of device memory, zeros in front of it
+    u32 W = 0;                 // min(dict_len, 32768)
+    u32 wtiles = 0;            // window tiles in front of every slot's input tiles
+    u32 dictid = 0;            // Adler-32 of the whole dictionary
+};
+static int df_batch_window(bz_gpu_engine *g, DfWorkspace *w, const uint8_t *dict, size_t dict_len, DfBatchDict &bd)
+{
+    bd = DfBatchDict{};
+    if (!dict_len) return BZ_OK;
+    const u32 W = (u32)std::min<size_t>(dict_len, kWin);
+    const int rc = w->b_win.ensure(kWin);
+    if (rc != BZ_OK) return rc;
+    if (W < kWin) HIPCHK(hipMemsetAsync(w->b_win.p, 0, kWin - W, g->st));
+    HIPCHK(hipMemcpyAsync(w->b_win.as<u8>() + (kWin - W), dict + (dict_len - W), W, hipMemcpyHostToDevice, g->st));
+    bd.d_win = w->b_win.as<u8>();
+    bd.W = W;
+    bd.wtiles = (W + kPTile - 1) / kPTile;
+    bd.dictid = df_adler32_host(dict, dict_len);
+    return BZ_OK;
+}
+
+// inputs [first, first + ns) of the call, all of at most kBlockMax bytes, ntiles tiles together (window tiles included); their
+// streams go to d_out + cursor .. in input order, *used = bytes taken there (a multiple of 4)
 static int df_batch_run(bz_gpu_engine *g, int kind, const u8 *d_in, const uint64_t *h_in_off, const uint64_t *h_in_len, size_t first,
-                        u32 ns, u32 ntiles, u8 *d_out, size_t cap, u64 cursor, uint64_t *h_out_off, uint64_t *h_out_len, u64 *used,
-                        double t_acc[6])
+                        u32 ns, u32 ntiles, const DfBatchDict &bd, u8 *d_out, size_t cap, u64 cursor, uint64_t *h_out_off,
+                        uint64_t *h_out_len, u64 *used, double t_acc[6])
 {
     DfWorkspace *w = g->df;
     hipStream_t st = g->st;
@@ -599,11 +648,11 @@ static int df_batch_run(bz_gpu_engine *g, int kind, const u8 *d_in, const uint64
         for (u32 j = 0; j < ns; ++j) {
             const u64 n = h_in_len[first + j];
             slots[j].src = h_in_off[first + j];
-            slots[j].lo = t * kPTile;
+            slots[j].lo = (t + bd.wtiles) * kPTile;
             slots[j].len = (u32)n;
             bse[2 * (size_t)j] = slots[j].lo;
             bse[2 * (size_t)j + 1] = slots[j].lo + n;
-            for (u32 k = df_slot_tiles(n); k; --k) tile_slot[t++] = j;
+            for (u32 k = bd.wtiles + df_slot_tiles(n); k; --k) tile_slot[t++] = j;
             bound += (df_encode_bound((size_t)n) + 3u) & ~(size_t)3;
         }
     }
@@ -622,7 +671,7 @@ static int df_batch_run(bz_gpu_engine *g, int kind, const u8 *d_in, const uint64
     const DfSlot *d_slots = w->b_slots.as<DfSlot>();
     const u32 *d_tile_slot = w->b_tile_slot.as<u32>();
     const u64 *d_bse = w->b_bse.as<u64>();
-    const u32 head = kind == 1 ? 2u : (kind == 2 ? 10u : 0u), tail = kind == 1 ? 4u : (kind == 2 ? 8u : 0u);
+    const u32 head = kind == 1 ? (bd.W ? 6u : 2u) : (kind == 2 ? 10u : 0u), tail = kind == 1 ? 4u : (kind == 2 ? 8u : 0u);
     const u32 ns_word = ns;
     // (the host arrays live on this stack frame: the wait below)
     HIPCHK(hipMemcpyAsync(w->b_slots.p, slots.data(), (size_t)ns * sizeof(DfSlot), hipMemcpyHostToDevice, st));
@@ -632,15 +681,15 @@ static int df_batch_run(bz_gpu_engine *g, int kind, const u8 *d_in, const uint64
     HIPCHK(hipMemsetAsync(w->b_stats.p, 0, 64, st));
     HIPCHK(hipEventRecord(w->ev[0], st));
     HIPCHK(hipMemsetAsync(w->stream.p, 0, bound + 64, st));
-    if (df_launch_gather(st, d_in, d_slots, d_tile_slot, ntiles, image) != 0) return BZ_E_UNEXPECTED;
+    if (df_launch_gather(st, d_in, d_slots, d_tile_slot, ntiles, image, bd.d_win) != 0) return BZ_E_UNEXPECTED;
     if (df_launch_chains(st, image, nimg, w->vals_in.as<u32>(), w->vals_out.as<u32>(), nullptr, w->sort_tmp.as<u32>(), w->keys_out.as<u32>(),
                          nullptr) != 0)
         return BZ_E_UNEXPECTED;
     HIPCHK(hipEventRecord(w->ev[1], st));
-    if (df_launch_match2_batch(st, image, nimg, w->vals_out.as<u32>(), M, d_tile_slot, d_slots) != 0) return BZ_E_UNEXPECTED;
+    if (df_launch_match2_batch(st, image, nimg, w->vals_out.as<u32>(), M, d_tile_slot, d_slots, bd.W) != 0) return BZ_E_UNEXPECTED;
     HIPCHK(hipEventRecord(w->ev[2], st));
-    if (df_launch_parse_batch(st, M, nimg, ntiles, d_slots, ns, w->keys_in.as<u16>(), w->tabs.as<u16>(), w->ents.as<u16>(), code,
-                              w->bitmap.as<u64>(), w->canon.as<u64>()) != 0)
+    if (df_launch_parse_batch(st, M, nimg, ntiles, d_slots, ns, bd.wtiles, w->keys_in.as<u16>(), w->tabs.as<u16>(), w->ents.as<u16>(),
+                              code, w->bitmap.as<u64>(), w->canon.as<u64>()) != 0)
         return BZ_E_UNEXPECTED;
     HIPCHK(hipEventRecord(w->ev[3], st));
     if (df_launch_blocks_batch(st, image, code, d_bse, w->nb.as<u32>(), ns, w->blocks.as<DfBlock>(), w->lens.as<u8>(), w->hdr.as<u32>(),
@@ -653,7 +702,7 @@ static int df_batch_run(bz_gpu_engine *g, int kind, const u8 *d_in, const uint64
                              w->stream.as<u32>()) != 0)
         return BZ_E_UNEXPECTED;
     if (df_launch_batch_wrap(st, image, d_slots, ns, w->blocks.as<DfBlock>(), w->b_outs.as<DfBatchOut>(), kind, df_crc_shifts(), w->stream.as<u8>(),
-                             w->b_stats.as<u32>()) != 0)
+                             w->b_stats.as<u32>(), bd.W != 0, bd.dictid) != 0)
         return BZ_E_UNEXPECTED;
     HIPCHK(hipEventRecord(w->ev[5], st));
     std::vector<DfBatchOut> outs(ns);
@@ -697,7 +746,15 @@ extern "C" int df_gpu_encode_batch_device(bz_gpu_engine *g, int kind, const void
                                           const uint64_t *h_in_len, size_t count, void *d_out, size_t cap, uint64_t *h_out_off,
                                           uint64_t *h_out_len)
 {
+    return df_gpu_encode_batch_device_dict(g, kind, d_in, h_in_off, h_in_len, count, nullptr, 0, d_out, cap, h_out_off, h_out_len);
+}
+
+extern "C" int df_gpu_encode_batch_device_dict(bz_gpu_engine *g, int kind, const void *d_in, const uint64_t *h_in_off,
+                                               const uint64_t *h_in_len, size_t count, const uint8_t *dict, size_t dict_len,
+                                               void *d_out, size_t cap, uint64_t *h_out_off, uint64_t *h_out_len)
+{
     if (!g || kind < 0 || kind > 2) return BZ_E_PARAM;
+    if (df_dict_param(kind, dict, dict_len) != BZ_OK) return BZ_E_PARAM;
     if (count == 0) return BZ_OK;
     if (!h_in_off || !h_in_len || !h_out_off || !h_out_len || !d_out) return BZ_E_PARAM;
     if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 3u)) return BZ_E_PARAM;
@@ -714,6 +771,9 @@ extern "C" int df_gpu_encode_batch_device(bz_gpu_engine *g, int kind, const void
     const u8 *in8 = static_cast<const u8 *>(d_in);
     u8 *out8 = static_cast<u8 *>(d_out);
     const u64 image_max = df_batch_image_bytes();
+    DfBatchDict bd;
+    const int drc = df_batch_window(g, w, dict, dict_len, bd);
+    if (drc != BZ_OK) return drc;
     double t_acc[6] = {0, 0, 0, 0, 0, 0};
     u64 cursor = 0;
     bool batched = false;
@@ -721,7 +781,7 @@ extern "C" int df_gpu_encode_batch_device(bz_gpu_engine *g, int kind, const void
         if (h_in_len[i] > kBlockMax) { // more than one block: the one-input path, in its place
             size_t got = 0;
             if (cursor > cap) return BZ_E_CAPACITY;
-            const int rc = df_encode_parts(g, kind, in8 + h_in_off[i], h_in_len[i], nullptr, 0, out8 + cursor, cap - cursor, &got);
+            const int rc = df_encode_parts(g, kind, in8 + h_in_off[i], h_in_len[i], dict, dict_len, out8 + cursor, cap - cursor, &got);
             if (rc != BZ_OK) return rc;
             const u64 slot = ((u64)got + 3u) & ~(u64)3;
             if (cursor + slot > cap) return BZ_E_CAPACITY;
@@ -736,13 +796,13 @@ extern "C" int df_gpu_encode_batch_device(bz_gpu_engine *g, int kind, const void
         size_t j = i;
         u64 tiles = 0;
         while (j < count && h_in_len[j] <= kBlockMax && j - i < kBatchSlots &&
-               (j == i || (tiles + df_slot_tiles(h_in_len[j])) * kPTile <= image_max)) {
-            tiles += df_slot_tiles(h_in_len[j]);
+               (j == i || (tiles + bd.wtiles + df_slot_tiles(h_in_len[j])) * kPTile <= image_max)) {
+            tiles += bd.wtiles + df_slot_tiles(h_in_len[j]);
             ++j;
         }
         u64 used = 0;
-        const int rc = df_batch_run(g, kind, in8, h_in_off, h_in_len, i, (u32)(j - i), (u32)tiles, out8, cap, cursor, h_out_off, h_out_len,
-                                    &used, t_acc);
+        const int rc = df_batch_run(g, kind, in8, h_in_off, h_in_len, i, (u32)(j - i), (u32)tiles, bd, out8, cap, cursor, h_out_off,
+                                    h_out_len, &used, t_acc);
         if (rc != BZ_OK) return rc;
         cursor += used;
         w->batch_stats[0] += j - i;
@@ -786,9 +846,16 @@ static int df_download(uint8_t **out, const void *d_src, size_t total)
 extern "C" int df_encode_batch(int kind, int device, const uint8_t *const *ins, const size_t *lens, size_t count, uint8_t **out,
                                uint64_t *out_off, uint64_t *out_len)
 {
+    return df_encode_batch_dict(kind, device, ins, lens, count, nullptr, 0, out, out_off, out_len);
+}
+
+extern "C" int df_encode_batch_dict(int kind, int device, const uint8_t *const *ins, const size_t *lens, size_t count, const uint8_t *dict,
+                                    size_t dict_len, uint8_t **out, uint64_t *out_off, uint64_t *out_len)
+{
     if (!out) return BZ_E_PARAM;
     *out = nullptr;
     if (kind < 0 || kind > 2) return BZ_E_PARAM;
+    if (df_dict_param(kind, dict, dict_len) != BZ_OK) return BZ_E_PARAM;
     if (count && (!ins || !lens || !out_off || !out_len)) return BZ_E_PARAM;
     const BatchLayout lay(ins, lens, count, 16);
     if (lay.status != BZ_OK) return lay.status;
@@ -808,7 +875,8 @@ extern "C" int df_encode_batch(int kind, int device, const uint8_t *const *ins, 
     if (rc == BZ_OK && lay.total && hipMemcpy(g->dec_in.p, packed.data(), (size_t)lay.total, hipMemcpyHostToDevice) != hipSuccess)
         rc = BZ_E_UNEXPECTED;
     if (rc == BZ_OK)
-        rc = df_gpu_encode_batch_device(g, kind, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), count, g->oneshot_out.p, cap, out_off, out_len);
+        rc = df_gpu_encode_batch_device_dict(g, kind, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), count, dict, dict_len, g->oneshot_out.p,
+                                             cap, out_off, out_len);
     if (rc == BZ_OK) rc = df_download(out, g->oneshot_out.p, (size_t)(out_off[count - 1] + ((out_len[count - 1] + 3u) & ~(u64)3)));
     lease.settle(rc);
     return rc;
@@ -1171,12 +1239,6 @@ static void df_inf_stats_add(DfWorkspace *w, const DfInfRec &r)
     w->inf_stats[6] += (r.end_bit + 7u) >> 3;
 }
 
-// the parameter errors of a dictionary, the same in every form: a length without a pointer, and gzip (GZipDecoder has no with_dict)
-static int df_decode_dict_param(int kind, const uint8_t *dict, size_t dict_len)
-{
-    return dict_len && (!dict || kind == 2) ? BZ_E_PARAM : BZ_OK;
-}
-
 // The window of a call: the last min(dict_len, 32768) bytes of the dictionary, uploaded into the workspace (once per call, not
 // kept: 32 KiB), and the Adler-32 of the WHOLE dictionary (adler32.rs:20-66), which is what a zlib header's DICTID holds.
 static int df_decode_window(bz_gpu_engine *g, DfWorkspace *w, const uint8_t *dict, size_t dict_len, DfWindow &win)
@@ -1187,19 +1249,9 @@ static int df_decode_window(bz_gpu_engine *g, DfWorkspace *w, const uint8_t *dic
     int rc = w->i_dict.ensure(32768);
     if (rc != BZ_OK) return rc;
     HIPCHK(hipMemcpyAsync(w->i_dict.p, dict + (dict_len - W), W, hipMemcpyHostToDevice, g->st));
-    u32 a = 1, b = 0;
-    for (size_t i = 0; i < dict_len;) { // (5552 bytes keep b below 2^32: the largest n with 255 n (n + 1) / 2 + (n + 1) 65520 < 2^32)
-        const size_t end = std::min(dict_len, i + 5552);
-        for (; i < end; ++i) {
-            a += dict[i];
-            b += a;
-        }
-        a %= 65521;
-        b %= 65521;
-    }
     win.p = w->i_dict.as<u8>();
     win.W = W;
-    win.adler = (b << 16) | a;
+    win.adler = df_adler32_host(dict, dict_len);
     return BZ_OK;
 }
 
@@ -1209,7 +1261,7 @@ static int df_decode_batch_core(bz_gpu_engine *g, int kind, const void *d_in, co
                                 uint64_t *h_out_len, int32_t *h_verdict)
 {
     if (!g || kind < 0 || kind > 2) return BZ_E_PARAM;
-    if (df_decode_dict_param(kind, dict, dict_len) != BZ_OK) return BZ_E_PARAM;
+    if (df_dict_param(kind, dict, dict_len) != BZ_OK) return BZ_E_PARAM;
     if (count == 0) return BZ_OK;
     if (!h_in_off || !h_in_len || !h_out_off || !h_out_len || !h_verdict || count > 0x7FFFFFFFu) return BZ_E_PARAM;
     if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u)) return BZ_E_PARAM;
@@ -1303,7 +1355,7 @@ extern "C" int df_decode_batch_dict(int kind, int device, const uint8_t *const *
     if (!out) return BZ_E_PARAM;
     *out = nullptr;
     if (kind < 0 || kind > 2) return BZ_E_PARAM;
-    if (df_decode_dict_param(kind, dict, dict_len) != BZ_OK) return BZ_E_PARAM;
+    if (df_dict_param(kind, dict, dict_len) != BZ_OK) return BZ_E_PARAM;
     if (count && (!ins || !lens || !out_off || !out_len || !verdict)) return BZ_E_PARAM;
     const BatchLayout lay(ins, lens, count, 4);
     if (lay.status != BZ_OK) return lay.status;

@@ -108,17 +108,20 @@ int df_launch_emit(hipStream_t st, const u8 *in, const u32 *code, const u64 *bst
 // ---- many inputs in one pass (df_gpu_encode_batch_device): every input of at most kBlockMax bytes is one block of its own.
 // The inputs of a sub-batch lie in one IMAGE, each in a SLOT that starts at a multiple of kPTile (an input of 0 bytes has
 // one tile too); tile_slot[t] = the slot that tile t of the image belongs to.
+// With a preset dictionary every slot has `wtiles` = ceil(W / kPTile) WINDOW TILES in front of `lo`, which belong to it in
+// tile_slot: the dictionary's last W bytes at [lo - W, lo), zeros in front of them.  `win` (device memory) holds that window
+// right-aligned in kWin bytes, zeros in front of it; win == nullptr, W == 0, wtiles == 0: no dictionary, the kernels of old.
 struct DfSlot {
     u64 src;  // where the input lies, relative to the caller's buffer
-    u32 lo;   // the slot's first image position
+    u32 lo;   // the input's first image position
     u32 len;  // bytes of the input: the rest of the slot's last tile is a gap of zeros
 };
 struct DfBatchOut { u32 off, len; }; // a stream inside the sub-batch's output (off: a multiple of 4)
-int df_launch_gather(hipStream_t st, const u8 *d_in, const DfSlot *slots, const u32 *tile_slot, u32 ntiles, u8 *image);
-int df_launch_match2_batch(hipStream_t st, const u8 *image, u64 n, const u32 *s, u32 *M, const u32 *tile_slot, const DfSlot *slots);
-// the parse of every slot: entered at offset 0 of its first tile, tile after tile (no entry crosses a slot)
-int df_launch_parse_batch(hipStream_t st, const u32 *M, u64 n, u32 ntiles, const DfSlot *slots, u32 nslots, u16 *step, u16 *tab,
-                          u16 *ent, u32 *code, u64 *bm, u64 *canon);
+int df_launch_gather(hipStream_t st, const u8 *d_in, const DfSlot *slots, const u32 *tile_slot, u32 ntiles, u8 *image, const u8 *win);
+int df_launch_match2_batch(hipStream_t st, const u8 *image, u64 n, const u32 *s, u32 *M, const u32 *tile_slot, const DfSlot *slots, u32 W);
+// the parse of every slot: entered at offset 0 of its first input tile, tile after tile (no entry crosses a slot)
+int df_launch_parse_batch(hipStream_t st, const u32 *M, u64 n, u32 ntiles, const DfSlot *slots, u32 nslots, u32 wtiles, u16 *step,
+                          u16 *tab, u16 *ent, u32 *code, u64 *bm, u64 *canon);
 // bse: (start, end) of block j = slot j; every block is the final block of its stream
 int df_launch_blocks_batch(hipStream_t st, const u8 *image, const u32 *code, const u64 *bse, const u32 *nb, u32 nslots, DfBlock *blocks,
                            u8 *lens, u32 *hdr, u32 *lm_scratch);
@@ -130,8 +133,9 @@ struct DfCrcShifts { u32 x[8]; }; // x^(8 * 256 * 2^k) mod P, reflected: moves a
 int df_launch_sums(hipStream_t st, const u8 *in, u64 n, u64 *asum, u64 *bsum, u32 *crc, u32 *last_sub, DfCrcShifts xk);
 // container header and trailer of every stream, written on the device (kind 1: Adler-32, kind 2: CRC-32 + ISIZE), and
 // what kinds of blocks there were: stats[0..4] += stored, fixed, dynamic, limited tables, dynamic without distances
+// with_dict (kind 1): the six-byte header with FDICT and `dictid`, the Adler-32 of the whole dictionary
 int df_launch_batch_wrap(hipStream_t st, const u8 *image, const DfSlot *slots, u32 nslots, const DfBlock *blocks, const DfBatchOut *outs,
-                         int kind, DfCrcShifts xk, u8 *out, u32 *stats);
+                         int kind, DfCrcShifts xk, u8 *out, u32 *stats, bool with_dict, u32 dictid);
 // ---- decode of many streams (df_gpu_decode_batch_device; k_inflate.hip): what the sizes launch leaves per entry
 struct DfInfRec {
     u64 end_bit;  // bits of the entry consumed: to the end of the stream or its trailer, or to the failing code

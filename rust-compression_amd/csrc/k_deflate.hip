@@ -517,11 +517,16 @@ __device__ __forceinline__ u32 df_diff16(df_u32x4 x, df_u32x4 y)
 // front of the slot's start ends the chain like the start of the chunk does (the window and the 255 candidates then
 // count own candidates only); the text ends at the input's end; positions without a trigram inside their input (its
 // last two bytes, the gap behind it) have no candidates at all and get "no match".
-template <bool BATCH>
+// DICT (df_gpu_encode_batch_device_dict): the last W bytes of a preset dictionary lie in front of every input, at
+// image[lo - W, lo) -- df_encode_core's history, once per slot.  The chain then ends at the first candidate in front of
+// lo - W: own candidates first, the window's behind them, window and 255 candidates counted together; the entries of the
+// window itself (and of the zeros in front of it) are candidates only and get "no match" without a step.
+template <bool BATCH, bool DICT = false>
 __global__ __launch_bounds__(kM2Threads) void k_df_match2(const u8 *__restrict__ in, u64 n, u64 ntri, const u32 *__restrict__ S,
                                                           u32 *__restrict__ M, const u32 *__restrict__ tile_slot,
-                                                          const DfSlot *__restrict__ slots)
+                                                          const DfSlot *__restrict__ slots, u32 W)
 {
+    static_assert(BATCH || !DICT, "the window in front of a slot is a form of the batch kernel");
     typedef df_u32x4 u32x4;
     __shared__ u32x4 s_snip[kM2Hist + kM2Threads];
     __shared__ u32 s_pos[kM2Hist + kM2Threads];
@@ -570,13 +575,15 @@ __global__ __launch_bounds__(kM2Threads) void k_df_match2(const u8 *__restrict__
     const u32 p = s_pos[li], h = s_key[li];
     const u32x4 a = s_snip[li];
     const bool own = i0 + tid < count && (u64)p >= (u64)c * kChunk; // a history entry is written by the chunk that owns it
-    u32 slo = 0, tend = n32; // BATCH: the entry's input is image[slo, tend)
+    u32 slo = 0, tend = n32; // BATCH: the entry's input is image[lo, tend), its candidates lie in image[slo, p)
+    bool live = own;
     if (BATCH) {
         const DfSlot sl = slots[tile_slot[p / kPTile]];
-        slo = sl.lo;
+        slo = DICT ? sl.lo - W : sl.lo;
         tend = sl.lo + sl.len;
+        live = own && p + kMinMatch <= tend; // (its trigram lies inside its input)
+        if (DICT) live = live && p >= sl.lo;
     }
-    const bool live = BATCH ? (own && p + kMinMatch <= tend) : own; // (its trigram lies inside its input)
     // chain length: the entries in front with the same hash and within the window form one run (monotone in j)
     u32 e = 0;
     if (live && s_key[li - 1] == h && p - s_pos[li - 1] <= kWin && (!BATCH || s_pos[li - 1] >= slo)) {
@@ -1930,17 +1937,19 @@ int df_launch_match2(hipStream_t st, const u8 *in, u64 n, const u32 *s, u32 *M)
     DFCHK(hipMemsetAsync(M + ntri, 0, (n - ntri + 8) * sizeof(u32), st)); // the last two positions have no trigram
     if (!ntri) return 0;
     hipLaunchKernelGGL((k_df_match2<false>), dim3(df_chunks(n) * kM2Span), dim3(kM2Threads), 0, st, in, n, ntri, s, M, (const u32 *)nullptr,
-                       (const DfSlot *)nullptr);
+                       (const DfSlot *)nullptr, 0u);
     return 0;
 }
 
-int df_launch_match2_batch(hipStream_t st, const u8 *image, u64 n, const u32 *s, u32 *M, const u32 *tile_slot, const DfSlot *slots)
+int df_launch_match2_batch(hipStream_t st, const u8 *image, u64 n, const u32 *s, u32 *M, const u32 *tile_slot, const DfSlot *slots, u32 W)
 {
     if (!n) return 0;
     const u64 ntri = n >= 3 ? n - 2 : 0;
     DFCHK(hipMemsetAsync(M + ntri, 0, (n - ntri + 8) * sizeof(u32), st));
     if (!ntri) return 0;
-    hipLaunchKernelGGL((k_df_match2<true>), dim3(df_chunks(n) * kM2Span), dim3(kM2Threads), 0, st, image, n, ntri, s, M, tile_slot, slots);
+    const dim3 grid(df_chunks(n) * kM2Span);
+    if (W) hipLaunchKernelGGL((k_df_match2<true, true>), grid, dim3(kM2Threads), 0, st, image, n, ntri, s, M, tile_slot, slots, W);
+    else hipLaunchKernelGGL((k_df_match2<true>), grid, dim3(kM2Threads), 0, st, image, n, ntri, s, M, tile_slot, slots, 0u);
     return 0;
 }
 
@@ -2125,6 +2134,10 @@ int df_launch_part_tail(hipStream_t st, const DfBlock *blocks, const u64 *bstart
 // the chunk sort as it is (its order is (hash, position), whoever owns the position), k_df_match2<true> with the
 // slot rules, k_df_adv / k_df_tile_orbit / k_df_mark2 as they are (a gap holds "no match", so no step crosses an input's
 // end and a slot is entered at offset 0 of its first tile), k_df_block<true> / k_df_emit<true> with one block per slot.
+// With a preset dictionary (df_gpu_encode_batch_device_dict) a slot has ceil(W / kPTile) WINDOW TILES in front of its input
+// tiles: the dictionary's last W bytes end where the input starts (DfSlot::lo stays the input's first position), zeros in
+// front of them.  k_df_gather_dict fills them, k_df_match2<true, true> takes candidates from them, k_df_slot_entries<true>
+// keeps the marking kernel out of them; blocks, emission and checksums see [lo, lo + len) as before.
 
 // one workgroup per tile of the image, 16 bytes per thread: the input's bytes, zeros behind its end
 __global__ __launch_bounds__(256) void k_df_gather(const u8 *__restrict__ d_in, const DfSlot *__restrict__ slots,
@@ -2141,15 +2154,45 @@ __global__ __launch_bounds__(256) void k_df_gather(const u8 *__restrict__ d_in, 
         for (u32 b = 0; off + b < sl.len; ++b) dst[b] = d_in[sl.src + off + b];
 }
 
+// The same with window tiles: `win` is the dictionary's window right-aligned in kWin bytes, zeros in front of it, so
+// the image byte d positions in front of the input (d <= kWin: a slot has at most kWin / kPTile window tiles) is
+// win[kWin - d] whether it lies in the window or in front of it, and 16 of them are one aligned load.
+__global__ __launch_bounds__(256) void k_df_gather_dict(const u8 *__restrict__ d_in, const DfSlot *__restrict__ slots,
+                                                        const u32 *__restrict__ tile_slot, u8 *__restrict__ image,
+                                                        const u8 *__restrict__ win)
+{
+    const u32 tile = blockIdx.x;
+    const DfSlot sl = slots[tile_slot[tile]];
+    const u32 q = tile * kPTile + threadIdx.x * 16u; // image position
+    u8 *dst = image + (size_t)q;
+    df_u32x4 v = {0, 0, 0, 0};
+    if (q < sl.lo) { // a window tile (lo and q are multiples of 16)
+        const u32 d = sl.lo - q;
+        if (d <= kWin) v = *reinterpret_cast<const df_u32x4 *>(win + (kWin - d));
+        *reinterpret_cast<df_u32x4 *>(dst) = v;
+        return;
+    }
+    const u32 off = q - sl.lo; // offset inside the input
+    if (off + 16u <= sl.len) v = *reinterpret_cast<const df_u32x4 *>(d_in + sl.src + off); // (src is a multiple of 16)
+    *reinterpret_cast<df_u32x4 *>(dst) = v;
+    if (off < sl.len && off + 16u > sl.len) // the input ends inside these 16 bytes: nothing behind its end is read
+        for (u32 b = 0; off + b < sl.len; ++b) dst[b] = d_in[sl.src + off + b];
+}
+
 // entry offset of every tile of a slot: 0 for the first one, the exit of tile t for tile t + 1 (k_df_compose /
 // k_df_resolve of the one-stream path; a slot has at most 16 tiles)
+// DICT: the slot's `wtiles` window tiles, in front of sl.lo, are entered at kPTile -- behind their end: k_df_mark2 then
+// finds no step in them and writes neither code words nor bits (nothing reads either in front of an input).
+template <bool DICT>
 __global__ __launch_bounds__(64) void k_df_slot_entries(const DfSlot *__restrict__ slots, u32 nslots, const u16 *__restrict__ tab,
-                                                        u16 *__restrict__ ent)
+                                                        u16 *__restrict__ ent, u32 wtiles)
 {
     const u32 j = blockIdx.x * 64 + threadIdx.x;
     if (j >= nslots) return;
     const DfSlot sl = slots[j];
     const u32 t0 = sl.lo / kPTile, nt = sl.len ? (sl.len + kPTile - 1) / kPTile : 1u;
+    if (DICT)
+        for (u32 t = 1; t <= wtiles; ++t) ent[t0 - t] = (u16)kPTile;
     u32 v = 0;
     for (u32 t = 0; t < nt; ++t) {
         ent[t0 + t] = (u16)v;
@@ -2195,9 +2238,13 @@ __global__ __launch_bounds__(256) void k_df_batch_offsets(DfBlock *__restrict__ 
 // The input's full 256-byte pieces go to the LAST threads (piece j of m to thread 256 - m + j), so that the fold of
 // k_df_sums applies whatever m is: the threads in front hold a zero register, which stays zero; thread 0 (an input has
 // at most 255 full pieces) takes the bytes behind the last full piece.
+// DICT (kind 1 only): the header is 78 F9 and DICTID, the Adler-32 of the whole dictionary (zlib/encoder.rs:74-93); the
+// trailer's checksum covers the input alone, as without one.
+template <bool DICT>
 __global__ __launch_bounds__(256) void k_df_batch_wrap(const u8 *__restrict__ image, const DfSlot *__restrict__ slots,
                                                        const DfBlock *__restrict__ blocks, const DfBatchOut *__restrict__ outs,
-                                                       int kind, DfCrcShifts xk, u8 *__restrict__ out, u32 *__restrict__ stats)
+                                                       int kind, DfCrcShifts xk, u8 *__restrict__ out, u32 *__restrict__ stats,
+                                                       u32 dictid)
 {
     __shared__ u32 s_tab[256];
     __shared__ u64 s_a[256], s_b[256];
@@ -2260,7 +2307,8 @@ __global__ __launch_bounds__(256) void k_df_batch_wrap(const u8 *__restrict__ im
         for (u32 t = 0; t < 256; ++t) { sa += s_a[t]; sb += s_b[t]; }
         const u32 A = (u32)((1 + sa) % 65521), B = (u32)((len + sb) % 65521); // adler32.rs:20-66 from (1, 0)
         const u32 h = (B << 16) | A;
-        p[0] = 0x78; p[1] = 0xDA;
+        p[0] = 0x78; p[1] = DICT ? 0xF9 : 0xDA;
+        if (DICT) { p[2] = (u8)(dictid >> 24); p[3] = (u8)(dictid >> 16); p[4] = (u8)(dictid >> 8); p[5] = (u8)dictid; }
         u8 *t = p + o.len - 4;
         t[0] = (u8)(h >> 24); t[1] = (u8)(h >> 16); t[2] = (u8)(h >> 8); t[3] = (u8)h;
     } else {
@@ -2272,20 +2320,22 @@ __global__ __launch_bounds__(256) void k_df_batch_wrap(const u8 *__restrict__ im
     }
 }
 
-int df_launch_gather(hipStream_t st, const u8 *d_in, const DfSlot *slots, const u32 *tile_slot, u32 ntiles, u8 *image)
+int df_launch_gather(hipStream_t st, const u8 *d_in, const DfSlot *slots, const u32 *tile_slot, u32 ntiles, u8 *image, const u8 *win)
 {
-    hipLaunchKernelGGL(k_df_gather, dim3(ntiles), dim3(256), 0, st, d_in, slots, tile_slot, image);
+    if (win) hipLaunchKernelGGL(k_df_gather_dict, dim3(ntiles), dim3(256), 0, st, d_in, slots, tile_slot, image, win);
+    else hipLaunchKernelGGL(k_df_gather, dim3(ntiles), dim3(256), 0, st, d_in, slots, tile_slot, image);
     DFCHK(hipMemsetAsync(image + (size_t)ntiles * kPTile, 0, 64, st));
     return 0;
 }
 
-int df_launch_parse_batch(hipStream_t st, const u32 *M, u64 n, u32 ntiles, const DfSlot *slots, u32 nslots, u16 *step, u16 *tab,
-                          u16 *ent, u32 *code, u64 *bm, u64 *canon)
+int df_launch_parse_batch(hipStream_t st, const u32 *M, u64 n, u32 ntiles, const DfSlot *slots, u32 nslots, u32 wtiles, u16 *step,
+                          u16 *tab, u16 *ent, u32 *code, u64 *bm, u64 *canon)
 {
     DFCHK(hipMemsetAsync(bm, 0, ((n + 63) / 64 + 2) * sizeof(u64), st));
     hipLaunchKernelGGL(k_df_adv, dim3((u32)((n + 1023) / 1024)), dim3(256), 0, st, M, n, step);
     hipLaunchKernelGGL(k_df_tile_orbit, dim3(ntiles), dim3(kOrbThreads), 0, st, step, n, tab, canon);
-    hipLaunchKernelGGL(k_df_slot_entries, dim3((nslots + 63) / 64), dim3(64), 0, st, slots, nslots, tab, ent);
+    if (wtiles) hipLaunchKernelGGL((k_df_slot_entries<true>), dim3((nslots + 63) / 64), dim3(64), 0, st, slots, nslots, tab, ent, wtiles);
+    else hipLaunchKernelGGL((k_df_slot_entries<false>), dim3((nslots + 63) / 64), dim3(64), 0, st, slots, nslots, tab, ent, 0u);
     hipLaunchKernelGGL(k_df_mark2, dim3(ntiles), dim3(kMark2Threads), 0, st, step, M, ent, tab, canon, n, code, bm, 0u);
     return 0;
 }
@@ -2312,9 +2362,11 @@ int df_launch_emit_batch(hipStream_t st, const u8 *image, const u32 *code, const
 }
 
 int df_launch_batch_wrap(hipStream_t st, const u8 *image, const DfSlot *slots, u32 nslots, const DfBlock *blocks, const DfBatchOut *outs,
-                         int kind, DfCrcShifts xk, u8 *out, u32 *stats)
+                         int kind, DfCrcShifts xk, u8 *out, u32 *stats, bool with_dict, u32 dictid)
 {
-    hipLaunchKernelGGL(k_df_batch_wrap, dim3(nslots), dim3(256), 0, st, image, slots, blocks, outs, kind, xk, out, stats);
+    if (with_dict && kind == 1)
+        hipLaunchKernelGGL((k_df_batch_wrap<true>), dim3(nslots), dim3(256), 0, st, image, slots, blocks, outs, kind, xk, out, stats, dictid);
+    else hipLaunchKernelGGL((k_df_batch_wrap<false>), dim3(nslots), dim3(256), 0, st, image, slots, blocks, outs, kind, xk, out, stats, 0u);
     return 0;
 }
 

@@ -257,6 +257,34 @@ template <int Kind> class DeflateFamilyEncoder {
         return Result<uint8_t>::Ok(buf_[pos_++]);
     }
 
+    // Many independent inputs in one call (df_encode_batch): element i of the result is the stream this encoder makes of
+    // inputs[i] with Action::Finish, bit for bit; inputs of at most 65 535 bytes are encoded together.  `inputs`: any range
+    // of byte ranges with data() and size().
+    template <class Spans> static Result<std::vector<std::vector<uint8_t>>> encode_batch(const Spans &inputs, int device = 0)
+    {
+        return encode_batch(inputs, nullptr, 0, device);
+    }
+    // ... with one preset dictionary for every input (df_encode_batch_dict): the streams of ::with_dict encoders
+    template <class Spans>
+    static Result<std::vector<std::vector<uint8_t>>> encode_batch(const Spans &inputs, const uint8_t *dict, size_t dict_len, int device = 0)
+    {
+        using R = Result<std::vector<std::vector<uint8_t>>>;
+        std::vector<const uint8_t *> ptrs;
+        std::vector<size_t> lens;
+        for (const auto &x : inputs) {
+            ptrs.push_back(reinterpret_cast<const uint8_t *>(x.data()));
+            lens.push_back(x.size());
+        }
+        std::vector<uint64_t> off(ptrs.size()), len(ptrs.size());
+        uint8_t *out = nullptr;
+        const int rc = df_encode_batch_dict(Kind, device, ptrs.data(), lens.data(), ptrs.size(), dict, dict_len, &out, off.data(), len.data());
+        if (rc != BZ_OK) return R::Err(from_status(rc));
+        std::vector<std::vector<uint8_t>> streams(ptrs.size());
+        for (size_t i = 0; i < ptrs.size(); ++i) streams[i].assign(out + off[i], out + off[i] + len[i]);
+        bz_free(out);
+        return R::Ok(std::move(streams));
+    }
+
   private:
     int refill()
     {

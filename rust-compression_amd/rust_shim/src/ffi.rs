@@ -55,6 +55,8 @@ extern "C" {
     pub fn df_gpu_encode_batch_device(g: *mut c_void, kind: i32, d_in: *const c_void, h_in_off: *const u64, h_in_len: *const u64, count: usize, d_out: *mut c_void, cap: usize, h_out_off: *mut u64, h_out_len: *mut u64) -> i32;
     pub fn df_gpu_last_batch_stats(g: *mut c_void, out: *mut u64) -> i32;
     pub fn df_encode_batch(kind: i32, device: i32, ins: *const *const u8, lens: *const usize, count: usize, out: *mut *mut u8, out_off: *mut u64, out_len: *mut u64) -> i32;
+    pub fn df_gpu_encode_batch_device_dict(g: *mut c_void, kind: i32, d_in: *const c_void, h_in_off: *const u64, h_in_len: *const u64, count: usize, dict: *const u8, dict_len: usize, d_out: *mut c_void, cap: usize, h_out_off: *mut u64, h_out_len: *mut u64) -> i32;
+    pub fn df_encode_batch_dict(kind: i32, device: i32, ins: *const *const u8, lens: *const usize, count: usize, dict: *const u8, dict_len: usize, out: *mut *mut u8, out_off: *mut u64, out_len: *mut u64) -> i32;
 
     // section 5: Deflater / ZlibDecoder / GZipDecoder (many streams in one call; *out is released with bz_free)
     pub fn df_gpu_decode_batch_device(g: *mut c_void, kind: i32, d_in: *const c_void, h_in_off: *const u64, h_in_len: *const u64, count: usize, d_out: *mut c_void, cap: usize, h_out_off: *mut u64, h_out_len: *mut u64, h_verdict: *mut i32) -> i32;

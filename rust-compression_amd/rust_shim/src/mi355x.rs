@@ -80,7 +80,15 @@ pub fn encode_batch(level: usize, inputs: &[&[u8]]) -> Result<Vec<Vec<u8>>, Comp
 /// `GZipEncoder`) collects, bit for bit.  Inputs of at most 65 535 bytes are one block for certain and are encoded together,
 /// however many there are.  Panics on a kind outside 0..=2.
 pub fn deflate_encode_batch(kind: usize, inputs: &[&[u8]]) -> Result<Vec<Vec<u8>>, CompressionError> {
+    deflate_encode_batch_dict(kind, inputs, &[])
+}
+
+/// The same with one preset dictionary for every input (`df_encode_batch_dict`): element `i` is the stream of
+/// `Inflater::with_dict(dict)` / `ZlibEncoder::with_dict(dict)` over `inputs[i]`.  An empty dictionary is none.  Panics on
+/// a kind outside 0..=2 and on gzip with a dictionary (`GZipEncoder` has no `with_dict`).
+pub fn deflate_encode_batch_dict(kind: usize, inputs: &[&[u8]], dict: &[u8]) -> Result<Vec<Vec<u8>>, CompressionError> {
     assert!(kind <= 2, "invalid kind");
+    assert!(kind != 2 || dict.is_empty(), "gzip takes no preset dictionary");
     let ptrs: Vec<*const u8> = inputs.iter().map(|x| x.as_ptr()).collect();
     let lens: Vec<usize> = inputs.iter().map(|x| x.len()).collect();
     let mut off: Vec<u64> = Vec::new();
@@ -88,7 +96,9 @@ pub fn deflate_encode_batch(kind: usize, inputs: &[&[u8]]) -> Result<Vec<Vec<u8>
     let mut len = off.clone();
     let mut out: *mut u8 = core::ptr::null_mut();
     let rc = unsafe {
-        ffi::df_encode_batch(kind as i32, 0, ptrs.as_ptr(), lens.as_ptr(), inputs.len(), &mut out, off.as_mut_ptr(), len.as_mut_ptr())
+        ffi::df_encode_batch_dict(
+            kind as i32, 0, ptrs.as_ptr(), lens.as_ptr(), inputs.len(), dict.as_ptr(), dict.len(), &mut out, off.as_mut_ptr(), len.as_mut_ptr(),
+        )
     };
     if rc != ffi::BZ_OK {
         note_status(rc);

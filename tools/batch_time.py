@@ -29,6 +29,15 @@ path inside the batch call and is the control; corpus16k takes the batch path.  
 df_gpu_last_timings and df_gpu_last_batch_stats of one df_gpu_encode_batch_device call over the same inputs in HBM.
 BZ_DF_BATCH_MIB sets the sub-batch size.
 
+    tools/batch_time.py --deflate --dict-kib N [--kind deflate|zlib] [--workload ...]
+
+Encoding with a preset dictionary of N KiB of another chapter of the bench corpus: one df_encode_batch_dict call
+(deflate_compress_batch(.., dict_=)) against the loop of df_encode_buffer_dict calls over the same inputs (the parent
+commit's code), both host to host, and -- the control -- the batch call WITHOUT a dictionary over the same inputs; the three
+alternate within every run.  The streams of batch and loop are compared byte for byte before anything is timed.  The line
+also carries, per form ("dict", "plain"), `calls` df_gpu_encode_batch_device_dict calls over the inputs in HBM, alternating
+the forms call by call: wall time, df_gpu_last_timings, df_gpu_last_batch_stats, and the stream bytes.
+
     tools/batch_time.py --inflate [--kind deflate|zlib|gzip] [--workload ...|text64m] [--runs 3] [--calls 5] [--loops 3]
 
 The same workloads, compressed once with deflate_compress_batch: one df_decode_batch call (deflate_decompress_batch), host
@@ -41,8 +50,8 @@ df_gpu_last_decode_batch_stats.  text64m is ONE entry of 64 MiB of the bench cor
     tools/batch_time.py --inflate --dict-kib N [--kind deflate|zlib] [--workload ...]
 
 Decoding with a preset dictionary (section 5, clause (c) of the header): the dictionary is N KiB of another chapter of the
-bench corpus, the streams are zlib's (level 6) -- made once with zdict= and once without, since the batched encoder takes no
-dictionary.  Per form ("dict", "plain"), in the same run and alternating: deflate_decompress_batch host to host, the loop
+bench corpus, the streams are zlib's (level 6) -- made once with zdict= and once without -- and the project's own
+(deflate_compress_batch(.., dict_=)).  Per form ("dict", "plain", "own_dict"), in the same run and alternating: deflate_decompress_batch host to host, the loop
 of zlib.decompressobj(wbits, zdict=) on one host thread, and one deflate_decode_batch_device call over the streams in HBM
 with its launches' times.  With --inflate-one the ONE stream is zlib's, made with the dictionary; --inflate-one --zlib-made
 is its control: zlib's stream of the same bytes without a dictionary.
@@ -185,6 +194,8 @@ def deflate_mode(pkg, a, names):
         finally:
             eng.close()
 
+    if a.dict_kib:
+        return deflate_dict_mode(pkg, a, names, kind)
     for name in names:
         datas = workload(name)
         total = sum(len(d) for d in datas)
@@ -212,6 +223,84 @@ def deflate_mode(pkg, a, names):
                           "batch_GBps": round(total / bm / 1e6, 3), "loop_GBps": round(total / lm / 1e6, 3),
                           "device_call_ms": wall_ms, "device_call_stage_ms": stage_ms, "device_call_batch_stats": stats,
                           "runs": runs}), flush=True)
+        if not same:
+            raise SystemExit("batch_time.py: the batch's streams differ from the loop's")
+
+
+def deflate_dict_mode(pkg, a, names, kind):
+    import torch
+    L = pkg.lib()
+    if kind == pkg.GZIP:
+        raise SystemExit("batch_time.py: gzip takes no dictionary")
+    dict_ = bench_dictionary(a.dict_kib)
+
+    def loop(datas):
+        out = []
+        for d in datas:
+            p, n = C.POINTER(C.c_uint8)(), C.c_size_t(0)
+            rc = L.df_encode_buffer_dict(kind, 0, d, len(d), dict_, len(dict_), C.byref(p), C.byref(n))
+            if rc != 0:
+                raise SystemExit("df_encode_buffer_dict: %d" % rc)
+            out.append(C.string_at(p, n.value))
+            L.bz_free(p)
+        return out
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        fn()
+        return time.perf_counter() - t0
+
+    for name in names:
+        datas = workload(name)
+        total = sum(len(d) for d in datas)
+        forms = {"dict": dict_, "plain": b""}
+        streams = {f: pkg.deflate_compress_batch(datas, kind, dict_=d) for f, d in forms.items()}   # (warms the engine's workspace too)
+        same = streams["dict"] == loop(datas)
+        runs = []
+        for _ in range(a.runs):
+            t = {"dict": [], "plain": [], "loop": []}
+            for _ in range(a.calls):
+                for f, d in forms.items():
+                    t[f].append(timed(lambda: pkg.deflate_compress_batch(datas, kind, dict_=d)))
+            for _ in range(a.loops):
+                t["loop"].append(timed(lambda: loop(datas)))
+            runs.append({k + "_ms": round(statistics.median(v) * 1e3, 2) for k, v in t.items()})
+            runs[-1].update({k + "_all_ms": [round(x * 1e3, 2) for x in v] for k, v in t.items()})
+        med = {k: statistics.median(r[k + "_ms"] for r in runs) for k in ("dict", "plain", "loop")}
+        # the inputs in HBM: the two forms alternating call by call on one engine
+        off, buf = [], bytearray()
+        for d in datas:
+            off.append(len(buf))
+            buf += d
+            buf += bytes(-len(buf) % 16)
+        lens = [len(d) for d in datas]
+        tin = torch.frombuffer(buf + bytes(16), dtype=torch.uint8).cuda()
+        cap = pkg.deflate_encode_batch_bound(lens)
+        o = torch.empty((cap + 64,), dtype=torch.uint8, device="cuda")
+        eng = pkg.GpuEngine(0, 1)
+        dev = {f: {"wall_ms": [], "stage_ms": []} for f in forms}
+        try:
+            call = lambda d: eng.deflate_encode_batch_device(kind, tin.data_ptr(), off, lens, o.data_ptr(), cap, dict_=d)
+            for d in forms.values():
+                call(d)   # (warm)
+            for _ in range(a.calls):
+                for f, d in forms.items():
+                    dev[f]["wall_ms"].append(round(timed(lambda: call(d)) * 1e3, 3))
+                    dev[f]["stage_ms"].append({k: round(v * 1e3, 3) for k, v in eng.deflate_timings().items()})
+                    dev[f]["batch_stats"] = eng.deflate_batch_stats()
+        finally:
+            eng.close()
+        line = {"mode": "deflate-dict", "kind": a.kind, "workload": name, "dict_kib": a.dict_kib, "inputs": len(datas), "bytes": total,
+                "batch_mib": os.environ.get("BZ_DF_BATCH_MIB", "default"), "streams_equal": same,
+                "batch_dict_ms": med["dict"], "batch_plain_ms": med["plain"], "loop_dict_ms": med["loop"],
+                "loop_over_batch": round(med["loop"] / med["dict"], 2), "dict_over_plain": round(med["dict"] / med["plain"], 2), "runs": runs}
+        for f in forms:
+            w = dev[f]["wall_ms"]
+            line[f] = {"compressed_bytes": sum(len(z) for z in streams[f]), "device_call_ms": statistics.median(w), "device_call_all_ms": w,
+                       "device_call_stage_ms": {k: statistics.median(x[k] for x in dev[f]["stage_ms"]) for k in dev[f]["stage_ms"][0]},
+                       "device_call_batch_stats": dev[f]["batch_stats"]}
+        line["device_dict_over_plain"] = round(line["dict"]["device_call_ms"] / line["plain"]["device_call_ms"], 2)
+        print(json.dumps(line), flush=True)
         if not same:
             raise SystemExit("batch_time.py: the batch's streams differ from the loop's")
 
@@ -308,6 +397,7 @@ def inflate_dict_mode(pkg, a, names, kind, wbits, loop, device_call):
                 c = zlib.compressobj(6, zlib.DEFLATED, wbits, zdict=d) if d else zlib.compressobj(6, zlib.DEFLATED, wbits)
                 streams.append(c.compress(x) + c.flush())
             forms[form] = (d, streams)
+        forms["own_dict"] = (dict_, pkg.deflate_compress_batch(datas, kind, dict_=dict_))
         same = all(pkg.deflate_decompress_batch(z, kind, dict_=d) == [(x, 0) for x in datas] and loop(z, d) == datas for d, z in forms.values())
         times = {form: {"batch": [], "zlib_loop": []} for form in forms}
         for _ in range(a.runs):
@@ -415,7 +505,7 @@ def main():
     ap.add_argument("--inflate-one", type=float, default=0, metavar="SIZE_MIB", help="time ONE Deflate stream of that many MiB of text")
     ap.add_argument("--one-wave", action="store_true", help="--inflate-one: one more call on the one-wave path")
     ap.add_argument("--zlib-made", action="store_true", help="--inflate-one: the stream is zlib's (level 6), the control of --dict-kib")
-    ap.add_argument("--dict-kib", type=int, default=0, metavar="N", help="--inflate / --inflate-one: zlib's streams, made with a dictionary of N KiB")
+    ap.add_argument("--dict-kib", type=int, default=0, metavar="N", help="--deflate / --inflate / --inflate-one: with a preset dictionary of N KiB")
     ap.add_argument("--kind", default="deflate", choices=["deflate", "zlib", "gzip"])
     ap.add_argument("--decode", action="store_true", help="time decompress_batch against a loop of bz_decode_buffer")
     ap.add_argument("--workload", default="all")
