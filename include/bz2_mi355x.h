@@ -898,6 +898,57 @@ int df_gpu_last_decode_members_timings(bz_gpu_engine *g, double out_seconds[4]);
  * with bz_free.  in_len == 0: BZ_OK, an empty buffer, no device is touched.  Without a GPU: BZ_E_NOGPU. */
 int df_decode_members_buffer(int device, const uint8_t *in, size_t in_len, uint8_t **out, size_t *out_len);
 
+/* ========================================================================
+ * 7. WRITING BGZF (the blocked gzip of .bam, .vcf.gz and bgzip; SAM
+ *    specification section 4.1): one contiguous input as a series of gzip
+ *    members of at most 65 280 input bytes each -- the file that section 6
+ *    decodes member-parallel and that htslib seeks in.  The reference has no
+ *    such writer; its GZipEncoder (section 4) writes one member.
+ *
+ * THE FILE.  With B = block_bytes (0 means DF_BGZF_BLOCK; any value from 1 to
+ * 65 280, not only multiples of 16), block k holds the input bytes
+ * [k * B, min(n, (k + 1) * B)).  The file is the blocks in order, byte against
+ * byte, no padding; with eof != 0 the standard 28-byte EOF marker follows
+ * (1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 1b 00 03 00 and eight zero
+ * bytes).  n == 0 writes the marker alone, or nothing.
+ *
+ * A BLOCK is the 18-byte header 1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6,
+ * 42 43 02 00, BSIZE = block length - 1 (little-endian u16); then ONE final
+ * Deflate block; then CRC-32 and ISIZE of the block's input, little endian.
+ * The Deflate block is, bit for bit, the reference's one-block stream of that
+ * input alone (section 4, kind 0: window, chains and matches inside the block,
+ * as in the batch path) with one exception, THE STRICT RULE: where the reference
+ * chooses a dynamic block although the block has no match, it writes HDIST = 0
+ * and no distance code length (df_gpu_last_stats [6]), which zlib and section 5
+ * refuse.  Such a block -- literals only -- is written stored if
+ * 8 * len + 34 <= fixed, otherwise fixed, where fixed = 2 + the fixed code lengths
+ * of its literals + 7 for the end-of-block code.  Every Deflate block is at most
+ * len + 5 bytes, so a block is at most len + 31 bytes and BSIZE fits.
+ * ======================================================================== */
+#define DF_BGZF_BLOCK 65280u          /* htslib's block size, the default and the maximum */
+size_t df_bgzf_block_count(size_t n, uint32_t block_bytes);      /* ceil(n / B); 0 for n == 0 */
+size_t df_bgzf_bound(size_t n, uint32_t block_bytes, int eof);   /* n + 31 * count + (eof ? 28 : 0) */
+/* d_in[n] (HBM, 16-byte aligned; nothing at or behind d_in + n is read) -> the file at d_out (HBM, any alignment):
+ * *out_len bytes.  h_block_off, when not NULL, receives count + 1 file offsets: entry k is where block k starts, the last
+ * one where the EOF marker starts (*out_len when there is none) -- with k * B beside it the .gzi table, and the coffset
+ * half of a virtual offset.  The blocks go through the batch pipeline of section 4 in sub-batches of BZ_DF_BATCH_MIB
+ * (default 64 MiB of 4 KiB-aligned slots: 1 024 blocks of 65 280 bytes), each placed at the running byte total; n is a
+ * size_t and the offsets are 64-bit.  BZ_E_PARAM: a null engine or out_len, d_in null with n > 0 or not 16-byte aligned,
+ * block_bytes > 65 280; BZ_E_CAPACITY: the file does not fit in cap (df_bgzf_bound always suffices).  Nothing at or
+ * behind d_out + cap is ever written, and on success nothing at or behind d_out + *out_len. */
+int df_gpu_bgzf_encode_device(bz_gpu_engine *g, const void *d_in, size_t n, uint32_t block_bytes, int eof,
+                              void *d_out, size_t cap, uint64_t *out_len, uint64_t *h_block_off);
+/* The last df_gpu_bgzf_encode_device call: [0] blocks (the marker not counted) [1] sub-batches, and of the blocks
+ * [2] stored [3] fixed [4] dynamic [5] tables on the length-limited path [6] blocks the strict rule replaced
+ * [7] file bytes.  After such a call df_gpu_last_timings holds the stages summed over the sub-batches. */
+int df_gpu_last_bgzf_stats(bz_gpu_engine *g, uint64_t out[8]);
+/* Host to host: one upload, one device call on an engine of the per-process cache, one download; *out is malloc'ed,
+ * release with bz_free; block_off (may be NULL) as h_block_off above.  The parameters are checked before any device is
+ * touched (BZ_E_PARAM: a null out or out_len, in null with n > 0, block_bytes > 65 280), then BZ_E_NOGPU without a
+ * GPU.  n == 0: BZ_OK with the marker or an empty buffer, no device is touched. */
+int df_bgzf_encode_buffer(int device, const uint8_t *in, size_t n, uint32_t block_bytes, int eof,
+                          uint8_t **out, size_t *out_len, uint64_t *block_off);
+
 #ifdef __cplusplus
 }
 #endif

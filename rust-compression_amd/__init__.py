@@ -29,7 +29,7 @@ import sys
 from . import _build
 
 __all__ = ["Action", "CompressionError", "BZip2Error", "BZip2Encoder", "BZip2Decoder", "encode", "decode",
-           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "deflate_decompress", "deflate_decompress_batch", "Deflater", "ZlibDecoder", "GZipDecoder", "gzip_decompress_members", "MultiGZipDecoder", "GpuEngine", "release_cached_resources", "last_call_phases",
+           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "deflate_decompress", "deflate_decompress_batch", "Deflater", "ZlibDecoder", "GZipDecoder", "gzip_decompress_members", "MultiGZipDecoder", "bgzf_compress", "bgzf_bound", "bgzf_block_count", "GpuEngine", "release_cached_resources", "last_call_phases",
            "build", "lib", "device_count", "encode_bound", "shard_window", "rccl_lib", "rccl_unique_id", "RcclComm"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -101,6 +101,7 @@ EXPORTS = [
     "df_gpu_decode_batch_device", "df_gpu_last_decode_batch_stats", "df_gpu_last_decode_split_stats", "df_gpu_last_decode_split_timings", "df_decode_batch", "df_decode_buffer",
     "df_gpu_decode_batch_device_dict", "df_decode_batch_dict", "df_decode_buffer_dict",
     "df_gpu_decode_members_device", "df_gpu_last_decode_members_stats", "df_gpu_last_decode_members_timings", "df_decode_members_buffer",
+    "df_bgzf_block_count", "df_bgzf_bound", "df_gpu_bgzf_encode_device", "df_gpu_last_bgzf_stats", "df_bgzf_encode_buffer",
 ]
 
 
@@ -264,6 +265,13 @@ def lib():
     L.df_gpu_last_decode_members_stats.argtypes = [vp, u64p]
     L.df_gpu_last_decode_members_timings.argtypes = [vp, C.POINTER(C.c_double)]
     L.df_decode_members_buffer.argtypes = [C.c_int, C.c_char_p, sz, C.POINTER(u8p), szp]
+    L.df_bgzf_block_count.restype = sz
+    L.df_bgzf_block_count.argtypes = [sz, C.c_uint32]
+    L.df_bgzf_bound.restype = sz
+    L.df_bgzf_bound.argtypes = [sz, C.c_uint32, C.c_int]
+    L.df_gpu_bgzf_encode_device.argtypes = [vp, vp, sz, C.c_uint32, C.c_int, vp, sz, u64p, u64p]
+    L.df_gpu_last_bgzf_stats.argtypes = [vp, u64p]
+    L.df_bgzf_encode_buffer.argtypes = [C.c_int, C.c_char_p, sz, C.c_uint32, C.c_int, C.POINTER(u8p), szp, u64p]
     L.df_decode_buffer.argtypes = [C.c_int, C.c_int, C.c_char_p, sz, C.POINTER(u8p), szp]
     L.df_gpu_decode_batch_device_dict.argtypes = [vp, C.c_int, vp, u64p, u64p, sz, C.c_char_p, sz, vp, sz, u64p, u64p, i32p]
     L.df_decode_batch_dict.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, sz, C.c_char_p, sz, C.POINTER(u8p), u64p, u64p, i32p]
@@ -720,6 +728,43 @@ def deflate_compress_batch(datas, kind=DEFLATE, device=0, dict_=b""):
     return _batch_call(lib().df_encode_batch_dict, (kind, device), datas, False, (dict_, len(dict_)))
 
 
+BGZF_BLOCK = 65280  # DF_BGZF_BLOCK: htslib's block size, the default and the maximum
+
+
+def _bgzf_block_bytes(block_bytes):
+    if not 0 <= block_bytes <= BGZF_BLOCK:
+        raise ValueError("bgzf: block_bytes is 0 (the default, 65 280) or 1 .. 65 280")
+    return block_bytes
+
+
+def bgzf_block_count(n, block_bytes=0):
+    """Blocks of a BGZF file of n input bytes (df_bgzf_block_count): ceil(n / B), the EOF marker not counted."""
+    return lib().df_bgzf_block_count(n, _bgzf_block_bytes(block_bytes))
+
+
+def bgzf_bound(n, block_bytes=0, eof=True):
+    """An output capacity that always suffices for GpuEngine.bgzf_encode_device (df_bgzf_bound)."""
+    return lib().df_bgzf_bound(n, _bgzf_block_bytes(block_bytes), 1 if eof else 0)
+
+
+def bgzf_compress(data, block_bytes=0, eof=True, device=0, offsets=False):
+    """One input as a BGZF file (df_bgzf_encode_buffer): gzip members of at most block_bytes (default 65 280) input bytes,
+    side by side, then the 28-byte EOF marker unless eof is false.  Every member decodes with zlib / gzip / htslib.
+    offsets=True: -> (file, offsets), count + 1 file offsets: where block k starts, and last where the marker starts."""
+    data = bytes(data)
+    block_bytes = _bgzf_block_bytes(block_bytes)
+    out = C.POINTER(C.c_uint8)()
+    n = C.c_size_t(0)
+    k = (len(data) + (block_bytes or BGZF_BLOCK) - 1) // (block_bytes or BGZF_BLOCK)
+    offs = (C.c_uint64 * (k + 1))()
+    _check(lib().df_bgzf_encode_buffer(device, data, len(data), block_bytes, 1 if eof else 0, C.byref(out), C.byref(n), offs))
+    try:
+        z = C.string_at(out, n.value)
+    finally:
+        lib().bz_free(out)
+    return (z, [int(x) for x in offs]) if offsets else z
+
+
 _DECODER_VERDICTS = (BZ_E_DATA, BZ_E_MAGIC_FIRST, BZ_E_MAGIC)
 
 
@@ -1166,6 +1211,25 @@ class GpuEngine:
         the block counts are those of the batch-path inputs."""
         s = (C.c_uint64 * 8)()
         _check(lib().df_gpu_last_batch_stats(self._h, s))
+        return [int(x) for x in s]
+
+    BGZF_STATS = ("blocks", "sub_batches", "stored", "fixed", "dynamic", "limited_tables", "strict_replaced", "file_bytes")
+
+    def bgzf_encode_device(self, d_in, n, d_out, cap, block_bytes=0, eof=True, offsets=False):
+        """The n bytes at d_in (16-byte aligned) as a BGZF file at d_out, any alignment (df_gpu_bgzf_encode_device); returns
+        the file's length, or with offsets=True (length, offsets): count + 1 file offsets, where block k starts and last
+        where the EOF marker starts.  block_bytes outside 0 .. 65 280 is the C call's BZ_E_PARAM."""
+        _settle()
+        out_len = C.c_uint64(0)
+        k = bgzf_block_count(n, block_bytes) if 0 <= block_bytes <= BGZF_BLOCK else 0
+        offs = (C.c_uint64 * (k + 1))()
+        _check(lib().df_gpu_bgzf_encode_device(self._h, d_in, n, block_bytes, 1 if eof else 0, d_out, cap, C.byref(out_len), offs))
+        return (out_len.value, [int(x) for x in offs]) if offsets else out_len.value
+
+    def bgzf_stats(self):
+        """The last bgzf_encode_device call, in the order of BGZF_STATS (df_gpu_last_bgzf_stats)."""
+        s = (C.c_uint64 * 8)()
+        _check(lib().df_gpu_last_bgzf_stats(self._h, s))
         return [int(x) for x in s]
 
     DEFLATE_DECODE_BATCH_STATS = ("clean", "errors", "stored", "fixed", "dynamic", "decoded_bytes", "consumed_bytes", "launches")

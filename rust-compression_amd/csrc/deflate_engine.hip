@@ -29,6 +29,7 @@ struct DfWorkspace {
     DevBuf b_slots, b_tile_slot, b_bse, b_outs, b_stats; // a sub-batch of df_gpu_encode_batch_device: slot tables, block ends, streams' places
     DevBuf b_win;                                      // ... and the window of a call with a preset dictionary (uploaded per call)
     u64 batch_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // df_gpu_last_batch_stats
+    u64 bgzf_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // df_gpu_last_bgzf_stats
     DevBuf i_in, i_ooff, i_rec;                        // df_gpu_decode_batch_device: the entries' ranges, their outputs' places, their records
     DevBuf i_dict;                                     // ... and the window of a call with a preset dictionary (uploaded per call)
     u64 inf_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // df_gpu_last_decode_batch_stats
@@ -632,9 +633,12 @@ static int df_batch_window(bz_gpu_engine *g, DfWorkspace *w, const uint8_t *dict
 
 // inputs [first, first + ns) of the call, all of at most kBlockMax bytes, ntiles tiles together (window tiles included); their
 // streams go to d_out + cursor .. in input order, *used = bytes taken there (a multiple of 4)
+// bgzf (df_gpu_bgzf_encode_device; kind 2, no dictionary): the inputs are cuts of one buffer at any byte offset, the streams are
+// BGZF blocks side by side without padding (*used is their bytes, d_out + cursor has any alignment) and no block is a dynamic
+// one without a match; the block kinds are counted into bgzf_stats[2..6]
 static int df_batch_run(bz_gpu_engine *g, int kind, const u8 *d_in, const uint64_t *h_in_off, const uint64_t *h_in_len, size_t first,
                         u32 ns, u32 ntiles, const DfBatchDict &bd, u8 *d_out, size_t cap, u64 cursor, uint64_t *h_out_off,
-                        uint64_t *h_out_len, u64 *used, double t_acc[6])
+                        uint64_t *h_out_len, u64 *used, double t_acc[6], bool bgzf = false)
 {
     DfWorkspace *w = g->df;
     hipStream_t st = g->st;
@@ -653,7 +657,7 @@ static int df_batch_run(bz_gpu_engine *g, int kind, const u8 *d_in, const uint64
             bse[2 * (size_t)j] = slots[j].lo;
             bse[2 * (size_t)j + 1] = slots[j].lo + n;
             for (u32 k = bd.wtiles + df_slot_tiles(n); k; --k) tile_slot[t++] = j;
-            bound += (df_encode_bound((size_t)n) + 3u) & ~(size_t)3;
+            bound += bgzf ? (size_t)n + 31u : (df_encode_bound((size_t)n) + 3u) & ~(size_t)3;
         }
     }
     int rc;
@@ -671,7 +675,7 @@ static int df_batch_run(bz_gpu_engine *g, int kind, const u8 *d_in, const uint64
     const DfSlot *d_slots = w->b_slots.as<DfSlot>();
     const u32 *d_tile_slot = w->b_tile_slot.as<u32>();
     const u64 *d_bse = w->b_bse.as<u64>();
-    const u32 head = kind == 1 ? (bd.W ? 6u : 2u) : (kind == 2 ? 10u : 0u), tail = kind == 1 ? 4u : (kind == 2 ? 8u : 0u);
+    const u32 head = bgzf ? 18u : kind == 1 ? (bd.W ? 6u : 2u) : (kind == 2 ? 10u : 0u), tail = kind == 1 ? 4u : (kind == 2 ? 8u : 0u);
     const u32 ns_word = ns;
     // (the host arrays live on this stack frame: the wait below)
     HIPCHK(hipMemcpyAsync(w->b_slots.p, slots.data(), (size_t)ns * sizeof(DfSlot), hipMemcpyHostToDevice, st));
@@ -681,7 +685,9 @@ static int df_batch_run(bz_gpu_engine *g, int kind, const u8 *d_in, const uint64
     HIPCHK(hipMemsetAsync(w->b_stats.p, 0, 64, st));
     HIPCHK(hipEventRecord(w->ev[0], st));
     HIPCHK(hipMemsetAsync(w->stream.p, 0, bound + 64, st));
-    if (df_launch_gather(st, d_in, d_slots, d_tile_slot, ntiles, image, bd.d_win) != 0) return BZ_E_UNEXPECTED;
+    if ((bgzf ? df_launch_gather_cut(st, d_in, d_slots, d_tile_slot, ntiles, image)
+              : df_launch_gather(st, d_in, d_slots, d_tile_slot, ntiles, image, bd.d_win)) != 0)
+        return BZ_E_UNEXPECTED;
     if (df_launch_chains(st, image, nimg, w->vals_in.as<u32>(), w->vals_out.as<u32>(), nullptr, w->sort_tmp.as<u32>(), w->keys_out.as<u32>(),
                          nullptr) != 0)
         return BZ_E_UNEXPECTED;
@@ -692,17 +698,20 @@ static int df_batch_run(bz_gpu_engine *g, int kind, const u8 *d_in, const uint64
                               code, w->bitmap.as<u64>(), w->canon.as<u64>()) != 0)
         return BZ_E_UNEXPECTED;
     HIPCHK(hipEventRecord(w->ev[3], st));
-    if (df_launch_blocks_batch(st, image, code, d_bse, w->nb.as<u32>(), ns, w->blocks.as<DfBlock>(), w->lens.as<u8>(), w->hdr.as<u32>(),
-                               w->lm.as<u32>()) != 0)
+    if ((bgzf ? df_launch_blocks_strict : df_launch_blocks_batch)(st, image, code, d_bse, w->nb.as<u32>(), ns, w->blocks.as<DfBlock>(),
+                                                                  w->lens.as<u8>(), w->hdr.as<u32>(), w->lm.as<u32>()) != 0)
         return BZ_E_UNEXPECTED;
-    if (df_launch_batch_offsets(st, w->blocks.as<DfBlock>(), ns, head, tail, w->b_outs.as<DfBatchOut>(), w->total.as<u64>()) != 0)
+    if ((bgzf ? df_launch_exact_offsets : df_launch_batch_offsets)(st, w->blocks.as<DfBlock>(), ns, head, tail, w->b_outs.as<DfBatchOut>(),
+                                                                   w->total.as<u64>()) != 0)
         return BZ_E_UNEXPECTED;
     HIPCHK(hipEventRecord(w->ev[4], st));
     if (df_launch_emit_batch(st, image, code, d_bse, w->nb.as<u32>(), ns, w->blocks.as<DfBlock>(), w->lens.as<u8>(), w->hdr.as<u32>(),
                              w->stream.as<u32>()) != 0)
         return BZ_E_UNEXPECTED;
-    if (df_launch_batch_wrap(st, image, d_slots, ns, w->blocks.as<DfBlock>(), w->b_outs.as<DfBatchOut>(), kind, df_crc_shifts(), w->stream.as<u8>(),
-                             w->b_stats.as<u32>(), bd.W != 0, bd.dictid) != 0)
+    if ((bgzf ? df_launch_bgzf_wrap(st, image, d_slots, ns, w->blocks.as<DfBlock>(), w->b_outs.as<DfBatchOut>(), df_crc_shifts(),
+                                    w->stream.as<u8>(), w->b_stats.as<u32>())
+              : df_launch_batch_wrap(st, image, d_slots, ns, w->blocks.as<DfBlock>(), w->b_outs.as<DfBatchOut>(), kind, df_crc_shifts(),
+                                     w->stream.as<u8>(), w->b_stats.as<u32>(), bd.W != 0, bd.dictid)) != 0)
         return BZ_E_UNEXPECTED;
     HIPCHK(hipEventRecord(w->ev[5], st));
     std::vector<DfBatchOut> outs(ns);
@@ -721,7 +730,7 @@ static int df_batch_run(bz_gpu_engine *g, int kind, const u8 *d_in, const uint64
         h_out_off[first + j] = cursor + outs[j].off;
         h_out_len[first + j] = outs[j].len;
     }
-    for (int i = 0; i < 5; ++i) w->batch_stats[3 + i] += bst[i];
+    for (int i = 0; i < 5; ++i) (bgzf ? w->bgzf_stats[2 + i] : w->batch_stats[3 + i]) += bst[i];
     HIPCHK(hipStreamSynchronize(st)); // (the workspace is free for the next sub-batch, the events are over)
     df_stage_times(w, t_acc, true);
     *used = total;
@@ -821,6 +830,92 @@ extern "C" int df_gpu_encode_batch_device_dict(bz_gpu_engine *g, int kind, const
     return BZ_OK;
 }
 
+// ---- a BGZF file (section 7 of the header): the batch path over cuts of one contiguous input --------------------------
+// Block k is the bytes [k * B, min(n, (k + 1) * B)) and a gzip member of its own: the 18-byte BGZF header, one final Deflate
+// block, CRC-32 and ISIZE.  The members of a sub-batch come out of df_batch_run side by side, without padding, and are placed
+// at the running byte total; the EOF marker follows the last one.
+static const u8 kBgzfEof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+static int df_bgzf_params(size_t n, const void *in, uint32_t block_bytes)
+{
+    return block_bytes > DF_BGZF_BLOCK || (n && !in) ? BZ_E_PARAM : BZ_OK;
+}
+
+extern "C" size_t df_bgzf_block_count(size_t n, uint32_t block_bytes)
+{
+    const size_t B = block_bytes && block_bytes <= DF_BGZF_BLOCK ? block_bytes : DF_BGZF_BLOCK;
+    return n / B + (n % B ? 1 : 0);
+}
+
+extern "C" size_t df_bgzf_bound(size_t n, uint32_t block_bytes, int eof)
+{
+    return n + 31 * df_bgzf_block_count(n, block_bytes) + (eof ? sizeof kBgzfEof : 0);
+}
+
+extern "C" int df_gpu_last_bgzf_stats(bz_gpu_engine *g, uint64_t out[8])
+{
+    if (!g || !out) return BZ_E_PARAM;
+    for (int i = 0; i < 8; ++i) out[i] = g->df ? g->df->bgzf_stats[i] : 0;
+    return BZ_OK;
+}
+
+extern "C" int df_gpu_bgzf_encode_device(bz_gpu_engine *g, const void *d_in, size_t n, uint32_t block_bytes, int eof, void *d_out,
+                                         size_t cap, uint64_t *out_len, uint64_t *h_block_off)
+{
+    if (!g || !out_len || df_bgzf_params(n, d_in, block_bytes) != BZ_OK || ((uintptr_t)d_in & 15u)) return BZ_E_PARAM;
+    const size_t marker = eof ? sizeof kBgzfEof : 0;
+    if ((n || marker) && !d_out) return cap ? BZ_E_PARAM : BZ_E_CAPACITY;
+    DfWorkspace *w = nullptr;
+    const int wrc = df_workspace(g, &w);
+    if (wrc != BZ_OK) return wrc;
+    for (u64 &s : w->bgzf_stats) s = 0;
+    const u64 B = block_bytes ? block_bytes : DF_BGZF_BLOCK;
+    const u64 count = df_bgzf_block_count(n, block_bytes);
+    const u8 *in8 = static_cast<const u8 *>(d_in);
+    u8 *out8 = static_cast<u8 *>(d_out);
+    const u64 image_max = df_batch_image_bytes();
+    const u32 slot_tiles = df_slot_tiles(B); // (the last block may take fewer)
+    const DfBatchDict bd;
+    std::vector<uint64_t> in_off, in_len, o_off, o_len;
+    double t_acc[6] = {0, 0, 0, 0, 0, 0};
+    u64 cursor = 0;
+    for (u64 k = 0; k < count;) {
+        u64 ns = std::max<u64>(1, image_max / ((u64)slot_tiles * kPTile));
+        ns = std::min<u64>(std::min<u64>(ns, kBatchSlots), count - k);
+        in_off.resize(ns); in_len.resize(ns); o_off.resize(ns); o_len.resize(ns);
+        u64 tiles = 0;
+        for (u64 j = 0; j < ns; ++j) {
+            in_off[j] = (k + j) * B;
+            in_len[j] = std::min<u64>(B, n - in_off[j]);
+            tiles += df_slot_tiles(in_len[j]);
+        }
+        u64 used = 0;
+        const int rc = df_batch_run(g, 2, in8, in_off.data(), in_len.data(), 0, (u32)ns, (u32)tiles, bd, out8, cap, cursor, o_off.data(),
+                                    o_len.data(), &used, t_acc, true);
+        if (rc != BZ_OK) return rc;
+        if (h_block_off)
+            for (u64 j = 0; j < ns; ++j) h_block_off[k + j] = o_off[j];
+        cursor += used;
+        w->bgzf_stats[1] += 1;
+        k += ns;
+    }
+    if (cursor + marker > cap) return BZ_E_CAPACITY;
+    if (marker) HIPCHK(hipMemcpyAsync(out8 + cursor, kBgzfEof, marker, hipMemcpyHostToDevice, g->st));
+    HIPCHK(hipStreamSynchronize(g->st));
+    if (h_block_off) h_block_off[count] = cursor;
+    w->bgzf_stats[0] = count;
+    w->bgzf_stats[7] = cursor + marker;
+    *out_len = cursor + marker;
+    if (count) { // df_gpu_last_timings: the stages of the batch path, summed over the sub-batches
+        for (int i = 0; i < 6; ++i) w->t_stage[i] = t_acc[i];
+        w->h_nb = 0; // (df_gpu_debug_blocks describes one-stream calls)
+        w->h_fetched = true;
+        w->h_blocks.clear();
+        w->h_bstart.assign(1, 0);
+    }
+    return BZ_OK;
+}
+
 // ---- the host-to-host forms: an engine of the cache for the length of the call (EngineLease, host_call.h) ----------
 // A device number out of range is BZ_E_NOGPU for the entry points that ask here first (df_encode_batch, df_decode_batch and
 // with it df_decode_buffer, df_enc_create); the others pass on what bz_gpu_engine_create answers (BZ_E_PARAM).
@@ -878,6 +973,40 @@ extern "C" int df_encode_batch_dict(int kind, int device, const uint8_t *const *
         rc = df_gpu_encode_batch_device_dict(g, kind, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), count, dict, dict_len, g->oneshot_out.p,
                                              cap, out_off, out_len);
     if (rc == BZ_OK) rc = df_download(out, g->oneshot_out.p, (size_t)(out_off[count - 1] + ((out_len[count - 1] + 3u) & ~(u64)3)));
+    lease.settle(rc);
+    return rc;
+}
+
+// A BGZF file from host memory: one upload, df_gpu_bgzf_encode_device on an engine of the cache, one download.
+extern "C" int df_bgzf_encode_buffer(int device, const uint8_t *in, size_t n, uint32_t block_bytes, int eof, uint8_t **out, size_t *out_len,
+                                     uint64_t *block_off)
+{
+    if (!out) return BZ_E_PARAM;
+    *out = nullptr;
+    if (!out_len || df_bgzf_params(n, in, block_bytes) != BZ_OK) return BZ_E_PARAM;
+    *out_len = 0;
+    if (n == 0) { // the marker alone, or nothing: no device is touched
+        const size_t m = eof ? sizeof kBgzfEof : 0;
+        uint8_t *h = (uint8_t *)malloc(m ? m : 1);
+        if (!h) return BZ_E_NOMEM;
+        memcpy(h, kBgzfEof, m);
+        if (block_off) block_off[0] = 0;
+        *out = h;
+        *out_len = m;
+        return BZ_OK;
+    }
+    if (df_device_in_range(device) != BZ_OK) return BZ_E_NOGPU;
+    EngineLease lease(device, 2, 1);
+    if (lease.status() != BZ_OK) return lease.status();
+    bz_gpu_engine *g = lease.engine();
+    const size_t cap = df_bgzf_bound(n, block_bytes, eof);
+    uint64_t total = 0;
+    int rc = g->dec_in.ensure(n + 64);
+    if (rc == BZ_OK) rc = g->oneshot_out.ensure(cap + 64);
+    if (rc == BZ_OK && hipMemcpy(g->dec_in.p, in, n, hipMemcpyHostToDevice) != hipSuccess) rc = BZ_E_UNEXPECTED;
+    if (rc == BZ_OK) rc = df_gpu_bgzf_encode_device(g, g->dec_in.p, n, block_bytes, eof, g->oneshot_out.p, cap, &total, block_off);
+    if (rc == BZ_OK) rc = df_download(out, g->oneshot_out.p, (size_t)total);
+    if (rc == BZ_OK) *out_len = (size_t)total;
     lease.settle(rc);
     return rc;
 }

@@ -136,6 +136,17 @@ int df_launch_sums(hipStream_t st, const u8 *in, u64 n, u64 *asum, u64 *bsum, u3
 // with_dict (kind 1): the six-byte header with FDICT and `dictid`, the Adler-32 of the whole dictionary
 int df_launch_batch_wrap(hipStream_t st, const u8 *image, const DfSlot *slots, u32 nslots, const DfBlock *blocks, const DfBatchOut *outs,
                          int kind, DfCrcShifts xk, u8 *out, u32 *stats, bool with_dict, u32 dictid);
+// ---- a BGZF file (df_gpu_bgzf_encode_device): the batch pipeline over cuts of one contiguous input.  The slots' sources
+// start at any byte (df_launch_gather_cut); a dynamic block without any match is never written (df_launch_blocks_strict:
+// stored or fixed instead, DfBlock::lm bit 9); the members lie byte against byte (df_launch_exact_offsets: outs[j].off is
+// any byte offset); df_launch_bgzf_wrap writes the 18-byte header with BSIZE and the gzip trailer, and counts
+// stats[0..4] += stored, fixed, dynamic, limited tables, blocks the strict rule replaced.
+int df_launch_gather_cut(hipStream_t st, const u8 *d_in, const DfSlot *slots, const u32 *tile_slot, u32 ntiles, u8 *image);
+int df_launch_blocks_strict(hipStream_t st, const u8 *image, const u32 *code, const u64 *bse, const u32 *nb, u32 nslots, DfBlock *blocks,
+                            u8 *lens, u32 *hdr, u32 *lm_scratch);
+int df_launch_exact_offsets(hipStream_t st, DfBlock *blocks, u32 nslots, u32 head, u32 tail, DfBatchOut *outs, u64 *total);
+int df_launch_bgzf_wrap(hipStream_t st, const u8 *image, const DfSlot *slots, u32 nslots, const DfBlock *blocks, const DfBatchOut *outs,
+                        DfCrcShifts xk, u8 *out, u32 *stats);
 // ---- decode of many streams (df_gpu_decode_batch_device; k_inflate.hip): what the sizes launch leaves per entry
 struct DfInfRec {
     u64 end_bit;  // bits of the entry consumed: to the end of the stream or its trailer, or to the failing code

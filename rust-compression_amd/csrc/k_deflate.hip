@@ -1469,7 +1469,9 @@ __device__ __forceinline__ u32 df_tab_runs(const u8 *tab, u32 n, u8 *ls, u8 *le,
 
 // one workgroup per Deflate block: symbol counts, the three tables, the header, the choice of block type
 // BATCH: block k is bstart[2k] .. bstart[2k + 1] (slot k of the image) and the final block of a stream of its own
-template <bool BATCH>
+// STRICT (the BGZF writer): a dynamic block without any match -- which the reference writes with HDIST = 0 and no distance
+// code length, and every RFC 1951 decoder refuses -- is written stored or fixed instead, whichever is shorter (lm bit 9)
+template <bool BATCH, bool STRICT>
 __global__ __launch_bounds__(kBThreads) void k_df_block(const u8 *__restrict__ in, const u32 *__restrict__ code,
                                                         const u64 *__restrict__ bstart, const u32 *__restrict__ nb_p,
                                                         DfBlock *__restrict__ blocks, u8 *__restrict__ lens,
@@ -1624,6 +1626,11 @@ __global__ __launch_bounds__(kBThreads) void k_df_block(const u8 *__restrict__ i
         o.lm = s_lm + lm2;
         if (original <= custom && original <= fixed) { o.btype = 0; o.hdr_bits = 3; o.bits = 0; s_hdr[0] = is_final ? 1u : 0u; }
         else if (fixed <= custom) { o.btype = 1; o.hdr_bits = 3; o.bits = 1 + fixed; s_hdr[0] = (is_final ? 1u : 0u) | 2u; }
+        else if (STRICT && off_n == 0) { // literals only: both forms are plain, and either is at most dlen + 5 bytes
+            o.lm |= 0x200u;
+            if (original <= fixed) { o.btype = 0; o.hdr_bits = 3; o.bits = 0; s_hdr[0] = is_final ? 1u : 0u; }
+            else { o.btype = 1; o.hdr_bits = 3; o.bits = 1 + fixed; s_hdr[0] = (is_final ? 1u : 0u) | 2u; }
+        }
         else { o.btype = 2; o.hdr_bits = hdr_bits; o.bits = 1 + custom; if (off_n == 0) o.lm |= 0x100u; } // no distance code at all
         blocks[k] = o;
         s_btype = o.btype;
@@ -2014,7 +2021,7 @@ u32 df_cut_pieces(u32 ntiles) { return ntiles < kCutPieces * 64 ? 1u : kCutPiece
 int df_launch_blocks_piece(hipStream_t st, const u8 *in, const u32 *code, u64 *bstart, u32 *nb, u32 cap, DfBlock *blocks, u8 *lens,
                            u32 *hdr, u32 *lm_scratch, u32 dl0, u32 last_is_final, const u32 *kr, u32 piece_last)
 {
-    hipLaunchKernelGGL((k_df_block<false>), dim3(cap), dim3(kBThreads), 0, st, in, code, bstart, nb, blocks, lens, hdr, lm_scratch, dl0,
+    hipLaunchKernelGGL((k_df_block<false, false>), dim3(cap), dim3(kBThreads), 0, st, in, code, bstart, nb, blocks, lens, hdr, lm_scratch, dl0,
                        last_is_final, kr, piece_last);
     return 0;
 }
@@ -2027,7 +2034,7 @@ int df_launch_block_offsets(hipStream_t st, DfBlock *blocks, const u32 *nb, u64 
 int df_launch_blocks(hipStream_t st, const u8 *in, const u32 *code, u64 *bstart, u32 *nb, u32 cap,
                      DfBlock *blocks, u8 *lens, u32 *hdr, u32 *lm_scratch, u64 *total_bits, u32 dl0, u32 last_is_final, u32 bit0)
 {
-    hipLaunchKernelGGL((k_df_block<false>), dim3(cap), dim3(kBThreads), 0, st, in, code, bstart, nb, blocks, lens, hdr, lm_scratch, dl0,
+    hipLaunchKernelGGL((k_df_block<false, false>), dim3(cap), dim3(kBThreads), 0, st, in, code, bstart, nb, blocks, lens, hdr, lm_scratch, dl0,
                        last_is_final, (const u32 *)nullptr, 1u);
     hipLaunchKernelGGL(k_df_offsets, dim3(1), dim3(256), 0, st, blocks, nb, total_bits, bit0);
     return 0;
@@ -2154,6 +2161,23 @@ __global__ __launch_bounds__(256) void k_df_gather(const u8 *__restrict__ d_in, 
         for (u32 b = 0; off + b < sl.len; ++b) dst[b] = d_in[sl.src + off + b];
 }
 
+// The same for slots that are cuts of one contiguous input (df_gpu_bgzf_encode_device): src is any byte offset, so the 16
+// bytes of a thread come from one unaligned load (global_load_dwordx4 takes any address on gfx950; the match kernel reads
+// its snippets the same way) and go out as the aligned store of k_df_gather.  Nothing at or behind src + len is read.
+__global__ __launch_bounds__(256) void k_df_gather_cut(const u8 *__restrict__ d_in, const DfSlot *__restrict__ slots,
+                                                       const u32 *__restrict__ tile_slot, u8 *__restrict__ image)
+{
+    const u32 tile = blockIdx.x;
+    const DfSlot sl = slots[tile_slot[tile]];
+    const u32 off = tile * kPTile - sl.lo + threadIdx.x * 16u; // offset inside the input
+    u8 *dst = image + (size_t)tile * kPTile + threadIdx.x * 16u;
+    df_u32x4 v = {0, 0, 0, 0};
+    if (off + 16u <= sl.len) v = *reinterpret_cast<const df_u32x4u *>(d_in + sl.src + off);
+    *reinterpret_cast<df_u32x4 *>(dst) = v;
+    if (off < sl.len && off + 16u > sl.len) // the input ends inside these 16 bytes: nothing behind its end is read
+        for (u32 b = 0; off + b < sl.len; ++b) dst[b] = d_in[sl.src + off + b];
+}
+
 // The same with window tiles: `win` is the dictionary's window right-aligned in kWin bytes, zeros in front of it, so
 // the image byte d positions in front of the input (d <= kWin: a slot has at most kWin / kPTile window tiles) is
 // win[kWin - d] whether it lies in the window or in front of it, and 16 of them are one aligned load.
@@ -2208,6 +2232,10 @@ __device__ __forceinline__ u32 df_stream_bytes(const DfBlock &b, u32 head, u32 t
     return head + body + tail;
 }
 
+// PAD: every stream at a multiple of 4 (the batch calls); !PAD: byte against byte (the members of a BGZF file).  Emission
+// ORs its bits atomically into zeroed words at any bit offset and writes a stored block byte by byte, and two blocks'
+// bodies are head + tail >= 26 bytes apart: no word of the output belongs to two blocks of the emit launch.
+template <bool PAD>
 __global__ __launch_bounds__(256) void k_df_batch_offsets(DfBlock *__restrict__ blocks, u32 nslots, u32 head, u32 tail,
                                                           DfBatchOut *__restrict__ outs, u64 *__restrict__ total)
 {
@@ -2215,7 +2243,7 @@ __global__ __launch_bounds__(256) void k_df_batch_offsets(DfBlock *__restrict__ 
     const u32 tid = threadIdx.x;
     const u32 per = (nslots + 255u) / 256u, j0 = tid * per, j1 = (j0 + per < nslots) ? j0 + per : nslots;
     u64 sum = 0;
-    for (u32 j = j0; j < j1; ++j) sum += (df_stream_bytes(blocks[j], head, tail) + 3u) & ~3u;
+    for (u32 j = j0; j < j1; ++j) sum += PAD ? (df_stream_bytes(blocks[j], head, tail) + 3u) & ~3u : df_stream_bytes(blocks[j], head, tail);
     s_sum[tid] = sum;
     __syncthreads();
     if (tid == 0) {
@@ -2230,7 +2258,7 @@ __global__ __launch_bounds__(256) void k_df_batch_offsets(DfBlock *__restrict__ 
         outs[j].off = (u32)off;
         outs[j].len = len;
         blocks[j].bit_off = (off + head) * 8u;
-        off += (len + 3u) & ~3u;
+        off += PAD ? (len + 3u) & ~3u : len;
     }
 }
 
@@ -2240,7 +2268,9 @@ __global__ __launch_bounds__(256) void k_df_batch_offsets(DfBlock *__restrict__ 
 // at most 255 full pieces) takes the bytes behind the last full piece.
 // DICT (kind 1 only): the header is 78 F9 and DICTID, the Adler-32 of the whole dictionary (zlib/encoder.rs:74-93); the
 // trailer's checksum covers the input alone, as without one.
-template <bool DICT>
+// BGZF (kind 2 only): the member's header is the 18 bytes of a BGZF block -- FLG.FEXTRA, XLEN 6, the subfield `BC` with
+// BSIZE = the member's length - 1 -- and stats[4] counts the blocks that k_df_block<true, true> replaced.
+template <bool DICT, bool BGZF>
 __global__ __launch_bounds__(256) void k_df_batch_wrap(const u8 *__restrict__ image, const DfSlot *__restrict__ slots,
                                                        const DfBlock *__restrict__ blocks, const DfBatchOut *__restrict__ outs,
                                                        int kind, DfCrcShifts xk, u8 *__restrict__ out, u32 *__restrict__ stats,
@@ -2257,7 +2287,7 @@ __global__ __launch_bounds__(256) void k_df_batch_wrap(const u8 *__restrict__ im
         const DfBlock b = blocks[j];
         atomicAdd(&stats[b.btype < 3u ? b.btype : 0u], 1u);
         if (b.lm & 0xFFu) atomicAdd(&stats[3], b.lm & 0xFFu);
-        if ((b.lm >> 8) & 1u) atomicAdd(&stats[4], 1u);
+        if ((b.lm >> (BGZF ? 9 : 8)) & 1u) atomicAdd(&stats[4], 1u);
     }
     if (kind == 0) return;
     {
@@ -2314,7 +2344,11 @@ __global__ __launch_bounds__(256) void k_df_batch_wrap(const u8 *__restrict__ im
     } else {
         const u32 raw = df_gf_mul(s_c[0], df_gf_xpow8(rest)) ^ s_tail; // register for a zero initial value
         const u32 crc = raw ^ df_gf_mul(0xFFFFFFFFu, df_gf_xpow8(len)) ^ 0xFFFFFFFFu;
-        p[0] = 0x1F; p[1] = 0x8B; p[2] = 0x08; p[3] = 0; p[4] = 0; p[5] = 0; p[6] = 0; p[7] = 0; p[8] = 0; p[9] = 0xFF;
+        p[0] = 0x1F; p[1] = 0x8B; p[2] = 0x08; p[3] = BGZF ? 4 : 0; p[4] = 0; p[5] = 0; p[6] = 0; p[7] = 0; p[8] = 0; p[9] = 0xFF;
+        if (BGZF) {
+            const u32 bsize = o.len - 1u; // (at most 65 280 + 30)
+            p[10] = 6; p[11] = 0; p[12] = 0x42; p[13] = 0x43; p[14] = 2; p[15] = 0; p[16] = (u8)bsize; p[17] = (u8)(bsize >> 8);
+        }
         u8 *t = p + o.len - 8;
         for (u32 i = 0; i < 4; ++i) { t[i] = (u8)(crc >> (8 * i)); t[4 + i] = (u8)(len >> (8 * i)); }
     }
@@ -2324,6 +2358,13 @@ int df_launch_gather(hipStream_t st, const u8 *d_in, const DfSlot *slots, const 
 {
     if (win) hipLaunchKernelGGL(k_df_gather_dict, dim3(ntiles), dim3(256), 0, st, d_in, slots, tile_slot, image, win);
     else hipLaunchKernelGGL(k_df_gather, dim3(ntiles), dim3(256), 0, st, d_in, slots, tile_slot, image);
+    DFCHK(hipMemsetAsync(image + (size_t)ntiles * kPTile, 0, 64, st));
+    return 0;
+}
+
+int df_launch_gather_cut(hipStream_t st, const u8 *d_in, const DfSlot *slots, const u32 *tile_slot, u32 ntiles, u8 *image)
+{
+    hipLaunchKernelGGL(k_df_gather_cut, dim3(ntiles), dim3(256), 0, st, d_in, slots, tile_slot, image);
     DFCHK(hipMemsetAsync(image + (size_t)ntiles * kPTile, 0, 64, st));
     return 0;
 }
@@ -2343,14 +2384,28 @@ int df_launch_parse_batch(hipStream_t st, const u32 *M, u64 n, u32 ntiles, const
 int df_launch_blocks_batch(hipStream_t st, const u8 *image, const u32 *code, const u64 *bse, const u32 *nb, u32 nslots, DfBlock *blocks,
                            u8 *lens, u32 *hdr, u32 *lm_scratch)
 {
-    hipLaunchKernelGGL((k_df_block<true>), dim3(nslots), dim3(kBThreads), 0, st, image, code, bse, nb, blocks, lens, hdr, lm_scratch, 0u, 1u,
+    hipLaunchKernelGGL((k_df_block<true, false>), dim3(nslots), dim3(kBThreads), 0, st, image, code, bse, nb, blocks, lens, hdr, lm_scratch, 0u, 1u,
+                       (const u32 *)nullptr, 1u);
+    return 0;
+}
+
+int df_launch_blocks_strict(hipStream_t st, const u8 *image, const u32 *code, const u64 *bse, const u32 *nb, u32 nslots, DfBlock *blocks,
+                            u8 *lens, u32 *hdr, u32 *lm_scratch)
+{
+    hipLaunchKernelGGL((k_df_block<true, true>), dim3(nslots), dim3(kBThreads), 0, st, image, code, bse, nb, blocks, lens, hdr, lm_scratch, 0u, 1u,
                        (const u32 *)nullptr, 1u);
     return 0;
 }
 
 int df_launch_batch_offsets(hipStream_t st, DfBlock *blocks, u32 nslots, u32 head, u32 tail, DfBatchOut *outs, u64 *total)
 {
-    hipLaunchKernelGGL(k_df_batch_offsets, dim3(1), dim3(256), 0, st, blocks, nslots, head, tail, outs, total);
+    hipLaunchKernelGGL((k_df_batch_offsets<true>), dim3(1), dim3(256), 0, st, blocks, nslots, head, tail, outs, total);
+    return 0;
+}
+
+int df_launch_exact_offsets(hipStream_t st, DfBlock *blocks, u32 nslots, u32 head, u32 tail, DfBatchOut *outs, u64 *total)
+{
+    hipLaunchKernelGGL((k_df_batch_offsets<false>), dim3(1), dim3(256), 0, st, blocks, nslots, head, tail, outs, total);
     return 0;
 }
 
@@ -2365,8 +2420,15 @@ int df_launch_batch_wrap(hipStream_t st, const u8 *image, const DfSlot *slots, u
                          int kind, DfCrcShifts xk, u8 *out, u32 *stats, bool with_dict, u32 dictid)
 {
     if (with_dict && kind == 1)
-        hipLaunchKernelGGL((k_df_batch_wrap<true>), dim3(nslots), dim3(256), 0, st, image, slots, blocks, outs, kind, xk, out, stats, dictid);
-    else hipLaunchKernelGGL((k_df_batch_wrap<false>), dim3(nslots), dim3(256), 0, st, image, slots, blocks, outs, kind, xk, out, stats, 0u);
+        hipLaunchKernelGGL((k_df_batch_wrap<true, false>), dim3(nslots), dim3(256), 0, st, image, slots, blocks, outs, kind, xk, out, stats, dictid);
+    else hipLaunchKernelGGL((k_df_batch_wrap<false, false>), dim3(nslots), dim3(256), 0, st, image, slots, blocks, outs, kind, xk, out, stats, 0u);
+    return 0;
+}
+
+int df_launch_bgzf_wrap(hipStream_t st, const u8 *image, const DfSlot *slots, u32 nslots, const DfBlock *blocks, const DfBatchOut *outs,
+                        DfCrcShifts xk, u8 *out, u32 *stats)
+{
+    hipLaunchKernelGGL((k_df_batch_wrap<false, true>), dim3(nslots), dim3(256), 0, st, image, slots, blocks, outs, 2, xk, out, stats, 0u);
     return 0;
 }
 

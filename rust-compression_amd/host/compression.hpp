@@ -507,6 +507,26 @@ using ZlibDecoder = DeflateFamilyDecoder<DF_KIND_ZLIB>;
 using GZipDecoder = DeflateFamilyDecoder<DF_KIND_GZIP>;
 using MultiGZipDecoder = DeflateFamilyDecoder<DF_KIND_GZIP, true>;
 
+// One input as a BGZF file (include/bz2_mi355x.h section 7, df_bgzf_encode_buffer): gzip members of at most block_bytes
+// (0: 65 280) input bytes side by side, then the 28-byte EOF marker unless eof is false.  The reference has no such writer;
+// every member is a stream that zlib, gzip(1) and htslib read.  block_off, when not null, receives the file offset of every
+// block and, last, that of the marker (the file's length without one).
+inline Result<std::vector<uint8_t>> bgzf_compress(const uint8_t *in, size_t n, uint32_t block_bytes = 0, bool eof = true, int device = 0,
+                                                  std::vector<uint64_t> *block_off = nullptr)
+{
+    using R = Result<std::vector<uint8_t>>;
+    if (block_bytes > DF_BGZF_BLOCK) return R::Err(from_status(BZ_E_PARAM));
+    std::vector<uint64_t> off(df_bgzf_block_count(n, block_bytes) + 1);
+    uint8_t *out = nullptr;
+    size_t len = 0;
+    const int rc = df_bgzf_encode_buffer(device, in, n, block_bytes, eof ? 1 : 0, &out, &len, off.data());
+    if (rc != BZ_OK) return R::Err(from_status(rc));
+    std::vector<uint8_t> file(out, out + len);
+    bz_free(out);
+    if (block_off) *block_off = std::move(off);
+    return R::Ok(std::move(file));
+}
+
 // DecodeIterator (src/traits/decoder.rs:45-86)
 template <class I, class S, class D> class DecodeIterator {
   public:

@@ -75,4 +75,11 @@ extern "C" {
     pub fn df_gpu_last_decode_members_stats(g: *mut c_void, out: *mut u64) -> i32;
     pub fn df_gpu_last_decode_members_timings(g: *mut c_void, out_seconds: *mut f64) -> i32;
     pub fn df_decode_members_buffer(device: i32, input: *const u8, in_len: usize, out: *mut *mut u8, out_len: *mut usize) -> i32;
+
+    // section 7: writing BGZF (gzip members of at most 65 280 input bytes; *out is released with bz_free)
+    pub fn df_bgzf_block_count(n: usize, block_bytes: u32) -> usize;
+    pub fn df_bgzf_bound(n: usize, block_bytes: u32, eof: i32) -> usize;
+    pub fn df_gpu_bgzf_encode_device(g: *mut c_void, d_in: *const c_void, n: usize, block_bytes: u32, eof: i32, d_out: *mut c_void, cap: usize, out_len: *mut u64, h_block_off: *mut u64) -> i32;
+    pub fn df_gpu_last_bgzf_stats(g: *mut c_void, out: *mut u64) -> i32;
+    pub fn df_bgzf_encode_buffer(device: i32, input: *const u8, n: usize, block_bytes: u32, eof: i32, out: *mut *mut u8, out_len: *mut usize, block_off: *mut u64) -> i32;
 }

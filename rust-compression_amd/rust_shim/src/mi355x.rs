@@ -111,6 +111,29 @@ pub fn deflate_encode_batch_dict(kind: usize, inputs: &[&[u8]], dict: &[u8]) -> 
     Ok(streams)
 }
 
+/// One input as a BGZF file (`df_bgzf_encode_buffer`, device 0): gzip members of at most `block_bytes` (0: 65 280) input
+/// bytes side by side, then the 28-byte EOF marker when `eof` is set.  The reference has no such writer; every member is
+/// a stream that zlib, gzip(1) and htslib read.  Returns the file and the file offset of every block, the last entry
+/// being where the marker starts (the file's length without one).  Panics on a `block_bytes` above 65 280.
+pub fn bgzf_encode(input: &[u8], block_bytes: u32, eof: bool) -> Result<(Vec<u8>, Vec<u64>), CompressionError> {
+    assert!(block_bytes <= 65280, "invalid block size");
+    let count = unsafe { ffi::df_bgzf_block_count(input.len(), block_bytes) };
+    let mut off: Vec<u64> = Vec::new();
+    off.resize(count + 1, 0);
+    let mut out: *mut u8 = core::ptr::null_mut();
+    let mut len: usize = 0;
+    let rc = unsafe {
+        ffi::df_bgzf_encode_buffer(0, input.as_ptr(), input.len(), block_bytes, eof as i32, &mut out, &mut len, off.as_mut_ptr())
+    };
+    if rc != ffi::BZ_OK {
+        note_status(rc);
+        return Err(CompressionError::from_status(rc));
+    }
+    let file = unsafe { core::slice::from_raw_parts(out, len) }.to_vec();
+    unsafe { ffi::bz_free(out as *mut core::ffi::c_void) };
+    Ok((file, off))
+}
+
 /// Many independent streams in one call (`bz_decode_batch`, device 0): element `i` of the result is what
 /// `inputs[i].iter().cloned().decode(&mut BZip2Decoder::new())` yields -- `Ok(bytes)`, or the `BZip2Error` with the bytes
 /// the iterator hands out in front of it.  An entry's verdict is its own: a bad one hides nothing behind it.  The outer
