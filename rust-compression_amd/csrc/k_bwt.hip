@@ -3206,7 +3206,8 @@ __global__ __launch_bounds__(kSortThreads) void k_period_mark(BwtArgs a, u32 ste
 // pair_bits != nullptr: also the map of the byte pairs (T[i], T[(i + 1) mod n]) in use, 65 536 bits per block, bit
 // (first << 8 | second).  A workgroup keeps its map in LDS and looks at a bit before it sets it -- text has a few
 // hundred pairs, the map is full after a few thousand positions and the rest only read -- and ORs the words that
-// are not zero into the block's map.
+// are not zero into the block's map.  With the map the bytes in use are read off its rows; without it (BZ_PAIR_KEYS=0)
+// they come from a 256-bit set kept per byte.
 __global__ __launch_bounds__(kSortThreads) void k_block_symbols(BwtArgs a, u32 *__restrict__ inuse_bits /*[nb][8]*/,
                                                                 u32 *__restrict__ pair_bits /*[nb][kPairWords] or null*/)
 {
@@ -3234,13 +3235,48 @@ __global__ __launch_bounds__(kSortThreads) void k_block_symbols(BwtArgs a, u32 *
     const u32 lead = (u32)(p0 & 15u);
     const uint4 *src = reinterpret_cast<const uint4 *>(p0 - lead);
     const u32 t0 = text[0];
+    if (pair_bits) {
+        // The bytes in use are a projection of the pair map: every position i sets the bit of (T[i], T[(i + 1) mod n]), so
+        // byte b occurs iff row b of the map -- words 8b .. 8b+7 -- is not empty.  No per-byte set here: the four
+        // selects and ORs per byte, and the wave reductions behind them, cost more than the load and the map together.
+        for (u32 c = threadIdx.x; c * 16u < lead + cnt; c += kSortThreads) {
+            const uint4 v = src[c];
+            const u32 w[4] = {v.x, v.y, v.z, v.w};
+            const u32 behind = start + c * 16u + 16u - lead; // (the byte behind the sixteen: the pair of the last one,
+            const u32 nxt = (behind < n) ? (u32)text[behind] : t0; // the block's first byte behind its last)
+#pragma unroll
+            for (u32 k = 0; k < 16; ++k) {
+                const u32 pos = c * 16u + k;
+                if (pos < lead || pos >= lead + cnt) continue;
+                const u32 b = (w[k >> 2] >> ((k & 3u) * 8u)) & 0xFFu;
+                u32 b2 = (k < 15u) ? ((w[(k + 1u) >> 2] >> (((k + 1u) & 3u) * 8u)) & 0xFFu) : nxt;
+                if (start + (pos - lead) + 1u == n) b2 = t0;
+                const u32 pr = (b << 8) | b2;
+                if (!((s_pair[pr >> 5] >> (pr & 31u)) & 1u)) atomicOr(&s_pair[pr >> 5], 1u << (pr & 31u));
+            }
+        }
+        __syncthreads();
+        for (u32 b0 = 0; b0 < 256u; b0 += kSortThreads) { // (whole waves: 256 is a multiple of 64)
+            const u32 b = b0 + threadIdx.x;
+            u32 row = 0;
+            if (b < 256u) {
+#pragma unroll
+                for (u32 q = 0; q < 8; ++q) row |= s_pair[8u * b + q];
+            }
+            const u64 m = __ballot(row != 0u);
+            if ((threadIdx.x & 63u) == 0 && b < 256u) {
+                if ((u32)m) atomicOr(&inuse_bits[lb * 8 + (b >> 5)], (u32)m);
+                if ((u32)(m >> 32)) atomicOr(&inuse_bits[lb * 8 + (b >> 5) + 1u], (u32)(m >> 32));
+            }
+        }
+        for (u32 i = threadIdx.x; i < kPairWords; i += kSortThreads)
+            if (s_pair[i]) atomicOr(&pair_bits[(size_t)lb * kPairWords + i], s_pair[i]);
+        return;
+    }
     u64 set[4] = {0, 0, 0, 0};
     for (u32 c = threadIdx.x; c * 16u < lead + cnt; c += kSortThreads) {
         const uint4 v = src[c];
         const u32 w[4] = {v.x, v.y, v.z, v.w};
-        // the byte behind the sixteen: the pair of the last one (the block's first byte behind its last)
-        const u32 behind = start + c * 16u + 16u - lead;
-        const u32 nxt = (pair_bits && behind < n) ? (u32)text[behind] : t0;
 #pragma unroll
         for (u32 k = 0; k < 16; ++k) {
             const u32 pos = c * 16u + k;
@@ -3250,12 +3286,6 @@ __global__ __launch_bounds__(kSortThreads) void k_block_symbols(BwtArgs a, u32 *
             const u32 hi = b >> 6;
 #pragma unroll
             for (u32 q = 0; q < 4; ++q) set[q] |= (hi == q) ? bit : 0ull;
-            if (pair_bits && in) {
-                u32 b2 = (k < 15u) ? ((w[(k + 1u) >> 2] >> (((k + 1u) & 3u) * 8u)) & 0xFFu) : nxt;
-                if (start + (pos - lead) + 1u == n) b2 = t0;
-                const u32 pr = (b << 8) | b2;
-                if (!((s_pair[pr >> 5] >> (pr & 31u)) & 1u)) atomicOr(&s_pair[pr >> 5], 1u << (pr & 31u));
-            }
         }
     }
     u32 seen[8];
@@ -3273,9 +3303,6 @@ __global__ __launch_bounds__(kSortThreads) void k_block_symbols(BwtArgs a, u32 *
     }
     __syncthreads();
     if (threadIdx.x < 8 && s_bits[threadIdx.x]) atomicOr(&inuse_bits[lb * 8 + threadIdx.x], s_bits[threadIdx.x]);
-    if (pair_bits)
-        for (u32 i = threadIdx.x; i < kPairWords; i += kSortThreads)
-            if (s_pair[i]) atomicOr(&pair_bits[(size_t)lb * kPairWords + i], s_pair[i]);
 }
 
 // one 256-thread workgroup per block: byte -> code table (rank among the bytes in use, the

@@ -1035,52 +1035,118 @@ __global__ __launch_bounds__(kHuffThreads, 4) void k_huffman(HuffArgs a) // (4 w
 }
 
 // ---- payload: one lane per 50-symbol group (encoder.rs:609-629) ---------------------------
-__global__ __launch_bounds__(256) void k_emit_payload(HuffArgs a)
+// The 256 groups of a workgroup are consecutive in the block's bit string, so the workgroup owns one span of it.  The
+// lanes put their words into a copy of that span in LDS (a lane's groups lie about 28 bytes apart on text: stored to
+// global memory straight from the lanes, every store instruction was a handful of lone 4-byte writes, and every group
+// cost two global atomics), and the workgroup then stores the span with consecutive lanes on consecutive words.  Only
+// the span's first and last word are shared -- with the header or with the neighbouring workgroups -- and are ORed
+// into the words k_huff_header zeroed.
+// The span is at most 256 groups x 50 symbols x kLim bits = 6800 words, one more when it starts inside a word, and up to
+// three in front so that word 0 of the buffer is a 16-byte boundary of the stream: every span fits, there is no other
+// path.  The buffer is the staging area of the symbols first; a lane holds its 25 dwords in registers by the time the
+// span is cleared.  With the code tables 33.4 KB: four workgroups share a CU.
+constexpr u32 kEmitThreads = 256;
+constexpr u32 kEmitBufWords = kEmitThreads * kGSize * kLim / 32u + 1u + 3u;
+static_assert(kEmitThreads * kGSize * kLim % 32u == 0 && kEmitBufWords % 4u == 0, "the span buffer is whole 16-byte pieces");
+static_assert(kEmitBufWords >= kEmitThreads * kGSize / 2, "the span buffer first holds the staged symbols");
+
+__global__ __launch_bounds__(kEmitThreads) void k_emit_payload(HuffArgs a)
 {
-    __shared__ u32 s_code[6 * kMaxAlpha];
-    __shared__ u32 s_sym[256 * kGSize / 2];
-    const u32 lb = blockIdx.y;
+    __shared__ u32 s_code[6 * kMaxAlpha + 1]; // (the last entry: no bits, what a symbol behind the group's end codes to)
+    __shared__ __attribute__((aligned(16))) u32 s_buf[kEmitBufWords];
+    const u32 lb = blockIdx.y, tid = threadIdx.x;
     const BlockOut &bo = a.out[lb];
     const u32 mtf_count = bo.mtf_count;
     const u32 n_selectors = bo.n_selectors;
-    const u32 g0 = blockIdx.x * 256u;
+    const u32 g0 = blockIdx.x * kEmitThreads;
     if (g0 >= n_selectors) return;
     const u32 *code_len = a.code_len + (size_t)lb * 6 * kMaxAlpha;
-    for (u32 i = threadIdx.x; i < 6 * kMaxAlpha; i += 256u) s_code[i] = code_len[i];
+    for (u32 i = tid; i < 6 * kMaxAlpha; i += kEmitThreads) s_code[i] = code_len[i];
+    if (tid == 0) s_code[6 * kMaxAlpha] = 0;
     const u16 *mtf = a.mtf + (size_t)lb * a.mtf_stride;
-    stage_symbols(s_sym, mtf, g0, mtf_count);
-    __syncthreads();
-    const u32 g = g0 + threadIdx.x;
-    if (g >= n_selectors) return;
-    const u32 gs = g * kGSize;
-    const u32 cnt = (gs + kGSize < mtf_count) ? kGSize : mtf_count - gs;
-    const u32 *my = s_sym + threadIdx.x * (kGSize / 2);
-    const u32 *tab = s_code + (u32)a.selector[(size_t)lb * kSelStride + g] * kMaxAlpha;
-    const u32 bitpos = bo.header_bits + a.group_bitoff[(size_t)lb * kGboStride + g];
+    stage_symbols(s_buf, mtf, g0, mtf_count);
+    // the span [lo, hi) in bits of the block's stream, its first and last word, and the word of s_buf[0]
+    const u32 *gbo = a.group_bitoff + (size_t)lb * kGboStride;
+    const u32 hb = bo.header_bits;
+    const u32 g1 = g0 + kEmitThreads;
+    const u32 lo = hb + gbo[g0];
+    const u32 hi = (g1 < n_selectors) ? hb + gbo[g1] : (u32)bo.total_bits;
+    if (hi <= lo) return;
     u32 *stream = a.stream + (size_t)lb * kStreamWords;
-    u32 widx = bitpos >> 5;
-    u32 nacc = bitpos & 31u;
-    u64 acc = 0;
-    bool first = true;
-    for (u32 i = 0; i < cnt; ++i) {
-        const u32 cl = tab[(my[i >> 1] >> ((i & 1u) * 16u)) & 0xFFFFu];
-        const u32 len = cl >> 24, code = cl & 0xFFFFFFu;
-        acc |= (u64)code << (64u - nacc - len);
-        nacc += len;
-        if (nacc >= 32u) {
-            const u32 word = (u32)(acc >> 32);
-            if (first) {
-                atomicOr(&stream[widx], word); // shared with the previous group / the header
-                first = false;
-            } else {
-                stream[widx] = word;           // all 32 bits are this group's
+    const u32 wf = lo >> 5, wl = (hi - 1u) >> 5;
+    const u32 base = wf - ((wf + (u32)((reinterpret_cast<uintptr_t>(stream) >> 2) & 3u)) & 3u); // (wf > 3: the header)
+    const u32 nwords = wl - base + 1u;
+    if (nwords > kEmitBufWords) { // (a code above kLim bits: no table kernel leaves one)
+        if (tid == 0) atomicExch(a.error_flag, 1u);
+        return;
+    }
+    const u32 g = g0 + tid;
+    const bool live = g < n_selectors;
+    const u32 gs = g * kGSize;
+    const u32 cnt = !live ? 0u : (gs + kGSize < mtf_count) ? kGSize : mtf_count - gs;
+    __syncthreads();
+    u32 sym[kGSize / 2];
+#pragma unroll
+    for (u32 k = 0; k < kGSize / 2; ++k) sym[k] = s_buf[tid * (kGSize / 2) + k];
+    __syncthreads();
+    for (u32 q = tid * 4u; q < nwords; q += kEmitThreads * 4u) *reinterpret_cast<uint4 *>(s_buf + q) = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+    if (live) {
+        const u32 tab = (u32)a.selector[(size_t)lb * kSelStride + g] * kMaxAlpha;
+        const u32 bitpos = hb + gbo[g];
+        u32 widx = (bitpos >> 5) - base;
+        u32 nacc = bitpos & 31u;
+        u64 acc = 0;
+        bool first = true;
+        // ten look-ups at a time, then their ten steps: a symbol behind the group's end (the block's last group)
+        // reads the entry without bits and changes nothing
+#pragma unroll
+        for (u32 k0 = 0; k0 < kGSize / 2; k0 += 5) {
+            u32 cl[10];
+#pragma unroll
+            for (u32 j = 0; j < 10; ++j) {
+                const u32 i = 2u * k0 + j;
+                const u32 s = (sym[i >> 1] >> ((i & 1u) * 16u)) & 0xFFFFu;
+                cl[j] = s_code[(i < cnt) ? tab + s : 6u * kMaxAlpha];
             }
-            ++widx;
-            acc <<= 32;
-            nacc -= 32u;
+#pragma unroll
+            for (u32 j = 0; j < 10; ++j) {
+                const u32 len = cl[j] >> 24, code = cl[j] & 0xFFFFFFu;
+                acc |= (u64)code << ((64u - nacc - len) & 63u);
+                nacc += len;
+                if (nacc >= 32u) {
+                    const u32 word = (u32)(acc >> 32);
+                    if (first) {
+                        atomicOr(&s_buf[widx], word); // shared with the previous group
+                        first = false;
+                    } else {
+                        s_buf[widx] = word;           // all 32 bits are this group's
+                    }
+                    ++widx;
+                    acc <<= 32;
+                    nacc -= 32u;
+                }
+            }
+        }
+        if (nacc) atomicOr(&s_buf[widx], (u32)(acc >> 32)); // shared with the next group
+    }
+    __syncthreads();
+    // s_buf[q] is word base + q of the stream, and that is a 16-byte boundary when q is a multiple of four
+    for (u32 q = tid * 4u; q < nwords; q += kEmitThreads * 4u) {
+        const u32 w = base + q;
+        if (w > wf && w + 3u < wl && w + 3u < kStreamWords) {
+            *reinterpret_cast<uint4 *>(stream + w) = *reinterpret_cast<const uint4 *>(s_buf + q);
+            continue;
+        }
+#pragma unroll
+        for (u32 j = 0; j < 4; ++j) {
+            const u32 ww = w + j;
+            if (ww < wf || ww > wl || ww >= kStreamWords) continue;
+            const u32 v = s_buf[q + j];
+            if (ww != wf && ww != wl) stream[ww] = v;
+            else if (v) atomicOr(&stream[ww], v); // shared with the header, a neighbouring workgroup's span
         }
     }
-    if (nacc) atomicOr(&stream[widx], (u32)(acc >> 32)); // shared with the next group
 }
 
 // =====================================================================================================
