@@ -949,6 +949,114 @@ int df_gpu_last_bgzf_stats(bz_gpu_engine *g, uint64_t out[8]);
 int df_bgzf_encode_buffer(int device, const uint8_t *in, size_t n, uint32_t block_bytes, int eof,
                           uint8_t **out, size_t *out_len, uint64_t *block_off);
 
+/* ========================================================================
+ * 8. READING BGZF: the block index from BSIZE, range reads, one decode pass
+ *    (DESIGN_deflate.md, "Reading BGZF").  Section 6 reads such a file as an
+ *    anonymous run of gzip members: it guesses the starts, decodes every member
+ *    twice and copies its bytes into place, and it reads the whole file.  A
+ *    BGZF block says what that path has to find out: BSIZE is its length, ISIZE
+ *    its output's length, so every block's place in the output is a prefix sum
+ *    known before the first bit is decoded.
+ *
+ * A BLOCK HEADER at byte p is htslib's rule with FLG exact: in[p .. p + 16) ==
+ * 1f 8b 08 04 ?? ?? ?? ?? ?? ?? 06 00 42 43 02 00 -- MTIME, XFL and OS may be
+ * anything, FLG is exactly 4, XLEN exactly 6 with the BC subfield first and
+ * alone.  BSIZE = u16 at p + 16, the block is BSIZE + 1 bytes, ISIZE = u32 in
+ * its last four bytes.  A gzip file whose members carry other extra subfields
+ * is legal gzip, and legal by the letter of the SAM specification; htslib does
+ * not read it and neither does this section: such a file goes through section 6.
+ *
+ * THE CHAIN, from pos = 0, upos = 0, over a file of len bytes:
+ *
+ *     repeat:
+ *         if pos == len: BZ_OK, stop
+ *         if len - pos < 18: BZ_E_EOF, stop              (a cut header, whatever its bytes are)
+ *         if the header rule fails at pos: BZ_E_DATA, stop
+ *         if BSIZE + 1 < 28: BZ_E_DATA, stop             (18 + a 2-byte empty final block + 8)
+ *         if pos + BSIZE + 1 > len: BZ_E_EOF, stop
+ *         if ISIZE > 65536: BZ_E_DATA, stop
+ *         record block (coff = pos, uoff = upos); pos += BSIZE + 1; upos += ISIZE
+ *
+ * Zero padding is NOT skipped (htslib does not skip it; section 6 does).  THE
+ * INDEX is count + 1 pairs (coff[k], uoff[k]); the last pair is the end of the
+ * last complete block; on an error verdict the blocks in front of the fault
+ * are still indexed.  The 28-byte EOF marker is an ordinary block with ISIZE 0.
+ * The two arrays ARE the .gzi table (files of that layout are not read or
+ * written here).
+ *
+ * A BLOCK IS CLEAN iff its Deflate bytes [coff[k] + 18, coff[k + 1] - 8) decode
+ * under section 5, kind 0, with NO history in front of the block (a distance
+ * that reaches in front of the block's first byte is a fault although, written
+ * in place, the previous block's bytes lie right there), produce exactly ISIZE
+ * bytes, end in the byte in front of the trailer, and the CRC-32 of the output
+ * is the trailer's.  Every fault inside a block is BZ_E_DATA, running out of
+ * bits included: the cut is BSIZE's, not the file's end.  BZ_E_EOF comes from
+ * the index calls only.
+ *
+ * So every file this section reads with BZ_OK yields, over [0, total), exactly
+ * the bytes of section 6 and of Python's gzip.decompress.  On faulty files the
+ * two sections may differ, deliberately in two places: a trailer fault in
+ * block k delivers nothing of block k here (section 6 delivers all of member
+ * k), and zeros between blocks are an error here.
+ *
+ * WHAT A RANGE READ IS WORTH.  One wave decodes one block; a 64 KiB block takes
+ * milliseconds on the device whatever surrounds it.  Range reads pay off for
+ * ranges of many blocks (a region of tens of MiB of a large file), not for one
+ * record.  Figures: profiles/r22_bgzf_read.md.
+ * ======================================================================== */
+
+/* The chain on the HOST, over host memory (sixteen thousand steps per GiB).  This is parsing, not decoding: it touches no
+ * device and works without a GPU -- the one exception to "there is no CPU path".  *coff and *uoff are malloc'ed arrays of
+ * *count + 1 entries, release each with bz_free; *verdict is the chain's (BZ_OK, BZ_E_DATA, BZ_E_EOF).  The return value is
+ * the infrastructure status only.  BZ_E_PARAM: a null result pointer, in null with in_len > 0. */
+int df_bgzf_index_buffer(const uint8_t *in, size_t in_len, uint64_t **coff, uint64_t **uoff, size_t *count, int32_t *verdict);
+/* The same index for a file in HBM (d_in 16-byte aligned; nothing at or behind d_in + in_len is read).  h_coff and h_uoff are
+ * HOST arrays with room for cap_blocks + 1 entries; BZ_E_CAPACITY with *count set when cap_blocks is too small (cap_blocks
+ * == 0 with null arrays asks for the count).  A search lists every position that satisfies the 16-byte header rule with at
+ * least 18 bytes behind it (ascending, 64-bit positions, tiles of 4 096 positions, count then scatter), a second kernel
+ * fetches BSIZE, and ISIZE where the block fits, per candidate, and the host walks the chain over the list: a chain
+ * position that is not in the list is a header-rule failure; false candidates (a stored block whose payload is a BGZF
+ * file) are never landed on and cost nothing.  The list is handled in windows of BZ_DF_BGZF_BATCH candidates (environment;
+ * default 65 536, read per call). */
+int df_gpu_bgzf_index_device(bz_gpu_engine *g, const void *d_in, size_t in_len, uint64_t *h_coff, uint64_t *h_uoff,
+                             size_t cap_blocks, size_t *count, int32_t *verdict);
+/* The uncompressed bytes [ustart, min(ustart + ulen, uoff[count])) at d_out (any alignment).  Only the blocks that the range
+ * touches are decoded: from the block that holds its first byte to the block that holds its last, empty blocks between
+ * them included.  The blocks that lie whole inside the range are decoded by ONE launch, one wave per block, straight to
+ * d_out + (uoff[k] - ustart); the at most two blocks the range cuts are decoded in the same launch into two 64 KiB slots
+ * of the engine's workspace and their slices copied out; a second kernel compares the CRC-32s.  Blocks go to the launch in
+ * groups of at most BZ_DF_BGZF_BATCH.
+ * THE INDEX is the caller's -- from either index call, from df_gpu_bgzf_encode_device's h_block_off with k * B beside it, or
+ * from a .gzi -- count + 1 entries per array; coff is relative to d_in (16-byte aligned), coff[0] need not be 0 and uoff[0]
+ * need not be 0 (ustart counts in the same coordinates).  It is checked where it is used: for every block k touched the
+ * header rule holds at coff[k], coff[k + 1] - coff[k] == BSIZE + 1 and uoff[k + 1] - uoff[k] == ISIZE, else BZ_E_DATA at
+ * block k.  BZ_E_PARAM: a null engine, index, out_len or verdict; d_in misaligned, or null with in_len > 0; arrays that are
+ * not ascending (coff strictly); coff[count] > in_len; ustart < uoff[0]; a block longer than 65 536 bytes either way.
+ * RESULT.  The return value is the infrastructure status.  *verdict BZ_OK: *out_len is the range's length.  BZ_E_DATA:
+ * *out_len is the range's bytes in front of the first faulty block (the lowest k).  Decided before any write: d_out ==
+ * NULL gives sizes only (*out_len is the range's length, no kernel is launched); BZ_E_CAPACITY when cap is below the
+ * range's length (*out_len holds it), d_out untouched.  ulen == 0 or ustart >= uoff[count]: BZ_OK, no bytes, no launch.
+ * THE PRICE OF ONE PASS: on an error verdict the bytes of d_out in [*out_len, range length) are UNSPECIFIED.  Nothing at or
+ * behind d_out + range length is ever written, and a block's stores are clipped to its own [uoff[k], uoff[k + 1]).
+ * Afterwards df_gpu_last_timings holds [0] search and chain of the last index call [1] decode [2] checksums [3] edge copy
+ * [5] their sum. */
+int df_gpu_bgzf_read_device(bz_gpu_engine *g, const void *d_in, size_t in_len, const uint64_t *h_coff, const uint64_t *h_uoff,
+                            size_t count, uint64_t ustart, uint64_t ulen, void *d_out, size_t cap, uint64_t *out_len,
+                            int32_t *verdict);
+/* The last df_gpu_bgzf_read_device call: [0] blocks decoded [1] of them written in place [2] edge blocks through the workspace
+ * [5] bytes decoded [6] bytes delivered [7] kernel launches; and the last df_gpu_bgzf_index_device call: [3] candidates found
+ * [4] candidates never landed on. */
+int df_gpu_last_bgzf_read_stats(bz_gpu_engine *g, uint64_t out[8]);
+/* Host to host: the index is built on the host, only the compressed bytes of the blocks touched are uploaded, one device
+ * call on an engine of the per-process cache, one download; *out is malloc'ed, release with bz_free.  Returns BZ_OK with the
+ * bytes, or the verdict with the bytes in front of it (as df_decode_members_buffer does): an index verdict of BZ_E_EOF or
+ * BZ_E_DATA in front of or inside the range is the call's verdict, with the bytes of the range that lie in clean indexed
+ * blocks in front of it.  ulen = UINT64_MAX reads to the end.  The parameters are checked before any device is touched
+ * (BZ_E_PARAM: a null out or out_len, in null with in_len > 0); in_len == 0 or a range without bytes: an empty buffer, no
+ * device.  Without a GPU: BZ_E_NOGPU. */
+int df_bgzf_read_buffer(int device, const uint8_t *in, size_t in_len, uint64_t ustart, uint64_t ulen,
+                        uint8_t **out, size_t *out_len);
+
 #ifdef __cplusplus
 }
 #endif

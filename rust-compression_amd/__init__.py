@@ -29,7 +29,7 @@ import sys
 from . import _build
 
 __all__ = ["Action", "CompressionError", "BZip2Error", "BZip2Encoder", "BZip2Decoder", "encode", "decode",
-           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "deflate_decompress", "deflate_decompress_batch", "Deflater", "ZlibDecoder", "GZipDecoder", "gzip_decompress_members", "MultiGZipDecoder", "bgzf_compress", "bgzf_bound", "bgzf_block_count", "GpuEngine", "release_cached_resources", "last_call_phases",
+           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "deflate_decompress", "deflate_decompress_batch", "Deflater", "ZlibDecoder", "GZipDecoder", "gzip_decompress_members", "MultiGZipDecoder", "bgzf_compress", "bgzf_bound", "bgzf_block_count", "BgzfIndex", "bgzf_index", "bgzf_decompress", "bgzf_read", "GpuEngine", "release_cached_resources", "last_call_phases",
            "build", "lib", "device_count", "encode_bound", "shard_window", "rccl_lib", "rccl_unique_id", "RcclComm"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -102,6 +102,7 @@ EXPORTS = [
     "df_gpu_decode_batch_device_dict", "df_decode_batch_dict", "df_decode_buffer_dict",
     "df_gpu_decode_members_device", "df_gpu_last_decode_members_stats", "df_gpu_last_decode_members_timings", "df_decode_members_buffer",
     "df_bgzf_block_count", "df_bgzf_bound", "df_gpu_bgzf_encode_device", "df_gpu_last_bgzf_stats", "df_bgzf_encode_buffer",
+    "df_bgzf_index_buffer", "df_gpu_bgzf_index_device", "df_gpu_bgzf_read_device", "df_gpu_last_bgzf_read_stats", "df_bgzf_read_buffer",
 ]
 
 
@@ -272,6 +273,11 @@ def lib():
     L.df_gpu_bgzf_encode_device.argtypes = [vp, vp, sz, C.c_uint32, C.c_int, vp, sz, u64p, u64p]
     L.df_gpu_last_bgzf_stats.argtypes = [vp, u64p]
     L.df_bgzf_encode_buffer.argtypes = [C.c_int, C.c_char_p, sz, C.c_uint32, C.c_int, C.POINTER(u8p), szp, u64p]
+    L.df_bgzf_index_buffer.argtypes = [C.c_char_p, sz, C.POINTER(u64p), C.POINTER(u64p), szp, i32p]
+    L.df_gpu_bgzf_index_device.argtypes = [vp, vp, sz, u64p, u64p, sz, szp, i32p]
+    L.df_gpu_bgzf_read_device.argtypes = [vp, vp, sz, u64p, u64p, sz, C.c_uint64, C.c_uint64, vp, sz, u64p, i32p]
+    L.df_gpu_last_bgzf_read_stats.argtypes = [vp, u64p]
+    L.df_bgzf_read_buffer.argtypes = [C.c_int, C.c_char_p, sz, C.c_uint64, C.c_uint64, C.POINTER(u8p), szp]
     L.df_decode_buffer.argtypes = [C.c_int, C.c_int, C.c_char_p, sz, C.POINTER(u8p), szp]
     L.df_gpu_decode_batch_device_dict.argtypes = [vp, C.c_int, vp, u64p, u64p, sz, C.c_char_p, sz, vp, sz, u64p, u64p, i32p]
     L.df_decode_batch_dict.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, sz, C.c_char_p, sz, C.POINTER(u8p), u64p, u64p, i32p]
@@ -765,6 +771,116 @@ def bgzf_compress(data, block_bytes=0, eof=True, device=0, offsets=False):
     return (z, [int(x) for x in offs]) if offsets else z
 
 
+class BgzfIndex:
+    """The block index of a BGZF file (section 8 of the header): count + 1 pairs -- block k starts at file offset coff[k]
+    and at uncompressed offset uoff[k]; the last pair is the end of the last complete block.  `verdict` is the chain's
+    (BZ_OK, BZ_E_DATA or BZ_E_EOF: the blocks in front of a fault are still indexed).  The two lists are the .gzi table."""
+
+    def __init__(self, coff, uoff, verdict=BZ_OK):
+        self.coff = [int(x) for x in coff]
+        self.uoff = [int(x) for x in uoff]
+        if len(self.coff) != len(self.uoff) or not self.coff:
+            raise ValueError("BgzfIndex: coff and uoff hold count + 1 entries each")
+        self.verdict = int(verdict)
+
+    @property
+    def blocks(self):
+        return len(self.coff) - 1
+
+    @property
+    def total(self):
+        """uncompressed bytes of the indexed blocks"""
+        return self.uoff[-1] - self.uoff[0]
+
+    def _block_of(self, upos):
+        import bisect
+        return bisect.bisect_right(self.uoff, upos, 0, self.blocks) - 1
+
+    def voffset(self, upos):
+        """htslib's virtual offset of uncompressed position upos: coff << 16 | offset inside the block.  A position at a
+        block's edge belongs to the block that starts there (the last of them, behind empty blocks); upos == the end of the
+        last block is the end of the file: (coff[count], 0)."""
+        if not self.uoff[0] <= upos <= self.uoff[-1]:
+            raise ValueError("BgzfIndex.voffset: position outside the index")
+        if upos == self.uoff[-1]:
+            return self.coff[-1] << 16
+        k = self._block_of(upos)
+        return self.coff[k] << 16 | (upos - self.uoff[k])
+
+    def upos(self, voffset):
+        """the uncompressed position of a virtual offset (its coff must be a block's start, or the end of the last block)"""
+        import bisect
+        c, o = voffset >> 16, voffset & 0xFFFF
+        k = bisect.bisect_left(self.coff, c)
+        if k >= len(self.coff) or self.coff[k] != c:
+            raise ValueError("BgzfIndex.upos: no block starts at file offset %d" % c)
+        if k == self.blocks:
+            if o:
+                raise ValueError("BgzfIndex.upos: an offset behind the last block")
+            return self.uoff[-1]
+        if o >= max(self.uoff[k + 1] - self.uoff[k], 1):
+            raise ValueError("BgzfIndex.upos: offset %d is not inside block %d" % (o, k))
+        return self.uoff[k] + o
+
+    def _arrays(self):
+        """the two lists as the C call takes them; made once (an index is not changed after it is made)"""
+        if getattr(self, "_c", None) is None:
+            n = len(self.coff)
+            self._c = (C.c_uint64 * n)(*self.coff), (C.c_uint64 * n)(*self.uoff)
+        return self._c
+
+    def __eq__(self, other):
+        return isinstance(other, BgzfIndex) and (self.coff, self.uoff, self.verdict) == (other.coff, other.uoff, other.verdict)
+
+    def __repr__(self):
+        return "BgzfIndex(blocks=%d, total=%d, verdict=%d)" % (self.blocks, self.total, self.verdict)
+
+
+class BgzfError(CompressionError):
+    """A BGZF read that ended on a verdict: `partial` holds the bytes of the range in front of the fault."""
+
+    def __init__(self, code, partial=b""):
+        super().__init__(code)
+        self.partial = partial
+
+
+def bgzf_index(data):
+    """The block index of a BGZF file in host memory (df_bgzf_index_buffer): the BSIZE chain, walked on the host.  Parsing,
+    not decoding: no GPU is needed.  A faulty file does not raise: see BgzfIndex.verdict."""
+    data = bytes(data)
+    pc, pu = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+    n = C.c_size_t(0)
+    v = C.c_int32(0)
+    _check(lib().df_bgzf_index_buffer(data, len(data), C.byref(pc), C.byref(pu), C.byref(n), C.byref(v)))
+    try:
+        return BgzfIndex(pc[:n.value + 1], pu[:n.value + 1], v.value)
+    finally:
+        lib().bz_free(pc)
+        lib().bz_free(pu)
+
+
+def bgzf_read(data, ustart, ulen, index=None, device=0):
+    """The uncompressed bytes [ustart, ustart + ulen) of a BGZF file in host memory, clamped to its end (df_bgzf_read_buffer):
+    only the blocks the range touches are uploaded and decoded.  ulen = None: to the end.  `index` (a BgzfIndex of this
+    file) is accepted for symmetry with GpuEngine.bgzf_read_device; the host form walks the chain itself (parsing a file in
+    host memory costs less than passing its table).  A fault raises BgzfError (a CompressionError, kind DataError or
+    UnexpectedEof) whose `partial` holds the range's bytes in front of it."""
+    if ustart < 0 or (ulen is not None and ulen < 0):
+        raise ValueError("bgzf_read: a negative range")
+    if index is not None and not isinstance(index, BgzfIndex):
+        raise TypeError("bgzf_read: index is a BgzfIndex")
+    out, rc = _decode_call(lib().df_bgzf_read_buffer, (device,), data, _DF_VERDICTS,
+                           (C.c_uint64(ustart), C.c_uint64(0xFFFFFFFFFFFFFFFF if ulen is None else ulen)))
+    if rc != BZ_OK:
+        raise BgzfError(rc, out)
+    return out
+
+
+def bgzf_decompress(data, device=0):
+    """A whole BGZF file (bgzf_read over everything): the bytes of gzip.decompress for every file this reader accepts."""
+    return bgzf_read(data, 0, None, device=device)
+
+
 _DECODER_VERDICTS = (BZ_E_DATA, BZ_E_MAGIC_FIRST, BZ_E_MAGIC)
 
 
@@ -1230,6 +1346,45 @@ class GpuEngine:
         """The last bgzf_encode_device call, in the order of BGZF_STATS (df_gpu_last_bgzf_stats)."""
         s = (C.c_uint64 * 8)()
         _check(lib().df_gpu_last_bgzf_stats(self._h, s))
+        return [int(x) for x in s]
+
+    BGZF_READ_STATS = ("blocks_decoded", "in_place", "edge_blocks", "candidates", "never_landed_on", "decoded_bytes", "delivered_bytes", "launches")
+
+    def bgzf_index_device(self, d_in, in_len, cap_blocks=None):
+        """The block index of the BGZF file d_in[in_len] in device memory, 16-byte aligned (df_gpu_bgzf_index_device) -> a
+        BgzfIndex whose verdict is the chain's.  cap_blocks: room for that many blocks (BZ_E_CAPACITY raises); None:
+        room for one block per 4 KiB of file, and a second call with the count the first one reports if that is too few."""
+        _settle()
+        cap = in_len // 4096 + 64 if cap_blocks is None else cap_blocks
+        n = C.c_size_t(0)
+        v = C.c_int32(0)
+        while True:
+            coff, uoff = (C.c_uint64 * (cap + 1))(), (C.c_uint64 * (cap + 1))()
+            rc = lib().df_gpu_bgzf_index_device(self._h, d_in, in_len, coff, uoff, cap, C.byref(n), C.byref(v))
+            if rc != BZ_E_CAPACITY or cap_blocks is not None or n.value <= cap:
+                break
+            cap = n.value
+        _check(rc)
+        return BgzfIndex(coff[:n.value + 1], uoff[:n.value + 1], v.value)
+
+    def bgzf_read_device(self, d_in, in_len, index, ustart, ulen, d_out, cap):
+        """The uncompressed bytes [ustart, ustart + ulen), clamped to the index's end, of the BGZF file at d_in (16-byte aligned)
+        at d_out, any alignment (df_gpu_bgzf_read_device) -> (out_len, verdict).  index: a BgzfIndex, or a (coff, uoff) pair of
+        count + 1 entries each, relative to d_in.  d_out = None: sizes only."""
+        if not isinstance(index, BgzfIndex):
+            index = BgzfIndex(index[0], index[1])
+        _settle()
+        coff, uoff = index._arrays()
+        n = C.c_uint64(0)
+        v = C.c_int32(0)
+        _check(lib().df_gpu_bgzf_read_device(self._h, d_in, in_len, coff, uoff, index.blocks, ustart, ulen, d_out, cap, C.byref(n), C.byref(v)))
+        return int(n.value), int(v.value)
+
+    def bgzf_read_stats(self):
+        """The last bgzf_read_device call and, [3] and [4], the last bgzf_index_device call, in the order of BGZF_READ_STATS
+        (df_gpu_last_bgzf_read_stats)."""
+        s = (C.c_uint64 * 8)()
+        _check(lib().df_gpu_last_bgzf_read_stats(self._h, s))
         return [int(x) for x in s]
 
     DEFLATE_DECODE_BATCH_STATS = ("clean", "errors", "stored", "fixed", "dynamic", "decoded_bytes", "consumed_bytes", "launches")

@@ -20,6 +20,7 @@
 #include "k_deflate.h"
 #include "inf_split.h"
 #include "gz_members.h"
+#include "bgzf_index.h"
 
 using namespace dfgpu;
 
@@ -40,6 +41,10 @@ struct DfWorkspace {
                                                        // window of the list, span tables, the batch image, zero skips, the members' bytes
     u64 mem_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // df_gpu_last_decode_members_stats
     double mem_ms[4] = {0, 0, 0, 0};                   // search, gather, zero skip, compaction
+    DevBuf z_cnt, z_base, z_cand, z_info, z_desc, z_rec, z_slots; // reading BGZF: candidates per tile and in front of it, a window of the
+                                                       // list and its blocks' sizes, a group's descriptors and records, the two edge slots
+    u64 bgzf_read_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // df_gpu_last_bgzf_read_stats
+    double bgzf_index_s = 0;                           // search and chain of the last index call
     double t_stage[6] = {0, 0, 0, 0, 0, 0}; // chains, matches, parse, blocks, emit, total
     u64 stats[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // blocks, stored, fixed, dynamic, limited tables, stream bytes, dynamic w/o distances
     hipEvent_t ev[7] = {};
@@ -1968,6 +1973,342 @@ extern "C" int df_decode_members_buffer(int device, const uint8_t *in, size_t in
     if (rc != BZ_OK) return rc;
     *out_len = (size_t)n;
     return v;
+}
+
+// ---- reading BGZF (section 8 of the header; bgzf_index.h; kernels: k_bgzf_read.hip, k_bgzf_inflate / k_bgzf_check) ----------
+// The index comes from BSIZE and ISIZE (df_bgzf_index_buffer on the host, df_gpu_bgzf_index_device over a search's list);
+// a read decodes the blocks its range touches in ONE pass, each straight to its place, the at most two blocks the range
+// cuts through two slots of the workspace.
+static_assert(bgzf::kOk == BZ_OK && bgzf::kData == BZ_E_DATA && bgzf::kEof == BZ_E_EOF, "bgzf_index.h names the verdicts by value");
+
+extern "C" int df_gpu_last_bgzf_read_stats(bz_gpu_engine *g, uint64_t out[8])
+{
+    if (!g || !out) return BZ_E_PARAM;
+    for (int i = 0; i < 8; ++i) out[i] = g->df ? g->df->bgzf_read_stats[i] : 0;
+    return BZ_OK;
+}
+
+// candidates per list window, blocks per decode launch; read per call
+static u64 df_bgzf_batch()
+{
+    const u64 v = df_env_kib("BZ_DF_BGZF_BATCH", bgzf::kBatch);
+    return v < 1 ? 1 : v > (1u << 20) ? (1u << 20) : v;
+}
+
+// the index as the two malloc'ed arrays of the host call
+static int df_bgzf_index_out(const std::vector<u64> &c, const std::vector<u64> &u, uint64_t **coff, uint64_t **uoff)
+{
+    uint64_t *a = (uint64_t *)malloc(c.size() * 8), *b = (uint64_t *)malloc(u.size() * 8);
+    if (!a || !b) {
+        free(a);
+        free(b);
+        return BZ_E_NOMEM;
+    }
+    memcpy(a, c.data(), c.size() * 8);
+    memcpy(b, u.data(), u.size() * 8);
+    *coff = a;
+    *uoff = b;
+    return BZ_OK;
+}
+
+extern "C" int df_bgzf_index_buffer(const uint8_t *in, size_t in_len, uint64_t **coff, uint64_t **uoff, size_t *count, int32_t *verdict)
+{
+    if (!coff || !uoff || !count || !verdict || (in_len && !in)) return BZ_E_PARAM;
+    *coff = *uoff = nullptr;
+    *count = 0;
+    *verdict = BZ_OK;
+    std::vector<u64> c, u;
+    u64 ec = 0, eu = 0;
+    int v = BZ_OK;
+    (void)bgzf::chain_host(in, in_len, [&](u64 a, u64 b) { c.push_back(a); u.push_back(b); }, &ec, &eu, &v);
+    c.push_back(ec);
+    u.push_back(eu);
+    const int rc = df_bgzf_index_out(c, u, coff, uoff);
+    if (rc != BZ_OK) return rc;
+    *count = c.size() - 1;
+    *verdict = v;
+    return BZ_OK;
+}
+
+// The candidate list of a file in HBM, a window at a time: the counts per tile are kept, the positions and their blocks'
+// sizes are listed on demand (GzCands' way, with 64-bit positions).
+struct BgzfCands {
+    bz_gpu_engine *g = nullptr;
+    DfWorkspace *w = nullptr;
+    const u8 *in = nullptr;
+    u64 len = 0;
+    std::vector<u64> tpre; // per tile: the candidates in front of it; [ntiles]: all
+    u64 total = 0, sub = 0, first = 0, launches = 0;
+    std::vector<u64> win;  // candidates first .. first + win.size()
+    std::vector<BgzfInfo> info;
+
+    int count()
+    {
+        const u64 nt = (len + bgzf::kTile - 1) / bgzf::kTile;
+        if (nt >= (1ull << 31)) return BZ_E_PARAM;
+        const u32 ntiles = (u32)nt;
+        int rc = w->z_cnt.ensure((size_t)ntiles * 4);
+        if (rc == BZ_OK) rc = w->z_base.ensure((size_t)ntiles * 8);
+        if (rc != BZ_OK) return rc;
+        std::vector<u32> cnt(ntiles);
+        if (df_launch_bgzf_search_count(g->st, in, len, ntiles, w->z_cnt.as<u32>()) != 0) return BZ_E_UNEXPECTED;
+        HIPCHK(hipMemcpyAsync(cnt.data(), w->z_cnt.p, (size_t)ntiles * 4, hipMemcpyDeviceToHost, g->st));
+        HIPCHK(hipStreamSynchronize(g->st));
+        tpre.assign((size_t)ntiles + 1, 0);
+        for (u32 t = 0; t < ntiles; ++t) tpre[t + 1] = tpre[t] + cnt[t];
+        total = tpre[ntiles];
+        HIPCHK(hipMemcpyAsync(w->z_base.p, tpre.data(), (size_t)ntiles * 8, hipMemcpyHostToDevice, g->st));
+        HIPCHK(hipStreamSynchronize(g->st));
+        launches += 1;
+        return BZ_OK;
+    }
+    // candidates idx .. idx + n (cut at the list's end) become the window
+    int fetch(u64 idx, u64 n)
+    {
+        if (idx >= total) return BZ_E_UNEXPECTED;
+        n = std::min(n, total - idx);
+        const u32 t0 = (u32)(std::upper_bound(tpre.begin(), tpre.end(), idx) - tpre.begin() - 1);
+        const u32 t1 = (u32)(std::upper_bound(tpre.begin(), tpre.end(), idx + n - 1) - tpre.begin() - 1);
+        int rc = w->z_cand.ensure((size_t)n * 8);
+        if (rc == BZ_OK) rc = w->z_info.ensure((size_t)n * sizeof(BgzfInfo));
+        if (rc != BZ_OK) return rc;
+        if (df_launch_bgzf_search_list(g->st, in, len, t0, t1 - t0 + 1, w->z_base.as<u64>(), idx, (u32)n, w->z_cand.as<u64>()) != 0)
+            return BZ_E_UNEXPECTED;
+        if (df_launch_bgzf_block_info(g->st, in, len, w->z_cand.as<u64>(), (u32)n, w->z_info.as<BgzfInfo>()) != 0) return BZ_E_UNEXPECTED;
+        win.resize((size_t)n);
+        info.resize((size_t)n);
+        HIPCHK(hipMemcpyAsync(win.data(), w->z_cand.p, (size_t)n * 8, hipMemcpyDeviceToHost, g->st));
+        HIPCHK(hipMemcpyAsync(info.data(), w->z_info.p, (size_t)n * sizeof(BgzfInfo), hipMemcpyDeviceToHost, g->st));
+        HIPCHK(hipStreamSynchronize(g->st));
+        first = idx;
+        launches += 2;
+        return BZ_OK;
+    }
+    bool has(u64 idx) const { return idx >= first && idx < first + win.size(); }
+};
+
+extern "C" int df_gpu_bgzf_index_device(bz_gpu_engine *g, const void *d_in, size_t in_len, uint64_t *h_coff, uint64_t *h_uoff, size_t cap_blocks,
+                                        size_t *count, int32_t *verdict)
+{
+    if (!g || !count || !verdict || (in_len && !d_in) || ((uintptr_t)d_in & 15u)) return BZ_E_PARAM;
+    if (cap_blocks && (!h_coff || !h_uoff)) return BZ_E_PARAM;
+    *count = 0;
+    *verdict = BZ_OK;
+    DfWorkspace *w = nullptr;
+    const int wrc = df_workspace(g, &w);
+    if (wrc != BZ_OK) return wrc;
+    w->bgzf_read_stats[3] = w->bgzf_read_stats[4] = 0;
+    w->bgzf_index_s = 0;
+    const double t0 = df_now_ms();
+    BgzfCands cs;
+    cs.g = g;
+    cs.w = w;
+    cs.in = static_cast<const u8 *>(d_in);
+    cs.len = in_len;
+    cs.sub = df_bgzf_batch();
+    if (in_len) {
+        const int rc = cs.count();
+        if (rc != BZ_OK) return rc;
+    }
+    // the chain over the list: a position that is not in it is a header-rule failure; the candidates the chain steps over
+    // (a stored block whose payload is a BGZF file) are never looked at
+    u64 idx = 0, landed = 0, nblocks = 0, ec = 0, eu = 0;
+    int v = BZ_OK;
+    const int rc = bgzf::chain(
+        in_len,
+        [&](u64 pos, bool *ok, u32 *bsize1, u32 *isize) {
+            idx = std::max(idx, cs.tpre[(size_t)(pos / bgzf::kTile)]);
+            for (; idx < cs.total; ++idx) {
+                if (!cs.has(idx)) {
+                    const int frc = cs.fetch(idx, cs.sub);
+                    if (frc != BZ_OK) return frc;
+                }
+                const u64 c = cs.win[(size_t)(idx - cs.first)];
+                if (c < pos) continue;
+                if (c == pos) {
+                    const BgzfInfo bi = cs.info[(size_t)(idx - cs.first)];
+                    *ok = true;
+                    *bsize1 = bi.bsize1;
+                    *isize = bi.isize;
+                    ++landed;
+                    ++idx;
+                }
+                break;
+            }
+            return (int)BZ_OK;
+        },
+        [&](u64 a, u64 b) {
+            if (nblocks < cap_blocks) {
+                h_coff[nblocks] = a;
+                h_uoff[nblocks] = b;
+            }
+            ++nblocks;
+        },
+        &ec, &eu, &v);
+    if (rc != BZ_OK) return rc;
+    *count = (size_t)nblocks;
+    w->bgzf_read_stats[3] = cs.total;
+    w->bgzf_read_stats[4] = cs.total - landed;
+    w->bgzf_index_s = (df_now_ms() - t0) * 1e-3;
+    for (int i = 0; i < 6; ++i) w->t_stage[i] = 0;
+    w->t_stage[0] = w->t_stage[5] = w->bgzf_index_s;
+    if (nblocks > cap_blocks) return BZ_E_CAPACITY;
+    if (h_coff && h_uoff) { // (cap_blocks + 1 pairs of room: the last one is the end of the last complete block)
+        h_coff[nblocks] = ec;
+        h_uoff[nblocks] = eu;
+    }
+    *verdict = v;
+    return BZ_OK;
+}
+
+extern "C" int df_gpu_bgzf_read_device(bz_gpu_engine *g, const void *d_in, size_t in_len, const uint64_t *h_coff, const uint64_t *h_uoff, size_t count,
+                                       uint64_t ustart, uint64_t ulen, void *d_out, size_t cap, uint64_t *out_len, int32_t *verdict)
+{
+    if (!g || !out_len || !verdict || !h_coff || !h_uoff || (in_len && !d_in) || ((uintptr_t)d_in & 15u)) return BZ_E_PARAM;
+    *out_len = 0;
+    *verdict = BZ_OK;
+    if (g->df)
+        for (int i : {0, 1, 2, 5, 6, 7}) g->df->bgzf_read_stats[i] = 0; // (a call that launches nothing decodes nothing)
+    if (h_coff[count] > in_len || ustart < h_uoff[0]) return BZ_E_PARAM;
+    for (size_t k = 0; k < count; ++k)
+        if (h_coff[k + 1] <= h_coff[k] || h_uoff[k + 1] < h_uoff[k] || h_coff[k + 1] - h_coff[k] > bgzf::kMaxBlock ||
+            h_uoff[k + 1] - h_uoff[k] > bgzf::kMaxBlock)
+            return BZ_E_PARAM;
+    const u64 total = h_uoff[count];
+    if (ulen == 0 || ustart >= total) return BZ_OK;
+    const u64 uend = ulen < total - ustart ? ustart + ulen : total, rlen = uend - ustart;
+    if (!d_out) { // sizes only: the index says it all
+        *out_len = rlen;
+        return BZ_OK;
+    }
+    if (cap < rlen) {
+        *out_len = rlen;
+        return BZ_E_CAPACITY;
+    }
+    DfWorkspace *w = nullptr;
+    const int wrc = df_workspace(g, &w);
+    if (wrc != BZ_OK) return wrc;
+    u64 *rs = w->bgzf_read_stats;
+    rs[0] = rs[1] = rs[2] = rs[5] = rs[6] = rs[7] = 0;
+    u64 first = 0, last = 0;
+    bgzf::touched(h_uoff, count, ustart, uend, &first, &last);
+    const u64 batch = df_bgzf_batch();
+    const u8 *in8 = static_cast<const u8 *>(d_in);
+    u8 *out8 = static_cast<u8 *>(d_out);
+    int rc = w->z_slots.ensure(2 * (size_t)bgzf::kMaxBlock + 16);
+    if (rc != BZ_OK) return rc;
+    double t_dec = 0, t_chk = 0, t_copy = 0;
+    std::vector<BgzfDesc> desc;
+    std::vector<BgzfRec> rec;
+    u64 fault = ~0ull;
+    for (u64 a = first; a <= last && fault == ~0ull; a += batch) {
+        const u64 n = std::min<u64>(batch, last + 1 - a);
+        desc.clear();
+        std::vector<BgzfDesc> edges;
+        for (u64 k = a; k < a + n; ++k) {
+            BgzfDesc q = {};
+            q.coff = h_coff[k];
+            q.csize = (u32)(h_coff[k + 1] - h_coff[k]);
+            q.usize = (u32)(h_uoff[k + 1] - h_uoff[k]);
+            const u64 lo = std::max<u64>(ustart, h_uoff[k]), hi = std::min<u64>(uend, h_uoff[k + 1]);
+            q.dst = lo - ustart;
+            if (h_uoff[k] < ustart || h_uoff[k + 1] > uend) { // the range cuts it: through a slot
+                q.slot = k == first ? 1u : 2u;
+                q.lo = (u32)(lo - h_uoff[k]);
+                q.n = (u32)(hi - lo);
+                edges.push_back(q);
+            }
+            desc.push_back(q);
+        }
+        desc.insert(desc.end(), edges.begin(), edges.end()); // (the edge copy's table: behind the group's)
+        if ((rc = w->z_desc.ensure(desc.size() * sizeof(BgzfDesc))) != BZ_OK) return rc;
+        if ((rc = w->z_rec.ensure((size_t)n * sizeof(BgzfRec))) != BZ_OK) return rc;
+        const BgzfDesc *d_desc = w->z_desc.as<BgzfDesc>();
+        HIPCHK(hipMemcpyAsync(w->z_desc.p, desc.data(), desc.size() * sizeof(BgzfDesc), hipMemcpyHostToDevice, g->st));
+        HIPCHK(hipEventRecord(w->ev[0], g->st));
+        if (df_launch_bgzf_inflate(g->st, in8, d_desc, (u32)n, out8, w->z_slots.as<u8>(), w->z_rec.as<BgzfRec>()) != 0) return BZ_E_UNEXPECTED;
+        HIPCHK(hipEventRecord(w->ev[1], g->st));
+        if (df_launch_bgzf_check(g->st, d_desc, (u32)n, out8, w->z_slots.as<u8>(), w->z_rec.as<BgzfRec>()) != 0) return BZ_E_UNEXPECTED;
+        HIPCHK(hipEventRecord(w->ev[2], g->st));
+        if (!edges.empty() && df_launch_bgzf_edge_copy(g->st, d_desc + n, (u32)edges.size(), w->z_slots.as<u8>(), out8) != 0) return BZ_E_UNEXPECTED;
+        HIPCHK(hipEventRecord(w->ev[3], g->st));
+        rec.resize((size_t)n);
+        HIPCHK(hipMemcpyAsync(rec.data(), w->z_rec.p, (size_t)n * sizeof(BgzfRec), hipMemcpyDeviceToHost, g->st));
+        HIPCHK(hipStreamSynchronize(g->st));
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, w->ev[0], w->ev[1]);
+        t_dec += ms;
+        (void)hipEventElapsedTime(&ms, w->ev[1], w->ev[2]);
+        t_chk += ms;
+        (void)hipEventElapsedTime(&ms, w->ev[2], w->ev[3]);
+        t_copy += ms;
+        rs[0] += n;
+        rs[1] += n - edges.size();
+        rs[2] += edges.size();
+        rs[7] += edges.empty() ? 2 : 3;
+        for (u64 i = 0; i < n; ++i) {
+            rs[5] += rec[(size_t)i].len;
+            if (rec[(size_t)i].verdict != BZ_OK && fault == ~0ull) fault = a + i; // the lowest k decides
+        }
+    }
+    if (fault != ~0ull) {
+        *verdict = BZ_E_DATA;
+        *out_len = h_uoff[fault] > ustart ? h_uoff[fault] - ustart : 0;
+    } else *out_len = rlen;
+    rs[6] = *out_len;
+    // df_gpu_last_timings: [0] search and chain of the last index call [1] decode [2] checksums [3] edge copy [5] their sum
+    w->t_stage[0] = w->bgzf_index_s;
+    w->t_stage[1] = t_dec * 1e-3;
+    w->t_stage[2] = t_chk * 1e-3;
+    w->t_stage[3] = t_copy * 1e-3;
+    w->t_stage[4] = 0;
+    w->t_stage[5] = w->t_stage[0] + w->t_stage[1] + w->t_stage[2] + w->t_stage[3];
+    return BZ_OK;
+}
+
+// Host to host: the index on the host, the compressed bytes of the blocks touched up, one device call, the range down.
+extern "C" int df_bgzf_read_buffer(int device, const uint8_t *in, size_t in_len, uint64_t ustart, uint64_t ulen, uint8_t **out, size_t *out_len)
+{
+    if (!out || !out_len || (in_len && !in)) return BZ_E_PARAM;
+    *out = nullptr;
+    *out_len = 0;
+    std::vector<u64> c, u;
+    u64 ec = 0, eu = 0;
+    int vi = BZ_OK;
+    (void)bgzf::chain_host(in, in_len, [&](u64 a, u64 b) { c.push_back(a); u.push_back(b); }, &ec, &eu, &vi);
+    c.push_back(ec);
+    u.push_back(eu);
+    const u64 count = c.size() - 1, total = eu;
+    // the index's fault lies at uncompressed position `total`: inside or in front of a range that reaches behind it
+    const bool reaches = ulen != 0 && (ustart >= total || ulen > total - ustart);
+    const int v_index = reaches ? vi : BZ_OK;
+    if (ulen == 0 || ustart >= total) { // no bytes: no device
+        *out = (uint8_t *)malloc(1);
+        return *out ? v_index : BZ_E_NOMEM;
+    }
+    const u64 uend = ulen < total - ustart ? ustart + ulen : total, rlen = uend - ustart;
+    if (df_device_in_range(device) != BZ_OK) return BZ_E_NOGPU;
+    EngineLease lease(device, 2, 1);
+    if (lease.status() != BZ_OK) return lease.status();
+    bz_gpu_engine *g = lease.engine();
+    u64 first = 0, last = 0;
+    bgzf::touched(u.data(), count, ustart, uend, &first, &last);
+    const u64 cbase = c[(size_t)first] & ~(u64)15, clen = c[(size_t)last + 1] - cbase; // (the device call wants 16-byte alignment)
+    std::vector<u64> rc_off((size_t)(last - first + 2));
+    for (size_t k = 0; k < rc_off.size(); ++k) rc_off[k] = c[(size_t)first + k] - cbase;
+    uint64_t n = 0;
+    int32_t v = BZ_OK;
+    int rc = g->dec_in.ensure((size_t)clen + 64);
+    if (rc == BZ_OK) rc = g->oneshot_out.ensure((size_t)rlen + 64);
+    if (rc == BZ_OK && hipMemcpy(g->dec_in.p, in + cbase, (size_t)clen, hipMemcpyHostToDevice) != hipSuccess) rc = BZ_E_UNEXPECTED;
+    if (rc == BZ_OK)
+        rc = df_gpu_bgzf_read_device(g, g->dec_in.p, (size_t)clen, rc_off.data(), u.data() + first, (size_t)(last - first + 1), ustart, rlen,
+                                     g->oneshot_out.p, (size_t)rlen, &n, &v);
+    if (rc == BZ_OK) rc = df_download(out, g->oneshot_out.p, (size_t)n);
+    lease.settle(rc); // (the file's verdict is not the engine's business)
+    if (rc != BZ_OK) return rc;
+    *out_len = (size_t)n;
+    return v != BZ_OK ? v : v_index;
 }
 
 // ---- C ABI ------------------------------------------------------------------------------------------------

@@ -205,4 +205,35 @@ int df_launch_gz_search_list(hipStream_t st, const u8 *in, u32 len, u32 tile0, u
 int df_launch_gz_gather(hipStream_t st, const u8 *in, const GzSpan *spans, u32 count, u32 max_len, u8 *image);
 int df_launch_gz_zero_skip(hipStream_t st, const u8 *in, const u32 *from, const u32 *bound, u32 count, u32 *out);
 int df_launch_gz_compact(hipStream_t st, const u8 *staged, const GzSpan *spans, u32 count, u32 max_len, u8 *out);
+// ---- reading BGZF (bgzf_index.h; k_bgzf_read.hip, k_bgzf_inflate and k_bgzf_check in k_inflate.hip)
+struct BgzfInfo {
+    u32 bsize1; // BSIZE + 1 of a candidate
+    u32 isize;  // its ISIZE when the block lies whole inside the input and is at least 28 bytes, else 0
+};
+// the candidates per tile of bgzf::kTile positions; then, behind the host's exclusive sum (base: per tile of the INPUT, the
+// candidates in front of it), the candidates numbered [first, first + n) found in the tiles [tile0, tile0 + ntiles)
+int df_launch_bgzf_search_count(hipStream_t st, const u8 *in, u64 len, u32 ntiles, u32 *cnt);
+int df_launch_bgzf_search_list(hipStream_t st, const u8 *in, u64 len, u32 tile0, u32 ntiles, const u64 *base, u64 first, u32 n, u64 *list);
+int df_launch_bgzf_block_info(hipStream_t st, const u8 *in, u64 len, const u64 *list, u32 n, BgzfInfo *info);
+// One block of a read as its wave is told it: the index's word about it, and where its bytes go.
+struct BgzfDesc {
+    u64 coff;  // where the block starts, relative to the input
+    u64 dst;   // slot == 0: where its bytes go, relative to the output; else where its slice [lo, lo + n) goes
+    u32 csize; // coff[k + 1] - coff[k]: 1 .. 65536
+    u32 usize; // uoff[k + 1] - uoff[k]: 0 .. 65536
+    u32 slot;  // 0: written in place; 1, 2: an edge block, decoded into that 64 KiB slot of the workspace
+    u32 lo, n; // the slice of an edge block that belongs to the range
+    u32 pad;
+};
+struct BgzfRec {
+    int verdict;  // BZ_OK or BZ_E_DATA
+    u32 len;      // bytes produced
+    u32 check;    // the trailer's CRC-32
+    u32 nblk[3];  // stored, fixed, dynamic Deflate blocks decoded whole
+    u32 pad[2];
+};
+int df_launch_bgzf_inflate(hipStream_t st, const u8 *in, const BgzfDesc *desc, u32 count, u8 *out, u8 *slots, BgzfRec *rec);
+int df_launch_bgzf_check(hipStream_t st, const BgzfDesc *desc, u32 count, const u8 *out, const u8 *slots, BgzfRec *rec);
+// the slices of the edge blocks (descriptors with slot != 0; `count` of them, at most two) from their slots into the output
+int df_launch_bgzf_edge_copy(hipStream_t st, const BgzfDesc *desc, u32 count, const u8 *slots, u8 *out);
 } // namespace dfgpu

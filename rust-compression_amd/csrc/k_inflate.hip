@@ -49,6 +49,7 @@
 #include "k_deflate.h"
 #include "k_df_fold.h"
 #include "inf_split.h"
+#include "bgzf_index.h"
 
 namespace dfgpu {
 using namespace bzgpu;
@@ -998,6 +999,279 @@ __global__ __launch_bounds__(256) void k_df_inflate_check(const u8 *__restrict__
         ok = ((B << 16) | A) == rec[j].check;
     } else ok = df_crc_finish(raw, len) == rec[j].check && rec[j].isize == len;
     if (!ok) rec[j].verdict = BZ_E_DATA;
+}
+
+// ---- reading BGZF (include/bz2_mi355x.h section 8; DESIGN_deflate.md "Reading BGZF")
+// One wave per block of the index, ONE pass: the block's length comes from BSIZE and its output's length from ISIZE, both
+// checked against the index here, so the bytes go straight to their place.  This is k_df_inflate<true, false>'s loop for
+// kind 0 -- a copy, as inf_decode is, so that the kernels above stay the machine code they were -- with another entry and
+// another end: the lanes check the header rule (bgzf_index.h) at the block's coff, which may have any byte phase (the
+// reader starts at the 4-aligned byte in front of it, 18 + phase bytes in: inf_seek, and `total` counts from there);
+// `limit` is ISIZE; the output may start at any byte; every fault is BZ_E_DATA, running out of bits included (the cut is
+// BSIZE's, not the file's); a clean block produces exactly ISIZE bytes and ends in the byte in front of its trailer.  A
+// distance that reaches in front of the block's first byte is a fault although the block in front lies right there.
+// An edge block (slot != 0) is decoded into its 64 KiB slot of the workspace instead.  Stores are clipped to `limit`.
+__global__ __launch_bounds__(64) void k_bgzf_inflate(const u8 *__restrict__ in, const BgzfDesc *__restrict__ desc, u8 *out_all, u8 *slots,
+                                                     BgzfRec *rec)
+{
+    __shared__ u16 s_tl[1u << kLBits], s_td[1u << kDBits], s_tc[1u << kCBits];
+    __shared__ u16 s_sl[288], s_sd[32], s_sc[32];
+    __shared__ u32 s_nl[16], s_nd[16], s_nc[16];
+    __shared__ u8 s_cl[320], s_clen[32];
+    const u32 lane = threadIdx.x, j = blockIdx.x;
+    const BgzfDesc q = desc[j];
+    u8 *const out = q.slot ? slots + (size_t)(q.slot - 1u) * bgzf::kMaxBlock : out_all + q.dst;
+    const u32 limit = q.usize;
+    const u32 phase = (u32)q.coff & 3u;
+    InfIn r;
+    r.base = in + (q.coff - phase);
+    r.len = phase + q.csize - bgzf::kTrailer;
+    r.buf = 0;
+    r.cnt = 0;
+    r.nextw = 0;
+    r.cw = 0;
+    r.cbase = 0xFFFFFF00u;
+    const u64 total = 8ull * r.len;
+    u32 p = 0, npend = 0, lit = 0, fenced = 0;
+    u32 nblk0 = 0, nblk1 = 0, nblk2 = 0, check = 0;
+    int verdict = BZ_OK;
+    bool fixed_ready = false;
+    u32 maxl = 0, maxd = 0;
+    bool head_ok = false;
+    if (q.csize >= bgzf::kMinBlock && q.csize <= bgzf::kMaxBlock) { // lanes 0 .. 17: the header's bytes, 18 .. 25: the trailer's
+        u32 hb = 0;
+        if (lane < bgzf::kHeader) hb = in[q.coff + lane];
+        else if (lane < bgzf::kHeader + bgzf::kTrailer) hb = in[q.coff + q.csize - (bgzf::kHeader + bgzf::kTrailer) + lane];
+#define BG_B(l) ((u32)__builtin_amdgcn_readlane((int)hb, (l)))
+#define BG_W(l) (BG_B(l) | BG_B((l) + 1) << 8 | BG_B((l) + 2) << 16 | BG_B((l) + 3) << 24)
+        const u32 bsize1 = (BG_B(16) | BG_B(17) << 8) + 1u, isize = BG_W(22);
+        check = BG_W(18);
+        head_ok = bgzf::header_words(BG_W(0), BG_W(8), BG_W(12)) && bsize1 == q.csize && isize == q.usize;
+#undef BG_B
+#undef BG_W
+    }
+
+#define INF_FLUSH()                                                                   \
+    do {                                                                              \
+        if (npend) {                                                                  \
+            const u32 q_ = p - npend + lane;                                          \
+            if (lane < npend && q_ < limit) out[q_] = (u8)lit;                        \
+        }                                                                             \
+        npend = 0;                                                                    \
+    } while (0)
+#define INF_FAIL()                                                                    \
+    do {                                                                              \
+        verdict = BZ_E_DATA;                                                          \
+        goto done;                                                                    \
+    } while (0)
+// (bits behind the Deflate bytes are zeros to the reader: having used one is the block's fault; so is a byte too many)
+#define INF_EOF_CHECK()                                                               \
+    do {                                                                              \
+        if (inf_consumed(r) > total || p > limit) INF_FAIL();                         \
+    } while (0)
+
+    if (!head_ok) INF_FAIL();
+    inf_seek(r, phase + bgzf::kHeader, lane);
+    for (;;) {
+        inf_fill(r, lane);
+        const u32 bfinal = inf_take(r, 1), btype = inf_take(r, 2);
+        INF_EOF_CHECK();
+        if (btype == 3u) INF_FAIL();
+        if (btype == 0u) {
+            (void)inf_take(r, r.cnt & 7u);
+            inf_fill(r, lane);
+            const u32 ln = inf_take(r, 16), nl = inf_take(r, 16);
+            INF_EOF_CHECK();
+            if ((ln ^ nl) != 0xFFFFu) INF_FAIL();
+            const u32 bytepos = (u32)(inf_consumed(r) >> 3);
+            if ((u64)bytepos + ln > r.len) INF_FAIL();
+            INF_FLUSH();
+            for (u32 i = lane; i < ln; i += 64u)
+                if (p + i < limit) out[p + i] = r.base[bytepos + i];
+            p += ln;
+            if (p > limit) INF_FAIL();
+            inf_seek(r, bytepos + ln, lane);
+            ++nblk0;
+        } else {
+            if (btype == 1u) {
+                if (!fixed_ready) {
+                    __syncthreads();
+                    for (u32 i = lane; i < 320u; i += 64u) s_cl[i] = (u8)(i < 144u ? 8u : i < 256u ? 9u : i < 280u ? 7u : i < 288u ? 8u : 5u);
+                    __syncthreads();
+                    u32 ns;
+                    (void)inf_build(s_cl, 288, s_tl, kLBits, s_nl, s_sl, lane, ns, maxl);
+                    (void)inf_build(s_cl + 288, 32, s_td, kDBits, s_nd, s_sd, lane, ns, maxd);
+                    fixed_ready = true;
+                }
+            } else {
+                fixed_ready = false;
+                const u32 hlit = inf_take(r, 5) + 257u, hdist = inf_take(r, 5) + 1u, hclen = inf_take(r, 4) + 4u;
+                INF_EOF_CHECK();
+                if (hlit > 286u || hdist > 30u) INF_FAIL();
+                __syncthreads();
+                if (lane < 19u) s_clen[lane] = 0;
+                __syncthreads();
+                for (u32 k = 0; k < hclen; ++k) {
+                    inf_fill(r, lane);
+                    const u32 v = inf_take(r, 3);
+                    if (lane == 0) s_clen[c_cl_order[k]] = (u8)v;
+                }
+                INF_EOF_CHECK();
+                __syncthreads();
+                u32 ns, maxc;
+                if (inf_build(s_clen, 19, s_tc, kCBits, s_nc, s_sc, lane, ns, maxc) != 0) INF_FAIL();
+                const u32 ncl = hlit + hdist;
+                u32 i = 0, prev = 0;
+                while (i < ncl) {
+                    inf_fill(r, lane);
+                    const int sy = inf_sym(r, s_tc, kCBits, s_nc, s_sc);
+                    if (sy < 0) INF_FAIL();
+                    if (sy < 16) {
+                        INF_EOF_CHECK();
+                        if (lane == 0) s_cl[i] = (u8)sy;
+                        prev = (u32)sy;
+                        ++i;
+                        continue;
+                    }
+                    u32 rep, val = 0;
+                    if (sy == 16) {
+                        rep = 3u + inf_take(r, 2);
+                        val = prev;
+                    } else if (sy == 17) rep = 3u + inf_take(r, 3);
+                    else rep = 11u + inf_take(r, 7);
+                    INF_EOF_CHECK();
+                    if ((sy == 16 && i == 0) || i + rep > ncl) INF_FAIL();
+                    for (u32 k = lane; k < rep; k += 64u) s_cl[i + k] = (u8)val;
+                    prev = val;
+                    i += rep;
+                }
+                __syncthreads();
+                if (s_cl[256] == 0) INF_FAIL(); // no end-of-block code
+                const int rl = inf_build(s_cl, hlit, s_tl, kLBits, s_nl, s_sl, lane, ns, maxl);
+                if (rl != 0) INF_FAIL();
+                const int rd = inf_build(s_cl + hlit, hdist, s_td, kDBits, s_nd, s_sd, lane, ns, maxd);
+                if (rd == 1 || (rd == 2 && !(ns == 0u || (ns == 1u && maxd == 1u)))) INF_FAIL();
+            }
+            // ---- the codes of the block
+            for (;;) {
+                inf_fill(r, lane);
+                const int sy = inf_sym(r, s_tl, kLBits, s_nl, s_sl);
+                if (sy < 0) INF_FAIL();
+                if (sy < 256) {
+                    if (lane == npend) lit = (u32)sy;
+                    ++npend;
+                    ++p;
+                    INF_EOF_CHECK();
+                    if (npend == 64u) INF_FLUSH();
+                    continue;
+                }
+                if (sy == 256) {
+                    INF_EOF_CHECK();
+                    break;
+                }
+                if (sy > 285) INF_FAIL();
+                const u32 len = c_len_base[sy - 257] + inf_take(r, c_len_extra[sy - 257]);
+                inf_fill(r, lane);
+                const int ds = inf_sym(r, s_td, kDBits, s_nd, s_sd);
+                if (ds < 0) INF_FAIL();
+                if (ds > 29) INF_FAIL();
+                const u32 d = c_dist_base[ds] + inf_take(r, c_dist_extra[ds]);
+                INF_EOF_CHECK();
+                if (d > p) INF_FAIL(); // in front of the block's first byte
+                INF_FLUSH();
+                {
+                    const u32 span = d < len ? d : len;
+                    if (p - d + span > fenced) {
+                        __threadfence_block();
+                        fenced = p;
+                    }
+                    const u8 *src = out + (p - d);
+                    for (u32 b = 0; b < len; b += 64u) {
+                        const u32 i = b + lane;
+                        if (i < len && p + i < limit) out[p + i] = src[d >= len ? i : i % d];
+                    }
+                }
+                p += len;
+                if (p > limit) INF_FAIL();
+            }
+            if (btype == 1u) ++nblk1;
+            else ++nblk2;
+        }
+        if (bfinal) break;
+    }
+    // exactly ISIZE bytes, and the stream ends in the byte in front of the trailer
+    (void)inf_take(r, r.cnt & 7u);
+    if (p != limit || inf_consumed(r) != total) verdict = BZ_E_DATA;
+done:
+    INF_FLUSH();
+    if (lane == 0) {
+        BgzfRec o;
+        o.verdict = verdict;
+        o.len = p;
+        o.check = check;
+        o.nblk[0] = nblk0;
+        o.nblk[1] = nblk1;
+        o.nblk[2] = nblk2;
+        o.pad[0] = o.pad[1] = 0;
+        rec[j] = o;
+    }
+#undef INF_FLUSH
+#undef INF_FAIL
+#undef INF_EOF_CHECK
+}
+
+// The CRC-32 of every clean block's bytes against its trailer, a workgroup per block: k_df_inflate_check's fold for an
+// output that starts at ANY byte -- thread 0 takes the bytes in front of the first multiple of 16 with its slice, every
+// slice behind starts at a multiple of 16 and is read in 16-byte loads.  A mismatch turns the verdict to BZ_E_DATA.
+__global__ __launch_bounds__(256) void k_bgzf_check(const BgzfDesc *__restrict__ desc, const u8 *__restrict__ out_all, const u8 *__restrict__ slots,
+                                                    BgzfRec *rec)
+{
+    __shared__ u32 s_tab[256];
+    __shared__ u32 s_c[256];
+    const u32 tid = threadIdx.x, j = blockIdx.x;
+    if (rec[j].verdict != BZ_OK) return;
+    const BgzfDesc q = desc[j];
+    const u32 len = q.usize;
+    {
+        u32 c = tid;
+        for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
+        s_tab[tid] = c;
+    }
+    __syncthreads();
+    const u8 *src = q.slot ? slots + (size_t)(q.slot - 1u) * bgzf::kMaxBlock : out_all + q.dst;
+    const u32 head = (16u - (u32)((uintptr_t)src & 15u)) & 15u;
+    const u32 slice = (((len + 255u) >> 8) + 15u) & ~15u;
+    const u32 lo = tid == 0 ? 0u : (head + tid * slice < len ? head + tid * slice : len);
+    const u32 hi = head + (tid + 1u) * slice < len ? head + (tid + 1u) * slice : len;
+    u64 a = 0, b = 0; // (the Adler sums of df_fold_byte: not used)
+    u32 c = 0;
+    u32 i = lo;
+    for (; i < hi && ((uintptr_t)(src + i) & 15u); ++i) df_fold_byte(src[i], 0, s_tab, a, b, c);
+    for (; i + 16 <= hi; i += 16) {
+        const u32x4_t v = *reinterpret_cast<const u32x4_t *>(src + i);
+        const u32 w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (u32 k = 0; k < 16; ++k) df_fold_byte((w[k >> 2] >> (8 * (k & 3u))) & 0xFFu, 0, s_tab, a, b, c);
+    }
+    for (; i < hi; ++i) df_fold_byte(src[i], 0, s_tab, a, b, c);
+    s_c[tid] = df_gf_mul(c, df_gf_xpow8(len - hi));
+    __syncthreads();
+    if (tid != 0) return;
+    u32 raw = 0;
+    for (u32 t = 0; t < 256; ++t) raw ^= s_c[t];
+    if (df_crc_finish(raw, len) != rec[j].check) rec[j].verdict = BZ_E_DATA;
+}
+
+int df_launch_bgzf_inflate(hipStream_t st, const u8 *in, const BgzfDesc *desc, u32 count, u8 *out, u8 *slots, BgzfRec *rec)
+{
+    hipLaunchKernelGGL(k_bgzf_inflate, dim3(count), dim3(64), 0, st, in, desc, out, slots, rec);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int df_launch_bgzf_check(hipStream_t st, const BgzfDesc *desc, u32 count, const u8 *out, const u8 *slots, BgzfRec *rec)
+{
+    hipLaunchKernelGGL(k_bgzf_check, dim3(count), dim3(256), 0, st, desc, out, slots, rec);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int df_launch_inflate(hipStream_t st, bool write, const u8 *in, const u64 *in_off, const u64 *in_len, u32 count, int kind, u8 *out,

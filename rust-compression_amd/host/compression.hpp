@@ -527,6 +527,57 @@ inline Result<std::vector<uint8_t>> bgzf_compress(const uint8_t *in, size_t n, u
     return R::Ok(std::move(file));
 }
 
+// Reading BGZF (include/bz2_mi355x.h section 8).  The index of a file in host memory: the BSIZE chain, walked on the host
+// (parsing, not decoding: no GPU is needed).  coff / uoff hold count + 1 entries -- the .gzi table, and the last pair the
+// end of the last complete block; verdict is the chain's: the blocks in front of a fault are still indexed.
+struct BgzfIndex {
+    std::vector<uint64_t> coff, uoff;
+    int verdict = BZ_OK;
+    size_t blocks() const { return coff.empty() ? 0 : coff.size() - 1; }
+    uint64_t total() const { return uoff.empty() ? 0 : uoff.back() - uoff.front(); }
+};
+inline Result<BgzfIndex> bgzf_index(const uint8_t *in, size_t n)
+{
+    using R = Result<BgzfIndex>;
+    uint64_t *c = nullptr, *u = nullptr;
+    size_t count = 0;
+    int32_t v = BZ_OK;
+    const int rc = df_bgzf_index_buffer(in, n, &c, &u, &count, &v);
+    if (rc != BZ_OK) return R::Err(from_status(rc));
+    BgzfIndex ix;
+    ix.coff.assign(c, c + count + 1);
+    ix.uoff.assign(u, u + count + 1);
+    ix.verdict = v;
+    bz_free(c);
+    bz_free(u);
+    return R::Ok(std::move(ix));
+}
+// The uncompressed bytes [ustart, ustart + ulen) of a BGZF file, clamped to its end (df_bgzf_read_buffer): only the blocks
+// the range touches are uploaded and decoded.  A fault in front of or inside the range is the Err; `partial`, when not
+// null, receives the range's bytes in front of it.  Range reads pay off for ranges of many blocks, not for one record.
+inline Result<std::vector<uint8_t>> bgzf_read(const uint8_t *in, size_t n, uint64_t ustart, uint64_t ulen, int device = 0,
+                                              std::vector<uint8_t> *partial = nullptr)
+{
+    using R = Result<std::vector<uint8_t>>;
+    uint8_t *out = nullptr;
+    size_t len = 0;
+    const int rc = df_bgzf_read_buffer(device, in, n, ustart, ulen, &out, &len);
+    std::vector<uint8_t> bytes;
+    if (out) {
+        bytes.assign(out, out + len);
+        bz_free(out);
+    }
+    if (rc != BZ_OK) {
+        if (partial) *partial = std::move(bytes);
+        return R::Err(from_status(rc));
+    }
+    return R::Ok(std::move(bytes));
+}
+inline Result<std::vector<uint8_t>> bgzf_decompress(const uint8_t *in, size_t n, int device = 0, std::vector<uint8_t> *partial = nullptr)
+{
+    return bgzf_read(in, n, 0, UINT64_MAX, device, partial);
+}
+
 // DecodeIterator (src/traits/decoder.rs:45-86)
 template <class I, class S, class D> class DecodeIterator {
   public:

@@ -82,4 +82,11 @@ extern "C" {
     pub fn df_gpu_bgzf_encode_device(g: *mut c_void, d_in: *const c_void, n: usize, block_bytes: u32, eof: i32, d_out: *mut c_void, cap: usize, out_len: *mut u64, h_block_off: *mut u64) -> i32;
     pub fn df_gpu_last_bgzf_stats(g: *mut c_void, out: *mut u64) -> i32;
     pub fn df_bgzf_encode_buffer(device: i32, input: *const u8, n: usize, block_bytes: u32, eof: i32, out: *mut *mut u8, out_len: *mut usize, block_off: *mut u64) -> i32;
+
+    // section 8: reading BGZF (the index from BSIZE, range reads; *coff, *uoff and *out are released with bz_free)
+    pub fn df_bgzf_index_buffer(input: *const u8, in_len: usize, coff: *mut *mut u64, uoff: *mut *mut u64, count: *mut usize, verdict: *mut i32) -> i32;
+    pub fn df_gpu_bgzf_index_device(g: *mut c_void, d_in: *const c_void, in_len: usize, h_coff: *mut u64, h_uoff: *mut u64, cap_blocks: usize, count: *mut usize, verdict: *mut i32) -> i32;
+    pub fn df_gpu_bgzf_read_device(g: *mut c_void, d_in: *const c_void, in_len: usize, h_coff: *const u64, h_uoff: *const u64, count: usize, ustart: u64, ulen: u64, d_out: *mut c_void, cap: usize, out_len: *mut u64, verdict: *mut i32) -> i32;
+    pub fn df_gpu_last_bgzf_read_stats(g: *mut c_void, out: *mut u64) -> i32;
+    pub fn df_bgzf_read_buffer(device: i32, input: *const u8, in_len: usize, ustart: u64, ulen: u64, out: *mut *mut u8, out_len: *mut usize) -> i32;
 }

@@ -134,6 +134,62 @@ pub fn bgzf_encode(input: &[u8], block_bytes: u32, eof: bool) -> Result<(Vec<u8>
     Ok((file, off))
 }
 
+/// The block index of a BGZF file (`df_bgzf_index_buffer`): `coff[k]` / `uoff[k]` are where block `k` starts in the file and
+/// in the uncompressed bytes, `count + 1` entries each, the last pair being the end of the last complete block -- the
+/// `.gzi` table.  `verdict` is the chain's (0, or the status of a `DataError` / `UnexpectedEof`): the blocks in front of a
+/// fault are still indexed.
+pub struct BgzfIndex {
+    pub coff: Vec<u64>,
+    pub uoff: Vec<u64>,
+    pub verdict: i32,
+}
+
+/// The BSIZE chain of a BGZF file, walked on the host: parsing, not decoding -- no GPU is needed.
+pub fn bgzf_index(input: &[u8]) -> Result<BgzfIndex, CompressionError> {
+    let mut c: *mut u64 = core::ptr::null_mut();
+    let mut u: *mut u64 = core::ptr::null_mut();
+    let mut count: usize = 0;
+    let mut verdict: i32 = 0;
+    let rc = unsafe { ffi::df_bgzf_index_buffer(input.as_ptr(), input.len(), &mut c, &mut u, &mut count, &mut verdict) };
+    if rc != ffi::BZ_OK {
+        note_status(rc);
+        return Err(CompressionError::from_status(rc));
+    }
+    let coff = unsafe { core::slice::from_raw_parts(c, count + 1) }.to_vec();
+    let uoff = unsafe { core::slice::from_raw_parts(u, count + 1) }.to_vec();
+    unsafe {
+        ffi::bz_free(c as *mut core::ffi::c_void);
+        ffi::bz_free(u as *mut core::ffi::c_void);
+    }
+    Ok(BgzfIndex { coff, uoff, verdict })
+}
+
+/// The uncompressed bytes `[ustart, ustart + ulen)` of a BGZF file, clamped to its end (`df_bgzf_read_buffer`, device 0):
+/// only the blocks the range touches are uploaded and decoded.  `Err` carries the bytes of the range in front of the
+/// fault.  Range reads pay off for ranges of many blocks, not for one record.
+pub fn bgzf_read(input: &[u8], ustart: u64, ulen: u64) -> Result<Vec<u8>, (CompressionError, Vec<u8>)> {
+    let mut out: *mut u8 = core::ptr::null_mut();
+    let mut len: usize = 0;
+    let rc = unsafe { ffi::df_bgzf_read_buffer(0, input.as_ptr(), input.len(), ustart, ulen, &mut out, &mut len) };
+    let bytes = if out.is_null() {
+        Vec::new()
+    } else {
+        let b = unsafe { core::slice::from_raw_parts(out, len) }.to_vec();
+        unsafe { ffi::bz_free(out as *mut core::ffi::c_void) };
+        b
+    };
+    if rc != ffi::BZ_OK {
+        note_status(rc);
+        return Err((CompressionError::from_status(rc), bytes));
+    }
+    Ok(bytes)
+}
+
+/// A whole BGZF file: `bgzf_read` over everything.
+pub fn bgzf_decode(input: &[u8]) -> Result<Vec<u8>, (CompressionError, Vec<u8>)> {
+    bgzf_read(input, 0, u64::MAX)
+}
+
 /// Many independent streams in one call (`bz_decode_batch`, device 0): element `i` of the result is what
 /// `inputs[i].iter().cloned().decode(&mut BZip2Decoder::new())` yields -- `Ok(bytes)`, or the `BZip2Error` with the bytes
 /// the iterator hands out in front of it.  An entry's verdict is its own: a bad one hides nothing behind it.  The outer
