@@ -646,6 +646,8 @@ def fill_crcs(streams, oracle):
 class Case:
     def __init__(self, name, z, status, data=None, multi=False, cap=None):
         self.name, self.z, self.status, self.data, self.multi, self.cap = name, z, status, data, multi, cap
+        self.images = self.flips = None  # families h and i: the block images, and what is xored into each CRC
+        self.no_oracle = False           # True: the oracle has no answer for this stream (see family_h)
 
     def __repr__(self):
         return "Case(%s, %d bytes, status %d)" % (self.name, len(self.z), self.status)
@@ -1076,7 +1078,706 @@ def family_g(oracle):
     return out
 
 
-FAMILIES = ("a", "b", "c", "d", "e", "f", "g")
+# ---------------------------------------------------------------------------- families h and i: stage D4
+# The last decode stage (the RLE1 undo and the block CRC) is fed IMAGES: what the walk yields, chosen byte by byte,
+# wrapped into a block with the image's true BWT.  The expected bytes are rle1_undo's, never a decoder's.
+#
+# The tiling of the stage, each constant where rust-compression_amd/csrc/k_dec.hip has it:
+SUB = 64              # k_dec_rle_sub: image bytes per sub-tile (`p = sub * 64u`)
+WAVE = 64 * SUB       # k_dec_rle_expand: one lane per sub-tile, 64 sub-tiles (4 096 image bytes) per wave
+GROUP = 4 * WAVE      # k_dec_rle_expand: four waves (16 384 image bytes) per workgroup (`blockIdx.x * 4u + w`)
+CHAIN = 1024          # k_dec_rle_chain: threads per block; each folds K = ceil(nsub / 1024) sub-tiles
+EXP_STAGE = 8192      # kExpStage: a wave stages its output in LDS when total + shift <= 8192
+PIECE = 16            # k_dec_crc: bytes per piece, aligned in memory
+TILE_PIECES = 256     # k_dec_crc: pieces per tile (one per thread)
+SLICE_PIECES = 4096   # k_dec_crc: pieces per workgroup (16 tiles)
+NO_COUNT = -100       # the oracle's answer to a block that ends behind four equal bytes, at any capacity
+
+
+def share_k(n):
+    """sub-tiles per thread of k_dec_rle_chain for an image of n bytes"""
+    nsub = (n + SUB - 1) // SUB
+    return (nsub + CHAIN - 1) // CHAIN
+
+
+def rle1_parse(image):
+    """(image as uint8 array, mask of the bytes that are counts, True when the image ends behind four equal bytes
+    with no count).  The state machine of decoder.rs:555-577, run by run: inside a run of equal bytes that starts
+    fresh every fifth byte is a count, and a run of 5 k + 4 bytes takes the byte behind it as its count."""
+    x = np.frombuffer(bytes(image), np.uint8)
+    n = len(x)
+    is_count = np.zeros(n, bool)
+    if n == 0:
+        return x, is_count, False
+    brk = np.flatnonzero(x[1:] != x[:-1]) + 1
+    starts = np.concatenate([[0], brk])
+    ends = np.concatenate([brk, [n]])
+    long_ = ends - starts >= 4  # (a run whose first byte was eaten as a count only gets shorter)
+    eaten, pending = -1, False
+    for s, e in zip(starts[long_].tolist(), ends[long_].tolist()):
+        if s == eaten:
+            s += 1
+        if e - s < 4:
+            continue
+        is_count[s + 4:e:5] = True
+        if (e - s) % 5 == 4:
+            if e < n:
+                is_count[e] = True
+                eaten = e
+            else:
+                pending = True
+    return x, is_count, pending
+
+
+def rle1_undo(image):
+    """(bytes, ends_in_count): the plain RLE1 undo of an image; ends_in_count is True when the image ends behind
+    four equal bytes (the count is missing: the bytes are then those in front of it)"""
+    x, is_count, pending = rle1_parse(image)
+    reps = np.where(is_count, x, 1).astype(np.int64)
+    vals = x.copy()
+    idx = np.flatnonzero(is_count)
+    vals[idx] = x[idx - 1]
+    return np.repeat(vals, reps).tobytes(), pending
+
+
+def rle1_states(x, is_count):
+    """per image byte: the entering state in the kernel's terms (0 fresh, 1..3 that many equal bytes in front,
+    4 this byte is a count)"""
+    n = len(x)
+    fresh = np.ones(n, bool)
+    fresh[1:] = ((x[1:] != x[:-1]) & ~is_count[1:]) | is_count[:-1]
+    start = np.maximum.accumulate(np.where(fresh, np.arange(n), 0))
+    e = (np.arange(n) - start) % 5
+    assert np.array_equal(e == 4, is_count)
+    return e
+
+
+def block_from_image(image, crc=None, flip=0):
+    """a block whose walk yields `image`: its true BWT, as blocks_from_bytes makes it, without the RLE1 encoder in
+    front.  The CRC is that of rle1_undo(image) (`flip` is xored into it)."""
+    from oracle import oracle
+    image = bytes(image)
+    sa = oracle.bwt(image)
+    sym, freq, orig, n_in_use = oracle.mtf_zle(image, sa)
+    in_use = sorted(set(image))
+    assert len(in_use) == n_in_use
+    lens = oracle.bzip2_code_lengths(freq[:n_in_use + 2], 17)[0]
+    if crc is None:
+        crc = oracle.crc32_bzip2(rle1_undo(image)[0])
+    return Block(sym, [lens, lens], [0] * ((len(sym) + G_SIZE - 1) // G_SIZE), in_use, orig, crc=crc ^ flip)
+
+
+# ---- a model of the three-step undo and of the CRC geometry, for the mutants of tests/test_bzforge.py ----------
+RLE_MUTANTS = ("exit ignores nxt", "exit for cnt==4 dropped", "e=4 run byte from X[p]",
+               "count equal to run byte extends the run", "K share rounded down", "staging test uses <",
+               "flush drops tail bytes", "flush drops head bytes")
+CRC_MUTANTS = ("leading lo bytes not zeroed", "ragged branch for a full last piece", "last-tile cover ends at piece edge",
+               "initial value uses R")
+FILL = 0xA5  # what the model's output memory holds where nothing was written
+
+
+def _rle_steps(X, n, last, cnt, mut, emit):
+    """64 steps of the state machine over the rows of X (sub-tiles) for any number of state columns; returns
+    (out sizes, last, cnt) and, with emit, the per-byte (repeat, value) arrays of column 0"""
+    nsub = X.shape[0]
+    p0 = np.arange(nsub) * SUB
+    out = np.zeros(last.shape, np.int64)
+    reps = np.zeros((nsub, SUB), np.int64)
+    vals = np.zeros((nsub, SUB), np.uint8)
+    for k in range(SUB):
+        valid = (p0 + k < n)[:, None]
+        b = X[:, k].astype(np.int64)[:, None]
+        is4 = cnt == 4
+        if mut == "count equal to run byte extends the run":
+            is4 = is4 & (b != last)
+            lit_at_4 = (cnt == 4) & (b == last)
+        eq = (b == last) & ~is4
+        if emit:
+            reps[:, k] = np.where(valid, np.where(is4, b, 1), 0)[:, 0]
+            vals[:, k] = np.where(is4, last, b)[:, 0].astype(np.uint8)
+        out += np.where(valid, np.where(is4, b, 1), 0)
+        nl = np.where(is4, 0x100, np.where(eq, last, b))
+        nc = np.where(is4, 0, np.where(eq, cnt + 1, 1))
+        if mut == "count equal to run byte extends the run":
+            nc = np.where(lit_at_4, 4, nc)
+        last = np.where(valid, nl, last)
+        cnt = np.where(valid, nc, cnt)
+    return out, last, cnt, reps, vals
+
+
+def tiled_undo(image, phase=0, mut=None):
+    """(bytes, None | NO_COUNT, per wave True = staged): the undo as stage D4 tiles it -- tabulate every sub-tile
+    for five entering states, compose along the block in 1024 shares, replay every sub-tile, flush staged waves as
+    dwords and end bytes.  `phase` is the address of the block's first output byte mod 4; `mut` one of
+    RLE_MUTANTS.  Memory nothing writes holds FILL."""
+    x = np.frombuffer(bytes(image), np.uint8)
+    n = len(x)
+    nsub = (n + SUB - 1) // SUB
+    xp = np.concatenate([x, np.zeros(nsub * SUB + 1 - n, np.uint8)])
+    X = xp[:nsub * SUB].reshape(nsub, SUB)
+    p0 = np.arange(nsub) * SUB
+    # tabulate (k_dec_rle_sub)
+    b0 = X[:, 0].astype(np.int64)
+    last = np.stack([np.full(nsub, 0x100), b0, b0, b0, np.full(nsub, 0x100)], 1)
+    cnt = np.tile(np.arange(5), (nsub, 1))
+    t_out, last, cnt, _, _ = _rle_steps(X, n, last, cnt, mut, False)
+    nxt = np.where(p0 + SUB < n, xp[np.minimum(p0 + SUB, len(xp) - 1)].astype(np.int64), 0x200)[:, None]
+    if mut == "exit ignores nxt":
+        t_ex = np.where(cnt == 4, 4, cnt)
+    elif mut == "exit for cnt==4 dropped":
+        t_ex = np.where(last == nxt, cnt, 0)
+    else:
+        t_ex = np.where(cnt == 4, 4, np.where(last == nxt, cnt, 0))
+    t_ex = np.minimum(t_ex, 4)
+    # compose (k_dec_rle_chain): every thread folds its share for the five states, thread 0 links them
+    K = nsub // CHAIN if mut == "K share rounded down" else (nsub + CHAIN - 1) // CHAIN
+    j = np.arange(CHAIN)
+    s0 = j * K
+    s1 = np.minimum(s0 + K, nsub)
+    e = np.tile(np.arange(5), (CHAIN, 1))
+    off = np.zeros((CHAIN, 5), np.int64)
+    for t in range(K):
+        s = s0 + t
+        ok = (s < s1)[:, None]
+        sc = np.minimum(s, nsub - 1)[:, None]
+        off = off + np.where(ok, t_out[sc, e], 0)
+        e = np.where(ok, t_ex[sc, e], e)
+    in_e = np.zeros(CHAIN, np.int64)
+    in_off = np.zeros(CHAIN, np.int64)
+    ce, co = 0, 0
+    for t in range(CHAIN):
+        in_e[t], in_off[t] = ce, co
+        co += int(off[t, ce])
+        ce = int(e[t, ce])
+    out_len = co
+    if ce == 4:
+        return b"", NO_COUNT, []
+    sub_e = np.zeros(nsub, np.int64)
+    soff = np.zeros(nsub + 1, np.int64)
+    soff[nsub] = out_len
+    ce, co = in_e.copy(), in_off.copy()
+    for t in range(K):
+        s = s0 + t
+        ok = s < s1
+        sc = np.minimum(s, nsub - 1)
+        sub_e[sc[ok]] = ce[ok]
+        soff[sc[ok]] = co[ok]
+        co = co + np.where(ok, t_out[sc, ce], 0)
+        ce = np.where(ok, t_ex[sc, ce], ce)
+    # replay (k_dec_rle_expand), 64 waves at a time
+    out = np.full(out_len + 8, FILL, np.uint8)
+    staged_log = []
+    prev = np.concatenate([[0], xp[p0[1:] - 1]]).astype(np.int64) if nsub > 1 else np.zeros(1, np.int64)
+    run4 = b0 if mut == "e=4 run byte from X[p]" else prev
+    r_last = np.where(sub_e == 0, 0x100, np.where(sub_e == 4, run4, b0))[:, None]
+    r_cnt = sub_e[:, None]
+    step = 64 * 64
+    for c0 in range(0, nsub, step):
+        c1 = min(c0 + step, nsub)
+        _, _, _, reps, vals = _rle_steps(X[c0:c1], n - c0 * SUB, r_last[c0:c1], r_cnt[c0:c1], mut, True)
+        o_in = np.cumsum(reps, 1) - reps
+        subs = np.arange(c0, c1)
+        wave0 = (subs // 64) * 64
+        base = soff[wave0]
+        total = soff[np.minimum(wave0 + 64, nsub)] - base
+        shift = (phase + base) & 3
+        lim = EXP_STAGE - 1 if mut == "staging test uses <" else EXP_STAGE
+        staged = total + shift <= lim
+        staged_log += staged[::64].tolist()
+        # position of every emitted byte inside its wave's output, then its fate
+        keep = reps.ravel() > 0
+        rp = reps.ravel()[keep]
+        w_pos = np.repeat((soff[subs][:, None] - base[:, None] + o_in).ravel()[keep], rp)
+        w_pos = w_pos + (np.arange(len(w_pos)) - np.repeat(np.cumsum(rp) - rp, rp))
+        rows = np.repeat(np.repeat(np.arange(c1 - c0), SUB)[keep], rp)
+        v = np.repeat(vals.ravel()[keep], rp)
+        st, sh, tot, bs = staged[rows], shift[rows], total[rows], base[rows]
+        sp = w_pos + sh  # byte index in the staging buffer
+        first, lastb = sh, sh + tot
+        dw0, dw1 = (first + 3) // 4, lastb // 4
+        ok = np.ones(len(v), bool)
+        ok &= ~st | ((sp < EXP_STAGE + 8) & (sp < lastb))  # (the flush copies [first, lastb) only)
+        if mut == "flush drops tail bytes":
+            ok &= ~(st & (dw0 <= dw1) & (sp >= dw1 * 4))
+        if mut == "flush drops head bytes":
+            ok &= ~(st & (dw0 <= dw1) & (sp < dw0 * 4))
+        d = bs + w_pos
+        ok &= (d >= 0) & (d < len(out))
+        out[d[ok]] = v[ok]
+    return out[:out_len].tobytes(), None, staged_log
+
+
+_CRC_TAB = []
+
+
+def _crc_tab():
+    if not _CRC_TAB:
+        t = []
+        for i in range(256):
+            c = i << 24
+            for _ in range(8):
+                c = ((c << 1) ^ 0x04C11DB7) & 0xFFFFFFFF if c & 0x80000000 else (c << 1) & 0xFFFFFFFF
+            t.append(c)
+        _CRC_TAB.append(np.array(t, np.uint64))
+    return _CRC_TAB[0]
+
+
+def _gf_mul(a, b):
+    """a * b in GF(2)[x] / 0x104C11DB7 (numpy uint64 arrays or ints that hold 32 bits)"""
+    a = np.asarray(a, np.uint64)
+    b = np.asarray(b, np.uint64)
+    r = np.zeros(np.broadcast(a, b).shape, np.uint64)
+    M = np.uint64(0xFFFFFFFF)
+    for i in range(31, -1, -1):
+        r = ((r << np.uint64(1)) & M) ^ np.where(r & np.uint64(0x80000000), np.uint64(0x04C11DB7), np.uint64(0))
+        r = r ^ np.where((b >> np.uint64(i)) & np.uint64(1), a, np.uint64(0))
+    return r
+
+
+_XP = {}
+
+
+def _xpow_bytes(nbytes):
+    """x^(8 nbytes) mod P; nbytes is taken mod 2^64 as the kernel's u64 would be"""
+    if not _XP:
+        xp2 = [0x100]
+        for _ in range(63):
+            xp2.append(int(_gf_mul(xp2[-1], xp2[-1])))
+        xp16 = [1]
+        for _ in range(255):
+            xp16.append(int(_gf_mul(xp16[-1], xp2[4])))
+        _XP["xp2"], _XP["xp16"] = xp2, np.array(xp16, np.uint64)
+    nbytes &= (1 << 64) - 1
+    r, k = 1, 0
+    while nbytes:
+        if nbytes & 1:
+            r = int(_gf_mul(r, _XP["xp2"][k]))
+        nbytes >>= 1
+        k += 1
+    return r
+
+
+def crc_model(mem, A, ln, mut=None):
+    """the CRC of mem[A:A + ln] as k_dec_crc folds it: aligned 16-byte pieces from (A & ~15) on, 256-piece tiles,
+    4096-piece slices.  `mem` is a uint8 array whose index 0 stands at a 16-byte aligned address and which has 16
+    spare bytes at its end; `mut` one of CRC_MUTANTS."""
+    tab = _crc_tab()
+    _xpow_bytes(0)
+    xp16 = _XP["xp16"]
+    a0 = A & ~15
+    R = A - a0 + ln
+    npieces = (R + 15) // 16
+    total = 0
+    for sl in range(max(1, (npieces + SLICE_PIECES - 1) // SLICE_PIECES)):
+        p0 = sl * SLICE_PIECES
+        s_tile = []
+        for tile in range(16):
+            i = p0 + tile * TILE_PIECES + np.arange(TILE_PIECES, dtype=np.int64)
+            i = i[i < npieces]
+            if not len(i):
+                s_tile.append(0)
+                continue
+            by = mem[a0 + i[0] * 16:a0 + (i[-1] + 1) * 16].reshape(len(i), 16).astype(np.uint64)
+            pbeg = i * 16
+            pend = np.minimum(pbeg + 16, R)
+            lo = np.where(i == 0, 0 if mut == "leading lo bytes not zeroed" else A - a0, 0)
+            hi = pend - pbeg
+            c = np.zeros(len(i), np.uint64)
+            for k in range(16):
+                b = np.where(k >= lo, by[:, k], np.uint64(0))
+                nc = tab[((c >> np.uint64(24)) ^ b).astype(np.int64)] ^ ((c << np.uint64(8)) & np.uint64(0xFFFFFFFF))
+                c = np.where(k < hi, nc, c)
+            last = min(p0 + tile * TILE_PIECES + TILE_PIECES - 1, npieces - 1)
+            if last == npieces - 1 and ((R & 15) or mut == "ragged branch for a full last piece"):
+                c2 = _gf_mul(_gf_mul(c, xp16[np.clip(last - 1 - i, 0, 255)]), _xpow_bytes(R & 15))
+            else:
+                c2 = _gf_mul(c, xp16[last - i])
+            c = np.where(pend == R, c, c2)
+            s_tile.append(int(np.bitwise_xor.reduce(c)))
+        acc, end_piece = 0, 0
+        for tile in range(16):
+            first = p0 + tile * TILE_PIECES
+            if first >= npieces:
+                break
+            lastp = min(first + TILE_PIECES - 1, npieces - 1)
+            cover_end = R if lastp == npieces - 1 and mut != "last-tile cover ends at piece edge" else (lastp + 1) * 16
+            acc = int(_gf_mul(acc, _xpow_bytes(cover_end - first * 16))) ^ s_tile[tile]
+            end_piece = cover_end
+        if npieces:
+            acc = int(_gf_mul(acc, _xpow_bytes(R - end_piece)))
+        if sl == 0:
+            acc ^= int(_gf_mul(0xFFFFFFFF, _xpow_bytes(R if mut == "initial value uses R" else ln)))
+        total ^= acc
+    return total ^ 0xFFFFFFFF
+
+
+# ---- targets ----------------------------------------------------------------------------------------------------------
+H_EDGES = ("sub", "wave", "group", "share2", "share14")
+H_COUNTS = (0, 1, 3, 4, 251, 252, 255)
+H_SELF_V = (0, 1, 4, 5, 255)
+H_SELF_N = tuple(n for n in list(range(1, 12)) + [63, 64, 65, 4095, 4096, 4097, 16383, 16384, 16385, 70001]
+                 if n % 5 != 4)  # (n = 5 k + 4 ends behind four equal bytes: no count)
+I_PIECES = (1, 2, 255, 256, 257, 4095, 4096, 4097, 8191, 8192, 8193)
+
+
+def _required_h():
+    r = set()
+    for edge in H_EDGES:
+        r |= {"H edge=%s e=0" % edge, "H edge=%s e=4" % edge}
+        for e in (1, 2, 3):
+            r |= {"H edge=%s e=%d goes on" % (edge, e), "H edge=%s e=%d breaks" % (edge, e)}
+    for at in ("", " at sub edge"):
+        r |= {"H count=%d%s" % (c, at) for c in H_COUNTS}
+        r |= {"H count==run byte" + at, "H byte after count equals run byte" + at}
+    r |= {"H self v=%d n=%d" % (v, n) for v in H_SELF_V for n in H_SELF_N}
+    r |= {"H period5 n<64", "H period5 n>=4096", "H sub out>=3300"}
+    r |= {"H end n%64=0", "H end n%64=1", "H end n%64=63", "H end n=1", "H end count=0", "H end count=255",
+          "H end equal=1", "H end equal=2", "H end equal=3"}
+    r |= {"H stage total+shift=%d shift=%d" % (t, s) for t in (8191, 8192, 8193) for s in range(4)}
+    r |= {"H seam %s shift=%d" % (k, s) for k in ("staged|direct", "direct|staged") for s in range(4)}
+    r |= {"H total<4 shift=%d" % s for s in (1, 2, 3)}
+    # the one-dword branch of the flush (dw0 > dw1) needs shift + total < 4: shift 3 never takes it
+    r |= {"H one-dword flush shift=1", "H one-dword flush shift=2"}
+    r |= {"H no count only", "H no count middle", "H no count last"}
+    return r
+
+
+def _required_i():
+    r = {"I a=%d r=%d" % (a, q) for a in range(16) for q in range(16)}
+    r |= {"I pieces=%d last=%s a=%d" % (p, l, a) for p in I_PIECES for l in ("full", "ragged") for a in (0, 1, 15)}
+    r.discard("I pieces=1 last=ragged a=15")  # (R = 15 + len >= 16: one piece behind 15 bytes is a full one)
+    r |= {"I wrong crc pieces=1", "I wrong crc ragged tile seam", "I wrong crc slice seam"}
+    return r
+
+
+REQUIRED = {"h": _required_h(), "i": _required_i()}
+
+
+def _hits_h_image(image, phase):
+    """targets one block's image reaches, its first output byte at an address = phase (mod 4)"""
+    h = set()
+    x, is_count, pending = rle1_parse(image)
+    n = len(x)
+    e = rle1_states(x, is_count)
+    reps = np.where(is_count, x, 1).astype(np.int64)
+    cpad = np.concatenate([is_count, np.zeros(8, bool)])
+    K = share_k(n)
+    P = np.arange(SUB, n, SUB)
+    if len(P):
+        full = (e[P] == 0) & cpad[P + 4]  # four equal bytes and their count begin at the edge
+        kinds = {"sub": P % WAVE != 0, "wave": (P % WAVE == 0) & (P % GROUP != 0), "group": P % GROUP == 0,
+                 "share2": (P % (2 * SUB) == 0) & (K == 2), "share14": (P % (14 * SUB) == 0) & (K == 14)}
+        what = {"e=0": full, "e=4": is_count[P]}
+        for c in (1, 2, 3):
+            what["e=%d goes on" % c] = (e[P] == c) & cpad[P + 4 - c]
+            what["e=%d breaks" % c] = full & (x[P] != x[P - 1]) & ~is_count[P - 1] & (e[P - 1] == c - 1)
+        for kn, km in kinds.items():
+            for wn, wm in what.items():
+                if np.any(km & wm):
+                    h.add("H edge=%s %s" % (kn, wn))
+    ci = np.flatnonzero(is_count)
+    xpad = np.concatenate([x.astype(np.int64), np.full(8, -1)])
+    for at, sel in (("", ci), (" at sub edge", ci[ci % SUB == 0])):
+        for c in set(x[sel].tolist()) & set(H_COUNTS):
+            h.add("H count=%d%s" % (c, at))
+        if np.any(x[sel] == x[sel - 1]):
+            h.add("H count==run byte" + at)
+        if np.any((xpad[sel + 1] == x[sel - 1]) & cpad[sel + 5]):
+            h.add("H byte after count equals run byte" + at)
+    if n and np.all(x == x[0]) and int(x[0]) in H_SELF_V and n in H_SELF_N:
+        h.add("H self v=%d n=%d" % (x[0], n))
+    if n >= 10 and n % 5 == 0 and np.array_equal(x, np.tile(x[:5], n // 5)) and len(set(x[:4].tolist())) == 1 \
+            and x[4] != x[0]:
+        h.add("H period5 n<64" if n < 64 else "H period5 n>=4096" if n >= 4096 else "H period5")
+    outpos = np.concatenate([[0], np.cumsum(reps)])
+    subs = np.arange(0, n, SUB)
+    if np.any(outpos[np.minimum(subs + SUB, n)] - outpos[subs] >= 3300):
+        h.add("H sub out>=3300")
+    if not pending:
+        if n % 64 in (0, 1, 63):
+            h.add("H end n%%64=%d" % (n % 64))
+        if n == 1:
+            h.add("H end n=1")
+        if is_count[-1] and int(x[-1]) in (0, 255):
+            h.add("H end count=%d" % x[-1])
+        if not is_count[-1] and 1 <= e[-1] + 1 <= 3:
+            h.add("H end equal=%d" % (e[-1] + 1))
+    # waves of k_dec_rle_expand
+    w0 = np.arange(0, n, WAVE)
+    base = outpos[w0]
+    total = outpos[np.minimum(w0 + WAVE, n)] - base
+    shift = (phase + base) & 3
+    staged = total + shift <= EXP_STAGE
+    for t, s, sg in zip(total.tolist(), shift.tolist(), staged.tolist()):
+        if t + s in (8191, 8192, 8193):
+            h.add("H stage total+shift=%d shift=%d" % (t + s, s))
+        if 0 < t < 4 and s:
+            h.add("H total<4 shift=%d" % s)
+        if 0 < t and s and t + s < 4:
+            h.add("H one-dword flush shift=%d" % s)
+    for w in range(1, len(w0)):
+        if staged[w - 1] != staged[w]:
+            h.add("H seam %s shift=%d" % ("staged|direct" if staged[w - 1] else "direct|staged", shift[w]))
+    return h, pending, int(outpos[-1])
+
+
+def hits(case, k=0):
+    """the named targets a case of family h or i reaches, recomputed from its images with the tiling constants
+    above; k is the address of the stream's first output byte mod 16"""
+    h = set()
+    pos = k
+    fam = case.name[0]
+    nblk = len(case.images)
+    for bi, image in enumerate(case.images):
+        if fam == "H":
+            hh, pending, ln = _hits_h_image(image, pos & 3)
+            if pending:
+                h.add("H no count " + ("only" if nblk == 1 else "last" if bi == nblk - 1 else "middle"))
+                break
+            h |= hh
+        else:
+            ln = len(rle1_undo(image)[0])
+            a = pos & 15
+            R = a + ln
+            npieces = (R + 15) // 16
+            ragged = bool(R & 15)
+            if ln <= 48:
+                h.add("I a=%d r=%d" % (a, R & 15))
+            if npieces in I_PIECES and a in (0, 1, 15):
+                h.add("I pieces=%d last=%s a=%d" % (npieces, "ragged" if ragged else "full", a))
+            if case.flips and case.flips[bi]:
+                if npieces == 1:
+                    h.add("I wrong crc pieces=1")
+                if npieces == TILE_PIECES + 1 and ragged:
+                    h.add("I wrong crc ragged tile seam")
+                if npieces == SLICE_PIECES + 1:
+                    h.add("I wrong crc slice seam")
+                break
+        pos += ln
+    return h & REQUIRED[fam.lower()]
+
+
+# ---- images -------------------------------------------------------------------------------------------------------------
+def norun(rng, n):
+    """n bytes, no two neighbours equal"""
+    if n == 0:
+        return np.zeros(0, np.uint8)
+    return (np.cumsum(1 + rng.integers(0, 254, n)) % 256).astype(np.uint8)
+
+
+def _other(rng, *avoid):
+    while True:
+        v = int(rng.integers(0, 256))
+        if v not in avoid:
+            return v
+
+
+def plant(x, P, e, breaks, count, rng):
+    """write a group v v v v count into x so that position P falls behind e of its equal bytes (e = 4: on the
+    count); with `breaks`, e bytes of another value u stand in front of P and the group begins at P"""
+    if breaks:
+        s = P - e
+        u = _other(rng, int(x[s - 1]))
+        x[s:P] = u
+        g = P
+    else:
+        g = P - e
+        u = int(x[g - 1])
+    v = _other(rng, u)
+    x[g:g + 4] = v
+    x[g + 4] = v if count is None else count
+
+
+_EDGE_VARIANTS = [(0, False), (1, False), (2, False), (3, False), (1, True), (2, True), (3, True), (4, False)]
+
+
+def image_with_total(rng, total, n_lit):
+    """an image whose undo has exactly `total` bytes: about n_lit literals without runs, then groups of count 255
+    with changing run bytes, then one group or a few literals for the rest"""
+    n_lit = min(n_lit, total)
+    rest = total - n_lit
+    if 0 < rest < 4:
+        n_lit, rest = total, 0
+    parts = [norun(rng, n_lit)]
+    prev = int(parts[0][-1]) if n_lit else -1
+    while rest:
+        take = min(rest, 259)
+        if rest - take in (1, 2, 3):
+            take -= 4
+        v = _other(rng, prev)
+        parts.append(np.array([v, v, v, v, take - 4], np.uint8))
+        prev = -1  # (behind a count everything is fresh)
+        rest -= take
+    return np.concatenate(parts).tobytes()
+
+
+def _img_case(name, images, status=0, flips=None, cut=None, **kw):
+    """a case from block images: expected bytes from rle1_undo of the blocks in front of `cut` (all of them when
+    None)"""
+    blocks = [block_from_image(im, flip=(flips[i] if flips else 0)) for i, im in enumerate(images)]
+    z = write(Stream(9, blocks))
+    data = b"".join(rle1_undo(im)[0] for im in (images if cut is None else images[:cut]))
+    c = Case(name, z, status, data, multi=len(images) > 1, **kw)
+    c.images, c.flips = [bytes(im) for im in images], flips
+    c.no_oracle = False
+    return c
+
+
+_MEMO = {}
+
+
+def family_h(oracle):
+    """the RLE1 undo at its tile seams (stage D4): run groups at chosen phases against sub-tile, wave, workgroup
+    and thread-share edges, the count values and a count equal to its run byte, self-similar images, image ends,
+    waves on both sides of the staging threshold at every dword phase, and blocks that end behind four equal bytes.
+    Expected bytes come from rle1_undo."""
+    if "h" in _MEMO:
+        return _MEMO["h"]
+    rng = np.random.default_rng(808)
+    out = []
+    counts = list(H_COUNTS) + [None]  # None: the count equals the run byte
+    # sub-tile, wave and workgroup edges: one block per variant, 16 384 + 200 bytes
+    images = []
+    for vi, (e, brk) in enumerate(_EDGE_VARIANTS):
+        x = norun(rng, GROUP + 200)
+        for j, P in enumerate((GROUP, WAVE, 3 * WAVE, SUB, 7 * SUB, WAVE + SUB, GROUP - SUB, GROUP + SUB)):
+            plant(x, P, e, brk, counts[(vi + j) % len(counts)], rng)
+        images.append(x)
+    out.append(_img_case("H-edges-sub-wave-group", images))
+    # thread shares of two sub-tiles (65 537..131 072 image bytes) and of fourteen (899 981)
+    for name, n in (("share2", 70000), ("share14", 899981)):
+        x = norun(rng, n)
+        K = share_k(n)
+        assert K == (2 if name == "share2" else 14)
+        edges = [K * SUB * j for j in range(1, n // (K * SUB))]
+        picks = [edges[i * (len(edges) - 1) // 23] for i in range(24)]  # the first, the last, and between
+        for i, P in enumerate(picks):
+            e, brk = _EDGE_VARIANTS[i % 8]
+            plant(x, P, e, brk, counts[(i // 8 + i) % len(counts)], rng)
+        out.append(_img_case("H-edges-%s" % name, [x], cap=8 << 20))
+    # counts: every value, a count equal to its run byte, a fresh run behind a count; each also with the count
+    # as the first byte of a sub-tile
+    x = norun(rng, 40 * SUB)
+    P = SUB
+    for at_edge in (False, True):
+        for c in counts:
+            plant(x, P if at_edge else P + 17, 4, False, c, rng)
+            P += 2 * SUB
+        g = P - 4 if at_edge else P + 9   # a a a a 00 a a a a 02
+        a = _other(rng, int(x[g - 1]), int(x[g + 10]), 0, 2)
+        x[g:g + 10] = [a, a, a, a, 0, a, a, a, a, 2]
+        P += 2 * SUB
+    out.append(_img_case("H-counts", [x]))
+    # self-similar images: the parse has period 5 against tiles of 64
+    for v in H_SELF_V:
+        out.append(_img_case("H-self-%d" % v, [bytes([v]) * n for n in H_SELF_N], cap=16 << 20))
+    out.append(_img_case("H-period5", [bytes([97, 97, 97, 97, 3]) * 3, bytes([0, 0, 0, 0, 255]) * 1000,
+                                       bytes([7, 7, 7, 7, 0]) * 13, bytes([4, 4, 4, 4, 5]) * 900]))
+    # image ends
+    ends = [norun(rng, 128), norun(rng, 65), norun(rng, 63), norun(rng, 1)]
+    for tail in ([9, 9, 9, 9, 0], [9, 9, 9, 9, 255], [9], [9, 9], [9, 9, 9]):
+        b = norun(rng, 100)
+        b[-1] = 8
+        ends.append(np.concatenate([b, np.array(tail, np.uint8)]))
+    out.append(_img_case("H-ends", ends))
+    # staging: one-wave blocks on both sides of the threshold at every phase; fillers of 1-3 bytes set the phase
+    images, pos = [], 0
+
+    def at_phase(s):
+        nonlocal pos
+        f = (s - pos) % 4
+        if f:
+            images.append(norun(rng, f))
+            pos += f
+
+    def add(im):
+        nonlocal pos
+        images.append(im)
+        pos += len(rle1_undo(im)[0])
+
+    for s in range(4):
+        for t in (8191, 8192, 8193):
+            at_phase(s)
+            add(image_with_total(rng, t - s, 3900))
+    for s in range(4):  # a staged wave, a wave of count-255 groups (direct), a staged one
+        at_phase(s)
+        v = _other(rng)
+        mid = np.tile(np.array([v, v, v, v, 255], np.uint8), 819)
+        add(np.concatenate([norun(rng, WAVE - 1), [_other(rng, v)], mid, [_other(rng, v)], norun(rng, 1000)]).astype(np.uint8))
+    for s in (1, 2, 3):  # a last wave of one to three bytes, and whole blocks that small
+        at_phase(s)
+        add(norun(rng, WAVE + s))
+        for t in (1, 2, 3):
+            at_phase(s)
+            add(norun(rng, t))
+    out.append(_img_case("H-staging", images))
+    # four equal bytes and no count: DataError, the blocks in front intact, nothing of that block.  The oracle,
+    # like the reference, reads on around the closed pointer chain and answers -100 at any capacity, so these
+    # cases are not compared with it (no_oracle).
+    good = [norun(rng, 300), norun(rng, 77)]
+    bad = np.concatenate([norun(rng, 200), np.array([5, 6, 6, 6, 6], np.uint8)])
+    for name, imgs, cut in (("only", [bad], 0), ("middle", [good[0], bad, good[1]], 1), ("last", [good[0], bad], 1)):
+        c = _img_case("H-no-count-%s" % name, imgs, status=E_DATA, cut=cut)
+        c.no_oracle = True
+        c.multi = len(imgs) > 1
+        out.append(c)
+    # 899 981 bytes of ff: fourteen sub-tiles per thread, every sub-tile near its largest output (46.6 MB)
+    out.append(_img_case("H-ff-899981", [b"\xff" * 899981], cap=64 << 20))
+    _MEMO["h"] = out
+    return out
+
+
+def _euler_circuit(k):
+    """a closed walk over the complete directed graph on k nodes with loops that takes every edge once"""
+    nxt = {a: list(range(k)) for a in range(k)}
+    stack, walk = [0], []
+    while stack:
+        a = stack[-1]
+        if nxt[a]:
+            stack.append(nxt[a].pop())
+        else:
+            walk.append(stack.pop())
+    return walk[::-1]
+
+
+def family_i(oracle):
+    """the block CRC at every geometry of k_dec_crc: all 256 pairs of (address of the first byte, end) mod 16 on
+    blocks of 1-48 bytes, piece counts around the tile (256) and slice (4096) seams with a full and a ragged last
+    piece at alignments 0, 1 and 15, and a wrong stored CRC at three of these"""
+    if "i" in _MEMO:
+        return _MEMO["i"]
+    rng = np.random.default_rng(909)
+    out = []
+    walk = _euler_circuit(16)
+    assert len(walk) == 257 and walk[0] == 0
+    images = []
+    for a, r in zip(walk, walk[1:]):
+        ln = (r - a) % 16 + 16 * int(rng.integers(0, 3))
+        images.append(image_with_total(rng, ln or 16 * int(rng.integers(1, 4)), 6))
+    out.append(_img_case("I-grid", images))
+    for a in (0, 1, 15):
+        images, pos = [], 0
+        for p in I_PIECES:
+            for ragged in (False, True):
+                if p == 1 and ragged and a == 15:
+                    continue
+                f = (a - pos) % 16
+                if f:
+                    images.append(image_with_total(rng, f, 16))
+                    pos += f
+                R = 16 * p - (int(rng.integers(1, 16 - (a if p == 1 else 0))) if ragged else 0)
+                images.append(image_with_total(rng, R - a, 100))
+                pos += R - a
+        out.append(_img_case("I-pieces-a%d" % a, images))
+    for name, a, R in (("one-piece", 3, 9), ("ragged-tile-seam", 5, 16 * 256 + 7), ("slice-seam", 15, 16 * 4096 + 16)):
+        images = [image_with_total(rng, 16 + a, 16), image_with_total(rng, R - a, 100), norun(rng, 40)]
+        out.append(_img_case("I-wrong-crc-%s" % name, images, status=E_DATA, flips=[0, 1 << int(rng.integers(0, 32)), 0],
+                             cut=2))
+    _MEMO["i"] = out
+    return out
+
+
+FAMILIES = ("a", "b", "c", "d", "e", "f", "g", "h", "i")
 
 
 def all_cases(oracle, families=FAMILIES):
