@@ -1,5 +1,5 @@
 // k_bgzf_read.hip -- reading BGZF (include/bz2_mi355x.h section 8, DESIGN_deflate.md "Reading BGZF"): the kernels around the
-// one-pass decode (k_bgzf_inflate and k_bgzf_check live beside the decoder they copy, in k_inflate.hip).
+// one-pass decode (k_bgzf_inflate instantiates the decode loop of k_inflate.hip and lives there, with k_bgzf_check).
 //
 // k_bgzf_search<false>: candidates per tile of bgzf::kTile byte positions; <true>: behind the host's exclusive sum, the
 //   candidates numbered [first, first + n) as an ascending list of 64-bit positions.  A candidate is a position at which

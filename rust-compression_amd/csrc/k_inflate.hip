@@ -3,6 +3,12 @@
 // decoder (src/deflate/decoder.rs), which swallows errors; the container header checks are the reference's
 // (src/zlib/decoder.rs:78-90, src/gzip/decoder.rs:92-108, 175-191).
 //
+// ONE DECODE LOOP, three uses.  inf_decode<USE, WRITE, DICT> is the block loop -- block header, stored block, fixed and dynamic
+// tables, codes, copies, the end -- written once; the comment at it lists the places where the uses differ, each settled at
+// compile time.  A kernel keeps what is its own: how the reader is positioned and which header is checked, the call, the
+// record written.  k_df_inflate: a whole entry per wave; k_df_inflate_piece: a piece of a split entry per wave (inf_split.h);
+// k_bgzf_inflate: a BGZF block per wave.  What follows describes the loop by its first use.
+//
 // k_df_inflate<WRITE, DICT>: one 64-lane workgroup (one wave) per entry, from the entry's first bit to its last.  Everything that
 // steers the decode -- bit buffer, positions, the symbol just decoded -- is wave-uniform; the lanes share the work that
 // has width: building the tables, staging the input, storing literals, copying matches.
@@ -41,7 +47,7 @@
 // q = p - d + (i mod d) < 0 is dictw[W + q] -- a signed index per lane; out + (p - d) is never formed for p < d.  Nobody writes
 // the window, so a read from it needs no fence: `fenced` concerns q >= 0 only.  The zlib header then wants FDICT and, as
 // DICTID, the Adler-32 of the whole dictionary (`dict_adler`).  The DICT = false instantiations never look at the three
-// trailing parameters: they are the kernels as they were, instruction for instruction.
+// trailing parameters.
 #include <hip/hip_runtime.h>
 
 #include "../../include/bz2_mi355x.h"
@@ -58,10 +64,12 @@ namespace {
 constexpr u32 kLBits = 10, kDBits = 9, kCBits = 7;
 
 __constant__ u8 c_cl_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-__constant__ u16 c_len_base[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
-__constant__ u8 c_len_extra[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
-__constant__ u16 c_dist_base[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
-__constant__ u8 c_dist_extra[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
+// a length / distance code's base value and extra bits in ONE word (base | bits << 16): one load per code, so the value
+// never waits for a second load behind the first
+#define X(base, bits) ((base) | (bits) << 16)
+__constant__ u32 c_len_code[29] = {X(3, 0), X(4, 0), X(5, 0), X(6, 0), X(7, 0), X(8, 0), X(9, 0), X(10, 0), X(11, 1), X(13, 1), X(15, 1), X(17, 1), X(19, 2), X(23, 2), X(27, 2), X(31, 2), X(35, 3), X(43, 3), X(51, 3), X(59, 3), X(67, 4), X(83, 4), X(99, 4), X(115, 4), X(131, 5), X(163, 5), X(195, 5), X(227, 5), X(258, 0)};
+__constant__ u32 c_dist_code[30] = {X(1, 0), X(2, 0), X(3, 0), X(4, 0), X(5, 1), X(7, 1), X(9, 2), X(13, 2), X(17, 3), X(25, 3), X(33, 4), X(49, 4), X(65, 5), X(97, 5), X(129, 6), X(193, 6), X(257, 7), X(385, 7), X(513, 8), X(769, 8), X(1025, 9), X(1537, 9), X(2049, 10), X(3073, 10), X(4097, 11), X(6145, 11), X(8193, 12), X(12289, 12), X(16385, 13), X(24577, 13)};
+#undef X
 
 __device__ __forceinline__ u32 uni(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
 
@@ -194,304 +202,6 @@ __device__ __forceinline__ int inf_build(const u8 *lens, u32 n, u16 *tab, u32 tb
     __syncthreads();
     return left > 0 ? 2 : 0;
 }
-} // namespace
-
-template <bool WRITE, bool DICT>
-__global__ __launch_bounds__(64) void k_df_inflate(const u8 *__restrict__ in, const u64 *__restrict__ in_off, const u64 *__restrict__ in_len,
-                                                   int kind, u8 *out_all, const u64 *__restrict__ out_off, DfInfRec *rec,
-                                                   const u8 *__restrict__ dictw, u32 W, u32 dict_adler)
-{
-    __shared__ u16 s_tl[1u << kLBits], s_td[1u << kDBits], s_tc[1u << kCBits];
-    __shared__ u16 s_sl[288], s_sd[32], s_sc[32];
-    __shared__ u32 s_nl[16], s_nd[16], s_nc[16];
-    __shared__ u8 s_cl[320], s_clen[32];
-    const u32 lane = threadIdx.x, j = blockIdx.x;
-    InfIn r;
-    r.base = in + in_off[j];
-    r.len = (u32)in_len[j];
-    r.buf = 0;
-    r.cnt = 0;
-    r.nextw = 0;
-    r.cw = 0;
-    r.cbase = 0xFFFFFF00u;
-    const u64 total = 8ull * r.len;
-    u8 *out = WRITE ? out_all + out_off[j] : nullptr;
-    const u32 limit = WRITE ? rec[j].len : 0u;
-    u32 p = 0;       // bytes produced, pending literals included
-    u32 npend = 0;   // literals waiting in `lit`
-    u32 lit = 0;     // PER LANE: pending literal number `lane`
-    u32 fenced = 0;  // stores below this position are ordered before every later load
-    u32 nblk0 = 0, nblk1 = 0, nblk2 = 0, check = 0, isize = 0, flags = 0;
-    u64 end_bit = 0;
-    int verdict = BZ_OK;
-    bool fixed_ready = false;
-    u32 maxl = 0, maxd = 0;
-
-#define INF_FLUSH()                                                                   \
-    do {                                                                              \
-        if (WRITE && npend) {                                                         \
-            const u32 q_ = p - npend + lane;                                          \
-            if (lane < npend && q_ < limit) out[q_] = (u8)lit;                        \
-        }                                                                             \
-        npend = 0;                                                                    \
-    } while (0)
-// a failure: BZ_E_EOF if the bits looked at (those consumed and `extra` more) reach behind the entry, else BZ_E_DATA
-#define INF_FAIL(extra)                                                               \
-    do {                                                                              \
-        verdict = (inf_consumed(r) + (extra)) > total ? BZ_E_EOF : BZ_E_DATA;         \
-        goto done;                                                                    \
-    } while (0)
-#define INF_EOF_CHECK()                                                               \
-    do {                                                                              \
-        if (inf_consumed(r) > total) {                                                \
-            verdict = BZ_E_EOF;                                                       \
-            goto done;                                                                \
-        }                                                                             \
-    } while (0)
-
-    // ---- container header
-    if (kind == 1) {
-        inf_fill(r, lane);
-        const u32 cmf = inf_take(r, 8), flg = inf_take(r, 8);
-        INF_EOF_CHECK();
-        if (DICT) { // zlib/decoder.rs:62-101: FDICT first, then the six bytes, then what they hold
-            if (!(flg & 0x20u)) INF_FAIL(0);
-            inf_fill(r, lane);
-            const u32 v = inf_take(r, 32);
-            INF_EOF_CHECK();
-            const u32 id = (v >> 24) | ((v >> 8) & 0xFF00u) | ((v << 8) & 0xFF0000u) | (v << 24);
-            if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || id != dict_adler) INF_FAIL(0);
-        } else if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 0x20u)) INF_FAIL(0);
-    } else if (kind == 2) {
-        u32 hc = 0xFFFFFFFFu, flg = 0, xlen = 0;
-#define INF_HBYTE(v)                                                                  \
-    do {                                                                              \
-        inf_fill(r, lane);                                                            \
-        (v) = inf_take(r, 8);                                                         \
-        INF_EOF_CHECK();                                                              \
-        hc ^= (v);                                                                    \
-        for (int k_ = 0; k_ < 8; ++k_) hc = (hc & 1u) ? (hc >> 1) ^ 0xEDB88320u : hc >> 1; \
-    } while (0)
-        for (u32 k = 0; k < 10; ++k) {
-            u32 b;
-            INF_HBYTE(b);
-            if ((k == 0 && b != 0x1Fu) || (k == 1 && b != 0x8Bu) || (k == 2 && b != 8u) || (k == 3 && (b & 0xE0u))) INF_FAIL(0);
-            if (k == 3) flg = b;
-        }
-        if (flg & 4u) {
-            u32 b0, b1;
-            INF_HBYTE(b0);
-            INF_HBYTE(b1);
-            xlen = b0 | (b1 << 8);
-            for (u32 k = 0; k < xlen; ++k) INF_HBYTE(b0);
-        }
-        for (u32 f = 8u; f <= 16u; f <<= 1) // FNAME, FCOMMENT: up to the zero byte
-            if (flg & f) {
-                u32 b;
-                do INF_HBYTE(b);
-                while (b != 0);
-            }
-        if (flg & 2u) {
-            const u32 want = (hc ^ 0xFFFFFFFFu) & 0xFFFFu;
-            inf_fill(r, lane);
-            const u32 got = inf_take(r, 16);
-            INF_EOF_CHECK();
-            if (got != want) INF_FAIL(0);
-        }
-#undef INF_HBYTE
-    }
-
-    // ---- blocks
-    for (;;) {
-        inf_fill(r, lane);
-        const u32 bfinal = inf_take(r, 1), btype = inf_take(r, 2);
-        INF_EOF_CHECK();
-        if (btype == 3u) INF_FAIL(0);
-        if (btype == 0u) {
-            (void)inf_take(r, r.cnt & 7u);
-            inf_fill(r, lane);
-            const u32 ln = inf_take(r, 16), nl = inf_take(r, 16);
-            INF_EOF_CHECK();
-            if ((ln ^ nl) != 0xFFFFu) INF_FAIL(0);
-            const u32 bytepos = (u32)(inf_consumed(r) >> 3);
-            if ((u64)bytepos + ln > r.len) {
-                verdict = BZ_E_EOF;
-                goto done;
-            }
-            if (p > 0xFFFFFFFFu - 0x10000u) {
-                flags |= 1u;
-                INF_FAIL(0);
-            }
-            INF_FLUSH();
-            if (WRITE)
-                for (u32 i = lane; i < ln; i += 64u)
-                    if (p + i < limit) out[p + i] = r.base[bytepos + i];
-            p += ln;
-            inf_seek(r, bytepos + ln, lane);
-            ++nblk0;
-        } else {
-            if (btype == 1u) {
-                if (!fixed_ready) {
-                    __syncthreads();
-                    for (u32 i = lane; i < 320u; i += 64u) s_cl[i] = (u8)(i < 144u ? 8u : i < 256u ? 9u : i < 280u ? 7u : i < 288u ? 8u : 5u);
-                    __syncthreads();
-                    u32 ns;
-                    (void)inf_build(s_cl, 288, s_tl, kLBits, s_nl, s_sl, lane, ns, maxl);
-                    (void)inf_build(s_cl + 288, 32, s_td, kDBits, s_nd, s_sd, lane, ns, maxd);
-                    fixed_ready = true;
-                }
-            } else {
-                fixed_ready = false;
-                const u32 hlit = inf_take(r, 5) + 257u, hdist = inf_take(r, 5) + 1u, hclen = inf_take(r, 4) + 4u;
-                INF_EOF_CHECK();
-                if (hlit > 286u || hdist > 30u) INF_FAIL(0);
-                __syncthreads();
-                if (lane < 19u) s_clen[lane] = 0;
-                __syncthreads();
-                for (u32 k = 0; k < hclen; ++k) {
-                    inf_fill(r, lane);
-                    const u32 v = inf_take(r, 3);
-                    if (lane == 0) s_clen[c_cl_order[k]] = (u8)v;
-                }
-                INF_EOF_CHECK();
-                __syncthreads();
-                u32 ns, maxc;
-                if (inf_build(s_clen, 19, s_tc, kCBits, s_nc, s_sc, lane, ns, maxc) != 0) INF_FAIL(0);
-                const u32 ncl = hlit + hdist;
-                u32 i = 0, prev = 0;
-                while (i < ncl) {
-                    inf_fill(r, lane);
-                    const int sy = inf_sym(r, s_tc, kCBits, s_nc, s_sc);
-                    if (sy < 0) INF_FAIL(maxc);
-                    if (sy < 16) {
-                        INF_EOF_CHECK();
-                        if (lane == 0) s_cl[i] = (u8)sy;
-                        prev = (u32)sy;
-                        ++i;
-                        continue;
-                    }
-                    u32 rep, val = 0;
-                    if (sy == 16) {
-                        rep = 3u + inf_take(r, 2);
-                        val = prev;
-                    } else if (sy == 17) rep = 3u + inf_take(r, 3);
-                    else rep = 11u + inf_take(r, 7);
-                    INF_EOF_CHECK();
-                    if ((sy == 16 && i == 0) || i + rep > ncl) INF_FAIL(0);
-                    for (u32 q = lane; q < rep; q += 64u) s_cl[i + q] = (u8)val;
-                    prev = val;
-                    i += rep;
-                }
-                __syncthreads();
-                if (s_cl[256] == 0) INF_FAIL(0); // no end-of-block code
-                // (one sequence of hlit + hdist lengths: a run may cross from one alphabet into the other)
-                const int rl = inf_build(s_cl, hlit, s_tl, kLBits, s_nl, s_sl, lane, ns, maxl);
-                if (rl != 0) INF_FAIL(0);
-                const int rd = inf_build(s_cl + hlit, hdist, s_td, kDBits, s_nd, s_sd, lane, ns, maxd);
-                if (rd == 1 || (rd == 2 && !(ns == 0u || (ns == 1u && maxd == 1u)))) INF_FAIL(0);
-            }
-            // ---- the codes of the block
-            for (;;) {
-                inf_fill(r, lane);
-                const int sy = inf_sym(r, s_tl, kLBits, s_nl, s_sl);
-                if (sy < 0) INF_FAIL(maxl);
-                if (sy < 256) {
-                    INF_EOF_CHECK();
-                    if (lane == npend) lit = (u32)sy;
-                    ++npend;
-                    ++p;
-                    if (npend == 64u) INF_FLUSH();
-                    continue;
-                }
-                if (sy == 256) {
-                    INF_EOF_CHECK();
-                    break;
-                }
-                if (sy > 285) INF_FAIL(0);
-                const u32 len = c_len_base[sy - 257] + inf_take(r, c_len_extra[sy - 257]);
-                inf_fill(r, lane);
-                const int ds = inf_sym(r, s_td, kDBits, s_nd, s_sd);
-                if (ds < 0) INF_FAIL(maxd);
-                if (ds > 29) INF_FAIL(0);
-                const u32 d = c_dist_base[ds] + inf_take(r, c_dist_extra[ds]);
-                INF_EOF_CHECK();
-                if (DICT ? d > p && d - p > W : d > p) INF_FAIL(0);
-                if (p > 0xFFFFFFFFu - 0x10000u) {
-                    flags |= 1u;
-                    INF_FAIL(0);
-                }
-                INF_FLUSH();
-                if (WRITE && DICT) {
-                    // source byte q < 0 is window byte W + q: nobody writes the window, so only q >= 0 needs the fence
-                    const u32 span = d < len ? d : len;
-                    const long long q0 = (long long)p - d;
-                    if (q0 + span > (long long)fenced) {
-                        __threadfence_block();
-                        fenced = p;
-                    }
-                    for (u32 b = 0; b < len; b += 64u) {
-                        const u32 i = b + lane;
-                        if (i < len && p + i < limit) {
-                            const long long q = q0 + (d >= len ? i : i % d);
-                            out[p + i] = q < 0 ? dictw[(long long)W + q] : out[q];
-                        }
-                    }
-                } else if (WRITE) {
-                    const u32 span = d < len ? d : len;
-                    if (p - d + span > fenced) {
-                        __threadfence_block();
-                        fenced = p;
-                    }
-                    const u8 *src = out + (p - d);
-                    for (u32 b = 0; b < len; b += 64u) {
-                        const u32 i = b + lane;
-                        if (i < len && p + i < limit) out[p + i] = src[d >= len ? i : i % d];
-                    }
-                }
-                p += len;
-            }
-            if (btype == 1u) ++nblk1;
-            else ++nblk2;
-        }
-        if (bfinal) break;
-    }
-    // ---- container trailer
-    (void)inf_take(r, r.cnt & 7u);
-    if (kind == 1) {
-        inf_fill(r, lane);
-        const u32 v = inf_take(r, 32);
-        INF_EOF_CHECK();
-        check = (v >> 24) | ((v >> 8) & 0xFF00u) | ((v << 8) & 0xFF0000u) | (v << 24);
-    } else if (kind == 2) {
-        inf_fill(r, lane);
-        check = inf_take(r, 32);
-        inf_fill(r, lane);
-        isize = inf_take(r, 32);
-        INF_EOF_CHECK();
-    }
-done:
-    INF_FLUSH();
-    end_bit = inf_consumed(r) < total ? inf_consumed(r) : total;
-    if (!WRITE && lane == 0) {
-        DfInfRec o;
-        o.end_bit = end_bit;
-        o.len = p;
-        o.verdict = verdict;
-        o.nblk[0] = nblk0;
-        o.nblk[1] = nblk1;
-        o.nblk[2] = nblk2;
-        o.check = check;
-        o.isize = isize;
-        o.flags = flags;
-        o.pad[0] = o.pad[1] = 0;
-        rec[j] = o;
-    }
-#undef INF_FLUSH
-#undef INF_FAIL
-#undef INF_EOF_CHECK
-}
-
-namespace {
 // the tables of one wave (LDS)
 struct InfTabs {
     u16 tl[1u << kLBits], td[1u << kDBits], tc[1u << kCBits];
@@ -506,87 +216,64 @@ struct InfOut {
     int verdict;
     u32 reach, end_mode, ended; // of a piece (k_df_inflate_piece)
 };
+// what only a piece has (kPiece below; the other uses pass InfPiece{})
+struct InfPiece {
+    u32 *smap;   // the source map of the piece's bytes (WRITE)
+    u32 base;    // where the piece's output starts inside the entry's, or infsplit::kBaseUnknown
+    u64 stop;    // the piece ends at the first block boundary at or behind this bit
+    bool at_len; // the reader stands at the LEN field of a stored block
+};
 
-// The decode loop of a PIECE of a split entry (k_df_inflate_piece, inf_split.h).  It is k_df_inflate's loop, code for code --
-// a copy, so that the one-wave kernel stays the text and the machine code it was; what one of them learns the other must be
-// taught -- from the reader's position (`head`: the container header comes first, `at_len`: the position is the LEN field of
-// a stored block) to the first block boundary at or behind `stop`; `base` is where the piece's output starts inside the
-// entry's (infsplit::kBaseUnknown: not known yet, a distance that reaches in front of the piece is recorded in `reach` and
-// believed); with WRITE every byte i gets smap[i]: i itself when out[i] holds its value, else the position inside the
-// entry's output (in front of the piece) that does.  DICT: a source in front of the ENTRY is a window byte (above): it is
-// stored at once and is its own root -- the source map never points into the window -- and `base + p + W` bounds a distance.
-template <bool WRITE, bool DICT>
-__device__ __forceinline__ void inf_decode(InfTabs &t, InfIn &r, const u32 lane, const int kind, const bool head, u8 *out, const u32 limit,
-                                           u32 *smap, const u32 base, const u64 stop, bool at_len, InfOut &o, const u8 *__restrict__ dictw,
-                                           const u32 W, const u32 dict_adler)
+__device__ __forceinline__ InfIn inf_open(const u8 *base, u32 len)
 {
-    u16 *const s_tl = t.tl, *const s_td = t.td, *const s_tc = t.tc, *const s_sl = t.sl, *const s_sd = t.sd, *const s_sc = t.sc;
-    u32 *const s_nl = t.nl, *const s_nd = t.nd, *const s_nc = t.nc;
-    u8 *const s_cl = t.cl, *const s_clen = t.clen;
+    InfIn r;
+    r.base = base;
+    r.len = len;
+    r.buf = 0;
+    r.cnt = 0;
+    r.nextw = 0;
+    r.cw = 0;
+    r.cbase = 0xFFFFFF00u;
+    return r;
+}
+
+// The container header in front of the Deflate bits, zlib (kind 1) or gzip (kind 2): BZ_OK, BZ_E_EOF when it runs behind the
+// input, else BZ_E_DATA.  Every field is looked at behind the test for the end, so what is wrong with it is a data error.
+template <bool DICT>
+__device__ __forceinline__ int inf_header(InfIn &r, const u32 lane, const int kind, const u32 dict_adler)
+{
     const u64 total = 8ull * r.len;
-    u32 p = 0;       // bytes produced, pending literals included
-    u32 npend = 0;   // literals waiting in `lit`
-    u32 lit = 0;     // PER LANE: pending literal number `lane`
-    u32 fenced = 0;  // stores below this position are ordered before every later load
-    u32 nblk0 = 0, nblk1 = 0, nblk2 = 0, check = 0, isize = 0, flags = 0;
-    u32 reach = 0, end_mode = 0, ended = 1;
-    u64 end_key = 0;
-    int verdict = BZ_OK;
-    bool fixed_ready = false;
-    u32 maxl = 0, maxd = 0;
-
-#define INF_FLUSH()                                                                   \
+#define INF_HEOF()                                                                    \
     do {                                                                              \
-        if (WRITE && npend) {                                                         \
-            const u32 q_ = p - npend + lane;                                          \
-            if (lane < npend && q_ < limit) {                                         \
-                out[q_] = (u8)lit;                                                    \
-                smap[q_] = base + q_;                                                 \
-            }                                                                         \
-        }                                                                             \
-        npend = 0;                                                                    \
+        if (inf_consumed(r) > total) return BZ_E_EOF;                                 \
     } while (0)
-// a failure: BZ_E_EOF if the bits looked at (those consumed and `extra` more) reach behind the entry, else BZ_E_DATA
-#define INF_FAIL(extra)                                                               \
-    do {                                                                              \
-        verdict = (inf_consumed(r) + (extra)) > total ? BZ_E_EOF : BZ_E_DATA;         \
-        goto done;                                                                    \
-    } while (0)
-#define INF_EOF_CHECK()                                                               \
-    do {                                                                              \
-        if (inf_consumed(r) > total) {                                                \
-            verdict = BZ_E_EOF;                                                       \
-            goto done;                                                                \
-        }                                                                             \
-    } while (0)
-
-    // ---- container header
-    if (head && kind == 1) {
+    if (kind == 1) {
         inf_fill(r, lane);
         const u32 cmf = inf_take(r, 8), flg = inf_take(r, 8);
-        INF_EOF_CHECK();
+        INF_HEOF();
         if (DICT) { // zlib/decoder.rs:62-101: FDICT first, then the six bytes, then what they hold
-            if (!(flg & 0x20u)) INF_FAIL(0);
+            if (!(flg & 0x20u)) return BZ_E_DATA;
             inf_fill(r, lane);
             const u32 v = inf_take(r, 32);
-            INF_EOF_CHECK();
+            INF_HEOF();
             const u32 id = (v >> 24) | ((v >> 8) & 0xFF00u) | ((v << 8) & 0xFF0000u) | (v << 24);
-            if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || id != dict_adler) INF_FAIL(0);
-        } else if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 0x20u)) INF_FAIL(0);
-    } else if (head && kind == 2) {
+            if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || id != dict_adler) return BZ_E_DATA;
+        } else if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 0x20u)) return BZ_E_DATA;
+    } else if (kind == 2) {
         u32 hc = 0xFFFFFFFFu, flg = 0, xlen = 0;
 #define INF_HBYTE(v)                                                                  \
     do {                                                                              \
         inf_fill(r, lane);                                                            \
         (v) = inf_take(r, 8);                                                         \
-        INF_EOF_CHECK();                                                              \
+        INF_HEOF();                                                                   \
         hc ^= (v);                                                                    \
         for (int k_ = 0; k_ < 8; ++k_) hc = (hc & 1u) ? (hc >> 1) ^ 0xEDB88320u : hc >> 1; \
     } while (0)
+#pragma unroll 1
         for (u32 k = 0; k < 10; ++k) {
             u32 b;
             INF_HBYTE(b);
-            if ((k == 0 && b != 0x1Fu) || (k == 1 && b != 0x8Bu) || (k == 2 && b != 8u) || (k == 3 && (b & 0xE0u))) INF_FAIL(0);
+            if ((k == 0 && b != 0x1Fu) || (k == 1 && b != 0x8Bu) || (k == 2 && b != 8u) || (k == 3 && (b & 0xE0u))) return BZ_E_DATA;
             if (k == 3) flg = b;
         }
         if (flg & 4u) {
@@ -606,28 +293,98 @@ __device__ __forceinline__ void inf_decode(InfTabs &t, InfIn &r, const u32 lane,
             const u32 want = (hc ^ 0xFFFFFFFFu) & 0xFFFFu;
             inf_fill(r, lane);
             const u32 got = inf_take(r, 16);
-            INF_EOF_CHECK();
-            if (got != want) INF_FAIL(0);
+            INF_HEOF();
+            if (got != want) return BZ_E_DATA;
         }
 #undef INF_HBYTE
     }
+#undef INF_HEOF
+    return BZ_OK;
+}
 
-    // ---- blocks
+// THE decode loop: the blocks of one Deflate stream from where the reader stands -- block header, stored block, fixed and
+// dynamic tables, codes, copies -- and what ends it.  Written once and instantiated per use; the uses differ in the places
+// below and nowhere else, each resolved at compile time (`if constexpr`), so no instantiation carries another's test:
+//   kEntry (k_df_inflate): a whole entry.  Stores are clipped to `limit` while p runs on (the 4 GiB guard sets flags bit 0); a
+//     fault is BZ_E_EOF when the bits looked at reach behind the input, else BZ_E_DATA; a distance may reach p bytes back, with
+//     DICT p + W, and a source in front of position 0 is a window byte; the end is the container trailer by `kind`.
+//   kPiece (k_df_inflate_piece, inf_split.h): a piece of a split entry, kEntry but for this: the reader may stand at a stored
+//     block's LEN (pc.at_len); at every block boundary the piece ends if the block behind it starts at or behind pc.stop
+//     (end_key, end_mode, ended; a non-final stored block is named by its LEN position); `pc.base` is where the piece's output
+//     starts inside the entry's (infsplit::kBaseUnknown: not known yet, a distance that reaches in front of the piece is
+//     recorded in `reach` and believed), else base + p (+ W) bounds a distance; with WRITE every byte i gets smap[i]: i itself
+//     when out[i] holds its value, else the position inside the entry's output (in front of the piece) that does -- no byte is
+//     written then.  DICT: a source in front of the ENTRY is a window byte: it is stored at once and is its own root, the
+//     source map never points into the window.
+//   kBgzf (k_bgzf_inflate): the Deflate bytes of one BGZF block, kind 0, always written.  Every fault is BZ_E_DATA, running out of
+//     bits included (the cut is BSIZE's, not the file's: bits behind the Deflate bytes are zeros to the reader, having used one
+//     is the block's fault); so is a byte too many, p > limit, looked at with the end test and behind a stored block and a
+//     match; a distance may reach p bytes back; a clean block produces exactly `limit` bytes and uses every bit.
+// `verdict` is what the use's own entrance found: anything but BZ_OK and nothing is decoded.  The reader and the piece's
+// data come by value and the result leaves by value: everything that steers the loop is a local of this function.
+enum InfUse { kEntry, kPiece, kBgzf };
+
+template <InfUse USE, bool WRITE, bool DICT>
+__device__ __forceinline__ InfOut inf_decode(InfTabs &t, InfIn r, const u32 lane, int verdict, const int kind, u8 *out, const u32 limit,
+                                             const InfPiece pc, const u8 *__restrict__ dictw, const u32 W)
+{
+    static_assert(USE != kBgzf || (WRITE && !DICT), "a BGZF block is written in its one pass and has no dictionary");
+    const u64 total = 8ull * r.len;
+    const u32 base = pc.base;
+    u32 p = 0;       // bytes produced, pending literals included
+    u32 npend = 0;   // literals waiting in `lit`
+    u32 lit = 0;     // PER LANE: pending literal number `lane`
+    u32 fenced = 0;  // stores below this position are ordered before every later load
+    u32 nblk0 = 0, nblk1 = 0, nblk2 = 0, check = 0, isize = 0, flags = 0;
+    u32 reach = 0, end_mode = 0, ended = 1;
+    u64 end_key = 0;
+    bool at_len = pc.at_len;
+    bool fixed_ready = false;
+    u32 maxl = 0, maxd = 0;
+
+#define INF_FLUSH()                                                                   \
+    do {                                                                              \
+        if (WRITE && npend) {                                                         \
+            const u32 q_ = p - npend + lane;                                          \
+            if (lane < npend && q_ < limit) {                                         \
+                out[q_] = (u8)lit;                                                    \
+                if constexpr (USE == kPiece) pc.smap[q_] = base + q_;                 \
+            }                                                                         \
+        }                                                                             \
+        npend = 0;                                                                    \
+    } while (0)
+// a failure: BZ_E_EOF if the bits looked at (those consumed and `extra` more) reach behind the input, else BZ_E_DATA
+#define INF_FAIL(extra)                                                               \
+    do {                                                                              \
+        verdict = USE != kBgzf && (inf_consumed(r) + (extra)) > total ? BZ_E_EOF : BZ_E_DATA; \
+        goto done;                                                                    \
+    } while (0)
+#define INF_EOF_CHECK()                                                               \
+    do {                                                                              \
+        if (inf_consumed(r) > total || (USE == kBgzf && p > limit)) {                 \
+            verdict = USE == kBgzf ? BZ_E_DATA : BZ_E_EOF;                            \
+            goto done;                                                                \
+        }                                                                             \
+    } while (0)
+
+    if (verdict != BZ_OK) goto done;
     for (;;) {
         u32 bfinal = 0, btype = 0;
-        const bool from_len = at_len; // (a piece that starts at a stored block's LEN: its header bits lie in front)
+        const bool from_len = USE == kPiece && at_len; // (the header bits of that stored block lie in front of the piece)
         at_len = false;
         if (!from_len) {
-            // a boundary: the block behind it is the next piece's if it starts at or behind `stop`
-            const u64 h = inf_consumed(r);
             inf_fill(r, lane);
-            const bool st0 = h + 3 <= total && ((u32)r.buf & 7u) == 0u; // a non-final stored block: known by its LEN
-            const u64 key = st0 ? (h + 10) & ~7ull : h;
-            if (key >= stop) {
-                end_key = key;
-                end_mode = st0 ? 1u : 0u;
-                ended = 0;
-                goto done;
+            if constexpr (USE == kPiece) {
+                // a boundary: the block behind it is the next piece's if it starts at or behind `stop`
+                const u64 h = inf_consumed(r);
+                const bool st0 = h + 3 <= total && ((u32)r.buf & 7u) == 0u; // a non-final stored block: known by its LEN
+                const u64 key = st0 ? (h + 10) & ~7ull : h;
+                if (key >= pc.stop) {
+                    end_key = key;
+                    end_mode = st0 ? 1u : 0u;
+                    ended = 0;
+                    goto done;
+                }
             }
             bfinal = inf_take(r, 1);
             btype = inf_take(r, 2);
@@ -642,10 +399,10 @@ __device__ __forceinline__ void inf_decode(InfTabs &t, InfIn &r, const u32 lane,
             if ((ln ^ nl) != 0xFFFFu) INF_FAIL(0);
             const u32 bytepos = (u32)(inf_consumed(r) >> 3);
             if ((u64)bytepos + ln > r.len) {
-                verdict = BZ_E_EOF;
+                verdict = USE == kBgzf ? BZ_E_DATA : BZ_E_EOF;
                 goto done;
             }
-            if (p > 0xFFFFFFFFu - 0x10000u) {
+            if (USE != kBgzf && p > 0xFFFFFFFFu - 0x10000u) {
                 flags |= 1u;
                 INF_FAIL(0);
             }
@@ -654,20 +411,21 @@ __device__ __forceinline__ void inf_decode(InfTabs &t, InfIn &r, const u32 lane,
                 for (u32 i = lane; i < ln; i += 64u)
                     if (p + i < limit) {
                         out[p + i] = r.base[bytepos + i];
-                        smap[p + i] = base + p + i;
+                        if constexpr (USE == kPiece) pc.smap[p + i] = base + p + i;
                     }
             p += ln;
+            if (USE == kBgzf && p > limit) INF_FAIL(0);
             inf_seek(r, bytepos + ln, lane);
             ++nblk0;
         } else {
             if (btype == 1u) {
                 if (!fixed_ready) {
                     __syncthreads();
-                    for (u32 i = lane; i < 320u; i += 64u) s_cl[i] = (u8)(i < 144u ? 8u : i < 256u ? 9u : i < 280u ? 7u : i < 288u ? 8u : 5u);
+                    for (u32 i = lane; i < 320u; i += 64u) t.cl[i] = (u8)(i < 144u ? 8u : i < 256u ? 9u : i < 280u ? 7u : i < 288u ? 8u : 5u);
                     __syncthreads();
                     u32 ns;
-                    (void)inf_build(s_cl, 288, s_tl, kLBits, s_nl, s_sl, lane, ns, maxl);
-                    (void)inf_build(s_cl + 288, 32, s_td, kDBits, s_nd, s_sd, lane, ns, maxd);
+                    (void)inf_build(t.cl, 288, t.tl, kLBits, t.nl, t.sl, lane, ns, maxl);
+                    (void)inf_build(t.cl + 288, 32, t.td, kDBits, t.nd, t.sd, lane, ns, maxd);
                     fixed_ready = true;
                 }
             } else {
@@ -676,26 +434,26 @@ __device__ __forceinline__ void inf_decode(InfTabs &t, InfIn &r, const u32 lane,
                 INF_EOF_CHECK();
                 if (hlit > 286u || hdist > 30u) INF_FAIL(0);
                 __syncthreads();
-                if (lane < 19u) s_clen[lane] = 0;
+                if (lane < 19u) t.clen[lane] = 0;
                 __syncthreads();
                 for (u32 k = 0; k < hclen; ++k) {
                     inf_fill(r, lane);
                     const u32 v = inf_take(r, 3);
-                    if (lane == 0) s_clen[c_cl_order[k]] = (u8)v;
+                    if (lane == 0) t.clen[c_cl_order[k]] = (u8)v;
                 }
                 INF_EOF_CHECK();
                 __syncthreads();
                 u32 ns, maxc;
-                if (inf_build(s_clen, 19, s_tc, kCBits, s_nc, s_sc, lane, ns, maxc) != 0) INF_FAIL(0);
+                if (inf_build(t.clen, 19, t.tc, kCBits, t.nc, t.sc, lane, ns, maxc) != 0) INF_FAIL(0);
                 const u32 ncl = hlit + hdist;
                 u32 i = 0, prev = 0;
                 while (i < ncl) {
                     inf_fill(r, lane);
-                    const int sy = inf_sym(r, s_tc, kCBits, s_nc, s_sc);
+                    const int sy = inf_sym(r, t.tc, kCBits, t.nc, t.sc);
                     if (sy < 0) INF_FAIL(maxc);
                     if (sy < 16) {
                         INF_EOF_CHECK();
-                        if (lane == 0) s_cl[i] = (u8)sy;
+                        if (lane == 0) t.cl[i] = (u8)sy;
                         prev = (u32)sy;
                         ++i;
                         continue;
@@ -708,28 +466,29 @@ __device__ __forceinline__ void inf_decode(InfTabs &t, InfIn &r, const u32 lane,
                     else rep = 11u + inf_take(r, 7);
                     INF_EOF_CHECK();
                     if ((sy == 16 && i == 0) || i + rep > ncl) INF_FAIL(0);
-                    for (u32 q = lane; q < rep; q += 64u) s_cl[i + q] = (u8)val;
+                    for (u32 q = lane; q < rep; q += 64u) t.cl[i + q] = (u8)val;
                     prev = val;
                     i += rep;
                 }
                 __syncthreads();
-                if (s_cl[256] == 0) INF_FAIL(0); // no end-of-block code
+                if (t.cl[256] == 0) INF_FAIL(0); // no end-of-block code
                 // (one sequence of hlit + hdist lengths: a run may cross from one alphabet into the other)
-                const int rl = inf_build(s_cl, hlit, s_tl, kLBits, s_nl, s_sl, lane, ns, maxl);
+                const int rl = inf_build(t.cl, hlit, t.tl, kLBits, t.nl, t.sl, lane, ns, maxl);
                 if (rl != 0) INF_FAIL(0);
-                const int rd = inf_build(s_cl + hlit, hdist, s_td, kDBits, s_nd, s_sd, lane, ns, maxd);
+                const int rd = inf_build(t.cl + hlit, hdist, t.td, kDBits, t.nd, t.sd, lane, ns, maxd);
                 if (rd == 1 || (rd == 2 && !(ns == 0u || (ns == 1u && maxd == 1u)))) INF_FAIL(0);
             }
             // ---- the codes of the block
             for (;;) {
                 inf_fill(r, lane);
-                const int sy = inf_sym(r, s_tl, kLBits, s_nl, s_sl);
+                const int sy = inf_sym(r, t.tl, kLBits, t.nl, t.sl);
                 if (sy < 0) INF_FAIL(maxl);
                 if (sy < 256) {
-                    INF_EOF_CHECK();
+                    if constexpr (USE != kBgzf) INF_EOF_CHECK();
                     if (lane == npend) lit = (u32)sy;
                     ++npend;
                     ++p;
+                    if constexpr (USE == kBgzf) INF_EOF_CHECK(); // (behind ++p: the byte too many is counted in len)
                     if (npend == 64u) INF_FLUSH();
                     continue;
                 }
@@ -738,54 +497,80 @@ __device__ __forceinline__ void inf_decode(InfTabs &t, InfIn &r, const u32 lane,
                     break;
                 }
                 if (sy > 285) INF_FAIL(0);
-                const u32 len = c_len_base[sy - 257] + inf_take(r, c_len_extra[sy - 257]);
+                const u32 lc = c_len_code[sy - 257];
+                const u32 len = (lc & 0xFFFFu) + inf_take(r, lc >> 16);
                 inf_fill(r, lane);
-                const int ds = inf_sym(r, s_td, kDBits, s_nd, s_sd);
+                const int ds = inf_sym(r, t.td, kDBits, t.nd, t.sd);
                 if (ds < 0) INF_FAIL(maxd);
                 if (ds > 29) INF_FAIL(0);
-                const u32 d = c_dist_base[ds] + inf_take(r, c_dist_extra[ds]);
+                const u32 dc = c_dist_code[ds];
+                const u32 d = (dc & 0xFFFFu) + inf_take(r, dc >> 16);
                 INF_EOF_CHECK();
-                if (d > p) { // in front of the piece: inside the entry's output if the piece knows where it lies
-                    if (base != infsplit::kBaseUnknown && (u64)d > (u64)base + p + (DICT ? W : 0u)) INF_FAIL(0);
-                    if (d - p > reach) reach = d - p;
-                }
-                if (p > 0xFFFFFFFFu - 0x10000u) {
+                if constexpr (USE == kPiece) {
+                    if (d > p) { // in front of the piece: inside the entry's output if the piece knows where it lies
+                        if (base != infsplit::kBaseUnknown && (u64)d > (u64)base + p + (DICT ? W : 0u)) INF_FAIL(0);
+                        if (d - p > reach) reach = d - p;
+                    }
+                } else if (DICT ? d > p && d - p > W : d > p) INF_FAIL(0); // in front of the first byte (of the window)
+                if (USE != kBgzf && p > 0xFFFFFFFFu - 0x10000u) {
                     flags |= 1u;
                     INF_FAIL(0);
                 }
                 INF_FLUSH();
                 if (WRITE) {
+                    // The last source byte is p - d + span - 1, which may lie in front of position 0 (nobody writes there: it
+                    // needs no fence): p - d + span > fenced, with fenced <= p and no term below zero.
                     const u32 span = d < len ? d : len;
-                    if ((long long)p - d + span > (long long)fenced) {
+                    if (p - fenced + span > d) {
                         __threadfence_block();
                         fenced = p;
                     }
-                    for (u32 b = 0; b < len; b += 64u) {
-                        const u32 i = b + lane;
-                        if (i < len && p + i < limit) {
-                            const long long q = (long long)p - d + (d >= len ? i : i % d);
-                            if (DICT && (long long)base + q < 0) { // in front of the entry: a window byte, its own root
-                                out[p + i] = dictw[(long long)W + base + q];
-                                smap[p + i] = base + p + i;
-                            } else if (q < 0) smap[p + i] = (u32)((long long)base + q); // (no byte: the gather brings it)
-                            else {
-                                const u32 sv = smap[q];
-                                out[p + i] = out[q];
-                                smap[p + i] = sv == base + (u32)q ? base + p + i : sv;
+                    if constexpr (USE == kPiece) {
+                        for (u32 b = 0; b < len; b += 64u) {
+                            const u32 i = b + lane;
+                            if (i < len && p + i < limit) {
+                                const long long q = (long long)p - d + (d >= len ? i : i % d);
+                                if (DICT && (long long)base + q < 0) { // in front of the entry: a window byte, its own root
+                                    out[p + i] = dictw[(long long)W + base + q];
+                                    pc.smap[p + i] = base + p + i;
+                                } else if (q < 0) pc.smap[p + i] = (u32)((long long)base + q); // (no byte: the gather brings it)
+                                else {
+                                    const u32 sv = pc.smap[q];
+                                    out[p + i] = out[q];
+                                    pc.smap[p + i] = sv == base + (u32)q ? base + p + i : sv;
+                                }
                             }
+                        }
+                    } else if constexpr (DICT) { // source byte q < 0 is window byte W + q; out + (p - d) is never formed for p < d
+                        const long long q0 = (long long)p - d;
+                        for (u32 b = 0; b < len; b += 64u) {
+                            const u32 i = b + lane;
+                            if (i < len && p + i < limit) {
+                                const long long q = q0 + (d >= len ? i : i % d);
+                                out[p + i] = q < 0 ? dictw[(long long)W + q] : out[q];
+                            }
+                        }
+                    } else {
+                        const u8 *src = out + (p - d);
+                        for (u32 b = 0; b < len; b += 64u) {
+                            const u32 i = b + lane;
+                            if (i < len && p + i < limit) out[p + i] = src[d >= len ? i : i % d];
                         }
                     }
                 }
                 p += len;
+                if (USE == kBgzf && p > limit) INF_FAIL(0);
             }
             if (btype == 1u) ++nblk1;
             else ++nblk2;
         }
         if (bfinal) break;
     }
-    // ---- container trailer
+    // ---- the end
     (void)inf_take(r, r.cnt & 7u);
-    if (kind == 1) {
+    if constexpr (USE == kBgzf) { // exactly `limit` bytes, and the stream ends in the last byte of the input
+        if (p != limit || inf_consumed(r) != total) verdict = BZ_E_DATA;
+    } else if (kind == 1) {
         inf_fill(r, lane);
         const u32 v = inf_take(r, 32);
         INF_EOF_CHECK();
@@ -799,6 +584,7 @@ __device__ __forceinline__ void inf_decode(InfTabs &t, InfIn &r, const u32 lane,
     }
 done:
     INF_FLUSH();
+    InfOut o;
     o.end_bit = !ended ? end_key : inf_consumed(r) < total ? inf_consumed(r) : total;
     o.p = p;
     o.verdict = verdict;
@@ -811,6 +597,7 @@ done:
     o.reach = reach;
     o.end_mode = end_mode;
     o.ended = ended;
+    return o;
 #undef INF_FLUSH
 #undef INF_FAIL
 #undef INF_EOF_CHECK
@@ -832,6 +619,21 @@ __device__ __forceinline__ DfInfRec inf_record(const InfOut &o)
     return q;
 }
 } // namespace
+
+// One wave per entry: the container header, then the decode loop from the entry's first block to its trailer.
+template <bool WRITE, bool DICT>
+__global__ __launch_bounds__(64) void k_df_inflate(const u8 *__restrict__ in, const u64 *__restrict__ in_off, const u64 *__restrict__ in_len,
+                                                   int kind, u8 *out_all, const u64 *__restrict__ out_off, DfInfRec *rec,
+                                                   const u8 *__restrict__ dictw, u32 W, u32 dict_adler)
+{
+    __shared__ InfTabs t;
+    const u32 lane = threadIdx.x, j = blockIdx.x;
+    InfIn r = inf_open(in + in_off[j], (u32)in_len[j]);
+    const int head = inf_header<DICT>(r, lane, kind, dict_adler);
+    const InfOut o = inf_decode<kEntry, WRITE, DICT>(t, r, lane, head, kind, WRITE ? out_all + out_off[j] : nullptr, WRITE ? rec[j].len : 0u,
+                                                     InfPiece{}, dictw, W);
+    if (!WRITE && lane == 0) rec[j] = inf_record(o);
+}
 
 // ---- one large entry across many waves (inf_split.h; DESIGN_deflate.md "One large stream across many waves")
 // The first candidate of every piece but the first: 64 bit offsets per step, one per lane.
@@ -886,14 +688,7 @@ __global__ __launch_bounds__(64) void k_df_inflate_piece(const u8 *__restrict__ 
     __shared__ InfTabs t;
     const u32 lane = threadIdx.x, j = blockIdx.x;
     const DfPiece q = pc[j];
-    InfIn r;
-    r.base = ebase;
-    r.len = elen;
-    r.buf = 0;
-    r.cnt = 0;
-    r.nextw = 0;
-    r.cw = 0;
-    r.cbase = 0xFFFFFF00u;
+    InfIn r = inf_open(ebase, elen);
     const bool head = (q.mode & 2u) != 0, at_len = (q.mode & 1u) != 0;
     if (at_len) inf_seek(r, (u32)(q.start >> 3), lane);
     else if (!head) {
@@ -901,9 +696,9 @@ __global__ __launch_bounds__(64) void k_df_inflate_piece(const u8 *__restrict__ 
         inf_fill(r, lane);
         (void)inf_take(r, (u32)q.start & 31u);
     }
-    InfOut o;
-    inf_decode<WRITE, DICT>(t, r, lane, kind, head, WRITE ? eout + q.base : nullptr, WRITE ? q.len : 0u, WRITE ? emap + q.base : nullptr,
-                            q.base, q.stop, at_len, o, dictw, W, dict_adler);
+    const int hv = head ? inf_header<DICT>(r, lane, kind, dict_adler) : BZ_OK; // (the entry's first piece)
+    const InfOut o = inf_decode<kPiece, WRITE, DICT>(t, r, lane, hv, kind, WRITE ? eout + q.base : nullptr, WRITE ? q.len : 0u,
+                                                     InfPiece{WRITE ? emap + q.base : nullptr, q.base, q.stop, at_len}, dictw, W);
     if (!WRITE && lane == 0) {
         DfPieceRec x;
         x.r = inf_record(o);
@@ -1003,40 +798,22 @@ __global__ __launch_bounds__(256) void k_df_inflate_check(const u8 *__restrict__
 
 // ---- reading BGZF (include/bz2_mi355x.h section 8; DESIGN_deflate.md "Reading BGZF")
 // One wave per block of the index, ONE pass: the block's length comes from BSIZE and its output's length from ISIZE, both
-// checked against the index here, so the bytes go straight to their place.  This is k_df_inflate<true, false>'s loop for
-// kind 0 -- a copy, as inf_decode is, so that the kernels above stay the machine code they were -- with another entry and
-// another end: the lanes check the header rule (bgzf_index.h) at the block's coff, which may have any byte phase (the
-// reader starts at the 4-aligned byte in front of it, 18 + phase bytes in: inf_seek, and `total` counts from there);
-// `limit` is ISIZE; the output may start at any byte; every fault is BZ_E_DATA, running out of bits included (the cut is
-// BSIZE's, not the file's); a clean block produces exactly ISIZE bytes and ends in the byte in front of its trailer.  A
-// distance that reaches in front of the block's first byte is a fault although the block in front lies right there.
-// An edge block (slot != 0) is decoded into its 64 KiB slot of the workspace instead.  Stores are clipped to `limit`.
+// checked against the index here, so the bytes go straight to their place.  The decode loop is inf_decode's kBgzf form (its
+// rules are listed there); this kernel's own part is the entrance: the lanes check the header rule (bgzf_index.h) at the
+// block's coff, which may have any byte phase (the reader starts at the 4-aligned byte in front of it, 18 + phase bytes in:
+// inf_seek, and the loop's `total` counts from there to the byte in front of the trailer); `limit` is ISIZE; the output may
+// start at any byte.  A distance that reaches in front of the block's first byte is a fault although the block in front lies
+// right there.  An edge block (slot != 0) is decoded into its 64 KiB slot of the workspace instead.
 __global__ __launch_bounds__(64) void k_bgzf_inflate(const u8 *__restrict__ in, const BgzfDesc *__restrict__ desc, u8 *out_all, u8 *slots,
                                                      BgzfRec *rec)
 {
-    __shared__ u16 s_tl[1u << kLBits], s_td[1u << kDBits], s_tc[1u << kCBits];
-    __shared__ u16 s_sl[288], s_sd[32], s_sc[32];
-    __shared__ u32 s_nl[16], s_nd[16], s_nc[16];
-    __shared__ u8 s_cl[320], s_clen[32];
+    __shared__ InfTabs t;
     const u32 lane = threadIdx.x, j = blockIdx.x;
     const BgzfDesc q = desc[j];
     u8 *const out = q.slot ? slots + (size_t)(q.slot - 1u) * bgzf::kMaxBlock : out_all + q.dst;
-    const u32 limit = q.usize;
     const u32 phase = (u32)q.coff & 3u;
-    InfIn r;
-    r.base = in + (q.coff - phase);
-    r.len = phase + q.csize - bgzf::kTrailer;
-    r.buf = 0;
-    r.cnt = 0;
-    r.nextw = 0;
-    r.cw = 0;
-    r.cbase = 0xFFFFFF00u;
-    const u64 total = 8ull * r.len;
-    u32 p = 0, npend = 0, lit = 0, fenced = 0;
-    u32 nblk0 = 0, nblk1 = 0, nblk2 = 0, check = 0;
-    int verdict = BZ_OK;
-    bool fixed_ready = false;
-    u32 maxl = 0, maxd = 0;
+    InfIn r = inf_open(in + (q.coff - phase), phase + q.csize - bgzf::kTrailer);
+    u32 check = 0;
     bool head_ok = false;
     if (q.csize >= bgzf::kMinBlock && q.csize <= bgzf::kMaxBlock) { // lanes 0 .. 17: the header's bytes, 18 .. 25: the trailer's
         u32 hb = 0;
@@ -1050,174 +827,19 @@ __global__ __launch_bounds__(64) void k_bgzf_inflate(const u8 *__restrict__ in, 
 #undef BG_B
 #undef BG_W
     }
-
-#define INF_FLUSH()                                                                   \
-    do {                                                                              \
-        if (npend) {                                                                  \
-            const u32 q_ = p - npend + lane;                                          \
-            if (lane < npend && q_ < limit) out[q_] = (u8)lit;                        \
-        }                                                                             \
-        npend = 0;                                                                    \
-    } while (0)
-#define INF_FAIL()                                                                    \
-    do {                                                                              \
-        verdict = BZ_E_DATA;                                                          \
-        goto done;                                                                    \
-    } while (0)
-// (bits behind the Deflate bytes are zeros to the reader: having used one is the block's fault; so is a byte too many)
-#define INF_EOF_CHECK()                                                               \
-    do {                                                                              \
-        if (inf_consumed(r) > total || p > limit) INF_FAIL();                         \
-    } while (0)
-
-    if (!head_ok) INF_FAIL();
-    inf_seek(r, phase + bgzf::kHeader, lane);
-    for (;;) {
-        inf_fill(r, lane);
-        const u32 bfinal = inf_take(r, 1), btype = inf_take(r, 2);
-        INF_EOF_CHECK();
-        if (btype == 3u) INF_FAIL();
-        if (btype == 0u) {
-            (void)inf_take(r, r.cnt & 7u);
-            inf_fill(r, lane);
-            const u32 ln = inf_take(r, 16), nl = inf_take(r, 16);
-            INF_EOF_CHECK();
-            if ((ln ^ nl) != 0xFFFFu) INF_FAIL();
-            const u32 bytepos = (u32)(inf_consumed(r) >> 3);
-            if ((u64)bytepos + ln > r.len) INF_FAIL();
-            INF_FLUSH();
-            for (u32 i = lane; i < ln; i += 64u)
-                if (p + i < limit) out[p + i] = r.base[bytepos + i];
-            p += ln;
-            if (p > limit) INF_FAIL();
-            inf_seek(r, bytepos + ln, lane);
-            ++nblk0;
-        } else {
-            if (btype == 1u) {
-                if (!fixed_ready) {
-                    __syncthreads();
-                    for (u32 i = lane; i < 320u; i += 64u) s_cl[i] = (u8)(i < 144u ? 8u : i < 256u ? 9u : i < 280u ? 7u : i < 288u ? 8u : 5u);
-                    __syncthreads();
-                    u32 ns;
-                    (void)inf_build(s_cl, 288, s_tl, kLBits, s_nl, s_sl, lane, ns, maxl);
-                    (void)inf_build(s_cl + 288, 32, s_td, kDBits, s_nd, s_sd, lane, ns, maxd);
-                    fixed_ready = true;
-                }
-            } else {
-                fixed_ready = false;
-                const u32 hlit = inf_take(r, 5) + 257u, hdist = inf_take(r, 5) + 1u, hclen = inf_take(r, 4) + 4u;
-                INF_EOF_CHECK();
-                if (hlit > 286u || hdist > 30u) INF_FAIL();
-                __syncthreads();
-                if (lane < 19u) s_clen[lane] = 0;
-                __syncthreads();
-                for (u32 k = 0; k < hclen; ++k) {
-                    inf_fill(r, lane);
-                    const u32 v = inf_take(r, 3);
-                    if (lane == 0) s_clen[c_cl_order[k]] = (u8)v;
-                }
-                INF_EOF_CHECK();
-                __syncthreads();
-                u32 ns, maxc;
-                if (inf_build(s_clen, 19, s_tc, kCBits, s_nc, s_sc, lane, ns, maxc) != 0) INF_FAIL();
-                const u32 ncl = hlit + hdist;
-                u32 i = 0, prev = 0;
-                while (i < ncl) {
-                    inf_fill(r, lane);
-                    const int sy = inf_sym(r, s_tc, kCBits, s_nc, s_sc);
-                    if (sy < 0) INF_FAIL();
-                    if (sy < 16) {
-                        INF_EOF_CHECK();
-                        if (lane == 0) s_cl[i] = (u8)sy;
-                        prev = (u32)sy;
-                        ++i;
-                        continue;
-                    }
-                    u32 rep, val = 0;
-                    if (sy == 16) {
-                        rep = 3u + inf_take(r, 2);
-                        val = prev;
-                    } else if (sy == 17) rep = 3u + inf_take(r, 3);
-                    else rep = 11u + inf_take(r, 7);
-                    INF_EOF_CHECK();
-                    if ((sy == 16 && i == 0) || i + rep > ncl) INF_FAIL();
-                    for (u32 k = lane; k < rep; k += 64u) s_cl[i + k] = (u8)val;
-                    prev = val;
-                    i += rep;
-                }
-                __syncthreads();
-                if (s_cl[256] == 0) INF_FAIL(); // no end-of-block code
-                const int rl = inf_build(s_cl, hlit, s_tl, kLBits, s_nl, s_sl, lane, ns, maxl);
-                if (rl != 0) INF_FAIL();
-                const int rd = inf_build(s_cl + hlit, hdist, s_td, kDBits, s_nd, s_sd, lane, ns, maxd);
-                if (rd == 1 || (rd == 2 && !(ns == 0u || (ns == 1u && maxd == 1u)))) INF_FAIL();
-            }
-            // ---- the codes of the block
-            for (;;) {
-                inf_fill(r, lane);
-                const int sy = inf_sym(r, s_tl, kLBits, s_nl, s_sl);
-                if (sy < 0) INF_FAIL();
-                if (sy < 256) {
-                    if (lane == npend) lit = (u32)sy;
-                    ++npend;
-                    ++p;
-                    INF_EOF_CHECK();
-                    if (npend == 64u) INF_FLUSH();
-                    continue;
-                }
-                if (sy == 256) {
-                    INF_EOF_CHECK();
-                    break;
-                }
-                if (sy > 285) INF_FAIL();
-                const u32 len = c_len_base[sy - 257] + inf_take(r, c_len_extra[sy - 257]);
-                inf_fill(r, lane);
-                const int ds = inf_sym(r, s_td, kDBits, s_nd, s_sd);
-                if (ds < 0) INF_FAIL();
-                if (ds > 29) INF_FAIL();
-                const u32 d = c_dist_base[ds] + inf_take(r, c_dist_extra[ds]);
-                INF_EOF_CHECK();
-                if (d > p) INF_FAIL(); // in front of the block's first byte
-                INF_FLUSH();
-                {
-                    const u32 span = d < len ? d : len;
-                    if (p - d + span > fenced) {
-                        __threadfence_block();
-                        fenced = p;
-                    }
-                    const u8 *src = out + (p - d);
-                    for (u32 b = 0; b < len; b += 64u) {
-                        const u32 i = b + lane;
-                        if (i < len && p + i < limit) out[p + i] = src[d >= len ? i : i % d];
-                    }
-                }
-                p += len;
-                if (p > limit) INF_FAIL();
-            }
-            if (btype == 1u) ++nblk1;
-            else ++nblk2;
-        }
-        if (bfinal) break;
-    }
-    // exactly ISIZE bytes, and the stream ends in the byte in front of the trailer
-    (void)inf_take(r, r.cnt & 7u);
-    if (p != limit || inf_consumed(r) != total) verdict = BZ_E_DATA;
-done:
-    INF_FLUSH();
+    if (head_ok) inf_seek(r, phase + bgzf::kHeader, lane);
+    const InfOut o = inf_decode<kBgzf, true, false>(t, r, lane, head_ok ? BZ_OK : BZ_E_DATA, 0, out, q.usize, InfPiece{}, nullptr, 0u);
     if (lane == 0) {
-        BgzfRec o;
-        o.verdict = verdict;
-        o.len = p;
-        o.check = check;
-        o.nblk[0] = nblk0;
-        o.nblk[1] = nblk1;
-        o.nblk[2] = nblk2;
-        o.pad[0] = o.pad[1] = 0;
-        rec[j] = o;
+        BgzfRec x;
+        x.verdict = o.verdict;
+        x.len = o.p;
+        x.check = check;
+        x.nblk[0] = o.nblk0;
+        x.nblk[1] = o.nblk1;
+        x.nblk[2] = o.nblk2;
+        x.pad[0] = x.pad[1] = 0;
+        rec[j] = x;
     }
-#undef INF_FLUSH
-#undef INF_FAIL
-#undef INF_EOF_CHECK
 }
 
 // The CRC-32 of every clean block's bytes against its trailer, a workgroup per block: k_df_inflate_check's fold for an

@@ -79,6 +79,14 @@ def of_chunks(chunks, level=6, eof=False):
     return File(parts)
 
 
+def forged_clean_file():
+    """every clean raw stream of the Deflate forge (dfforge.clean_cases) that fits a block, a block each, in the forge's order
+    -> (File, the names of the cases that do not fit)"""
+    cases = [c for c in dfforge.clean_cases() if c.kind == dfforge.RAW]
+    fit = [c for c in cases if len(c.stream) + 26 <= 65536 and len(c.data) <= 65536]
+    return File([(bgzfref.wrap(c.data, c.stream), c.data) for c in fit]), [c.name for c in cases if c not in fit]
+
+
 def text(n, seed=1):
     """compressible, not periodic"""
     words = (b"the ", b"block ", b"index ", b"of ", b"a ", b"file ", b"read ", b"range ", b"gzip ", b"member ", b"\n")

@@ -87,3 +87,14 @@ def test_forged_trailers():
 def test_dfforge_streams_wrap():
     c = [x for x in dfforge.clean_cases() if x.kind == dfforge.RAW][0]
     assert gzip.decompress(bgzfref.wrap(c.data, c.stream)) == c.data
+
+
+def test_forged_clean_file_holds_every_clean_raw_stream_but_one():
+    f, left_out = F.forged_clean_file()
+    clean = [c for c in dfforge.clean_cases() if c.kind == dfforge.RAW]
+    assert len(clean) == 160 and f.count == 159 and left_out == ["stored_65535"]
+    assert len(next(c for c in clean if c.name == "stored_65535").stream) == 65540
+    assert f.chunks == [c.data for c in clean if c.name != "stored_65535"] and len(f.data) == 494490
+    assert gzip.decompress(f.file) == f.data
+    assert F.chain(f.file) == (f.coff, f.uoff, F.OK)
+    assert len(f.chunks[0]) >= 2 and len(f.chunks[-1]) >= 2          # a range can begin inside the first and end inside the last

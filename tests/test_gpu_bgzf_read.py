@@ -176,6 +176,20 @@ def test_whole_file(eng, name):
     whole(eng, CLEAN[name]())
 
 
+def test_every_clean_forged_stream_as_a_block(eng):
+    """The decode loop is the one the entry and piece kernels run: its BGZF form sees the corpus they see -- every clean raw
+    stream of dfforge.clean_cases() that fits a block (all but stored_65535), a block each; the expected bytes are the forge's.
+    Whole, then as a range that begins inside the first block and ends inside the last: both edge blocks go through a slot."""
+    f, left_out = F.forged_clean_file()
+    assert left_out == ["stored_65535"] and f.count == 159
+    whole(eng, f)
+    s, e = 1, f.uoff[-1] - 1
+    assert 0 < s < f.uoff[1] and f.uoff[-2] < e < f.uoff[-1]
+    t = on_device(f.file)
+    read(eng, t.data_ptr(), len(f.file), (f.coff, f.uoff), s, e - s, f.data[s:e], phases=(next(_turn),))
+    assert eng.bgzf_read_stats()[1:3] == [f.count - 2, 2] == list(_counts(f.uoff, s, e - s))
+
+
 @pytest.mark.parametrize("block_bytes", [4093, 65280])
 def test_whole_file_of_the_writers_own_output(eng, pkg, block_bytes):
     data = F.text(block_bytes + 1000 if block_bytes == 65280 else 3 * block_bytes + 17, 6)

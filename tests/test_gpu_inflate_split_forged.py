@@ -1,7 +1,7 @@
-"""GPU tests of the decode loop that the pieces of a split entry run (inf_decode in csrc/k_inflate.hip, a COPY of the
-one-wave kernel's loop; DESIGN_deflate.md "One large stream across many waves") on the whole forged corpus of
-tests/dfforge.py, and of what the copy adds to the loop: a start at any bit, the source map at a piece's start, `reach`,
-the jump rounds.
+"""GPU tests of the decode loop in the form that the pieces of a split entry run (inf_decode<kPiece, ..> in
+csrc/k_inflate.hip: the one loop that the one-wave kernel and the BGZF reader instantiate too; DESIGN_deflate.md "One large
+stream across many waves") on the whole forged corpus of tests/dfforge.py, and of what the piece form adds to the loop: a
+start at any bit, the source map at a piece's start, `reach`, the jump rounds.
 
 The threshold and the piece are 1 KiB here (BZ_DF_INF_SPLIT_KIB=1, BZ_DF_INF_PIECE_KIB=1), the smallest there are: the forged
 streams are short, and a tail of 0xFF bytes (a.) or a preamble (b. to e.: dfforge.preamble, whose last block starts at the
