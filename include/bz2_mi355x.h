@@ -1057,6 +1057,90 @@ int df_gpu_last_bgzf_read_stats(bz_gpu_engine *g, uint64_t out[8]);
 int df_bgzf_read_buffer(int device, const uint8_t *in, size_t in_len, uint64_t ustart, uint64_t ulen,
                         uint8_t **out, size_t *out_len);
 
+/* ========================================================================
+ * 9. LZHUF DECODE  ==  `LzhufDecoder` with `LzhufMethod::{Lh4, Lh5, Lh6, Lh7}`
+ *    (src/lzhuf/decoder.rs; the LHA methods -lh4- .. -lh7-) on the streams
+ *    `LzhufEncoder` writes; the contract below decides everywhere else.
+ *
+ * Many independent streams in one call, one wave per stream (k_lzhuf.hip;
+ * DESIGN_lzhuf.md has the stream format and the reasons).  One method per call:
+ *   method            BZ_LZH_LH4  BZ_LZH_LH5  BZ_LZH_LH6  BZ_LZH_LH7
+ *   dictionary_bits       12          13          15          16
+ *   offset_bits            4           4           5           5
+ * The window is 1 << dictionary_bits bytes.
+ *
+ * THE CONTRACT.  The reference's decoder cannot be the standard on anything but
+ * its encoder's streams: it pads the input with zero bits, accepts runs that
+ * pass a table's count, reads distances out of a 64 KiB ring nobody wrote, and
+ * builds a table from any lengths below 32.
+ * (a) THE END.  The format has no end marker.  At a block boundary the stream
+ *     ends with BZ_OK when fewer than 16 bits of the entry remain
+ *     (decoder.rs:221-237) or when the 16-bit block length is 0; bytes behind
+ *     that end are ignored.  An empty entry is BZ_OK without bytes.  So an entry
+ *     cut exactly at a block boundary is a clean, shorter stream: only a known
+ *     original length (b) can tell.
+ * (b) A KNOWN ORIGINAL LENGTH (what an LHA member header carries): h_orig_len
+ *     (NULL: no entry has one; an entry of UINT64_MAX: not this one).  With a
+ *     length L decoding ends with BZ_OK as soon as L bytes exist: a match that
+ *     crosses L is cut at it, nothing behind the code that reached L is read,
+ *     L == 0 reads nothing.  When the end (a) comes with fewer than L bytes the
+ *     verdict is BZ_E_EOF with the bytes produced.
+ * (c) BZ_E_EOF: a field or a code, in a block header or among a block's codes,
+ *     uses a bit behind the entry's end.  Every failure that only the zero bits
+ *     behind the end made possible is BZ_E_EOF, never BZ_E_DATA (section 5 (b)).
+ * (d) BZ_E_DATA, with the bytes in front of the failing code or block header:
+ *     a t-count above 19; a skip field that runs past the t-count; a c-count
+ *     above 510; a zero run that runs past the c-count (a constant t-code 1 or 2
+ *     that does not meet the count exactly is this case); a p-count above
+ *     dictionary_bits + 1; a constant t-symbol above 18, c-symbol above 509 or
+ *     p-symbol above dictionary_bits; any code length above 16; an explicit
+ *     length set whose Kraft sum is not exactly 1 (an all-zero set and a single
+ *     code of length 1 included: the encoder writes a lone symbol in the
+ *     constant form only); a distance greater than the bytes produced so far
+ *     when prefill < 0; a distance greater than 1 << dictionary_bits, always
+ *     (the p-count rule already keeps every distance inside the window).
+ * (e) PREFILL.  -1: strict, as above.  0 .. 255: every byte in front of position
+ *     0 of an entry's output has that value, so any distance up to the window is
+ *     valid at any position.  No address in front of the entry's output is ever
+ *     formed.  (The reference's ring reads 0 there; LHA's decoders fill their
+ *     window with 0x20.)
+ * (f) Placement, isolation, capacity and parameter errors are section 5's: d_in
+ *     16-byte aligned, input offsets multiples of 4, the ranges ascending and
+ *     disjoint, each shorter than 4 GiB; no byte at or behind the end of an
+ *     entry's range is read (its last, partial word byte by byte); output offsets
+ *     multiples of 16 in input order; NOTHING outside the reported ranges is
+ *     written; no entry's verdict or bytes change another's; the return value is
+ *     the infrastructure status.  Two launches: sizes, then (cap checked:
+ *     BZ_E_CAPACITY leaves d_out untouched) the bytes.  d_out == NULL: sizes
+ *     only.  An entry whose output would reach 4 GiB makes the call return
+ *     BZ_E_PARAM (a block of constant codes makes 16 MiB from a few bytes).
+ *     BZ_E_PARAM also: a method outside 4..7, a prefill outside -1..255, a null
+ *     engine, a null array (h_orig_len excepted) with count > 0, a misaligned
+ *     d_in, d_out or offset.  count == 0: BZ_OK, nothing touched.
+ * ======================================================================== */
+#define BZ_LZH_LH4 4
+#define BZ_LZH_LH5 5
+#define BZ_LZH_LH6 6
+#define BZ_LZH_LH7 7
+int bz_gpu_lzh_decode_batch_device(bz_gpu_engine *g, int method, int prefill, const void *d_in,
+                                   const uint64_t *h_in_off, const uint64_t *h_in_len, const uint64_t *h_orig_len, size_t count,
+                                   void *d_out, size_t cap, uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_verdict);
+/* The last bz_gpu_lzh_decode_batch_device call: [0] entries decoded clean [1] entries with an error verdict [2] blocks
+ * decoded whole (all their codes) [3] literal codes [4] match codes (one cut by the original length included) [5] decoded
+ * bytes [6] compressed bytes consumed by the clean entries (to the end (a), the zero length included, or to the code that
+ * completed the original length) [7] kernel launches. */
+int bz_gpu_last_lzh_decode_stats(bz_gpu_engine *g, uint64_t out[8]);
+/* The host form (mirrors df_decode_batch): the entries packed at 4-byte-aligned offsets, one upload, one device call on an
+ * engine of the per-process cache, one download; *out is ONE malloc'ed buffer (bz_free), entry i at out_off[i] (multiples
+ * of 16).  orig_lens as h_orig_len.  The parameters are checked before any device is touched; count == 0: BZ_OK, an empty
+ * buffer, no device.  Without a GPU: BZ_E_NOGPU. */
+int bz_lzh_decode_batch(int method, int prefill, int device, const uint8_t *const *ins, const size_t *lens,
+                        const uint64_t *orig_lens, size_t count, uint8_t **out, uint64_t *out_off, uint64_t *out_len, int32_t *verdict);
+/* The batch of one == `in.iter().cloned().decode(&mut LzhufDecoder::new(&method))` under the contract above (orig_len
+ * UINT64_MAX: not known): BZ_OK with the bytes, or the verdict with the bytes in front of it. */
+int bz_lzh_decode_buffer(int method, int prefill, int device, const uint8_t *in, size_t in_len,
+                         uint64_t orig_len, uint8_t **out, size_t *out_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,7 @@ import sys
 from . import _build
 
 __all__ = ["Action", "CompressionError", "BZip2Error", "BZip2Encoder", "BZip2Decoder", "encode", "decode",
-           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "deflate_decompress", "deflate_decompress_batch", "Deflater", "ZlibDecoder", "GZipDecoder", "gzip_decompress_members", "MultiGZipDecoder", "bgzf_compress", "bgzf_bound", "bgzf_block_count", "BgzfIndex", "bgzf_index", "bgzf_decompress", "bgzf_read", "GpuEngine", "release_cached_resources", "last_call_phases",
+           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "deflate_decompress", "deflate_decompress_batch", "Deflater", "ZlibDecoder", "GZipDecoder", "gzip_decompress_members", "MultiGZipDecoder", "bgzf_compress", "bgzf_bound", "bgzf_block_count", "BgzfIndex", "bgzf_index", "bgzf_decompress", "bgzf_read", "LzhufMethod", "LzhufDecoder", "lzhuf_decompress", "lzhuf_decompress_batch", "GpuEngine", "release_cached_resources", "last_call_phases",
            "build", "lib", "device_count", "encode_bound", "shard_window", "rccl_lib", "rccl_unique_id", "RcclComm"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -103,6 +103,7 @@ EXPORTS = [
     "df_gpu_decode_members_device", "df_gpu_last_decode_members_stats", "df_gpu_last_decode_members_timings", "df_decode_members_buffer",
     "df_bgzf_block_count", "df_bgzf_bound", "df_gpu_bgzf_encode_device", "df_gpu_last_bgzf_stats", "df_bgzf_encode_buffer",
     "df_bgzf_index_buffer", "df_gpu_bgzf_index_device", "df_gpu_bgzf_read_device", "df_gpu_last_bgzf_read_stats", "df_bgzf_read_buffer",
+    "bz_gpu_lzh_decode_batch_device", "bz_gpu_last_lzh_decode_stats", "bz_lzh_decode_batch", "bz_lzh_decode_buffer",
 ]
 
 
@@ -282,6 +283,10 @@ def lib():
     L.df_gpu_decode_batch_device_dict.argtypes = [vp, C.c_int, vp, u64p, u64p, sz, C.c_char_p, sz, vp, sz, u64p, u64p, i32p]
     L.df_decode_batch_dict.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, sz, C.c_char_p, sz, C.POINTER(u8p), u64p, u64p, i32p]
     L.df_decode_buffer_dict.argtypes = [C.c_int, C.c_int, C.c_char_p, sz, C.c_char_p, sz, C.POINTER(u8p), szp]
+    L.bz_gpu_lzh_decode_batch_device.argtypes = [vp, C.c_int, C.c_int, vp, u64p, u64p, u64p, sz, vp, sz, u64p, u64p, i32p]
+    L.bz_gpu_last_lzh_decode_stats.argtypes = [vp, u64p]
+    L.bz_lzh_decode_batch.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, u64p, sz, C.POINTER(u8p), u64p, u64p, i32p]
+    L.bz_lzh_decode_buffer.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, sz, C.c_uint64, C.POINTER(u8p), szp]
     _LIB = L
     return L
 
@@ -1095,6 +1100,77 @@ class MultiGZipDecoder(Deflater):
         return gzip_decompress_members(data, self._device)
 
 
+class LzhufMethod(enum.IntEnum):
+    """`LzhufMethod` (src/lzhuf/mod.rs:14-38): the LHA methods -lh4- .. -lh7-; the values are the C ABI's BZ_LZH_LH4 .. 7."""
+    Lh4 = 4
+    Lh5 = 5
+    Lh6 = 6
+    Lh7 = 7
+
+    @property
+    def dictionary_bits(self):
+        return {4: 12, 5: 13, 6: 15, 7: 16}[int(self)]
+
+    @property
+    def offset_bits(self):
+        return 4 if self in (LzhufMethod.Lh4, LzhufMethod.Lh5) else 5
+
+
+LZH_NO_LEN = 0xFFFFFFFFFFFFFFFF  # an original length that is not known (UINT64_MAX)
+
+
+def _lzh_params(method, prefill):
+    if int(method) not in (4, 5, 6, 7):
+        raise ValueError("invalid LZHUF method")
+    if not -1 <= int(prefill) <= 255:
+        raise ValueError("prefill must be -1 (strict) or a byte value")
+    return int(method), int(prefill)
+
+
+def _lzh_len(orig_len):
+    return LZH_NO_LEN if orig_len is None else int(orig_len)
+
+
+def lzhuf_decompress(data, method, orig_len=None, prefill=-1, device=0):
+    """One-shot over host buffers (bz_lzh_decode_buffer) -> (bytes yielded, verdict code): BZ_OK, BZ_E_DATA or BZ_E_EOF
+    under the contract of section 9 of the header.  orig_len: the original length an LHA member header carries (None: not
+    known, the stream ends at a block boundary with fewer than 16 bits left or a zero block length).  prefill: -1 is
+    strict (no distance may reach in front of the output), 0..255 the value of every byte in front of it."""
+    method, prefill = _lzh_params(method, prefill)
+    return _decode_call(lib().bz_lzh_decode_buffer, (method, prefill, device), data, _DF_VERDICTS, (_lzh_len(orig_len),))
+
+
+def lzhuf_decompress_batch(datas, method, orig_lens=None, prefill=-1, device=0):
+    """Many independent streams in one call (bz_lzh_decode_batch) -> list of (bytes yielded, verdict code): element i is
+    lzhuf_decompress(datas[i], method, orig_lens[i]).  An entry's verdict is its own; CompressionError is raised for
+    infrastructure errors only."""
+    method, prefill = _lzh_params(method, prefill)
+    datas = list(datas)
+    ol = None
+    if orig_lens is not None:
+        if len(orig_lens) != len(datas):
+            raise ValueError("lzhuf_decompress_batch: datas and orig_lens differ in length")
+        ol = (C.c_uint64 * max(len(datas), 1))(*[_lzh_len(x) for x in orig_lens])
+    return _batch_call(lambda m, f, d, ins, lens, k, *rest: lib().bz_lzh_decode_batch(m, f, d, ins, lens, ol, k, *rest),
+                       (method, prefill, device), datas, True)
+
+
+class LzhufDecoder(Deflater):
+    """`LzhufDecoder::new(&method)` (src/lzhuf/decoder.rs) with the `next(it)` / `decode_all(data)` surface of Deflater,
+    over bz_lzh_decode_buffer; strict (prefill -1) unless told otherwise.  Creating one does not touch the device."""
+
+    def __init__(self, method, device=0, orig_len=None, prefill=-1):
+        self._method, self._prefill = _lzh_params(method, prefill)
+        self._orig_len = orig_len
+        self._device = device
+        self._ready = None
+        self._pos = 0
+        self._verdict = BZ_OK
+
+    def _decode(self, data):
+        return lzhuf_decompress(data, self._method, self._orig_len, self._prefill, self._device)
+
+
 class GpuEngine:
     """Device-resident engine (section 2 of the C ABI).  Pointers are plain ints
     (e.g. torch.Tensor.data_ptr())."""
@@ -1406,6 +1482,33 @@ class GpuEngine:
         verdicts = (C.c_int32 * max(k, 1))()
         _check(lib().df_gpu_decode_batch_device_dict(self._h, kind, d_in, a_off, a_len, k, dict_, len(dict_), d_out, cap, o_off, o_len, verdicts))
         return list(o_off[:k]), list(o_len[:k]), [int(v) for v in verdicts[:k]]
+
+    LZH_DECODE_STATS = ("clean", "errors", "blocks", "literals", "matches", "decoded_bytes", "consumed_bytes", "launches")
+
+    def lzh_decode_batch_device(self, method, d_in, in_off, in_len, d_out, cap, orig_len=None, prefill=-1):
+        """Many LZHUF streams in one call (bz_gpu_lzh_decode_batch_device; section 9 of the header): entry i is the
+        in_len[i] bytes at d_in + in_off[i] (offsets multiples of 4, ascending); returns (out_off, out_len, verdicts), entry
+        i's bytes at d_out + out_off[i].  d_out = None: sizes only.  orig_len: None, or one length per entry (None: not
+        known).  A method outside 4..7 or a prefill outside -1..255 is the C call's BZ_E_PARAM."""
+        _settle()
+        k = len(in_off)
+        if len(in_len) != k or (orig_len is not None and len(orig_len) != k):
+            raise ValueError("lzh_decode_batch_device: the per-entry arrays differ in length")
+        a_off = (C.c_uint64 * max(k, 1))(*in_off)
+        a_len = (C.c_uint64 * max(k, 1))(*in_len)
+        a_ol = None if orig_len is None else (C.c_uint64 * max(k, 1))(*[_lzh_len(x) for x in orig_len])
+        o_off = (C.c_uint64 * max(k, 1))()
+        o_len = (C.c_uint64 * max(k, 1))()
+        verdicts = (C.c_int32 * max(k, 1))()
+        _check(lib().bz_gpu_lzh_decode_batch_device(self._h, int(method), int(prefill), d_in, a_off, a_len, a_ol, k, d_out, cap, o_off, o_len,
+                                                    verdicts))
+        return list(o_off[:k]), list(o_len[:k]), [int(v) for v in verdicts[:k]]
+
+    def lzh_decode_stats(self):
+        """The last lzh_decode_batch_device call, in the order of LZH_DECODE_STATS (bz_gpu_last_lzh_decode_stats)."""
+        s = (C.c_uint64 * 8)()
+        _check(lib().bz_gpu_last_lzh_decode_stats(self._h, s))
+        return [int(x) for x in s]
 
     def deflate_decode_batch_stats(self):
         """The last deflate_decode_batch_device call, in the order of DEFLATE_DECODE_BATCH_STATS

@@ -246,6 +246,7 @@ extern "C" void bz_gpu_engine_destroy(bz_gpu_engine *g)
     (void)hipStreamSynchronize(g->st2);
     dec_workspace_free(g->dec);
     df_workspace_free(g->df);
+    lzh_workspace_free(g->lzh);
     if (g->h_active) (void)hipHostFree(g->h_active);
     mail_release(g->st);
     mail_release(g->st2);

@@ -22,6 +22,8 @@ int dec_decode_for_verify(struct bz_gpu_engine *g, const uint8_t *d_in, uint64_t
 void dec_spare_bufs_clear(); // dec_engine.hip: the byte buffers finished bz_dec contexts leave for the next one
 struct DfWorkspace;
 void df_workspace_free(DfWorkspace *w);
+struct LzhWorkspace;
+void lzh_workspace_free(LzhWorkspace *w);
 
 #define HIPCHK(x)                                                                                     \
     do {                                                                                              \
@@ -108,5 +110,6 @@ struct bz_gpu_engine {
     DecWorkspace *dec = nullptr; // decode workspace, created by the first decode call
     DevBuf dec_in, oneshot_out;  // bz_decode_buffer / df_encode_buffer: the caller's bytes on the device and the result (kept with the cached engine)
     DfWorkspace *df = nullptr;   // Deflate encode workspace, created by the first df_gpu_encode_device call
+    LzhWorkspace *lzh = nullptr; // LZHUF decode workspace, created by the first bz_gpu_lzh_decode_batch_device call
 };
 

@@ -507,6 +507,91 @@ using ZlibDecoder = DeflateFamilyDecoder<DF_KIND_ZLIB>;
 using GZipDecoder = DeflateFamilyDecoder<DF_KIND_GZIP>;
 using MultiGZipDecoder = DeflateFamilyDecoder<DF_KIND_GZIP, true>;
 
+// LZHUF decoder (include/bz2_mi355x.h section 9):
+//   enum LzhufMethod    src/lzhuf/mod.rs:14-38        the LHA methods -lh4- .. -lh7-
+//   LzhufDecoder        src/lzhuf/decoder.rs:323-349  LzhufDecoder::new(&method)
+// The first next() collects the input range and decodes it in one bz_lzh_decode_buffer call; the bytes come out in order,
+// then the Err item if the stream is bad under the contract of section 9, then None.  orig_len: the original length an LHA
+// member header carries (none: the stream ends at a block boundary with fewer than 16 bits left or a zero block length);
+// prefill: -1 strict (the default), 0 .. 255 the value of every byte in front of the output (LHA's decoders use 0x20).
+enum class LzhufMethod { Lh4 = BZ_LZH_LH4, Lh5 = BZ_LZH_LH5, Lh6 = BZ_LZH_LH6, Lh7 = BZ_LZH_LH7 };
+
+class LzhufDecoder {
+  public:
+    using Input = uint8_t;
+    using Output = uint8_t;
+    using Error = CompressionError;
+
+    explicit LzhufDecoder(LzhufMethod method, int device = 0, std::optional<uint64_t> orig_len = std::nullopt, int prefill = -1)
+        : method_(static_cast<int>(method)), device_(device), prefill_(prefill), orig_len_(orig_len ? *orig_len : UINT64_MAX)
+    {
+    } // (does not touch the device)
+
+    template <class I, class S> std::optional<Result<uint8_t>> next(I &it, const S &end)
+    {
+        if (!ran_) {
+            ran_ = true;
+            std::vector<uint8_t> in;
+            for (; it != end; ++it) in.push_back(static_cast<uint8_t>(*it));
+            uint8_t *out = nullptr;
+            size_t n = 0;
+            verdict_ = bz_lzh_decode_buffer(method_, prefill_, device_, in.data(), in.size(), orig_len_, &out, &n);
+            if (out) {
+                buf_.assign(out, out + n);
+                bz_free(out);
+            }
+        }
+        if (pos_ < buf_.size()) return Result<uint8_t>::Ok(buf_[pos_++]);
+        if (verdict_ != BZ_OK) {
+            const int rc = verdict_;
+            verdict_ = BZ_OK;
+            return Result<uint8_t>::Err(from_status(rc));
+        }
+        return std::nullopt;
+    }
+
+    // Many independent streams in one call (bz_lzh_decode_batch): element i is what `inputs[i].decode(..)` yields.
+    // orig_lens: empty, or one length per stream (UINT64_MAX: not known).
+    struct Entry {
+        std::vector<uint8_t> bytes;
+        std::optional<CompressionError> error;
+    };
+    template <class Spans>
+    static Result<std::vector<Entry>> decode_batch(const Spans &inputs, LzhufMethod method, const std::vector<uint64_t> &orig_lens = {},
+                                                   int prefill = -1, int device = 0)
+    {
+        using R = Result<std::vector<Entry>>;
+        std::vector<const uint8_t *> ptrs;
+        std::vector<size_t> lens;
+        for (const auto &x : inputs) {
+            ptrs.push_back(reinterpret_cast<const uint8_t *>(x.data()));
+            lens.push_back(x.size());
+        }
+        if (!orig_lens.empty() && orig_lens.size() != ptrs.size()) return R::Err(from_status(BZ_E_PARAM));
+        std::vector<uint64_t> off(ptrs.size()), len(ptrs.size());
+        std::vector<int32_t> verdict(ptrs.size());
+        uint8_t *out = nullptr;
+        const int rc = bz_lzh_decode_batch(static_cast<int>(method), prefill, device, ptrs.data(), lens.data(),
+                                           orig_lens.empty() ? nullptr : orig_lens.data(), ptrs.size(), &out, off.data(), len.data(), verdict.data());
+        if (rc != BZ_OK) return R::Err(from_status(rc));
+        std::vector<Entry> entries(ptrs.size());
+        for (size_t i = 0; i < ptrs.size(); ++i) {
+            entries[i].bytes.assign(out + off[i], out + off[i] + len[i]);
+            if (verdict[i] != BZ_OK) entries[i].error = from_status(verdict[i]);
+        }
+        bz_free(out);
+        return R::Ok(std::move(entries));
+    }
+
+  private:
+    int method_, device_, prefill_;
+    uint64_t orig_len_;
+    bool ran_ = false;
+    int verdict_ = BZ_OK;
+    std::vector<uint8_t> buf_;
+    size_t pos_ = 0;
+};
+
 // One input as a BGZF file (include/bz2_mi355x.h section 7, df_bgzf_encode_buffer): gzip members of at most block_bytes
 // (0: 65 280) input bytes side by side, then the 28-byte EOF marker unless eof is false.  The reference has no such writer;
 // every member is a stream that zlib, gzip(1) and htslib read.  block_off, when not null, receives the file offset of every

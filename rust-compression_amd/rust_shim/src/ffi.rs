@@ -70,6 +70,12 @@ extern "C" {
     pub fn df_decode_batch_dict(kind: i32, device: i32, ins: *const *const u8, lens: *const usize, count: usize, dict: *const u8, dict_len: usize, out: *mut *mut u8, out_off: *mut u64, out_len: *mut u64, verdict: *mut i32) -> i32;
     pub fn df_decode_buffer_dict(kind: i32, device: i32, input: *const u8, in_len: usize, dict: *const u8, dict_len: usize, out: *mut *mut u8, out_len: *mut usize) -> i32;
 
+    // section 9: LZHUF decode (LzhufDecoder); h_orig_len / orig_lens may be null, an entry of u64::MAX is "not known"
+    pub fn bz_gpu_lzh_decode_batch_device(g: *mut c_void, method: i32, prefill: i32, d_in: *const c_void, h_in_off: *const u64, h_in_len: *const u64, h_orig_len: *const u64, count: usize, d_out: *mut c_void, cap: usize, h_out_off: *mut u64, h_out_len: *mut u64, h_verdict: *mut i32) -> i32;
+    pub fn bz_gpu_last_lzh_decode_stats(g: *mut c_void, out: *mut u64) -> i32;
+    pub fn bz_lzh_decode_batch(method: i32, prefill: i32, device: i32, ins: *const *const u8, lens: *const usize, orig_lens: *const u64, count: usize, out: *mut *mut u8, out_off: *mut u64, out_len: *mut u64, verdict: *mut i32) -> i32;
+    pub fn bz_lzh_decode_buffer(method: i32, prefill: i32, device: i32, input: *const u8, in_len: usize, orig_len: u64, out: *mut *mut u8, out_len: *mut usize) -> i32;
+
     // section 6: every member of a gzip file (MultiGZipDecoder)
     pub fn df_gpu_decode_members_device(g: *mut c_void, d_in: *const c_void, in_len: usize, d_out: *mut c_void, cap: usize, out_len: *mut u64, verdict: *mut i32) -> i32;
     pub fn df_gpu_last_decode_members_stats(g: *mut c_void, out: *mut u64) -> i32;

@@ -221,6 +221,41 @@ pub fn decode_batch(inputs: &[&[u8]]) -> Result<Vec<Result<Vec<u8>, (BZip2Error,
     Ok(entries)
 }
 
+/// Many independent LZHUF streams in one call (`bz_lzh_decode_batch`, device 0, strict): element `i` of the result is what
+/// `inputs[i].iter().cloned().decode(&mut LzhufDecoder::new(&method))` yields -- `Ok(bytes)`, or the error with the bytes in
+/// front of it.  `orig_lens`: empty, or the original length of every stream (`u64::MAX`: not known).  The outer `Err` is an
+/// infrastructure failure (`last_status` says which).
+#[cfg(feature = "lzhuf")]
+pub fn lzh_decode_batch(method: crate::lzhuf::LzhufMethod, inputs: &[&[u8]], orig_lens: &[u64]) -> Result<Vec<Result<Vec<u8>, (CompressionError, Vec<u8>)>>, CompressionError> {
+    if !orig_lens.is_empty() && orig_lens.len() != inputs.len() {
+        return Err(CompressionError::from_status(ffi::BZ_E_PARAM));
+    }
+    let ptrs: Vec<*const u8> = inputs.iter().map(|x| x.as_ptr()).collect();
+    let lens: Vec<usize> = inputs.iter().map(|x| x.len()).collect();
+    let mut off: Vec<u64> = Vec::new();
+    off.resize(inputs.len(), 0);
+    let mut len = off.clone();
+    let mut verdict: Vec<i32> = Vec::new();
+    verdict.resize(inputs.len(), 0);
+    let mut out: *mut u8 = core::ptr::null_mut();
+    let ol = if orig_lens.is_empty() { core::ptr::null() } else { orig_lens.as_ptr() };
+    let rc = unsafe {
+        ffi::bz_lzh_decode_batch(method.abi(), -1, 0, ptrs.as_ptr(), lens.as_ptr(), ol, inputs.len(), &mut out, off.as_mut_ptr(), len.as_mut_ptr(), verdict.as_mut_ptr())
+    };
+    if rc != ffi::BZ_OK {
+        note_status(rc);
+        return Err(CompressionError::from_status(rc));
+    }
+    let entries = (0..inputs.len())
+        .map(|i| {
+            let bytes = unsafe { core::slice::from_raw_parts(out.add(off[i] as usize), len[i] as usize) }.to_vec();
+            if verdict[i] == ffi::BZ_OK { Ok(bytes) } else { Err((CompressionError::from_status(verdict[i]), bytes)) }
+        })
+        .collect();
+    unsafe { ffi::bz_free(out as *mut core::ffi::c_void) };
+    Ok(entries)
+}
+
 pub(crate) fn note_status(rc: i32) {
     if rc != 0 {
         LAST_STATUS.store(rc, Ordering::Relaxed);
