@@ -1141,6 +1141,63 @@ int bz_lzh_decode_batch(int method, int prefill, int device, const uint8_t *cons
 int bz_lzh_decode_buffer(int method, int prefill, int device, const uint8_t *in, size_t in_len,
                          uint64_t orig_len, uint8_t **out, size_t *out_len);
 
+/* ========================================================================
+ * 10. LZHUF ENCODE  ==  `LzhufEncoder::new(&method)` driven with Action::Finish
+ *     (src/lzhuf/encoder.rs), many independent inputs in one call.
+ *
+ * Stream i is `input_i.encode(&mut LzhufEncoder::new(&method), Action::Finish)`
+ * collected, byte for byte: LzssEncoder with a window of 1 << dictionary_bits,
+ * matches of 3 .. 256 bytes, lazy level 3 and Deflate's comparison; blocks of
+ * 65 535 CODES (the last one shorter) with their t-, c- and p-table; no end
+ * marker; zero bits to the next byte at the end of the stream; an empty input
+ * gives an empty stream.  One method per call (section 9's table).
+ *
+ * Inputs as in df_gpu_encode_batch_device: d_in 16-byte aligned, h_in_off
+ * multiples of 16, the ranges ascending and disjoint; every input at most
+ * 1 GiB (positions are 32-bit; a longer one is BZ_E_PARAM -- encoding in
+ * parts is not offered).  Streams are written to d_out (4-byte aligned) in
+ * input order, stream i at h_out_off[i] (a multiple of 4) with h_out_len[i]
+ * bytes, zeros between a stream's end and the next multiple of 4, and nothing
+ * at or behind d_out + cap.  (d_out, h_out_off, h_out_len) are valid
+ * (d_in, h_in_off, h_in_len) of bz_gpu_lzh_decode_batch_device, and that
+ * call's outputs (multiples of 16) are valid inputs of this one.
+ * BZ_E_CAPACITY: cap is too small (bz_lzh_encode_batch_bound always suffices;
+ * bytes in front of d_out + cap may have been written).  BZ_E_PARAM: a method
+ * outside 4 .. 7, a null engine, a null array or d_out with count > 0, a
+ * misaligned d_in, d_out or offset, ranges out of order, an input above 1 GiB.
+ * count == 0: BZ_OK, nothing touched.
+ * ======================================================================== */
+int bz_gpu_lzh_encode_batch_device(bz_gpu_engine *g, int method, const void *d_in, const uint64_t *h_in_off,
+                                   const uint64_t *h_in_len, size_t count, void *d_out, size_t cap, uint64_t *h_out_off,
+                                   uint64_t *h_out_len);
+/* The last bz_gpu_lzh_encode_batch_device call: [0] inputs [1] sub-batches (BZ_DF_BATCH_MIB of slot image each; an input
+ * larger than that has one of its own) [2] blocks [3] literal codes [4] match codes [5] input bytes [6] stream bytes
+ * [7] c-tables that took make_table's length-limited path. */
+int bz_gpu_last_lzh_encode_stats(bz_gpu_engine *g, uint64_t out[8]);
+/* Bytes that always suffice for the streams of inputs of these lengths, each rounded up to 4 (DESIGN_lzhuf.md section 8: a
+ * code costs at most 16 bits per input byte, a block header at most 1 084 bytes per 65 535 codes). */
+size_t bz_lzh_encode_batch_bound(const uint64_t *in_len, size_t count);
+/* The host form (mirrors df_encode_batch): the inputs packed at 16-byte-aligned offsets, one upload, one device call on an
+ * engine of the per-process cache, one download; *out is ONE malloc'ed buffer (bz_free), stream i at out_off[i].  The
+ * parameters are checked before any device is touched; count == 0: BZ_OK, an empty buffer, no device.  Without a GPU:
+ * BZ_E_NOGPU. */
+int bz_lzh_encode_batch(int method, int device, const uint8_t *const *ins, const size_t *lens, size_t count, uint8_t **out,
+                        uint64_t *out_off, uint64_t *out_len);
+/* The batch of one == `in.encode(&mut LzhufEncoder::new(&method), Action::Finish).collect()`. */
+int bz_lzh_encode_buffer(int method, int device, const uint8_t *in, size_t in_len, uint8_t **out, size_t *out_len);
+/* Test hook: the LZSS codes of ONE input (n bytes of device memory, 16-byte aligned) under `method`, in stream order as
+ * (len, pos) pairs, len 0 = the literal `pos`, else a match of len bytes at distance pos + 1 (what LzssEncoder::next
+ * yields).  At most cap pairs are written; *count is the number of codes. */
+int bz_gpu_lzh_debug_codes(bz_gpu_engine *g, int method, const void *d_in, size_t n, uint32_t *out_pairs, size_t cap,
+                           size_t *count);
+/* Test hook: the block stage's table builder on the host's counts (510 c-counts: literals, then lengths 3 .. 256; 17
+ * p-counts by the bit length of distance - 1).  c_len[510], p_len[17], t_len[19]: make_table's lengths (a lone symbol has
+ * length 1 and is written in the constant form; t_len is all zero when the c-table is a constant).  res[0]: bits of the
+ * block header, the 16-bit code count included; res[1]: bit 0 the c-table is a constant, bit 1 the p-table, bit 2 the
+ * t-table; res[2]: tables that took the length-limited path. */
+int bz_gpu_lzh_debug_tables(bz_gpu_engine *g, int method, const uint32_t *c_freq, const uint32_t *p_freq, uint8_t *c_len,
+                            uint8_t *p_len, uint8_t *t_len, uint32_t res[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,7 @@ import sys
 from . import _build
 
 __all__ = ["Action", "CompressionError", "BZip2Error", "BZip2Encoder", "BZip2Decoder", "encode", "decode",
-           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "deflate_decompress", "deflate_decompress_batch", "Deflater", "ZlibDecoder", "GZipDecoder", "gzip_decompress_members", "MultiGZipDecoder", "bgzf_compress", "bgzf_bound", "bgzf_block_count", "BgzfIndex", "bgzf_index", "bgzf_decompress", "bgzf_read", "LzhufMethod", "LzhufDecoder", "lzhuf_decompress", "lzhuf_decompress_batch", "GpuEngine", "release_cached_resources", "last_call_phases",
+           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "deflate_decompress", "deflate_decompress_batch", "Deflater", "ZlibDecoder", "GZipDecoder", "gzip_decompress_members", "MultiGZipDecoder", "bgzf_compress", "bgzf_bound", "bgzf_block_count", "BgzfIndex", "bgzf_index", "bgzf_decompress", "bgzf_read", "LzhufMethod", "LzhufDecoder", "lzhuf_decompress", "lzhuf_decompress_batch", "LzhufEncoder", "lzhuf_compress", "lzhuf_compress_batch", "lzhuf_encode_batch_bound", "GpuEngine", "release_cached_resources", "last_call_phases",
            "build", "lib", "device_count", "encode_bound", "shard_window", "rccl_lib", "rccl_unique_id", "RcclComm"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -104,6 +104,8 @@ EXPORTS = [
     "df_bgzf_block_count", "df_bgzf_bound", "df_gpu_bgzf_encode_device", "df_gpu_last_bgzf_stats", "df_bgzf_encode_buffer",
     "df_bgzf_index_buffer", "df_gpu_bgzf_index_device", "df_gpu_bgzf_read_device", "df_gpu_last_bgzf_read_stats", "df_bgzf_read_buffer",
     "bz_gpu_lzh_decode_batch_device", "bz_gpu_last_lzh_decode_stats", "bz_lzh_decode_batch", "bz_lzh_decode_buffer",
+    "bz_gpu_lzh_encode_batch_device", "bz_gpu_last_lzh_encode_stats", "bz_lzh_encode_batch_bound", "bz_lzh_encode_batch",
+    "bz_lzh_encode_buffer", "bz_gpu_lzh_debug_codes", "bz_gpu_lzh_debug_tables",
 ]
 
 
@@ -287,6 +289,14 @@ def lib():
     L.bz_gpu_last_lzh_decode_stats.argtypes = [vp, u64p]
     L.bz_lzh_decode_batch.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, u64p, sz, C.POINTER(u8p), u64p, u64p, i32p]
     L.bz_lzh_decode_buffer.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, sz, C.c_uint64, C.POINTER(u8p), szp]
+    L.bz_gpu_lzh_encode_batch_device.argtypes = [vp, C.c_int, vp, u64p, u64p, sz, vp, sz, u64p, u64p]
+    L.bz_gpu_last_lzh_encode_stats.argtypes = [vp, u64p]
+    L.bz_lzh_encode_batch_bound.argtypes = [u64p, sz]
+    L.bz_lzh_encode_batch_bound.restype = sz
+    L.bz_lzh_encode_batch.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, sz, C.POINTER(u8p), u64p, u64p]
+    L.bz_lzh_encode_buffer.argtypes = [C.c_int, C.c_int, C.c_char_p, sz, C.POINTER(u8p), szp]
+    L.bz_gpu_lzh_debug_codes.argtypes = [vp, C.c_int, vp, sz, C.POINTER(C.c_uint32), sz, szp]
+    L.bz_gpu_lzh_debug_tables.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u8p, u8p, u8p, C.POINTER(C.c_uint32)]
     _LIB = L
     return L
 
@@ -1171,6 +1181,91 @@ class LzhufDecoder(Deflater):
         return lzhuf_decompress(data, self._method, self._orig_len, self._prefill, self._device)
 
 
+def _lzh_method(method):
+    if int(method) not in (4, 5, 6, 7):
+        raise ValueError("invalid LZHUF method")
+    return int(method)
+
+
+def lzhuf_encode_batch_bound(lens):
+    """An output capacity that always suffices for GpuEngine.lzh_encode_batch_device (bz_lzh_encode_batch_bound)."""
+    a = (C.c_uint64 * max(len(lens), 1))(*lens)
+    return lib().bz_lzh_encode_batch_bound(a, len(lens))
+
+
+def lzhuf_compress(data, method, device=0):
+    """One-shot over host buffers (bz_lzh_encode_buffer): `data.encode(&mut LzhufEncoder::new(&method), Action::Finish)`
+    collected, byte for byte.  An empty input gives an empty stream."""
+    method = _lzh_method(method)
+    data = bytes(data)
+    out = C.POINTER(C.c_uint8)()
+    n = C.c_size_t(0)
+    _check(lib().bz_lzh_encode_buffer(method, device, data, len(data), C.byref(out), C.byref(n)))
+    try:
+        return C.string_at(out, n.value)
+    finally:
+        lib().bz_free(out)
+
+
+def lzhuf_compress_batch(datas, method, device=0):
+    """Many independent inputs in one call (bz_lzh_encode_batch) -> list of streams: element i is
+    lzhuf_compress(datas[i], method), bit for bit.  All inputs share passes of the pipeline, however many there are."""
+    return _batch_call(lib().bz_lzh_encode_batch, (_lzh_method(method), device), datas, False)
+
+
+class LzhufEncoder:
+    """`LzhufEncoder::new(&method)` (src/lzhuf/encoder.rs) in the shape of Inflater: `next(it, action)`, `write`, `end`,
+    `read_all`, `encode_all`.  Action.RUN accumulates and Action.FINISH ends the stream; Action.FLUSH is NOT offered (the
+    reference's flush closes the block and pads to a byte in the middle of a stream; this encoder writes whole streams
+    only) and is a parameter error.  The bytes are encoded by one bz_lzh_encode_buffer call when the stream is finished;
+    creating an encoder does not touch the device."""
+
+    def __init__(self, method, device=0):
+        self._method = _lzh_method(method)
+        self._device = device
+        self._in = bytearray()
+        self._ready = b""
+        self._pos = 0
+        self._finished = False
+
+    def write(self, data):
+        if self._finished:
+            raise CompressionError(BZ_E_PARAM)
+        self._in += bytes(data)
+
+    def end(self, action):
+        if int(action) == int(Action.FLUSH):
+            raise CompressionError(BZ_E_PARAM)
+        if int(action) not in (int(Action.RUN), int(Action.FINISH)):
+            raise ValueError("invalid action")
+        if int(action) == int(Action.FINISH) and not self._finished:
+            self._ready = self._ready[self._pos:] + lzhuf_compress(bytes(self._in), self._method, self._device)
+            self._pos = 0
+            self._in = bytearray()
+            self._finished = True
+
+    def next(self, it, action):
+        """One `Encoder::next(iter, action)` call: an int byte, or None (Action.RUN: nothing is yielded before FINISH)."""
+        if self._pos >= len(self._ready) and not self._finished:
+            self._in += bytes(bytearray(it))
+            self.end(action)
+        if self._pos >= len(self._ready):
+            return None
+        b = self._ready[self._pos]
+        self._pos += 1
+        return b
+
+    def read_all(self):
+        out = self._ready[self._pos:]
+        self._ready, self._pos = b"", 0
+        return out
+
+    def encode_all(self, data, action=Action.FINISH):
+        self.write(data)
+        self.end(action)
+        return self.read_all()
+
+
 class GpuEngine:
     """Device-resident engine (section 2 of the C ABI).  Pointers are plain ints
     (e.g. torch.Tensor.data_ptr())."""
@@ -1509,6 +1604,52 @@ class GpuEngine:
         s = (C.c_uint64 * 8)()
         _check(lib().bz_gpu_last_lzh_decode_stats(self._h, s))
         return [int(x) for x in s]
+
+    LZH_ENCODE_STATS = ("inputs", "sub_batches", "blocks", "literals", "matches", "input_bytes", "stream_bytes", "limited_tables")
+
+    def lzh_encode_batch_device(self, method, d_in, in_off, in_len, d_out, cap):
+        """Many inputs, one LZHUF stream each (bz_gpu_lzh_encode_batch_device; section 10 of the header): input i is the
+        in_len[i] bytes at d_in + in_off[i] (offsets multiples of 16, ascending); returns (out_off, out_len), stream i at
+        d_out + out_off[i] (multiples of 4).  A method outside 4..7 is the C call's BZ_E_PARAM."""
+        _settle()
+        k = len(in_off)
+        if len(in_len) != k:
+            raise ValueError("lzh_encode_batch_device: in_off and in_len differ in length")
+        a_off = (C.c_uint64 * max(k, 1))(*in_off)
+        a_len = (C.c_uint64 * max(k, 1))(*in_len)
+        o_off = (C.c_uint64 * max(k, 1))()
+        o_len = (C.c_uint64 * max(k, 1))()
+        _check(lib().bz_gpu_lzh_encode_batch_device(self._h, int(method), d_in, a_off, a_len, k, d_out, cap, o_off, o_len))
+        return list(o_off[:k]), list(o_len[:k])
+
+    def lzh_encode_stats(self):
+        """The last lzh_encode_batch_device call, in the order of LZH_ENCODE_STATS (bz_gpu_last_lzh_encode_stats)."""
+        s = (C.c_uint64 * 8)()
+        _check(lib().bz_gpu_last_lzh_encode_stats(self._h, s))
+        return [int(x) for x in s]
+
+    def lzh_debug_codes(self, method, d_in, n):
+        """The LZSS codes of the n bytes at d_in under `method` (bz_gpu_lzh_debug_codes): numpy uint32 [count, 2] of
+        (len, pos); len 0: the literal pos, else a match of len bytes at distance pos + 1."""
+        import numpy as np
+        _settle()
+        buf = np.zeros((n + 1, 2), dtype=np.uint32)
+        cnt = C.c_size_t(0)
+        _check(lib().bz_gpu_lzh_debug_codes(self._h, int(method), d_in, n, buf.ctypes.data_as(C.POINTER(C.c_uint32)), n + 1, C.byref(cnt)))
+        return buf[:cnt.value]
+
+    def lzh_debug_tables(self, method, c_freq, p_freq):
+        """The block stage's table builder on 510 c-counts and 17 p-counts (bz_gpu_lzh_debug_tables) ->
+        (c_len[510], p_len[17], t_len[19], header bits, flags, limited tables)."""
+        _settle()
+        if len(c_freq) != 510 or len(p_freq) != 17:
+            raise ValueError("lzh_debug_tables: 510 c-counts and 17 p-counts")
+        cf = (C.c_uint32 * 510)(*c_freq)
+        pf = (C.c_uint32 * 17)(*p_freq)
+        cl, pl, tl = (C.c_uint8 * 510)(), (C.c_uint8 * 17)(), (C.c_uint8 * 19)()
+        res = (C.c_uint32 * 3)()
+        _check(lib().bz_gpu_lzh_debug_tables(self._h, int(method), cf, pf, cl, pl, tl, res))
+        return list(cl), list(pl), list(tl), int(res[0]), int(res[1]), int(res[2])
 
     def deflate_decode_batch_stats(self):
         """The last deflate_decode_batch_device call, in the order of DEFLATE_DECODE_BATCH_STATS

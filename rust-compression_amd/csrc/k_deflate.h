@@ -147,6 +147,42 @@ int df_launch_blocks_strict(hipStream_t st, const u8 *image, const u32 *code, co
 int df_launch_exact_offsets(hipStream_t st, DfBlock *blocks, u32 nslots, u32 head, u32 tail, DfBatchOut *outs, u64 *total);
 int df_launch_bgzf_wrap(hipStream_t st, const u8 *image, const DfSlot *slots, u32 nslots, const DfBlock *blocks, const DfBatchOut *outs,
                         DfCrcShifts xk, u8 *out, u32 *stats);
+// ---- LZHUF encode (bz_gpu_lzh_encode_batch_device, lzhuf_engine.hip; DESIGN_lzhuf.md sections 7 to 9): the batch front end
+// above with LZHUF's window (1 << dbits), its longest match (256) and 64 KiB of history in front of every sort chunk, then
+// blocks of 65 535 CODES.  Block k of a sub-batch belongs to slot `slot`; the blocks of slot j are bbase[j] .. bbase[j + 1] - 1,
+// as many as the input could need (ceil(len / 65535)); those its parse does not fill have ncodes == 0.
+constexpr u32 kLzhHist = 0x10000;                 // positions sorted in front of a chunk: the window of lh7
+constexpr u32 kLzhStride = kChunk + kLzhHist;     // entries of one sort chunk
+constexpr u32 kLzhBlockCodes = 0xFFFF;            // lzhuf/encoder.rs: codes per block
+constexpr u32 kLzhNC = 510, kLzhNP = 17, kLzhNT = 19;
+constexpr u32 kLzhHdrWords = 288;                 // a block header is at most 8 665 bits (DESIGN_lzhuf.md section 8)
+constexpr u32 kLzhLensBytes = 576;                // per block: 512 c-lengths, 32 p-lengths, 32 t-lengths
+constexpr u32 kLzhLmWords = 3 * kLzhNC + 64 + 2 * 16 * (2 * kLzhNC + 4); // scratch of one length-limited c-table
+constexpr u32 kLzhSerialTiles = 64;               // a sub-batch of ONE slot with more tiles composes its exit tables
+struct LzhBlk {
+    u64 start, end; // image positions: its first code, and one past its last code's position
+    u64 bits;       // header and codes
+    u64 bit_off;    // where it starts in the sub-batch's output
+    u32 slot, ncodes, hdr_bits;
+    u32 flags;      // bit 0: the c-table is a constant, bit 1: the p-table is (or there is no match), bit 2: the t-table is
+    u32 nlit, nmatch, lm, pad;
+};
+static_assert(sizeof(LzhBlk) == 64, "LzhBlk is copied between host and device as it is");
+struct LzhOut { u64 off, len; }; // a stream inside the sub-batch's output (off: a multiple of 4)
+// v0, s: df_chunks(n) * kLzhStride + 16 words each (and at least n + 16: M and code take their place); hist:
+// (df_chunks(n) * kLzhStride / kSortTile + 1) * 256 words; tbase: 2 * (df_chunks(n) + 1) * 256 words
+int lzh_launch_front(hipStream_t st, u32 dbits, const u8 *image, u64 n, u32 ntiles, const DfSlot *slots, u32 nslots, const u32 *tile_slot,
+                     u32 *v0, u32 *s, u32 *hist, u32 *tbase, u16 *step, u16 *tab, u16 *ent, u64 *bm, u64 *canon);
+// tab: lzh_tab_entries(ntiles) u16, ent: lzh_ent_entries(ntiles) u16
+size_t lzh_tab_entries(u32 ntiles);
+size_t lzh_ent_entries(u32 ntiles);
+int lzh_launch_cuts(hipStream_t st, const DfSlot *slots, u32 nslots, const u32 *bbase, const u64 *bm, LzhBlk *blks);
+int lzh_launch_blocks(hipStream_t st, const u8 *image, const u32 *code, LzhBlk *blks, u32 nblks, u32 pbits, u8 *lens, u32 *hdr, u32 *lm_scratch);
+int lzh_launch_offsets(hipStream_t st, LzhBlk *blks, const u32 *bbase, u32 nslots, LzhOut *outs, u64 *total);
+int lzh_launch_emit(hipStream_t st, const u8 *image, const u32 *code, const LzhBlk *blks, u32 nblks, const u8 *lens, const u32 *hdr, u32 *out);
+// the block stage's table builder on given counts (bz_gpu_lzh_debug_tables): lens as one block's, res[0] = header bits
+// (the 16-bit code count included), res[1] = flags, res[2] = tables on the length-limited path
+int lzh_launch_tables_debug(hipStream_t st, const u32 *cfreq, const u32 *pfreq, u32 pbits, u8 *lens, u32 *hdr, u32 *lm_scratch, u32 *res);
 // ---- decode of many streams (df_gpu_decode_batch_device; k_inflate.hip): what the sizes launch leaves per entry
 struct DfInfRec {
     u64 end_bit;  // bits of the entry consumed: to the end of the stream or its trailer, or to the failing code

@@ -65,42 +65,45 @@ __device__ __forceinline__ u32 df_hash_at(const u8 *__restrict__ in, u32 pos, u6
     return hash16(w & 0xFFu, (w >> 8) & 0xFFu, (w >> 16) & 0xFFu);
 }
 
+// HIST: the positions in front of a chunk that are sorted with it (kWin for Deflate; LZHUF's lh7 looks back 64 KiB)
+template <u32 HIST = kWin>
 __device__ __forceinline__ u32 df_chunk_count(u32 c, u64 ntri, u32 &j0)
 {
-    j0 = c == 0 ? kWin : 0u;
-    const u64 lim = ntri - (u64)c * kChunk + kWin; // entries j with position < ntri
-    return (u32)(lim < kChunkStride ? lim : kChunkStride) - j0;
+    j0 = c == 0 ? HIST : 0u;
+    const u64 lim = ntri - (u64)c * kChunk + HIST; // entries j with position < ntri
+    return (u32)(lim < kChunk + HIST ? lim : kChunk + HIST) - j0;
 }
 
 // element `idx` of the pass input of chunk c.  PASS 0: the chunk's positions in order, digit = low byte of the
 // hash; what it hands on is the position relative to the chunk (21 bits) with the HIGH byte of the hash on top,
 // so that PASS 1 (digit = that byte) does not touch the text again.
-template <int PASS>
+template <int PASS, u32 HIST = kWin>
 __device__ __forceinline__ bool df_pass_elem(const u8 *__restrict__ in, u64 ntri, const u32 *__restrict__ src, u32 c, u32 idx,
                                              u32 count, u32 j0, u32 &val, u32 &dg)
 {
     if (idx >= count) { val = 0; dg = 0; return false; }
     if (PASS == 0) {
         const u32 rel = j0 + idx;
-        const u32 h = df_hash_at(in, c * kChunk - kWin + rel, ntri);
+        const u32 h = df_hash_at(in, c * kChunk - HIST + rel, ntri);
         dg = h & 0xFFu;
         val = rel | ((h >> 8) << 24);
     } else {
-        const u32 e = src[(size_t)c * kChunkStride + idx];
+        const u32 e = src[(size_t)c * (kChunk + HIST) + idx];
         dg = e >> 24;
-        val = c * kChunk - kWin + (e & 0xFFFFFFu); // the position itself goes out
+        val = c * kChunk - HIST + (e & 0xFFFFFFu); // the position itself goes out
     }
     return true;
 }
 
-template <int PASS>
+template <int PASS, u32 HIST = kWin>
 __global__ __launch_bounds__(kSortThreads) void k_df_shist(const u8 *__restrict__ in, u64 ntri, const u32 *__restrict__ src,
                                                            u32 *__restrict__ hist)
 {
+    constexpr u32 hTiles = (kChunk + HIST) / kSortTile;
     __shared__ u32 s_hist[4][256];
-    const u32 c = blockIdx.x / kChunkTiles, tile = blockIdx.x % kChunkTiles;
+    const u32 c = blockIdx.x / hTiles, tile = blockIdx.x % hTiles;
     u32 j0;
-    const u32 count = df_chunk_count(c, ntri, j0);
+    const u32 count = df_chunk_count<HIST>(c, ntri, j0);
     const u32 start = tile * kSortTile;
     for (u32 i = threadIdx.x; i < 4u * 256u; i += kSortThreads) (&s_hist[0][0])[i] = 0;
     __syncthreads();
@@ -109,7 +112,7 @@ __global__ __launch_bounds__(kSortThreads) void k_df_shist(const u8 *__restrict_
 #pragma unroll 4
         for (u32 r = 0; r < 16; ++r) {
             u32 pos, dg;
-            if (df_pass_elem<PASS>(in, ntri, src, c, start + r * kSortThreads + threadIdx.x, count, j0, pos, dg)) atomicAdd(&mine[dg], 1u);
+            if (df_pass_elem<PASS, HIST>(in, ntri, src, c, start + r * kSortThreads + threadIdx.x, count, j0, pos, dg)) atomicAdd(&mine[dg], 1u);
         }
     }
     __syncthreads();
@@ -118,13 +121,15 @@ __global__ __launch_bounds__(kSortThreads) void k_df_shist(const u8 *__restrict_
             s_hist[0][threadIdx.x] + s_hist[1][threadIdx.x] + s_hist[2][threadIdx.x] + s_hist[3][threadIdx.x];
 }
 
+template <u32 HIST = kWin>
 __global__ __launch_bounds__(256) void k_df_sscan(u32 *__restrict__ hist, u32 *__restrict__ tbase)
 {
+    constexpr u32 hTiles = (kChunk + HIST) / kSortTile;
     __shared__ u32 s_w[4];
     const u32 c = blockIdx.x, d = threadIdx.x;
-    u32 *h = hist + (size_t)c * kChunkTiles * 256u;
+    u32 *h = hist + (size_t)c * hTiles * 256u;
     u32 run = 0;
-    for (u32 t = 0; t < kChunkTiles; ++t) {
+    for (u32 t = 0; t < hTiles; ++t) {
         const u32 v = h[t * 256u + d];
         h[t * 256u + d] = run;
         run += v;
@@ -137,13 +142,14 @@ __global__ __launch_bounds__(256) void k_df_sscan(u32 *__restrict__ hist, u32 *_
     tbase[(size_t)c * 256u + d] = carry + inc - run;
 }
 
-template <int PASS>
+template <int PASS, u32 HIST = kWin>
 __global__ __launch_bounds__(kSortThreads) void k_df_sscatter(const u8 *__restrict__ in, u64 ntri, const u32 *__restrict__ src,
                                                               const u32 *__restrict__ hist, const u32 *__restrict__ tbase,
                                                               u32 *__restrict__ dst, const u32 *__restrict__ tbase0,
                                                               u16 *__restrict__ hash_out)
 {
     constexpr u32 NW = kSortThreads / 64;
+    constexpr u32 hTiles = (kChunk + HIST) / kSortTile, hStride = kChunk + HIST;
     __shared__ u32 s_buf[kSortTile];
     __shared__ u8 s_dg[kSortTile];
     __shared__ u8 s_lo[PASS ? kSortTile : 4];
@@ -152,9 +158,9 @@ __global__ __launch_bounds__(kSortThreads) void k_df_sscatter(const u8 *__restri
     __shared__ u16 s_tpre[256];
     __shared__ u16 s_cnt[NW][256];
     __shared__ u32 s_wsum[4];
-    const u32 c = blockIdx.x / kChunkTiles, tile = blockIdx.x % kChunkTiles;
+    const u32 c = blockIdx.x / hTiles, tile = blockIdx.x % hTiles;
     u32 j0;
-    const u32 count = df_chunk_count(c, ntri, j0);
+    const u32 count = df_chunk_count<HIST>(c, ntri, j0);
     const u32 start = tile * kSortTile;
     if (start >= count) return;
     for (u32 i = threadIdx.x; i < NW * 256u / 2u; i += kSortThreads) reinterpret_cast<u32 *>(&s_cnt[0][0])[i] = 0;
@@ -168,7 +174,7 @@ __global__ __launch_bounds__(kSortThreads) void k_df_sscatter(const u8 *__restri
     u32 okmask = 0;
 #pragma unroll
     for (u32 r = 0; r < 16; ++r)
-        okmask |= (df_pass_elem<PASS>(in, ntri, src, c, start + w * 1024u + r * 64u + l, count, j0, posv[r], dgv[r]) ? 1u : 0u) << r;
+        okmask |= (df_pass_elem<PASS, HIST>(in, ntri, src, c, start + w * 1024u + r * 64u + l, count, j0, posv[r], dgv[r]) ? 1u : 0u) << r;
 #pragma unroll
     for (u32 r = 0; r < 16; ++r) {
         const bool ok = (okmask >> r) & 1u;
@@ -220,7 +226,7 @@ __global__ __launch_bounds__(kSortThreads) void k_df_sscatter(const u8 *__restri
         }
     }
     __syncthreads();
-    u32 *out = dst + (size_t)c * kChunkStride;
+    u32 *out = dst + (size_t)c * hStride;
 #pragma unroll
     for (u32 k = 0; k < 16; ++k) {
         const u32 i = k * kSortThreads + threadIdx.x;
@@ -228,7 +234,7 @@ __global__ __launch_bounds__(kSortThreads) void k_df_sscatter(const u8 *__restri
             const u32 dg = s_dg[i];
             const u32 o = s_base[dg] + (i - (u32)s_tpre[dg]);
             out[o] = s_buf[i];
-            if (PASS && hash_out) hash_out[(size_t)c * kChunkStride + o] = (u16)((dg << 8) | s_lo[i]);
+            if (PASS && hash_out) hash_out[(size_t)c * hStride + o] = (u16)((dg << 8) | s_lo[i]);
         }
     }
 }
@@ -521,12 +527,16 @@ __device__ __forceinline__ u32 df_diff16(df_u32x4 x, df_u32x4 y)
 // image[lo - W, lo) -- df_encode_core's history, once per slot.  The chain then ends at the first candidate in front of
 // lo - W: own candidates first, the window's behind them, window and 255 candidates counted together; the entries of the
 // window itself (and of the zeros in front of it) are candidates only and get "no match" without a step.
-template <bool BATCH, bool DICT = false>
+// WIN, MAXM: the window and the longest match (Deflate: 32 KiB, 258; LZHUF: 4 .. 64 KiB, 256); HIST: the history of the
+// chunk sort whose order S is (HIST >= WIN)
+template <bool BATCH, bool DICT = false, u32 WIN = kWin, u32 MAXM = kMaxMatch, u32 HIST = kWin>
 __global__ __launch_bounds__(kM2Threads) void k_df_match2(const u8 *__restrict__ in, u64 n, u64 ntri, const u32 *__restrict__ S,
                                                           u32 *__restrict__ M, const u32 *__restrict__ tile_slot,
                                                           const DfSlot *__restrict__ slots, u32 W)
 {
     static_assert(BATCH || !DICT, "the window in front of a slot is a form of the batch kernel");
+    static_assert(HIST >= WIN && (kChunk + HIST) % kM2Threads == 0 && MAXM <= 16 + 61 * 4, "history, tiling, the measuring's reach");
+    constexpr u32 hStride = kChunk + HIST, hSpan = hStride / kM2Threads;
     typedef df_u32x4 u32x4;
     __shared__ u32x4 s_snip[kM2Hist + kM2Threads];
     __shared__ u32 s_pos[kM2Hist + kM2Threads];
@@ -536,15 +546,15 @@ __global__ __launch_bounds__(kM2Threads) void k_df_match2(const u8 *__restrict__
     u32 slice = blockIdx.x;
     {
         const u32 x = blockIdx.x & 7u, r = blockIdx.x >> 3;
-        const u32 cand = ((r / kM2Span) * 8 + x) * kM2Span + (r % kM2Span);
-        const u32 full = gridDim.x / (8 * kM2Span) * (8 * kM2Span);
+        const u32 cand = ((r / hSpan) * 8 + x) * hSpan + (r % hSpan);
+        const u32 full = gridDim.x / (8 * hSpan) * (8 * hSpan);
         if (blockIdx.x < full) slice = cand;
     }
-    const u32 c = slice / kM2Span, i0 = (slice % kM2Span) * kM2Threads;
+    const u32 c = slice / hSpan, i0 = (slice % hSpan) * kM2Threads;
     u32 j0;
-    const u32 count = df_chunk_count(c, ntri, j0);
+    const u32 count = df_chunk_count<HIST>(c, ntri, j0);
     if (i0 >= count) return;
-    const u32 *Sc = S + (size_t)c * kChunkStride;
+    const u32 *Sc = S + (size_t)c * hStride;
     const u32 tid = threadIdx.x;
     // the workgroup's entries and the 256 in front of them: position, hash, the first 16 text bytes (positions fit
     // 32 bits: a part of a long stream is at most 1 GiB + history)
@@ -586,11 +596,11 @@ __global__ __launch_bounds__(kM2Threads) void k_df_match2(const u8 *__restrict__
     }
     // chain length: the entries in front with the same hash and within the window form one run (monotone in j)
     u32 e = 0;
-    if (live && s_key[li - 1] == h && p - s_pos[li - 1] <= kWin && (!BATCH || s_pos[li - 1] >= slo)) {
+    if (live && s_key[li - 1] == h && p - s_pos[li - 1] <= WIN && (!BATCH || s_pos[li - 1] >= slo)) {
         u32 lo = li - kChain, hi = li - 1;
         while (lo < hi) {
             const u32 mid = (lo + hi) >> 1;
-            if (s_key[mid] == h && s_pos[mid] + kWin >= p && (!BATCH || s_pos[mid] >= slo)) hi = mid; else lo = mid + 1;
+            if (s_key[mid] == h && s_pos[mid] + WIN >= p && (!BATCH || s_pos[mid] >= slo)) hi = mid; else lo = mid + 1;
         }
         e = li - lo;
     }
@@ -598,7 +608,7 @@ __global__ __launch_bounds__(kM2Threads) void k_df_match2(const u8 *__restrict__
     // another trigram: fewer than three bytes agree, which never beats "no match"); only a chain cut by the window, by
     // the 255 candidates or by the start of the chunk's entries has to be masked.  em: the step a lane is masked from.
     const u32 em = (live && !(s_key[li - e - 1] != 0xFFFFFFFFu && s_key[li - e - 1] != h)) ? e : 0xFFFFFFFFu;
-    const u32 limit = (BATCH && !live) ? 0u : ((tend - p) < kMaxMatch ? tend - p : kMaxMatch); // search_dic :228
+    const u32 limit = (BATCH && !live) ? 0u : ((tend - p) < MAXM ? tend - p : MAXM); // search_dic :228
     // A step gives r = first differing bit of the 16 bytes, at most `cap` (the limit where it lies inside them, else
     // 128: "all 16 agree, the rest is to be measured").  What a lane keeps is the greatest key
     //     (r | 7) << 24 | (255 - k) << 16
@@ -748,15 +758,16 @@ __global__ __launch_bounds__(kM2Threads) void k_df_match2(const u8 *__restrict__
 
 // ---------------------------------------------------------------------------------- parse
 // lzss/encoder.rs:132-184: step[p] = advance | lazy_index << 9 if a code sequence started at p
+template <u32 MAXM = kMaxMatch>
 __device__ __forceinline__ u32 df_step_word(u32 m0, u32 m1, u32 m2)
 {
     u32 out_len = m0 & 511u, out_pos = m0 >> 9, li = 0;
     if (out_len < kMinMatch) return 1u;
-    if (out_len < kMaxMatch) {
+    if (out_len < MAXM) {
         const u32 il = m1 & 511u, ip = m1 >> 9;
         if (il > kMinMatch && (il << 3) + ip > (out_len << 3) + out_pos) { out_len = il; out_pos = ip; li = 1; }
     }
-    if (out_len < kMaxMatch) {
+    if (out_len < MAXM) {
         const u32 il = m2 & 511u, ip = m2 >> 9;
         if (il > kMinMatch && (il << 3) + ip > (out_len << 3) + out_pos) { out_len = il; out_pos = ip; li = 2; }
     }
@@ -764,6 +775,7 @@ __device__ __forceinline__ u32 df_step_word(u32 m0, u32 m1, u32 m2)
 }
 
 // four positions per thread: two aligned 16-byte loads of match words, one 8-byte store of step words
+template <u32 MAXM = kMaxMatch>
 __global__ __launch_bounds__(256) void k_df_adv(const u32 *__restrict__ M, u64 n, u16 *__restrict__ step)
 {
     typedef u32 u32x4 __attribute__((ext_vector_type(4)));
@@ -779,7 +791,7 @@ __global__ __launch_bounds__(256) void k_df_adv(const u32 *__restrict__ M, u64 n
         for (u32 j = 0; j < 8 && p0 + j < n; ++j) m[j] = M[p0 + j]; // (a match word behind the end is "no match")
     u32 s[4];
 #pragma unroll
-    for (u32 j = 0; j < 4; ++j) s[j] = df_step_word(m[j], m[j + 1], m[j + 2]);
+    for (u32 j = 0; j < 4; ++j) s[j] = df_step_word<MAXM>(m[j], m[j + 1], m[j + 2]);
     if (al && p0 + 4 <= n) {
         u32x2 o;
         o.x = s[0] | (s[1] << 16); o.y = s[2] | (s[3] << 16);
@@ -1924,12 +1936,12 @@ int df_launch_chains(hipStream_t st, const u8 *in, u64 n, u32 *v0, u32 *s, u16 *
     const u32 nchunks = df_chunks(n);
     const dim3 tiles(nchunks * kChunkTiles);
     hipLaunchKernelGGL((k_df_shist<0>), tiles, dim3(kSortThreads), 0, st, in, ntri, (const u32 *)nullptr, hist);
-    hipLaunchKernelGGL(k_df_sscan, dim3(nchunks), dim3(256), 0, st, hist, tbase);
+    hipLaunchKernelGGL((k_df_sscan<>), dim3(nchunks), dim3(256), 0, st, hist, tbase);
     u32 *tbase1 = tbase + (size_t)nchunks * 256;
     hipLaunchKernelGGL((k_df_sscatter<0>), tiles, dim3(kSortThreads), 0, st, in, ntri, (const u32 *)nullptr, hist, tbase, v0,
                        (const u32 *)nullptr, (u16 *)nullptr);
     hipLaunchKernelGGL((k_df_shist<1>), tiles, dim3(kSortThreads), 0, st, in, ntri, v0, hist);
-    hipLaunchKernelGGL(k_df_sscan, dim3(nchunks), dim3(256), 0, st, hist, tbase1);
+    hipLaunchKernelGGL((k_df_sscan<>), dim3(nchunks), dim3(256), 0, st, hist, tbase1);
     // (the hashes of the sorted positions are only kept for k_df_prev: k_df_match2 has the trigrams in hand)
     hipLaunchKernelGGL((k_df_sscatter<1>), tiles, dim3(kSortThreads), 0, st, in, ntri, v0, hist, tbase1, s, tbase, pe ? hs : (u16 *)nullptr);
     if (pe) hipLaunchKernelGGL(k_df_prev, dim3(nchunks * kPrevSpan), dim3(256), 0, st, ntri, s, hs, pe);
@@ -1974,7 +1986,7 @@ int df_launch_parse(hipStream_t st, const u32 *M, u64 n, u16 *step, u16 *const *
 {
     if (!n) return 0;
     DFCHK(hipMemsetAsync(bm, 0, ((n + 63) / 64 + 2) * sizeof(u64), st));
-    hipLaunchKernelGGL(k_df_adv, dim3((u32)((n + 1023) / 1024)), dim3(256), 0, st, M, n, step);
+    hipLaunchKernelGGL((k_df_adv<>), dim3((u32)((n + 1023) / 1024)), dim3(256), 0, st, M, n, step);
     if (canon) hipLaunchKernelGGL(k_df_tile_orbit, dim3(counts[0]), dim3(kOrbThreads), 0, st, step, n, tabs[0], canon);
     else hipLaunchKernelGGL(k_df_tile_tab, dim3(counts[0]), dim3(kTabThreads), 0, st, step, n, tabs[0]);
     for (u32 l = 1; l + 1 < nlevels; ++l)
@@ -2204,7 +2216,8 @@ __global__ __launch_bounds__(256) void k_df_gather_dict(const u8 *__restrict__ d
 }
 
 // entry offset of every tile of a slot: 0 for the first one, the exit of tile t for tile t + 1 (k_df_compose /
-// k_df_resolve of the one-stream path; a slot has at most 16 tiles)
+// k_df_resolve of the one-stream path).  A Deflate slot has at most 16 tiles; an LZHUF slot holds a whole input, up to
+// 262 144 tiles: a sub-batch of one slot of more than kLzhSerialTiles tiles has its tables composed instead (lzh_launch_front)
 // DICT: the slot's `wtiles` window tiles, in front of sl.lo, are entered at kPTile -- behind their end: k_df_mark2 then
 // finds no step in them and writes neither code words nor bits (nothing reads either in front of an input).
 template <bool DICT>
@@ -2373,7 +2386,7 @@ int df_launch_parse_batch(hipStream_t st, const u32 *M, u64 n, u32 ntiles, const
                           u16 *tab, u16 *ent, u32 *code, u64 *bm, u64 *canon)
 {
     DFCHK(hipMemsetAsync(bm, 0, ((n + 63) / 64 + 2) * sizeof(u64), st));
-    hipLaunchKernelGGL(k_df_adv, dim3((u32)((n + 1023) / 1024)), dim3(256), 0, st, M, n, step);
+    hipLaunchKernelGGL((k_df_adv<>), dim3((u32)((n + 1023) / 1024)), dim3(256), 0, st, M, n, step);
     hipLaunchKernelGGL(k_df_tile_orbit, dim3(ntiles), dim3(kOrbThreads), 0, st, step, n, tab, canon);
     if (wtiles) hipLaunchKernelGGL((k_df_slot_entries<true>), dim3((nslots + 63) / 64), dim3(64), 0, st, slots, nslots, tab, ent, wtiles);
     else hipLaunchKernelGGL((k_df_slot_entries<false>), dim3((nslots + 63) / 64), dim3(64), 0, st, slots, nslots, tab, ent, 0u);
@@ -2429,6 +2442,499 @@ int df_launch_bgzf_wrap(hipStream_t st, const u8 *image, const DfSlot *slots, u3
                         DfCrcShifts xk, u8 *out, u32 *stats)
 {
     hipLaunchKernelGGL((k_df_batch_wrap<false, true>), dim3(nslots), dim3(256), 0, st, image, slots, blocks, outs, 2, xk, out, stats, 0u);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------- LZHUF encode
+// (bz_gpu_lzh_encode_batch_device, lzhuf_engine.hip; DESIGN_lzhuf.md sections 7 to 9)  LzhufEncoder is LzssEncoder with
+// Deflate's comparison closure, a window of 1 << dictionary_bits and matches of at most 256 bytes (lzhuf/encoder.rs), so the
+// front end is the batch image's: gather, the chain sort with 64 KiB of history, k_df_match2<true, false, WIN, 256, 64 KiB>,
+// k_df_adv<256>, tile orbits, slot entries, marking.  What follows is LZHUF's own: a block is 65 535 CODES
+// (LzhufEncoderInner::next counts codes, whatever a step of the parse is), so block b of a slot starts at its code
+// 65 535 * b -- a prefix count over the code-start bitmap --, and write_block's three tables, MSB first.
+
+// one workgroup per slot: the positions of the codes 0, 65 535, 2 * 65 535, .. of its input
+__global__ __launch_bounds__(256) void k_lzh_cuts(const DfSlot *__restrict__ slots, const u32 *__restrict__ bbase, const u64 *__restrict__ bm,
+                                                  LzhBlk *__restrict__ blks)
+{
+    __shared__ u32 s_sum[256];
+    __shared__ u32 s_total;
+    const u32 tid = threadIdx.x, j = blockIdx.x;
+    const DfSlot sl = slots[j];
+    const u32 b0 = bbase[j], nbmax = bbase[j + 1] - b0;
+    if (!nbmax) return; // (an empty input: no block, no byte)
+    const u64 w0 = sl.lo >> 6; // (a slot starts at a multiple of kPTile)
+    const u32 nw = (sl.len + 63u) >> 6, per = (nw + 255u) / 256u;
+    const u32 i0 = tid * per < nw ? tid * per : nw, i1 = i0 + per < nw ? i0 + per : nw;
+    // (the gap behind the input is walked by the marking kernel too: its bits are not codes)
+    const u64 tailmask = (sl.len & 63u) ? (1ull << (sl.len & 63u)) - 1ull : ~0ull;
+    u32 sum = 0;
+    for (u32 i = i0; i < i1; ++i) sum += (u32)__popcll(bm[w0 + i] & (i + 1 == nw ? tailmask : ~0ull));
+    s_sum[tid] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        u32 run = 0;
+        for (u32 t = 0; t < 256; ++t) { const u32 v = s_sum[t]; s_sum[t] = run; run += v; }
+        s_total = run;
+    }
+    __syncthreads();
+    u32 run = s_sum[tid];
+    for (u32 i = i0; i < i1; ++i) {
+        const u64 v = bm[w0 + i] & (i + 1 == nw ? tailmask : ~0ull);
+        const u32 pc = (u32)__popcll(v);
+        u32 b = (run + kLzhBlockCodes - 1) / kLzhBlockCodes; // the first block that starts at or behind code `run`
+        while (b * kLzhBlockCodes < run + pc) {
+            u64 t = v;
+            for (u32 r = b * kLzhBlockCodes - run; r; --r) t &= t - 1;
+            if (b < nbmax) blks[b0 + b].start = (w0 + i) * 64u + (u32)__builtin_ctzll(t);
+            ++b;
+        }
+        run += pc;
+    }
+    __threadfence_block();
+    __syncthreads();
+    const u32 total = s_total, nblocks = (total + kLzhBlockCodes - 1) / kLzhBlockCodes;
+    for (u32 b = tid; b < nbmax; b += 256) {
+        LzhBlk *k = blks + b0 + b;
+        const bool used = b < nblocks;
+        if (!used) k->start = 0;
+        k->end = !used ? 0 : (b + 1 < nblocks && b + 1 < nbmax ? blks[b0 + b + 1].start : (u64)sl.lo + sl.len);
+        k->bits = 0;
+        k->bit_off = 0;
+        k->slot = j;
+        k->ncodes = !used ? 0u : (total - b * kLzhBlockCodes < kLzhBlockCodes ? total - b * kLzhBlockCodes : kLzhBlockCodes);
+        k->hdr_bits = 0; k->flags = 0; k->nlit = 0; k->nmatch = 0; k->lm = 0; k->pad = 0;
+    }
+}
+
+struct MsbSink { // single lane, MSB first into 32-bit words: bit 32 k of the string is bit 31 of word k
+    u32 *w;
+    u64 acc;
+    u32 nacc, widx;
+    __device__ __forceinline__ void put(u32 v, u32 nbits) // nbits <= 16
+    {
+        if (!nbits) return;
+        acc = (acc << nbits) | (u64)(v & ((1u << nbits) - 1u));
+        nacc += nbits;
+        if (nacc >= 32) { w[widx++] = (u32)(acc >> (nacc - 32)); nacc -= 32; }
+    }
+    __device__ __forceinline__ void put_len(u32 ln) // enc_len (lzhuf/encoder.rs:285-296)
+    {
+        if (ln >= 7) {
+            put(7, 3);
+            for (u32 i = 7; i < ln; ++i) put(1, 1);
+            put(0, 1);
+        } else put(ln, 3);
+    }
+    __device__ __forceinline__ u32 bits() const { return widx * 32 + nacc; }
+    __device__ __forceinline__ void finish() { if (nacc) w[widx] = (u32)(acc << (32 - nacc)); }
+};
+
+// canonical codes as numbers (huffman/mod.rs:16-63 without is_reverse): shorter lengths first, equal lengths by ascending
+// symbol.  nx: 17 words.  One lane.
+__device__ __forceinline__ void lzh_make_codes(const u8 *len, u32 n, u16 *code, u32 *nx)
+{
+    for (u32 l = 0; l <= 16; ++l) nx[l] = 0;
+    for (u32 s = 0; s < n; ++s) nx[len[s]] += 1;
+    u32 c = 0, prev = 0;
+    for (u32 l = 1; l <= 16; ++l) {
+        c = (c + prev) << 1;
+        prev = nx[l];
+        nx[l] = c;
+    }
+    for (u32 s = 0; s < n; ++s) {
+        const u32 l = len[s];
+        code[s] = 0;
+        if (l) { code[s] = (u16)nx[l]; nx[l] += 1; }
+    }
+}
+
+// what a wave needs in LDS to make one block's tables
+struct LzhTabLds {
+    u32 cf[512], pf[32], tf[32]; // counts: c (510), p (17), t (19)
+    u32 buf[1024], w[512];       // df_make_table_wave: the heap's image (2 * 510 words), the non-zero counts
+    u8 tmp[512];
+    u8 clen[512], plen[32], tlen[32];
+    u8 ls[640];                  // write_symb_tab's list: the t-symbol of every entry (at most 510 + 510 / 20 + 1) ...
+    u16 le[640];                 // ... and the field behind it (symbols 1 and 2)
+    u16 tcode[32];
+    u32 nx[20];
+    u32 lm, nlist;
+};
+
+// write_block's tables (lzhuf/encoder.rs:298-520) for the counts in L.cf / L.pf, by one wave (all 64 lanes call): make_table
+// three times, write_symb_tab's run coding, the t-, c- and p-table MSB first into hdr behind the 16-bit code count.
+// Returns the header's bits; flags as LzhBlk::flags.
+__device__ __forceinline__ u32 lzh_tables(LzhTabLds &L, u32 ncodes, u32 pbits, u32 *hdr, u32 *lm_scr, u32 lane, u32 &flags)
+{
+    if (lane == 0) L.lm = 0;
+    if (lane < 32) { L.tf[lane] = 0; L.tlen[lane] = 0; }
+    __builtin_amdgcn_wave_barrier();
+    // (only the c-table can pass 16 bits -- 18 symbols with Fibonacci weights, 6 764 codes; 17 p-symbols and 19 t-symbols fed
+    // by at most 510 + 26 entries cannot -- but every table gets the check)
+    const u32 clast = df_make_table_wave<16>(L.cf, kLzhNC, 16, L.clen, L.buf, L.w, L.tmp, lm_scr, &L.lm, lane);
+    const u32 plast = df_make_table_wave<1>(L.pf, kLzhNP, 16, L.plen, L.buf, L.w, L.tmp, lm_scr, &L.lm, lane);
+    u32 cused = 0, pused = 0;
+    for (u32 i0 = 0; i0 < kLzhNC; i0 += 64) cused += (u32)__popcll(__ballot(i0 + lane < kLzhNC && L.clen[i0 + lane] != 0));
+    pused = (u32)__popcll(__ballot(lane < kLzhNP && L.plen[lane] != 0));
+    flags = (cused <= 1 ? 1u : 0u) | (pused <= 1 ? 2u : 0u);
+    if (cused > 1 && lane == 0) { // the run coding of the c-lengths (write_symb_tab :318-372)
+        u32 k = 0, i = 0;
+        for (u32 ind = 0; ind < clast; ++ind) {
+            const u32 ln = L.clen[ind];
+            if (!ln) continue;
+            const u32 gap = ind - i;
+            i = ind + 1;
+            if (gap > 19) { L.ls[k] = 2; L.le[k++] = (u16)(gap - 20); L.tf[2] += 1; }
+            else if (gap == 19) { L.ls[k] = 1; L.le[k++] = 15; L.ls[k] = 0; L.le[k++] = 0; L.tf[1] += 1; L.tf[0] += 1; }
+            else if (gap > 2) { L.ls[k] = 1; L.le[k++] = (u16)(gap - 3); L.tf[1] += 1; }
+            else if (gap > 0) { for (u32 t = 0; t < gap; ++t) { L.ls[k] = 0; L.le[k++] = 0; } L.tf[0] += gap; }
+            L.ls[k] = (u8)(ln + 2); L.le[k++] = 0;
+            L.tf[ln + 2] += 1;
+        }
+        L.nlist = k;
+    }
+    __builtin_amdgcn_wave_barrier();
+    u32 tlast = 0;
+    if (cused > 1) tlast = df_make_table_wave<1>(L.tf, kLzhNT, 16, L.tlen, L.buf, L.w, L.tmp, lm_scr, &L.lm, lane);
+    const u32 tused = (u32)__popcll(__ballot(lane < kLzhNT && L.tlen[lane] != 0));
+    if (cused > 1 && tused <= 1) flags |= 4u;
+    u32 hbits = 0;
+    if (lane == 0) {
+        MsbSink sk{hdr, 0, 0, 0};
+        sk.put(ncodes, 16);
+        if (cused <= 1) { // a lone symbol (a block has at least one code): both tables in their two-field form
+            u32 sym = 0;
+            for (u32 s = 0; s < clast; ++s) if (L.clen[s]) sym = s;
+            sk.put(0, 5); sk.put(0, 5); sk.put(0, 9); sk.put(sym, 9);
+        } else {
+            if (tused <= 1) { // one t-symbol: zero bits per use
+                sk.put(0, 5);
+                sk.put(tlast - 1, 5);
+            } else {
+                lzh_make_codes(L.tlen, kLzhNT, L.tcode, L.nx);
+                sk.put(tlast, 5);
+                u32 i = 0;
+                for (u32 ind = 0; ind < tlast; ++ind) {
+                    const u32 ln = L.tlen[ind];
+                    if (!ln) continue;
+                    while (ind >= i) {
+                        if (i == 3) { // the skip field (:398-410)
+                            const u32 skip = ind > 6 ? 3u : ind - 3u;
+                            sk.put(skip, 2);
+                            i += skip;
+                        }
+                        if (ind != i) sk.put(0, 3); else sk.put_len(ln);
+                        i += 1;
+                    }
+                }
+            }
+            sk.put(clast, 9);
+            const u32 nl = L.nlist;
+            for (u32 k = 0; k < nl; ++k) {
+                const u32 ts = L.ls[k];
+                if (tused > 1) sk.put(L.tcode[ts], L.tlen[ts]);
+                if (ts == 1) sk.put(L.le[k], 4);
+                else if (ts == 2) sk.put(L.le[k], 9);
+            }
+        }
+        if (pused <= 1) { // write_offset_tab (:435-472)
+            u32 sym = 0;
+            for (u32 s = 0; s < plast; ++s) if (L.plen[s]) sym = s;
+            sk.put(0, pbits); sk.put(sym, pbits);
+        } else {
+            sk.put(plast, pbits);
+            u32 i = 0;
+            for (u32 ind = 0; ind < plast; ++ind) {
+                const u32 ln = L.plen[ind];
+                if (!ln) continue;
+                while (ind >= i) {
+                    if (ind != i) sk.put(0, 3); else sk.put_len(ln);
+                    i += 1;
+                }
+            }
+        }
+        hbits = sk.bits();
+        sk.finish();
+    }
+    __builtin_amdgcn_wave_barrier();
+    return (u32)__builtin_amdgcn_readfirstlane((int)hbits);
+}
+
+// the p-symbol of pos = distance - 1 (LzhufLzssCode::from :94-108): its bit length; v - 1 bits of pos follow it for v > 1
+__device__ __forceinline__ u32 lzh_psym(u32 pos) { return pos ? 32u - (u32)__clz(pos) : 0u; }
+
+// one workgroup per block: the counts of its codes, write_block's tables (wave 0), its header and its bit length
+__global__ __launch_bounds__(256) void k_lzh_block(const u8 *__restrict__ image, const u32 *__restrict__ code, LzhBlk *__restrict__ blks,
+                                                   u32 pbits, u8 *__restrict__ lens, u32 *__restrict__ hdr, u32 *__restrict__ lm_scratch)
+{
+    __shared__ LzhTabLds L;
+    const u32 tid = threadIdx.x, k = blockIdx.x;
+    const u32 ncodes = blks[k].ncodes;
+    if (!ncodes) return;
+    const u64 start = blks[k].start, end = blks[k].end;
+    for (u32 i = tid; i < 512; i += 256) L.cf[i] = 0;
+    if (tid < 32) L.pf[tid] = 0;
+    __syncthreads();
+    for (u64 q = start + tid; q < end; q += 256) {
+        const u32 cw = code[q];
+        if (!(cw & F_CODE)) continue;
+        if (cw & F_REF) {
+            atomicAdd(&L.cf[(cw & 511u) + 256u - kMinMatch], 1u);
+            atomicAdd(&L.pf[lzh_psym((cw >> 9) & 0xFFFFu)], 1u);
+        } else atomicAdd(&L.cf[image[q]], 1u);
+    }
+    __syncthreads();
+    if (tid >= 64) return;
+    u32 flags = 0;
+    const u32 hbits = lzh_tables(L, ncodes, pbits, hdr + (size_t)k * kLzhHdrWords, lm_scratch + (size_t)k * kLzhLmWords, tid, flags);
+    u32 bits = 0, nlit = 0, nmatch = 0;
+    for (u32 s = tid; s < kLzhNC; s += 64) {
+        const u32 f = L.cf[s];
+        bits += (flags & 1u) ? 0u : f * L.clen[s];
+        if (s < 256) nlit += f; else nmatch += f;
+    }
+    if (tid < kLzhNP) bits += L.pf[tid] * (((flags & 2u) ? 0u : (u32)L.plen[tid]) + (tid > 1 ? tid - 1 : 0u));
+    bits = (u32)__builtin_amdgcn_readlane((int)wave_incl_sum(bits), 63);
+    nlit = (u32)__builtin_amdgcn_readlane((int)wave_incl_sum(nlit), 63);
+    nmatch = (u32)__builtin_amdgcn_readlane((int)wave_incl_sum(nmatch), 63);
+    u8 *ln = lens + (size_t)k * kLzhLensBytes;
+    for (u32 s = tid; s < 512; s += 64) ln[s] = s < kLzhNC ? L.clen[s] : (u8)0;
+    if (tid < 32) { ln[512 + tid] = tid < kLzhNP ? L.plen[tid] : (u8)0; ln[544 + tid] = tid < kLzhNT ? L.tlen[tid] : (u8)0; }
+    if (tid == 0) {
+        blks[k].hdr_bits = hbits;
+        blks[k].bits = (u64)hbits + bits;
+        blks[k].flags = flags;
+        blks[k].nlit = nlit;
+        blks[k].nmatch = nmatch;
+        blks[k].lm = L.lm;
+    }
+}
+
+// bz_gpu_lzh_debug_tables: lzh_tables on counts the host gives
+__global__ __launch_bounds__(64) void k_lzh_tables_debug(const u32 *__restrict__ cfreq, const u32 *__restrict__ pfreq, u32 pbits,
+                                                         u8 *__restrict__ lens, u32 *__restrict__ hdr, u32 *__restrict__ lm_scratch,
+                                                         u32 *__restrict__ res)
+{
+    __shared__ LzhTabLds L;
+    const u32 tid = threadIdx.x;
+    u32 n = 0;
+    for (u32 i = tid; i < 512; i += 64) { L.cf[i] = i < kLzhNC ? cfreq[i] : 0u; n += L.cf[i]; }
+    if (tid < 32) L.pf[tid] = tid < kLzhNP ? pfreq[tid] : 0u;
+    __builtin_amdgcn_wave_barrier();
+    n = (u32)__builtin_amdgcn_readlane((int)wave_incl_sum(n), 63);
+    u32 flags = 0;
+    const u32 hbits = lzh_tables(L, n < kLzhBlockCodes ? n : kLzhBlockCodes, pbits, hdr, lm_scratch, tid, flags);
+    for (u32 s = tid; s < 512; s += 64) lens[s] = s < kLzhNC ? L.clen[s] : (u8)0;
+    if (tid < 32) { lens[512 + tid] = tid < kLzhNP ? L.plen[tid] : (u8)0; lens[544 + tid] = tid < kLzhNT ? L.tlen[tid] : (u8)0; }
+    if (tid == 0) { res[0] = hbits; res[1] = flags; res[2] = L.lm; }
+}
+
+// Streams in slot order, each at a multiple of 4, its blocks bit against bit: one scan over the slots (the blocks of a
+// slot are walked by its thread: there are len / 65 535 of them)
+__global__ __launch_bounds__(256) void k_lzh_offsets(LzhBlk *__restrict__ blks, const u32 *__restrict__ bbase, u32 nslots,
+                                                     LzhOut *__restrict__ outs, u64 *__restrict__ total)
+{
+    __shared__ u64 s_sum[256];
+    const u32 tid = threadIdx.x;
+    const u32 per = (nslots + 255u) / 256u, j0 = tid * per < nslots ? tid * per : nslots, j1 = j0 + per < nslots ? j0 + per : nslots;
+    u64 sum = 0;
+    for (u32 j = j0; j < j1; ++j) {
+        u64 bits = 0;
+        for (u32 b = bbase[j]; b < bbase[j + 1]; ++b) bits += blks[b].bits;
+        sum += (((bits + 7u) >> 3) + 3u) & ~(u64)3;
+    }
+    s_sum[tid] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        u64 run = 0;
+        for (u32 t = 0; t < 256; ++t) { const u64 v = s_sum[t]; s_sum[t] = run; run += v; }
+        *total = run;
+    }
+    __syncthreads();
+    u64 off = s_sum[tid];
+    for (u32 j = j0; j < j1; ++j) {
+        u64 bits = 0;
+        for (u32 b = bbase[j]; b < bbase[j + 1]; ++b) {
+            blks[b].bit_off = off * 8u + bits;
+            bits += blks[b].bits;
+        }
+        const u64 len = (bits + 7u) >> 3;
+        outs[j].off = off;
+        outs[j].len = len;
+        off += (len + 3u) & ~(u64)3;
+    }
+}
+
+// nbits <= 32 bits of v, MSB first, at bit `bit` of a zeroed output: stream bit i is bit 7 - i % 8 of byte i / 8, so a
+// 32-bit word of the string goes out byte-swapped.  A word behind the string's last bit is never touched.
+__device__ __forceinline__ void lzh_or_bits(u32 *out, u64 bit, u32 v, u32 nbits)
+{
+    if (!nbits) return;
+    const u64 x = (u64)v << (64u - nbits - (u32)(bit & 31u));
+    const u32 hi = (u32)(x >> 32), lo = (u32)x;
+    if (hi) atomicOr(out + (bit >> 5), __builtin_bswap32(hi));
+    if (lo) atomicOr(out + (bit >> 5) + 1, __builtin_bswap32(lo));
+}
+
+// one workgroup per block: its header's words, then its codes 256 positions at a time -- a code's place is the block's bit
+// offset plus the bits of the codes in front of it (a scan per 256 positions, the running sum carried).  A code is at most
+// 16 + 16 + 15 bits: the c-code is one piece, the p-code with the bits behind it the other.
+__global__ __launch_bounds__(256) void k_lzh_emit(const u8 *__restrict__ image, const u32 *__restrict__ code, const LzhBlk *__restrict__ blks,
+                                                  const u8 *__restrict__ lens, const u32 *__restrict__ hdr, u32 *__restrict__ out)
+{
+    __shared__ u8 s_clen[512], s_plen[32];
+    __shared__ u16 s_ccode[512], s_pcode[32];
+    __shared__ u32 s_nx[2][20];
+    __shared__ u32 s_w[2][4];
+    const u32 tid = threadIdx.x, k = blockIdx.x;
+    const LzhBlk bk = blks[k];
+    if (!bk.ncodes) return;
+    const u8 *ln = lens + (size_t)k * kLzhLensBytes;
+    for (u32 s = tid; s < 512; s += 256) s_clen[s] = (bk.flags & 1u) ? (u8)0 : ln[s];
+    if (tid < 32) s_plen[tid] = (bk.flags & 2u) ? (u8)0 : ln[512 + tid];
+    __syncthreads();
+    if (tid == 0) lzh_make_codes(s_clen, kLzhNC, s_ccode, s_nx[0]);
+    if (tid == 64) lzh_make_codes(s_plen, kLzhNP, s_pcode, s_nx[1]); // (a lane of another wave, beside the first)
+    __syncthreads();
+    const u32 *hw = hdr + (size_t)k * kLzhHdrWords;
+    for (u32 wd = tid; wd * 32u < bk.hdr_bits; wd += 256) {
+        const u32 n = bk.hdr_bits - wd * 32u < 32u ? bk.hdr_bits - wd * 32u : 32u;
+        lzh_or_bits(out, bk.bit_off + wd * 32u, hw[wd] >> (32u - n), n);
+    }
+    u64 base = bk.bit_off + bk.hdr_bits;
+    u32 par = 0;
+    for (u64 q0 = bk.start; q0 < bk.end; q0 += 256, par ^= 1u) {
+        const u64 q = q0 + tid;
+        u32 v1 = 0, n1 = 0, v2 = 0, n2 = 0;
+        if (q < bk.end) {
+            const u32 cw = code[q];
+            if (cw & F_CODE) {
+                if (cw & F_REF) {
+                    const u32 cs = (cw & 511u) + 256u - kMinMatch, pos = (cw >> 9) & 0xFFFFu, ps = lzh_psym(pos);
+                    v1 = s_ccode[cs]; n1 = s_clen[cs];
+                    const u32 xb = ps > 1 ? ps - 1 : 0u;
+                    v2 = ((u32)s_pcode[ps] << xb) | (pos & ((1u << xb) - 1u));
+                    n2 = s_plen[ps] + xb;
+                } else { const u32 b = image[q]; v1 = s_ccode[b]; n1 = s_clen[b]; }
+            }
+        }
+        const u32 tot = n1 + n2, inc = wave_incl_sum(tot);
+        if ((tid & 63u) == 63u) s_w[par][tid >> 6] = inc;
+        __syncthreads();
+        u32 carry = 0, all = 0;
+        for (u32 w = 0; w < 4; ++w) { const u32 x = s_w[par][w]; if (w < (tid >> 6)) carry += x; all += x; }
+        const u64 at = base + carry + inc - tot;
+        lzh_or_bits(out, at, v1, n1);
+        lzh_or_bits(out, at + n1, v2, n2);
+        base += all;
+    }
+}
+
+template <u32 WIN>
+static void lzh_match_launch(hipStream_t st, dim3 grid, const u8 *image, u64 n, u64 ntri, const u32 *s, u32 *M, const u32 *tile_slot,
+                             const DfSlot *slots)
+{
+    hipLaunchKernelGGL((k_df_match2<true, false, WIN, 256u, kLzhHist>), grid, dim3(kM2Threads), 0, st, image, n, ntri, s, M, tile_slot, slots, 0u);
+}
+
+// M takes the place of v0 and the code words that of s (as in df_batch_run)
+int lzh_launch_front(hipStream_t st, u32 dbits, const u8 *image, u64 n, u32 ntiles, const DfSlot *slots, u32 nslots, const u32 *tile_slot,
+                     u32 *v0, u32 *s, u32 *hist, u32 *tbase, u16 *step, u16 *tab, u16 *ent, u64 *bm, u64 *canon)
+{
+    if (!n) return 0;
+    const u64 ntri = n >= 3 ? n - 2 : 0;
+    const u32 nchunks = df_chunks(n);
+    u32 *M = v0, *code = s;
+    if (ntri) {
+        const dim3 tiles(nchunks * (kLzhStride / kSortTile));
+        u32 *tbase1 = tbase + (size_t)nchunks * 256;
+        hipLaunchKernelGGL((k_df_shist<0, kLzhHist>), tiles, dim3(kSortThreads), 0, st, image, ntri, (const u32 *)nullptr, hist);
+        hipLaunchKernelGGL((k_df_sscan<kLzhHist>), dim3(nchunks), dim3(256), 0, st, hist, tbase);
+        hipLaunchKernelGGL((k_df_sscatter<0, kLzhHist>), tiles, dim3(kSortThreads), 0, st, image, ntri, (const u32 *)nullptr, hist, tbase, v0,
+                           (const u32 *)nullptr, (u16 *)nullptr);
+        hipLaunchKernelGGL((k_df_shist<1, kLzhHist>), tiles, dim3(kSortThreads), 0, st, image, ntri, v0, hist);
+        hipLaunchKernelGGL((k_df_sscan<kLzhHist>), dim3(nchunks), dim3(256), 0, st, hist, tbase1);
+        hipLaunchKernelGGL((k_df_sscatter<1, kLzhHist>), tiles, dim3(kSortThreads), 0, st, image, ntri, v0, hist, tbase1, s, tbase, (u16 *)nullptr);
+    }
+    DFCHK(hipMemsetAsync(M + ntri, 0, (n - ntri + 8) * sizeof(u32), st)); // the last two positions have no trigram
+    if (ntri) {
+        const dim3 grid(nchunks * (kLzhStride / kM2Threads));
+        switch (dbits) {
+        case 12: lzh_match_launch<0x1000>(st, grid, image, n, ntri, s, M, tile_slot, slots); break;
+        case 13: lzh_match_launch<0x2000>(st, grid, image, n, ntri, s, M, tile_slot, slots); break;
+        case 15: lzh_match_launch<0x8000>(st, grid, image, n, ntri, s, M, tile_slot, slots); break;
+        case 16: lzh_match_launch<0x10000>(st, grid, image, n, ntri, s, M, tile_slot, slots); break;
+        default: return -1;
+        }
+    }
+    DFCHK(hipMemsetAsync(bm, 0, ((n + 63) / 64 + 2) * sizeof(u64), st));
+    hipLaunchKernelGGL((k_df_adv<256u>), dim3((u32)((n + 1023) / 1024)), dim3(256), 0, st, M, n, step);
+    hipLaunchKernelGGL(k_df_tile_orbit, dim3(ntiles), dim3(kOrbThreads), 0, st, step, n, tab, canon);
+    if (nslots == 1 && ntiles > kLzhSerialTiles) {
+        // one slot at position 0 is the one-stream layout: the exit tables are composed kFan at a time and resolved top
+        // down (df_launch_parse), log_64(ntiles) dependent launches instead of ntiles dependent look-ups on one lane
+        u32 counts[8], nlevels = 1;
+        u16 *tabs[8], *ents[8];
+        counts[0] = ntiles;
+        while (counts[nlevels - 1] > 1) { counts[nlevels] = (counts[nlevels - 1] + kFan - 1) / kFan; ++nlevels; }
+        u16 *t = tab, *e = ent;
+        for (u32 l = 0; l < nlevels; ++l) {
+            tabs[l] = t; t += (size_t)counts[l] * kEntries;
+            ents[l] = e; e += counts[l] + 8;
+        }
+        for (u32 l = 1; l + 1 < nlevels; ++l)
+            hipLaunchKernelGGL(k_df_compose, dim3(counts[l]), dim3(320), 0, st, tabs[l - 1], counts[l - 1], tabs[l]);
+        DFCHK(hipMemsetAsync(ents[nlevels - 1], 0, sizeof(u16), st)); // the single top group is entered at 0
+        for (u32 l = nlevels - 1; l >= 1; --l)
+            hipLaunchKernelGGL(k_df_resolve, dim3((counts[l] + 63) / 64), dim3(64), 0, st, tabs[l - 1], counts[l - 1], ents[l], counts[l],
+                               ents[l - 1]);
+    } else hipLaunchKernelGGL((k_df_slot_entries<false>), dim3((nslots + 63) / 64), dim3(64), 0, st, slots, nslots, tab, ent, 0u);
+    hipLaunchKernelGGL(k_df_mark2, dim3(ntiles), dim3(kMark2Threads), 0, st, step, M, ent, tab, canon, n, code, bm, 0u);
+    return 0;
+}
+
+// u16 entries of `tab` and of `ent` that lzh_launch_front needs for an image of ntiles tiles (all levels of a composed slot)
+size_t lzh_tab_entries(u32 ntiles)
+{
+    size_t s = 0;
+    for (u32 c = ntiles;; c = (c + kFan - 1) / kFan) { s += (size_t)c * kEntries; if (c <= 1) break; }
+    return s + 32;
+}
+size_t lzh_ent_entries(u32 ntiles)
+{
+    size_t s = 0;
+    for (u32 c = ntiles;; c = (c + kFan - 1) / kFan) { s += (size_t)c + 8; if (c <= 1) break; }
+    return s + 32;
+}
+
+int lzh_launch_cuts(hipStream_t st, const DfSlot *slots, u32 nslots, const u32 *bbase, const u64 *bm, LzhBlk *blks)
+{
+    hipLaunchKernelGGL(k_lzh_cuts, dim3(nslots), dim3(256), 0, st, slots, bbase, bm, blks);
+    return 0;
+}
+
+int lzh_launch_blocks(hipStream_t st, const u8 *image, const u32 *code, LzhBlk *blks, u32 nblks, u32 pbits, u8 *lens, u32 *hdr, u32 *lm_scratch)
+{
+    if (nblks) hipLaunchKernelGGL(k_lzh_block, dim3(nblks), dim3(256), 0, st, image, code, blks, pbits, lens, hdr, lm_scratch);
+    return 0;
+}
+
+int lzh_launch_offsets(hipStream_t st, LzhBlk *blks, const u32 *bbase, u32 nslots, LzhOut *outs, u64 *total)
+{
+    hipLaunchKernelGGL(k_lzh_offsets, dim3(1), dim3(256), 0, st, blks, bbase, nslots, outs, total);
+    return 0;
+}
+
+int lzh_launch_emit(hipStream_t st, const u8 *image, const u32 *code, const LzhBlk *blks, u32 nblks, const u8 *lens, const u32 *hdr, u32 *out)
+{
+    if (nblks) hipLaunchKernelGGL(k_lzh_emit, dim3(nblks), dim3(256), 0, st, image, code, blks, lens, hdr, out);
+    return 0;
+}
+
+int lzh_launch_tables_debug(hipStream_t st, const u32 *cfreq, const u32 *pfreq, u32 pbits, u8 *lens, u32 *hdr, u32 *lm_scratch, u32 *res)
+{
+    hipLaunchKernelGGL(k_lzh_tables_debug, dim3(1), dim3(64), 0, st, cfreq, pfreq, pbits, lens, hdr, lm_scratch, res);
     return 0;
 }
 

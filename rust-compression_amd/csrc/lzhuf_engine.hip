@@ -1,16 +1,25 @@
-// lzhuf_engine.hip -- the driver of the LZHUF decoder (include/bz2_mi355x.h section 9; kernel: k_lzhuf.hip): the device
-// call with its two launches, its figures, and the host-to-host forms on an engine of the per-process cache (host_call.h).
+// lzhuf_engine.hip -- the drivers of the LZHUF decoder (include/bz2_mi355x.h section 9; kernel: k_lzhuf.hip) and encoder
+// (section 10; kernels: k_deflate.hip, the batch front end and "LZHUF encode"): the device calls, their figures, and the
+// host-to-host forms on an engine of the per-process cache (host_call.h).
 #include "engine_state.h"
 #include "k_lzhuf.h"
+#include "k_deflate.h"
 
 #include <cstdlib>
 #include <vector>
 
 using namespace lzhgpu;
+using namespace dfgpu;
 
 struct LzhWorkspace {
     DevBuf in, olen, ooff, rec; // the entries' ranges, their known lengths, their outputs' places, their records
     u64 stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // the encoder: a sub-batch's image, the sort's two arrays (later match and code words), step words, digit counts and bases,
+    // canonical orbits, the code-start bitmap, exit tables, tile entries, slot tables, blocks, their lengths, headers and
+    // scratch, the streams' places, and what the debug entries move
+    DevBuf e_image, e_v0, e_s, e_step, e_hist, e_tbase, e_canon, e_bm, e_tabs, e_ents, e_slots, e_tile_slot, e_bbase, e_blks, e_lens, e_hdr,
+        e_lm, e_outs, e_total, e_dbg;
+    u64 enc_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 void lzh_workspace_free(LzhWorkspace *w) { delete w; }
@@ -181,4 +190,312 @@ extern "C" int bz_lzh_decode_buffer(int method, int prefill, int device, const u
     if (rc != BZ_OK) return rc;
     *out_len = (size_t)len; // (the one entry lies at offset 0)
     return verdict;
+}
+
+// ---- the encoder (section 10 of the header; DESIGN_lzhuf.md sections 7 to 9) ------------------------------------------
+static u64 lzh_batch_image_bytes()
+{
+    const char *s = getenv("BZ_DF_BATCH_MIB"); // the Deflate batch path's switch: slot image per sub-batch, read per call
+    double mib = s ? atof(s) : 64.0;
+    if (!(mib >= 1.0 / 16)) mib = 1.0 / 16;
+    if (mib > 1024) mib = 1024;
+    return (u64)(mib * 1048576.0);
+}
+constexpr u32 kLzhBatchSlots = 4096;     // inputs per sub-batch at most (a block's scratch is 134 KB)
+constexpr u64 kLzhMaxInput = 1ull << 30; // positions are 32-bit
+static u32 lzh_slot_tiles(u64 n) { return n ? (u32)((n + kPTile - 1) / kPTile) : 1u; }
+static u32 lzh_max_blocks(u64 n) { return (u32)((n + kLzhBlockCodes - 1) / kLzhBlockCodes); } // (codes <= bytes)
+
+// DESIGN_lzhuf.md section 8: 16 bits per input byte, 1 084 bytes of header per block, blocks <= ceil(n / 65535)
+static size_t lzh_bound_one(u64 n) { return n ? (size_t)((2 * n + 1084ull * lzh_max_blocks(n) + 3u) & ~(u64)3) : 0; }
+
+extern "C" size_t bz_lzh_encode_batch_bound(const uint64_t *in_len, size_t count)
+{
+    size_t s = 0;
+    for (size_t i = 0; in_len && i < count; ++i) s += lzh_bound_one(in_len[i]);
+    return s;
+}
+
+extern "C" int bz_gpu_last_lzh_encode_stats(bz_gpu_engine *g, uint64_t out[8])
+{
+    if (!g || !out) return BZ_E_PARAM;
+    for (int i = 0; i < 8; ++i) out[i] = g->lzh ? g->lzh->enc_stats[i] : 0;
+    return BZ_OK;
+}
+
+static int lzh_enc_workspace(bz_gpu_engine *g, LzhWorkspace **out)
+{
+    HIPCHK(hipSetDevice(g->device));
+    if (!g->lzh) g->lzh = new LzhWorkspace();
+    *out = g->lzh;
+    return BZ_OK;
+}
+
+// the image of the slots and its parse: afterwards e_s holds the code words, e_bm the code starts, e_image the bytes
+// (the host arrays must outlive the stream's work: the callers wait before they let go of them)
+static int lzh_front(bz_gpu_engine *g, LzhWorkspace *w, u32 dbits, const u8 *d_in, const std::vector<DfSlot> &slots,
+                     const std::vector<u32> &tile_slot)
+{
+    hipStream_t st = g->st;
+    const u32 ns = (u32)slots.size(), ntiles = (u32)tile_slot.size();
+    const u64 nimg = (u64)ntiles * kPTile, npad = nimg + 16;
+    const u64 nchunks = df_chunks(nimg), nsort = nchunks * kLzhStride + 16;
+    const u64 words = nsort > npad ? nsort : npad;
+    int rc;
+    if ((rc = w->e_image.ensure(nimg + 64)) != BZ_OK) return rc;
+    if ((rc = w->e_v0.ensure(words * 4)) != BZ_OK) return rc;
+    if ((rc = w->e_s.ensure(words * 4)) != BZ_OK) return rc;
+    if ((rc = w->e_step.ensure(npad * 2)) != BZ_OK) return rc;
+    if ((rc = w->e_hist.ensure((nchunks * (kLzhStride / kSortTile) + 1) * 256 * 4)) != BZ_OK) return rc;
+    if ((rc = w->e_tbase.ensure(2 * (nchunks + 1) * 256 * 4)) != BZ_OK) return rc;
+    if ((rc = w->e_canon.ensure((size_t)ntiles * 64 * 8 + 64)) != BZ_OK) return rc;
+    if ((rc = w->e_bm.ensure((nimg / 64 + 8) * 8)) != BZ_OK) return rc;
+    if ((rc = w->e_tabs.ensure(lzh_tab_entries(ntiles) * 2)) != BZ_OK) return rc;
+    if ((rc = w->e_ents.ensure(lzh_ent_entries(ntiles) * 2)) != BZ_OK) return rc;
+    if ((rc = w->e_slots.ensure((size_t)ns * sizeof(DfSlot))) != BZ_OK) return rc;
+    if ((rc = w->e_tile_slot.ensure((size_t)ntiles * 4)) != BZ_OK) return rc;
+    HIPCHK(hipMemcpyAsync(w->e_slots.p, slots.data(), (size_t)ns * sizeof(DfSlot), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(w->e_tile_slot.p, tile_slot.data(), (size_t)ntiles * 4, hipMemcpyHostToDevice, st));
+    if (df_launch_gather(st, d_in, w->e_slots.as<DfSlot>(), w->e_tile_slot.as<u32>(), ntiles, w->e_image.as<u8>(), nullptr) != 0)
+        return BZ_E_UNEXPECTED;
+    if (lzh_launch_front(st, dbits, w->e_image.as<u8>(), nimg, ntiles, w->e_slots.as<DfSlot>(), ns, w->e_tile_slot.as<u32>(), w->e_v0.as<u32>(),
+                         w->e_s.as<u32>(), w->e_hist.as<u32>(), w->e_tbase.as<u32>(), w->e_step.as<u16>(), w->e_tabs.as<u16>(), w->e_ents.as<u16>(),
+                         w->e_bm.as<u64>(), w->e_canon.as<u64>()) != 0)
+        return BZ_E_UNEXPECTED;
+    return BZ_OK;
+}
+
+// inputs [first, first + ns) of the call in ntiles tiles; their streams go to d_out + cursor .. in input order, *used = the
+// bytes taken there (a multiple of 4)
+static int lzh_batch_run(bz_gpu_engine *g, LzhWorkspace *w, u32 dbits, u32 pbits, const u8 *d_in, const uint64_t *h_in_off,
+                         const uint64_t *h_in_len, size_t first, u32 ns, u32 ntiles, u8 *d_out, size_t cap, u64 cursor, uint64_t *h_out_off,
+                         uint64_t *h_out_len, u64 *used)
+{
+    hipStream_t st = g->st;
+    std::vector<DfSlot> slots(ns);
+    std::vector<u32> tile_slot(ntiles), bbase((size_t)ns + 1);
+    {
+        u32 t = 0, b = 0;
+        for (u32 j = 0; j < ns; ++j) {
+            const u64 n = h_in_len[first + j];
+            slots[j].src = h_in_off[first + j];
+            slots[j].lo = t * kPTile;
+            slots[j].len = (u32)n;
+            for (u32 k = lzh_slot_tiles(n); k; --k) tile_slot[t++] = j;
+            bbase[j] = b;
+            b += lzh_max_blocks(n);
+        }
+        bbase[ns] = b;
+    }
+    const u32 nblks = bbase[ns];
+    int rc;
+    if ((rc = lzh_front(g, w, dbits, d_in, slots, tile_slot)) != BZ_OK) return rc;
+    if ((rc = w->e_bbase.ensure(((size_t)ns + 1) * 4)) != BZ_OK) return rc;
+    if ((rc = w->e_blks.ensure(((size_t)nblks + 1) * sizeof(LzhBlk))) != BZ_OK) return rc;
+    if ((rc = w->e_lens.ensure(((size_t)nblks + 1) * kLzhLensBytes)) != BZ_OK) return rc;
+    if ((rc = w->e_hdr.ensure(((size_t)nblks + 1) * kLzhHdrWords * 4)) != BZ_OK) return rc;
+    if ((rc = w->e_lm.ensure(((size_t)nblks + 1) * kLzhLmWords * 4)) != BZ_OK) return rc;
+    if ((rc = w->e_outs.ensure((size_t)ns * sizeof(LzhOut))) != BZ_OK) return rc;
+    if ((rc = w->e_total.ensure(64)) != BZ_OK) return rc;
+    HIPCHK(hipMemcpyAsync(w->e_bbase.p, bbase.data(), ((size_t)ns + 1) * 4, hipMemcpyHostToDevice, st));
+    LzhBlk *d_blks = w->e_blks.as<LzhBlk>();
+    if (lzh_launch_cuts(st, w->e_slots.as<DfSlot>(), ns, w->e_bbase.as<u32>(), w->e_bm.as<u64>(), d_blks) != 0) return BZ_E_UNEXPECTED;
+    if (lzh_launch_blocks(st, w->e_image.as<u8>(), w->e_s.as<u32>(), d_blks, nblks, pbits, w->e_lens.as<u8>(), w->e_hdr.as<u32>(),
+                          w->e_lm.as<u32>()) != 0)
+        return BZ_E_UNEXPECTED;
+    if (lzh_launch_offsets(st, d_blks, w->e_bbase.as<u32>(), ns, w->e_outs.as<LzhOut>(), w->e_total.as<u64>()) != 0) return BZ_E_UNEXPECTED;
+    std::vector<LzhOut> outs(ns);
+    std::vector<LzhBlk> blks(nblks);
+    u64 total = 0;
+    HIPCHK(hipMemcpyAsync(outs.data(), w->e_outs.p, (size_t)ns * sizeof(LzhOut), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&total, w->e_total.p, 8, hipMemcpyDeviceToHost, st));
+    if (nblks) HIPCHK(hipMemcpyAsync(blks.data(), d_blks, (size_t)nblks * sizeof(LzhBlk), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st)); // the one look at the device per sub-batch: the streams' sizes decide about `cap`
+    HIPCHK(hipGetLastError());
+    if (total > cap || cursor > cap - total) return BZ_E_CAPACITY;
+    if (total) {
+        HIPCHK(hipMemsetAsync(d_out + cursor, 0, (size_t)total, st)); // (emission ORs its bits into zeroed words)
+        if (lzh_launch_emit(st, w->e_image.as<u8>(), w->e_s.as<u32>(), d_blks, nblks, w->e_lens.as<u8>(), w->e_hdr.as<u32>(),
+                            reinterpret_cast<u32 *>(d_out + cursor)) != 0)
+            return BZ_E_UNEXPECTED;
+    }
+    for (u32 j = 0; j < ns; ++j) {
+        h_out_off[first + j] = cursor + outs[j].off;
+        h_out_len[first + j] = outs[j].len;
+        w->enc_stats[5] += h_in_len[first + j];
+        w->enc_stats[6] += outs[j].len;
+    }
+    for (const LzhBlk &b : blks) {
+        if (!b.ncodes) continue;
+        w->enc_stats[2] += 1;
+        w->enc_stats[3] += b.nlit;
+        w->enc_stats[4] += b.nmatch;
+        w->enc_stats[7] += b.lm;
+    }
+    HIPCHK(hipStreamSynchronize(st)); // (the workspace is free for the next sub-batch)
+    HIPCHK(hipGetLastError());
+    *used = total;
+    return BZ_OK;
+}
+
+extern "C" int bz_gpu_lzh_encode_batch_device(bz_gpu_engine *g, int method, const void *d_in, const uint64_t *h_in_off,
+                                              const uint64_t *h_in_len, size_t count, void *d_out, size_t cap, uint64_t *h_out_off,
+                                              uint64_t *h_out_len)
+{
+    u32 dbits = 0, pbits = 0;
+    if (!g || !lzh_method(method, dbits, pbits)) return BZ_E_PARAM;
+    if (count == 0) return BZ_OK;
+    if (!h_in_off || !h_in_len || !h_out_off || !h_out_len || !d_out) return BZ_E_PARAM;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 3u)) return BZ_E_PARAM;
+    u64 in_end = 0;
+    for (size_t i = 0; i < count; ++i) {
+        if ((h_in_off[i] & 15u) || h_in_off[i] < in_end || h_in_off[i] + h_in_len[i] < h_in_off[i] || h_in_len[i] > kLzhMaxInput) return BZ_E_PARAM;
+        in_end = h_in_off[i] + h_in_len[i];
+    }
+    if (in_end && !d_in) return BZ_E_PARAM;
+    LzhWorkspace *w = nullptr;
+    const int wrc = lzh_enc_workspace(g, &w);
+    if (wrc != BZ_OK) return wrc;
+    for (u64 &s : w->enc_stats) s = 0;
+    const u64 image_max = lzh_batch_image_bytes();
+    u64 cursor = 0;
+    for (size_t i = 0; i < count;) {
+        size_t j = i;
+        u64 tiles = 0;
+        while (j < count && j - i < kLzhBatchSlots && (j == i || (tiles + lzh_slot_tiles(h_in_len[j])) * kPTile <= image_max)) {
+            tiles += lzh_slot_tiles(h_in_len[j]);
+            ++j;
+        }
+        u64 used = 0;
+        const int rc = lzh_batch_run(g, w, dbits, pbits, static_cast<const u8 *>(d_in), h_in_off, h_in_len, i, (u32)(j - i), (u32)tiles,
+                                     static_cast<u8 *>(d_out), cap, cursor, h_out_off, h_out_len, &used);
+        if (rc != BZ_OK) return rc;
+        cursor += used;
+        w->enc_stats[0] += j - i;
+        w->enc_stats[1] += 1;
+        i = j;
+    }
+    return BZ_OK;
+}
+
+extern "C" int bz_gpu_lzh_debug_codes(bz_gpu_engine *g, int method, const void *d_in, size_t n, uint32_t *out_pairs, size_t cap, size_t *count)
+{
+    u32 dbits = 0, pbits = 0;
+    if (!g || !lzh_method(method, dbits, pbits) || !count || (cap && !out_pairs) || (n && !d_in) || n > kLzhMaxInput) return BZ_E_PARAM;
+    if ((uintptr_t)d_in & 15u) return BZ_E_PARAM;
+    *count = 0;
+    if (!n) return BZ_OK;
+    LzhWorkspace *w = nullptr;
+    const int wrc = lzh_enc_workspace(g, &w);
+    if (wrc != BZ_OK) return wrc;
+    std::vector<DfSlot> slots(1);
+    slots[0].src = 0; slots[0].lo = 0; slots[0].len = (u32)n;
+    std::vector<u32> tile_slot(lzh_slot_tiles(n), 0u);
+    const int rc = lzh_front(g, w, dbits, static_cast<const u8 *>(d_in), slots, tile_slot);
+    if (rc != BZ_OK) return rc;
+    std::vector<u32> code(n);
+    std::vector<u8> in(n);
+    HIPCHK(hipMemcpyAsync(code.data(), w->e_s.p, n * 4, hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipMemcpyAsync(in.data(), w->e_image.p, n, hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipStreamSynchronize(g->st));
+    HIPCHK(hipGetLastError());
+    size_t k = 0;
+    for (size_t q = 0; q < n; ++q) {
+        const u32 c = code[q];
+        if (!(c & F_CODE)) continue;
+        if (k < cap) {
+            if (c & F_REF) { out_pairs[2 * k] = c & 511u; out_pairs[2 * k + 1] = (c >> 9) & 0xFFFFu; }
+            else { out_pairs[2 * k] = 0; out_pairs[2 * k + 1] = in[q]; }
+        }
+        ++k;
+    }
+    *count = k;
+    return BZ_OK;
+}
+
+extern "C" int bz_gpu_lzh_debug_tables(bz_gpu_engine *g, int method, const uint32_t *c_freq, const uint32_t *p_freq, uint8_t *c_len,
+                                       uint8_t *p_len, uint8_t *t_len, uint32_t res[3])
+{
+    u32 dbits = 0, pbits = 0;
+    if (!g || !lzh_method(method, dbits, pbits) || !c_freq || !p_freq || !c_len || !p_len || !t_len || !res) return BZ_E_PARAM;
+    LzhWorkspace *w = nullptr;
+    const int wrc = lzh_enc_workspace(g, &w);
+    if (wrc != BZ_OK) return wrc;
+    // [c counts 512][p counts 32][res 16][header words][lengths][scratch]
+    const size_t o_p = 512, o_res = o_p + 32, o_hdr = o_res + 16, o_lens = o_hdr + kLzhHdrWords, o_lm = o_lens + kLzhLensBytes / 4;
+    const int rc = w->e_dbg.ensure((o_lm + kLzhLmWords) * 4);
+    if (rc != BZ_OK) return rc;
+    u32 *d = w->e_dbg.as<u32>();
+    HIPCHK(hipMemcpyAsync(d, c_freq, kLzhNC * 4, hipMemcpyHostToDevice, g->st));
+    HIPCHK(hipMemcpyAsync(d + o_p, p_freq, kLzhNP * 4, hipMemcpyHostToDevice, g->st));
+    if (lzh_launch_tables_debug(g->st, d, d + o_p, pbits, reinterpret_cast<u8 *>(d + o_lens), d + o_hdr, d + o_lm, d + o_res) != 0)
+        return BZ_E_UNEXPECTED;
+    u8 lens[kLzhLensBytes];
+    HIPCHK(hipMemcpyAsync(lens, d + o_lens, kLzhLensBytes, hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipMemcpyAsync(res, d + o_res, 12, hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipStreamSynchronize(g->st));
+    HIPCHK(hipGetLastError());
+    memcpy(c_len, lens, kLzhNC);
+    memcpy(p_len, lens + 512, kLzhNP);
+    memcpy(t_len, lens + 544, kLzhNT);
+    return BZ_OK;
+}
+
+// Many inputs: packed at 16-byte-aligned offsets (BatchLayout), one upload, one device call, one download.
+extern "C" int bz_lzh_encode_batch(int method, int device, const uint8_t *const *ins, const size_t *lens, size_t count, uint8_t **out,
+                                   uint64_t *out_off, uint64_t *out_len)
+{
+    if (!out) return BZ_E_PARAM;
+    *out = nullptr;
+    u32 dbits = 0, pbits = 0;
+    if (!lzh_method(method, dbits, pbits)) return BZ_E_PARAM;
+    if (count && (!ins || !lens || !out_off || !out_len)) return BZ_E_PARAM;
+    const BatchLayout lay(ins, lens, count, 16);
+    if (lay.status != BZ_OK) return lay.status;
+    for (size_t i = 0; i < count; ++i)
+        if (lens[i] > kLzhMaxInput) return BZ_E_PARAM;
+    if (count == 0) {
+        *out = (uint8_t *)malloc(1);
+        return *out ? BZ_OK : BZ_E_NOMEM;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return BZ_E_NOGPU;
+    EngineLease lease(device, 0, 1);
+    if (lease.status() != BZ_OK) return lease.status();
+    bz_gpu_engine *g = lease.engine();
+    const size_t cap = bz_lzh_encode_batch_bound(lay.in_len.data(), count);
+    std::vector<uint8_t> packed((size_t)lay.total + 16);
+    lay.pack_into(packed.data());
+    int rc = g->dec_in.ensure((size_t)lay.total + 64);
+    if (rc == BZ_OK) rc = g->oneshot_out.ensure(cap + 64);
+    if (rc == BZ_OK && lay.total && hipMemcpy(g->dec_in.p, packed.data(), (size_t)lay.total, hipMemcpyHostToDevice) != hipSuccess)
+        rc = BZ_E_UNEXPECTED;
+    if (rc == BZ_OK)
+        rc = bz_gpu_lzh_encode_batch_device(g, method, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), count, g->oneshot_out.p, cap, out_off,
+                                            out_len);
+    if (rc == BZ_OK) {
+        const size_t total = (size_t)(out_off[count - 1] + out_len[count - 1]);
+        uint8_t *h = (uint8_t *)malloc(total ? total : 1);
+        if (!h) rc = BZ_E_NOMEM;
+        else if (total && hipMemcpy(h, g->oneshot_out.p, total, hipMemcpyDeviceToHost) != hipSuccess) {
+            free(h);
+            rc = BZ_E_UNEXPECTED;
+        } else *out = h;
+    }
+    lease.settle(rc);
+    return rc;
+}
+
+extern "C" int bz_lzh_encode_buffer(int method, int device, const uint8_t *in, size_t in_len, uint8_t **out, size_t *out_len)
+{
+    if (!out || !out_len || (in_len && !in)) return BZ_E_PARAM;
+    *out = nullptr;
+    *out_len = 0;
+    uint64_t off = 0, len = 0;
+    const uint8_t *ins[1] = {in};
+    const size_t lens[1] = {in_len};
+    const int rc = bz_lzh_encode_batch(method, device, ins, lens, 1, out, &off, &len);
+    if (rc != BZ_OK) return rc;
+    *out_len = (size_t)len; // (the one stream lies at offset 0)
+    return BZ_OK;
 }

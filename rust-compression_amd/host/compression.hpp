@@ -592,6 +592,73 @@ class LzhufDecoder {
     size_t pos_ = 0;
 };
 
+// LZHUF encoder (include/bz2_mi355x.h section 10):
+//   LzhufEncoder        src/lzhuf/encoder.rs          LzhufEncoder::new(&method)
+// Action::Run collects the input range and yields nothing; Action::Finish collects the rest, encodes everything in one
+// bz_lzh_encode_buffer call and yields the stream, byte for byte the reference's.  Action::Flush is not offered: a
+// parameter error.
+class LzhufEncoder {
+  public:
+    using Input = uint8_t;
+    using Output = uint8_t;
+    using Error = CompressionError;
+
+    explicit LzhufEncoder(LzhufMethod method, int device = 0) : method_(static_cast<int>(method)), device_(device) {} // (does not touch the device)
+
+    template <class I, class S> std::optional<Result<uint8_t>> next(I &it, const S &end, Action action)
+    {
+        if (!done_) {
+            if (action == Action::Flush) return Result<uint8_t>::Err(from_status(BZ_E_PARAM));
+            for (; it != end; ++it) in_.push_back(static_cast<uint8_t>(*it));
+            if (action == Action::Run) return std::nullopt;
+            done_ = true;
+            uint8_t *out = nullptr;
+            size_t n = 0;
+            status_ = bz_lzh_encode_buffer(method_, device_, in_.data(), in_.size(), &out, &n);
+            if (out) {
+                buf_.assign(out, out + n);
+                bz_free(out);
+            }
+            in_.clear();
+        }
+        if (status_ != BZ_OK) {
+            const int rc = status_;
+            status_ = BZ_OK;
+            return Result<uint8_t>::Err(from_status(rc));
+        }
+        if (pos_ < buf_.size()) return Result<uint8_t>::Ok(buf_[pos_++]);
+        return std::nullopt;
+    }
+
+    // Many independent inputs in one call (bz_lzh_encode_batch): element i is the stream of inputs[i].
+    template <class Spans>
+    static Result<std::vector<std::vector<uint8_t>>> encode_batch(const Spans &inputs, LzhufMethod method, int device = 0)
+    {
+        using R = Result<std::vector<std::vector<uint8_t>>>;
+        std::vector<const uint8_t *> ptrs;
+        std::vector<size_t> lens;
+        for (const auto &x : inputs) {
+            ptrs.push_back(reinterpret_cast<const uint8_t *>(x.data()));
+            lens.push_back(x.size());
+        }
+        std::vector<uint64_t> off(ptrs.size()), len(ptrs.size());
+        uint8_t *out = nullptr;
+        const int rc = bz_lzh_encode_batch(static_cast<int>(method), device, ptrs.data(), lens.data(), ptrs.size(), &out, off.data(), len.data());
+        if (rc != BZ_OK) return R::Err(from_status(rc));
+        std::vector<std::vector<uint8_t>> streams(ptrs.size());
+        for (size_t i = 0; i < ptrs.size(); ++i) streams[i].assign(out + off[i], out + off[i] + len[i]);
+        bz_free(out);
+        return R::Ok(std::move(streams));
+    }
+
+  private:
+    int method_, device_;
+    bool done_ = false;
+    int status_ = BZ_OK;
+    std::vector<uint8_t> in_, buf_;
+    size_t pos_ = 0;
+};
+
 // One input as a BGZF file (include/bz2_mi355x.h section 7, df_bgzf_encode_buffer): gzip members of at most block_bytes
 // (0: 65 280) input bytes side by side, then the 28-byte EOF marker unless eof is false.  The reference has no such writer;
 // every member is a stream that zlib, gzip(1) and htslib read.  block_off, when not null, receives the file offset of every

@@ -75,6 +75,15 @@ extern "C" {
     pub fn bz_gpu_last_lzh_decode_stats(g: *mut c_void, out: *mut u64) -> i32;
     pub fn bz_lzh_decode_batch(method: i32, prefill: i32, device: i32, ins: *const *const u8, lens: *const usize, orig_lens: *const u64, count: usize, out: *mut *mut u8, out_off: *mut u64, out_len: *mut u64, verdict: *mut i32) -> i32;
     pub fn bz_lzh_decode_buffer(method: i32, prefill: i32, device: i32, input: *const u8, in_len: usize, orig_len: u64, out: *mut *mut u8, out_len: *mut usize) -> i32;
+    // section 10: LZHUF encode (LzhufEncoder)
+    pub fn bz_gpu_lzh_encode_batch_device(g: *mut c_void, method: i32, d_in: *const c_void, h_in_off: *const u64, h_in_len: *const u64, count: usize, d_out: *mut c_void, cap: usize, h_out_off: *mut u64, h_out_len: *mut u64) -> i32;
+    pub fn bz_gpu_last_lzh_encode_stats(g: *mut c_void, out: *mut u64) -> i32;
+    pub fn bz_lzh_encode_batch_bound(in_len: *const u64, count: usize) -> usize;
+    pub fn bz_lzh_encode_batch(method: i32, device: i32, ins: *const *const u8, lens: *const usize, count: usize, out: *mut *mut u8, out_off: *mut u64, out_len: *mut u64) -> i32;
+    pub fn bz_lzh_encode_buffer(method: i32, device: i32, input: *const u8, in_len: usize, out: *mut *mut u8, out_len: *mut usize) -> i32;
+    // (test hooks: the LZSS codes of one input; the block stage's table builder on given counts)
+    pub fn bz_gpu_lzh_debug_codes(g: *mut c_void, method: i32, d_in: *const c_void, n: usize, out_pairs: *mut u32, cap: usize, count: *mut usize) -> i32;
+    pub fn bz_gpu_lzh_debug_tables(g: *mut c_void, method: i32, c_freq: *const u32, p_freq: *const u32, c_len: *mut u8, p_len: *mut u8, t_len: *mut u8, res: *mut u32) -> i32;
 
     // section 6: every member of a gzip file (MultiGZipDecoder)
     pub fn df_gpu_decode_members_device(g: *mut c_void, d_in: *const c_void, in_len: usize, d_out: *mut c_void, cap: usize, out_len: *mut u64, verdict: *mut i32) -> i32;

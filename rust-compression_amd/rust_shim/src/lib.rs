@@ -11,8 +11,8 @@
 //! Output is bit-identical to the reference's encoders / decoders (checked against the C oracle in
 //! this repository).  NOT compiled in this repository's image (no Rust toolchain there); module
 //! layout, feature flags and `prelude` follow the reference (its `src/lib.rs:48-117`, `Cargo.toml:28-38`).
-//! What the reference has and this crate does not: `LzhufEncoder` (`LzhufDecoder` and `LzhufMethod` are
-//! here) and the standalone `LzssEncoder` / `LzssDecoder`.  The Deflate-family decoders (`Deflater`, `GZipDecoder`, `ZlibDecoder`) follow RFC 1951 /
+//! What the reference has and this crate does not: the standalone `LzssEncoder` / `LzssDecoder` (`LzhufEncoder`,
+//! `LzhufDecoder` and `LzhufMethod` are here; `LzhufEncoder` takes `Action::Run` and `Action::Finish`, not `Flush`).  The Deflate-family decoders (`Deflater`, `GZipDecoder`, `ZlibDecoder`) follow RFC 1951 /
 //! 1950 / 1952 on malformed input, where the reference's swallow errors (see `src/deflate/decoder.rs` here).
 #![cfg_attr(not(feature = "std"), no_std)]
 #[cfg(not(feature = "std"))]
@@ -59,6 +59,8 @@ pub mod prelude {
     pub use crate::gzip::encoder::GZipEncoder;
     #[cfg(all(feature = "lzhuf", feature = "mi355x"))]
     pub use crate::lzhuf::decoder::LzhufDecoder;
+    #[cfg(all(feature = "lzhuf", feature = "mi355x"))]
+    pub use crate::lzhuf::encoder::LzhufEncoder;
     #[cfg(all(feature = "lzhuf", feature = "mi355x"))]
     pub use crate::lzhuf::LzhufMethod;
     #[cfg(all(feature = "zlib", feature = "mi355x"))]

@@ -1,6 +1,7 @@
-//! `lzhuf` (the reference's `src/lzhuf/mod.rs`): the LHA methods `-lh4-` .. `-lh7-`.  The decoder runs on the GPU
-//! (section 9 of the C ABI); the reference's `LzhufEncoder` has no GPU path yet.
+//! `lzhuf` (the reference's `src/lzhuf/mod.rs`): the LHA methods `-lh4-` .. `-lh7-`.  Decoder and encoder run on the
+//! GPU (sections 9 and 10 of the C ABI).
 pub mod decoder;
+pub mod encoder;
 
 #[derive(Clone, Copy, Debug)]
 pub enum LzhufMethod {

@@ -256,6 +256,26 @@ pub fn lzh_decode_batch(method: crate::lzhuf::LzhufMethod, inputs: &[&[u8]], ori
     Ok(entries)
 }
 
+/// Many independent inputs as LZHUF streams in one call (`bz_lzh_encode_batch`, device 0): element `i` of the result is
+/// `inputs[i].iter().cloned().encode(&mut LzhufEncoder::new(&method), Action::Finish)` collected, byte for byte.
+#[cfg(feature = "lzhuf")]
+pub fn lzh_encode_batch(method: crate::lzhuf::LzhufMethod, inputs: &[&[u8]]) -> Result<Vec<Vec<u8>>, CompressionError> {
+    let ptrs: Vec<*const u8> = inputs.iter().map(|x| x.as_ptr()).collect();
+    let lens: Vec<usize> = inputs.iter().map(|x| x.len()).collect();
+    let mut off: Vec<u64> = Vec::new();
+    off.resize(inputs.len(), 0);
+    let mut len = off.clone();
+    let mut out: *mut u8 = core::ptr::null_mut();
+    let rc = unsafe { ffi::bz_lzh_encode_batch(method.abi(), 0, ptrs.as_ptr(), lens.as_ptr(), inputs.len(), &mut out, off.as_mut_ptr(), len.as_mut_ptr()) };
+    if rc != ffi::BZ_OK {
+        note_status(rc);
+        return Err(CompressionError::from_status(rc));
+    }
+    let streams = (0..inputs.len()).map(|i| unsafe { core::slice::from_raw_parts(out.add(off[i] as usize), len[i] as usize) }.to_vec()).collect();
+    unsafe { ffi::bz_free(out as *mut core::ffi::c_void) };
+    Ok(streams)
+}
+
 pub(crate) fn note_status(rc: i32) {
     if rc != 0 {
         LAST_STATUS.store(rc, Ordering::Relaxed);
