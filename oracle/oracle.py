@@ -293,13 +293,13 @@ def lzss_tokens(data: bytes, dict_: bytes = b"", comparison: str = "deflate", wi
     return [("ref", buf[2 * i], buf[2 * i + 1]) if buf[2 * i] else ("sym", buf[2 * i + 1]) for i in range(n)]
 
 
-def lzss_tokens_raw(data: bytes):
+def lzss_tokens_raw(data: bytes, dict_: bytes = b""):
     """Deflate-parameter LZSS codes as a numpy uint32 array [n, 2] of (len, pos); len 0: literal pos."""
     import numpy as np
-    data = bytes(data)
+    data, dict_ = bytes(data), bytes(dict_)
     cap = len(data) + 16
     buf = np.zeros((cap, 2), dtype=np.uint32)
-    n = lib().dfo_lzss_tokens(data, len(data), b"", 0, 0, 0x8000, 258, 3, 3,
+    n = lib().dfo_lzss_tokens(data, len(data), dict_, len(dict_), 0, 0x8000, 258, 3, 3,
                               buf.ctypes.data_as(C.POINTER(C.c_uint32)), cap)
     return buf[:n]
 

@@ -250,9 +250,11 @@ def build(case):
 
 
 # ------------------------------------------------------------------------------------------------------- the model
-def naive_steps(data, window, max_match=R.MAX_MATCH, mutate=()):
+def naive_steps(data, window, max_match=R.MAX_MATCH, mutate=(), start=0, stop=None):
     """SlideDict::search_dic + LzssEncoder::encode restated plainly: [(position, lazy_index, m0, m1, m2, chosen)] with
-    m = (len, pos) or None.  Quadratic in the worst case: for the small Z cases and the tails of the B cases."""
+    m = (len, pos) or None.  Quadratic in the worst case: for the small Z cases and the tails of the B cases.
+    start / stop: the steps from position `start` (it must be the first byte of a step; everything in front of it is
+    history) to the first one at or behind `stop` (tests/dfseams.py: the steps around a part seam)."""
     n = len(data)
     chains = {}
 
@@ -293,8 +295,8 @@ def naive_steps(data, window, max_match=R.MAX_MATCH, mutate=()):
 
     floor = R.MIN_MATCH - 1 if "lazy_accepts_3" in mutate else R.MIN_MATCH
 
-    steps, p = [], 0
-    while p < n:
+    steps, p = [], start
+    while p < n and (stop is None or p < stop):
         m0 = search(p)
         m1 = m2 = None
         out, li = m0, 0
