@@ -1117,6 +1117,18 @@ int df_bgzf_read_buffer(int device, const uint8_t *in, size_t in_len, uint64_t u
  *     BZ_E_PARAM also: a method outside 4..7, a prefill outside -1..255, a null
  *     engine, a null array (h_orig_len excepted) with count > 0, a misaligned
  *     d_in, d_out or offset.  count == 0: BZ_OK, nothing touched.
+ * (g) ONE LARGE ENTRY ACROSS MANY WAVES.  An entry of BZ_LZH_SPLIT_KIB KiB of
+ *     compressed bytes or more (default 1024; 0: never; read per call) is
+ *     decoded by one wave per block: every bit position that holds a whole
+ *     block header valid under (d) and inside the entry is a candidate, every
+ *     candidate is decoded, and the walk from bit 0 keeps the pieces that start
+ *     where the piece in front of them stopped (DESIGN_lzhuf.md section 11).
+ *     Such an entry obeys (a) to (f) clause by clause: its bytes, length,
+ *     verdict and its share of bz_gpu_last_lzh_decode_stats [0..6] are those
+ *     of the one-wave path, which it takes after all when its chain has fewer
+ *     than two pieces, when it holds more than max(64, in_len /
+ *     BZ_LZH_SPLIT_CAND_BYTES) candidates (default 1024) or when the source
+ *     map (4 bytes per output byte, for the length of the call) cannot be had.
  * ======================================================================== */
 #define BZ_LZH_LH4 4
 #define BZ_LZH_LH5 5
@@ -1130,6 +1142,13 @@ int bz_gpu_lzh_decode_batch_device(bz_gpu_engine *g, int method, int prefill, co
  * bytes [6] compressed bytes consumed by the clean entries (to the end (a), the zero length included, or to the code that
  * completed the original length) [7] kernel launches. */
 int bz_gpu_last_lzh_decode_stats(bz_gpu_engine *g, uint64_t out[8]);
+/* The split entries (g) of the last call: [0] entries split [1] candidates [2] pieces in chains [3] false pieces (decoded,
+ * not in a chain) [4] pieces decoded again with their place known [5] jump rounds [6] bytes filled by the gather (their value
+ * lay in an earlier piece) [7] fallbacks to the one-wave path. */
+int bz_gpu_last_lzh_decode_split_stats(bz_gpu_engine *g, uint64_t out[8]);
+/* Seconds of the last call's split entries in: [0] search [1] sizes launch [2] chain and pieces decoded again [3] writing
+ * launch [4] jump rounds [5] gather. */
+int bz_gpu_last_lzh_decode_split_timings(bz_gpu_engine *g, double out_seconds[6]);
 /* The host form (mirrors df_decode_batch): the entries packed at 4-byte-aligned offsets, one upload, one device call on an
  * engine of the per-process cache, one download; *out is ONE malloc'ed buffer (bz_free), entry i at out_off[i] (multiples
  * of 16).  orig_lens as h_orig_len.  The parameters are checked before any device is touched; count == 0: BZ_OK, an empty

@@ -104,6 +104,7 @@ EXPORTS = [
     "df_bgzf_block_count", "df_bgzf_bound", "df_gpu_bgzf_encode_device", "df_gpu_last_bgzf_stats", "df_bgzf_encode_buffer",
     "df_bgzf_index_buffer", "df_gpu_bgzf_index_device", "df_gpu_bgzf_read_device", "df_gpu_last_bgzf_read_stats", "df_bgzf_read_buffer",
     "bz_gpu_lzh_decode_batch_device", "bz_gpu_last_lzh_decode_stats", "bz_lzh_decode_batch", "bz_lzh_decode_buffer",
+    "bz_gpu_last_lzh_decode_split_stats", "bz_gpu_last_lzh_decode_split_timings",
     "bz_gpu_lzh_encode_batch_device", "bz_gpu_last_lzh_encode_stats", "bz_lzh_encode_batch_bound", "bz_lzh_encode_batch",
     "bz_lzh_encode_buffer", "bz_gpu_lzh_debug_codes", "bz_gpu_lzh_debug_tables",
 ]
@@ -287,6 +288,8 @@ def lib():
     L.df_decode_buffer_dict.argtypes = [C.c_int, C.c_int, C.c_char_p, sz, C.c_char_p, sz, C.POINTER(u8p), szp]
     L.bz_gpu_lzh_decode_batch_device.argtypes = [vp, C.c_int, C.c_int, vp, u64p, u64p, u64p, sz, vp, sz, u64p, u64p, i32p]
     L.bz_gpu_last_lzh_decode_stats.argtypes = [vp, u64p]
+    L.bz_gpu_last_lzh_decode_split_stats.argtypes = [vp, u64p]
+    L.bz_gpu_last_lzh_decode_split_timings.argtypes = [vp, C.POINTER(C.c_double)]
     L.bz_lzh_decode_batch.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, u64p, sz, C.POINTER(u8p), u64p, u64p, i32p]
     L.bz_lzh_decode_buffer.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, sz, C.c_uint64, C.POINTER(u8p), szp]
     L.bz_gpu_lzh_encode_batch_device.argtypes = [vp, C.c_int, vp, u64p, u64p, sz, vp, sz, u64p, u64p]
@@ -1604,6 +1607,22 @@ class GpuEngine:
         s = (C.c_uint64 * 8)()
         _check(lib().bz_gpu_last_lzh_decode_stats(self._h, s))
         return [int(x) for x in s]
+
+    LZH_DECODE_SPLIT_STATS = ("entries_split", "candidates", "chain_pieces", "false_pieces", "pieces_decoded_again", "jump_rounds",
+                              "gathered_bytes", "fallbacks")
+
+    def lzh_decode_split_stats(self):
+        """The entries of the last lzh_decode_batch_device call that went across many waves, in the order of
+        LZH_DECODE_SPLIT_STATS (bz_gpu_last_lzh_decode_split_stats; section 9 (g) of the header)."""
+        s = (C.c_uint64 * 8)()
+        _check(lib().bz_gpu_last_lzh_decode_split_stats(self._h, s))
+        return [int(x) for x in s]
+
+    def lzh_decode_split_timings(self):
+        """Seconds the last call's split entries spent in: search, sizes, pieces decoded again, writing, jump, gather."""
+        s = (C.c_double * 6)()
+        _check(lib().bz_gpu_last_lzh_decode_split_timings(self._h, s))
+        return [float(x) for x in s]
 
     LZH_ENCODE_STATS = ("inputs", "sub_batches", "blocks", "literals", "matches", "input_bytes", "stream_bytes", "limited_tables")
 

@@ -9,6 +9,8 @@
 //   <false> sums the output length and writes nothing but the entry's record;
 //   <true>  decodes again and writes the bytes at the place the driver gave the entry, never at or behind the length the
 //           first launch reported (`limit`).
+// The loop itself is lzh_decode<USE, WRITE>, once: kEntry is the above; kPiece is k_lzh_decode_piece<WRITE>, one wave per
+// PIECE of one large entry (DESIGN_lzhuf.md section 11; the rules: lzh_split.h), whose starts k_lzh_split_search finds.
 //
 // INPUT.  Bits are read MSB first: the bit buffer (64 bits) holds the next bits at its TOP, and is refilled in 32-bit words
 // whose bytes are swapped on the way in.  A word comes from a 64-word stage the lanes load together (lane l holds word
@@ -40,6 +42,7 @@
 #include "../../include/bz2_mi355x.h"
 #include "bzgpu.h"
 #include "k_lzhuf.h"
+#include "lzh_split.h"
 
 namespace lzhgpu {
 using namespace bzgpu;
@@ -178,43 +181,63 @@ struct LzhTabs {
     u32 nc[20], np[20], nt[20];
     u8 cl[512], pl[32], tl[32];
 };
-} // namespace
 
-template <bool WRITE>
-__global__ __launch_bounds__(64) void k_lzh_decode(const u8 *__restrict__ in, const u64 *__restrict__ in_off, const u64 *__restrict__ in_len,
-                                                   const u64 *__restrict__ orig_len, u32 dbits, u32 pbits, int prefill, u8 *out_all,
-                                                   const u64 *__restrict__ out_off, LzhRec *rec)
+// The decode loop, once.  kEntry: a whole entry from its first bit (k_lzh_decode).  kPiece: a piece of a split entry
+// (k_lzh_decode_piece; lzh_split.h), which differs only where `if constexpr (USE == kPiece)` says so: it starts at any bit; at
+// a block boundary at or behind `stop` whose header it has read and found valid it stops (so where a piece stops there is a
+// candidate); a distance that reaches in front of the piece is believed while `base` is unknown and held against base + p
+// once it is known, its excess d - p recorded in `reach`; with WRITE every byte i gets smap[i]: base + i itself when the
+// byte is stored, else the position in the entry's output, in front of the piece, that holds its value.  A source in front
+// of the ENTRY (prefill >= 0) is the constant: stored at once, its own root.
+enum LzhUse { kEntry, kPiece };
+struct LzhPieceArg {
+    u32 *smap; // the source map of the piece's bytes (WRITE)
+    u32 base;  // where the piece's output starts in the entry's (lzhsplit::kBaseUnknown: not known)
+    u64 stop;  // the next candidate
+};
+// r: open at the first bit to decode; L: the byte limit (has_len: reaching the end (a) in front of it is BZ_E_EOF); out, limit:
+// where the bytes go and how many of them (WRITE); rec (and prec, kPiece): what a sizes launch leaves
+template <LzhUse USE, bool WRITE>
+__device__ __forceinline__ void lzh_decode(const u8 *const ebase, const u32 elen, const u64 start, const u32 lane, const u32 L, const bool has_len,
+                                             const u32 dbits, const u32 pbits, const int prefill, u8 *const out, const u32 limit,
+                                           const LzhPieceArg pc, LzhRec *const rec, LzhPieceRec *const prec)
 {
     __shared__ LzhTabs t;
-    const u32 lane = threadIdx.x, j = blockIdx.x;
     LzhIn r;
-    r.base = in + in_off[j];
-    r.len = (u32)in_len[j];
+    r.base = ebase;
+    r.len = elen;
     r.buf = 0;
     r.cnt = 0;
     r.nextw = 0;
     r.cw = 0;
     r.cbase = 0xFFFFFF00u;
     const u64 total = 8ull * r.len;
-    const u64 ol = orig_len ? orig_len[j] : kNoLen;
-    const bool has_len = ol != kNoLen;
-    const u32 L = ol > 0xFFFFFFFEull ? 0xFFFFFFFFu : (u32)ol; // (a length the 4 GiB guard comes in front of is as good as none)
-    u8 *const out = WRITE ? out_all + out_off[j] : nullptr;
-    const u32 limit = WRITE ? rec[j].len : 0u;
+    if constexpr (USE == kPiece) { // any bit of the entry
+        r.nextw = (u32)(start >> 5);
+        lzh_fill(r, lane);
+        (void)lzh_take(r, (u32)start & 31u);
+    }
     const u32 window = 1u << dbits;
+    [[maybe_unused]] const u32 base = pc.base;
 
     u32 p = 0;      // bytes produced, pending literals included
     u32 npend = 0;  // literals waiting in `lit`
     u32 lit = 0;    // PER LANE: pending literal number `lane`
     u32 fenced = 0; // stores below this position are ordered before every later load
     u32 nblk = 0, nlit = 0, nmatch = 0, flags = 0;
+    [[maybe_unused]] u32 reach = 0;
+    [[maybe_unused]] bool stopped = false;
+    [[maybe_unused]] u64 boundary = 0;
     int verdict = BZ_OK;
 
 #define LZH_FLUSH()                                                                   \
     do {                                                                              \
         if (WRITE && npend) {                                                         \
             const u32 q_ = p - npend + lane;                                          \
-            if (lane < npend && q_ < limit) out[q_] = (u8)lit;                        \
+            if (lane < npend && q_ < limit) {                                         \
+                out[q_] = (u8)lit;                                                    \
+                if constexpr (USE == kPiece) pc.smap[q_] = base + q_;                 \
+            }                                                                         \
         }                                                                             \
         npend = 0;                                                                    \
     } while (0)
@@ -250,6 +273,7 @@ __global__ __launch_bounds__(64) void k_lzh_decode(const u8 *__restrict__ in, co
         if (p >= L) break; // (b): the known length is there
         lzh_fill(r, lane);
         if (total - lzh_consumed(r) < 16u) break; // (a): no room for a block length
+        if constexpr (USE == kPiece) boundary = lzh_consumed(r);
         const u32 ncodes = lzh_take(r, 16);
         if (ncodes == 0) break; // (a)
         int tconst = -1, cconst = -1, pconst = -1;
@@ -342,10 +366,16 @@ __global__ __launch_bounds__(64) void k_lzh_decode(const u8 *__restrict__ in, co
                 if (lzh_build(t.pl, n, t.tp, kSBits, t.np, t.sp, lane) != 0) LZH_DATA();
             }
         }
+        if constexpr (USE == kPiece) {
+            if (boundary >= pc.stop) { // a valid header at or behind the next candidate: that candidate's piece goes on from here
+                stopped = true;
+                goto done;
+            }
+        }
         // ---- the codes of the block
         for (u32 k = 0; k < ncodes; ++k) {
             if (p >= L) goto done; // (b)
-            if (p > 0xFFFFFFFFu - 0x200u) {
+            if (USE == kPiece && base != lzhsplit::kBaseUnknown ? (u64)base + p > 0xFFFFFFFFu - 0x200u : p > 0xFFFFFFFFu - 0x200u) {
                 flags |= 1u;
                 LZH_DATA();
             }
@@ -374,7 +404,13 @@ __global__ __launch_bounds__(64) void k_lzh_decode(const u8 *__restrict__ in, co
             const u32 pos = v > 1 ? (1u << (v - 1)) | lzh_take(r, (u32)v - 1u) : (u32)v;
             LZH_EOF_CHECK();
             const u32 d = pos + 1u;
-            if (d > window || (prefill < 0 && d > p)) LZH_DATA();
+            if constexpr (USE == kPiece) {
+                if (d > window) LZH_DATA();
+                if (d > p) { // in front of the piece: inside the entry's output if the piece knows where it lies
+                    if (prefill < 0 && base != lzhsplit::kBaseUnknown && (u64)d > (u64)base + p) LZH_DATA();
+                    if (d - p > reach) reach = d - p;
+                }
+            } else if (d > window || (prefill < 0 && d > p)) LZH_DATA();
             if (len > L - p) len = L - p; // (b): cut at the known length
             LZH_FLUSH();
             if (WRITE) {
@@ -390,7 +426,17 @@ __global__ __launch_bounds__(64) void k_lzh_decode(const u8 *__restrict__ in, co
                     const u32 i = b + lane;
                     if (i < len && p + i < limit) {
                         const long long q = q0 + (d >= len ? i : i % d);
-                        out[p + i] = q < 0 ? (u8)prefill : out[q];
+                        if constexpr (USE == kPiece) {
+                            if ((long long)base + q < 0) { // in front of the entry: the constant, its own root
+                                out[p + i] = (u8)prefill;
+                                pc.smap[p + i] = base + p + i;
+                            } else if (q < 0) pc.smap[p + i] = (u32)((long long)base + q); // (no byte: the gather brings it)
+                            else {
+                                const u32 sv = pc.smap[q];
+                                out[p + i] = out[q];
+                                pc.smap[p + i] = sv == base + (u32)q ? base + p + i : sv;
+                            }
+                        } else out[p + i] = q < 0 ? (u8)prefill : out[q];
                     }
                 }
             }
@@ -405,18 +451,96 @@ done:
     if (!WRITE && lane == 0) {
         LzhRec q;
         q.end_bit = lzh_consumed(r) < total ? lzh_consumed(r) : total;
+        if constexpr (USE == kPiece) {
+            if (stopped) q.end_bit = boundary;
+        }
         q.len = p;
         q.verdict = verdict;
         q.nblk = nblk;
         q.nlit = nlit;
         q.nmatch = nmatch;
         q.flags = flags;
-        rec[j] = q;
+        *rec = q;
+        if constexpr (USE == kPiece) {
+            prec->reach = reach;
+            prec->ended = stopped ? 0u : 1u;
+            prec->pad[0] = prec->pad[1] = 0;
+        }
     }
 #undef LZH_FLUSH
 #undef LZH_EOF_CHECK
 #undef LZH_DATA
 #undef LZH_LEN
+}
+} // namespace
+
+template <bool WRITE>
+__global__ __launch_bounds__(64) void k_lzh_decode(const u8 *__restrict__ in, const u64 *__restrict__ in_off, const u64 *__restrict__ in_len,
+                                                   const u64 *__restrict__ orig_len, u32 dbits, u32 pbits, int prefill, u8 *out_all,
+                                                   const u64 *__restrict__ out_off, LzhRec *rec)
+{
+    const u32 lane = threadIdx.x, j = blockIdx.x;
+    const u8 *const ebase = in + in_off[j];
+    const u32 elen = (u32)in_len[j];
+    const u64 ol = orig_len ? orig_len[j] : kNoLen;
+    const bool has_len = ol != kNoLen;
+    const u32 L = ol > 0xFFFFFFFEull ? 0xFFFFFFFFu : (u32)ol; // (a length the 4 GiB guard comes in front of is as good as none)
+    lzh_decode<kEntry, WRITE>(ebase, elen, 0, lane, L, has_len, dbits, pbits, prefill, WRITE ? out_all + out_off[j] : nullptr,
+                              WRITE ? rec[j].len : 0u, LzhPieceArg{nullptr, 0, 0}, rec + j, nullptr);
+}
+
+// One wave per piece.  <false>: what the piece is (LzhPieceRec); <true>: its bytes and their source map, below pc.limit.
+template <bool WRITE>
+__global__ __launch_bounds__(64) void k_lzh_decode_piece(const u8 *__restrict__ ebase, u32 elen, u32 dbits, u32 pbits, int prefill,
+                                                         const LzhPiece *__restrict__ pcs, LzhPieceRec *rec, u8 *eout, u32 *emap)
+{
+    const u32 lane = threadIdx.x, j = blockIdx.x;
+    const LzhPiece q = pcs[j];
+    // the writing launch knows its base: eout + base and emap + base are the piece's own ranges
+    lzh_decode<kPiece, WRITE>(ebase, elen, q.start, lane, q.limit, !WRITE && q.has_len != 0, dbits, pbits, prefill, WRITE ? eout + q.base : nullptr,
+                              WRITE ? q.limit : 0u, LzhPieceArg{WRITE ? emap + q.base : nullptr, q.base, q.stop}, WRITE ? nullptr : &rec[j].r,
+                              WRITE ? nullptr : rec + j);
+}
+
+// ---- the candidates of one entry (lzh_split.h), all of them, ascending.  A wave looks at kSearchBits bit offsets, 64 per
+// step, one per lane.  FILL false: cnt[wave] = its candidates; FILL true: it writes them behind first[wave], in order (the
+// host has summed the counts in between: no atomic decides an order).
+constexpr u32 kSearchBits = 1024;
+template <bool FILL>
+__global__ __launch_bounds__(64) void k_lzh_split_search(const u8 *__restrict__ ebase, u32 elen, u32 dbits, u32 pbits, u32 *cnt,
+                                                         const u32 *__restrict__ first, u64 *cand, u32 ncand)
+{
+    const u32 lane = threadIdx.x;
+    const u64 total = 8ull * elen, lo = (u64)blockIdx.x * kSearchBits;
+    const u64 hi = lo + kSearchBits < total ? lo + kSearchBits : total;
+    if (FILL && cnt[blockIdx.x] == 0) return; // (the count pass found nothing in this wave's bits)
+    u32 n = 0;
+    const u32 at = FILL ? first[blockIdx.x] : 0u;
+    for (u64 o = lo; o < hi; o += 64u) {
+        const u64 bit = o + lane;
+        u32 w[5]; // (unrolled: registers) the words that hold bits [bit, bit + 128)
+#pragma unroll
+        for (u32 q = 0; q < 5; ++q) {
+            const u64 byte = 4ull * ((bit >> 5) + q);
+            u32 v = 0;
+            if (byte + 4 <= elen) v = *reinterpret_cast<const u32 *>(ebase + byte);
+            else
+                for (u32 b = 0; b < 4 && byte + b < elen; ++b) v |= (u32)ebase[byte + b] << (8 * b);
+            w[q] = __builtin_bswap32(v);
+        }
+        const u32 sh = (u32)bit & 31u;
+        const u64 a0 = (u64)w[0] << 32 | w[1], a1 = (u64)w[2] << 32 | w[3], a2 = (u64)w[4] << 32;
+        const u64 b0 = sh ? a0 << sh | a1 >> (64u - sh) : a0;
+        const u64 b1 = sh ? a1 << sh | a2 >> (64u - sh) : a1;
+        const bool found = bit < hi && lzhsplit::prefilter(b0, b1) && lzhsplit::header_ok(ebase, elen, bit, dbits, pbits);
+        const u64 m = __ballot(found);
+        if (FILL && found) {
+            const u32 at_ = at + n + (u32)__popcll(m & ((1ull << lane) - 1ull));
+            if (at_ < ncand) cand[at_] = bit; // (the counts were taken from the same bytes: always)
+        }
+        n += (u32)__popcll(m);
+    }
+    if (!FILL && lane == 0) cnt[blockIdx.x] = n;
 }
 
 int lzh_launch_decode(hipStream_t st, bool write, const u8 *in, const u64 *in_off, const u64 *in_len, const u64 *orig_len, u32 count,
@@ -426,6 +550,26 @@ int lzh_launch_decode(hipStream_t st, bool write, const u8 *in, const u64 *in_of
         hipLaunchKernelGGL((k_lzh_decode<true>), dim3(count), dim3(64), 0, st, in, in_off, in_len, orig_len, dbits, pbits, prefill, out, out_off, rec);
     else
         hipLaunchKernelGGL((k_lzh_decode<false>), dim3(count), dim3(64), 0, st, in, in_off, in_len, orig_len, dbits, pbits, prefill, out, out_off, rec);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int lzh_launch_decode_piece(hipStream_t st, bool write, const u8 *ebase, u32 elen, u32 dbits, u32 pbits, int prefill, const LzhPiece *pcs,
+                            u32 count, LzhPieceRec *rec, u8 *eout, u32 *emap)
+{
+    if (write)
+        hipLaunchKernelGGL((k_lzh_decode_piece<true>), dim3(count), dim3(64), 0, st, ebase, elen, dbits, pbits, prefill, pcs, rec, eout, emap);
+    else
+        hipLaunchKernelGGL((k_lzh_decode_piece<false>), dim3(count), dim3(64), 0, st, ebase, elen, dbits, pbits, prefill, pcs, rec, eout, emap);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+u32 lzh_split_search_waves(u32 elen) { return (u32)((8ull * elen + kSearchBits - 1) / kSearchBits); }
+int lzh_launch_split_search(hipStream_t st, bool fill, const u8 *ebase, u32 elen, u32 dbits, u32 pbits, u32 *cnt, const u32 *first, u64 *cand,
+                            u32 ncand)
+{
+    const u32 waves = lzh_split_search_waves(elen);
+    if (fill) hipLaunchKernelGGL((k_lzh_split_search<true>), dim3(waves), dim3(64), 0, st, ebase, elen, dbits, pbits, cnt, first, cand, ncand);
+    else hipLaunchKernelGGL((k_lzh_split_search<false>), dim3(waves), dim3(64), 0, st, ebase, elen, dbits, pbits, cnt, first, cand, ncand);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

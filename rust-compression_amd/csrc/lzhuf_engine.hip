@@ -4,7 +4,10 @@
 #include "engine_state.h"
 #include "k_lzhuf.h"
 #include "k_deflate.h"
+#include "lzh_split.h"
 
+#include <algorithm>
+#include <chrono>
 #include <cstdlib>
 #include <vector>
 
@@ -14,6 +17,11 @@ using namespace dfgpu;
 struct LzhWorkspace {
     DevBuf in, olen, ooff, rec; // the entries' ranges, their known lengths, their outputs' places, their records
     u64 stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // an entry across many waves: the search waves' counts and firsts, the candidates, pieces, their records, the source map
+    // and the jump rounds' counters
+    DevBuf s_cnt, s_cand, s_piece, s_prec, s_map, s_jump;
+    u64 split_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double split_ms[6] = {0, 0, 0, 0, 0, 0}; // search, sizes, pieces decoded again, writing, jump, gather
     // the encoder: a sub-batch's image, the sort's two arrays (later match and code words), step words, digit counts and bases,
     // canonical orbits, the code-start bitmap, exit tables, tile entries, slot tables, blocks, their lengths, headers and
     // scratch, the streams' places, and what the debug entries move
@@ -48,6 +56,208 @@ extern "C" int bz_gpu_last_lzh_decode_stats(bz_gpu_engine *g, uint64_t out[8])
     return BZ_OK;
 }
 
+// ---- one large entry across many waves (lzh_split.h; DESIGN_lzhuf.md section 11) --------------------------------------
+// An entry of BZ_LZH_SPLIT_KIB KiB or more of compressed bytes is split (0: none is; a fraction is allowed); an entry with more
+// than max(64, in_len / BZ_LZH_SPLIT_CAND_BYTES) candidates is not.  Both are read per call.
+static double lzh_env_num(const char *name, double dflt)
+{
+    const char *s = getenv(name);
+    if (!s || !*s) return dflt;
+    char *end = nullptr;
+    const double v = strtod(s, &end);
+    return end == s || !(v >= 0) ? dflt : v;
+}
+static double lzh_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+extern "C" int bz_gpu_last_lzh_decode_split_stats(bz_gpu_engine *g, uint64_t out[8])
+{
+    if (!g || !out) return BZ_E_PARAM;
+    for (int i = 0; i < 8; ++i) out[i] = g->lzh ? g->lzh->split_stats[i] : 0;
+    return BZ_OK;
+}
+extern "C" int bz_gpu_last_lzh_decode_split_timings(bz_gpu_engine *g, double out_seconds[6])
+{
+    if (!g || !out_seconds) return BZ_E_PARAM;
+    for (int i = 0; i < 6; ++i) out_seconds[i] = g->lzh ? g->lzh->split_ms[i] * 1e-3 : 0.0;
+    return BZ_OK;
+}
+
+struct LzhSplitEntry {
+    size_t index = 0;            // of the entry in the call
+    std::vector<LzhPiece> chain; // the confirmed pieces in stream order, each with its place in the entry's output and its length
+    LzhRec rec;                  // what the one-wave path would have left for the entry
+    // its share of bz_gpu_last_lzh_decode_split_stats, of the launches and of the phases search, sizes, pieces decoded again:
+    // counted in once the entry is known to stay split
+    u64 st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    u64 launches = 0;
+    double ms[3] = {0, 0, 0};
+};
+struct LzhMethod {
+    u32 dbits, pbits;
+    int prefill;
+};
+
+// the sizes launch over n pieces, and their records
+static int lzh_split_pieces(bz_gpu_engine *g, LzhWorkspace *w, LzhMethod m, const u8 *ebase, u32 elen, const LzhPiece *pcs, u32 n, LzhPieceRec *out,
+                            u64 *launches)
+{
+    int rc = w->s_piece.ensure((size_t)n * sizeof(LzhPiece));
+    if (rc == BZ_OK) rc = w->s_prec.ensure((size_t)n * sizeof(LzhPieceRec));
+    if (rc != BZ_OK) return rc;
+    HIPCHK(hipMemcpyAsync(w->s_piece.p, pcs, (size_t)n * sizeof(LzhPiece), hipMemcpyHostToDevice, g->st));
+    if (lzh_launch_decode_piece(g->st, false, ebase, elen, m.dbits, m.pbits, m.prefill, w->s_piece.as<LzhPiece>(), n, w->s_prec.as<LzhPieceRec>(),
+                                nullptr, nullptr) != 0)
+        return BZ_E_UNEXPECTED;
+    HIPCHK(hipMemcpyAsync(out, w->s_prec.p, (size_t)n * sizeof(LzhPieceRec), hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipStreamSynchronize(g->st));
+    *launches += 1;
+    return BZ_OK;
+}
+
+// Search, sizes and chain of one entry.  ol: its known length or kNoLen.  *fallback: the entry takes the one-wave path.
+static int lzh_split_sizes(bz_gpu_engine *g, LzhWorkspace *w, LzhMethod m, const u8 *ebase, u32 elen, u64 ol, LzhSplitEntry &e, bool *fallback)
+{
+    using namespace lzhsplit;
+    *fallback = true;
+    int rc;
+    double t0 = lzh_now_ms();
+    // ---- every candidate, ascending: the search waves' counts, their sums, the list
+    const u32 waves = lzh_split_search_waves(elen);
+    if ((rc = w->s_cnt.ensure((size_t)waves * 8)) != BZ_OK) return rc;
+    u32 *d_cnt = w->s_cnt.as<u32>(), *d_first = d_cnt + waves;
+    if (lzh_launch_split_search(g->st, false, ebase, elen, m.dbits, m.pbits, d_cnt, nullptr, nullptr, 0) != 0) return BZ_E_UNEXPECTED;
+    std::vector<u32> first(waves);
+    HIPCHK(hipMemcpyAsync(first.data(), d_cnt, (size_t)waves * 4, hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipStreamSynchronize(g->st));
+    e.launches += 1;
+    u64 ncand = 0;
+    for (u32 &c : first) {
+        const u32 n = c;
+        c = (u32)ncand;
+        ncand += n;
+    }
+    const double per = std::max(1.0, lzh_env_num("BZ_LZH_SPLIT_CAND_BYTES", 1024.0));
+    if (ncand > std::max<u64>(64, (u64)(elen / per))) return BZ_OK; // every candidate is a wave that may decode 65 535 codes
+    std::vector<u64> cands((size_t)ncand);
+    if (ncand) {
+        if ((rc = w->s_cand.ensure((size_t)ncand * 8)) != BZ_OK) return rc;
+        HIPCHK(hipMemcpyAsync(d_first, first.data(), (size_t)waves * 4, hipMemcpyHostToDevice, g->st));
+        if (lzh_launch_split_search(g->st, true, ebase, elen, m.dbits, m.pbits, d_cnt, d_first, w->s_cand.as<u64>(), (u32)ncand) != 0)
+            return BZ_E_UNEXPECTED;
+        HIPCHK(hipMemcpyAsync(cands.data(), w->s_cand.p, (size_t)ncand * 8, hipMemcpyDeviceToHost, g->st));
+        HIPCHK(hipStreamSynchronize(g->st));
+        e.launches += 1;
+    }
+    if (!cands.empty() && cands[0] == 0) cands.erase(cands.begin()); // (piece 0 starts there whatever the header says)
+    e.st[1] = cands.size();
+    double t1 = lzh_now_ms();
+    e.ms[0] += t1 - t0;
+    // ---- every piece at once: the entry's first bit and every candidate, each to the next candidate.  Piece 0 knows its place
+    // and the entry's length; the others believe their distances.
+    const bool has_len = ol != kNoLen;
+    const auto limit_of = [&](u64 sum) { return !has_len || ol - sum > 0xFFFFFFFEull ? kNoLimit : (u32)(ol - sum); };
+    std::vector<LzhPiece> pcs(1 + cands.size());
+    for (size_t k = 0; k < pcs.size(); ++k) {
+        LzhPiece &q = pcs[k];
+        q.start = k ? cands[k - 1] : 0;
+        q.stop = k < cands.size() ? cands[k] : kNoStop;
+        q.base = k ? kBaseUnknown : 0u;
+        q.limit = k ? kNoLimit : limit_of(0);
+        q.has_len = k ? 0u : (u32)has_len;
+        q.pad = 0;
+    }
+    std::vector<LzhPieceRec> prs(pcs.size());
+    if ((rc = lzh_split_pieces(g, w, m, ebase, elen, pcs.data(), (u32)pcs.size(), prs.data(), &e.launches)) != BZ_OK) return rc;
+    t0 = lzh_now_ms();
+    e.ms[1] += t0 - t1;
+    // ---- the chain: a candidate's piece counts if and only if the confirmed piece in front of it stopped exactly there.  A
+    // piece is decoded again, alone, with its place and what is left of the known length, where the strict distance rule, the
+    // known length or the 4 GiB guard may end the stream inside it.
+    e.chain.clear();
+    LzhRec total{};
+    u64 sum = 0, j = 0;
+    size_t cur = 0;
+    for (;;) {
+        LzhPiece pc = pcs[cur];
+        LzhPieceRec pr = prs[cur];
+        pc.base = (u32)sum;
+        if (cur != 0) {
+            const u64 left = has_len ? ol - sum : ~0ull; // (sum < ol here: the chain ends where the length is reached)
+            const bool again = (m.prefill < 0 && pr.reach > sum) || pr.r.len > left || (pr.r.len == left && pr.ended) ||
+                               sum + pr.r.len > 0xFFFFFFFFull - 0x200u;
+            if (again) {
+                pc.limit = limit_of(sum);
+                pc.has_len = (u32)has_len;
+                if ((rc = lzh_split_pieces(g, w, m, ebase, elen, &pc, 1, &pr, &e.launches)) != BZ_OK) return rc;
+                e.st[4] += 1;
+            } else if (has_len && pr.ended && pr.r.verdict == BZ_OK && pr.r.len < left) pr.r.verdict = BZ_E_EOF; // the end (a) in front of it
+        }
+        pc.limit = pr.r.len; // (the writing launch)
+        pc.has_len = 0;
+        e.chain.push_back(pc);
+        sum += pr.r.len;
+        total.nblk += pr.r.nblk;
+        total.nlit += pr.r.nlit;
+        total.nmatch += pr.r.nmatch;
+        total.flags |= pr.r.flags;
+        total.end_bit = pr.r.end_bit;
+        total.verdict = pr.r.verdict;
+        if (pr.ended || (has_len && sum >= ol)) break;
+        if (chain_next(cands.data(), cands.size(), PieceEnd{pr.r.end_bit, false}, j) != Next::Confirmed) return BZ_OK; // (the rule is broken)
+        cur = 1 + (size_t)j++;
+    }
+    e.ms[2] += lzh_now_ms() - t0;
+    if (e.chain.size() < 2 || (sum > 0xFFFFFFFFull && !(total.flags & 1u))) return BZ_OK;
+    total.len = (u32)sum;
+    e.rec = total;
+    e.st[0] = 1;
+    e.st[2] = e.chain.size();
+    e.st[3] = pcs.size() - e.chain.size();
+    *fallback = false;
+    return BZ_OK;
+}
+
+// The bytes of one split entry at `eout`: the writing launch over the chain's pieces with its source map, pointer jumping
+// until nothing moves, the gather.
+static int lzh_split_write(bz_gpu_engine *g, LzhWorkspace *w, LzhMethod m, const u8 *ebase, u32 elen, u8 *eout, const LzhSplitEntry &e)
+{
+    const u32 n = e.rec.len, np = (u32)e.chain.size();
+    if (n == 0) return BZ_OK;
+    u32 *map = w->s_map.as<u32>(), *cnt = w->s_jump.as<u32>();
+    int rc = w->s_piece.ensure((size_t)np * sizeof(LzhPiece));
+    if (rc != BZ_OK) return rc;
+    double t0 = lzh_now_ms();
+    HIPCHK(hipMemcpyAsync(w->s_piece.p, e.chain.data(), (size_t)np * sizeof(LzhPiece), hipMemcpyHostToDevice, g->st));
+    if (lzh_launch_decode_piece(g->st, true, ebase, elen, m.dbits, m.pbits, m.prefill, w->s_piece.as<LzhPiece>(), np, nullptr, eout, map) != 0)
+        return BZ_E_UNEXPECTED;
+    HIPCHK(hipStreamSynchronize(g->st));
+    w->stats[7] += 1;
+    double t1 = lzh_now_ms();
+    w->split_ms[3] += t1 - t0;
+    u32 left = 0;
+    for (u32 round = 0;; ++round) {
+        u32 h[2] = {0, 0};
+        HIPCHK(hipMemsetAsync(cnt, 0, 8, g->st));
+        if (df_launch_split_jump(g->st, map, n, cnt) != 0) return BZ_E_UNEXPECTED;
+        HIPCHK(hipMemcpyAsync(h, cnt, 8, hipMemcpyDeviceToHost, g->st));
+        HIPCHK(hipStreamSynchronize(g->st));
+        w->stats[7] += 1;
+        w->split_stats[5] += 1;
+        if (round == 0) left = h[0];
+        if (h[1] == 0) break;
+    }
+    w->split_stats[6] += left;
+    t0 = lzh_now_ms();
+    w->split_ms[4] += t0 - t1;
+    if (left) {
+        if (df_launch_split_gather(g->st, eout, map, n) != 0) return BZ_E_UNEXPECTED;
+        HIPCHK(hipStreamSynchronize(g->st));
+        w->stats[7] += 1;
+    }
+    w->split_ms[5] += lzh_now_ms() - t0;
+    return BZ_OK;
+}
+
 // grow != nullptr: the output is the engine's own buffer, sized between the two launches (the host forms)
 static int lzh_decode_batch_core(bz_gpu_engine *g, int method, int prefill, const void *d_in, const uint64_t *h_in_off, const uint64_t *h_in_len,
                                  const uint64_t *h_orig_len, size_t count, void *d_out, size_t cap, DevBuf *grow, uint64_t *h_out_off,
@@ -68,17 +278,57 @@ static int lzh_decode_batch_core(bz_gpu_engine *g, int method, int prefill, cons
     if (!g->lzh) g->lzh = new LzhWorkspace();
     LzhWorkspace *w = g->lzh;
     for (u64 &s : w->stats) s = 0;
+    for (u64 &s : w->split_stats) s = 0;
+    for (double &s : w->split_ms) s = 0;
+    const u8 *in8 = static_cast<const u8 *>(d_in);
+    const LzhMethod m{dbits, pbits, prefill};
+    // the entries that go across many waves, one after the other; in the launches over all entries they are entries of no bytes
+    const u64 split_min = (u64)(lzh_env_num("BZ_LZH_SPLIT_KIB", 1024.0) * 1024.0);
+    std::vector<LzhSplitEntry> splits;
+    u64 fallbacks = 0;
+    for (size_t i = 0; split_min && i < count; ++i) {
+        if (h_in_len[i] < split_min) continue;
+        LzhSplitEntry e;
+        bool fallback = false;
+        e.index = i;
+        const int src = lzh_split_sizes(g, w, m, in8 + h_in_off[i], (u32)h_in_len[i], h_orig_len ? h_orig_len[i] : kNoLen, e, &fallback);
+        if (src != BZ_OK) return src;
+        if (!fallback && (e.rec.flags & 1u)) return BZ_E_PARAM; // an entry of 4 GiB or more of output
+        w->stats[7] += e.launches;
+        if (fallback) ++fallbacks;
+        else splits.push_back(std::move(e));
+    }
+    // ONE source map for all of them, sized here, before any entry is committed to the split path.  If it cannot be had, every
+    // entry takes the one-wave path (and the failed allocation's error is not the next launch's).
+    if (!splits.empty() && (d_out || grow)) {
+        size_t map_bytes = 0;
+        for (const LzhSplitEntry &e : splits) map_bytes = std::max(map_bytes, (size_t)e.rec.len * 4 + 64);
+        if (w->s_map.ensure(map_bytes) != BZ_OK || w->s_jump.ensure(64) != BZ_OK) {
+            (void)hipGetLastError();
+            fallbacks += splits.size();
+            splits.clear();
+        }
+    }
+    w->split_stats[7] = fallbacks;
+    std::vector<u64> len_small;
+    if (!splits.empty()) {
+        len_small.assign(h_in_len, h_in_len + count);
+        for (const LzhSplitEntry &e : splits) {
+            len_small[e.index] = 0;
+            for (int k = 0; k < 7; ++k) w->split_stats[k] += e.st[k];
+            for (int k = 0; k < 3; ++k) w->split_ms[k] += e.ms[k];
+        }
+    }
     int rc = w->in.ensure(2 * count * sizeof(u64));
     if (rc == BZ_OK) rc = w->olen.ensure(count * sizeof(u64));
     if (rc == BZ_OK) rc = w->ooff.ensure(count * sizeof(u64));
     if (rc == BZ_OK) rc = w->rec.ensure(count * sizeof(LzhRec));
     if (rc != BZ_OK) return rc;
-    const u8 *in8 = static_cast<const u8 *>(d_in);
     u64 *d_off = w->in.as<u64>(), *d_len = d_off + count, *d_ooff = w->ooff.as<u64>();
     u64 *d_olen = h_orig_len ? w->olen.as<u64>() : nullptr;
     LzhRec *d_rec = w->rec.as<LzhRec>();
     HIPCHK(hipMemcpyAsync(d_off, h_in_off, count * sizeof(u64), hipMemcpyHostToDevice, g->st));
-    HIPCHK(hipMemcpyAsync(d_len, h_in_len, count * sizeof(u64), hipMemcpyHostToDevice, g->st));
+    HIPCHK(hipMemcpyAsync(d_len, splits.empty() ? h_in_len : len_small.data(), count * sizeof(u64), hipMemcpyHostToDevice, g->st));
     if (d_olen) HIPCHK(hipMemcpyAsync(d_olen, h_orig_len, count * sizeof(u64), hipMemcpyHostToDevice, g->st));
     // ---- the sizes
     if (lzh_launch_decode(g->st, false, in8, d_off, d_len, d_olen, (u32)count, dbits, pbits, prefill, nullptr, nullptr, d_rec) != 0)
@@ -86,6 +336,7 @@ static int lzh_decode_batch_core(bz_gpu_engine *g, int method, int prefill, cons
     std::vector<LzhRec> rec(count);
     HIPCHK(hipMemcpyAsync(rec.data(), d_rec, count * sizeof(LzhRec), hipMemcpyDeviceToHost, g->st));
     HIPCHK(hipStreamSynchronize(g->st));
+    for (const LzhSplitEntry &e : splits) rec[e.index] = e.rec;
     // the outputs' places: input order, each at a multiple of 16
     u64 cursor = 0, need = 0;
     for (size_t i = 0; i < count; ++i) {
@@ -108,8 +359,10 @@ static int lzh_decode_batch_core(bz_gpu_engine *g, int method, int prefill, cons
         if (lzh_launch_decode(g->st, true, in8, d_off, d_len, d_olen, (u32)count, dbits, pbits, prefill, out8, d_ooff, d_rec) != 0)
             return BZ_E_UNEXPECTED;
         HIPCHK(hipStreamSynchronize(g->st));
-        w->stats[7] = 2;
-    } else w->stats[7] = 1;
+        w->stats[7] += 2;
+        for (const LzhSplitEntry &e : splits)
+            if ((rc = lzh_split_write(g, w, m, in8 + h_in_off[e.index], (u32)h_in_len[e.index], out8 + h_out_off[e.index], e)) != BZ_OK) return rc;
+    } else w->stats[7] += 1;
     for (size_t i = 0; i < count; ++i) {
         const LzhRec &q = rec[i];
         w->stats[q.verdict == BZ_OK ? 0 : 1] += 1;
