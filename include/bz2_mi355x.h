@@ -1217,6 +1217,88 @@ int bz_gpu_lzh_debug_codes(bz_gpu_engine *g, int method, const void *d_in, size_
 int bz_gpu_lzh_debug_tables(bz_gpu_engine *g, int method, const uint32_t *c_freq, const uint32_t *p_freq, uint8_t *c_len,
                             uint8_t *p_len, uint8_t *t_len, uint32_t res[3]);
 
+/* ========================================================================
+ * 11. LHA ARCHIVES (.lzh / .lha), READING: the member table on the host, the
+ *     bytes of all members or of a chosen subset in one device call, every
+ *     member with its own verdict and its CRC-16 checked on the device.
+ *
+ * The header rules (levels 0, 1 and 2; DESIGN_lzhuf.md section 12 has the
+ * table) stand in csrc/lha_archive.h alone.  Methods: -lh4- .. -lh7- are
+ * decoded by section 9's call, -lh0- and -lz4- are stored, -lhd- is a directory
+ * (no data, clean without a launch); any other id of the form -???- is listed
+ * with BZ_LHA_OTHER and reads as BZ_E_UNEXPECTED without bytes.  Header level 3
+ * and the 64-bit size extension are not read.
+ * ======================================================================== */
+#define BZ_LHA_STORED 0
+#define BZ_LHA_DIR 1
+#define BZ_LHA_LH4 4 /* .. BZ_LHA_LH7 7: BZ_LZH_LH4 .. BZ_LZH_LH7 */
+#define BZ_LHA_LH5 5
+#define BZ_LHA_LH6 6
+#define BZ_LHA_LH7 7
+#define BZ_LHA_OTHER 255
+typedef struct bz_lha_member {
+    uint64_t header_off; /* where the member's header starts in the archive */
+    uint64_t data_off;   /* where its data starts */
+    uint64_t packed_len; /* bytes of data */
+    uint64_t orig_len;   /* bytes it stands for */
+    uint64_t name_off;   /* the name's bytes in the archive (a type-0x01 extended header's when there is one), raw */
+    uint64_t dir_off;    /* the directory's (type 0x02, components separated by 0xFF) */
+    uint32_t name_len, dir_len;
+    uint32_t mtime;      /* levels 0 and 1: MS-DOS time and date; level 2: Unix time; raw */
+    uint16_t crc16;      /* CRC-16/ARC of the original bytes */
+    uint8_t method;      /* BZ_LHA_* */
+    uint8_t level;
+    uint8_t os_id;       /* levels 1 and 2; level 0: 0 */
+    uint8_t attr;        /* raw */
+    uint8_t method_id[5];
+    uint8_t pad;
+} bz_lha_member;
+/* The member table, on the host alone (never BZ_E_NOGPU).  At most cap records are written; members == NULL counts.
+ * *count: the members found.  *fault: BZ_OK when the archive ends cleanly (at in_len, or at a header position that holds a
+ * 0 byte; bytes behind that are ignored), else the verdict that ended the walk and *fault_pos the header it lies in:
+ * BZ_E_EOF, a header or a member's data needs a byte behind in_len; BZ_E_DATA, a wrong byte sum (levels 0, 1) or header
+ * CRC (level 2), a level above 2, a method id not of the form -???-, a header size below what its fields need, an extended
+ * header of size 1 or 2, a level-1 skip size below its extended headers.  The table lists every member in front of the
+ * fault; a member whose data is cut by the end of the archive is listed too (it reads as BZ_E_EOF).  Returns BZ_OK, or
+ * BZ_E_PARAM (a null count, fault or fault_pos; in null with in_len > 0). */
+int bz_lha_index_buffer(const uint8_t *in, size_t in_len, bz_lha_member *members, size_t cap, size_t *count, int32_t *fault,
+                        uint64_t *fault_pos);
+/* The members h_sel[0 .. nsel) (indices into h_members[0 .. nmembers), strictly ascending; NULL: all, nsel == nmembers) of
+ * the archive d_in[0 .. in_len) (HBM, 16-byte aligned).  Selected members are grouped by method: one gather of their spans
+ * (they lie at any byte phase) and ONE call into section 9's decode path per method present, with the members' original
+ * lengths and `prefill` (section 9 (e); LHA's encoders match against a window of spaces, so the archive-shaped wrappers
+ * default to 0x20); the split path (g), its fallbacks and BZ_LZH_SPLIT_KIB apply as there.  Stored members are copied.
+ * Then ONE CRC-16 launch (parts of BZ_LHA_CRC_PART_KIB KiB, default 1024, read per call) and its join run over all clean
+ * members of the call.
+ * Member k of the selection lies at h_out_off[k], a multiple of 16, in selection order: its slot is its header's original
+ * length rounded up to 16 (no bytes for a directory, a BZ_LHA_OTHER member, a stored member whose sizes differ, a member
+ * whose data is cut), so the places are known before any launch: cap must reach the end of the last slot's original
+ * length, else BZ_E_CAPACITY with d_out untouched.  h_out_len[k] is what was produced (the original length for a clean
+ * member).  NOTHING outside the reported ranges is written.  d_out == NULL: sizes and verdicts only (no CRC: a member
+ * that decodes is reported clean).
+ * h_verdict[k]: BZ_OK only when the member's bytes are whole and their CRC-16 is the header's; BZ_E_DATA: the decoder's
+ * (section 9 (d)), a stored member whose packed and original sizes differ, or a CRC mismatch (the bytes are there);
+ * BZ_E_EOF: the decoder's, a stream that ends short of the original length (section 9 (b)), or data cut by the end of
+ * the archive; BZ_E_UNEXPECTED: a method that is not decoded.  No member's verdict or bytes change another's; the
+ * return value is the infrastructure status.
+ * BZ_E_PARAM, before any device is touched: a null engine, a null array with nsel > 0, a misaligned d_in or d_out, a
+ * selection out of order or out of range, a record whose header or data starts behind in_len or whose packed or
+ * original length is 4 GiB or more, a prefill outside -1 .. 255.  nsel == 0: BZ_OK, nothing touched. */
+int bz_gpu_lha_read_device(bz_gpu_engine *g, const void *d_in, size_t in_len, const bz_lha_member *h_members, size_t nmembers,
+                           const size_t *h_sel, size_t nsel, int prefill, void *d_out, size_t cap, uint64_t *h_out_off,
+                           uint64_t *h_out_len, int32_t *h_verdict);
+/* The last bz_gpu_lha_read_device call: [0] members read clean [1] with an error verdict [2] stored [3] directories
+ * [4] not decodable (BZ_E_UNEXPECTED) [5] CRC mismatches [6] bytes out [7] kernel launches.  (Section 9's figures are
+ * those of the call's last decode call.) */
+int bz_gpu_last_lha_read_stats(bz_gpu_engine *g, uint64_t out[8]);
+/* The host form (the shape of bz_lzh_decode_batch): the table is built here, one upload, one device call on an engine of
+ * the per-process cache, one download; *out is ONE malloc'ed buffer (bz_free), member k of the selection at out_off[k].
+ * sel == NULL: all members, and nsel must be their count (bz_lha_index_buffer).  *fault: the index's verdict; the members
+ * in front of it are read.  The parameters are checked before any device is touched; nsel == 0: BZ_OK, an empty buffer,
+ * no device.  Without a GPU: BZ_E_NOGPU. */
+int bz_lha_read_buffer(int device, const uint8_t *in, size_t in_len, const size_t *sel, size_t nsel, int prefill, uint8_t **out,
+                       uint64_t *out_off, uint64_t *out_len, int32_t *verdict, int32_t *fault);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@ include/bz2_mi355x.h) loaded with ctypes.  There is no CPU implementation in thi
 library or a gfx950 device is missing, calls raise.  PyTorch is used only by GpuEngine's callers
 for device memory (tensor.data_ptr()); nothing here imports torch.
 """
+import collections
 import ctypes as C
 import enum
 import os
@@ -29,7 +30,7 @@ import sys
 from . import _build
 
 __all__ = ["Action", "CompressionError", "BZip2Error", "BZip2Encoder", "BZip2Decoder", "encode", "decode",
-           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "deflate_decompress", "deflate_decompress_batch", "Deflater", "ZlibDecoder", "GZipDecoder", "gzip_decompress_members", "MultiGZipDecoder", "bgzf_compress", "bgzf_bound", "bgzf_block_count", "BgzfIndex", "bgzf_index", "bgzf_decompress", "bgzf_read", "LzhufMethod", "LzhufDecoder", "lzhuf_decompress", "lzhuf_decompress_batch", "LzhufEncoder", "lzhuf_compress", "lzhuf_compress_batch", "lzhuf_encode_batch_bound", "GpuEngine", "release_cached_resources", "last_call_phases",
+           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "deflate_decompress", "deflate_decompress_batch", "Deflater", "ZlibDecoder", "GZipDecoder", "gzip_decompress_members", "MultiGZipDecoder", "bgzf_compress", "bgzf_bound", "bgzf_block_count", "BgzfIndex", "bgzf_index", "bgzf_decompress", "bgzf_read", "LzhufMethod", "LzhufDecoder", "lzhuf_decompress", "lzhuf_decompress_batch", "LzhufEncoder", "lha_index", "lha_extract", "LhaArchive", "LhaIndex", "LhaMember", "lzhuf_compress", "lzhuf_compress_batch", "lzhuf_encode_batch_bound", "GpuEngine", "release_cached_resources", "last_call_phases",
            "build", "lib", "device_count", "encode_bound", "shard_window", "rccl_lib", "rccl_unique_id", "RcclComm"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -107,6 +108,7 @@ EXPORTS = [
     "bz_gpu_last_lzh_decode_split_stats", "bz_gpu_last_lzh_decode_split_timings",
     "bz_gpu_lzh_encode_batch_device", "bz_gpu_last_lzh_encode_stats", "bz_lzh_encode_batch_bound", "bz_lzh_encode_batch",
     "bz_lzh_encode_buffer", "bz_gpu_lzh_debug_codes", "bz_gpu_lzh_debug_tables",
+    "bz_lha_index_buffer", "bz_gpu_lha_read_device", "bz_gpu_last_lha_read_stats", "bz_lha_read_buffer",
 ]
 
 
@@ -300,6 +302,10 @@ def lib():
     L.bz_lzh_encode_buffer.argtypes = [C.c_int, C.c_int, C.c_char_p, sz, C.POINTER(u8p), szp]
     L.bz_gpu_lzh_debug_codes.argtypes = [vp, C.c_int, vp, sz, C.POINTER(C.c_uint32), sz, szp]
     L.bz_gpu_lzh_debug_tables.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u8p, u8p, u8p, C.POINTER(C.c_uint32)]
+    L.bz_lha_index_buffer.argtypes = [C.c_char_p, sz, vp, sz, szp, i32p, u64p]
+    L.bz_gpu_lha_read_device.argtypes = [vp, vp, sz, vp, sz, szp, sz, C.c_int, vp, sz, u64p, u64p, i32p]
+    L.bz_gpu_last_lha_read_stats.argtypes = [vp, u64p]
+    L.bz_lha_read_buffer.argtypes = [C.c_int, C.c_char_p, sz, szp, sz, C.c_int, C.POINTER(u8p), u64p, u64p, i32p, i32p]
     _LIB = L
     return L
 
@@ -1269,6 +1275,108 @@ class LzhufEncoder:
         return self.read_all()
 
 
+# ---- LHA archives (section 11 of the header): the member table on the host, every member's bytes in one device call
+class _LhaMemberRec(C.Structure):
+    """bz_lha_member"""
+    _fields_ = [("header_off", C.c_uint64), ("data_off", C.c_uint64), ("packed_len", C.c_uint64), ("orig_len", C.c_uint64),
+                ("name_off", C.c_uint64), ("dir_off", C.c_uint64), ("name_len", C.c_uint32), ("dir_len", C.c_uint32),
+                ("mtime", C.c_uint32), ("crc16", C.c_uint16), ("method", C.c_uint8), ("level", C.c_uint8), ("os_id", C.c_uint8),
+                ("attr", C.c_uint8), ("method_id", C.c_uint8 * 5), ("pad", C.c_uint8)]
+
+
+LhaMember = collections.namedtuple("LhaMember", "name directory method level packed_len orig_len crc16 mtime os_id data_off header_off attr")
+LhaMember.__doc__ = """One member of an LHA archive: `name` and `directory` are raw bytes (a directory's components are
+separated by 0xFF), `method` the five bytes of its id (b"-lh5-"), `mtime` the header's raw time field."""
+
+
+class LhaIndex(tuple):
+    """The members of an archive in its order, and `.fault`: BZ_OK when the archive ends cleanly, else (verdict, position of
+    the header the fault lies in); the members in front of the fault are listed."""
+    fault = BZ_OK
+    _records = None
+
+
+def lha_index(data):
+    """The member table of an LHA archive (bz_lha_index_buffer; the host alone, no GPU) -> LhaIndex."""
+    data = bytes(data)
+    L = lib()
+    n, fault, pos = C.c_size_t(0), C.c_int32(0), C.c_uint64(0)
+    _check(L.bz_lha_index_buffer(data, len(data), None, 0, C.byref(n), C.byref(fault), C.byref(pos)))
+    recs = (_LhaMemberRec * max(n.value, 1))()
+    _check(L.bz_lha_index_buffer(data, len(data), recs, n.value, C.byref(n), C.byref(fault), C.byref(pos)))
+    idx = LhaIndex(LhaMember(data[r.name_off:r.name_off + r.name_len], data[r.dir_off:r.dir_off + r.dir_len], bytes(r.method_id), r.level,
+                             r.packed_len, r.orig_len, r.crc16, r.mtime, r.os_id, r.data_off, r.header_off, r.attr)
+                   for r in recs[:n.value])
+    idx.fault = BZ_OK if fault.value == BZ_OK else (int(fault.value), int(pos.value))
+    idx._records = recs
+    return idx
+
+
+def _lha_selection(index, members):
+    """indices (ascending, as the C call wants them) of `members`: None (all), or indices and names (the first member of that
+    name) in any order -> (sorted indices, the position of each request in them)"""
+    if members is None:
+        return None, list(range(len(index)))
+    want = []
+    for m in members:
+        if isinstance(m, (bytes, bytearray, str)):
+            name = m.encode() if isinstance(m, str) else bytes(m)
+            hits = [i for i, q in enumerate(index) if q.name == name]
+            if not hits:
+                raise KeyError(m)
+            want.append(hits[0])
+        else:
+            i = int(m)
+            if not 0 <= i < len(index):
+                raise IndexError("no member %d" % i)
+            want.append(i)
+    order = sorted(set(want))
+    return order, [order.index(i) for i in want]
+
+
+def lha_extract(data, members=None, prefill=0x20, device=0, check=False):
+    """The bytes of the members of an LHA archive in one call (bz_lha_read_buffer) -> list of (bytes, verdict), one per
+    request: members = None (all), or indices and names.  A member is BZ_OK only when its CRC-16 is its header's.
+    check=True: the first verdict that is not BZ_OK is raised as CompressionError."""
+    data = bytes(data)
+    index = lha_index(data)
+    order, pos = _lha_selection(index, members)
+    k = len(index) if order is None else len(order)
+    sel = None if order is None else (C.c_size_t * max(k, 1))(*order)
+    off, ln, v = (C.c_uint64 * max(k, 1))(), (C.c_uint64 * max(k, 1))(), (C.c_int32 * max(k, 1))()
+    out = C.POINTER(C.c_uint8)()
+    fault = C.c_int32(0)
+    if not -1 <= int(prefill) <= 255:
+        raise ValueError("prefill must be -1 (strict) or a byte value")
+    _check(lib().bz_lha_read_buffer(device, data, len(data), sel, k, int(prefill), C.byref(out), off, ln, v, C.byref(fault)))
+    try:
+        base = C.addressof(out.contents) if k else 0
+        res = [(C.string_at(base + off[j], ln[j]), int(v[j])) for j in pos]
+    finally:
+        lib().bz_free(out)
+    if check:
+        for _, verdict in res:
+            if verdict != BZ_OK:
+                raise CompressionError(verdict)
+    return res
+
+
+class LhaArchive:
+    """An LHA archive in host memory: `.members` (LhaIndex), `.read(index or name)` -> (bytes, verdict), `.read_all()`.
+    Creating one builds the table on the host and does not touch the device."""
+
+    def __init__(self, data, prefill=0x20, device=0):
+        self._data = bytes(data)
+        self._prefill, self._device = prefill, device
+        self.members = lha_index(self._data)
+
+    def read(self, member):
+        return lha_extract(self._data, [member], self._prefill, self._device)[0]
+
+    def read_all(self):
+        return lha_extract(self._data, None, self._prefill, self._device)
+
+
 class GpuEngine:
     """Device-resident engine (section 2 of the C ABI).  Pointers are plain ints
     (e.g. torch.Tensor.data_ptr())."""
@@ -1606,6 +1714,29 @@ class GpuEngine:
         """The last lzh_decode_batch_device call, in the order of LZH_DECODE_STATS (bz_gpu_last_lzh_decode_stats)."""
         s = (C.c_uint64 * 8)()
         _check(lib().bz_gpu_last_lzh_decode_stats(self._h, s))
+        return [int(x) for x in s]
+
+    LHA_READ_STATS = ("clean", "errors", "stored", "directories", "not_decodable", "crc_mismatches", "bytes_out", "launches")
+
+    def lha_read_device(self, d_in, in_len, index, d_out, cap, members=None, prefill=0x20):
+        """Members of the LHA archive at d_in (in_len bytes of device memory, 16-byte aligned) in one call
+        (bz_gpu_lha_read_device; section 11 of the header).  index: what lha_index gave for the same bytes; members: None
+        (all) or ascending indices.  Returns (out_off, out_len, verdicts) in selection order, member k's bytes at d_out +
+        out_off[k].  d_out = None: sizes and verdicts only."""
+        _settle()
+        n = len(index)
+        k = n if members is None else len(members)
+        sel = None if members is None else (C.c_size_t * max(k, 1))(*members)
+        o_off = (C.c_uint64 * max(k, 1))()
+        o_len = (C.c_uint64 * max(k, 1))()
+        verdicts = (C.c_int32 * max(k, 1))()
+        _check(lib().bz_gpu_lha_read_device(self._h, d_in, in_len, index._records, n, sel, k, int(prefill), d_out, cap, o_off, o_len, verdicts))
+        return list(o_off[:k]), list(o_len[:k]), [int(v) for v in verdicts[:k]]
+
+    def lha_read_stats(self):
+        """The last lha_read_device call, in the order of LHA_READ_STATS (bz_gpu_last_lha_read_stats)."""
+        s = (C.c_uint64 * 8)()
+        _check(lib().bz_gpu_last_lha_read_stats(self._h, s))
         return [int(x) for x in s]
 
     LZH_DECODE_SPLIT_STATS = ("entries_split", "candidates", "chain_pieces", "false_pieces", "pieces_decoded_again", "jump_rounds",

@@ -247,6 +247,7 @@ extern "C" void bz_gpu_engine_destroy(bz_gpu_engine *g)
     dec_workspace_free(g->dec);
     df_workspace_free(g->df);
     lzh_workspace_free(g->lzh);
+    lha_workspace_free(g->lha);
     if (g->h_active) (void)hipHostFree(g->h_active);
     mail_release(g->st);
     mail_release(g->st2);

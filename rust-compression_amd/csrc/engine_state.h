@@ -24,6 +24,13 @@ struct DfWorkspace;
 void df_workspace_free(DfWorkspace *w);
 struct LzhWorkspace;
 void lzh_workspace_free(LzhWorkspace *w);
+// bz_gpu_lzh_decode_batch_device with the outputs' places given by the caller (lzhuf_engine.hip; every entry has a known
+// original length, and h_place[i], a multiple of 16, has room for it)
+int lzh_decode_batch_placed(struct bz_gpu_engine *g, int method, int prefill, const void *d_in, const uint64_t *h_in_off, const uint64_t *h_in_len,
+                            const uint64_t *h_orig_len, size_t count, void *d_out, size_t cap, const uint64_t *h_place, uint64_t *h_out_len,
+                            int32_t *h_verdict);
+struct LhaWorkspace;
+void lha_workspace_free(LhaWorkspace *w);
 
 #define HIPCHK(x)                                                                                     \
     do {                                                                                              \
@@ -111,5 +118,6 @@ struct bz_gpu_engine {
     DevBuf dec_in, oneshot_out;  // bz_decode_buffer / df_encode_buffer: the caller's bytes on the device and the result (kept with the cached engine)
     DfWorkspace *df = nullptr;   // Deflate encode workspace, created by the first df_gpu_encode_device call
     LzhWorkspace *lzh = nullptr; // LZHUF decode workspace, created by the first bz_gpu_lzh_decode_batch_device call
+    LhaWorkspace *lha = nullptr; // LHA archive reader's workspace, created by the first bz_gpu_lha_read_device call
 };
 

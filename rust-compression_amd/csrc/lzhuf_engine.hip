@@ -258,10 +258,12 @@ static int lzh_split_write(bz_gpu_engine *g, LzhWorkspace *w, LzhMethod m, const
     return BZ_OK;
 }
 
-// grow != nullptr: the output is the engine's own buffer, sized between the two launches (the host forms)
+// grow != nullptr: the output is the engine's own buffer, sized between the two launches (the host forms).
+// h_place != nullptr: the caller has places for the outputs (multiples of 16, disjoint, entry i with room for h_orig_len[i]
+// bytes, which it then must have): the archive reader's members lie in its own order among those of other calls.
 static int lzh_decode_batch_core(bz_gpu_engine *g, int method, int prefill, const void *d_in, const uint64_t *h_in_off, const uint64_t *h_in_len,
-                                 const uint64_t *h_orig_len, size_t count, void *d_out, size_t cap, DevBuf *grow, uint64_t *h_out_off,
-                                 uint64_t *h_out_len, int32_t *h_verdict)
+                                 const uint64_t *h_orig_len, size_t count, void *d_out, size_t cap, DevBuf *grow, const uint64_t *h_place,
+                                 uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_verdict)
 {
     u32 dbits = 0, pbits = 0;
     if (!g || !lzh_method(method, dbits, pbits) || prefill < -1 || prefill > 255) return BZ_E_PARAM;
@@ -274,6 +276,8 @@ static int lzh_decode_batch_core(bz_gpu_engine *g, int method, int prefill, cons
         in_end = h_in_off[i] + h_in_len[i];
     }
     if (in_end && !d_in) return BZ_E_PARAM;
+    for (size_t i = 0; h_place && i < count; ++i)
+        if (!h_orig_len || h_orig_len[i] == kNoLen || (h_place[i] & 15u)) return BZ_E_PARAM;
     HIPCHK(hipSetDevice(g->device));
     if (!g->lzh) g->lzh = new LzhWorkspace();
     LzhWorkspace *w = g->lzh;
@@ -341,10 +345,10 @@ static int lzh_decode_batch_core(bz_gpu_engine *g, int method, int prefill, cons
     u64 cursor = 0, need = 0;
     for (size_t i = 0; i < count; ++i) {
         if (rec[i].flags & 1u) return BZ_E_PARAM; // an entry of 4 GiB or more of output
-        h_out_off[i] = cursor;
+        h_out_off[i] = h_place ? h_place[i] : cursor;
         h_out_len[i] = rec[i].len;
         h_verdict[i] = rec[i].verdict;
-        need = cursor + rec[i].len;
+        need = std::max(need, h_out_off[i] + rec[i].len);
         cursor += ((u64)rec[i].len + 15u) & ~(u64)15;
     }
     u8 *out8 = static_cast<u8 *>(d_out);
@@ -379,7 +383,17 @@ extern "C" int bz_gpu_lzh_decode_batch_device(bz_gpu_engine *g, int method, int 
                                               const uint64_t *h_in_len, const uint64_t *h_orig_len, size_t count, void *d_out, size_t cap,
                                               uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_verdict)
 {
-    return lzh_decode_batch_core(g, method, prefill, d_in, h_in_off, h_in_len, h_orig_len, count, d_out, cap, nullptr, h_out_off, h_out_len,
+    return lzh_decode_batch_core(g, method, prefill, d_in, h_in_off, h_in_len, h_orig_len, count, d_out, cap, nullptr, nullptr, h_out_off, h_out_len,
+                                 h_verdict);
+}
+
+// The same call with the outputs' places given (lha_engine.hip: one call per method of an archive's members).
+int lzh_decode_batch_placed(bz_gpu_engine *g, int method, int prefill, const void *d_in, const uint64_t *h_in_off, const uint64_t *h_in_len,
+                            const uint64_t *h_orig_len, size_t count, void *d_out, size_t cap, const uint64_t *h_place, uint64_t *h_out_len,
+                            int32_t *h_verdict)
+{
+    std::vector<uint64_t> off(count);
+    return lzh_decode_batch_core(g, method, prefill, d_in, h_in_off, h_in_len, h_orig_len, count, d_out, cap, nullptr, h_place, off.data(), h_out_len,
                                  h_verdict);
 }
 
@@ -412,7 +426,7 @@ extern "C" int bz_lzh_decode_batch(int method, int prefill, int device, const ui
         rc = BZ_E_UNEXPECTED;
     if (rc == BZ_OK)
         rc = lzh_decode_batch_core(g, method, prefill, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), orig_lens, count, nullptr, 0,
-                                   &g->oneshot_out, out_off, out_len, verdict);
+                                   &g->oneshot_out, nullptr, out_off, out_len, verdict);
     if (rc == BZ_OK) {
         const size_t total = (size_t)(out_off[count - 1] + out_len[count - 1]);
         uint8_t *h = (uint8_t *)malloc(total ? total : 1);

@@ -659,6 +659,55 @@ class LzhufEncoder {
     size_t pos_ = 0;
 };
 
+// LHA archives (include/bz2_mi355x.h section 11): the member table on the host (bz_lha_index_buffer, no GPU), and the bytes
+// of all members or of a chosen subset in one call (bz_lha_read_buffer), every member with its own verdict (clean only when
+// its CRC-16 is its header's).
+struct LhaIndex {
+    std::vector<bz_lha_member> members;
+    int fault = BZ_OK;      // BZ_OK: the archive ends cleanly; else the verdict that ended the walk
+    uint64_t fault_pos = 0; // ... and the header it lies in
+};
+inline Result<LhaIndex> lha_index(const uint8_t *in, size_t n)
+{
+    using R = Result<LhaIndex>;
+    LhaIndex idx;
+    size_t count = 0;
+    int32_t fault = BZ_OK;
+    int rc = bz_lha_index_buffer(in, n, nullptr, 0, &count, &fault, &idx.fault_pos);
+    if (rc != BZ_OK) return R::Err(from_status(rc));
+    idx.members.resize(count);
+    rc = bz_lha_index_buffer(in, n, idx.members.data(), count, &count, &fault, &idx.fault_pos);
+    if (rc != BZ_OK) return R::Err(from_status(rc));
+    idx.fault = fault;
+    return R::Ok(std::move(idx));
+}
+// sel: ascending member indices; empty with `all`: every member of the table
+inline Result<std::vector<LzhufDecoder::Entry>> lha_read(const uint8_t *in, size_t n, const std::vector<size_t> &sel = {}, bool all = true,
+                                                        int prefill = 0x20, int device = 0)
+{
+    using R = Result<std::vector<LzhufDecoder::Entry>>;
+    size_t count = sel.size();
+    if (all && sel.empty()) {
+        auto idx = lha_index(in, n);
+        if (!idx.ok) return R::Err(idx.error);
+        count = idx.value.members.size();
+    }
+    std::vector<uint64_t> off(count), len(count);
+    std::vector<int32_t> verdict(count);
+    uint8_t *out = nullptr;
+    int32_t fault = BZ_OK;
+    const int rc = bz_lha_read_buffer(device, in, n, sel.empty() && all ? nullptr : sel.data(), count, prefill, &out, off.data(), len.data(),
+                                      verdict.data(), &fault);
+    if (rc != BZ_OK) return R::Err(from_status(rc));
+    std::vector<LzhufDecoder::Entry> entries(count);
+    for (size_t i = 0; i < count; ++i) {
+        entries[i].bytes.assign(out + off[i], out + off[i] + len[i]);
+        if (verdict[i] != BZ_OK) entries[i].error = from_status(verdict[i]);
+    }
+    bz_free(out);
+    return R::Ok(std::move(entries));
+}
+
 // One input as a BGZF file (include/bz2_mi355x.h section 7, df_bgzf_encode_buffer): gzip members of at most block_bytes
 // (0: 65 280) input bytes side by side, then the 28-byte EOF marker unless eof is false.  The reference has no such writer;
 // every member is a stream that zlib, gzip(1) and htslib read.  block_off, when not null, receives the file offset of every

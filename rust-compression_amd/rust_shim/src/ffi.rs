@@ -16,6 +16,28 @@ pub const DF_KIND_DEFLATE: i32 = 0;
 pub const DF_KIND_ZLIB: i32 = 1;
 pub const DF_KIND_GZIP: i32 = 2;
 
+/// `bz_lha_member`: one member of an LHA archive as `bz_lha_index_buffer` lists it (72 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct LhaMember {
+    pub header_off: u64,
+    pub data_off: u64,
+    pub packed_len: u64,
+    pub orig_len: u64,
+    pub name_off: u64,
+    pub dir_off: u64,
+    pub name_len: u32,
+    pub dir_len: u32,
+    pub mtime: u32,
+    pub crc16: u16,
+    pub method: u8, // 0 stored, 1 directory, 4 .. 7 -lh4- .. -lh7-, 255 not decodable
+    pub level: u8,
+    pub os_id: u8,
+    pub attr: u8,
+    pub method_id: [u8; 5],
+    pub pad: u8,
+}
+
 extern "C" {
     pub fn bz_device_count() -> i32;
     pub fn bz_strerror(code: i32) -> *const core::ffi::c_char;
@@ -84,6 +106,12 @@ extern "C" {
     // (test hooks: the LZSS codes of one input; the block stage's table builder on given counts)
     pub fn bz_gpu_lzh_debug_codes(g: *mut c_void, method: i32, d_in: *const c_void, n: usize, out_pairs: *mut u32, cap: usize, count: *mut usize) -> i32;
     pub fn bz_gpu_lzh_debug_tables(g: *mut c_void, method: i32, c_freq: *const u32, p_freq: *const u32, c_len: *mut u8, p_len: *mut u8, t_len: *mut u8, res: *mut u32) -> i32;
+
+    // section 11: LHA archives, reading (members: *mut / *const LhaMember, the C struct bz_lha_member)
+    pub fn bz_lha_index_buffer(input: *const u8, in_len: usize, members: *mut LhaMember, cap: usize, count: *mut usize, fault: *mut i32, fault_pos: *mut u64) -> i32;
+    pub fn bz_gpu_lha_read_device(g: *mut c_void, d_in: *const c_void, in_len: usize, h_members: *const LhaMember, nmembers: usize, h_sel: *const usize, nsel: usize, prefill: i32, d_out: *mut c_void, cap: usize, h_out_off: *mut u64, h_out_len: *mut u64, h_verdict: *mut i32) -> i32;
+    pub fn bz_gpu_last_lha_read_stats(g: *mut c_void, out: *mut u64) -> i32;
+    pub fn bz_lha_read_buffer(device: i32, input: *const u8, in_len: usize, sel: *const usize, nsel: usize, prefill: i32, out: *mut *mut u8, out_off: *mut u64, out_len: *mut u64, verdict: *mut i32, fault: *mut i32) -> i32;
 
     // section 6: every member of a gzip file (MultiGZipDecoder)
     pub fn df_gpu_decode_members_device(g: *mut c_void, d_in: *const c_void, in_len: usize, d_out: *mut c_void, cap: usize, out_len: *mut u64, verdict: *mut i32) -> i32;

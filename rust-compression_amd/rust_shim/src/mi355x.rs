@@ -276,6 +276,60 @@ pub fn lzh_encode_batch(method: crate::lzhuf::LzhufMethod, inputs: &[&[u8]]) -> 
     Ok(streams)
 }
 
+/// The member table of an LHA archive (`bz_lha_index_buffer`; the host alone, no GPU): the members in front of the first
+/// fault, and the fault as `Some((verdict, position of its header))` when the archive does not end cleanly.
+#[cfg(feature = "lzhuf")]
+pub fn lha_index(archive: &[u8]) -> Result<(Vec<ffi::LhaMember>, Option<(CompressionError, u64)>), CompressionError> {
+    let (mut count, mut fault, mut pos) = (0usize, 0i32, 0u64);
+    let rc = unsafe { ffi::bz_lha_index_buffer(archive.as_ptr(), archive.len(), core::ptr::null_mut(), 0, &mut count, &mut fault, &mut pos) };
+    if rc != ffi::BZ_OK {
+        note_status(rc);
+        return Err(CompressionError::from_status(rc));
+    }
+    let mut members: Vec<ffi::LhaMember> = Vec::new();
+    members.resize(count, ffi::LhaMember::default());
+    let rc = unsafe { ffi::bz_lha_index_buffer(archive.as_ptr(), archive.len(), members.as_mut_ptr(), count, &mut count, &mut fault, &mut pos) };
+    if rc != ffi::BZ_OK {
+        note_status(rc);
+        return Err(CompressionError::from_status(rc));
+    }
+    Ok((members, if fault == ffi::BZ_OK { None } else { Some((CompressionError::from_status(fault), pos)) }))
+}
+
+/// Members of an LHA archive in one call (`bz_lha_read_buffer`, device 0, a window of spaces): `sel` holds ascending member
+/// indices, `None` reads all.  Element `k` is `Ok(bytes)` only when the member's CRC-16 is its header's, else the error with
+/// the bytes that exist.  The outer `Err` is an infrastructure failure (`last_status` says which).
+#[cfg(feature = "lzhuf")]
+pub fn lha_read(archive: &[u8], sel: Option<&[usize]>) -> Result<Vec<Result<Vec<u8>, (CompressionError, Vec<u8>)>>, CompressionError> {
+    let count = match sel {
+        Some(s) => s.len(),
+        None => lha_index(archive)?.0.len(),
+    };
+    let mut off: Vec<u64> = Vec::new();
+    off.resize(count, 0);
+    let mut len = off.clone();
+    let mut verdict: Vec<i32> = Vec::new();
+    verdict.resize(count, 0);
+    let mut out: *mut u8 = core::ptr::null_mut();
+    let mut fault = 0i32;
+    let sel_ptr = sel.map_or(core::ptr::null(), |s| s.as_ptr());
+    let rc = unsafe {
+        ffi::bz_lha_read_buffer(0, archive.as_ptr(), archive.len(), sel_ptr, count, 0x20, &mut out, off.as_mut_ptr(), len.as_mut_ptr(), verdict.as_mut_ptr(), &mut fault)
+    };
+    if rc != ffi::BZ_OK {
+        note_status(rc);
+        return Err(CompressionError::from_status(rc));
+    }
+    let entries = (0..count)
+        .map(|i| {
+            let bytes = unsafe { core::slice::from_raw_parts(out.add(off[i] as usize), len[i] as usize) }.to_vec();
+            if verdict[i] == ffi::BZ_OK { Ok(bytes) } else { Err((CompressionError::from_status(verdict[i]), bytes)) }
+        })
+        .collect();
+    unsafe { ffi::bz_free(out as *mut core::ffi::c_void) };
+    Ok(entries)
+}
+
 pub(crate) fn note_status(rc: i32) {
     if rc != 0 {
         LAST_STATUS.store(rc, Ordering::Relaxed);
