@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libbz2_mi355x.so")
 SOURCES = ["k_rle1.hip", "k_bwt.hip", "k_mtf.hip", "k_huff.hip", "k_emit.hip", "k_dec.hip", "k_deflate.hip", "k_inflate.hip", "k_gz_members.hip", "k_bgzf_read.hip", "k_lzhuf.hip", "k_lha.hip", "engine.hip", "engine_cache.hip", "dec_engine.hip", "deflate_engine.hip", "lzhuf_engine.hip", "lha_engine.hip", "capi.hip"]
-HEADERS = ["bzgpu.h", "engine_state.h", "dev_buf.h", "host_call.h", "copy_pool.h", "bz2_rnums.h", "dec_chain.h", "inf_split.h", "gz_members.h", "bgzf_index.h", "k_deflate.h", "k_df_fold.h", "k_lzhuf.h", "lzh_split.h", "k_lha.h", "lha_archive.h", os.path.join("..", "..", "include", "bz2_mi355x.h")]
+HEADERS = ["bzgpu.h", "engine_state.h", "dev_buf.h", "host_call.h", "one_shot.h", "batch_decode.h", "copy_pool.h", "bz2_rnums.h", "dec_chain.h", "inf_split.h", "gz_members.h", "bgzf_index.h", "k_deflate.h", "k_df_fold.h", "k_lzhuf.h", "lzh_split.h", "k_lha.h", "lha_archive.h", os.path.join("..", "..", "include", "bz2_mi355x.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-function",
          "-D__HIP_PLATFORM_AMD__"] + os.environ.get("BZ_EXTRA_FLAGS", "").split()

@@ -121,11 +121,6 @@ static bool enc_trace()
     static const bool v = getenv("BZ_ENC_TRACE") != nullptr;
     return v;
 }
-static double now_ms()
-{
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
 
 static std::mutex g_cache_mu;
 static std::vector<EncResources *> g_cache; // resources of destroyed contexts, ready for reuse

@@ -33,10 +33,6 @@ static bool dec_trace()
     static const bool on = getenv("BZ_DEC_TRACE") != nullptr;
     return on;
 }
-static double dec_now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 struct DecWorkspace {
     size_t slots = 0;
@@ -804,7 +800,7 @@ struct DecRun : DecCall {
         if (dec_trace())
             fprintf(stderr, "bz decode %s %u: %u blocks, %llu bytes; stages so far D0+D1 %.2f, MTF %.2f, walks %.2f, expand+CRC %.2f ms (at %.1f)\n",
                     what, batch_no, nb, (unsigned long long)valid, w->t_stage[0] * 1e3, w->t_stage[1] * 1e3, w->t_stage[2] * 1e3,
-                    w->t_stage[3] * 1e3, dec_now_ms());
+                    w->t_stage[3] * 1e3, now_ms());
     }
 
     // host destination, a buffer of its own for every sub-batch (the streaming context)
@@ -1405,7 +1401,7 @@ extern "C" int bz_decode_buffer(int device, const uint8_t *in, size_t in_len, ui
     if (!out || !out_len || (!in && in_len)) return BZ_E_PARAM;
     *out = nullptr;
     *out_len = 0;
-    const double t_enter = dec_now_ms();
+    const double t_enter = now_ms();
     EngineLease lease(device, 1, 0); // (a parked engine that has decoded before, or a new one; host_call.h)
     if (lease.status() != BZ_OK) return lease.status();
     bz_gpu_engine *g = lease.engine();
@@ -1431,7 +1427,7 @@ extern "C" int bz_decode_buffer(int device, const uint8_t *in, size_t in_len, ui
             rc = decode_core(g, static_cast<const u8 *>(g->dec_in.p), in_len, sink, &verdict);
         }
     }
-    if (dec_trace()) fprintf(stderr, "bz_decode_buffer: %zu -> %zu bytes, rc %d, done at %.1f (entered at %.1f)\n", in_len, host.len, rc, dec_now_ms(), t_enter);
+    if (dec_trace()) fprintf(stderr, "bz_decode_buffer: %zu -> %zu bytes, rc %d, done at %.1f (entered at %.1f)\n", in_len, host.len, rc, now_ms(), t_enter);
     lease.settle(rc); // (`verdict`, the stream's, is not the engine's business)
     if (rc != BZ_OK) return rc;
     // the bytes in front of an error are handed over too, as the reference's iterator yields them
@@ -1673,7 +1669,7 @@ static void dec_process(bz_dec *d, bz_dec::Lane &ln, DecJob &j, u64 no)
         }
         ln.g = lease.release(); // (the lane holds it until bz_dec_destroy ends it through a lease that adopts it)
     }
-    const double t0 = dec_now_ms();
+    const double t0 = now_ms();
     // the device holds [carry | new bytes]: two uploads, no copy of the chunk on the host; room for a whole chunk and a
     // block's worth of carry from the start, so that the buffer is made once
     const size_t nc = d->carry.size(), nn = j.bytes.size(), n = nc + nn;
@@ -1684,7 +1680,7 @@ static void dec_process(bz_dec *d, bz_dec::Lane &ln, DecJob &j, u64 no)
     if (rc == BZ_OK && nn && hipMemcpyAsync(static_cast<u8 *>(ln.d_in.p) + nc, j.bytes.data(), nn, hipMemcpyHostToDevice, ln.g->st) != hipSuccess)
         rc = BZ_E_UNEXPECTED;
     if (rc == BZ_OK && hipStreamSynchronize(ln.g->st) != hipSuccess) rc = BZ_E_UNEXPECTED;
-    const double t1 = dec_now_ms();
+    const double t1 = now_ms();
     int verdict = BZ_OK;
     size_t produced = 0;
     bool stopped = false, aborted = false;
@@ -1762,12 +1758,12 @@ static void dec_process(bz_dec *d, bz_dec::Lane &ln, DecJob &j, u64 no)
             }
             d->rs = fin;
             d->rs.pos &= 7u;
-            t_chain = dec_now_ms();
+            t_chain = now_ms();
             pass_chain();
         };
         sink.before_output = [&]() -> bool {
             const bool go = wait_out_turn();
-            t_out = dec_now_ms();
+            t_out = now_ms();
             return go;
         };
         sink.staging[0] = &ln.g->dec->staging;
@@ -1783,8 +1779,8 @@ static void dec_process(bz_dec *d, bz_dec::Lane &ln, DecJob &j, u64 no)
     pass_chain();
     if (dec_trace())
         fprintf(stderr, "bz_dec chunk %llu: %zu + %zu compressed bytes (final %d): upload %.2f ms, chain known after %.2f, waited for its turn %.2f, decode %.2f ms -> %zu bytes, rc %d verdict %d%s (at %.1f)\n",
-                (unsigned long long)no, nc, nn, (int)j.final, t1 - t0, t_chain ? t_chain - t1 : 0.0, t_out && t_chain ? t_out - t_chain : 0.0, dec_now_ms() - t1,
-                produced, rc, verdict, aborted ? " GIVEN UP" : "", dec_now_ms());
+                (unsigned long long)no, nc, nn, (int)j.final, t1 - t0, t_chain ? t_chain - t1 : 0.0, t_out && t_chain ? t_out - t_chain : 0.0, now_ms() - t1,
+                produced, rc, verdict, aborted ? " GIVEN UP" : "", now_ms());
     if (aborted) return;
     // (the bytes in front of an error have been handed over too, as the reference's iterator yields them)
     if (rc != BZ_OK || verdict != BZ_OK) {

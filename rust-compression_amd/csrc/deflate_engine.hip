@@ -12,9 +12,9 @@
 #include <vector>
 
 #include "engine_state.h"
+#include "batch_decode.h"
 #include "copy_pool.h"
 
-#include <chrono>
 #include <sys/mman.h>
 #include <functional>
 #include "k_deflate.h"
@@ -506,10 +506,6 @@ static bool df_trace()
     static const bool on = getenv("BZ_DF_TRACE") != nullptr; // (diagnostics: a line per part and per one-shot call)
     return on;
 }
-static double df_now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 static u64 df_part_bytes()
 {
     static const u64 v = [] {
@@ -566,12 +562,12 @@ static int df_encode_parts(bz_gpu_engine *g, int kind, const u8 *d_in, u64 n, co
         seg.accumulate_stats = k > 0;
         size_t got = 0;
         DfPartOut po;
-        const double t_part = df_now_ms();
+        const double t_part = now_ms();
         if (hooks && hooks->need_input) {
             const int irc = hooks->need_input(std::min<u64>(n, pos + len + 64));
             if (irc != BZ_OK) return irc;
         }
-        const double t_in = df_now_ms();
+        const double t_in = now_ms();
         const int rc = df_encode_core(g, kind, d_in + pos, len, dict, dict_len, d_out ? d_out + written : nullptr,
                                       d_out ? cap - written : 0, &got, seg, last ? dl_out : nullptr, &po);
         if (rc != BZ_OK) return rc;
@@ -580,7 +576,7 @@ static int df_encode_parts(bz_gpu_engine *g, int kind, const u8 *d_in, u64 n, co
             fprintf(stderr, "bz2_mi355x: deflate part %u: input [%llu, +%llu) of %llu, kept %llu bytes of it, %zu stream bytes, "
                             "%u bits handed on, %llu blocks; waited for its input %.2f ms, call %.2f ms of which kernels %.2f (at %.1f)\n", k, (unsigned long long)pos, (unsigned long long)len,
                     (unsigned long long)n, (unsigned long long)(last ? len : po.consumed), got, last ? 0u : po.end_bits,
-                    (unsigned long long)g->df->h_nb, t_in - t_part, df_now_ms() - t_in, g->df->t_stage[5] * 1e3, df_now_ms());
+                    (unsigned long long)g->df->h_nb, t_in - t_part, now_ms() - t_in, g->df->t_stage[5] * 1e3, now_ms());
         written += got;
         *out_len = written;
         if (last) return BZ_OK;
@@ -601,7 +597,7 @@ static int df_encode_parts(bz_gpu_engine *g, int kind, const u8 *d_in, u64 n, co
 // once per sub-batch.  Every other input goes through df_encode_parts, in its turn.
 // A preset dictionary (df_gpu_encode_batch_device_dict): its last W <= 32768 bytes go to the device once per call and into
 // the image in front of EVERY input (DfBatchDict; k_deflate.h "window tiles") -- df_encode_core's history layout, once per slot.
-static u64 df_batch_image_bytes()
+u64 df_batch_image_bytes() // (lzhuf_engine.hip sizes its sub-batches by it too)
 {
     const char *s = getenv("BZ_DF_BATCH_MIB"); // slot image per sub-batch (a fraction is taken too), read per call
     double mib = s ? atof(s) : 64.0;
@@ -921,27 +917,8 @@ extern "C" int df_gpu_bgzf_encode_device(bz_gpu_engine *g, const void *d_in, siz
     return BZ_OK;
 }
 
-// ---- the host-to-host forms: an engine of the cache for the length of the call (EngineLease, host_call.h) ----------
-// A device number out of range is BZ_E_NOGPU for the entry points that ask here first (df_encode_batch, df_decode_batch and
-// with it df_decode_buffer, df_enc_create); the others pass on what bz_gpu_engine_create answers (BZ_E_PARAM).
-static int df_device_in_range(int device)
-{
-    int ndev = 0;
-    return hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && device >= 0 && device < ndev ? BZ_OK : BZ_E_NOGPU;
-}
-// the result: `total` bytes of device memory in a malloc'ed block (bz_free), one byte for none
-static int df_download(uint8_t **out, const void *d_src, size_t total)
-{
-    uint8_t *h = (uint8_t *)malloc(total ? total : 1);
-    if (!h) return BZ_E_NOMEM;
-    if (total && hipMemcpy(h, d_src, total, hipMemcpyDeviceToHost) != hipSuccess) {
-        free(h);
-        return BZ_E_UNEXPECTED;
-    }
-    *out = h;
-    return BZ_OK;
-}
-
+// ---- the host-to-host forms: an engine of the cache for the length of the call (EngineLease, host_call.h); the forms that
+// are one upload, one device call and one download are their own checks and that call inside one_shot() (one_shot.h) ----
 // Many inputs: packed at 16-byte-aligned offsets (BatchLayout), one upload, one device call, one download.
 extern "C" int df_encode_batch(int kind, int device, const uint8_t *const *ins, const size_t *lens, size_t count, uint8_t **out,
                                uint64_t *out_off, uint64_t *out_len)
@@ -959,27 +936,14 @@ extern "C" int df_encode_batch_dict(int kind, int device, const uint8_t *const *
     if (count && (!ins || !lens || !out_off || !out_len)) return BZ_E_PARAM;
     const BatchLayout lay(ins, lens, count, 16);
     if (lay.status != BZ_OK) return lay.status;
-    if (count == 0) {
-        *out = (uint8_t *)malloc(1);
-        return *out ? BZ_OK : BZ_E_NOMEM;
-    }
-    if (df_device_in_range(device) != BZ_OK) return BZ_E_NOGPU;
-    EngineLease lease(device, 2, 1);
-    if (lease.status() != BZ_OK) return lease.status();
-    bz_gpu_engine *g = lease.engine();
+    if (count == 0) return one_shot_empty(out);
     const size_t cap = df_encode_batch_bound(lay.in_len.data(), count);
-    std::vector<uint8_t> packed((size_t)lay.total + 16);
-    lay.pack_into(packed.data());
-    int rc = g->dec_in.ensure((size_t)lay.total + 64);
-    if (rc == BZ_OK) rc = g->oneshot_out.ensure(cap + 64);
-    if (rc == BZ_OK && lay.total && hipMemcpy(g->dec_in.p, packed.data(), (size_t)lay.total, hipMemcpyHostToDevice) != hipSuccess)
-        rc = BZ_E_UNEXPECTED;
-    if (rc == BZ_OK)
-        rc = df_gpu_encode_batch_device_dict(g, kind, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), count, dict, dict_len, g->oneshot_out.p,
-                                             cap, out_off, out_len);
-    if (rc == BZ_OK) rc = df_download(out, g->oneshot_out.p, (size_t)(out_off[count - 1] + ((out_len[count - 1] + 3u) & ~(u64)3)));
-    lease.settle(rc);
-    return rc;
+    return one_shot(device, 2, lay, cap, kSettleStatus, out, [&](bz_gpu_engine *g, size_t *total) {
+        const int rc = df_gpu_encode_batch_device_dict(g, kind, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), count, dict, dict_len,
+                                                       g->oneshot_out.p, cap, out_off, out_len);
+        if (rc == BZ_OK) *total = (size_t)(out_off[count - 1] + ((out_len[count - 1] + 3u) & ~(u64)3));
+        return rc;
+    });
 }
 
 // A BGZF file from host memory: one upload, df_gpu_bgzf_encode_device on an engine of the cache, one download.
@@ -1000,19 +964,14 @@ extern "C" int df_bgzf_encode_buffer(int device, const uint8_t *in, size_t n, ui
         *out_len = m;
         return BZ_OK;
     }
-    if (df_device_in_range(device) != BZ_OK) return BZ_E_NOGPU;
-    EngineLease lease(device, 2, 1);
-    if (lease.status() != BZ_OK) return lease.status();
-    bz_gpu_engine *g = lease.engine();
     const size_t cap = df_bgzf_bound(n, block_bytes, eof);
-    uint64_t total = 0;
-    int rc = g->dec_in.ensure(n + 64);
-    if (rc == BZ_OK) rc = g->oneshot_out.ensure(cap + 64);
-    if (rc == BZ_OK && hipMemcpy(g->dec_in.p, in, n, hipMemcpyHostToDevice) != hipSuccess) rc = BZ_E_UNEXPECTED;
-    if (rc == BZ_OK) rc = df_gpu_bgzf_encode_device(g, g->dec_in.p, n, block_bytes, eof, g->oneshot_out.p, cap, &total, block_off);
-    if (rc == BZ_OK) rc = df_download(out, g->oneshot_out.p, (size_t)total);
-    if (rc == BZ_OK) *out_len = (size_t)total;
-    lease.settle(rc);
+    uint64_t made = 0;
+    const int rc = one_shot(device, 2, OneShotIn(in, n), cap, kSettleStatus, out, [&](bz_gpu_engine *g, size_t *total) {
+        const int drc = df_gpu_bgzf_encode_device(g, g->dec_in.p, n, block_bytes, eof, g->oneshot_out.p, cap, &made, block_off);
+        *total = (size_t)made;
+        return drc;
+    });
+    if (rc == BZ_OK) *out_len = (size_t)made;
     return rc;
 }
 
@@ -1084,7 +1043,7 @@ static int df_split_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *
     piece = (piece < 1 ? 1 : piece > (1u << 20) ? (1u << 20) : piece) * 1024;
     while (elen / piece > (1u << 20)) piece *= 2;
     const u32 npieces = (u32)((elen + piece - 1) / piece);
-    double t0 = df_now_ms();
+    double t0 = now_ms();
     std::vector<Cand> cands;
     int rc;
     if (npieces > 1) {
@@ -1098,7 +1057,7 @@ static int df_split_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *
             if (c.pos != kNoStop) cands.push_back(c);
     }
     e.st[1] += cands.size();
-    double t1 = df_now_ms();
+    double t1 = now_ms();
     e.ms[0] += t1 - t0;
     // every piece at once: the entry's first bit and every candidate, each to the next candidate
     std::vector<DfPiece> pcs(1 + cands.size());
@@ -1112,7 +1071,7 @@ static int df_split_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *
     }
     std::vector<DfPieceRec> prs(pcs.size());
     if ((rc = df_split_pieces(g, w, kind, ebase, elen, win, pcs.data(), (u32)pcs.size(), prs.data(), &e.st[7])) != BZ_OK) return rc;
-    t0 = df_now_ms();
+    t0 = now_ms();
     e.ms[1] += t0 - t1;
     // the chain: a candidate's piece counts if and only if the confirmed piece in front of it ended exactly there
     std::vector<DfPieceRec> crec;
@@ -1159,7 +1118,7 @@ static int df_split_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *
         sum += crec[k].r.len;
         if (crec[k].r.flags & 1u) sum = 1ull << 32;
     }
-    e.ms[2] += df_now_ms() - t0;
+    e.ms[2] += now_ms() - t0;
     if (sum >= (1ull << 31)) {
         *fallback = true;
         return BZ_OK;
@@ -1182,36 +1141,22 @@ static int df_split_write(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *
     u32 *map = w->s_map.as<u32>(), *cnt = w->s_cnt.as<u32>();
     int rc = w->s_piece.ensure((size_t)np * sizeof(DfPiece));
     if (rc != BZ_OK) return rc;
-    double t0 = df_now_ms();
+    const double t0 = now_ms();
     HIPCHK(hipMemcpyAsync(w->s_piece.p, e.chain.data(), (size_t)np * sizeof(DfPiece), hipMemcpyHostToDevice, g->st));
     if (df_launch_inflate_piece(g->st, true, ebase, elen, kind, w->s_piece.as<DfPiece>(), np, nullptr, eout, map, win) != 0)
         return BZ_E_UNEXPECTED;
     HIPCHK(hipStreamSynchronize(g->st));
     w->split_stats[7] += 1;
-    double t1 = df_now_ms();
-    w->split_ms[3] += t1 - t0;
-    u32 left = 0;
-    for (u32 round = 0; n && np > 1; ++round) {
-        u32 h[2] = {0, 0};
-        HIPCHK(hipMemsetAsync(cnt, 0, 8, g->st));
-        if (df_launch_split_jump(g->st, map, n, cnt) != 0) return BZ_E_UNEXPECTED;
-        HIPCHK(hipMemcpyAsync(h, cnt, 8, hipMemcpyDeviceToHost, g->st));
-        HIPCHK(hipStreamSynchronize(g->st));
-        w->split_stats[7] += 1;
-        w->split_stats[6] += 1;
-        if (round == 0) left = h[0];
-        if (h[1] == 0) break;
-    }
-    w->split_stats[5] += left;
-    t0 = df_now_ms();
-    w->split_ms[4] += t0 - t1;
-    if (left) {
-        if (df_launch_split_gather(g->st, eout, map, n) != 0) return BZ_E_UNEXPECTED;
-        HIPCHK(hipStreamSynchronize(g->st));
-        w->split_stats[7] += 1;
-    }
-    t1 = df_now_ms();
-    w->split_ms[5] += t1 - t0;
+    w->split_ms[3] += now_ms() - t0;
+    SplitTail t;
+    rc = split_jump_gather(g->st, n && np > 1, map, n, cnt, eout, t); // (one piece: every byte is in its place)
+    w->split_stats[7] += t.launches;
+    w->split_stats[6] += t.rounds;
+    w->split_stats[5] += t.left;
+    w->split_ms[4] += t.jump_ms;
+    w->split_ms[5] += t.gather_ms;
+    if (rc != BZ_OK) return rc;
+    const double t1 = now_ms();
     if (kind == 0 || e.rec.verdict != BZ_OK) return BZ_OK;
     const u32 npieces = (u32)(((u64)n + kSumPiece - 1) / kSumPiece);
     if ((rc = w->asum.ensure((size_t)(npieces + 1) * 8)) != BZ_OK) return rc;
@@ -1252,7 +1197,7 @@ static int df_split_write(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 *
         ok = (raw ^ gf_mul_reflected(0xFFFFFFFFu, gf_xpow8_reflected(n)) ^ 0xFFFFFFFFu) == e.rec.check && e.rec.isize == n;
     }
     if (!ok) e.rec.verdict = BZ_E_DATA;
-    w->split_ms[6] += df_now_ms() - t1;
+    w->split_ms[6] += now_ms() - t1;
     return BZ_OK;
 }
 
@@ -1274,7 +1219,6 @@ static int df_decode_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 
     const u64 split_min = df_env_kib("BZ_DF_INF_SPLIT_KIB", 1024) * 1024;
     std::vector<DfSplitEntry> &splits = s.splits;
     splits.clear();
-    s.len_small.clear();
     for (size_t i = 0; split_min && i < count; ++i) {
         if (h_in_len[i] < split_min) continue;
         DfSplitEntry e;
@@ -1284,23 +1228,10 @@ static int df_decode_sizes(bz_gpu_engine *g, DfWorkspace *w, int kind, const u8 
         if (rc != BZ_OK) return rc;
         if (!fallback) splits.push_back(std::move(e));
     }
-    // ONE source map for all of them, one after the other: sized here, before any entry is committed to the split path.  If
-    // it cannot be had, every entry takes the one-wave path (and the failed allocation's error is not the next launch's).
-    if (!splits.empty() && will_write) {
-        size_t map_bytes = 0;
-        for (const DfSplitEntry &e : splits) map_bytes = std::max(map_bytes, (size_t)e.rec.len * 4 + 64);
-        if (w->s_map.ensure(map_bytes) != BZ_OK || w->s_cnt.ensure(64) != BZ_OK) {
-            (void)hipGetLastError();
-            splits.clear();
-        }
-    }
+    (void)split_reserve(splits, will_write, w->s_map, w->s_cnt, h_in_len, count, s.len_small);
     for (const DfSplitEntry &e : splits) {
         for (int k = 0; k < 8; ++k) w->split_stats[k] += e.st[k];
         for (int k = 0; k < 3; ++k) w->split_ms[k] += e.ms[k];
-    }
-    if (!splits.empty()) {
-        s.len_small.assign(h_in_len, h_in_len + count);
-        for (const DfSplitEntry &e : splits) s.len_small[e.index] = 0;
     }
     rc = w->i_in.ensure(2 * count * sizeof(u64));
     if (rc == BZ_OK) rc = w->i_ooff.ensure(count * sizeof(u64));
@@ -1397,14 +1328,8 @@ static int df_decode_batch_core(bz_gpu_engine *g, int kind, const void *d_in, co
     if (!g || kind < 0 || kind > 2) return BZ_E_PARAM;
     if (df_dict_param(kind, dict, dict_len) != BZ_OK) return BZ_E_PARAM;
     if (count == 0) return BZ_OK;
-    if (!h_in_off || !h_in_len || !h_out_off || !h_out_len || !h_verdict || count > 0x7FFFFFFFu) return BZ_E_PARAM;
-    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u)) return BZ_E_PARAM;
-    u64 in_end = 0;
-    for (size_t i = 0; i < count; ++i) {
-        if ((h_in_off[i] & 3u) || h_in_off[i] < in_end || h_in_off[i] + h_in_len[i] < h_in_off[i] || h_in_len[i] > 0xFFFFFFFFull) return BZ_E_PARAM;
-        in_end = h_in_off[i] + h_in_len[i];
-    }
-    if (in_end && !d_in) return BZ_E_PARAM;
+    if (!h_in_off || !h_in_len || !h_out_off || !h_out_len || !h_verdict) return BZ_E_PARAM;
+    if (!batch_ranges_ok(d_in, d_out, h_in_off, h_in_len, count)) return BZ_E_PARAM;
     DfWorkspace *w = nullptr;
     int rc = df_workspace(g, &w);
     if (rc != BZ_OK) return rc;
@@ -1419,22 +1344,10 @@ static int df_decode_batch_core(bz_gpu_engine *g, int kind, const void *d_in, co
     rc = df_decode_sizes(g, w, kind, in8, h_in_off, h_in_len, count, win, d_out != nullptr || grow != nullptr, sz);
     if (rc != BZ_OK) return rc;
     const std::vector<DfInfRec> &rec = sz.rec;
-    // the outputs' places: input order, each at a multiple of 16
-    u64 cursor = 0, need = 0;
-    for (size_t i = 0; i < count; ++i) {
-        if (rec[i].flags & 1u) return BZ_E_PARAM; // an entry of 4 GiB or more of output
-        h_out_off[i] = cursor;
-        h_out_len[i] = rec[i].len;
-        h_verdict[i] = rec[i].verdict;
-        need = cursor + rec[i].len; // (the largest off + len: offsets ascend, so the last entry's, empty or not)
-        cursor += ((u64)rec[i].len + 15u) & ~(u64)15;
-    }
-    u8 *out8 = static_cast<u8 *>(d_out);
-    if (grow) {
-        rc = grow->ensure((size_t)need + 64);
-        if (rc != BZ_OK) return rc;
-        out8 = grow->as<u8>();
-    } else if (d_out && need > cap) return BZ_E_CAPACITY;
+    u64 need = 0;
+    u8 *out8 = nullptr;
+    if ((rc = batch_place(rec.data(), count, nullptr, h_out_off, h_out_len, h_verdict, &need)) != BZ_OK) return rc;
+    if ((rc = batch_output(need, d_out, cap, grow, &out8)) != BZ_OK) return rc;
     float ms[3] = {0, 0, 0};
     if (out8) {
         rc = df_decode_write(g, w, kind, in8, h_in_off, h_in_len, count, win, out8, h_out_off, sz, false);
@@ -1493,25 +1406,14 @@ extern "C" int df_decode_batch_dict(int kind, int device, const uint8_t *const *
     if (count && (!ins || !lens || !out_off || !out_len || !verdict)) return BZ_E_PARAM;
     const BatchLayout lay(ins, lens, count, 4);
     if (lay.status != BZ_OK) return lay.status;
-    if (count == 0) {
-        *out = (uint8_t *)malloc(1);
-        return *out ? BZ_OK : BZ_E_NOMEM;
-    }
-    if (df_device_in_range(device) != BZ_OK) return BZ_E_NOGPU;
-    EngineLease lease(device, 2, 1);
-    if (lease.status() != BZ_OK) return lease.status();
-    bz_gpu_engine *g = lease.engine();
-    std::vector<uint8_t> packed((size_t)lay.total + 16);
-    lay.pack_into(packed.data());
-    int rc = g->dec_in.ensure((size_t)lay.total + 64);
-    if (rc == BZ_OK && lay.total && hipMemcpy(g->dec_in.p, packed.data(), (size_t)lay.total, hipMemcpyHostToDevice) != hipSuccess)
-        rc = BZ_E_UNEXPECTED;
-    if (rc == BZ_OK)
-        rc = df_decode_batch_core(g, kind, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), count, dict, dict_len, nullptr, 0, &g->oneshot_out,
-                                  out_off, out_len, verdict);
-    if (rc == BZ_OK) rc = df_download(out, g->oneshot_out.p, (size_t)(out_off[count - 1] + out_len[count - 1]));
-    lease.settle(rc); // (the entries' verdicts are not the engine's business)
-    return rc;
+    if (count == 0) return one_shot_empty(out);
+    // (the entries' verdicts are not the engine's business)
+    return one_shot(device, 2, lay, kOutGrown, kSettleStatus, out, [&](bz_gpu_engine *g, size_t *total) {
+        const int rc = df_decode_batch_core(g, kind, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), count, dict, dict_len, nullptr, 0,
+                                            &g->oneshot_out, out_off, out_len, verdict);
+        if (rc == BZ_OK) *total = (size_t)(out_off[count - 1] + out_len[count - 1]);
+        return rc;
+    });
 }
 
 // The batch of one: BZ_OK with the bytes, or the entry's verdict with the bytes in front of it (as bz_decode_buffer).
@@ -1587,7 +1489,7 @@ struct GzCands {
         int rc = w->m_cnt.ensure((size_t)ntiles * 4);
         if (rc == BZ_OK) rc = w->m_base.ensure((size_t)ntiles * 4);
         if (rc != BZ_OK) return rc;
-        const double t0 = df_now_ms();
+        const double t0 = now_ms();
         std::vector<u32> cnt(ntiles), base(ntiles);
         if (df_launch_gz_search_count(g->st, in, len, ntiles, w->m_cnt.as<u32>()) != 0) return BZ_E_UNEXPECTED;
         HIPCHK(hipMemcpyAsync(cnt.data(), w->m_cnt.p, (size_t)ntiles * 4, hipMemcpyDeviceToHost, g->st));
@@ -1600,7 +1502,7 @@ struct GzCands {
         total = tpre[ntiles];
         HIPCHK(hipMemcpyAsync(w->m_base.p, base.data(), (size_t)ntiles * 4, hipMemcpyHostToDevice, g->st));
         HIPCHK(hipStreamSynchronize(g->st));
-        w->mem_ms[0] += df_now_ms() - t0;
+        w->mem_ms[0] += now_ms() - t0;
         w->mem_stats[7] += 1;
         return BZ_OK;
     }
@@ -1613,14 +1515,14 @@ struct GzCands {
         const u32 t1 = (u32)(std::upper_bound(tpre.begin(), tpre.end(), idx + n - 1) - tpre.begin() - 1);
         const int rc = w->m_cand.ensure((size_t)n * 4);
         if (rc != BZ_OK) return rc;
-        const double c0 = df_now_ms();
+        const double c0 = now_ms();
         if (df_launch_gz_search_list(g->st, in, len, t0, t1 - t0 + 1, w->m_base.as<u32>(), (u32)idx, (u32)n, w->m_cand.as<u32>()) != 0)
             return BZ_E_UNEXPECTED;
         win.resize((size_t)n);
         HIPCHK(hipMemcpyAsync(win.data(), w->m_cand.p, (size_t)n * 4, hipMemcpyDeviceToHost, g->st));
         HIPCHK(hipStreamSynchronize(g->st));
         first = idx;
-        w->mem_ms[0] += df_now_ms() - c0;
+        w->mem_ms[0] += now_ms() - c0;
         w->mem_stats[7] += 1;
         return BZ_OK;
     }
@@ -1656,11 +1558,11 @@ static int df_gz_gather(bz_gpu_engine *g, DfWorkspace *w, const u8 *in8, const s
     int rc = w->m_image.ensure((size_t)cur + 64);
     if (rc == BZ_OK) rc = w->m_span.ensure(n * sizeof(GzSpan));
     if (rc != BZ_OK) return rc;
-    const double t0 = df_now_ms();
+    const double t0 = now_ms();
     HIPCHK(hipMemcpyAsync(w->m_span.p, tab.data(), n * sizeof(GzSpan), hipMemcpyHostToDevice, g->st));
     if (df_launch_gz_gather(g->st, in8, w->m_span.as<GzSpan>(), (u32)n, max_len, w->m_image.as<u8>()) != 0) return BZ_E_UNEXPECTED;
     HIPCHK(hipStreamSynchronize(g->st));
-    w->mem_ms[1] += df_now_ms() - t0;
+    w->mem_ms[1] += now_ms() - t0;
     w->mem_stats[7] += 1;
     return BZ_OK;
 }
@@ -1686,13 +1588,13 @@ static int df_gz_zero_skip(bz_gpu_engine *g, DfWorkspace *w, const u8 *in8, cons
     const int rc = w->m_zs.ensure((size_t)n * 12);
     if (rc != BZ_OK) return rc;
     u32 *d = w->m_zs.as<u32>();
-    const double t0 = df_now_ms();
+    const double t0 = now_ms();
     HIPCHK(hipMemcpyAsync(d, from, (size_t)n * 4, hipMemcpyHostToDevice, g->st));
     HIPCHK(hipMemcpyAsync(d + n, bound, (size_t)n * 4, hipMemcpyHostToDevice, g->st));
     if (df_launch_gz_zero_skip(g->st, in8, d, d + n, n, d + 2 * (size_t)n) != 0) return BZ_E_UNEXPECTED;
     HIPCHK(hipMemcpyAsync(out, d + 2 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, g->st));
     HIPCHK(hipStreamSynchronize(g->st));
-    w->mem_ms[2] += df_now_ms() - t0;
+    w->mem_ms[2] += now_ms() - t0;
     w->mem_stats[7] += 1;
     return BZ_OK;
 }
@@ -1917,11 +1819,11 @@ static int df_members_core(bz_gpu_engine *g, const void *d_in, size_t in_len, vo
             }
         }
         if ((rc = w->m_span.ensure(tab.size() * sizeof(GzSpan))) != BZ_OK) return rc;
-        const double t0 = df_now_ms();
+        const double t0 = now_ms();
         HIPCHK(hipMemcpyAsync(w->m_span.p, tab.data(), tab.size() * sizeof(GzSpan), hipMemcpyHostToDevice, g->st));
         if (df_launch_gz_compact(g->st, w->m_stage.as<u8>(), w->m_span.as<GzSpan>(), (u32)tab.size(), max_len, out8) != 0) return BZ_E_UNEXPECTED;
         HIPCHK(hipStreamSynchronize(g->st));
-        w->mem_ms[3] += df_now_ms() - t0;
+        w->mem_ms[3] += now_ms() - t0;
         ms[7] += 1;
         a = b;
     }
@@ -1955,21 +1857,15 @@ extern "C" int df_decode_members_buffer(int device, const uint8_t *in, size_t in
     *out = nullptr;
     *out_len = 0;
     if ((u64)in_len >= (1ull << 32)) return BZ_E_PARAM;
-    if (in_len == 0) { // (no member: BZ_OK, no bytes, no device)
-        *out = (uint8_t *)malloc(1);
-        return *out ? BZ_OK : BZ_E_NOMEM;
-    }
-    if (df_device_in_range(device) != BZ_OK) return BZ_E_NOGPU;
-    EngineLease lease(device, 2, 1);
-    if (lease.status() != BZ_OK) return lease.status();
-    bz_gpu_engine *g = lease.engine();
+    if (in_len == 0) return one_shot_empty(out); // (no member: BZ_OK, no bytes, no device)
     uint64_t n = 0;
     int32_t v = BZ_OK;
-    int rc = g->dec_in.ensure(in_len + 64);
-    if (rc == BZ_OK && hipMemcpy(g->dec_in.p, in, in_len, hipMemcpyHostToDevice) != hipSuccess) rc = BZ_E_UNEXPECTED;
-    if (rc == BZ_OK) rc = df_members_core(g, g->dec_in.p, in_len, nullptr, 0, &g->oneshot_out, &n, &v);
-    if (rc == BZ_OK) rc = df_download(out, g->oneshot_out.p, (size_t)n);
-    lease.settle(rc); // (the stream's verdict is not the engine's business)
+    // (the stream's verdict is not the engine's business)
+    const int rc = one_shot(device, 2, OneShotIn(in, in_len), kOutGrown, kSettleStatus, out, [&](bz_gpu_engine *g, size_t *total) {
+        const int drc = df_members_core(g, g->dec_in.p, in_len, nullptr, 0, &g->oneshot_out, &n, &v);
+        *total = (size_t)n;
+        return drc;
+    });
     if (rc != BZ_OK) return rc;
     *out_len = (size_t)n;
     return v;
@@ -2099,7 +1995,7 @@ extern "C" int df_gpu_bgzf_index_device(bz_gpu_engine *g, const void *d_in, size
     if (wrc != BZ_OK) return wrc;
     w->bgzf_read_stats[3] = w->bgzf_read_stats[4] = 0;
     w->bgzf_index_s = 0;
-    const double t0 = df_now_ms();
+    const double t0 = now_ms();
     BgzfCands cs;
     cs.g = g;
     cs.w = w;
@@ -2149,7 +2045,7 @@ extern "C" int df_gpu_bgzf_index_device(bz_gpu_engine *g, const void *d_in, size
     *count = (size_t)nblocks;
     w->bgzf_read_stats[3] = cs.total;
     w->bgzf_read_stats[4] = cs.total - landed;
-    w->bgzf_index_s = (df_now_ms() - t0) * 1e-3;
+    w->bgzf_index_s = (now_ms() - t0) * 1e-3;
     for (int i = 0; i < 6; ++i) w->t_stage[i] = 0;
     w->t_stage[0] = w->t_stage[5] = w->bgzf_index_s;
     if (nblocks > cap_blocks) return BZ_E_CAPACITY;
@@ -2282,15 +2178,8 @@ extern "C" int df_bgzf_read_buffer(int device, const uint8_t *in, size_t in_len,
     // the index's fault lies at uncompressed position `total`: inside or in front of a range that reaches behind it
     const bool reaches = ulen != 0 && (ustart >= total || ulen > total - ustart);
     const int v_index = reaches ? vi : BZ_OK;
-    if (ulen == 0 || ustart >= total) { // no bytes: no device
-        *out = (uint8_t *)malloc(1);
-        return *out ? v_index : BZ_E_NOMEM;
-    }
+    if (ulen == 0 || ustart >= total) return one_shot_empty(out) == BZ_OK ? v_index : BZ_E_NOMEM; // no bytes: no device
     const u64 uend = ulen < total - ustart ? ustart + ulen : total, rlen = uend - ustart;
-    if (df_device_in_range(device) != BZ_OK) return BZ_E_NOGPU;
-    EngineLease lease(device, 2, 1);
-    if (lease.status() != BZ_OK) return lease.status();
-    bz_gpu_engine *g = lease.engine();
     u64 first = 0, last = 0;
     bgzf::touched(u.data(), count, ustart, uend, &first, &last);
     const u64 cbase = c[(size_t)first] & ~(u64)15, clen = c[(size_t)last + 1] - cbase; // (the device call wants 16-byte alignment)
@@ -2298,14 +2187,13 @@ extern "C" int df_bgzf_read_buffer(int device, const uint8_t *in, size_t in_len,
     for (size_t k = 0; k < rc_off.size(); ++k) rc_off[k] = c[(size_t)first + k] - cbase;
     uint64_t n = 0;
     int32_t v = BZ_OK;
-    int rc = g->dec_in.ensure((size_t)clen + 64);
-    if (rc == BZ_OK) rc = g->oneshot_out.ensure((size_t)rlen + 64);
-    if (rc == BZ_OK && hipMemcpy(g->dec_in.p, in + cbase, (size_t)clen, hipMemcpyHostToDevice) != hipSuccess) rc = BZ_E_UNEXPECTED;
-    if (rc == BZ_OK)
-        rc = df_gpu_bgzf_read_device(g, g->dec_in.p, (size_t)clen, rc_off.data(), u.data() + first, (size_t)(last - first + 1), ustart, rlen,
-                                     g->oneshot_out.p, (size_t)rlen, &n, &v);
-    if (rc == BZ_OK) rc = df_download(out, g->oneshot_out.p, (size_t)n);
-    lease.settle(rc); // (the file's verdict is not the engine's business)
+    // (the file's verdict is not the engine's business)
+    const int rc = one_shot(device, 2, OneShotIn(in + cbase, (size_t)clen), (size_t)rlen, kSettleStatus, out, [&](bz_gpu_engine *g, size_t *total) {
+        const int drc = df_gpu_bgzf_read_device(g, g->dec_in.p, (size_t)clen, rc_off.data(), u.data() + first, (size_t)(last - first + 1), ustart,
+                                                rlen, g->oneshot_out.p, (size_t)rlen, &n, &v);
+        *total = (size_t)n;
+        return drc;
+    });
     if (rc != BZ_OK) return rc;
     *out_len = (size_t)n;
     return v != BZ_OK ? v : v_index;
@@ -2408,7 +2296,7 @@ extern "C" int df_encode_buffer_dict(int kind, int device, const uint8_t *in, si
     if (!out || !out_len || (!in && in_len) || kind < 0 || kind > 2 || (!dict && dict_len)) return BZ_E_PARAM;
     *out = nullptr;
     *out_len = 0;
-    if (df_trace()) fprintf(stderr, "bz2_mi355x: df_encode_buffer entered at %.1f\n", df_now_ms());
+    if (df_trace()) fprintf(stderr, "bz2_mi355x: df_encode_buffer entered at %.1f\n", now_ms());
     // (an engine per device is kept between one-shot calls, with its workspace and the two buffers below:
     // bz_release_cached_resources frees it)
     EngineLease lease(device, 2, 1);
@@ -2460,9 +2348,9 @@ extern "C" int df_encode_buffer_dict(int kind, int device, const uint8_t *in, si
             };
             rc = df_encode_parts(g, kind, static_cast<const u8 *>(g->dec_in.p), in_len, dict, dict_len, static_cast<u8 *>(g->oneshot_out.p), cap,
                                  &n_out, DfSeg(), nullptr, &hooks);
-            const double t_parts = df_now_ms();
+            const double t_parts = now_ms();
             pool.wait_all();
-            if (df_trace()) fprintf(stderr, "bz2_mi355x: df_encode_buffer: parts over at %.1f, copies over at %.1f\n", t_parts, df_now_ms());
+            if (df_trace()) fprintf(stderr, "bz2_mi355x: df_encode_buffer: parts over at %.1f, copies over at %.1f\n", t_parts, now_ms());
             if (rc == BZ_OK && pool.failed()) rc = BZ_E_UNEXPECTED;
         }
         if (rc != BZ_OK) { // (the buffer is not shrunk to the stream: the pages behind it were never touched)
@@ -2472,7 +2360,7 @@ extern "C" int df_encode_buffer_dict(int kind, int device, const uint8_t *in, si
     } else {
         if (rc == BZ_OK && in_len && hipMemcpy(g->dec_in.p, in, in_len, hipMemcpyHostToDevice) != hipSuccess) rc = BZ_E_UNEXPECTED;
         if (rc == BZ_OK) rc = df_gpu_encode_device_dict(g, kind, g->dec_in.p, in_len, dict, dict_len, g->oneshot_out.p, cap, &n_out);
-        if (rc == BZ_OK) rc = df_download(&h, g->oneshot_out.p, n_out);
+        if (rc == BZ_OK) rc = one_shot_download(&h, g->oneshot_out.p, n_out);
     }
     lease.settle(rc);
     if (rc != BZ_OK) return rc;
@@ -2503,7 +2391,7 @@ struct df_enc {
 extern "C" int df_enc_create(df_enc **out, int kind, int device)
 {
     if (!out || kind < 0 || kind > 2) return BZ_E_PARAM;
-    if (df_device_in_range(device) != BZ_OK) return BZ_E_NOGPU;
+    if (device_in_range(device) != BZ_OK) return BZ_E_NOGPU;
     df_enc *e = new df_enc();
     e->kind = kind;
     e->device = device;

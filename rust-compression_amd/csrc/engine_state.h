@@ -22,6 +22,7 @@ int dec_decode_for_verify(struct bz_gpu_engine *g, const uint8_t *d_in, uint64_t
 void dec_spare_bufs_clear(); // dec_engine.hip: the byte buffers finished bz_dec contexts leave for the next one
 struct DfWorkspace;
 void df_workspace_free(DfWorkspace *w);
+uint64_t df_batch_image_bytes(); // deflate_engine.hip: BZ_DF_BATCH_MIB, the slot image of a sub-batch of either encoder
 struct LzhWorkspace;
 void lzh_workspace_free(LzhWorkspace *w);
 // bz_gpu_lzh_decode_batch_device with the outputs' places given by the caller (lzhuf_engine.hip; every entry has a known
@@ -31,16 +32,6 @@ int lzh_decode_batch_placed(struct bz_gpu_engine *g, int method, int prefill, co
                             int32_t *h_verdict);
 struct LhaWorkspace;
 void lha_workspace_free(LhaWorkspace *w);
-
-#define HIPCHK(x)                                                                                     \
-    do {                                                                                              \
-        hipError_t e_ = (x);                                                                          \
-        if (e_ != hipSuccess) {                                                                       \
-            fprintf(stderr, "bz2_mi355x: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__,   \
-                    __LINE__);                                                                        \
-            return BZ_E_UNEXPECTED;                                                                   \
-        }                                                                                             \
-    } while (0)
 
 struct bz_gpu_engine {
     int device = 0;
@@ -121,3 +112,4 @@ struct bz_gpu_engine {
     LhaWorkspace *lha = nullptr; // LHA archive reader's workspace, created by the first bz_gpu_lha_read_device call
 };
 
+#include "one_shot.h" // (behind the engine: its round trip uses dec_in and oneshot_out)

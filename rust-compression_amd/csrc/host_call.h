@@ -1,6 +1,6 @@
 // host_call.h -- what every host-to-host entry point does around its device work, in one place: the caller's HIP
 // device (CallerDevice), the engine a call borrows from the per-process cache (EngineLease: THE keep-or-destroy rule),
-// and the packing of a batch's entries into one image (BatchLayout).
+// the packing of a batch's entries into one image (BatchLayout), HIPCHK and the host clock (now_ms).
 // Host only; of HIP it uses hipGetDevice and hipSetDevice, and bz_gpu_engine stays an incomplete type.  Compiled as it
 // is by a host compiler against tests/host_stub/hip_shim.h (tests/test_host_call_host.py).
 #pragma once
@@ -11,9 +11,24 @@
 #include <hip/hip_runtime.h>
 #endif
 
+#include <chrono>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <vector>
+
+#define HIPCHK(x)                                                                                     \
+    do {                                                                                              \
+        hipError_t e_ = (x);                                                                          \
+        if (e_ != hipSuccess) {                                                                       \
+            fprintf(stderr, "bz2_mi355x: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__,   \
+                    __LINE__);                                                                        \
+            return BZ_E_UNEXPECTED;                                                                   \
+        }                                                                                             \
+    } while (0)
+
+// the host's steady clock in milliseconds: the spans the *_timings and the traces report
+inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // The engines that host-to-host calls and streaming contexts of BOTH codecs park between uses (engine_cache.hip).
 // prefer: 1 = an engine that holds a bzip2 decode workspace, 2 = one that holds a Deflate workspace.

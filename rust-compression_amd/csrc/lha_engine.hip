@@ -236,28 +236,10 @@ extern "C" int bz_lha_read_buffer(int device, const uint8_t *in, size_t in_len, 
     *fault = lha::index(in, in_len, members.data(), count, &count, &fault_pos);
     const LhaPlan plan(in_len, members.data(), count, sel, nsel);
     if (plan.status != BZ_OK) return plan.status;
-    if (nsel == 0) {
-        *out = (uint8_t *)malloc(1);
-        return *out ? BZ_OK : BZ_E_NOMEM;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return BZ_E_NOGPU;
-    EngineLease lease(device, 0, 1);
-    if (lease.status() != BZ_OK) return lease.status();
-    bz_gpu_engine *g = lease.engine();
-    int rc = g->dec_in.ensure(in_len + 64);
-    if (rc == BZ_OK) rc = g->oneshot_out.ensure((size_t)plan.need + 64);
-    if (rc == BZ_OK && in_len && hipMemcpy(g->dec_in.p, in, in_len, hipMemcpyHostToDevice) != hipSuccess) rc = BZ_E_UNEXPECTED;
-    if (rc == BZ_OK) rc = lha_read_core(g, g->dec_in.p, in_len, plan, prefill, g->oneshot_out.p, (size_t)plan.need, out_off, out_len, verdict);
-    if (rc == BZ_OK) {
-        const size_t total = (size_t)plan.need;
-        uint8_t *h = (uint8_t *)malloc(total ? total : 1);
-        if (!h) rc = BZ_E_NOMEM;
-        else if (total && hipMemcpy(h, g->oneshot_out.p, total, hipMemcpyDeviceToHost) != hipSuccess) {
-            free(h);
-            rc = BZ_E_UNEXPECTED;
-        } else *out = h;
-    }
-    lease.settle(rc == BZ_E_PARAM ? BZ_OK : rc); // (a call the decode path refused leaves a sound engine; so do the members' verdicts)
-    return rc;
+    if (nsel == 0) return one_shot_empty(out);
+    // (a call the decode path refused leaves a sound engine; so do the members' verdicts)
+    return one_shot(device, 0, OneShotIn(in, in_len), (size_t)plan.need, kSettleParamSound, out, [&](bz_gpu_engine *g, size_t *total) {
+        *total = (size_t)plan.need;
+        return lha_read_core(g, g->dec_in.p, in_len, plan, prefill, g->oneshot_out.p, (size_t)plan.need, out_off, out_len, verdict);
+    });
 }

@@ -2,12 +2,12 @@
 // (section 10; kernels: k_deflate.hip, the batch front end and "LZHUF encode"): the device calls, their figures, and the
 // host-to-host forms on an engine of the per-process cache (host_call.h).
 #include "engine_state.h"
+#include "batch_decode.h"
 #include "k_lzhuf.h"
 #include "k_deflate.h"
 #include "lzh_split.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
 #include <vector>
 
@@ -67,7 +67,6 @@ static double lzh_env_num(const char *name, double dflt)
     const double v = strtod(s, &end);
     return end == s || !(v >= 0) ? dflt : v;
 }
-static double lzh_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 extern "C" int bz_gpu_last_lzh_decode_split_stats(bz_gpu_engine *g, uint64_t out[8])
 {
@@ -120,7 +119,7 @@ static int lzh_split_sizes(bz_gpu_engine *g, LzhWorkspace *w, LzhMethod m, const
     using namespace lzhsplit;
     *fallback = true;
     int rc;
-    double t0 = lzh_now_ms();
+    double t0 = now_ms();
     // ---- every candidate, ascending: the search waves' counts, their sums, the list
     const u32 waves = lzh_split_search_waves(elen);
     if ((rc = w->s_cnt.ensure((size_t)waves * 8)) != BZ_OK) return rc;
@@ -150,7 +149,7 @@ static int lzh_split_sizes(bz_gpu_engine *g, LzhWorkspace *w, LzhMethod m, const
     }
     if (!cands.empty() && cands[0] == 0) cands.erase(cands.begin()); // (piece 0 starts there whatever the header says)
     e.st[1] = cands.size();
-    double t1 = lzh_now_ms();
+    double t1 = now_ms();
     e.ms[0] += t1 - t0;
     // ---- every piece at once: the entry's first bit and every candidate, each to the next candidate.  Piece 0 knows its place
     // and the entry's length; the others believe their distances.
@@ -168,7 +167,7 @@ static int lzh_split_sizes(bz_gpu_engine *g, LzhWorkspace *w, LzhMethod m, const
     }
     std::vector<LzhPieceRec> prs(pcs.size());
     if ((rc = lzh_split_pieces(g, w, m, ebase, elen, pcs.data(), (u32)pcs.size(), prs.data(), &e.launches)) != BZ_OK) return rc;
-    t0 = lzh_now_ms();
+    t0 = now_ms();
     e.ms[1] += t0 - t1;
     // ---- the chain: a candidate's piece counts if and only if the confirmed piece in front of it stopped exactly there.  A
     // piece is decoded again, alone, with its place and what is left of the known length, where the strict distance rule, the
@@ -206,7 +205,7 @@ static int lzh_split_sizes(bz_gpu_engine *g, LzhWorkspace *w, LzhMethod m, const
         if (chain_next(cands.data(), cands.size(), PieceEnd{pr.r.end_bit, false}, j) != Next::Confirmed) return BZ_OK; // (the rule is broken)
         cur = 1 + (size_t)j++;
     }
-    e.ms[2] += lzh_now_ms() - t0;
+    e.ms[2] += now_ms() - t0;
     if (e.chain.size() < 2 || (sum > 0xFFFFFFFFull && !(total.flags & 1u))) return BZ_OK;
     total.len = (u32)sum;
     e.rec = total;
@@ -226,36 +225,21 @@ static int lzh_split_write(bz_gpu_engine *g, LzhWorkspace *w, LzhMethod m, const
     u32 *map = w->s_map.as<u32>(), *cnt = w->s_jump.as<u32>();
     int rc = w->s_piece.ensure((size_t)np * sizeof(LzhPiece));
     if (rc != BZ_OK) return rc;
-    double t0 = lzh_now_ms();
+    const double t0 = now_ms();
     HIPCHK(hipMemcpyAsync(w->s_piece.p, e.chain.data(), (size_t)np * sizeof(LzhPiece), hipMemcpyHostToDevice, g->st));
     if (lzh_launch_decode_piece(g->st, true, ebase, elen, m.dbits, m.pbits, m.prefill, w->s_piece.as<LzhPiece>(), np, nullptr, eout, map) != 0)
         return BZ_E_UNEXPECTED;
     HIPCHK(hipStreamSynchronize(g->st));
     w->stats[7] += 1;
-    double t1 = lzh_now_ms();
-    w->split_ms[3] += t1 - t0;
-    u32 left = 0;
-    for (u32 round = 0;; ++round) {
-        u32 h[2] = {0, 0};
-        HIPCHK(hipMemsetAsync(cnt, 0, 8, g->st));
-        if (df_launch_split_jump(g->st, map, n, cnt) != 0) return BZ_E_UNEXPECTED;
-        HIPCHK(hipMemcpyAsync(h, cnt, 8, hipMemcpyDeviceToHost, g->st));
-        HIPCHK(hipStreamSynchronize(g->st));
-        w->stats[7] += 1;
-        w->split_stats[5] += 1;
-        if (round == 0) left = h[0];
-        if (h[1] == 0) break;
-    }
-    w->split_stats[6] += left;
-    t0 = lzh_now_ms();
-    w->split_ms[4] += t0 - t1;
-    if (left) {
-        if (df_launch_split_gather(g->st, eout, map, n) != 0) return BZ_E_UNEXPECTED;
-        HIPCHK(hipStreamSynchronize(g->st));
-        w->stats[7] += 1;
-    }
-    w->split_ms[5] += lzh_now_ms() - t0;
-    return BZ_OK;
+    w->split_ms[3] += now_ms() - t0;
+    SplitTail t;
+    rc = split_jump_gather(g->st, true, map, n, cnt, eout, t);
+    w->stats[7] += t.launches;
+    w->split_stats[5] += t.rounds;
+    w->split_stats[6] += t.left;
+    w->split_ms[4] += t.jump_ms;
+    w->split_ms[5] += t.gather_ms;
+    return rc;
 }
 
 // grow != nullptr: the output is the engine's own buffer, sized between the two launches (the host forms).
@@ -268,14 +252,8 @@ static int lzh_decode_batch_core(bz_gpu_engine *g, int method, int prefill, cons
     u32 dbits = 0, pbits = 0;
     if (!g || !lzh_method(method, dbits, pbits) || prefill < -1 || prefill > 255) return BZ_E_PARAM;
     if (count == 0) return BZ_OK;
-    if (!h_in_off || !h_in_len || !h_out_off || !h_out_len || !h_verdict || count > 0x7FFFFFFFu) return BZ_E_PARAM;
-    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u)) return BZ_E_PARAM;
-    u64 in_end = 0;
-    for (size_t i = 0; i < count; ++i) {
-        if ((h_in_off[i] & 3u) || h_in_off[i] < in_end || h_in_off[i] + h_in_len[i] < h_in_off[i] || h_in_len[i] > 0xFFFFFFFFull) return BZ_E_PARAM;
-        in_end = h_in_off[i] + h_in_len[i];
-    }
-    if (in_end && !d_in) return BZ_E_PARAM;
+    if (!h_in_off || !h_in_len || !h_out_off || !h_out_len || !h_verdict) return BZ_E_PARAM;
+    if (!batch_ranges_ok(d_in, d_out, h_in_off, h_in_len, count)) return BZ_E_PARAM;
     for (size_t i = 0; h_place && i < count; ++i)
         if (!h_orig_len || h_orig_len[i] == kNoLen || (h_place[i] & 15u)) return BZ_E_PARAM;
     HIPCHK(hipSetDevice(g->device));
@@ -302,26 +280,12 @@ static int lzh_decode_batch_core(bz_gpu_engine *g, int method, int prefill, cons
         if (fallback) ++fallbacks;
         else splits.push_back(std::move(e));
     }
-    // ONE source map for all of them, sized here, before any entry is committed to the split path.  If it cannot be had, every
-    // entry takes the one-wave path (and the failed allocation's error is not the next launch's).
-    if (!splits.empty() && (d_out || grow)) {
-        size_t map_bytes = 0;
-        for (const LzhSplitEntry &e : splits) map_bytes = std::max(map_bytes, (size_t)e.rec.len * 4 + 64);
-        if (w->s_map.ensure(map_bytes) != BZ_OK || w->s_jump.ensure(64) != BZ_OK) {
-            (void)hipGetLastError();
-            fallbacks += splits.size();
-            splits.clear();
-        }
-    }
-    w->split_stats[7] = fallbacks;
     std::vector<u64> len_small;
-    if (!splits.empty()) {
-        len_small.assign(h_in_len, h_in_len + count);
-        for (const LzhSplitEntry &e : splits) {
-            len_small[e.index] = 0;
-            for (int k = 0; k < 7; ++k) w->split_stats[k] += e.st[k];
-            for (int k = 0; k < 3; ++k) w->split_ms[k] += e.ms[k];
-        }
+    fallbacks += split_reserve(splits, d_out || grow, w->s_map, w->s_jump, h_in_len, count, len_small);
+    w->split_stats[7] = fallbacks;
+    for (const LzhSplitEntry &e : splits) {
+        for (int k = 0; k < 7; ++k) w->split_stats[k] += e.st[k];
+        for (int k = 0; k < 3; ++k) w->split_ms[k] += e.ms[k];
     }
     int rc = w->in.ensure(2 * count * sizeof(u64));
     if (rc == BZ_OK) rc = w->olen.ensure(count * sizeof(u64));
@@ -341,22 +305,10 @@ static int lzh_decode_batch_core(bz_gpu_engine *g, int method, int prefill, cons
     HIPCHK(hipMemcpyAsync(rec.data(), d_rec, count * sizeof(LzhRec), hipMemcpyDeviceToHost, g->st));
     HIPCHK(hipStreamSynchronize(g->st));
     for (const LzhSplitEntry &e : splits) rec[e.index] = e.rec;
-    // the outputs' places: input order, each at a multiple of 16
-    u64 cursor = 0, need = 0;
-    for (size_t i = 0; i < count; ++i) {
-        if (rec[i].flags & 1u) return BZ_E_PARAM; // an entry of 4 GiB or more of output
-        h_out_off[i] = h_place ? h_place[i] : cursor;
-        h_out_len[i] = rec[i].len;
-        h_verdict[i] = rec[i].verdict;
-        need = std::max(need, h_out_off[i] + rec[i].len);
-        cursor += ((u64)rec[i].len + 15u) & ~(u64)15;
-    }
-    u8 *out8 = static_cast<u8 *>(d_out);
-    if (grow) {
-        rc = grow->ensure((size_t)need + 64);
-        if (rc != BZ_OK) return rc;
-        out8 = grow->as<u8>();
-    } else if (d_out && need > cap) return BZ_E_CAPACITY;
+    u64 need = 0;
+    u8 *out8 = nullptr;
+    if ((rc = batch_place(rec.data(), count, h_place, h_out_off, h_out_len, h_verdict, &need)) != BZ_OK) return rc;
+    if ((rc = batch_output(need, d_out, cap, grow, &out8)) != BZ_OK) return rc;
     // ---- the bytes
     if (out8) {
         HIPCHK(hipMemcpyAsync(d_ooff, h_out_off, count * sizeof(u64), hipMemcpyHostToDevice, g->st));
@@ -410,35 +362,14 @@ extern "C" int bz_lzh_decode_batch(int method, int prefill, int device, const ui
     if (lay.status != BZ_OK) return lay.status;
     for (size_t i = 0; i < count; ++i)
         if (lens[i] > 0xFFFFFFFFull) return BZ_E_PARAM;
-    if (count == 0) {
-        *out = (uint8_t *)malloc(1);
-        return *out ? BZ_OK : BZ_E_NOMEM;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return BZ_E_NOGPU;
-    EngineLease lease(device, 0, 1);
-    if (lease.status() != BZ_OK) return lease.status();
-    bz_gpu_engine *g = lease.engine();
-    std::vector<uint8_t> packed((size_t)lay.total + 16);
-    lay.pack_into(packed.data());
-    int rc = g->dec_in.ensure((size_t)lay.total + 64);
-    if (rc == BZ_OK && lay.total && hipMemcpy(g->dec_in.p, packed.data(), (size_t)lay.total, hipMemcpyHostToDevice) != hipSuccess)
-        rc = BZ_E_UNEXPECTED;
-    if (rc == BZ_OK)
-        rc = lzh_decode_batch_core(g, method, prefill, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), orig_lens, count, nullptr, 0,
-                                   &g->oneshot_out, nullptr, out_off, out_len, verdict);
-    if (rc == BZ_OK) {
-        const size_t total = (size_t)(out_off[count - 1] + out_len[count - 1]);
-        uint8_t *h = (uint8_t *)malloc(total ? total : 1);
-        if (!h) rc = BZ_E_NOMEM;
-        else if (total && hipMemcpy(h, g->oneshot_out.p, total, hipMemcpyDeviceToHost) != hipSuccess) {
-            free(h);
-            rc = BZ_E_UNEXPECTED;
-        } else *out = h;
-    }
+    if (count == 0) return one_shot_empty(out);
     // a call the sizes launch refused (an entry of 4 GiB of output) leaves a sound engine; so do the entries' verdicts
-    lease.settle(rc == BZ_E_PARAM ? BZ_OK : rc);
-    return rc;
+    return one_shot(device, 0, lay, kOutGrown, kSettleParamSound, out, [&](bz_gpu_engine *g, size_t *total) {
+        const int rc = lzh_decode_batch_core(g, method, prefill, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), orig_lens, count, nullptr, 0,
+                                             &g->oneshot_out, nullptr, out_off, out_len, verdict);
+        if (rc == BZ_OK) *total = (size_t)(out_off[count - 1] + out_len[count - 1]);
+        return rc;
+    });
 }
 
 // The batch of one: BZ_OK with the bytes, or the entry's verdict with the bytes in front of it (as df_decode_buffer).
@@ -460,14 +391,6 @@ extern "C" int bz_lzh_decode_buffer(int method, int prefill, int device, const u
 }
 
 // ---- the encoder (section 10 of the header; DESIGN_lzhuf.md sections 7 to 9) ------------------------------------------
-static u64 lzh_batch_image_bytes()
-{
-    const char *s = getenv("BZ_DF_BATCH_MIB"); // the Deflate batch path's switch: slot image per sub-batch, read per call
-    double mib = s ? atof(s) : 64.0;
-    if (!(mib >= 1.0 / 16)) mib = 1.0 / 16;
-    if (mib > 1024) mib = 1024;
-    return (u64)(mib * 1048576.0);
-}
 constexpr u32 kLzhBatchSlots = 4096;     // inputs per sub-batch at most (a block's scratch is 134 KB)
 constexpr u64 kLzhMaxInput = 1ull << 30; // positions are 32-bit
 static u32 lzh_slot_tiles(u64 n) { return n ? (u32)((n + kPTile - 1) / kPTile) : 1u; }
@@ -624,7 +547,7 @@ extern "C" int bz_gpu_lzh_encode_batch_device(bz_gpu_engine *g, int method, cons
     const int wrc = lzh_enc_workspace(g, &w);
     if (wrc != BZ_OK) return wrc;
     for (u64 &s : w->enc_stats) s = 0;
-    const u64 image_max = lzh_batch_image_bytes();
+    const u64 image_max = df_batch_image_bytes(); // (the Deflate batch path's switch, BZ_DF_BATCH_MIB)
     u64 cursor = 0;
     for (size_t i = 0; i < count;) {
         size_t j = i;
@@ -721,36 +644,14 @@ extern "C" int bz_lzh_encode_batch(int method, int device, const uint8_t *const 
     if (lay.status != BZ_OK) return lay.status;
     for (size_t i = 0; i < count; ++i)
         if (lens[i] > kLzhMaxInput) return BZ_E_PARAM;
-    if (count == 0) {
-        *out = (uint8_t *)malloc(1);
-        return *out ? BZ_OK : BZ_E_NOMEM;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return BZ_E_NOGPU;
-    EngineLease lease(device, 0, 1);
-    if (lease.status() != BZ_OK) return lease.status();
-    bz_gpu_engine *g = lease.engine();
+    if (count == 0) return one_shot_empty(out);
     const size_t cap = bz_lzh_encode_batch_bound(lay.in_len.data(), count);
-    std::vector<uint8_t> packed((size_t)lay.total + 16);
-    lay.pack_into(packed.data());
-    int rc = g->dec_in.ensure((size_t)lay.total + 64);
-    if (rc == BZ_OK) rc = g->oneshot_out.ensure(cap + 64);
-    if (rc == BZ_OK && lay.total && hipMemcpy(g->dec_in.p, packed.data(), (size_t)lay.total, hipMemcpyHostToDevice) != hipSuccess)
-        rc = BZ_E_UNEXPECTED;
-    if (rc == BZ_OK)
-        rc = bz_gpu_lzh_encode_batch_device(g, method, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), count, g->oneshot_out.p, cap, out_off,
-                                            out_len);
-    if (rc == BZ_OK) {
-        const size_t total = (size_t)(out_off[count - 1] + out_len[count - 1]);
-        uint8_t *h = (uint8_t *)malloc(total ? total : 1);
-        if (!h) rc = BZ_E_NOMEM;
-        else if (total && hipMemcpy(h, g->oneshot_out.p, total, hipMemcpyDeviceToHost) != hipSuccess) {
-            free(h);
-            rc = BZ_E_UNEXPECTED;
-        } else *out = h;
-    }
-    lease.settle(rc);
-    return rc;
+    return one_shot(device, 0, lay, cap, kSettleStatus, out, [&](bz_gpu_engine *g, size_t *total) {
+        const int rc = bz_gpu_lzh_encode_batch_device(g, method, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), count, g->oneshot_out.p, cap,
+                                                      out_off, out_len);
+        if (rc == BZ_OK) *total = (size_t)(out_off[count - 1] + out_len[count - 1]);
+        return rc;
+    });
 }
 
 extern "C" int bz_lzh_encode_buffer(int method, int device, const uint8_t *in, size_t in_len, uint8_t **out, size_t *out_len)

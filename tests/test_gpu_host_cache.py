@@ -214,3 +214,73 @@ def test_streaming_decoder_two_lanes(pkg, oracle, monkeypatch):
     L.bz_dec_destroy(h)
     got, verdict = _stream_through(L, z[:5 << 20] + z[5 << 20:])
     assert verdict == 0 and got == data
+
+
+def test_single_call_forms_share_the_parked_engine(pkg, oracle):
+    """The eight host-to-host forms that are one upload, one device call and one download (csrc/one_shot.h:
+    df_encode_batch_dict, df_bgzf_encode_buffer, df_decode_batch_dict, df_decode_members_buffer, df_bgzf_read_buffer,
+    bz_lzh_decode_batch, bz_lzh_encode_batch, bz_lha_read_buffer) back to back on one device: they take turns on the parked
+    engine's input and output buffers.  Each form runs with about 64 KiB first, then about 1 KiB, then a result of no bytes,
+    so that a byte or a size left over from the larger call would show; each decoder gets one damaged entry between two
+    good ones, and the call behind it is as good as the one in front.  Expected bytes: the inputs themselves, zlib and gzip
+    of the standard library, tests/lzhref.py, tests/lhaforge.py and tests/bgzfref.py."""
+    import gzip
+    import zlib
+
+    import bgzfref
+    import lhaforge
+    import lzhref
+    import torch
+    torch.cuda.set_device(0)
+    big, small = _text(66_001, 31), _text(1_003, 32)
+    sizes = (big, small, b"")
+    zl = {d: zlib.compress(d, 6) for d in sizes}
+    gz = {d: gzip.compress(d[:len(d) // 2]) + b"\0" * 7 + gzip.compress(d[len(d) // 2:]) for d in sizes}  # two members, padding between
+    bg = {d: bgzfref.build(oracle, d)[0] for d in sizes}
+    lz = {d: lzhref.encode(d, 5) for d in sizes}
+    lz_cut = lz[small][:len(lz[small]) // 2]
+    lz_cut_want = lzhref.decode(lz_cut, 5, len(small))[:2]
+    assert lz_cut_want[1] != 0
+    lha = {d: lhaforge.wrap([(d, lz[d]), (small, lz[small])]) for d in sizes}
+    lha_bad = lhaforge.wrap([(small, lz[small]), (small, lz_cut), (big, lz[big])])
+    pkg.release_cached_resources()
+    for round_ in range(2):  # the second round starts on the engine the first one parked
+        # -- the encoders: every stream decodes to its input, the BGZF file and the LZHUF streams are the references'
+        for d in sizes:
+            got = pkg.deflate_compress_batch([d, small, b""], pkg.ZLIB)
+            assert [zlib.decompress(s) for s in got] == [d, small, b""]
+        assert pkg.deflate_compress_batch([], pkg.ZLIB) == []
+        for d in sizes:
+            assert pkg.bgzf_compress(d) == bg[d] and gzip.decompress(bg[d]) == d
+        for d in sizes:
+            assert pkg.lzhuf_compress_batch([d, small, b""], 5) == [lz[d], lz[small], b""]
+        assert pkg.lzhuf_compress_batch([], 5) == []
+        # -- the decoders, a damaged entry between two good ones in the first call, a clean call behind it
+        got = pkg.deflate_decompress_batch([zl[big], zl[small][:len(zl[small]) // 2], zl[small]], pkg.ZLIB)
+        assert got[0] == (big, 0) and got[2] == (small, 0) and got[1][1] != 0 and small.startswith(got[1][0])
+        for d in sizes:
+            assert pkg.deflate_decompress_batch([zl[d], zl[b""]], pkg.ZLIB) == [(d, 0), (b"", 0)]
+        assert pkg.deflate_decompress_batch([zl[b""]], pkg.ZLIB) == [(b"", 0)]  # (a device call that yields no byte)
+        assert pkg.deflate_decompress_batch([], pkg.ZLIB) == []
+        back, verdict = pkg.gzip_decompress_members(gz[big][:len(gz[big]) - 9])
+        assert verdict != 0 and big.startswith(back) and len(back) >= len(big) // 2
+        for d in sizes:
+            assert pkg.gzip_decompress_members(gz[d]) == (d, 0)
+        assert pkg.gzip_decompress_members(b"") == (b"", 0)
+        for d in (big, small):
+            assert pkg.bgzf_read(bg[d], 0, None) == d
+            assert pkg.bgzf_read(bg[d], len(d) // 3, 500) == d[len(d) // 3:len(d) // 3 + 500]
+            assert pkg.bgzf_read(bg[d], len(d), 10) == b""
+        assert pkg.bgzf_read(bg[b""], 0, None) == b""
+        got = pkg.lzhuf_decompress_batch([lz[big], lz_cut, lz[small]], 5, [len(big), len(small), len(small)])
+        assert got == [(big, 0), lz_cut_want, (small, 0)]
+        for d in sizes:
+            assert pkg.lzhuf_decompress_batch([lz[d], b""], 5, [len(d), 0]) == [(d, 0), (b"", 0)]
+        assert pkg.lzhuf_decompress_batch([], 5) == []
+        got = pkg.lha_extract(lha_bad)
+        assert got[0] == (small, 0) and got[2] == (big, 0) and got[1][1] != 0
+        for d in sizes:
+            assert pkg.lha_extract(lha[d]) == [(d, 0), (small, 0)]
+        assert pkg.lha_extract(lha[small], []) == []
+    pkg.release_cached_resources()
+    assert torch.cuda.current_device() == 0

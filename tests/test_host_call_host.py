@@ -1,8 +1,12 @@
 """csrc/host_call.h on the CPU: the engine lease of the host-to-host calls (one take or create, then exactly one put
 or destroy, decided by the call's infrastructure status; the caller's HIP device put back on every path, the failed
-creation included) and the batch layout (offsets, total and packing equal to the loops it replaced).
+creation included) and the batch layout (offsets, total and packing equal to the loops it replaced).  With it
+csrc/one_shot.h, the round trip of the calls that make one device call (the bytes a stand-in device call wrote come back,
+a failed dec_in / oneshot_out allocation or a failed download leaves *out null and destroys the engine, BZ_E_PARAM parks it
+under the LZHUF/LHA settle rule only), and csrc/batch_decode.h, the frame of the batch decoders (the range check as a
+table, the outputs' places and `need`, the split entries' reservation, the jump rounds against scripted launchers).
 
-The header is compiled AS IT IS by g++ with -DBZ_HOST_PIPELINE_TEST, which takes hipGetDevice / hipSetDevice from
+The headers are compiled AS THEY ARE by g++ with -DBZ_HOST_PIPELINE_TEST, which takes the HIP calls from
 tests/host_stub/hip_shim.h (four devices).  tests/host_stub/host_call_check.cpp supplies counting stand-ins for the
 engine cache and the engine, checks every rule and exits non-zero at the first one that fails; it runs plain, and again as
 a stand-alone program under AddressSanitizer + UBSan with leak detection (an engine the lease forgets or ends twice, a
