@@ -1299,6 +1299,67 @@ int bz_gpu_last_lha_read_stats(bz_gpu_engine *g, uint64_t out[8]);
 int bz_lha_read_buffer(int device, const uint8_t *in, size_t in_len, const size_t *sel, size_t nsel, int prefill, uint8_t **out,
                        uint64_t *out_off, uint64_t *out_len, int32_t *verdict, int32_t *fault);
 
+/* ========================================================================
+ * 12. LHA ARCHIVES, WRITING: every member in one device call -- section 10's
+ *     streams (or the members' own bytes) behind headers of level 0, 1 or 2,
+ *     every member's CRC-16 computed on the device.
+ *
+ * method: BZ_LHA_LH4 .. BZ_LHA_LH7, or BZ_LHA_STORED (every member -lh0-, no
+ * encode call at all).  level: the header level, 0, 1 or 2.  The data of
+ * member i is stream i of bz_gpu_lzh_encode_batch_device for that method, byte
+ * for byte, with one exception, THE STORED RULE (this project's own; LHA tools
+ * decide likewise but no text fixes the tie): a member whose stream is not
+ * shorter than its input (stream_len >= in_len, the empty input included; the
+ * tie goes to stored) is written as -lh0- with the input's own bytes.  crc16
+ * is the CRC-16/ARC of the input bytes.  An is_dir entry is a -lhd- member
+ * without data.  The archive ends with one 0 byte; count == 0 gives that byte
+ * alone.
+ *
+ * The header shape is fixed (csrc/lha_archive.h; DESIGN_lzhuf.md section 13):
+ * level 0 has the name in the base header and no place for a directory;
+ * level 1 has the name in the base header while 25 + N <= 255, else as a
+ * type-0x01 extended header with N = 0, and a non-empty dir as type 0x02;
+ * level 2 has a type-0x00 header CRC, the name as type 0x01 always, dir as
+ * type 0x02 when it is not empty, and one padding byte when the low byte of
+ * the header size would be 0.
+ * ======================================================================== */
+typedef struct bz_lha_entry {
+    const uint8_t *name; uint32_t name_len; /* raw bytes */
+    const uint8_t *dir;  uint32_t dir_len;  /* raw, components separated by 0xFF; may be empty */
+    uint32_t mtime;                         /* raw, as bz_lha_member.mtime */
+    uint8_t attr, os_id, is_dir, pad;       /* is_dir: a -lhd- member, no data */
+} bz_lha_entry;
+/* Bytes that always suffice for the archive: every header's size, every input's length and the end byte (the stored rule
+ * keeps a member's data at or below its input's length; header sizes do not depend on packed sizes).  The host alone.
+ * 0: a level outside 0 .. 2 or an entry that has no header at that level (see BZ_E_PARAM below). */
+size_t bz_lha_write_bound(int level, const bz_lha_entry *e, const uint64_t *in_len, size_t count);
+/* Inputs as in bz_gpu_lzh_encode_batch_device: d_in 16-byte aligned, h_in_off multiples of 16, the ranges ascending and
+ * disjoint; member i is h_entries[i] with the bytes d_in[h_in_off[i] .. + h_in_len[i]).  One call: the CRC-16 launch and its
+ * join over the inputs (parts of BZ_LHA_CRC_PART_KIB KiB as in section 11), section 10's encode call into a buffer of the
+ * engine (not for BZ_LHA_STORED, directories and empty inputs), ONE host step (the stored rule, the headers, the places,
+ * the capacity check), ONE launch that lays headers and data side by side at any byte phase of d_out.
+ * *out_len: the archive's length.  No byte of d_out outside [0, *out_len) is written.  BZ_E_CAPACITY: the finished archive
+ * does not fit cap; d_out is untouched (the archive is laid out last, its length known).  h_members (may be NULL; room for
+ * count records): the table bz_lha_index_buffer would build from the written bytes, field for field.
+ * BZ_E_PARAM, before any device is touched: a null engine, out_len or d_out; a null array with count > 0; a name or dir
+ * pointer null with a length; a misaligned d_in or offset, ranges out of order; a method outside the five, a level outside
+ * 0 .. 2; a non-empty dir at level 0 (no field a reader would give it back from); a name or directory whose header exceeds
+ * its size field (H > 255 at level 0, an extended header or T above 65 535); an input above 1 GiB with a compressing
+ * method, or one whose size field would reach 4 GiB - 1 with BZ_LHA_STORED; an is_dir entry with h_in_len != 0. */
+int bz_gpu_lha_write_device(bz_gpu_engine *g, int method, int level, const void *d_in, const uint64_t *h_in_off,
+                            const uint64_t *h_in_len, const bz_lha_entry *h_entries, size_t count, void *d_out, size_t cap,
+                            size_t *out_len, bz_lha_member *h_members);
+/* The last bz_gpu_lha_write_device call: [0] members [1] written compressed [2] stored by the rule [3] stored by request
+ * (BZ_LHA_STORED) [4] directories [5] input bytes [6] archive bytes [7] kernel launches of the writer itself (CRC, join,
+ * layout; section 10's figures are those of the call's encode call). */
+int bz_gpu_last_lha_write_stats(bz_gpu_engine *g, uint64_t out[8]);
+/* The host form (the shape of bz_lzh_encode_batch): the inputs packed at 16-byte-aligned offsets, one upload, one device call
+ * on an engine of the per-process cache, one download; *out is ONE malloc'ed buffer (bz_free) of *out_len bytes.  The
+ * parameters are checked before any device is touched; count == 0: BZ_OK, the end byte alone, no device.  Without a GPU:
+ * BZ_E_NOGPU. */
+int bz_lha_write_buffer(int method, int level, int device, const uint8_t *const *ins, const size_t *lens,
+                        const bz_lha_entry *entries, size_t count, uint8_t **out, size_t *out_len);
+
 #ifdef __cplusplus
 }
 #endif

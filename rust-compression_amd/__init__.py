@@ -30,7 +30,7 @@ import sys
 from . import _build
 
 __all__ = ["Action", "CompressionError", "BZip2Error", "BZip2Encoder", "BZip2Decoder", "encode", "decode",
-           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "deflate_decompress", "deflate_decompress_batch", "Deflater", "ZlibDecoder", "GZipDecoder", "gzip_decompress_members", "MultiGZipDecoder", "bgzf_compress", "bgzf_bound", "bgzf_block_count", "BgzfIndex", "bgzf_index", "bgzf_decompress", "bgzf_read", "LzhufMethod", "LzhufDecoder", "lzhuf_decompress", "lzhuf_decompress_batch", "LzhufEncoder", "lha_index", "lha_extract", "LhaArchive", "LhaIndex", "LhaMember", "lzhuf_compress", "lzhuf_compress_batch", "lzhuf_encode_batch_bound", "GpuEngine", "release_cached_resources", "last_call_phases",
+           "compress", "compress_batch", "encode_batch_bound", "decompress", "decompress_batch", "deflate_decompress", "deflate_decompress_batch", "Deflater", "ZlibDecoder", "GZipDecoder", "gzip_decompress_members", "MultiGZipDecoder", "bgzf_compress", "bgzf_bound", "bgzf_block_count", "BgzfIndex", "bgzf_index", "bgzf_decompress", "bgzf_read", "LzhufMethod", "LzhufDecoder", "lzhuf_decompress", "lzhuf_decompress_batch", "LzhufEncoder", "lha_index", "lha_extract", "LhaArchive", "LhaIndex", "LhaMember", "LhaEntry", "LHA_STORED", "lha_write_bound", "lha_compress", "lzhuf_compress", "lzhuf_compress_batch", "lzhuf_encode_batch_bound", "GpuEngine", "release_cached_resources", "last_call_phases",
            "build", "lib", "device_count", "encode_bound", "shard_window", "rccl_lib", "rccl_unique_id", "RcclComm"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -109,6 +109,7 @@ EXPORTS = [
     "bz_gpu_lzh_encode_batch_device", "bz_gpu_last_lzh_encode_stats", "bz_lzh_encode_batch_bound", "bz_lzh_encode_batch",
     "bz_lzh_encode_buffer", "bz_gpu_lzh_debug_codes", "bz_gpu_lzh_debug_tables",
     "bz_lha_index_buffer", "bz_gpu_lha_read_device", "bz_gpu_last_lha_read_stats", "bz_lha_read_buffer",
+    "bz_lha_write_bound", "bz_gpu_lha_write_device", "bz_gpu_last_lha_write_stats", "bz_lha_write_buffer",
 ]
 
 
@@ -306,6 +307,11 @@ def lib():
     L.bz_gpu_lha_read_device.argtypes = [vp, vp, sz, vp, sz, szp, sz, C.c_int, vp, sz, u64p, u64p, i32p]
     L.bz_gpu_last_lha_read_stats.argtypes = [vp, u64p]
     L.bz_lha_read_buffer.argtypes = [C.c_int, C.c_char_p, sz, szp, sz, C.c_int, C.POINTER(u8p), u64p, u64p, i32p, i32p]
+    L.bz_lha_write_bound.argtypes = [C.c_int, vp, u64p, sz]
+    L.bz_lha_write_bound.restype = sz
+    L.bz_gpu_lha_write_device.argtypes = [vp, C.c_int, C.c_int, vp, u64p, u64p, vp, sz, vp, sz, szp, vp]
+    L.bz_gpu_last_lha_write_stats.argtypes = [vp, u64p]
+    L.bz_lha_write_buffer.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p), szp, vp, sz, C.POINTER(u8p), szp]
     _LIB = L
     return L
 
@@ -1377,6 +1383,72 @@ class LhaArchive:
         return lha_extract(self._data, None, self._prefill, self._device)
 
 
+# ---- LHA archives, writing (section 12 of the header): every member in one device call
+class _LhaEntryRec(C.Structure):
+    """bz_lha_entry"""
+    _fields_ = [("name", C.c_char_p), ("name_len", C.c_uint32), ("dir", C.c_char_p), ("dir_len", C.c_uint32), ("mtime", C.c_uint32),
+                ("attr", C.c_uint8), ("os_id", C.c_uint8), ("is_dir", C.c_uint8), ("pad", C.c_uint8)]
+
+
+_LhaEntryBase = collections.namedtuple("LhaEntry", "name directory mtime attr os_id is_dir")
+
+
+class LhaEntry(_LhaEntryBase):
+    """What a member's header says beside its sizes and CRC: `name` and `directory` are raw bytes (a directory's components
+    are separated by 0xFF; str is encoded as UTF-8), `mtime` the header's raw time field (levels 0 and 1: MS-DOS time and
+    date; level 2: Unix time), `is_dir` a -lhd- member without data."""
+    __slots__ = ()
+
+    def __new__(cls, name, directory=b"", mtime=0, attr=0x20, os_id=0x55, is_dir=False):
+        raw = [x.encode() if isinstance(x, str) else bytes(x) for x in (name, directory)]
+        return super().__new__(cls, raw[0], raw[1], int(mtime), int(attr), int(os_id), bool(is_dir))
+
+
+LHA_STORED = 0   # the `method` of lha_compress / lha_write_device that writes every member as -lh0- (BZ_LHA_STORED)
+
+
+def _lha_method(method):
+    if int(method) not in (0, 4, 5, 6, 7):
+        raise ValueError("invalid LHA method")
+    return int(method)
+
+
+def _lha_entries(entries):
+    """-> (the bz_lha_entry array, what keeps its bytes alive)"""
+    ents = [e if isinstance(e, LhaEntry) else LhaEntry(e) for e in entries]
+    recs = (_LhaEntryRec * max(len(ents), 1))()
+    for r, e in zip(recs, ents):
+        r.name, r.name_len, r.dir, r.dir_len = e.name, len(e.name), e.directory, len(e.directory)
+        r.mtime, r.attr, r.os_id, r.is_dir = e.mtime, e.attr, e.os_id, int(e.is_dir)
+    return recs, ents
+
+
+def lha_write_bound(entries, lens, level=2):
+    """An output capacity that always suffices for GpuEngine.lha_write_device (bz_lha_write_bound; the host alone).  0: an
+    entry has no header at that level."""
+    recs, keep = _lha_entries(entries)
+    if len(lens) != len(keep):
+        raise ValueError("lha_write_bound: the arrays differ in length")
+    return lib().bz_lha_write_bound(int(level), recs, (C.c_uint64 * max(len(keep), 1))(*lens), len(keep))
+
+
+def lha_compress(members, method=LzhufMethod.Lh5, level=2, device=0):
+    """An LHA archive of `members`, a list of (name, data) or (LhaEntry, data), in one call (bz_lha_write_buffer) -> bytes.
+    method: a LzhufMethod, or LHA_STORED; a member whose stream would not be shorter than its bytes is stored."""
+    members = list(members)
+    recs, keep = _lha_entries([m[0] for m in members])
+    datas = [bytes(m[1]) for m in members]
+    k = len(datas)
+    ins = (C.c_char_p * max(k, 1))(*datas)
+    lens = (C.c_size_t * max(k, 1))(*[len(d) for d in datas])
+    out, n = C.POINTER(C.c_uint8)(), C.c_size_t(0)
+    _check(lib().bz_lha_write_buffer(_lha_method(method), int(level), device, ins, lens, recs, k, C.byref(out), C.byref(n)))
+    try:
+        return C.string_at(out, n.value)
+    finally:
+        lib().bz_free(out)
+
+
 class GpuEngine:
     """Device-resident engine (section 2 of the C ABI).  Pointers are plain ints
     (e.g. torch.Tensor.data_ptr())."""
@@ -1737,6 +1809,34 @@ class GpuEngine:
         """The last lha_read_device call, in the order of LHA_READ_STATS (bz_gpu_last_lha_read_stats)."""
         s = (C.c_uint64 * 8)()
         _check(lib().bz_gpu_last_lha_read_stats(self._h, s))
+        return [int(x) for x in s]
+
+    LHA_WRITE_STATS = ("members", "compressed", "stored_by_rule", "stored_by_request", "directories", "bytes_in", "archive_bytes", "launches")
+
+    def lha_write_device(self, d_in, in_off, in_len, entries, d_out, cap, method=LzhufMethod.Lh5, level=2):
+        """An LHA archive of the inputs d_in + in_off[i] (in_len[i] bytes of device memory each; d_in and the offsets 16-byte
+        aligned, ascending, disjoint) at d_out in one call (bz_gpu_lha_write_device; section 12 of the header).  entries: one
+        LhaEntry (or name) per input.  Returns (out_len, LhaIndex): the archive's length and the member table that lha_index
+        would build from its bytes (names and directories are the entries')."""
+        _settle()
+        recs, keep = _lha_entries(entries)
+        k = len(keep)
+        if len(in_off) != k or len(in_len) != k:
+            raise ValueError("lha_write_device: the per-member arrays differ in length")
+        a_off = (C.c_uint64 * max(k, 1))(*in_off)
+        a_len = (C.c_uint64 * max(k, 1))(*in_len)
+        table = (_LhaMemberRec * max(k, 1))()
+        n = C.c_size_t(0)
+        _check(lib().bz_gpu_lha_write_device(self._h, _lha_method(method), int(level), d_in, a_off, a_len, recs, k, d_out, cap, C.byref(n), table))
+        idx = LhaIndex(LhaMember(e.name, e.directory, bytes(r.method_id), r.level, r.packed_len, r.orig_len, r.crc16, r.mtime, r.os_id, r.data_off,
+                                 r.header_off, r.attr) for r, e in zip(table, keep))
+        idx._records = table
+        return n.value, idx
+
+    def lha_write_stats(self):
+        """The last lha_write_device call, in the order of LHA_WRITE_STATS (bz_gpu_last_lha_write_stats)."""
+        s = (C.c_uint64 * 8)()
+        _check(lib().bz_gpu_last_lha_write_stats(self._h, s))
         return [int(x) for x in s]
 
     LZH_DECODE_SPLIT_STATS = ("entries_split", "candidates", "chain_pieces", "false_pieces", "pieces_decoded_again", "jump_rounds",

@@ -6,6 +6,10 @@
 //   from 16-aligned outputs), moves its register to the end of the part and the workgroup XORs the 256 registers.
 // k_lha_crc16_join: one thread per member combines its parts and compares with the header's value.
 // k_lha_store: stored members from any byte phase of the archive to their 16-aligned places, exactly their bytes.
+// k_lha_pack (the writer, section 12): spans of headers, streams and stored inputs to ANY byte phase of the archive.  Two
+//   neighbours meet inside one 16-byte line, so a span's ragged head and tail go byte by byte and only its interior lines are
+//   whole 16-byte stores, built from aligned source words with funnel shifts; nothing outside a span is written, nothing
+//   behind a span's last source byte is read.
 #include <hip/hip_runtime.h>
 
 #include "k_lha.h"
@@ -127,6 +131,44 @@ __global__ __launch_bounds__(256) void k_lha_store(const u8 *__restrict__ in, u6
         }
 }
 
+__global__ __launch_bounds__(256) void k_lha_pack(const u8 *__restrict__ blob, const u8 *__restrict__ streams, const u8 *__restrict__ in,
+                                                  const LhaPackSpan *__restrict__ spans, u8 *out)
+{
+    const LhaPackSpan s = spans[blockIdx.x];
+    const u8 *src = (s.which == kPackBlob ? blob : s.which == kPackStream ? streams : in) + s.src;
+    u8 *dst = out + s.dst;
+    const u64 to_line = (0 - (u64)reinterpret_cast<uintptr_t>(dst)) & 15u;
+    const u64 head = to_line < s.len ? to_line : s.len, lines = (s.len - head) & ~(u64)15, tail = s.len - head - lines;
+    const u32 t = threadIdx.x;
+    if (blockIdx.y == 0) { // the bytes that share a line with a neighbour
+        if (t < head) dst[t] = src[t];
+        if (t < tail) dst[head + lines + t] = src[head + lines + t];
+    }
+    src += head;
+    dst += head; // (a multiple of 16)
+    const u32 ph = (u32)reinterpret_cast<uintptr_t>(src) & 15u, sh = (ph & 3u) * 8u; // (the same for every line of the span)
+    for (u64 lo = (u64)blockIdx.y * kStoreChunk; lo < lines; lo += (u64)gridDim.y * kStoreChunk)
+        for (u64 b = lo + 16ull * t; b < lo + kStoreChunk && b < lines; b += 16u * 256u) {
+            uint4 v;
+            if (ph == 0) v = *reinterpret_cast<const uint4 *>(src + b);
+            else if (sh == 0 || b + 20 - (ph & 3u) <= lines + tail) { // the aligned words end inside the span
+                const u32 *w = reinterpret_cast<const u32 *>(src + b - (ph & 3u));
+                const u32 w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = sh ? w[4] : 0u;
+                v.x = __funnelshift_r(w0, w1, sh);
+                v.y = __funnelshift_r(w1, w2, sh);
+                v.z = __funnelshift_r(w2, w3, sh);
+                v.w = __funnelshift_r(w3, w4, sh);
+            } else {
+                u32 q[4];
+#pragma unroll
+                for (u32 k = 0; k < 4; ++k)
+                    q[k] = (u32)src[b + 4 * k] | (u32)src[b + 4 * k + 1] << 8 | (u32)src[b + 4 * k + 2] << 16 | (u32)src[b + 4 * k + 3] << 24;
+                v = make_uint4(q[0], q[1], q[2], q[3]);
+            }
+            *reinterpret_cast<uint4 *>(dst + b) = v;
+        }
+}
+
 int lha_launch_crc16(hipStream_t st, const u8 *data, const LhaCrcJob *jobs, u32 njobs, u64 max_parts, u32 part_bytes, u32 *part_crc)
 {
     if (njobs == 0 || max_parts == 0) return 0;
@@ -147,6 +189,14 @@ int lha_launch_store(hipStream_t st, const u8 *in, u64 in_len, const dfgpu::GzSp
     if (count == 0) return 0;
     const u32 rows = max_len / kStoreChunk + 1u;
     hipLaunchKernelGGL(k_lha_store, dim3(count, rows < 64u ? rows : 64u), dim3(256), 0, st, in, in_len, spans, out);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int lha_launch_pack(hipStream_t st, const u8 *blob, const u8 *streams, const u8 *in, const LhaPackSpan *spans, u32 count, u64 max_len, u8 *out)
+{
+    if (count == 0) return 0;
+    const u64 rows = max_len / kStoreChunk + 1u;
+    hipLaunchKernelGGL(k_lha_pack, dim3(count, rows < 64u ? (u32)rows : 64u), dim3(256), 0, st, blob, streams, in, spans, out);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -1,6 +1,8 @@
 // lha_archive.h -- the member headers of an LHA archive (.lzh / .lha; include/bz2_mi355x.h section 11, DESIGN_lzhuf.md
 // section 12): the ONE place where the header rules stand.  bz_lha_index_buffer (lha_engine.hip) and the host test program
-// (tests/host_stub/lha_archive_check.cpp) share it; tests/lhaforge.py restates it in Python.
+// (tests/host_stub/lha_archive_check.cpp) share it; tests/lhaforge.py restates it in Python.  The writer of section 12 of the
+// header (header_size, write_header; DESIGN_lzhuf.md section 13) stands behind the parser: bz_gpu_lha_write_device and
+// tests/host_stub/lha_write_check.cpp share it, tests/lhawrite.py restates it.
 //
 // All integers are little-endian.  A header starts at p; the archive ends cleanly where p == len or in[p] == 0.
 //   levels 0 and 1: in[p] = H, the base header is [p, p + 2 + H); in[p + 1] = the sum of [p + 2, p + 2 + H) mod 256;
@@ -171,6 +173,117 @@ inline int index(const uint8_t *in, uint64_t len, bz_lha_member *out, size_t cap
     *count = n;
     *fault_pos = verdict == BZ_OK ? 0 : p;
     return verdict;
+}
+
+// ---- the writer (include/bz2_mi355x.h section 12, DESIGN_lzhuf.md section 13): ONE header shape per level ----------------
+//   level 0: H = 22 + N, the name in the base header; no directory.
+//   level 1: H = 25 + Nb; Nb = N while 25 + N <= 255, else Nb = 0 and the name is a type-0x01 extended header; a non-empty
+//     directory is a type-0x02 extended header behind it; skip size = packed size + the sizes of the extended headers.
+//   level 2: type 0x00 (header CRC, size 5), type 0x01 (the name, always), type 0x02 (a non-empty directory), and ONE 0 byte
+//     of padding when the low byte of T would be 0.
+// crc16() through a byte table: a level-2 header's CRC is on the write call's host step once per member
+inline uint16_t crc16_table(const uint8_t *in, uint64_t n)
+{
+    static const struct Tab {
+        uint16_t t[256];
+        Tab()
+        {
+            for (uint32_t i = 0; i < 256; ++i) {
+                uint32_t c = i;
+                for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ 0xA001u : c >> 1;
+                t[i] = (uint16_t)c;
+            }
+        }
+    } tab;
+    uint32_t c = 0;
+    for (uint64_t i = 0; i < n; ++i) c = tab.t[(c ^ in[i]) & 0xFFu] ^ (c >> 8);
+    return (uint16_t)c;
+}
+
+inline void wr16(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v, p[1] = (uint8_t)(v >> 8); }
+inline void wr32(uint8_t *p, uint32_t v) { wr16(p, v), wr16(p + 2, v >> 16); }
+
+// the five bytes of a BZ_LHA_* method the writer emits (STORED, DIR, LH4 .. LH7)
+inline void method_id_of(uint8_t method, uint8_t id[5])
+{
+    memcpy(id, "-lh0-", 5);
+    id[3] = method == BZ_LHA_DIR ? 'd' : (uint8_t)('0' + method);
+}
+
+inline bool name_in_base(int level, const bz_lha_entry &e) { return level == 0 || (level == 1 && 25u + e.name_len <= 255u); }
+
+// The bytes of a member's header with its extended headers and padding; 0: there is no such header (a level outside 0 .. 2,
+// a directory at level 0, H above 255, an extended header or T above 65 535).
+inline uint64_t header_size(int level, const bz_lha_entry &e)
+{
+    const uint64_t N = e.name_len, D = e.dir_len;
+    if (level == 0) return D == 0 && 22 + N <= 255 ? 2 + 22 + N : 0;
+    if (N + 3 > 65535 || D + 3 > 65535) return 0;
+    if (level == 1) return 2 + 25 + (name_in_base(1, e) ? N : N + 3) + (D ? D + 3 : 0);
+    if (level != 2) return 0;
+    uint64_t T = 26 + 5 + (N + 3) + (D ? D + 3 : 0);
+    if ((T & 255u) == 0) ++T;
+    return T <= 65535 ? T : 0;
+}
+
+// The header at out[0, header_size(level, e)): `packed` bytes of data follow it, they stand for `orig` bytes with CRC-16 `crc`.
+inline void write_header(int level, const bz_lha_entry &e, const uint8_t id[5], uint64_t packed, uint64_t orig, uint16_t crc, uint8_t *out)
+{
+    const uint32_t N = e.name_len, D = e.dir_len;
+    const uint64_t size = header_size(level, e);
+    uint8_t *q; // where the extended headers go; `first` holds the size of the first one
+    uint8_t *first;
+    memcpy(out + 2, id, 5);
+    wr32(out + 11, (uint32_t)orig);
+    wr32(out + 15, e.mtime);
+    out[19] = e.attr;
+    out[20] = (uint8_t)level;
+    if (level < 2) {
+        const uint32_t Nb = name_in_base(level, e) ? N : 0u, H = (level ? 25u : 22u) + Nb;
+        out[0] = (uint8_t)H;
+        wr32(out + 7, (uint32_t)(packed + (size - 2 - H))); // (level 0: no extended headers)
+        out[21] = (uint8_t)Nb;
+        if (Nb) memcpy(out + 22, e.name, Nb);
+        wr16(out + 22 + Nb, crc);
+        if (level == 0) {
+            uint32_t sum = 0;
+            for (uint32_t i = 2; i < 2 + H; ++i) sum += out[i];
+            out[1] = (uint8_t)sum;
+            return;
+        }
+        out[24 + Nb] = e.os_id;
+        first = out + H;
+        q = out + 2 + H;
+    } else {
+        wr16(out, (uint32_t)size);
+        wr32(out + 7, (uint32_t)packed);
+        wr16(out + 21, crc);
+        out[23] = e.os_id;
+        first = out + 24;
+        q = out + 26;
+    }
+    wr16(first, 0);
+    const auto ext = [&](uint8_t type, const uint8_t *data, uint32_t n) {
+        wr16(first, n + 3);
+        q[0] = type;
+        if (n) memcpy(q + 1, data, n);
+        first = q + 1 + n;
+        wr16(first, 0);
+        q += n + 3;
+    };
+    static const uint8_t zero2[2] = {0, 0};
+    if (level == 2) ext(0x00, zero2, 2);
+    if (level == 2 || !name_in_base(level, e)) ext(0x01, e.name, N);
+    if (D) ext(0x02, e.dir, D);
+    if (level == 1) {
+        const uint32_t H = out[0];
+        uint32_t sum = 0;
+        for (uint32_t i = 2; i < 2 + H; ++i) sum += out[i];
+        out[1] = (uint8_t)sum;
+    } else {
+        if (q < out + size) *q = 0;                      // (the padding byte)
+        wr16(out + 27, crc16_table(out, size));          // (its field still reads as zero)
+    }
 }
 
 } // namespace lha

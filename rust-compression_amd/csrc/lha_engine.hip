@@ -1,4 +1,4 @@
-// lha_engine.hip -- the driver of the LHA archive reader (include/bz2_mi355x.h section 11; header rules: lha_archive.h;
+// lha_engine.hip -- the drivers of the LHA archive reader and writer (include/bz2_mi355x.h sections 11, 12; header rules: lha_archive.h;
 // kernels: k_lha.hip, k_gz_member_gather of k_gz_members.hip and, through lzh_decode_batch_placed, k_lzhuf.hip): the member
 // table on the host, the device call, its figures, and the host-to-host form on an engine of the per-process cache.
 #include "engine_state.h"
@@ -15,6 +15,8 @@ using dfgpu::GzSpan;
 struct LhaWorkspace {
     DevBuf image, spans, jobs, parts, res; // a method's packed spans, span records, CRC jobs, their partials, their results
     u64 stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    DevBuf w_streams, w_blob; // the writer: the encode call's streams, the headers
+    u64 w_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 void lha_workspace_free(LhaWorkspace *w) { delete w; }
@@ -242,4 +244,217 @@ extern "C" int bz_lha_read_buffer(int device, const uint8_t *in, size_t in_len, 
         *total = (size_t)plan.need;
         return lha_read_core(g, g->dec_in.p, in_len, plan, prefill, g->oneshot_out.p, (size_t)plan.need, out_off, out_len, verdict);
     });
+}
+
+// ---- the writer (section 12 of the header; DESIGN_lzhuf.md section 13) ------------------------------------------------
+constexpr u64 kLhaMaxCompressed = 1ull << 30; // the encoder's limit
+
+// What of (method, level, entries, lengths) is checked before any device is touched.  hsize: every member's header size.
+static int lha_write_check(int method, int level, const bz_lha_entry *e, const uint64_t *len, size_t count, std::vector<u64> *hsize)
+{
+    const bool stored = method == BZ_LHA_STORED;
+    if (!stored && (method < BZ_LHA_LH4 || method > BZ_LHA_LH7)) return BZ_E_PARAM;
+    if (level < 0 || level > 2) return BZ_E_PARAM;
+    if (count > 0x3FFFFFFFu || (count && (!e || !len))) return BZ_E_PARAM; // (two spans a member and the end byte: one launch)
+    if (hsize) hsize->resize(count);
+    for (size_t i = 0; i < count; ++i) {
+        const bz_lha_entry &q = e[i];
+        if ((q.name_len && !q.name) || (q.dir_len && !q.dir)) return BZ_E_PARAM;
+        const u64 hs = lha::header_size(level, q);
+        if (!hs || (q.is_dir && len[i]) || (!stored && len[i] > kLhaMaxCompressed)) return BZ_E_PARAM;
+        const u64 ext = level == 1 ? hs - 27 - (lha::name_in_base(1, q) ? q.name_len : 0u) : 0; // (in the level-1 skip size)
+        if (len[i] + ext >= 0xFFFFFFFFull) return BZ_E_PARAM;
+        if (hsize) (*hsize)[i] = hs;
+    }
+    return BZ_OK;
+}
+
+extern "C" size_t bz_lha_write_bound(int level, const bz_lha_entry *e, const uint64_t *in_len, size_t count)
+{
+    if (level < 0 || level > 2 || (count && (!e || !in_len))) return 0;
+    size_t s = 1;
+    for (size_t i = 0; i < count; ++i) {
+        const u64 hs = lha::header_size(level, e[i]);
+        if (!hs) return 0;
+        s += (size_t)(hs + in_len[i]);
+    }
+    return s;
+}
+
+extern "C" int bz_gpu_last_lha_write_stats(bz_gpu_engine *g, uint64_t out[8])
+{
+    if (!g || !out) return BZ_E_PARAM;
+    for (int i = 0; i < 8; ++i) out[i] = g->lha ? g->lha->w_stats[i] : 0;
+    return BZ_OK;
+}
+
+// One call, its parameters checked: CRC launches, the encode call, the host step, the layout launch.
+static int lha_write_core(bz_gpu_engine *g, int method, int level, const void *d_in, const uint64_t *h_in_off, const uint64_t *h_in_len,
+                          const bz_lha_entry *h_entries, const std::vector<u64> &hsize, size_t count, void *d_out, size_t cap, size_t *out_len,
+                          bz_lha_member *h_members)
+{
+    const bool stored = method == BZ_LHA_STORED;
+    const u32 part_bytes = lha_crc_part_bytes();
+    std::vector<LhaCrcJob> jobs(count);
+    std::vector<LhaCrcRes> res(count);
+    u64 nparts = 0, max_parts = 0;
+    for (size_t i = 0; i < count; ++i) {
+        const u64 parts = lha_crc_parts(h_in_len[i], part_bytes);
+        jobs[i] = LhaCrcJob{h_in_off[i], h_in_len[i], (u32)nparts, 0u};
+        nparts += parts;
+        max_parts = std::max(max_parts, parts);
+    }
+    if (nparts > 0xFFFFFFFFull) return BZ_E_PARAM;
+    HIPCHK(hipSetDevice(g->device));
+    if (!g->lha) g->lha = new LhaWorkspace();
+    LhaWorkspace *w = g->lha;
+    for (u64 &s : w->w_stats) s = 0;
+    const u8 *in8 = static_cast<const u8 *>(d_in);
+    int rc;
+    // ---- the CRC-16 of every input: launched here, downloaded behind the encode call
+    if (count) {
+        const u32 nj = (u32)count;
+        if ((rc = w->jobs.ensure(nj * sizeof(LhaCrcJob))) != BZ_OK) return rc;
+        if ((rc = w->parts.ensure(((size_t)nparts + 1) * 4)) != BZ_OK) return rc;
+        if ((rc = w->res.ensure(nj * sizeof(LhaCrcRes))) != BZ_OK) return rc;
+        HIPCHK(hipMemcpyAsync(w->jobs.p, jobs.data(), nj * sizeof(LhaCrcJob), hipMemcpyHostToDevice, g->st));
+        if (lha_launch_crc16(g->st, in8, w->jobs.as<LhaCrcJob>(), nj, max_parts, part_bytes, w->parts.as<u32>()) != 0) return BZ_E_UNEXPECTED;
+        if (lha_launch_crc16_join(g->st, w->jobs.as<LhaCrcJob>(), nj, part_bytes, w->parts.as<u32>(), w->res.as<LhaCrcRes>()) != 0)
+            return BZ_E_UNEXPECTED;
+        w->w_stats[7] += max_parts ? 2 : 1;
+    }
+    // ---- the streams of every input that has bytes, in the engine's buffer
+    std::vector<u64> e_off, e_len, s_off, s_len;
+    for (size_t i = 0; !stored && i < count; ++i)
+        if (h_in_len[i]) {
+            e_off.push_back(h_in_off[i]);
+            e_len.push_back(h_in_len[i]);
+        }
+    if (!e_len.empty()) {
+        const size_t bound = bz_lzh_encode_batch_bound(e_len.data(), e_len.size());
+        s_off.resize(e_len.size());
+        s_len.resize(e_len.size());
+        if ((rc = w->w_streams.ensure(bound + 64)) != BZ_OK) return rc;
+        rc = bz_gpu_lzh_encode_batch_device(g, method, d_in, e_off.data(), e_len.data(), e_len.size(), w->w_streams.p, bound, s_off.data(),
+                                            s_len.data());
+        if (rc != BZ_OK) return rc;
+    }
+    // the one look at the device that is the writer's own: the CRCs (the encode call has waited for its work, and for theirs)
+    if (count) HIPCHK(hipMemcpyAsync(res.data(), w->res.p, count * sizeof(LhaCrcRes), hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipStreamSynchronize(g->st));
+    // ---- the host step: the stored rule, the headers (each at a blob offset congruent mod 16 to its place), the places
+    const uintptr_t base = reinterpret_cast<uintptr_t>(d_out);
+    std::vector<u8> blob;
+    std::vector<LhaPackSpan> spans;
+    std::vector<u64> h_at(count), place(count);
+    spans.reserve(2 * count + 1);
+    u64 cursor = 0, max_len = 1;
+    const auto blob_room = [&](u64 n) {
+        const size_t at = blob.size() + (size_t)((base + cursor - blob.size()) & 15u);
+        blob.resize(at + (size_t)n);
+        spans.push_back(LhaPackSpan{at, cursor, n, kPackBlob, 0u});
+        max_len = std::max(max_len, n);
+        cursor += n;
+        return at;
+    };
+    for (size_t i = 0, k = 0; i < count; ++i) {
+        const bz_lha_entry &q = h_entries[i];
+        u64 packed = h_in_len[i], src = h_in_off[i];
+        bool compressed = false;
+        if (!stored && h_in_len[i]) {
+            if (s_len[k] < h_in_len[i]) { // (the tie goes to stored)
+                compressed = true;
+                packed = s_len[k];
+                src = s_off[k];
+            }
+            ++k;
+        }
+        uint8_t id[5];
+        lha::method_id_of(q.is_dir ? BZ_LHA_DIR : compressed ? (uint8_t)method : BZ_LHA_STORED, id);
+        place[i] = cursor;
+        h_at[i] = blob_room(hsize[i]);
+        lha::write_header(level, q, id, packed, h_in_len[i], (uint16_t)res[i].crc, blob.data() + h_at[i]);
+        if (packed) {
+            spans.push_back(LhaPackSpan{src, cursor, packed, compressed ? kPackStream : kPackInput, 0u});
+            max_len = std::max(max_len, packed);
+            cursor += packed;
+        }
+        w->w_stats[q.is_dir ? 4 : compressed ? 1 : stored ? 3 : 2] += 1;
+        w->w_stats[5] += h_in_len[i];
+    }
+    blob_room(1); // (the end byte: blob.resize wrote the 0)
+    w->w_stats[0] = count;
+    w->w_stats[6] = cursor;
+    if (cursor > cap) return BZ_E_CAPACITY;
+    // ---- the archive, in one launch
+    if ((rc = w->w_blob.ensure(blob.size() + 64)) != BZ_OK) return rc;
+    if ((rc = w->spans.ensure(spans.size() * sizeof(LhaPackSpan))) != BZ_OK) return rc;
+    HIPCHK(hipMemcpyAsync(w->w_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, g->st));
+    HIPCHK(hipMemcpyAsync(w->spans.p, spans.data(), spans.size() * sizeof(LhaPackSpan), hipMemcpyHostToDevice, g->st));
+    if (lha_launch_pack(g->st, w->w_blob.as<u8>(), w->w_streams.as<u8>(), in8, w->spans.as<LhaPackSpan>(), (u32)spans.size(), max_len,
+                        static_cast<u8 *>(d_out)) != 0)
+        return BZ_E_UNEXPECTED;
+    HIPCHK(hipStreamSynchronize(g->st));
+    HIPCHK(hipGetLastError());
+    w->w_stats[7] += 1;
+    for (size_t i = 0; h_members && i < count; ++i) { // the parser's own reading of each header, moved to its place
+        bz_lha_member &m = h_members[i];
+        uint64_t next = 0;
+        if (lha::parse_header(blob.data() + h_at[i], hsize[i], 0, m, &next) != BZ_OK) return BZ_E_UNEXPECTED;
+        m.header_off += place[i];
+        m.data_off += place[i];
+        m.name_off += place[i];
+        if (m.dir_len) m.dir_off += place[i];
+    }
+    *out_len = (size_t)cursor;
+    return BZ_OK;
+}
+
+extern "C" int bz_gpu_lha_write_device(bz_gpu_engine *g, int method, int level, const void *d_in, const uint64_t *h_in_off,
+                                       const uint64_t *h_in_len, const bz_lha_entry *h_entries, size_t count, void *d_out, size_t cap,
+                                       size_t *out_len, bz_lha_member *h_members)
+{
+    if (!g || !out_len || !d_out || (count && !h_in_off)) return BZ_E_PARAM;
+    std::vector<u64> hsize;
+    const int rc = lha_write_check(method, level, h_entries, h_in_len, count, &hsize);
+    if (rc != BZ_OK) return rc;
+    if ((uintptr_t)d_in & 15u) return BZ_E_PARAM;
+    u64 in_end = 0;
+    for (size_t i = 0; i < count; ++i) {
+        if ((h_in_off[i] & 15u) || h_in_off[i] < in_end || h_in_off[i] + h_in_len[i] < h_in_off[i]) return BZ_E_PARAM;
+        in_end = h_in_off[i] + h_in_len[i];
+    }
+    if (in_end && !d_in) return BZ_E_PARAM;
+    return lha_write_core(g, method, level, d_in, h_in_off, h_in_len, h_entries, hsize, count, d_out, cap, out_len, h_members);
+}
+
+extern "C" int bz_lha_write_buffer(int method, int level, int device, const uint8_t *const *ins, const size_t *lens, const bz_lha_entry *entries,
+                                   size_t count, uint8_t **out, size_t *out_len)
+{
+    if (!out || !out_len) return BZ_E_PARAM;
+    *out = nullptr;
+    *out_len = 0;
+    if (count && (!ins || !lens)) return BZ_E_PARAM;
+    const std::vector<u64> len64(lens, lens + count);
+    std::vector<u64> hsize;
+    int rc = lha_write_check(method, level, entries, len64.data(), count, &hsize);
+    if (rc != BZ_OK) return rc;
+    const BatchLayout lay(ins, lens, count, 16);
+    if (lay.status != BZ_OK) return lay.status;
+    if (count == 0) { // the end byte alone
+        if ((rc = one_shot_empty(out)) != BZ_OK) return rc;
+        (*out)[0] = 0;
+        *out_len = 1;
+        return BZ_OK;
+    }
+    const size_t bound = bz_lha_write_bound(level, entries, len64.data(), count);
+    size_t n = 0;
+    rc = one_shot(device, 0, lay, bound, kSettleStatus, out, [&](bz_gpu_engine *g, size_t *total) {
+        const int wrc = lha_write_core(g, method, level, g->dec_in.p, lay.in_off.data(), lay.in_len.data(), entries, hsize, count,
+                                       g->oneshot_out.p, bound, &n, nullptr);
+        *total = n;
+        return wrc;
+    });
+    if (rc == BZ_OK) *out_len = n;
+    return rc;
 }

@@ -708,6 +708,37 @@ inline Result<std::vector<LzhufDecoder::Entry>> lha_read(const uint8_t *in, size
     return R::Ok(std::move(entries));
 }
 
+// An LHA archive of many members in one call (include/bz2_mi355x.h section 12, bz_lha_write_buffer): method BZ_LHA_LH4 ..
+// BZ_LHA_LH7 or BZ_LHA_STORED, header level 0 .. 2; a member whose stream would not be shorter than its bytes is stored.
+struct LhaFile {
+    std::vector<uint8_t> name, dir; // raw bytes; a directory's components are separated by 0xFF
+    std::vector<uint8_t> bytes;
+    uint32_t mtime = 0;
+    uint8_t attr = 0x20, os_id = 0x55;
+    bool is_dir = false;
+};
+inline Result<std::vector<uint8_t>> lha_write(const std::vector<LhaFile> &files, int method = BZ_LHA_LH5, int level = 2, int device = 0)
+{
+    using R = Result<std::vector<uint8_t>>;
+    std::vector<bz_lha_entry> entries(files.size());
+    std::vector<const uint8_t *> ins(files.size());
+    std::vector<size_t> lens(files.size());
+    for (size_t i = 0; i < files.size(); ++i) {
+        const LhaFile &f = files[i];
+        entries[i] = bz_lha_entry{f.name.data(), (uint32_t)f.name.size(), f.dir.data(), (uint32_t)f.dir.size(), f.mtime, f.attr, f.os_id,
+                                  (uint8_t)f.is_dir, 0};
+        ins[i] = f.bytes.data();
+        lens[i] = f.bytes.size();
+    }
+    uint8_t *out = nullptr;
+    size_t len = 0;
+    const int rc = bz_lha_write_buffer(method, level, device, ins.data(), lens.data(), entries.data(), files.size(), &out, &len);
+    if (rc != BZ_OK) return R::Err(from_status(rc));
+    std::vector<uint8_t> arc(out, out + len);
+    bz_free(out);
+    return R::Ok(std::move(arc));
+}
+
 // One input as a BGZF file (include/bz2_mi355x.h section 7, df_bgzf_encode_buffer): gzip members of at most block_bytes
 // (0: 65 280) input bytes side by side, then the 28-byte EOF marker unless eof is false.  The reference has no such writer;
 // every member is a stream that zlib, gzip(1) and htslib read.  block_off, when not null, receives the file offset of every

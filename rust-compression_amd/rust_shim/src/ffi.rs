@@ -38,6 +38,21 @@ pub struct LhaMember {
     pub pad: u8,
 }
 
+/// `bz_lha_entry`: what `bz_lha_write_buffer` writes into a member's header beside its sizes and CRC (40 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct LhaEntry {
+    pub name: *const u8,
+    pub name_len: u32,
+    pub dir: *const u8, // components separated by 0xFF; may be empty
+    pub dir_len: u32,
+    pub mtime: u32,
+    pub attr: u8,
+    pub os_id: u8,
+    pub is_dir: u8,
+    pub pad: u8,
+}
+
 extern "C" {
     pub fn bz_device_count() -> i32;
     pub fn bz_strerror(code: i32) -> *const core::ffi::c_char;
@@ -112,6 +127,11 @@ extern "C" {
     pub fn bz_gpu_lha_read_device(g: *mut c_void, d_in: *const c_void, in_len: usize, h_members: *const LhaMember, nmembers: usize, h_sel: *const usize, nsel: usize, prefill: i32, d_out: *mut c_void, cap: usize, h_out_off: *mut u64, h_out_len: *mut u64, h_verdict: *mut i32) -> i32;
     pub fn bz_gpu_last_lha_read_stats(g: *mut c_void, out: *mut u64) -> i32;
     pub fn bz_lha_read_buffer(device: i32, input: *const u8, in_len: usize, sel: *const usize, nsel: usize, prefill: i32, out: *mut *mut u8, out_off: *mut u64, out_len: *mut u64, verdict: *mut i32, fault: *mut i32) -> i32;
+    // section 12: LHA archives, writing (entries: *const LhaEntry, the C struct bz_lha_entry)
+    pub fn bz_lha_write_bound(level: i32, e: *const LhaEntry, in_len: *const u64, count: usize) -> usize;
+    pub fn bz_gpu_lha_write_device(g: *mut c_void, method: i32, level: i32, d_in: *const c_void, h_in_off: *const u64, h_in_len: *const u64, h_entries: *const LhaEntry, count: usize, d_out: *mut c_void, cap: usize, out_len: *mut usize, h_members: *mut LhaMember) -> i32;
+    pub fn bz_gpu_last_lha_write_stats(g: *mut c_void, out: *mut u64) -> i32;
+    pub fn bz_lha_write_buffer(method: i32, level: i32, device: i32, ins: *const *const u8, lens: *const usize, entries: *const LhaEntry, count: usize, out: *mut *mut u8, out_len: *mut usize) -> i32;
 
     // section 6: every member of a gzip file (MultiGZipDecoder)
     pub fn df_gpu_decode_members_device(g: *mut c_void, d_in: *const c_void, in_len: usize, d_out: *mut c_void, cap: usize, out_len: *mut u64, verdict: *mut i32) -> i32;

@@ -330,6 +330,42 @@ pub fn lha_read(archive: &[u8], sel: Option<&[usize]>) -> Result<Vec<Result<Vec<
     Ok(entries)
 }
 
+/// One member for `lha_write`: `name` and `dir` are raw bytes (a directory's components are separated by 0xFF), `mtime` the
+/// header's raw time field, `is_dir` a `-lhd-` member without data.
+#[cfg(feature = "lzhuf")]
+#[derive(Clone, Debug, Default)]
+pub struct LhaFile<'a> {
+    pub name: &'a [u8],
+    pub dir: &'a [u8],
+    pub bytes: &'a [u8],
+    pub mtime: u32,
+    pub attr: u8,
+    pub os_id: u8,
+    pub is_dir: bool,
+}
+
+/// An LHA archive of many members in one call (`bz_lha_write_buffer`, device 0): `method` is 4 .. 7 (`-lh4-` .. `-lh7-`) or
+/// 0 (stored), `level` the header level 0 .. 2.  A member whose stream would not be shorter than its bytes is stored.
+#[cfg(feature = "lzhuf")]
+pub fn lha_write(files: &[LhaFile], method: i32, level: i32) -> Result<Vec<u8>, CompressionError> {
+    let entries: Vec<ffi::LhaEntry> = files
+        .iter()
+        .map(|f| ffi::LhaEntry { name: f.name.as_ptr(), name_len: f.name.len() as u32, dir: f.dir.as_ptr(), dir_len: f.dir.len() as u32, mtime: f.mtime, attr: f.attr, os_id: f.os_id, is_dir: f.is_dir as u8, pad: 0 })
+        .collect();
+    let ins: Vec<*const u8> = files.iter().map(|f| f.bytes.as_ptr()).collect();
+    let lens: Vec<usize> = files.iter().map(|f| f.bytes.len()).collect();
+    let mut out: *mut u8 = core::ptr::null_mut();
+    let mut len = 0usize;
+    let rc = unsafe { ffi::bz_lha_write_buffer(method, level, 0, ins.as_ptr(), lens.as_ptr(), entries.as_ptr(), files.len(), &mut out, &mut len) };
+    if rc != ffi::BZ_OK {
+        note_status(rc);
+        return Err(CompressionError::from_status(rc));
+    }
+    let archive = unsafe { core::slice::from_raw_parts(out, len) }.to_vec();
+    unsafe { ffi::bz_free(out as *mut core::ffi::c_void) };
+    Ok(archive)
+}
+
 pub(crate) fn note_status(rc: i32) {
     if rc != 0 {
         LAST_STATUS.store(rc, Ordering::Relaxed);
